@@ -6,10 +6,17 @@ metric  : images/sec, forward + backward + optimiser step, 1024x1024 -> 80x80 fo
 step    : one full optimisation step (train_deform_semantic.py:74-129) on a synthetic batch that is
           already resident in HBM.
 modes   : the conv engine has three arithmetic modes, all fp32 tensors + fp32 accumulation.
-          All three are timed in ONE run.  `value` is the `--headline` mode, by default `bf16x3`: operands
-          split into three bf16 terms = 24 significand bits, the reference's fp32 operand width.  `f16x2`
-          (22-23 bit operands) and `f32` (fp32 MFMA) are reported next to it under `modes`.
-Usage   : python bench.py --gpus N --steps K --warmup W
+          `value` is the `--headline` mode, by default `bf16x3`: operands split into three bf16 terms = 24
+          significand bits, the reference's fp32 operand width.  With `--full`, `f16x2` (22-23 bit operands)
+          and `f32` (fp32 MFMA) are timed in the same run and reported next to it under `modes`.
+Usage   : python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+          A plain run sets up, warms up, times the K steps of the headline mode and prints the line.
+          The step runs in the library's default mode (bwd-weight split-K sums by fp32 atomics), as every
+          earlier figure did; --deterministic opts into the bit-reproducible mode (config.deterministic).
+          --full adds the other modes, the serialised per-kernel roofline pass, the forward-only and
+          host-fed rates, the CPU baseline and bench_detail.json.
+          --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32); it
+          implies --deterministic, so the same arguments write the same bits.
           N>1: under torch.distributed.run (one rank per GPU, RCCL); started WITHOUT a launcher it
           spawns that launcher itself before touching the GPU.
 Output  : ONE JSON line on rank 0 (see README/DESIGN.md "Measurement").
@@ -36,6 +43,7 @@ MODES = {
     "f16x2": ("PrecF16", 3, 22, "f32 storage + f32 accumulate; each operand scaled and split into 2 fp16 terms (22-23 significand bits), 3 x v_mfma_f32_32x32x16_f16 per product"),
     "f32": (None, 1, 24, "f32 storage, v_mfma_f32_32x32x2_f32 products, f32 accumulate"),
 }
+FULL_MODES = "bf16x3,f16x2,f32"     # what --full times when --modes is not given
 
 
 def mode_peak(mode):
@@ -200,9 +208,30 @@ def parse_args():
     ap.add_argument("--backend", default=None, help="torch.distributed backend (default nccl = RCCL; gloo for rehearsals)")
     ap.add_argument("--headline", default="bf16x3", choices=list(MODES),
                     help="the mode whose throughput is `value` (default bf16x3: 24-bit operands like the reference's fp32)")
-    ap.add_argument("--modes", default="bf16x3,f16x2,f32", help="comma list of conv arithmetic modes to time in this run")
+    ap.add_argument("--modes", default=None,
+                    help=f"comma list of conv arithmetic modes to time in this run (default: the headline mode alone; with --full: {FULL_MODES})")
     ap.add_argument("--conv-precision", default=None, choices=list(MODES), help="shorthand: time ONLY this mode and make it the headline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the other conv modes, the serialised per-kernel roofline pass, "
+                         "forward-only and host-fed rates, the CPU baseline; everything the line leaves out goes to bench_detail.json")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of the headline mode computed as DIR/<name>.npy (float32); "
+                         "implies --deterministic")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="run the step in the library's deterministic mode (bwd-weight split-K partials summed in index order instead of by "
+                         "fp32 atomics: bit-reproducible, ~3 %% slower); reported as config.deterministic")
     return ap.parse_args()
+
+
+def run_modes(args):
+    """The conv modes this run times, headline first: the headline alone, unless --modes or --full asks for more."""
+    if args.conv_precision:
+        args.headline, args.modes = args.conv_precision, args.conv_precision
+    modes = [m for m in (args.modes or (FULL_MODES if args.full else "")).split(",") if m]
+    if args.headline not in modes:
+        modes.insert(0, args.headline)
+    modes.sort(key=lambda m: m != args.headline)          # headline first
+    return modes
 
 
 def main():
@@ -219,14 +248,15 @@ def main():
     from fovealseg import ops
     from fovealseg import modules as Mods
 
-    if args.conv_precision:
-        args.headline, args.modes = args.conv_precision, args.conv_precision
-    modes = [m for m in args.modes.split(",") if m]
-    if args.headline not in modes:
-        modes.insert(0, args.headline)
-    modes.sort(key=lambda m: m != args.headline)          # headline first
+    modes = run_modes(args)
 
     fovealseg.hip.load()       # fail loudly if the HIP library is missing
+    # --deterministic (implied by --dump-outputs): bwd-weight sums its split-K partials in index order instead of by fp32 atomics (the
+    # reference's cudnn.deterministic = True, train_deform_semantic.py:680-681).  With the atomics the last bits differ from run to run and
+    # training on the one batch amplifies them step by step, so a dump is only comparable in this mode; it costs ~3 %.
+    # Without the flag the library's default mode is timed, as before.
+    if args.deterministic or args.dump_outputs:
+        fovealseg.hip.set_deterministic(True)
     rank, local_rank, world = T.ddp_setup(backend=args.backend)
     if world != args.gpus:
         raise SystemExit(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks")
@@ -289,13 +319,15 @@ def main():
         loss_val = float(out[0].detach())
         assert loss_val == loss_val, f"loss is NaN in mode {mode}"
         res = {"value": round(args.batch * world * args.steps / elapsed, 3), "unit": "img/s", "ms_per_step": round(1000.0 * elapsed / args.steps, 3),
-               "operand_significand_bits": MODES[mode][2], "arithmetic": MODES[mode][3], "loss": round(loss_val, 5)}
+               "operand_significand_bits": MODES[mode][2], "arithmetic": MODES[mode][3], "loss": round(loss_val, 5), "last_step_loss": loss_val}
+        if args.dump_outputs and mode == args.headline and rank == 0:
+            dump_outputs(args.dump_outputs, out, optimizers, module)     # before any further pass moves the parameters
 
-        # Per-kernel roofline pass.  In the timed region the HRNet branches run on 4 HIP streams, so kernel lifetimes overlap and
+        # Per-kernel roofline pass (--full).  In the timed region the HRNet branches run on 4 HIP streams, so kernel lifetimes overlap and
         # a per-launch duration is not separable; the same K steps are therefore repeated with the branch streams serialised and
         # every conv / BatchNorm / front-end launch bracketed by HIP events on the launch stream (NOT part of `value`).
         # (All ranks run it -- train_step holds the gradient all-reduce -- and rank 0's kernels are the ones reported.)
-        if not args.no_kernel_timer:
+        if args.full and not args.no_kernel_timer:
             saved = Mods.PARALLEL_BRANCHES
             Mods.PARALLEL_BRANCHES = False
             timer = ops.KernelTimer()
@@ -325,7 +357,7 @@ def main():
     tp = time.perf_counter()
     # forward-only (inference) rate of the same path, SURVEY.md 8(d): eval mode (running statistics, no dropout), no autograd
     fwd_only = None
-    if world == 1 and not args.no_forward_only:
+    if args.full and world == 1 and not args.no_forward_only:
         fwd_only = {}
         for mode in modes:
             fovealseg.hip.set_conv_precision(mode)
@@ -349,7 +381,7 @@ def main():
     # PCIe-inclusive rate (SURVEY 8(d) asks for both; never `value`): every step consumes a NEW batch that starts in pinned host memory as
     # decoded uint8 samples and reaches the device through data.DevicePrefetcher (copy stream + fs_ingest_sample one batch ahead)
     h2d = None
-    if world == 1 and not args.no_h2d:
+    if args.full and world == 1 and not args.no_h2d:
         try:
             h2d = host_fed_rate(T, module, optimizers, cfg, args, dev, modes[0], results[modes[0]]["value"])
         except Exception as exc:
@@ -363,7 +395,7 @@ def main():
 
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             tp = time.perf_counter()
             try:
                 cpu = cpu_baseline()
@@ -371,13 +403,18 @@ def main():
                 cpu = {"error": repr(exc)}
             phases["cpu_baseline_gpu_idle_s"] = round(time.perf_counter() - tp, 1)
         line, detail = build_lines(args.headline, world, args.steps, args.warmup, args.batch, args.size, results, fwd_only, cpu)
+        line["config"]["deterministic"] = fovealseg.hip.get_deterministic()
+        line["loss"] = results[args.headline]["last_step_loss"]        # the headline mode's last timed step (what --dump-outputs writes)
         detail["h2d_included"] = h2d
         detail["phases"] = phases
         line["wall"] = {"gpu_s": round(phases["gpu_timed_and_kernel_timer_passes_s"] + phases["gpu_forward_only_and_host_fed_s"], 1),
                         "cpu_baseline_s": phases.get("cpu_baseline_gpu_idle_s", 0.0), "setup_s": phases["setup_s"]}
         assert len(json.dumps(line)) < MAX_LINE_BYTES
         detail["distributed"] = distributed
-        write_detail(detail)
+        if args.full:
+            write_detail(detail)
+        else:
+            del line["detail"]                      # a plain run writes no side file
         print(json.dumps(line), flush=True)          # the LAST thing on stdout, < 2 KB: the driver parses this line
     if world > 1:
         dist.barrier()
@@ -421,6 +458,39 @@ def host_fed_rate(T, module, optimizers, cfg, args, dev, mode, resident_value):
             "what": "same step, a new batch per step from pinned host memory: uint8 RGBA image + uint8 mask per sample over PCIe on a copy "
                     "stream, fs_ingest_sample (ToTensor, padding, batch assembly) on the device one batch ahead (data.DevicePrefetcher); "
                     "the reference uploads fp32 (4x the bytes) through DDP's scatter (train_deform_semantic.py:74-95)"}
+
+
+ARENA_NAMES = ("encoder", "decoder", "saliency", "compress")      # train.create_optimizers order
+DUMP_SAMPLE = 1 << 20             # elements kept of an arena larger than this (encoder 115.7 M, decoder 14.4 M): a fixed, seeded sample
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, out, optimizers, module):
+    """--dump-outputs: what the last timed step computed, as a caller of train.train_step holds it afterwards, as DIR/<name>.npy
+    (float32): the step's return values (loss, acc[, edge_loss]), every optimiser arena's parameters after the Adam update and the
+    gradients that update used (`params_<arena>`, `grads_<arena>`; arenas above DUMP_SAMPLE elements at the same seeded sorted
+    indices in every run), and the module's float buffers (BatchNorm running statistics) in named_buffers() order.  The inputs are
+    seeded (synthetic_batch, name-keyed init, DropoutState.seed) and --dump-outputs implies deterministic mode, so two runs with the same
+    arguments write the same bits and two builds compare array for array."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for name, t in zip(("loss", "acc", "edge_loss"), out):
+        arrays[name] = torch.as_tensor(t).detach().float().reshape(-1).cpu().numpy()
+    for name, opt in zip(ARENA_NAMES, optimizers):
+        n = opt.flat.numel
+        idx = None
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))
+            idx = torch.from_numpy(idx).to(opt.flat.data.device)
+        for kind, t in (("params", opt.flat.data), ("grads", opt.flat.grad)):
+            arrays[f"{kind}_{name}"] = (t if idx is None else t[idx]).float().cpu().numpy()
+    arrays["buffers"] = torch.cat([b.detach().float().reshape(-1) for _, b in module.named_buffers() if b.is_floating_point()]).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, f"--dump-outputs would write {total} bytes"
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 MAX_LINE_BYTES = 2048

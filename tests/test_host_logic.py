@@ -196,7 +196,7 @@ def test_driver_contract_surface():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
-    for flag in ("--gpus", "--steps", "--warmup", "--conv-precision"):
+    for flag in ("--gpus", "--steps", "--warmup", "--conv-precision", "--full", "--dump-outputs", "--deterministic"):
         assert flag in out.stdout
     src = open(os.path.join(root, "bench.py")).read()
     for key in ('"metric"', '"value"', '"unit"', '"n_gpus"', '"ms_per_step"', '"higher_is_better"', '"scaling"', '"vs_baseline"', '"dtype"',
@@ -330,6 +330,100 @@ def test_bench_line_is_short_and_parseable(tmp_path, monkeypatch):
     src = open(os.path.join(root, "bench.py")).read()
     tail = src[src.index("print(json.dumps(line)"):src.index("MAX_LINE_BYTES = 2048")]
     assert "print(" not in tail[len("print(json.dumps(line)"):]
+
+
+def test_bench_plain_run_times_the_headline_alone(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the headline mode only; --full times all three (headline first), --modes
+    and --conv-precision still choose explicitly."""
+    import importlib
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+
+    def modes(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", *argv])
+        args = bench.parse_args()
+        return bench.run_modes(args), args
+
+    m, args = modes()
+    assert m == ["bf16x3"] and not args.full and args.dump_outputs is None and args.steps == 3 and args.warmup == 1
+    assert modes("--full")[0] == ["bf16x3", "f16x2", "f32"]
+    assert modes("--full", "--headline", "f32")[0] == ["f32", "bf16x3", "f16x2"]
+    assert modes("--conv-precision", "f16x2", "--full")[0] == ["f16x2"]
+    assert modes("--modes", "f32,bf16x3")[0] == ["bf16x3", "f32"]
+    assert modes("--dump-outputs", "out")[1].dump_outputs == "out"
+
+
+def test_bench_dump_outputs_layout(tmp_path):
+    """--dump-outputs writes the step's return values, the arenas' parameters and gradients (a fixed sorted sample of the large ones)
+    and the float buffers, all float32, within 64 MB; the sample indices do not depend on the run."""
+    import importlib
+    import types
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    g = torch.Generator().manual_seed(0)
+    sizes = (bench.DUMP_SAMPLE + 1000, 1000, 28)
+    datas = [torch.randn(n, generator=g) for n in sizes]
+    # grad = 2 * data elementwise: a params / grads pair taken at different indices cannot satisfy grads == 2 * params
+    opts = [types.SimpleNamespace(flat=types.SimpleNamespace(numel=n, data=d, grad=2 * d)) for n, d in zip(sizes, datas)]
+    net = torch.nn.Sequential(torch.nn.Conv2d(3, 4, 1), torch.nn.BatchNorm2d(4))
+    out = (torch.tensor(1.5), torch.tensor(0.25), torch.tensor(0.125, dtype=torch.float64))
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), out, opts, net)
+    names = sorted(f[:-4] for f in os.listdir(tmp_path / "a"))
+    assert names == sorted(["loss", "acc", "edge_loss", "buffers"] + [f"{k}_{a}" for k in ("params", "grads") for a in bench.ARENA_NAMES[:3]])
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / (n + ".npy")), np.load(tmp_path / "b" / (n + ".npy"))
+        assert a.dtype == np.float32 and np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "edge_loss.npy").tolist() == [0.125]
+    idx = np.sort(np.random.default_rng(0).choice(sizes[0], bench.DUMP_SAMPLE, replace=False))       # the documented sample: seed 0, sorted
+    big = np.load(tmp_path / "a" / "params_encoder.npy")
+    assert big.shape == (bench.DUMP_SAMPLE,) and np.array_equal(big, datas[0].numpy()[idx])
+    for arena in bench.ARENA_NAMES[:3]:                    # every params / grads pair at the same elements
+        assert np.array_equal(np.load(tmp_path / "a" / f"grads_{arena}.npy"), 2 * np.load(tmp_path / "a" / f"params_{arena}.npy")), arena
+    assert np.array_equal(np.load(tmp_path / "a" / "grads_decoder.npy"), opts[1].flat.grad.numpy())
+    assert np.load(tmp_path / "a" / "buffers.npy").shape == (8,)          # BatchNorm running mean + var (num_batches_tracked is an integer)
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_line_and_dump(tmp_path):
+    """Bench runs on the device at a small size.  A plain run times the library's default mode and its line carries the headline figure with
+    nothing of --full.  --dump-outputs (implies --deterministic) leaves finite float32 arrays of the LAST timed step: its loss is the line's
+    `loss`, a run with one timed step fewer dumps another loss, and two runs with the same arguments write the same arrays bit for bit
+    (several steps on one batch would amplify any run-to-run difference of the default mode's atomics)."""
+    import json
+
+    def run(name, steps, *extra):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--batch", "2",
+               "--size", "256", *extra]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, (name, r.stderr[-3000:])
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == steps and line["warmup"] == 2 and line["unit"] == "img/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f32" and line["value"] > 0 and abs(line["value"] - 2 * 1000.0 / line["ms_per_step"]) <= 1e-2 * line["value"]
+        assert list(line["modes"]) == ["bf16x3"] and "cpu_baseline" not in line and line["roofline"] is None and "detail" not in line
+        dump = None
+        if os.path.isdir(tmp_path / name):
+            dump = {f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))}
+        return line, dump
+
+    plain, none = run("plain", 3)
+    assert plain["config"]["deterministic"] is False and none is None          # the yardstick: the library's default mode, no dump
+    lines, dumps = zip(*(run(n, s, "--dump-outputs", str(tmp_path / n)) for n, s in (("a", 3), ("b", 3), ("c", 2))))
+    assert all(l["config"]["deterministic"] is True for l in lines)
+    for line, dump in zip(lines, dumps):
+        assert dump["loss"].dtype == np.float32 and dump["loss"].shape == (1,) and np.float32(line["loss"]) == dump["loss"][0]
+    for name in ("params_encoder", "grads_encoder", "params_decoder", "buffers"):
+        a = dumps[0][name]
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), name
+    assert set(dumps[0]) == set(dumps[1]) == set(dumps[2])
+    for name, a in dumps[0].items():
+        assert np.array_equal(a, dumps[1][name]), name
+    assert dumps[2]["loss"][0] != dumps[0]["loss"][0] and not np.array_equal(dumps[2]["params_encoder"], dumps[0]["params_encoder"])
 
 
 # ------------------------------------------------------------------------------------------------

@@ -7,12 +7,12 @@ O=$R/gpurun_out/r02prof
 rm -rf $O && mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 for MODE in bf16x3 f16x2; do
-  BENCH="python3 $R/bench.py --conv-precision $MODE --steps 3 --warmup 1 --serial-streams --no-cpu-baseline --no-kernel-timer --no-forward-only"
+  BENCH="python3 $R/bench.py --conv-precision $MODE --steps 3 --warmup 1 --serial-streams --no-cpu-baseline --no-kernel-timer --no-forward-only --full"
   rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_$MODE -- $BENCH > $O/stats_$MODE.log 2>&1 || { tail -5 $O/stats_$MODE.log; exit 1; }
   cp $(ls $O/stats_$MODE/*/*kernel_stats.csv | tail -1) $O/bench_serial_kernel_stats_$MODE.csv
   rm -rf $O/stats_$MODE
 done
-B1="python3 $R/bench.py --conv-precision bf16x3 --steps 1 --warmup 1 --serial-streams --no-cpu-baseline --no-kernel-timer --no-forward-only"
+B1="python3 $R/bench.py --conv-precision bf16x3 --steps 1 --warmup 1 --serial-streams --no-cpu-baseline --no-kernel-timer --no-forward-only --full"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $O/fetch --output-format csv -- $B1 > $O/fetch.log 2>&1 || { tail -5 $O/fetch.log; exit 1; }
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $O/write --output-format csv -- $B1 > $O/write.log 2>&1 || { tail -5 $O/write.log; exit 1; }
 python3 $R/tools/traffic_summary.py $O/fetch $O/write $O/hbm_traffic_serial.json > $O/traffic_top.txt
