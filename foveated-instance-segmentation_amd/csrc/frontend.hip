@@ -893,14 +893,8 @@ __global__ __launch_bounds__(256) void fill_row_nearest_kernel(const int* __rest
   __syncthreads();
   for (int x = tid; x < Ws; x += 256) r[x] = rowbuf[x];
 }
-__global__ void fill_col_nearest_kernel(const int* __restrict__ rowx, int* __restrict__ src, long n, int Hs, int Ws) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const long per = (long)Hs * Ws;
-  const long b = i / per;
-  const long rem = i - b * per;
-  const int y = (int)(rem / Ws), x = (int)(rem - (long)y * Ws);
-  const int* rx = rowx + b * per;
+// pixel index y'*Ws+x' of the claimed pixel nearest to (y, x), -1 when the image has none; rx = the image's rows of fill_row_nearest_kernel
+__device__ __forceinline__ int nearest_claimed(const int* __restrict__ rx, int y, int x, int Hs, int Ws) {
   long best = -1;
   int bsrc = -1;
   for (int d = 0; d < Hs; ++d) {                       // rows by increasing |y - y'|: stop once dy^2 alone exceeds the best
@@ -915,7 +909,16 @@ __global__ void fill_col_nearest_kernel(const int* __restrict__ rowx, int* __res
       if (best < 0 || dd < best || (dd == best && cand < bsrc)) { best = dd; bsrc = cand; }
     }
   }
-  src[i] = bsrc;
+  return bsrc;
+}
+__global__ void fill_col_nearest_kernel(const int* __restrict__ rowx, int* __restrict__ src, long n, int Hs, int Ws) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long per = (long)Hs * Ws;
+  const long b = i / per;
+  const long rem = i - b * per;
+  const int y = (int)(rem / Ws), x = (int)(rem - (long)y * Ws);
+  src[i] = nearest_claimed(rowx + b * per, y, x, Hs, Ws);
 }
 __global__ void fill_copy_kernel(float* __restrict__ vals, const int* __restrict__ owner, const int* __restrict__ src, int C, long per,
                                  long n) {
@@ -933,6 +936,73 @@ __global__ void fill_copy_kernel(float* __restrict__ vals, const int* __restrict
     v[(c + 0) * per + pix] = a0; v[(c + 1) * per + pix] = a1; v[(c + 2) * per + pix] = a2; v[(c + 3) * per + pix] = a3;
   }
   for (; c < C; ++c) v[c * per + pix] = v[c * per + sp];
+}
+
+// ---- class map at full resolution without the (B,K,Hs,Ws) prediction ----------------------------------------------------------------
+// The C1 prediction is pred[b,k] = cls[b,k] (k < K-1, one constant plane) and pred[b,K-1] = cls[b,K-1] * m[b] (fs_pred_assemble_fwd).
+// Through the inverse warp every full-resolution pixel carries the sample of pred at ONE grid point's inverse coordinate: its owner's
+// if claimed, its nearest claimed pixel's owner's if a hole, (0,0) in an image without any claim.  So argmax_k of unwarp_nearest(pred)
+// is a per-grid-point decision gathered through the owner map; both kernels repeat the float operations of the unfused route exactly.
+constexpr int UNWARP_MAX_K = 1024;
+// dec[b,p] = argmax_k of grid_sample(pred[b], inverse coordinate of point p) for p < h*w, and of the sample at (0,0) for p = h*w
+__global__ __launch_bounds__(256) void unwarp_decide_kernel(const float* __restrict__ cls, const float* __restrict__ m, int* __restrict__ dec,
+                                                            int K, int h, int w, int blocks_per_image) {
+  __shared__ float cs[UNWARP_MAX_K];
+  const int b = blockIdx.x / blocks_per_image;
+  const int hw = h * w;
+  for (int k = threadIdx.x; k < K; k += 256) cs[k] = cls[(long)b * K + k];
+  __syncthreads();
+  const int p = (blockIdx.x - b * blocks_per_image) * 256 + threadIdx.x;
+  if (p > hw) return;
+  float gx = 0.f, gy = 0.f;                            // the coordinate inverse_grid_kernel writes for this point / for a hole
+  if (p < hw) {
+    const int yi = p / w, xi = p - yi * w;
+    gx = __fsub_rn(__fmul_rn(__fdiv_rn((float)xi, (float)w), 2.f), 1.f);
+    gy = __fsub_rn(__fmul_rn(__fdiv_rn((float)yi, (float)h), 2.f), 1.f);
+  }
+  const Taps t = make_taps(gx, gy, h, w);
+  const bool inw = t.oky0 & t.okx0, ine = t.oky0 & t.okx1, isw = t.oky1 & t.okx0, ise = t.oky1 & t.okx1;
+  // sample_plane's sequence; a constant plane reads c at every in-bounds tap, 0 outside
+  auto sample4 = [&](float vnw, float vne, float vsw, float vse) {
+    float acc = __fmul_rn(vnw, t.nw);
+    acc = __fmaf_rn(vne, t.ne, acc);
+    acc = __fmaf_rn(vsw, t.sw, acc);
+    return __fmaf_rn(vse, t.se, acc);
+  };
+  // torch.argmax: the first maximal index; NaN counts as the maximum
+  float best = 0.f;
+  int arg = 0;
+  for (int k = 0; k < K - 1; ++k) {
+    const float c = cs[k];
+    const float v = sample4(inw ? c : 0.f, ine ? c : 0.f, isw ? c : 0.f, ise ? c : 0.f);
+    if (k == 0 || v > best || (v != v && best == best)) { best = v; arg = k; }
+  }
+  const float c = cs[K - 1];
+  const float* mp = m + (long)b * hw;
+  const float v = sample4(inw ? __fmul_rn(c, mp[t.y0 * w + t.x0]) : 0.f, ine ? __fmul_rn(c, mp[t.y0 * w + t.x0 + 1]) : 0.f,
+                          isw ? __fmul_rn(c, mp[(t.y0 + 1) * w + t.x0]) : 0.f, ise ? __fmul_rn(c, mp[(t.y0 + 1) * w + t.x0 + 1]) : 0.f);
+  if (v > best || (v != v && best == best)) arg = K - 1;
+  dec[(long)b * (hw + 1) + p] = arg;
+}
+// labels[b,v,u] = dec[b, point feeding the pixel]: its owner; a hole's nearest claimed pixel's owner (fill_col_nearest_kernel's search);
+// dec[b,h*w] in an image without any claim.  hole (nullable) = the pixel has no owner.
+__global__ __launch_bounds__(256) void unwarp_label_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
+                                                           long long* __restrict__ labels, unsigned char* __restrict__ hole, long n, int Hs, int Ws,
+                                                           int hw) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const long per = (long)Hs * Ws;
+  const long b = i / per;
+  const int o = owner[i];
+  int q = o;
+  if (o < 0) {
+    const long rem = i - b * per;
+    const int y = (int)(rem / Ws), x = (int)(rem - (long)y * Ws);
+    const int src = nearest_claimed(rowx + b * per, y, x, Hs, Ws);
+    q = src >= 0 ? owner[b * per + src] : hw;
+  }
+  labels[i] = (long long)dec[b * (hw + 1) + q];
+  if (hole != nullptr) hole[i] = o < 0;
 }
 
 }  // namespace
@@ -1261,6 +1331,34 @@ int fs_fill_nearest(float* vals, const int* owner, int* scratch, int B, int C, i
   hipLaunchKernelGGL(fill_col_nearest_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, rowx, src, n, Hs, Ws);
   FS_LAUNCH_CHECK();
   hipLaunchKernelGGL(fill_copy_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, vals, owner, src, C, per, n);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+long fs_unwarp_labels_scratch_ints(int B, int h, int w, int Hs, int Ws) {
+  return (B > 0 && h > 0 && w > 0 && Hs > 0 && Ws > 0) ? 2L * B * Hs * Ws + (long)B * ((long)h * w + 1) : 0;
+}
+
+int fs_unwarp_labels(const float* cls, const float* m, const float* grid, long long* labels, unsigned char* hole, int* scratch, int B, int K,
+                     int h, int w, int Hs, int Ws, hipStream_t stream) {
+  FS_REQUIRE(cls && m && grid && labels && scratch && B > 0 && K >= 2 && K <= UNWARP_MAX_K && h > 0 && w > 0 && Hs > 0 && Ws > 0);
+  FS_REQUIRE(Ws <= 16384 && (long)h * w < 2147483647L && (long)Hs * Ws < 2147483647L);      // one row in LDS; int pixel / point indices
+  const long per = (long)Hs * Ws, n = (long)B * per;
+  const long bpi = ((long)h * w + 1 + 255) / 256;
+  const long threads_max = 4294967295L - 255;          // every launch below: fewer than 2^32 work-items
+  FS_REQUIRE(n <= threads_max && (long)B * Hs * 256 <= threads_max && (long)B * bpi * 256 <= threads_max);
+  int* owner = scratch;         // [B*Hs*Ws]
+  int* rowx = scratch + n;      // [B*Hs*Ws]
+  int* dec = scratch + 2 * n;   // [B*(h*w+1)]
+  hipLaunchKernelGGL(unwarp_decide_kernel, dim3((unsigned)(B * bpi)), dim3(256), 0, stream, cls, m, dec, K, h, w, (int)bpi);
+  FS_LAUNCH_CHECK();
+  hipError_t e = hipMemsetAsync(owner, 0xFF, sizeof(int) * (size_t)n, stream);      // -1
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(inverse_owner_kernel, dim3(cdiv((long)B * h * w, 256)), dim3(256), 0, stream, grid, owner, B, h * w, Hs, Ws);
+  FS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(fill_row_nearest_kernel, dim3((unsigned)((long)B * Hs)), dim3(256), (size_t)Ws * sizeof(int), stream, owner, rowx, Ws);
+  FS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(unwarp_label_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, owner, rowx, dec, labels, hole, n, Hs, Ws, h * w);
   FS_LAUNCH_CHECK();
   return FS_OK;
 }

@@ -195,6 +195,44 @@ class DeformSegmentationModule(nn.Module):
         st["event"] = None
         assert not bool(st["host"][0]), "xs contains NaN values!"
 
+    @torch.no_grad()
+    def predict(self, img, focus, seg_size=None):
+        """Label-free inference: which class every full-resolution pixel of `img` belongs to, given the gaze point `focus`.
+
+        img (B,3,H,W) as forward's img_data, focus (B,2) as its focus_point; returns the int64 class map (B, *seg_size), seg_size
+        defaulting to (H, W).  The stages are forward's -- saliency, the sampling grid (uniform_sample and the task-size up-sampling
+        included), GridSample, encoder, C1 head -- then the inverse warp with nearest hole filling and the argmax over classes
+        (models/models.py:639-655,930-940; eval.py:195), fused in ops.unwarp_labels so that no (B,K,*seg_size) prediction exists.
+        The result equals `unwarp_nearest(decoder.forward_nhwc(feat), grid, *seg_size)[0].argmax(1)` bit for bit.
+
+        Class num_class - 1 is background: the gazed instance's mask is `labels != num_class - 1`.  Eval mode only (module.eval()):
+        a train-mode forward would update the BatchNorm running statistics.  No label is read, no loss is computed and no argument is
+        written to.  A NaN saliency map raises forward's `xs contains NaN values!` assertion at the next forward / predict or at
+        check_nan(), as in forward (_note_nan)."""
+        if self.training:
+            raise RuntimeError("predict() needs eval mode (module.eval()): in train mode the encoder would update its BatchNorm running statistics")
+        if img.dim() != 4 or img.shape[1] != 3:
+            raise ValueError(f"img must be (B,3,H,W), got {tuple(img.shape)}")
+        B = img.shape[0]
+        if tuple(focus.shape) != (B, 2):
+            raise ValueError(f"focus must be (B,2) = ({B},2), got {tuple(focus.shape)}")
+        if seg_size is None:
+            seg_size = (img.shape[2], img.shape[3])
+        if len(seg_size) != 2 or int(seg_size[0]) <= 0 or int(seg_size[1]) <= 0:
+            raise ValueError(f"seg_size must be (H, W) with positive sides, got {tuple(seg_size)}")
+        self.check_nan()
+        ops.reset_step_state()
+        x = img.contiguous()
+        xs, _ = self.saliency(x, focus.float().contiguous())
+        self._note_nan(xs)
+        if self.cfg.MODEL.uniform_sample != "":
+            xs = xs * 0 + 1.0 / (self.grid_size_x * self.grid_size_y)       # as forward, models/models.py:816-818
+        grid = self.create_grid(xs)
+        feat = self.encoder.forward_nhwc(ops.GridSample.apply(x, grid))
+        cls, m = self.decoder.forward_parts_nhwc(feat)
+        labels, _hole = ops.unwarp_labels(cls, m, grid, int(seg_size[0]), int(seg_size[1]))
+        return labels
+
     def forward(self, feed_dict, *, writer=None, segSize=None, F_Xlr_acc_map=False, count=None, epoch=None,
                 feed_dict_info=None, feed_batch_count=None, cur_iter=None, is_inference=False, rank=None):
         self.check_nan()

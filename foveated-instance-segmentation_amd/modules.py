@@ -503,7 +503,8 @@ class C1(nn.Module):
         self.conv_last = nn.Conv2d(fc_dim // 4, 1, 1, 1, 0)     # parameter holder (key names/shapes)
         self.cls_net = ResNet(inplanes=fc_dim, num_classes=num_class)
 
-    def forward_nhwc(self, feat):
+    def forward_parts_nhwc(self, feat):
+        """The head's two factors, (cls (B,K), m (B,H,W)): the prediction is PredAssemble(cls, m)."""
         # `feat` has two readers.  Through one fan-out, with the classification branch's gradient handed to the 3x3 conv's bwd-data epilogue
         # (ops.StashGrad; the node is created after the mask branch so that its backward runs first): no 1.57 GB + 1.57 GB add pass at B = 64
         fa, fb = ops.fan_out(feat, 2) if C1_STASH else (feat, feat)
@@ -513,7 +514,10 @@ class C1(nn.Module):
         if fan is not None:
             fb = ops.StashGrad.apply(fb, fan[0])
         cls = self.cls_net(fb)                                                      # (B,K)
-        return ops.PredAssemble.apply(cls, m)                                       # (B,K,H,W) NCHW
+        return cls, m
+
+    def forward_nhwc(self, feat):
+        return ops.PredAssemble.apply(*self.forward_parts_nhwc(feat))              # (B,K,H,W) NCHW
 
     def forward(self, conv_out, segSize=None, res=None):
         if res is not None:

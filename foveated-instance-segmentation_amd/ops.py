@@ -1467,6 +1467,23 @@ def unwarp_nearest(pred, grid, Hs, Ws):
     return out, owner < 0
 
 
+def unwarp_labels(cls, m, grid, Hs, Ws):
+    """Full-resolution class map of the C1 head (no autograd): bit for bit
+    `unwarp_nearest(PredAssemble.apply(cls, m), grid, Hs, Ws)[0].argmax(1)`, without the (B,K,Hs,Ws) prediction -- the argmax is
+    taken once per grid point and gathered through the owner map (fs_unwarp_labels).  cls (B,K), m (B,h,w) at the grid's
+    resolution, grid (B,h,w,2).  Returns (labels (B,Hs,Ws) int64, hole mask (B,Hs,Ws) bool)."""
+    B, K = cls.shape
+    _, h, w, _ = grid.shape
+    if tuple(m.shape) != (B, h, w):
+        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
+    labels = torch.empty(B, Hs, Ws, device=cls.device, dtype=torch.int64)
+    hole = torch.empty(B, Hs, Ws, device=cls.device, dtype=torch.bool)
+    scratch = torch.empty(hip.query("fs_unwarp_labels_scratch_ints", B, h, w, Hs, Ws), device=cls.device, dtype=torch.int32)
+    hip.call("fs_unwarp_labels", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(labels),
+             hip.ptr(hole), hip.ptr(scratch), B, K, h, w, Hs, Ws)
+    return labels, hole
+
+
 # ----------------------------------------------------------------------------------------------
 # SegFormer pieces (tokens = NHWC rows)
 # ----------------------------------------------------------------------------------------------

@@ -98,6 +98,16 @@ int fs_grid_sample_bwd_input(const float* gout, const float* grid, float* dx, in
  * then column) -- fillMissingValues_tensor(..., interp_mode='nearest'), models/models.py:159-286.  scratch = 2*B*Hs*Ws ints. */
 int fs_inverse_grid(const float* grid, int* owner, float* grid_inv, int B, int h, int w, int Hs, int Ws, fs_stream_t stream);
 int fs_fill_nearest(float* vals, const int* owner, int* scratch, int B, int C, int Hs, int Ws, fs_stream_t stream);
+/* Full-resolution class map of the C1 head without the (B,K,Hs,Ws) prediction: labels (B,Hs,Ws) int64 is bit-identical to
+ * argmax over k of fs_fill_nearest(fs_grid_sample_fwd(fs_pred_assemble_fwd(cls, m), grid_inv)) (first maximal k; NaN is maximal),
+ * the route of models/models.py:639-655,930-940 followed by the eval caller's torch.max(scores, dim=1) (eval.py:195).  Every
+ * pixel's K values are one grid point's samples (its owner's, its nearest claimed pixel's owner's, (0,0) in an image without a
+ * claim), so the argmax is taken once per grid point and gathered.  cls (B,K), m (B,h,w) at the grid's resolution, grid (B,h,w,2);
+ * hole (B,Hs,Ws) bytes, nullable: 1 where no grid point claims the pixel.  scratch = fs_unwarp_labels_scratch_ints(B, h, w, Hs, Ws)
+ * ints.  FS_ERR_ARG for K < 2 or K > 1024, Ws > 16384, or sizes beyond 32-bit pixel indices. */
+long fs_unwarp_labels_scratch_ints(int B, int h, int w, int Hs, int Ws);
+int fs_unwarp_labels(const float* cls, const float* m, const float* grid, long long* labels, unsigned char* hole, int* scratch, int B, int K,
+                     int h, int w, int Hs, int Ws, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
