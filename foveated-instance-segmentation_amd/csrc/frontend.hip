@@ -1005,6 +1005,173 @@ __global__ __launch_bounds__(256) void unwarp_label_kernel(const int* __restrict
   if (hole != nullptr) hole[i] = o < 0;
 }
 
+// ---- the four full-resolution accuracies without the class map ---------------------------------------------------------------------
+// unwarp_label_kernel's gather with the compare-and-count of seg_loss_fwd_kernel behind it: the predicted class of a pixel is
+// dec[point feeding it], its ground truth one read of the label mask (t = (long)y, gt = t*cls_label + (1-t)*(K-1), models.py:968),
+// and the six counters of models/models.py:378-474 are summed where the class would have been stored.
+// pixels per thread: one trip of four neighbours.  8 and 16 (fewer records) measured slower: 614 / 616 against 519 us at B = 64, 1024^2,
+// and 24 / 34 against 14 us at B = 1, where 256 workgroups a trip longer leave the CUs short of waves (profiles/r07)
+constexpr int UACC_PIX = 4;
+constexpr int UACC_CHUNK = 256 * UACC_PIX;             // pixels per workgroup, all of one image
+constexpr int UACC_REC = 8;                            // ints per workgroup record: the six counters + 2 of padding (two 16-byte stores)
+struct AccCount { int c[6]; };
+__device__ __forceinline__ int unwarp_class_at(const int* __restrict__ ob, const int* __restrict__ rx, const int* __restrict__ db, int o,
+                                               int y, int x, int Hs, int Ws, int hw) {
+  int q = o;
+  if (o < 0) {
+    const int src = nearest_claimed(rx, y, x, Hs, Ws);
+    q = src >= 0 ? ob[src] : hw;
+  }
+  return db[q];
+}
+// nearest_claimed for the four pixels (y, x .. x+3) of one row at once (x % 4 == 0, Ws % 4 == 0): one 16-byte read of rx per row serves
+// all four.  Every pixel sees its candidates in nearest_claimed's order and under its comparison; the rows past the point where
+// nearest_claimed would have stopped for it cannot win (dd >= d*d > best), so each src[k] is nearest_claimed's.  A claimed pixel
+// (hole bit clear) takes no part.
+__device__ __forceinline__ void nearest_claimed4(const int* __restrict__ rx, int y, int x, int Hs, int Ws, int holes, int src[4]) {
+  long best[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { best[k] = (holes >> k) & 1 ? -1 : 0; src[k] = -1; }
+  for (int d = 0; d < Hs; ++d) {
+    const long d2 = (long)d * d;
+    bool done = true;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) done = done && best[k] >= 0 && d2 > best[k];
+    if (done) break;
+    for (int sgn = 0; sgn < 2; ++sgn) {
+      const int yy = sgn == 0 ? y - d : y + d;
+      if (yy < 0 || yy >= Hs || (d == 0 && sgn == 1)) continue;
+      const int4 r = *reinterpret_cast<const int4*>(rx + (long)yy * Ws + x);
+      const int xs[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int xx = xs[k];
+        if (xx < 0) continue;
+        const long dx = (long)(x + k - xx);
+        const long dd = d2 + dx * dx;
+        const int cand = yy * Ws + xx;
+        if (best[k] < 0 || dd < best[k] || (dd == best[k] && cand < src[k])) { best[k] = dd; src[k] = cand; }
+      }
+    }
+  }
+}
+// head_loss.hip's predicates (seg_loss_fwd_kernel) on one pixel: a = predicted class, yv = the label mask's value
+__device__ __forceinline__ void count_pixel(AccCount& n, int a, float yv, long long cl, int bg) {
+  const long long t = (long long)yv;
+  const long long g = t * cl + (1 - t) * (long long)bg;
+  const bool vg = g < bg, vp = a < bg, bgg = g == bg, bgp = a == bg, eq = (long long)a == g;
+  n.c[0] += (vg && eq); n.c[1] += (vg && (vg == vp)); n.c[2] += (vg || vp);
+  n.c[3] += (bgg && eq); n.c[4] += (bgg && (bgg == bgp)); n.c[5] += (bgg || bgp);
+}
+// grid = B * blocks_per_image workgroups; workgroup (b, chunk) counts UACC_CHUNK consecutive pixels of image b into ONE record of
+// rec (plain stores: no zero-initialised scratch, no global atomics).  VEC: Ws % 4 == 0 and 16-byte aligned owner / y / labels, so
+// that four neighbours are one row's and load as one dwordx4 each.  labels (nullable) receives unwarp_label_kernel's class map.
+template <bool VEC>
+__global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
+                                                           const float* __restrict__ yl, const long long* __restrict__ cls_label,
+                                                           long long* __restrict__ labels, int* __restrict__ rec, int Hs, int Ws, int hw,
+                                                           int K, int blocks_per_image) {
+  __shared__ int part[4][6];
+  const int b = blockIdx.x / blocks_per_image, chunk = blockIdx.x - b * blocks_per_image;
+  const int per = Hs * Ws;
+  const long base = (long)b * per;
+  const int* ob = owner + base;
+  const int* rx = rowx + base;
+  const int* db = dec + (long)b * (hw + 1);
+  const float* yb = yl + base;
+  const long long cl = cls_label[b];
+  const int bg = K - 1;
+  AccCount n = {{0, 0, 0, 0, 0, 0}};
+  const int p0 = chunk * UACC_CHUNK;
+  if (VEC) {
+#pragma unroll 1
+    for (int j = 0; j < UACC_PIX / 4; ++j) {
+      const int p = p0 + (j * 256 + (int)threadIdx.x) * 4;
+      if (p >= per) break;                             // per % 4 == 0: the four pixels are in or out together
+      const int4 o4 = *reinterpret_cast<const int4*>(ob + p);
+      const float4 y4 = *reinterpret_cast<const float4*>(yb + p);
+      const int y = p / Ws, x = p - y * Ws;            // Ws % 4 == 0: one row
+      int q[4] = {o4.x, o4.y, o4.z, o4.w};
+      const int holes = (o4.x < 0) | (o4.y < 0) << 1 | (o4.z < 0) << 2 | (o4.w < 0) << 3;
+      if (holes) {
+        int src[4];
+        nearest_claimed4(rx, y, x, Hs, Ws, holes, src);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
+      }
+      const int a0 = db[q[0]], a1 = db[q[1]], a2 = db[q[2]], a3 = db[q[3]];
+      count_pixel(n, a0, y4.x, cl, bg); count_pixel(n, a1, y4.y, cl, bg);
+      count_pixel(n, a2, y4.z, cl, bg); count_pixel(n, a3, y4.w, cl, bg);
+      if (labels != nullptr) {
+        longlong2* lp = reinterpret_cast<longlong2*>(labels + base + p);
+        lp[0] = make_longlong2(a0, a1); lp[1] = make_longlong2(a2, a3);
+      }
+    }
+  } else {
+#pragma unroll 1
+    for (int j = 0; j < UACC_PIX; ++j) {
+      const int p = p0 + j * 256 + (int)threadIdx.x;
+      if (p >= per) break;
+      const int y = p / Ws, x = p - y * Ws;
+      const int a = unwarp_class_at(ob, rx, db, ob[p], y, x, Hs, Ws, hw);
+      count_pixel(n, a, yb[p], cl, bg);
+      if (labels != nullptr) labels[base + p] = (long long)a;
+    }
+  }
+  // in the wave by shuffles, across the four waves through LDS; integers: the same record whatever the order
+#pragma unroll
+  for (int q = 0; q < 6; ++q) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n.c[q] += __shfl_xor(n.c[q], o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) part[threadIdx.x >> 6][q] = n.c[q];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int s[6];
+#pragma unroll
+    for (int q = 0; q < 6; ++q) s[q] = (part[0][q] + part[1][q]) + (part[2][q] + part[3][q]);
+    int4* r = reinterpret_cast<int4*>(rec + (long)blockIdx.x * UACC_REC);
+    r[0] = make_int4(s[0], s[1], s[2], s[3]);
+    r[1] = make_int4(s[4], s[5], 0, 0);
+  }
+}
+// counts[b, 0..6) = the sum of image b's records; one workgroup per image
+__global__ __launch_bounds__(256) void unwarp_count_finalize_kernel(const int* __restrict__ rec, long long* __restrict__ counts,
+                                                                    int blocks_per_image) {
+  __shared__ long long red[16];
+  const int b = blockIdx.x;
+  const int4* r = reinterpret_cast<const int4*>(rec + (long)b * blocks_per_image * UACC_REC);
+  long long c[6] = {0, 0, 0, 0, 0, 0};
+  for (int j = threadIdx.x; j < blocks_per_image; j += 256) {
+    const int4 lo = r[2 * j], hi = r[2 * j + 1];
+    c[0] += lo.x; c[1] += lo.y; c[2] += lo.z; c[3] += lo.w; c[4] += hi.x; c[5] += hi.y;
+  }
+  for (int q = 0; q < 6; ++q) {
+    const long long s = block_sum<long long>(c[q], red);
+    if (threadIdx.x == 0) counts[(long)b * 6 + q] = s;
+  }
+}
+// acc[0..4) = acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg: seg_loss_finalize_kernel's arithmetic (head_loss.hip) on the integer counts
+__global__ __launch_bounds__(256) void unwarp_accuracy_kernel(const long long* __restrict__ counts, float* __restrict__ acc, int B) {
+  __shared__ double img[4][16];
+  double a[4] = {0, 0, 0, 0};
+  for (int b = threadIdx.x; b < B; b += blockDim.x) {
+    const long long* c = counts + (long)b * 6;
+    const float ufg = (float)c[2] + 1e-10f, ubg = (float)c[5] + 1e-10f;
+    const float cls_fg = (float)c[0] / ufg, bin_fg = (float)c[1] / ufg, cls_bg = (float)c[3] / ubg, bin_bg = (float)c[4] / ubg;
+    a[0] += cls_fg; a[1] += bin_fg; a[2] += cls_fg * 0.5f + cls_bg * 0.5f; a[3] += bin_fg * 0.5f + bin_bg * 0.5f;
+  }
+  for (int j = 0; j < 4; ++j) a[j] = block_sum<double>(a[j], img[j]);
+  if (threadIdx.x < 4) {
+    const int j = threadIdx.x;
+    acc[j] = (float)((j == 0 ? a[0] : j == 1 ? a[1] : j == 2 ? a[2] : a[3]) / (double)B);
+  }
+}
+
 }  // namespace
 
 // ---- input pipeline: decoded uint8 sample -> padded float planes of the batch, on the device ----
@@ -1359,6 +1526,55 @@ int fs_unwarp_labels(const float* cls, const float* m, const float* grid, long l
   hipLaunchKernelGGL(fill_row_nearest_kernel, dim3((unsigned)((long)B * Hs)), dim3(256), (size_t)Ws * sizeof(int), stream, owner, rowx, Ws);
   FS_LAUNCH_CHECK();
   hipLaunchKernelGGL(unwarp_label_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, owner, rowx, dec, labels, hole, n, Hs, Ws, h * w);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+// scratch of fs_unwarp_accuracy: fs_unwarp_labels' three maps, then (16-byte aligned) one record per workgroup of the count pass
+static long unwarp_accuracy_rec_offset(int B, int h, int w, int Hs, int Ws) {
+  return (2L * B * Hs * Ws + (long)B * ((long)h * w + 1) + 3) & ~3L;
+}
+long fs_unwarp_accuracy_scratch_ints(int B, int h, int w, int Hs, int Ws) {
+  if (!(B > 0 && h > 0 && w > 0 && Hs > 0 && Ws > 0)) return 0;
+  const long bpi = ((long)Hs * Ws + UACC_CHUNK - 1) / UACC_CHUNK;
+  return unwarp_accuracy_rec_offset(B, h, w, Hs, Ws) + (long)B * bpi * UACC_REC;
+}
+
+int fs_unwarp_accuracy(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
+                       float* acc, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws, hipStream_t stream) {
+  FS_REQUIRE(cls && m && grid && y && cls_label && counts && acc && scratch && B > 0 && K >= 2 && K <= UNWARP_MAX_K && h > 0 && w > 0 &&
+             Hs > 0 && Ws > 0);
+  // one row in LDS; int pixel / point indices, the count pass's included (a workgroup's last trip may start up to a chunk past the end)
+  FS_REQUIRE(Ws <= 16384 && (long)h * w < 2147483647L && (long)Hs * Ws < 2147483647L - UACC_CHUNK);
+  const long per = (long)Hs * Ws, n = (long)B * per;
+  const long bpi = ((long)h * w + 1 + 255) / 256;
+  const long cpi = (per + UACC_CHUNK - 1) / UACC_CHUNK;                 // count-pass workgroups (= records) per image
+  const long threads_max = 4294967295L - 255;          // every launch below: fewer than 2^32 work-items
+  FS_REQUIRE(n <= threads_max && (long)B * Hs * 256 <= threads_max && (long)B * bpi * 256 <= threads_max && (long)B * cpi * 256 <= threads_max);
+  int* owner = scratch;         // [B*Hs*Ws]
+  int* rowx = scratch + n;      // [B*Hs*Ws]
+  int* dec = scratch + 2 * n;   // [B*(h*w+1)]
+  int* rec = scratch + unwarp_accuracy_rec_offset(B, h, w, Hs, Ws);     // [B*cpi][UACC_REC]
+  FS_REQUIRE(((uintptr_t)scratch & 15) == 0);          // the records are stored and read 16 bytes at a time
+  hipLaunchKernelGGL(unwarp_decide_kernel, dim3((unsigned)(B * bpi)), dim3(256), 0, stream, cls, m, dec, K, h, w, (int)bpi);
+  FS_LAUNCH_CHECK();
+  hipError_t e = hipMemsetAsync(owner, 0xFF, sizeof(int) * (size_t)n, stream);      // -1
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL(inverse_owner_kernel, dim3(cdiv((long)B * h * w, 256)), dim3(256), 0, stream, grid, owner, B, h * w, Hs, Ws);
+  FS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(fill_row_nearest_kernel, dim3((unsigned)((long)B * Hs)), dim3(256), (size_t)Ws * sizeof(int), stream, owner, rowx, Ws);
+  FS_LAUNCH_CHECK();
+  const bool vec = Ws % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)labels & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(unwarp_count_kernel<true>, dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels, rec,
+                       Hs, Ws, h * w, K, (int)cpi);
+  else
+    hipLaunchKernelGGL(unwarp_count_kernel<false>, dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels, rec,
+                       Hs, Ws, h * w, K, (int)cpi);
+  FS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(unwarp_count_finalize_kernel, dim3((unsigned)B), dim3(256), 0, stream, rec, counts, (int)cpi);
+  FS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(unwarp_accuracy_kernel, dim3(1), dim3(256), 0, stream, counts, acc, B);
   FS_LAUNCH_CHECK();
   return FS_OK;
 }

@@ -195,22 +195,11 @@ class DeformSegmentationModule(nn.Module):
         st["event"] = None
         assert not bool(st["host"][0]), "xs contains NaN values!"
 
-    @torch.no_grad()
-    def predict(self, img, focus, seg_size=None):
-        """Label-free inference: which class every full-resolution pixel of `img` belongs to, given the gaze point `focus`.
-
-        img (B,3,H,W) as forward's img_data, focus (B,2) as its focus_point; returns the int64 class map (B, *seg_size), seg_size
-        defaulting to (H, W).  The stages are forward's -- saliency, the sampling grid (uniform_sample and the task-size up-sampling
-        included), GridSample, encoder, C1 head -- then the inverse warp with nearest hole filling and the argmax over classes
-        (models/models.py:639-655,930-940; eval.py:195), fused in ops.unwarp_labels so that no (B,K,*seg_size) prediction exists.
-        The result equals `unwarp_nearest(decoder.forward_nhwc(feat), grid, *seg_size)[0].argmax(1)` bit for bit.
-
-        Class num_class - 1 is background: the gazed instance's mask is `labels != num_class - 1`.  Eval mode only (module.eval()):
-        a train-mode forward would update the BatchNorm running statistics.  No label is read, no loss is computed and no argument is
-        written to.  A NaN saliency map raises forward's `xs contains NaN values!` assertion at the next forward / predict or at
-        check_nan(), as in forward (_note_nan)."""
+    def _head_parts(self, img, focus, seg_size, who):
+        """predict's / evaluate's shared front: argument checks, then forward's stages up to the C1 head's two factors.
+        Returns (cls (B,K), m (B,h,w), grid (B,h,w,2), seg_size as two ints)."""
         if self.training:
-            raise RuntimeError("predict() needs eval mode (module.eval()): in train mode the encoder would update its BatchNorm running statistics")
+            raise RuntimeError(f"{who}() needs eval mode (module.eval()): in train mode the encoder would update its BatchNorm running statistics")
         if img.dim() != 4 or img.shape[1] != 3:
             raise ValueError(f"img must be (B,3,H,W), got {tuple(img.shape)}")
         B = img.shape[0]
@@ -230,8 +219,50 @@ class DeformSegmentationModule(nn.Module):
         grid = self.create_grid(xs)
         feat = self.encoder.forward_nhwc(ops.GridSample.apply(x, grid))
         cls, m = self.decoder.forward_parts_nhwc(feat)
-        labels, _hole = ops.unwarp_labels(cls, m, grid, int(seg_size[0]), int(seg_size[1]))
+        return cls, m, grid, (int(seg_size[0]), int(seg_size[1]))
+
+    @torch.no_grad()
+    def predict(self, img, focus, seg_size=None):
+        """Label-free inference: which class every full-resolution pixel of `img` belongs to, given the gaze point `focus`.
+
+        img (B,3,H,W) as forward's img_data, focus (B,2) as its focus_point; returns the int64 class map (B, *seg_size), seg_size
+        defaulting to (H, W).  The stages are forward's -- saliency, the sampling grid (uniform_sample and the task-size up-sampling
+        included), GridSample, encoder, C1 head -- then the inverse warp with nearest hole filling and the argmax over classes
+        (models/models.py:639-655,930-940; eval.py:195), fused in ops.unwarp_labels so that no (B,K,*seg_size) prediction exists.
+        The result equals `unwarp_nearest(decoder.forward_nhwc(feat), grid, *seg_size)[0].argmax(1)` bit for bit.
+
+        Class num_class - 1 is background: the gazed instance's mask is `labels != num_class - 1`.  Eval mode only (module.eval()):
+        a train-mode forward would update the BatchNorm running statistics.  No label is read, no loss is computed and no argument is
+        written to.  A NaN saliency map raises forward's `xs contains NaN values!` assertion at the next forward / predict or at
+        check_nan(), as in forward (_note_nan)."""
+        cls, m, grid, seg_size = self._head_parts(img, focus, seg_size, "predict")
+        labels, _hole = ops.unwarp_labels(cls, m, grid, *seg_size)
         return labels
+
+    @torch.no_grad()
+    def evaluate(self, img, focus, seg_label, cls_label, seg_size=None, return_labels=False):
+        """Full-resolution scoring without the loss: predict's stages, then the four accuracies of forward's MODEL.upsample branch
+        (models/models.py:378-474,869-873,1074-1083) taken against the label in the pass that would have written the class map
+        (ops.unwarp_accuracy / fs_unwarp_accuracy): no (B,K,H,W) prediction, no class map and no ground-truth tensor exist.
+
+        img (B,3,H,W), focus (B,2) as predict's; seg_label (B,H,W) or (B,1,H,W) the label mask as fed to forward, cls_label (B,) or
+        (B,1) the gazed instance's class.  Returns (acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg, counts): four 0-d fp32 tensors, the
+        batch means forward(is_inference=True) reports, and counts (B,6) int64 = cls_fg, bin_fg, union_fg, cls_bg, bin_bg, union_bg per
+        image (train.FullResMeter accumulates them into dataset-level scores); with return_labels, predict's class map as a sixth
+        element.  seg_size defaults to the label's size and may not differ from it.  Eval mode only; no argument is written to,
+        nothing in the module changes, and a NaN saliency map is reported as in predict."""
+        if seg_label.dim() not in (3, 4) or (seg_label.dim() == 4 and seg_label.shape[1] != 1):
+            raise ValueError(f"seg_label must be (B,H,W) or (B,1,H,W), got {tuple(seg_label.shape)}")
+        label_size = (int(seg_label.shape[-2]), int(seg_label.shape[-1]))
+        if seg_size is not None and (len(seg_size) != 2 or (int(seg_size[0]), int(seg_size[1])) != label_size):
+            raise ValueError(f"seg_size {tuple(seg_size)} differs from the label's size {label_size}: the accuracies are taken pixel against pixel")
+        if seg_label.shape[0] != img.shape[0] or cls_label.shape[0] != img.shape[0]:
+            raise ValueError(f"seg_label {tuple(seg_label.shape)} and cls_label {tuple(cls_label.shape)} must have img's batch size {img.shape[0]}")
+        cls, m, grid, _ = self._head_parts(img, focus, label_size, "evaluate")
+        out = ops.unwarp_accuracy(cls, m, grid, seg_label, cls_label, return_labels=return_labels)
+        counts, acc = out[0], out[1]
+        res = (acc[0], acc[1], acc[2], acc[3], counts)
+        return res + (out[2],) if return_labels else res
 
     def forward(self, feed_dict, *, writer=None, segSize=None, F_Xlr_acc_map=False, count=None, epoch=None,
                 feed_dict_info=None, feed_batch_count=None, cur_iter=None, is_inference=False, rank=None):
@@ -269,7 +300,12 @@ class DeformSegmentationModule(nn.Module):
         label = ops.grid_sample_label(y, grid.detach())
         x_sampled = ops.grad_probe(ops.GridSample.apply(x, grid), "dx_sampled")      # (B,hs,ws,3) NHWC
         feat = self.encoder.forward_nhwc(x_sampled)
-        pred = self.decoder.forward_nhwc(feat)                         # (B,K,hs,ws)
+        if cfg.MODEL.upsample:
+            # the head's two factors feed the full-resolution accuracies below; the prediction is decoder.forward_nhwc's
+            head_cls, head_m = self.decoder.forward_parts_nhwc(feat)
+            pred = ops.PredAssemble.apply(head_cls, head_m)
+        else:
+            pred = self.decoder.forward_nhwc(feat)                     # (B,K,hs,ws)
         feed_dict["seg_label"] = label                                  # models/models.py:951
 
         cls = feed_dict["cls_label"].to(label.dtype)
@@ -283,14 +319,12 @@ class DeformSegmentationModule(nn.Module):
         if cfg.MODEL.upsample:
             # models/models.py:869-873,933-940,1074-1083: the loss stays at the sampled resolution, the four accuracies are taken at
             # FULL resolution on the prediction warped back through the inverse grid (never-claimed pixels filled from their
-            # nearest claimed neighbour) against the original label map.  No gradient flows through this branch.
+            # nearest claimed neighbour) against the original label map.  No gradient flows through this branch.  The class of a
+            # pixel is one grid point's decision and its ground truth one read of y, so the counters are taken in one gather pass
+            # (ops.unwarp_accuracy) instead of unwarp_nearest + SegLoss on a (B,K,H,W) prediction.
             with torch.no_grad():
-                Hf, Wf = int(y.shape[2]), int(y.shape[3])
-                pred_full, _hole = ops.unwarp_nearest(pred.detach().contiguous(), grid.detach(), Hf, Wf)
-                y_hs = y[:, 0].long()
-                gt_hs = y_hs * cls[:, :, None] + (1 - y_hs) * (cfg.DATASET.num_class - 1)
-                full = ops.SegLoss.apply(pred_full, gt_hs.contiguous(), 5.0)
-                acc, accs = full[3], (full[4], full[5], full[6])
+                _counts, full = ops.unwarp_accuracy(head_cls.detach(), head_m.detach(), grid.detach(), y, cls)
+                acc, accs = full[0], (full[1], full[2], full[3])
         if joint:
             if not is_inference:
                 return loss, acc, edge_loss

@@ -1484,6 +1484,52 @@ def unwarp_labels(cls, m, grid, Hs, Ws):
     return labels, hole
 
 
+def unwarp_accuracy(cls, m, grid, y, cls_label, return_labels=False):
+    """The four full-resolution accuracies of MODEL.upsample for the C1 head (no autograd), without the (B,K,Hs,Ws) prediction, a class
+    map or a ground-truth tensor: the predicted class of a pixel is `unwarp_labels`'s, its ground truth `t = y.long()`,
+    `t * cls_label + (1 - t) * (K - 1)`, and the gather pass counts instead of storing (fs_unwarp_accuracy).  cls (B,K), m (B,h,w),
+    grid (B,h,w,2) as for unwarp_labels; y (B,Hs,Ws) or (B,1,Hs,Ws) the label mask at the output size; cls_label (B,) or (B,1).
+    Returns (counts (B,6) int64 = cls_fg, bin_fg, union_fg, cls_bg, bin_bg, union_bg per image, acc (4,) fp32 = acc, acc_bin_fg,
+    acc_cls_fbg, acc_bin_fbg as SegLoss's out[3:7]) and, with return_labels, the (B,Hs,Ws) int64 class map of unwarp_labels."""
+    B, K = cls.shape
+    _, h, w, _ = grid.shape
+    if tuple(m.shape) != (B, h, w):
+        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
+    if y.dim() == 4 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.dim() != 3 or y.shape[0] != B:
+        raise ValueError(f"y {tuple(y.shape)} must be (B, Hs, Ws) or (B, 1, Hs, Ws) with B = {B}")
+    Hs, Ws = int(y.shape[1]), int(y.shape[2])
+    if cls_label.dim() == 2 and cls_label.shape[1] == 1:
+        cls_label = cls_label[:, 0]
+    if tuple(cls_label.shape) != (B,):
+        raise ValueError(f"cls_label {tuple(cls_label.shape)} must be (B,) or (B, 1) with B = {B}")
+    counts = torch.empty(B, 6, device=cls.device, dtype=torch.int64)
+    acc = torch.empty(4, device=cls.device, dtype=torch.float32)
+    labels = torch.empty(B, Hs, Ws, device=cls.device, dtype=torch.int64) if return_labels else None
+    scratch = torch.empty(hip.query("fs_unwarp_accuracy_scratch_ints", B, h, w, Hs, Ws), device=cls.device, dtype=torch.int32)
+    hip.call("fs_unwarp_accuracy", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()),
+             hip.ptr(y.float().contiguous()), hip.ptr(cls_label.long().contiguous()), hip.ptr(counts), hip.ptr(acc), hip.ptr(labels),
+             hip.ptr(scratch), B, K, h, w, Hs, Ws)
+    return (counts, acc, labels) if return_labels else (counts, acc)
+
+
+def image_accuracies_from_counts(counts):
+    """(B,6) counts -> (B,4) fp32 per-image acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg (models/models.py:378-474): plain torch, any device."""
+    c = counts.to(torch.float32)
+    ufg, ubg = c[:, 2] + 1e-10, c[:, 5] + 1e-10
+    cls_fg, bin_fg, cls_bg, bin_bg = c[:, 0] / ufg, c[:, 1] / ufg, c[:, 3] / ubg, c[:, 4] / ubg
+    return torch.stack([cls_fg, bin_fg, cls_fg * 0.5 + cls_bg * 0.5, bin_fg * 0.5 + bin_bg * 0.5], 1)
+
+
+def accuracies_from_counts(counts):
+    """(B,6) counts (unwarp_accuracy's, on any device) -> (4,) fp32: the batch's four accuracies, the mean over its images of the fp32
+    per-image quotients -- fs_unwarp_accuracy's and SegLoss's arithmetic in plain torch."""
+    if counts.dim() != 2 or counts.shape[1] != 6:
+        raise ValueError(f"counts must be (B, 6), got {tuple(counts.shape)}")
+    return (image_accuracies_from_counts(counts).double().sum(0) / counts.shape[0]).float()
+
+
 # ----------------------------------------------------------------------------------------------
 # SegFormer pieces (tokens = NHWC rows)
 # ----------------------------------------------------------------------------------------------

@@ -355,6 +355,19 @@ def eval_step(module, batch):
     return out
 
 
+@torch.no_grad()
+def evaluate_step(module, batch, meter=None):
+    """Full-resolution scoring of one batch without the loss: module.evaluate on (X, Fp, Y, cls) (module.eval() by caller), the way
+    eval_step wraps forward.  Returns evaluate's (acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg, counts); a FullResMeter given as `meter`
+    takes the counts (no host read)."""
+    X, Fp, Y, cls = batch
+    out = module.evaluate(X[:, :3], Fp, Y, cls)
+    module.check_nan()
+    if meter is not None:
+        meter.update(out[4])
+    return out
+
+
 def synthetic_batch(B, H, W, seed=1, device="cuda"):
     """uniform RGB, gaze in [0.1,0.9), disc mask of radius 0.15 H at the gaze."""
     g = torch.Generator().manual_seed(seed)
@@ -416,6 +429,44 @@ class DeviceMeter:
         tot = tot.cpu()
         n = float(tot[-1])
         return {k: (float(tot[i]) / n if n > 0 else float("nan")) for i, k in enumerate(self.names)}
+
+
+class FullResMeter:
+    """Dataset-level full-resolution scores from the per-image counts of module.evaluate / ops.unwarp_accuracy (SURVEY.md §8(f)-2:
+    'a single global IoU').  `update(counts)` adds a batch's (B,6) int64 counts into device-resident sums -- the six counters, the four
+    per-image accuracies (fp64) and the number of images -- without a host read; `result(reduce=True)` makes ONE all-reduce over the
+    ranks and ONE host read.  It returns the reference's mean-of-images accuracies (acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg: what
+    averaging forward's per-batch values weighted by batch size gives) beside the dataset-level iou_fg = sum cls_fg / sum union_fg and
+    iou_bin_fg = sum bin_fg / sum union_fg, in which a large instance weighs by its pixels, plus the raw `counts` and `images`."""
+
+    NAMES = ("acc", "acc_bin_fg", "acc_cls_fbg", "acc_bin_fbg")
+
+    def __init__(self, device):
+        self.counts = torch.zeros(6, device=device, dtype=torch.int64)
+        self.sums = torch.zeros(5, device=device, dtype=torch.float64)           # four accuracy sums, then the image count
+
+    def update(self, counts):
+        from . import ops
+        if counts.dim() != 2 or counts.shape[1] != 6:
+            raise ValueError(f"counts must be (B, 6), got {tuple(counts.shape)}")
+        counts = counts.to(device=self.counts.device, dtype=torch.int64)
+        self.counts.add_(counts.sum(0))
+        self.sums[:4].add_(ops.image_accuracies_from_counts(counts).double().sum(0))
+        self.sums[4:].add_(float(counts.shape[0]))
+
+    def result(self, reduce=True):
+        # one fp64 vector carries everything: each int64 sum as two 32-bit halves, whose sums over the ranks stay exact in fp64
+        tot = torch.cat([(self.counts >> 32).double(), (self.counts & 0xFFFFFFFF).double(), self.sums])
+        if reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(tot, op=dist.ReduceOp.SUM)
+        tot = tot.cpu().tolist()
+        c = [(int(tot[q]) << 32) + int(tot[6 + q]) for q in range(6)]
+        n = tot[16]
+        res = {k: (tot[12 + i] / n if n > 0 else float("nan")) for i, k in enumerate(self.NAMES)}
+        res["iou_fg"] = c[0] / c[2] if c[2] > 0 else 0.0                         # an empty union scores 0, as the per-image quotients do
+        res["iou_bin_fg"] = c[1] / c[2] if c[2] > 0 else 0.0
+        res["counts"], res["images"] = c, int(n)
+        return res
 
 
 # ----------------------------------------------------------------------------------------------

@@ -108,6 +108,19 @@ int fs_fill_nearest(float* vals, const int* owner, int* scratch, int B, int C, i
 long fs_unwarp_labels_scratch_ints(int B, int h, int w, int Hs, int Ws);
 int fs_unwarp_labels(const float* cls, const float* m, const float* grid, long long* labels, unsigned char* hole, int* scratch, int B, int K,
                      int h, int w, int Hs, int Ws, fs_stream_t stream);
+/* The four full-resolution accuracies of MODEL.upsample (models/models.py:378-474,869-873,1074-1083) without the class map: the
+ * predicted class of pixel (b,v,u) is fs_unwarp_labels' (same kernels up to the gather), its ground truth is t = (long)y[b,v,u],
+ * gt = t * cls_label[b] + (1 - t) * (K - 1) (:968), and the gather pass counts instead of storing.  y (B,Hs,Ws) fp32 label mask,
+ * cls_label (B) int64.  counts (B,6) int64 = cls_fg, bin_fg, union_fg, cls_bg, bin_bg, union_bg per image, background = K - 1, as
+ * fs_seg_loss_fwd counts them; acc (4) = acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg in its arithmetic (fp32 quotients with 1e-10
+ * added to the unions, summed over the images in a fixed order, / B).  labels (B,Hs,Ws) int64, nullable: fs_unwarp_labels' map.
+ * Counts are integer sums of per-workgroup records (plain stores, no atomics, scratch not zeroed): bit-reproducible in every mode.
+ * scratch = fs_unwarp_accuracy_scratch_ints(B, h, w, Hs, Ws) ints, 16-byte aligned.  FS_ERR_ARG as fs_unwarp_labels, and for
+ * Hs * Ws within 1024 (one workgroup's pixels) of 2^31. */
+long fs_unwarp_accuracy_scratch_ints(int B, int h, int w, int Hs, int Ws);
+int fs_unwarp_accuracy(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label,
+                       long long* counts, float* acc, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws,
+                       fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
