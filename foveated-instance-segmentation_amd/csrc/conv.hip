@@ -7,7 +7,7 @@
 //   bwd-data  : dX[m][n] = sum_{tap,co} dY[(pix(m)+pad-tap)/s][co] * W[tap][n][co] M=B*H*W   N=Cin
 //   bwd-weight: dW[tap][ci][co] = sum_pix X[pix+tap][ci] * dY[pix][co]             K=B*Ho*Wo (split)
 //
-// Which kernel runs (precision mode g_conv_precision: 0 = f32, 1 = bf16x3, 2 = f16x2):
+// Which kernel runs (forward / bwd-data: plan_conv below; precision mode g_conv_precision: 0 = f32, 1 = bf16x3, 2 = f16x2):
 //   3x3 stride 1 pad 1, aligned channels, modes 1/2, scratch given : conv_halo.hip (fwd, bwd-data), conv_wgrad.hip (bwd-weight)
 //   other multi-tap filters / strided bwd-data sub-problems, modes 1/2 : conv_tapset.hip; bwd-weight per tap class: conv_wgrad.hip
 //   1x1, stride >= filter size, single-tap sub-problems, modes 1/2 : conv_igemm_split_kernel<P> (this file)
@@ -250,7 +250,6 @@ struct AffArgs {
   float* stats;   // optional [nx][Cd][2] per-workgroup column sums / sums of squares of the STORED values
 };
 
-static thread_local hipStream_t a_stream = nullptr;   // host: stream of the launch being issued
 // 0 = fp32 MFMA (v_mfma_f32_32x32x2_f32), 1 = split-precision bf16x3 (six v_mfma_f32_32x32x16_bf16 per product),
 // 2 = f16x2 (three v_mfma_f32_32x32x16_f16 per product on scaled operands) in the 3x3 stride-1 kernels, bf16x3 elsewhere.
 // Default 1 = bf16x3: operands carry the reference's full 24 significand bits (the mode bench.py's headline and the parity claims are
@@ -303,7 +302,7 @@ __global__ __launch_bounds__(256) void conv_igemm_affine_kernel(AffArgs a) {
       roff[i] = (int)m * a.Cs + 4 * q;
       rmask[i] = 1u;
     } else if (m < M) {
-      const unsigned mu = (unsigned)m, hw = (unsigned)(a.Hq * a.Wq);       // M < 2^30: the source is below 4 GB (aligned_ok)
+      const unsigned mu = (unsigned)m, hw = (unsigned)(a.Hq * a.Wq);       // M < 2^30: the source is below 4 GB (plan_conv)
       const int b = (int)(mu / hw);
       const int rem = (int)(mu - (unsigned)b * hw);
       const int py = rem / a.Wq, px = rem - py * a.Wq;
@@ -547,7 +546,7 @@ __global__ __launch_bounds__(256) void conv_igemm_split_kernel(AffArgs a) {
       roff[i] = (int)m * a.Cs + 4 * q;
       rmask[i] = 1u;
     } else if (m < M) {
-      const unsigned mu = (unsigned)m, hw = (unsigned)(a.Hq * a.Wq);       // M < 2^30: the source is below 4 GB (aligned_ok)
+      const unsigned mu = (unsigned)m, hw = (unsigned)(a.Hq * a.Wq);       // M < 2^30: the source is below 4 GB (plan_conv)
       const int b = (int)(mu / hw);
       const int rem = (int)(mu - (unsigned)b * hw);
       const int py = rem / a.Wq, px = rem - py * a.Wq;
@@ -983,37 +982,61 @@ __global__ __launch_bounds__(256) void zero_classes_kernel(float* __restrict__ d
   }
 }
 
-int launch_affine_one(AffArgs& a) {
+int launch_affine_one(AffArgs& a, hipStream_t stream) {
   const long M = (long)a.B * a.Hq * a.Wq;
   a.nx = cdiv(M, 128);
   a.ny = cdiv(a.Cd, BN);
   // MT=2 (256-row tiles) needs 84 KB of LDS = one workgroup per CU and measured 20-25 % slower.
   if (g_conv_precision == 2)
-    hipLaunchKernelGGL(conv_igemm_split_kernel<fs_split::PrecF16>, dim3(a.nx * a.ny), dim3(256), 0, a_stream, a);
+    hipLaunchKernelGGL(conv_igemm_split_kernel<fs_split::PrecF16>, dim3(a.nx * a.ny), dim3(256), 0, stream, a);
   else if (g_conv_precision == 1)
-    hipLaunchKernelGGL(conv_igemm_split_kernel<fs_split::PrecX3>, dim3(a.nx * a.ny), dim3(256), 0, a_stream, a);
+    hipLaunchKernelGGL(conv_igemm_split_kernel<fs_split::PrecX3>, dim3(a.nx * a.ny), dim3(256), 0, stream, a);
   else
-    hipLaunchKernelGGL(conv_igemm_affine_kernel<1>, dim3(a.nx * a.ny), dim3(256), 0, a_stream, a);
+    hipLaunchKernelGGL(conv_igemm_affine_kernel<1>, dim3(a.nx * a.ny), dim3(256), 0, stream, a);
   FS_LAUNCH_CHECK();
   return FS_OK;
 }
 
-// The halo-tiled 3x3 kernel (conv_halo.hip) runs when the split-precision mode is on, the shape qualifies and the
-// caller handed over enough scratch for the weight pack.
-long halo_pack_bytes(int Cs, int Cd) { return fs_halo_pack_bytes(g_conv_precision, Cs, Cd); }
-bool use_halo(const ConvArgs& c) {
-  return g_conv_precision >= 1 && c.ws_ != nullptr && fs_halo_eligible(c.Hd, c.Wd, c.Cs, c.Cd, c.R, c.S, c.stride, c.pad, c.dil) &&
-         c.Hs == c.Hd && c.Ws == c.Wd && c.ws_bytes_ >= halo_pack_bytes(c.Cs, c.Cd) &&
-         (size_t)c.B * c.Hd * c.Wd * c.Cd * 4 < 4294967000UL &&      // 32-bit store offsets in the epilogue
-         (size_t)c.B * c.Hs * c.Ws * c.Cs * 4 < 4294967000UL;        // 32-bit buffer offsets of the source (fs_halo_conv3x3 rejects larger)
-}
+// ---- kernel selection for forward / bwd-data: plan_conv decides, launch_conv and every host-side query read its answer ------------------
+// Every kernel but the generic one addresses a tensor with 32-bit BYTE offsets (raw buffer resources, 32-bit store offsets in the
+// epilogues), so it takes tensors below 4 GB only -- 2^30 elements, not 2^31.
+bool fits32(size_t elements) { return elements * 4 < 4294967000UL; }
+size_t src_elems(const ConvArgs& c) { return (size_t)c.B * c.Hs * c.Ws * c.Cs; }
+size_t dst_elems(const ConvArgs& c) { return (size_t)c.B * c.Hd * c.Wd * c.Cd; }
 
-// ... and its F(2,3) variant (conv_wino.hip) where the shape additionally allows the pair tiling.
-bool use_wino(const ConvArgs& c) {
-  return use_halo(c) && fs_wino_eligible(g_conv_precision, c.B, c.Hd, c.Wd, c.Cs, c.Cd) && c.ws_bytes_ >= fs_wino_pack_bytes(g_conv_precision, c.Cs, c.Cd);
-}
+// One value per launch path of launch_conv.
+enum Route { GENERIC, PLAIN, HALO, WINO_F23, WINO_F43, TAPSET_FWD, TAPSET_BWD1, POINTWISE, GATHER, SCATTER, S2FWD, S2BWD, PARITY };
+// What fs_conv2d_kernel_choice reports for a route (include/fovealseg.h) and whether its scratch is ONE weight pack that depends on
+// (w, shape, precision mode) only.  SCATTER and PARITY re-pack ws tap by tap / class by class: no pack outlives the call.  PARITY reports
+// 3 where its multi-tap classes run on the tap-class kernel.
+struct RouteInfo { int family; bool persistent; };
+constexpr RouteInfo ROUTE_INFO[] = {
+    /* GENERIC */ {0, false},   /* PLAIN */ {1, false},      /* HALO */ {2, true},      /* WINO_F23 */ {5, true}, /* WINO_F43 */ {8, true},
+    /* TAPSET_FWD */ {3, true}, /* TAPSET_BWD1 */ {3, true}, /* POINTWISE */ {4, true}, /* GATHER */ {4, true},   /* SCATTER */ {1, false},
+    /* S2FWD */ {7, true},      /* S2BWD */ {6, true},       /* PARITY */ {1, false}};
 
-// Everything else that is channel-aligned, undilated and has scratch goes to the tap-class kernel (conv_tapset.hip).
+// Extras a caller can ask a conv launch to fuse into its epilogue.
+enum : unsigned {
+  EX_BNSUM = 1u,        // bwd-data: BatchNorm-backward column sums of the layer that produced x (FsBnSums::y ...)
+  EX_ADDEND = 2u,       // bwd-data: a second gradient joins dX; forward: dst = addend + DropPath(Dropout(conv + bias))
+  EX_AFFINE_ACT = 4u    // forward (inference): affine + residual + activation
+};
+
+struct ConvPlan {
+  Route route;
+  int family;          // public id 0-8
+  bool persistent;     // ws is one weight pack a caller may keep across calls
+  int slabs;           // rows of the [.][Cd][2] slab the route writes to stats_: forward BatchNorm partials; bwd-data: the EX_BNSUM sums
+  unsigned fuses;      // EX_* the route's kernel can fuse
+  bool tapset;         // the tap-class kernel is available to this problem (PARITY: its multi-tap classes take it)
+  bool ok;             // every extra the caller asked for is in `fuses`
+};
+
+// The kernel families with a pre-split weight pack: shape eligibility (batch-independent, so that fs_conv2d_workspace_bytes can ask) and
+// pack bytes for this problem.  The kernel A/B switches of -DFS_EXPERIMENTS builds are read here and nowhere else.
+enum Family { F_HALO, F_WINO, F_TAPSET, F_POINTWISE, F_GATHER, F_SCATTER, F_S2FWD, F_S2BWD, N_FAMILIES };
+struct FamilyFit { bool shape_ok; long pack; };
+
 bool tapset_shape_ok(int Cs, int Cd, int R, int S, int stride, int dil) {
   const int cr = stride < R ? stride : R, cs = stride < S ? stride : S;
   // 1x1 filters have no tap reuse: measured slower than conv_igemm_split_kernel (43 vs 55 TF on 64->256 @ 80x80), not routed here
@@ -1023,63 +1046,117 @@ bool tapset_shape_ok(int Cs, int Cd, int R, int S, int stride, int dil) {
   return dil == 1 && R * S > 1 && Cs % 4 == 0 && Cd % 4 == 0 && Cs >= 16 && cr * cs <= 9 &&
          ((R + stride - 1) / stride) * ((S + stride - 1) / stride) <= 64;
 }
-long tapset_pack_bytes(int Cs, int Cd, int taps) { return fs_tapset_pack_bytes(g_conv_precision, Cs, Cd, taps); }
-bool use_tapset(const ConvArgs& c) {
-  return g_conv_precision >= 1 && c.ws_ != nullptr && tapset_shape_ok(c.Cs, c.Cd, c.R, c.S, c.stride, c.dil) &&
-         c.ws_bytes_ >= tapset_pack_bytes(c.Cs, c.Cd, c.R * c.S) && (size_t)c.B * c.Hd * c.Wd * c.Cd * 4 < 4294967000UL &&
-         (size_t)c.B * c.Hs * c.Ws * c.Cs * 4 < 4294967000UL;        // the tap-class kernel addresses the source with 32-bit byte offsets too
+
+void conv_families(const ConvArgs& c, FamilyFit (&f)[N_FAMILIES]) {
+  static const bool s2fwd_on = FS_ENV_INT("FS_S2FWD", 1) != 0, s2bwd_on = FS_ENV_INT("FS_S2BWD", 1) != 0;
+  static const bool pointwise_on = FS_ENV_INT("FS_POINTWISE", 1) != 0, gather_on = FS_ENV_INT("FS_PW_GATHER", 1) != 0;
+  const int m = g_conv_precision;
+  const bool fwd = !c.transposed, same_size = c.Hs == c.Hd && c.Ws == c.Wd;
+  // 3x3 / stride 1 / pad 1: halo-tiled kernel (conv_halo.hip) and its F(2,3) / F(4,3) variants (conv_wino*.hip; whether the pair tiling
+  // fits also depends on B: plan_conv asks fs_wino_eligible)
+  const bool halo = same_size && fs_halo_eligible(c.Hd, c.Wd, c.Cs, c.Cd, c.R, c.S, c.stride, c.pad, c.dil);
+  f[F_HALO] = {halo, fs_halo_pack_bytes(m, c.Cs, c.Cd)};
+  f[F_WINO] = {halo, fs_wino_pack_bytes(m, c.Cs, c.Cd)};      // 4 components per filter row
+  // other multi-tap, undilated filters: tap-class kernel (conv_tapset.hip)
+  f[F_TAPSET] = {tapset_shape_ok(c.Cs, c.Cd, c.R, c.S, c.stride, c.dil), fs_tapset_pack_bytes(m, c.Cs, c.Cd, c.R * c.S)};
+  // 1x1 / stride 1: GEMM kernel with pre-split weights (conv_pointwise.hip)
+  f[F_POINTWISE] = {pointwise_on && same_size && fs_pointwise_eligible(c.Cs, c.Cd, c.R, c.S, c.stride, c.pad, c.dil),
+                    fs_pointwise_pack_bytes(m, c.Cs, c.Cd)};
+  // stride >= filter layers (3x3 / stride 4, 1x1 / stride 4): forward as that GEMM over gathered rows, bwd-data as one GEMM per tap whose
+  // rows are scattered to the tap's residue class of dX
+  f[F_GATHER] = {gather_on && fwd && fs_pointwise_gather_eligible(c.Cs, c.Cd, c.R, c.S, c.stride, c.dil),
+                 fs_pointwise_pack_bytes(m, c.R * c.S * c.Cs, c.Cd)};
+  f[F_SCATTER] = {gather_on && !fwd && fs_pointwise_scatter_eligible(c.Cd, c.Cs, c.R, c.S, c.stride, c.dil),
+                  fs_pointwise_pack_bytes(m, c.Cs, c.Cd)};
+  // 3x3 / stride 2 / pad 1: forward with the four input parity planes in one LDS refill per chunk (conv_s2fwd.hip), bwd-data with all
+  // four output parities in one launch (conv_s2bwd.hip)
+  f[F_S2FWD] = {s2fwd_on && fwd && fs_s2fwd_eligible(c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd, c.R, c.S, c.stride, c.pad, c.dil),
+                fs_s2fwd_pack_bytes(m, c.Cs, c.Cd)};
+  f[F_S2BWD] = {s2bwd_on && !fwd && fs_s2bwd_eligible(c.Hd, c.Wd, c.Cd, c.Hs, c.Ws, c.Cs, c.R, c.S, c.stride, c.pad, c.dil),
+                fs_s2bwd_pack_bytes(m, c.Cd, c.Cs)};
 }
 
-// forward of 3x3 / stride 2 / pad 1 layers: the four input parity planes in one LDS refill per chunk (conv_s2fwd.hip)
-static const bool g_s2fwd = FS_ENV_INT("FS_S2FWD", 1) != 0;      // kernel A/B builds only
-bool use_s2fwd(const ConvArgs& c) {
-  return g_s2fwd && g_conv_precision >= 1 && !c.transposed && c.ws_ != nullptr && c.bn_ == nullptr &&
-         fs_s2fwd_eligible(c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd, c.R, c.S, c.stride, c.pad, c.dil) &&
-         c.ws_bytes_ >= fs_s2fwd_pack_bytes(g_conv_precision, c.Cs, c.Cd) &&
-         (size_t)c.B * c.Hd * c.Wd * c.Cd * 4 < 4294967000UL && (size_t)c.B * c.Hs * c.Ws * c.Cs * 4 < 4294967000UL;
+// THE dispatch decision for one forward / bwd-data problem under the current precision mode with c.ws_bytes_ of scratch; `want` = the
+// EX_* extras the caller asks for.  First match wins (DESIGN.md section 4 has the reasons):
+//   1. GENERIC    channel counts that are no multiples of 4, more than 32 taps, or a source of 4 GB and more
+//   -- the split-precision families (modes 1 / 2, scratch that holds the family's pack, destination below 4 GB too) --
+//   2. S2FWD      3x3 / stride 2 / pad 1 forward
+//   3. WINO_F43, WINO_F23, HALO   3x3 / stride 1 / pad 1: minimal filtering where the width allows it, else the plain halo kernel
+//   4. TAPSET_FWD, TAPSET_BWD1    other multi-tap filters, forward at any stride and bwd-data at stride 1
+//   5. POINTWISE  1x1 / stride 1
+//   6. GATHER     forward, stride >= filter
+//   -- no family fits --
+//   7. PLAIN      forward at any stride, bwd-data at stride 1: the aligned implicit GEMM of this file splits weights in flight
+//   8. S2BWD      3x3 / stride 2 / pad 1 bwd-data
+//   9. SCATTER    bwd-data, stride >= filter
+//  10. PARITY     any other strided bwd-data: one dense sub-problem per output parity class
+ConvPlan plan_conv(const ConvArgs& c, unsigned want) {
+  const int m = g_conv_precision;
+  const bool fwd = !c.transposed;
+  FamilyFit f[N_FAMILIES];
+  conv_families(c, f);
+  const bool split = m >= 1 && c.ws_ != nullptr && fits32(dst_elems(c));
+  auto has = [&](Family k) { return split && f[k].shape_ok && c.ws_bytes_ >= f[k].pack; };
+  Route r;
+  if (c.Cs % 4 != 0 || c.Cd % 4 != 0 || c.R * c.S > 32 || !fits32(src_elems(c))) r = GENERIC;
+  else if (has(F_S2FWD)) r = S2FWD;
+  else if (has(F_HALO)) {
+    const bool wino = has(F_WINO) && fs_wino_eligible(m, c.B, c.Hd, c.Wd, c.Cs, c.Cd);
+    r = !wino ? HALO : fs_wino_takes_f43(m, c.B, c.Hd, c.Wd, c.Cs, c.Cd) ? WINO_F43 : WINO_F23;
+  } else if (has(F_TAPSET) && (fwd || c.stride == 1)) r = fwd ? TAPSET_FWD : TAPSET_BWD1;
+  else if (has(F_POINTWISE)) r = POINTWISE;
+  else if (has(F_GATHER)) r = GATHER;
+  else if (fwd || c.stride == 1) r = PLAIN;
+  else if (has(F_S2BWD)) r = S2BWD;
+  else if (has(F_SCATTER) && c.stride * c.stride <= 32) r = SCATTER;      // one bit per residue class in the zero-fill's mask
+  else r = PARITY;
+
+  // the kernels of this file and the 1x1 GEMM kernels write one slab row per 128 output rows
+  ConvPlan p{r, ROUTE_INFO[r].family, ROUTE_INFO[r].persistent, cdiv((long)c.B * c.Hd * c.Wd, 128), 0u, has(F_TAPSET), false};
+  switch (r) {
+    case S2FWD: p.slabs = fs_s2fwd_slabs(c.B, c.Hd, c.Wd); break;
+    case HALO: p.slabs = fs_halo_stats_slabs(c.B, c.Hd, c.Wd); break;
+    case WINO_F23:
+    case WINO_F43:
+      p.slabs = fs_wino_stats_slabs(m, c.B, c.Hd, c.Wd, c.Cs, c.Cd);
+      p.fuses = fwd ? EX_AFFINE_ACT : EX_BNSUM | EX_ADDEND;      // the row epilogue of the F(2,3) / F(4,3) kernels
+      break;
+    case TAPSET_FWD: p.slabs = fs_tapset_slabs(c.B, c.Hd, c.Wd, cdiv(c.R, c.stride), cdiv(c.S, c.stride)); break;
+    case POINTWISE: p.fuses = fwd ? EX_ADDEND : EX_BNSUM | EX_ADDEND; break;
+    case S2BWD:
+      p.slabs = fs_s2bwd_stats_slabs(c.B, c.Hs, c.Ws);
+      p.fuses = EX_BNSUM | EX_ADDEND;
+      break;
+    case PARITY: if (p.tapset) p.family = 3; break;
+    default: break;
+  }
+  p.ok = (want & ~p.fuses) == 0u;
+  return p;
 }
 
-// bwd-data of 3x3 / stride 2 / pad 1 layers: all four output parities in one launch (conv_s2bwd.hip)
-static const bool g_s2bwd = FS_ENV_INT("FS_S2BWD", 1) != 0;      // kernel A/B builds only
-bool use_s2bwd(const ConvArgs& c) {
-  return g_s2bwd && g_conv_precision >= 1 && c.transposed && c.ws_ != nullptr && c.bias == nullptr &&
-         fs_s2bwd_eligible(c.Hd, c.Wd, c.Cd, c.Hs, c.Ws, c.Cs, c.R, c.S, c.stride, c.pad, c.dil) &&
-         c.ws_bytes_ >= fs_s2bwd_pack_bytes(g_conv_precision, c.Cd, c.Cs) &&
-         (size_t)c.B * c.Hd * c.Wd * c.Cd * 4 < 4294967000UL && (size_t)c.B * c.Hs * c.Ws * c.Cs * 4 < 4294967000UL;
+int launch_generic(const ConvArgs& c) {
+  if (c.stats_ != nullptr) return FS_ERR_ARG;      // no BatchNorm partials in its epilogue
+  dim3 grid(cdiv((long)c.B * c.Hd * c.Wd, BM), cdiv(c.Cd, BN));
+  if (c.Cs % 4 == 0 && c.Cd % 4 == 0)
+    hipLaunchKernelGGL(conv_igemm_kernel<true>, grid, dim3(256), 0, c.stream_, c);
+  else
+    hipLaunchKernelGGL(conv_igemm_kernel<false>, grid, dim3(256), 0, c.stream_, c);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
 }
 
-// 1x1 / stride-1 layers go to the GEMM kernel with pre-split weights (conv_pointwise.hip) when the caller handed over its scratch.
-static const bool g_pointwise = FS_ENV_INT("FS_POINTWISE", 1) != 0;
-bool use_pointwise(const ConvArgs& c) {
-  return g_pointwise && g_conv_precision >= 1 && c.ws_ != nullptr && fs_pointwise_eligible(c.Cs, c.Cd, c.R, c.S, c.stride, c.pad, c.dil) &&
-         c.Hs == c.Hd && c.Ws == c.Wd && c.ws_bytes_ >= fs_pointwise_pack_bytes(g_conv_precision, c.Cs, c.Cd) &&
-         (size_t)c.B * c.Hd * c.Wd * c.Cd * 4 < 4294967000UL && (size_t)c.B * c.Hs * c.Ws * c.Cs * 4 < 4294967000UL;
+// dX pixels (y, x) whose class (y % stride, x % stride) is in `classes` <- 0: the classes no tap reaches (stride > filter size: 7 of 16 for
+// 3x3 stride 4, 15 of 16 for 1x1 stride 4), one store-only launch instead of one conv launch each (1x1 stride 4, 1.57 GB of dX: 1.13 -> 0.55 ms)
+int zero_classes(const ConvArgs& c, unsigned classes) {
+  if (classes == 0u) return FS_OK;
+  const long n4 = (long)c.B * c.Hd * c.Wd * (c.Cd / 4);
+  long blocks = (n4 + 255) / 256;
+  if (blocks > 65536) blocks = 65536;
+  hipLaunchKernelGGL(zero_classes_kernel, dim3((unsigned)blocks), dim3(256), 0, c.stream_, c.dst, n4, c.Hd, c.Wd, c.Cd / 4, c.stride, classes);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
 }
 
-// forward of stride >= filter layers (3x3 / stride 4, 1x1 / stride 4): the 1x1 GEMM kernel over gathered rows (conv_pointwise.hip)
-static const bool g_pw_gather = FS_ENV_INT("FS_PW_GATHER", 1) != 0;      // kernel A/B builds only
-bool use_pw_gather(const ConvArgs& c) {
-  return g_pw_gather && g_conv_precision >= 1 && !c.transposed && c.ws_ != nullptr && c.bn_ == nullptr &&
-         fs_pointwise_gather_eligible(c.Cs, c.Cd, c.R, c.S, c.stride, c.dil) &&
-         c.ws_bytes_ >= fs_pointwise_pack_bytes(g_conv_precision, c.R * c.S * c.Cs, c.Cd) &&
-         (size_t)c.B * c.Hd * c.Wd * c.Cd * 4 < 4294967000UL && (size_t)c.B * c.Hs * c.Ws * c.Cs * 4 < 4294967000UL;
-}
-
-// ... and their bwd-data: one 1x1 GEMM per tap, rows scattered to the tap's residue class of dX
-bool use_pw_scatter(const ConvArgs& c) {
-  return g_pw_gather && g_conv_precision >= 1 && c.transposed && c.ws_ != nullptr && c.bias == nullptr && c.bn_ == nullptr &&
-         c.stride * c.stride <= 32 && fs_pointwise_scatter_eligible(c.Cd, c.Cs, c.R, c.S, c.stride, c.dil) &&
-         c.ws_bytes_ >= fs_pointwise_pack_bytes(g_conv_precision, c.Cs, c.Cd) &&
-         (size_t)c.B * c.Hd * c.Wd * c.Cd * 4 < 4294967000UL && (size_t)c.B * c.Hs * c.Ws * c.Cs * 4 < 4294967000UL;
-}
-
-// The channel-aligned kernels (plain / halo / tap-class) address the SOURCE tensor with 32-bit BYTE offsets into a raw buffer
-// resource (AffArgs::src_bytes), so the source must stay below 4 GB -- 2^30 elements, not 2^31; larger problems take the
-// 64-bit-indexed conv_igemm_kernel.
-bool aligned_ok(const ConvArgs& c) {
-  return c.Cs % 4 == 0 && c.Cd % 4 == 0 && c.R * c.S <= 32 && (size_t)c.B * c.Hs * c.Ws * c.Cs * 4 < 4294967000UL;
-}
-int run_tapset(const FsTapsetProblem& p, hipStream_t stream) { return fs_tapset_conv(g_conv_precision, p, stream); }
 FsTapsetProblem tapset_base(const ConvArgs& c) {
   FsTapsetProblem p{};
   p.src = c.src; p.w = c.w; p.bias = c.bias; p.dst = c.dst; p.stats = c.stats_; p.ws = c.ws_; p.w_amax = c.w_amax_;
@@ -1087,94 +1164,15 @@ FsTapsetProblem tapset_base(const ConvArgs& c) {
   p.Cin = c.transposed ? c.Cd : c.Cs; p.Cout = c.transposed ? c.Cs : c.Cd; p.R = c.R; p.S = c.S;
   p.transposed = c.transposed;
   p.drop_scale = c.drop_scale; p.drop_thresh = c.drop_thresh; p.drop_key = c.drop_key;
+  p.Hq = c.Hd; p.Wq = c.Wd; p.os = 1; p.oy0 = 0; p.ox0 = 0; p.sm = 1;
   return p;
 }
-int launch_tapset_forward(const ConvArgs& c) {
-  FsTapsetProblem p = tapset_base(c);
-  p.Hq = c.Hd; p.Wq = c.Wd; p.os = 1; p.oy0 = 0; p.ox0 = 0; p.sm = c.stride;
-  const int st = c.stride;
-  p.ncls = 0;
-  for (int r0 = 0; r0 < st && r0 < c.R; ++r0)
-    for (int s0 = 0; s0 < st && s0 < c.S; ++s0)
-      p.cls[p.ncls++] = FsTapClass{r0 - c.pad, s0 - c.pad, (c.R - r0 + st - 1) / st, (c.S - s0 + st - 1) / st, r0, st, s0, st};
-  return run_tapset(p, c.stream_);
-}
 
-// bwd-data extras (BatchNorm-backward sums / addend) outside the 3x3 stride-1 family: the kernel launch_affine reaches for this problem is
-// the 1x1 GEMM or the one-launch stride-2 kernel (round 5).  Same predicates, same order as the dispatch below.
-bool bnsum_beyond_wino(const ConvArgs& c) {
-  // forward: only the residual form of a 1x1 layer (addend, no sums, no inference epilogue) on the 1x1 GEMM kernel
-  if (!c.transposed)
-    return c.bn_ != nullptr && c.bn_->y == nullptr && c.bn_->ep_scale == nullptr && c.bn_->add_src != nullptr && c.stats_ == nullptr &&
-           use_pointwise(c) && !use_wino(c) && !use_halo(c) && !use_s2fwd(c) && !use_tapset(c);
-  if (use_s2fwd(c)) return false;
-  if (c.stride == 1 && use_tapset(c) && !use_halo(c)) return false;
-  if (use_wino(c) || use_halo(c)) return false;
-  if (use_pointwise(c)) return true;
-  if (use_pw_gather(c) || c.stride == 1) return false;
-  return use_s2bwd(c);
-}
-
-int launch_affine(const ConvArgs& c, long M) {
-  AffArgs a{c.src, c.w, c.bias, c.dst, c.B, c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd, c.R, c.S, c.stride, c.pad, c.dil, c.transposed,
-            c.drop_scale, c.drop_thresh, c.drop_key,
-            (unsigned)((size_t)c.B * c.Hs * c.Ws * c.Cs * 4), (unsigned)((size_t)c.R * c.S * c.Cs * c.Cd * 4),
-            (size_t)c.B * c.Hd * c.Wd * c.Cd * 4 < 4294967000UL ? (unsigned)((size_t)c.B * c.Hd * c.Wd * c.Cd * 4) : 0u,
-            c.Hd, c.Wd, 1, 0, 0, 0, 0, 1, c.R, c.S, c.pad, c.pad, 0, 0, c.stats_};
-  a_stream = c.stream_;
-  (void)M;
-  if (use_s2fwd(c))
-    return fs_s2fwd_conv(g_conv_precision, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd,
-                         c.drop_scale, c.drop_thresh, c.drop_key, c.stream_);
-  if (!c.transposed && use_tapset(c) && !use_halo(c)) return launch_tapset_forward(c);
-  if (c.transposed && c.stride == 1 && use_tapset(c) && !use_halo(c)) {
-    FsTapsetProblem p = tapset_base(c);
-    p.Hq = c.Hd; p.Wq = c.Wd; p.os = 1; p.oy0 = 0; p.ox0 = 0; p.sm = 1;
-    p.ncls = 1;
-    p.cls[0] = FsTapClass{c.pad - (c.R - 1), c.pad - (c.S - 1), c.R, c.S, c.R - 1, -1, c.S - 1, -1};
-    return run_tapset(p, c.stream_);
-  }
-  if (use_wino(c))
-    return fs_wino_conv3x3(g_conv_precision, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cs, c.Cd,
-                           c.transposed ? c.Cd : c.Cs, c.transposed ? c.Cs : c.Cd, c.transposed, c.drop_scale, c.drop_thresh, c.drop_key, c.bn_, c.stream_);
-  if (c.bn_ != nullptr && !bnsum_beyond_wino(c)) return FS_ERR_ARG;        // the caller asked for fused sums on a shape fs_conv2d_bwd_data_bnsum_slabs reported 0 for
-  if (use_halo(c))
-    return fs_halo_conv3x3(g_conv_precision, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cs, c.Cd,
-                           c.transposed ? c.Cd : c.Cs, c.transposed ? c.Cs : c.Cd, c.transposed, c.drop_scale, c.drop_thresh, c.drop_key,
-                           c.stream_);
-  if (use_pointwise(c))
-    return fs_pointwise_conv(g_conv_precision, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, (long)c.B * c.Hd * c.Wd, c.Cs, c.Cd,
-                             c.transposed ? c.Cd : c.Cs, c.transposed ? c.Cs : c.Cd, c.transposed, c.drop_scale, c.drop_thresh, c.drop_key,
-                             c.bn_, c.stream_);
-  if (use_pw_gather(c))
-    return fs_pointwise_gather_conv(g_conv_precision, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd,
-                                    c.R, c.S, c.stride, c.pad, c.drop_scale, c.drop_thresh, c.drop_key, c.stream_);
-  if ((!c.transposed || c.stride == 1) && fs_ws_mode_tls != 0) return FS_ERR_ARG;      // the plain kernel has no weight pack
-  if (!c.transposed || c.stride == 1) return launch_affine_one(a);
-  if (use_s2bwd(c))
-    return fs_s2bwd_conv(g_conv_precision, c.src, c.w, c.dst, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cd, c.Hs, c.Ws, c.Cs, c.bn_, c.stats_, c.stream_);
-  // stride>1 bwd-data: one dense sub-problem per output parity class (oy0, ox0).  dX pixel y receives
-  // tap r iff (y + pad - r) % stride == 0, i.e. r = r0 + stride*t with r0 = (oy0 + pad) % stride, and then
-  // reads dY row (y + pad - r)/stride = py + (oy0 + pad - r0)/stride - t.
+// stride>1 bwd-data: one dense sub-problem per output parity class (oy0, ox0).  dX pixel y receives
+// tap r iff (y + pad - r) % stride == 0, i.e. r = r0 + stride*t with r0 = (oy0 + pad) % stride, and then
+// reads dY row (y + pad - r)/stride = py + (oy0 + pad - r0)/stride - t.
+int launch_parity(const ConvArgs& c, const AffArgs& a, bool tapset) {
   const int st = c.stride;
-  if (fs_ws_mode_tls != 0) return FS_ERR_ARG;      // the parity sub-problems below re-pack ws one after the other: no pack outlives the call
-  if (use_pw_scatter(c)) {
-    unsigned empty = 0u;
-    for (int oy0 = 0; oy0 < st; ++oy0)
-      for (int ox0 = 0; ox0 < st; ++ox0)
-        if ((oy0 + c.pad) % st >= c.R || (ox0 + c.pad) % st >= c.S) empty |= 1u << (oy0 * st + ox0);
-    if (empty != 0u) {
-      const long n4 = (long)c.B * c.Hd * c.Wd * (c.Cd / 4);
-      long blocks = (n4 + 255) / 256;
-      if (blocks > 65536) blocks = 65536;
-      hipLaunchKernelGGL(zero_classes_kernel, dim3((unsigned)blocks), dim3(256), 0, c.stream_, c.dst, n4, c.Hd, c.Wd, c.Cd / 4, st, empty);
-      FS_LAUNCH_CHECK();
-    }
-    return fs_pointwise_scatter_conv(g_conv_precision, c.src, c.w, c.dst, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cd, c.Hs, c.Ws, c.Cs, c.R, c.S,
-                                     c.stride, c.pad, c.stream_);
-  }
-  // classes no tap reaches (stride > filter size: 7 of 16 for 3x3 stride 4, 15 of 16 for 1x1 stride 4) are zero-filled by one
-  // store-only launch instead of one conv launch each (1x1 stride 4, 1.57 GB of dX: 1.13 -> 0.55 ms)
   const bool fill_ok = st * st <= 32 && c.Cd % 4 == 0 && c.bias == nullptr;
   unsigned empty_classes = 0u;
   for (int oy0 = 0; oy0 < st; ++oy0)
@@ -1189,27 +1187,113 @@ int launch_affine(const ConvArgs& c, long M) {
       b.cy = (oy0 + c.pad - b.r0) / st; b.cx = (ox0 + c.pad - b.s0) / st;
       if (b.Hq <= 0 || b.Wq <= 0) continue;
       if (b.nR == 0 && fill_ok) { empty_classes |= 1u << (oy0 * st + ox0); continue; }
-      if (b.nR * b.nS > 1 && use_tapset(c)) {       // single-tap sub-problems: no reuse, the plain kernel is faster
+      int e;
+      if (b.nR * b.nS > 1 && tapset) {       // single-tap sub-problems: no reuse, the plain kernel is faster
         // dY row of tap t is py + cy - t: in increasing source order tr = nR-1-t, filter row r0 + st*(nR-1-tr)
         FsTapsetProblem p = tapset_base(c);
-        p.Hq = b.Hq; p.Wq = b.Wq; p.os = st; p.oy0 = oy0; p.ox0 = ox0; p.sm = 1;
+        p.Hq = b.Hq; p.Wq = b.Wq; p.os = st; p.oy0 = oy0; p.ox0 = ox0;
         p.ncls = 1;
         p.cls[0] = FsTapClass{b.cy - (b.nR - 1), b.cx - (b.nS - 1), b.nR, b.nS, b.r0 + st * (b.nR - 1), -st, b.s0 + st * (b.nS - 1), -st};
-        int e2 = run_tapset(p, c.stream_);
-        if (e2 != FS_OK) return e2;
-        continue;
+        e = fs_tapset_conv(g_conv_precision, p, c.stream_);
+      } else {
+        e = launch_affine_one(b, c.stream_);
       }
-      int e = launch_affine_one(b);
       if (e != FS_OK) return e;
     }
-  if (empty_classes != 0u) {
-    const long n4 = (long)c.B * c.Hd * c.Wd * (c.Cd / 4);
-    long blocks = (n4 + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(zero_classes_kernel, dim3((unsigned)blocks), dim3(256), 0, c.stream_, c.dst, n4, c.Hd, c.Wd, c.Cd / 4, st, empty_classes);
-    FS_LAUNCH_CHECK();
+  return zero_classes(c, empty_classes);
+}
+
+int launch_conv(const ConvArgs& c, unsigned want = 0u) {
+  const ConvPlan plan = plan_conv(c, want);
+  if (!plan.ok) return FS_ERR_ARG;                                  // the matching _ok / _slabs query reported 0 for this problem
+  if (fs_ws_mode_tls != 0 && !plan.persistent) return FS_ERR_ARG;   // no weight pack that outlives a call
+  const int m = g_conv_precision, st = c.stride;
+  const int Cin = c.transposed ? c.Cd : c.Cs, Cout = c.transposed ? c.Cs : c.Cd;
+  AffArgs a{c.src, c.w, c.bias, c.dst, c.B, c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd, c.R, c.S, c.stride, c.pad, c.dil, c.transposed,
+            c.drop_scale, c.drop_thresh, c.drop_key, (unsigned)(src_elems(c) * 4), (unsigned)((size_t)c.R * c.S * c.Cs * c.Cd * 4),
+            fits32(dst_elems(c)) ? (unsigned)(dst_elems(c) * 4) : 0u,
+            c.Hd, c.Wd, 1, 0, 0, 0, 0, 1, c.R, c.S, c.pad, c.pad, 0, 0, c.stats_};
+  switch (plan.route) {
+    case GENERIC: return launch_generic(c);
+    case PLAIN: return launch_affine_one(a, c.stream_);
+    case S2FWD:
+      return fs_s2fwd_conv(m, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd, c.drop_scale,
+                           c.drop_thresh, c.drop_key, c.stream_);
+    case WINO_F23:
+    case WINO_F43:      // fs_wino_conv3x3 hands the F(4,3) problems on to conv_wino4.hip
+      return fs_wino_conv3x3(m, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cs, c.Cd, Cin, Cout, c.transposed,
+                             c.drop_scale, c.drop_thresh, c.drop_key, c.bn_, c.stream_);
+    case HALO:
+      return fs_halo_conv3x3(m, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cs, c.Cd, Cin, Cout, c.transposed,
+                             c.drop_scale, c.drop_thresh, c.drop_key, c.stream_);
+    case TAPSET_FWD: {
+      FsTapsetProblem p = tapset_base(c);
+      p.sm = st;
+      p.ncls = 0;
+      for (int r0 = 0; r0 < st && r0 < c.R; ++r0)
+        for (int s0 = 0; s0 < st && s0 < c.S; ++s0)
+          p.cls[p.ncls++] = FsTapClass{r0 - c.pad, s0 - c.pad, (c.R - r0 + st - 1) / st, (c.S - s0 + st - 1) / st, r0, st, s0, st};
+      return fs_tapset_conv(m, p, c.stream_);
+    }
+    case TAPSET_BWD1: {
+      FsTapsetProblem p = tapset_base(c);
+      p.ncls = 1;
+      p.cls[0] = FsTapClass{c.pad - (c.R - 1), c.pad - (c.S - 1), c.R, c.S, c.R - 1, -1, c.S - 1, -1};
+      return fs_tapset_conv(m, p, c.stream_);
+    }
+    case POINTWISE:
+      return fs_pointwise_conv(m, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, (long)c.B * c.Hd * c.Wd, c.Cs, c.Cd, Cin, Cout,
+                               c.transposed, c.drop_scale, c.drop_thresh, c.drop_key, c.bn_, c.stream_);
+    case GATHER:
+      return fs_pointwise_gather_conv(m, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd, c.R, c.S,
+                                      st, c.pad, c.drop_scale, c.drop_thresh, c.drop_key, c.stream_);
+    case S2BWD:
+      return fs_s2bwd_conv(m, c.src, c.w, c.dst, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cd, c.Hs, c.Ws, c.Cs, c.bn_, c.stats_, c.stream_);
+    case SCATTER: {
+      unsigned empty = 0u;
+      for (int oy0 = 0; oy0 < st; ++oy0)
+        for (int ox0 = 0; ox0 < st; ++ox0)
+          if ((oy0 + c.pad) % st >= c.R || (ox0 + c.pad) % st >= c.S) empty |= 1u << (oy0 * st + ox0);
+      const int e = zero_classes(c, empty);
+      if (e != FS_OK) return e;
+      return fs_pointwise_scatter_conv(m, c.src, c.w, c.dst, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cd, c.Hs, c.Ws, c.Cs, c.R, c.S, st, c.pad,
+                                       c.stream_);
+    }
+    case PARITY: return launch_parity(c, a, plan.tapset);
   }
-  return FS_OK;
+  return FS_ERR_ARG;
+}
+
+// ---- what the entry points share: argument checks, ConvArgs from the C-ABI arguments, dropout rate -> threshold ------------------------
+bool conv_shape_ok(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil) {
+  return B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0 && dil >= 1 &&
+         Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1;
+}
+
+// transposed = 0: src = X (B,H,W,Cin), dst = Y (B,Ho,Wo,Cout);  1 (bwd-data): src = dY, dst = dX
+ConvArgs conv_args(const float* src, const float* w, const float* bias, float* dst, int B, int H, int W, int Cin, int Ho, int Wo, int Cout,
+                   int R, int S, int stride, int pad, int dil, int transposed, void* ws, long ws_bytes, const unsigned* w_amax,
+                   hipStream_t stream) {
+  ConvArgs a = transposed ? ConvArgs{src, w, bias, dst, B, Ho, Wo, Cout, H, W, Cin, R, S, stride, pad, dil, 1, 1.f, 0u, 0u}
+                          : ConvArgs{src, w, bias, dst, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, 0u};
+  a.stream_ = stream;
+  a.ws_ = ws; a.ws_bytes_ = ws_bytes; a.w_amax_ = w_amax;
+  return a;
+}
+
+// the plan a launch of this problem with ws_bytes of scratch would follow (host-side queries: no tensors)
+ConvPlan query_plan(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil, int transposed,
+                    long ws_bytes, unsigned want = 0u) {
+  static unsigned char some_ws;
+  return plan_conv(conv_args(nullptr, nullptr, nullptr, nullptr, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed,
+                             ws_bytes > 0 ? &some_ws : nullptr, ws_bytes, nullptr, nullptr), want);
+}
+
+// drop probability p in [0, 1) -> the survivors' scale 1/(1-p) and the 32-bit hash threshold (p = 0 leaves 1 and 0 = off)
+void drop_rate(float p, float& drop_scale, uint32_t& drop_thresh) {
+  if (p <= 0.f) return;
+  drop_scale = 1.0f / (float)(1.0 - (double)p);
+  drop_thresh = (uint32_t)((double)p * 4294967296.0);
 }
 
 }  // namespace
@@ -1277,75 +1361,32 @@ int fs_weight_amax_segments(const float* arena, const long* offsets, const long*
   return fs_weight_amax_segments_impl(arena, offsets, sizes, nparams, out, stream);
 }
 
-// include/fovealseg.h: fs_conv2d_workspace_bytes -- scratch the conv entry points can use for this shape (0 = none).
+// include/fovealseg.h: fs_conv2d_workspace_bytes -- scratch the conv entry points can use for this shape (0 = none): the largest pack of
+// the families the shape is eligible for (asked before ws exists, so it cannot be the plan of one route).
 // transposed = 0 for fs_conv2d_fwd / fs_conv2d_fwd_stats, 1 for fs_conv2d_bwd_data.
 long fs_conv2d_workspace_bytes(int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil, int transposed) {
   if (g_conv_precision < 1) return 0;
-  const int Cs = transposed ? Cout : Cin, Cd = transposed ? Cin : Cout;
+  FamilyFit f[N_FAMILIES];
+  conv_families(conv_args(nullptr, nullptr, nullptr, nullptr, 1, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed, nullptr, 0, nullptr,
+                          nullptr), f);
   long need = 0;
-  if (H == Ho && W == Wo && fs_halo_eligible(H, W, Cs, Cd, R, S, stride, pad, dil)) {
-    need = halo_pack_bytes(Cs, Cd);
-    const long t = fs_wino_pack_bytes(g_conv_precision, Cs, Cd);       // the F(2,3) variant packs 4 components per filter row
-    if (t > need) need = t;
-  }
-  if (tapset_shape_ok(Cs, Cd, R, S, stride, dil)) {
-    const long t = tapset_pack_bytes(Cs, Cd, R * S);
-    if (t > need) need = t;
-  }
-  if (g_pointwise && H == Ho && W == Wo && fs_pointwise_eligible(Cs, Cd, R, S, stride, pad, dil)) {
-    const long t = fs_pointwise_pack_bytes(g_conv_precision, Cs, Cd);
-    if (t > need) need = t;
-  }
-  if (g_s2fwd && !transposed && fs_s2fwd_eligible(H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)) {
-    const long t = fs_s2fwd_pack_bytes(g_conv_precision, Cin, Cout);
-    if (t > need) need = t;
-  }
-  if (g_pw_gather && !transposed && fs_pointwise_gather_eligible(Cin, Cout, R, S, stride, dil)) {
-    const long t = fs_pointwise_pack_bytes(g_conv_precision, R * S * Cin, Cout);
-    if (t > need) need = t;
-  }
-  if (g_pw_gather && transposed && fs_pointwise_scatter_eligible(Cin, Cout, R, S, stride, dil)) {
-    const long t = fs_pointwise_pack_bytes(g_conv_precision, Cout, Cin);
-    if (t > need) need = t;
-  }
-  if (g_s2bwd && transposed && fs_s2bwd_eligible(H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)) {
-    const long t = fs_s2bwd_pack_bytes(g_conv_precision, Cin, Cout);
-    if (t > need) need = t;
-  }
+  for (const FamilyFit& k : f)
+    if (k.shape_ok && k.pack > need) need = k.pack;
   return need;
 }
 
 // include/fovealseg.h: fs_conv2d_kernel_choice -- which kernel family the conv entry points select for this problem under the current
-// precision mode and `ws_bytes` of scratch (host-side predicate, no launch; the dispatch below uses the same functions).
-// 0 = generic 64-bit-indexed kernel, 1 = plain aligned implicit GEMM, 2 = halo-tiled 3x3, 3 = tap-class kernel, 4 = 1x1 GEMM kernel,
-// 5 = halo-tiled 3x3 with F(2,3) minimal filtering along the row, 6 = stride-2 bwd-data with the four output parities in one launch,
-// 7 = stride-2 forward with the four input parity planes in one LDS refill, 8 = halo-tiled 3x3 with F(4,3) minimal filtering along the
-// row (conv_wino4.hip: bf16x3, widths that are multiples of 4).
+// precision mode and `ws_bytes` of scratch (host-side, no launch; ROUTE_INFO has the ids).
 int fs_conv2d_kernel_choice(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil,
                             int transposed, long ws_bytes) {
-  ConvArgs c{nullptr, nullptr, nullptr, nullptr, B, transposed ? Ho : H, transposed ? Wo : W, transposed ? Cout : Cin,
-             transposed ? H : Ho, transposed ? W : Wo, transposed ? Cin : Cout, R, S, stride, pad, dil, transposed, 1.f, 0u, 0u};
-  c.ws_ = ws_bytes > 0 ? (void*)&c : nullptr;
-  c.ws_bytes_ = ws_bytes;
-  if (!aligned_ok(c)) return 0;
-  if (use_s2fwd(c)) return 7;
-  if (!transposed && use_tapset(c) && !use_halo(c)) return 3;
-  if (transposed && stride == 1 && use_tapset(c) && !use_halo(c)) return 3;
-  if (use_wino(c)) return fs_wino_takes_f43(g_conv_precision, c.B, c.Hd, c.Wd, c.Cs, c.Cd) ? 8 : 5;
-  if (use_halo(c)) return 2;
-  if (use_pointwise(c) || use_pw_gather(c)) return 4;
-  if (use_s2bwd(c)) return 6;
-  if (transposed && stride > 1 && use_tapset(c)) return 3;     // the multi-tap parity sub-problems
-  return 1;
+  return query_plan(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed, ws_bytes).family;
 }
 
 // include/fovealseg.h: 1 when the scratch of this problem is ONE weight pack that depends on (w, shape, precision mode) only, so a caller
 // may keep it across calls (fs_conv2d_pack once per weight update, then FS_WS_RUN_ONLY calls); 0 = no pack, or one that does not outlive the call
 int fs_conv2d_pack_persistent(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil,
                               int transposed, long ws_bytes) {
-  const int k = fs_conv2d_kernel_choice(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed, ws_bytes);
-  if (k == 2 || k == 4 || k == 5 || k == 6 || k == 7 || k == 8) return 1;
-  return (k == 3 && !(transposed && stride > 1)) ? 1 : 0;
+  return query_plan(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed, ws_bytes).persistent ? 1 : 0;
 }
 
 // include/fovealseg.h: set how the calling thread's next conv calls treat ws (0 pack + run, 1 run only: ws holds the pack); returns the old mode
@@ -1358,18 +1399,14 @@ int fs_conv2d_ws_mode(int mode) {
 // include/fovealseg.h: run only the weight pack of the kernel fs_conv2d_fwd* (transposed = 0) / fs_conv2d_bwd_data* (1) select for this problem
 int fs_conv2d_pack(const float* w, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil,
                    int transposed, void* ws, long ws_bytes, const unsigned* w_amax, hipStream_t stream) {
-  FS_REQUIRE(w && ws && ws_bytes > 0 && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0 && dil >= 1);
-  FS_REQUIRE(Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1);
-  FS_REQUIRE(fs_conv2d_pack_persistent(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed, ws_bytes) == 1);
-  // src / dst are never dereferenced: every family returns after its pack launch in this mode (the predicate above excludes the rest)
-  const float* nowhere = reinterpret_cast<const float*>(ws);
-  ConvArgs a = transposed ? ConvArgs{nowhere, w, nullptr, reinterpret_cast<float*>(ws), B, Ho, Wo, Cout, H, W, Cin, R, S, stride, pad, dil, 1, 1.f, 0u, 0u}
-                          : ConvArgs{nowhere, w, nullptr, reinterpret_cast<float*>(ws), B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, 0u};
-  a.stream_ = stream;
-  a.ws_ = ws; a.ws_bytes_ = ws_bytes; a.w_amax_ = w_amax;
+  FS_REQUIRE(w && ws && ws_bytes > 0 && conv_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil));
+  // src / dst are never dereferenced: every family returns after its pack launch in this mode (launch_conv refuses the routes without a
+  // persistent pack before anything is launched)
+  const ConvArgs a = conv_args(reinterpret_cast<const float*>(ws), w, nullptr, reinterpret_cast<float*>(ws), B, H, W, Cin, Ho, Wo, Cout, R, S,
+                               stride, pad, dil, transposed, ws, ws_bytes, w_amax, stream);
   const int old = fs_ws_mode_tls;
   fs_ws_mode_tls = FS_WS_PACK_ONLY;
-  const int e = launch_affine(a, 0);
+  const int e = launch_conv(a);
   fs_ws_mode_tls = old;
   return e;
 }
@@ -1378,56 +1415,27 @@ int fs_conv2d_pack(const float* w, int B, int H, int W, int Cin, int Ho, int Wo,
 // this shape when called with ws_bytes of scratch (depends on which kernel it selects).
 int fs_conv2d_stats_slabs(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil,
                           long ws_bytes) {
-  // the SAME predicates, in the same order, as the dispatch of fs_conv2d_fwd_stats (launch_affine): a count derived from eligibility alone
-  // would describe another kernel's slab layout whenever a dispatch condition (precision mode, 4 GB bounds, scratch size) fails
-  ConvArgs c{nullptr, nullptr, nullptr, nullptr, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, 0u};
-  c.ws_ = ws_bytes > 0 ? (void*)&c : nullptr;
-  c.ws_bytes_ = ws_bytes;
-  if (aligned_ok(c)) {
-    if (use_s2fwd(c)) return fs_s2fwd_slabs(B, Ho, Wo);
-    if (use_tapset(c) && !use_halo(c)) return fs_tapset_slabs(B, Ho, Wo, (R + stride - 1) / stride, (S + stride - 1) / stride);
-    if (use_wino(c)) return fs_wino_stats_slabs(g_conv_precision, B, Ho, Wo, Cin, Cout);
-    if (use_halo(c)) return fs_halo_stats_slabs(B, Ho, Wo);
-  }
-  return cdiv((long)B * Ho * Wo, 128);      // the 1x1 GEMM kernels, the plain aligned kernel and the generic one: one slab per 128 rows
+  return query_plan(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws_bytes).slabs;
 }
 
 // include/fovealseg.h: fs_conv2d_fwd
 int fs_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, int B, int H, int W, int Cin,
                   int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil, float drop_p, uint32_t drop_key,
                   void* ws, long ws_bytes, const unsigned* w_amax, hipStream_t stream) {
-  FS_REQUIRE(x && w && y && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0);
-  FS_REQUIRE(dil >= 1 && Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1);
-  FS_REQUIRE(drop_p >= 0.f && drop_p < 1.f);
-  ConvArgs a{x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, drop_key};
-  a.stream_ = stream;
-  a.ws_ = ws; a.ws_bytes_ = ws_bytes; a.w_amax_ = w_amax;
-  if (drop_p > 0.f) {
-    a.drop_scale = 1.0f / (float)(1.0 - (double)drop_p);
-    a.drop_thresh = (uint32_t)((double)drop_p * 4294967296.0);
-  }
-  const long M = (long)B * Ho * Wo;
-  FS_REQUIRE(M * Cout < 4294967296L);
-  if (aligned_ok(a)) return launch_affine(a, M);
-  dim3 grid(cdiv(M, BM), cdiv(Cout, BN));
-  if ((Cin % 4 == 0) && (Cout % 4 == 0))
-    hipLaunchKernelGGL(conv_igemm_kernel<true>, grid, dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(conv_igemm_kernel<false>, grid, dim3(256), 0, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
+  FS_REQUIRE(x && w && y && conv_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil));
+  FS_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (long)B * Ho * Wo * Cout < 4294967296L);
+  ConvArgs a = conv_args(x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
+  a.drop_key = drop_key;
+  drop_rate(drop_p, a.drop_scale, a.drop_thresh);
+  return launch_conv(a);
 }
 
 // include/fovealseg.h: fs_conv2d_fwd_residual -- y = res + DropPath(Dropout(conv(x, w) + bias)) for a layer the 1x1 GEMM kernel runs
 int fs_conv2d_fwd_residual_ok(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil,
                               long rows_per_sample, long ws_bytes) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || rows_per_sample <= 0 || ((long)B * Ho * Wo) % rows_per_sample) return 0;
-  ConvArgs a{nullptr, nullptr, nullptr, nullptr, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, 0u};
-  static unsigned char dummy;
-  static const float one = 1.f;
-  const FsBnSums bn{nullptr, nullptr, nullptr, nullptr, &one, nullptr, nullptr, nullptr, nullptr, 0, 1.f, 0u, 0u, 0};
-  a.ws_ = ws_bytes > 0 ? &dummy : nullptr; a.ws_bytes_ = ws_bytes; a.bn_ = &bn;
-  return (aligned_ok(a) && bnsum_beyond_wino(a) && rows_per_sample >= 128 && rows_per_sample < 2147483647L && (long)B * Ho * Wo * Cout < 4294967296L) ? 1 : 0;
+  if (rows_per_sample < 128 || rows_per_sample >= 2147483647L || (long)B * Ho * Wo * Cout >= 4294967296L) return 0;
+  return query_plan(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws_bytes, EX_ADDEND).ok ? 1 : 0;
 }
 
 int fs_conv2d_fwd_residual(const float* x, const float* w, const float* bias, const float* res, float* y, int B, int H, int W, int Cin, int Ho,
@@ -1435,30 +1443,20 @@ int fs_conv2d_fwd_residual(const float* x, const float* w, const float* bias, co
                            uint32_t droppath_key, long rows_per_sample, void* ws, long ws_bytes, const unsigned* w_amax, hipStream_t stream) {
   FS_REQUIRE(x && w && res && y && drop_p >= 0.f && drop_p < 1.f && droppath_p >= 0.f && droppath_p < 1.f);
   FS_REQUIRE(fs_conv2d_fwd_residual_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, rows_per_sample, ws_bytes) == 1);
-  ConvArgs a{x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, drop_key};
-  a.stream_ = stream;
-  a.ws_ = ws; a.ws_bytes_ = ws_bytes; a.w_amax_ = w_amax;
-  if (drop_p > 0.f) {
-    a.drop_scale = 1.0f / (float)(1.0 - (double)drop_p);
-    a.drop_thresh = (uint32_t)((double)drop_p * 4294967296.0);
-  }
+  ConvArgs a = conv_args(x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
+  a.drop_key = drop_key;
+  drop_rate(drop_p, a.drop_scale, a.drop_thresh);
   FsBnSums bn{nullptr, nullptr, nullptr, nullptr, res, nullptr, nullptr, nullptr, nullptr, 0, 1.f, 0u, droppath_key, (int)rows_per_sample};
-  if (droppath_p > 0.f) {
-    bn.dp_scale = 1.0f / (float)(1.0 - (double)droppath_p);
-    bn.dp_thresh = (uint32_t)((double)droppath_p * 4294967296.0);
-  }
+  drop_rate(droppath_p, bn.dp_scale, bn.dp_thresh);
   a.bn_ = &bn;
-  return launch_affine(a, (long)B * Ho * Wo);
+  return launch_conv(a, EX_ADDEND);
 }
 
 // include/fovealseg.h: 1 when fs_conv2d_fwd_affine_act can serve this shape (the F(2,3) kernels' row epilogue), else 0
 int fs_conv2d_fwd_affine_act_ok(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil,
                                 long ws_bytes) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || dil != 1 || Cout % 4) return 0;
-  ConvArgs a{nullptr, nullptr, nullptr, nullptr, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, 0u};
-  static unsigned char dummy;
-  a.ws_ = ws_bytes > 0 ? &dummy : nullptr; a.ws_bytes_ = ws_bytes;
-  return (aligned_ok(a) && !(use_tapset(a) && !use_halo(a)) && use_wino(a)) ? 1 : 0;
+  return query_plan(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws_bytes, EX_AFFINE_ACT).ok ? 1 : 0;
 }
 
 // include/fovealseg.h: inference forward  z = act((conv(x, w) + bias) * scale[c] + shift[c] [+ res])  in one launch
@@ -1468,57 +1466,34 @@ int fs_conv2d_fwd_affine_act(const float* x, const float* w, const float* bias, 
   FS_REQUIRE(x && w && z && scale && shift && act >= 0 && act <= 2);
   FS_REQUIRE(fs_conv2d_fwd_affine_act_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes) == 1);
   FS_REQUIRE(Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1);
-  ConvArgs a{x, w, bias, z, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, 0u};
-  a.stream_ = stream;
-  a.ws_ = ws; a.ws_bytes_ = ws_bytes; a.w_amax_ = w_amax;
+  ConvArgs a = conv_args(x, w, bias, z, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
   const FsBnSums ep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, scale, shift, res, act};
   a.bn_ = &ep;
-  return launch_affine(a, (long)B * Ho * Wo);
+  return launch_conv(a, EX_AFFINE_ACT);
 }
 
 // include/fovealseg.h: fs_conv2d_fwd_stats -- forward conv that also emits per-workgroup BatchNorm partials.
-// stats = [ceil(B*Ho*Wo/128)][Cout][2] floats.  Requires Cin%4==0 && Cout%4==0 (the affine kernel).
+// stats = [fs_conv2d_stats_slabs][Cout][2] floats.  Requires Cin%4==0 && Cout%4==0 (every kernel but the generic one has the epilogue).
 int fs_conv2d_fwd_stats(const float* x, const float* w, const float* bias, float* y, float* stats, int B, int H, int W, int Cin,
                         int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil, float drop_p, uint32_t drop_key,
                         void* ws, long ws_bytes, const unsigned* w_amax, hipStream_t stream) {
-  FS_REQUIRE(x && w && y && stats && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0);
-  FS_REQUIRE(dil >= 1 && Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1);
-  FS_REQUIRE(drop_p >= 0.f && drop_p < 1.f);
-  ConvArgs a{x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, drop_key};
-  FS_REQUIRE(aligned_ok(a));
-  a.stream_ = stream;
+  FS_REQUIRE(x && w && y && stats && conv_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil));
+  FS_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (long)B * Ho * Wo * Cout < 4294967296L);
+  ConvArgs a = conv_args(x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
   a.stats_ = stats;
-  a.ws_ = ws; a.ws_bytes_ = ws_bytes; a.w_amax_ = w_amax;
-  if (drop_p > 0.f) {
-    a.drop_scale = 1.0f / (float)(1.0 - (double)drop_p);
-    a.drop_thresh = (uint32_t)((double)drop_p * 4294967296.0);
-  }
-  const long M = (long)B * Ho * Wo;
-  FS_REQUIRE(M * Cout < 4294967296L);
-  return launch_affine(a, M);
+  a.drop_key = drop_key;
+  drop_rate(drop_p, a.drop_scale, a.drop_thresh);
+  return launch_conv(a);
 }
 
 // include/fovealseg.h: fs_conv2d_bwd_data   (dX has the forward input's shape B,H,W,Cin)
 static int conv2d_bwd_data_impl(const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Ho, int Wo,
                                 int Cout, int R, int S, int stride, int pad, int dil, void* ws, long ws_bytes, const unsigned* w_amax,
                                 const FsBnSums* bn, float* slab, hipStream_t stream) {
-  FS_REQUIRE(dy && w && dx && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0);
-  FS_REQUIRE(dil >= 1 && Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1);
-  ConvArgs a{dy, w, nullptr, dx, B, Ho, Wo, Cout, H, W, Cin, R, S, stride, pad, dil, 1, 1.f, 0u, 0u};
-  FS_REQUIRE(stride == 1 || dil == 1);
-  const long M = (long)B * H * W;
-  a.stream_ = stream;
-  a.ws_ = ws; a.ws_bytes_ = ws_bytes; a.w_amax_ = w_amax;
+  FS_REQUIRE(dy && w && dx && conv_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil) && (stride == 1 || dil == 1));
+  ConvArgs a = conv_args(dy, w, nullptr, dx, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 1, ws, ws_bytes, w_amax, stream);
   a.bn_ = bn; a.stats_ = slab;
-  if (aligned_ok(a)) return launch_affine(a, M);
-  FS_REQUIRE(bn == nullptr);
-  dim3 grid(cdiv(M, BM), cdiv(Cin, BN));
-  if ((Cin % 4 == 0) && (Cout % 4 == 0))
-    hipLaunchKernelGGL(conv_igemm_kernel<true>, grid, dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(conv_igemm_kernel<false>, grid, dim3(256), 0, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
+  return launch_conv(a, bn == nullptr ? 0u : (bn->y ? EX_BNSUM : 0u) | (bn->add_src ? EX_ADDEND : 0u));
 }
 
 int fs_conv2d_bwd_data(const float* dy, const float* w, float* dx, int B, int H, int W, int Cin, int Ho, int Wo,
@@ -1530,13 +1505,8 @@ int fs_conv2d_bwd_data(const float* dy, const float* w, float* dx, int B, int H,
 int fs_conv2d_bwd_data_bnsum_slabs(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil,
                                    long ws_bytes) {
   if (B <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || dil != 1 || Cin % 4) return 0;
-  ConvArgs a{nullptr, nullptr, nullptr, nullptr, B, Ho, Wo, Cout, H, W, Cin, R, S, stride, pad, dil, 1, 1.f, 0u, 0u};
-  static unsigned char dummy;
-  a.ws_ = ws_bytes > 0 ? &dummy : nullptr; a.ws_bytes_ = ws_bytes;
-  if (!aligned_ok(a)) return 0;
-  if (bnsum_beyond_wino(a)) return use_pointwise(a) ? fs_pointwise_stats_slabs((long)B * H * W) : fs_s2bwd_stats_slabs(B, Ho, Wo);
-  if ((use_tapset(a) && !use_halo(a)) || !use_wino(a)) return 0;
-  return fs_wino_stats_slabs(g_conv_precision, B, H, W, Cout, Cin);      // bwd-data: source channels = Cout, destination = Cin
+  const ConvPlan p = query_plan(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 1, ws_bytes, EX_BNSUM | EX_ADDEND);
+  return p.ok ? p.slabs : 0;
 }
 
 // include/fovealseg.h: fs_conv2d_bwd_data + the BatchNorm-backward column sums of the layer that produced x (dx is that layer's dz)
@@ -1605,7 +1575,7 @@ int fs_conv2d_bwd_weight(const float* x, const float* dy, float* dw, int B, int 
     return fs_wgrad_reduce(ph.base, ph.used, n, dw, accumulate, stream);
   }
   if (ws != nullptr && wgrad_store_route(Cin, Cout, R, S, stride, pad, dil) &&
-      (size_t)B * H * W * Cin * 4 < 4294967000UL && (size_t)B * Ho * Wo * Cout * 4 < 4294967000UL) {
+      fits32((size_t)B * H * W * Cin) && fits32((size_t)B * Ho * Wo * Cout)) {
     const long n = (long)R * S * Cin * Cout, cap = wgrad_slab_cap(Cin, Cout, R, S, stride, pad, dil);
     if (ws_bytes >= cap * n * 4) {
       FsPartHost ph{static_cast<float*>(ws), n, cap, 0, 1};
@@ -1634,7 +1604,7 @@ static int conv2d_bwd_weight_impl(const float* x, const float* dy, float* dw, in
                                   int Cout, int R, int S, int stride, int pad, int dil, FsPartHost* ph, hipStream_t stream) {
   const long P = (long)B * Ho * Wo;
   if (g_conv_precision >= 1 && fs_wgrad_split_eligible(Cin, Cout, R, S, stride, pad, dil) &&
-      (size_t)B * H * W * Cin * 4 < 4294967000UL && (size_t)P * Cout * 4 < 4294967000UL)
+      fits32((size_t)B * H * W * Cin) && fits32((size_t)P * Cout))
     return fs_wgrad_split(g_conv_precision, x, dy, dw, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, ph, stream);
   const int tiles = cdiv(Cin, 64) * cdiv(Cout, 64);
   // one filter row per workgroup for narrow layers (more workgroups, fewer atomics each), the whole 3x3
@@ -1642,7 +1612,7 @@ static int conv2d_bwd_weight_impl(const float* x, const float* dy, float* dw, in
   // 192^2 106 TF / 960x240 87 TF / 512^2 87 TF with 9; per-tap kernel 71-83 TF).
   const int wg_mode = tiles >= 9 ? 9 : 3;
   if (R == 3 && S == 3 && (Cin % 4 == 0) && (Cout % 4 == 0) &&
-      (size_t)B * H * W * Cin * 4 < 4294967000UL && (size_t)P * Cout * 4 < 4294967000UL) {
+      fits32((size_t)B * H * W * Cin) && fits32((size_t)P * Cout)) {
     const int ng = 9 / wg_mode;
     long ns = (1024 + (long)tiles * ng - 1) / ((long)tiles * ng);
     long mx = (P + 127) / 128;

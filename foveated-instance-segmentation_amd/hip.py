@@ -266,19 +266,11 @@ def wgrad_workspace(device, Cin, Cout, R, S, stride, pad, dil):
 
 def conv_workspace_bytes(H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed):
     """Scratch bytes the conv entry points can use for this shape under the current precision mode (cached)."""
-    key = (H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed)
-    v = _ws_cache.get(key)
-    if v is None:
-        v = _ws_cache[key] = int(load().fs_conv2d_workspace_bytes(*key))
-    return v
+    return query("fs_conv2d_workspace_bytes", H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed)
 
 
 def conv_stats_slabs(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes):
-    key = ("slabs", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes)
-    v = _ws_cache.get(key)
-    if v is None:
-        v = _ws_cache[key] = int(load().fs_conv2d_stats_slabs(*key[1:]))
-    return v
+    return query("fs_conv2d_stats_slabs", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes)
 
 
 def attention_split_ws_bytes(B, Nk, heads, backward=False):
@@ -288,47 +280,27 @@ def attention_split_ws_bytes(B, Nk, heads, backward=False):
 
 def linear_bwd_weight_bias_ok(rows, Cin, Cout):
     """True where fs_linear_bwd_weight_bias (dW and dbias of a linear layer in one launch) exists under the current precision mode."""
-    key = ("lwb", rows, Cin, Cout)
-    v = _ws_cache.get(key)
-    if v is None:
-        v = _ws_cache[key] = int(load().fs_linear_bwd_weight_bias_ok(rows, Cin, Cout)) == 1
-    return v
+    return query("fs_linear_bwd_weight_bias_ok", rows, Cin, Cout) == 1
 
 
 def fwd_affine_act_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes):
     """True where fs_conv2d_fwd_affine_act serves this shape under the current precision mode (cached)."""
-    key = ("faa", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes)
-    v = _ws_cache.get(key)
-    if v is None:
-        v = _ws_cache[key] = int(load().fs_conv2d_fwd_affine_act_ok(*key[1:]))
-    return v == 1
+    return query("fs_conv2d_fwd_affine_act_ok", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes) == 1
 
 
 def fwd_residual_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, rows_per_sample, ws_bytes):
     """True where fs_conv2d_fwd_residual serves this shape under the current precision mode (cached)."""
-    key = ("fres", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, rows_per_sample, ws_bytes)
-    v = _ws_cache.get(key)
-    if v is None:
-        v = _ws_cache[key] = int(load().fs_conv2d_fwd_residual_ok(*key[1:]))
-    return v == 1
+    return query("fs_conv2d_fwd_residual_ok", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, rows_per_sample, ws_bytes) == 1
 
 
 def bwd_data_bnsum_slabs(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes):
     """Slab rows of fs_conv2d_bwd_data_bnsum for this problem under the current precision mode, 0 = not available (cached)."""
-    key = ("bdsum", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes)
-    v = _ws_cache.get(key)
-    if v is None:
-        v = _ws_cache[key] = int(load().fs_conv2d_bwd_data_bnsum_slabs(*key[1:]))
-    return v
+    return query("fs_conv2d_bwd_data_bnsum_slabs", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes)
 
 
 def bn_bwd_slabs(M, C):
     """Rows of the [.][C][2] partial-sum slab the BatchNorm-backward producers write for an (M, C) activation (cached)."""
-    key = ("bnslab", M, C)
-    v = _ws_cache.get(key)
-    if v is None:
-        v = _ws_cache[key] = int(load().fs_bn_bwd_slabs(M, C))
-    return v
+    return query("fs_bn_bwd_slabs", M, C)
 
 
 _mode_name = None      # the library's precision mode as a string, kept in step by set_conv_precision (one ctypes call less per conv launch)
