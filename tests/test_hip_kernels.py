@@ -2019,8 +2019,8 @@ def test_attention_keep_words_match_the_hash():
                    H.ptr(dv), H.ptr(scratch), H.ptr(wsb), nbb, B, N, Nk, heads, 0.125, p, key)
             outs.append((dq, dk, dv))
         assert torch.equal(outs[0][0], outs[1][0])                       # dq: no atomics, the same arithmetic
-        for a, b_ in zip(outs[0][1:], outs[1][1:]):                      # dk / dv: split-q partial sums meet in atomics
-            assert relerr(a, b_) <= 1e-6
+        for a, b_ in zip(outs[0][1:], outs[1][1:]):                      # dk / dv: the query splits' partial tensors are summed in index order
+            assert torch.equal(a, b_)
     finally:
         H.set_conv_precision(H.default_conv_precision())
 
