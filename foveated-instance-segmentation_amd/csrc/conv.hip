@@ -7,7 +7,7 @@
 //   bwd-data  : dX[m][n] = sum_{tap,co} dY[(pix(m)+pad-tap)/s][co] * W[tap][n][co] M=B*H*W   N=Cin
 //   bwd-weight: dW[tap][ci][co] = sum_pix X[pix+tap][ci] * dY[pix][co]             K=B*Ho*Wo (split)
 //
-// Which kernel runs (forward / bwd-data: plan_conv below; precision mode g_conv_precision: 0 = f32, 1 = bf16x3, 2 = f16x2):
+// Which kernel runs (forward / bwd-data: plan_conv below; bwd-weight: fs_wgrad_plan in conv_wgrad.hip; precision mode g_conv_precision: 0 = f32, 1 = bf16x3, 2 = f16x2):
 //   3x3 stride 1 pad 1, aligned channels, modes 1/2, scratch given : conv_halo.hip (fwd, bwd-data), conv_wgrad.hip (bwd-weight)
 //   other multi-tap filters / strided bwd-data sub-problems, modes 1/2 : conv_tapset.hip; bwd-weight per tap class: conv_wgrad.hip
 //   1x1, stride >= filter size, single-tap sub-problems, modes 1/2 : conv_igemm_split_kernel<P> (this file)
@@ -1304,16 +1304,24 @@ int fs_wgrad_reduce(float* part, int nslab, long n, float* dw, int accumulate, h
   return fs_slab_reduce_inplace(part, nslab, n, dw, accumulate, stream);
 }
 
-// slabs one bwd-weight call can need in deterministic mode: an upper bound of the split counts chosen below and in conv_wgrad.hip
-static long wgrad_slab_cap(int Cin, int Cout, int R, int S, int stride, int pad, int dil) {
-  const long tiles = (long)cdiv(Cin, 64) * cdiv(Cout, 64);
-  if (g_conv_precision >= 1 && fs_wgrad_split_eligible(Cin, Cout, R, S, stride, pad, dil)) {
-    if ((R == 1 && S == 1 && stride == 1 && pad == 0) || (stride >= R && stride >= S))
-      return 2048 / tiles + 2;      // linear_wgrad_kernel (plain or gathered rows): up to 1024 workgroups of 64 x 64 tiles, 512 of wider ones
-    return 512 / tiles + 2;                                                      // class kernels: 512 workgroups; transform-domain kernel: 2 x 256
+static bool wgrad_shape_ok(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil) {
+  return B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0 && dil >= 1 &&
+         Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1;
+}
+
+// How a bwd-weight plan (conv_kernels.h FsWgradPlan) accumulates over its pixel splits, around the launches run(part) issues: dW, or
+// zero_bytes of the slabs in ws, is zeroed first where the plan says so; slabs are summed into dW in index order afterwards -- dW itself
+// is then only touched by that sum.
+template <class Run>
+static int wgrad_accumulate(const FsWgradPlan& p, float* dw, long n, int accumulate, void* ws, size_t zero_bytes, hipStream_t stream, Run run) {
+  const bool slabs = p.accum == FS_WG_SLABS_ZEROED || p.accum == FS_WG_SLABS_STORED;
+  if (p.accum == FS_WG_ATOMIC_ZEROED || p.accum == FS_WG_SLABS_ZEROED) {
+    const hipError_t e = slabs ? hipMemsetAsync(ws, 0, zero_bytes, stream) : hipMemsetAsync(dw, 0, sizeof(float) * (size_t)n, stream);
+    if (e != hipSuccess) return (int)e;
   }
-  if (R == 3 && S == 3 && Cin % 4 == 0 && Cout % 4 == 0) return 1024 / tiles + 2;
-  return 2048 / (tiles * R * S) + 2;
+  const int r = run(slabs ? FsPart{static_cast<float*>(ws), n} : FsPart{nullptr, 0});
+  if (r != FS_OK || !slabs) return r;
+  return fs_wgrad_reduce(static_cast<float*>(ws), p.slabs, n, dw, accumulate, stream);
 }
 
 extern "C" {
@@ -1325,26 +1333,15 @@ int fs_set_deterministic(int on) {
 }
 int fs_get_deterministic(void) { return g_deterministic; }
 
-// include/fovealseg.h: scratch fs_conv2d_bwd_weight needs for this layer (0 unless deterministic mode is on)
-// Strided 3x3 layers (one round of <= 512 workgroups: ~50-85 us of patch rounds, then ~80 us of split-K atomics with nothing left to
-// overlap them): partial tiles by plain stores into per-split slabs + one ordered reduce launch instead of the atomics, in the default
-// mode too -- the machinery of deterministic mode, without the memset (the one-launch kernel writes every element of every slab it uses).
-static const int g_wgrad_store = FS_ENV_INT("FS_WGRAD_STORE", 1);      // kernel A/B builds only: 0 atomics everywhere, 2 also the 3x3 stride-1 class kernel
-static bool wgrad_store_route(int Cin, int Cout, int R, int S, int stride, int pad, int dil) {
-  if (g_wgrad_store == 0 || g_conv_precision < 1 || R != 3 || S != 3 || !fs_wgrad_split_eligible(Cin, Cout, R, S, stride, pad, dil)) return false;
-  if (g_conv_precision == 1 && fs_wgrad_gather_s2(Cin, R, S, stride) && g_wgrad_store != 3) return false;      // those run as gathered-row GEMMs (conv_wgrad.hip)
-  return stride == 2 || stride == 3 || (g_wgrad_store == 2 && stride == 1 && pad == 1);
-}
+// include/fovealseg.h: scratch fs_conv2d_bwd_weight needs for this layer (0 unless deterministic mode is on or the layer stores its partial tiles)
 long fs_conv2d_bwd_weight_ws_bytes(int Cin, int Cout, int R, int S, int stride, int pad, int dil) {
   if (Cin <= 0 || Cout <= 0 || R <= 0 || S <= 0 || stride <= 0) return 0;
-  if (!g_deterministic && !wgrad_store_route(Cin, Cout, R, S, stride, pad, dil)) return 0;
-  return wgrad_slab_cap(Cin, Cout, R, S, stride, pad, dil) * (long)R * S * Cin * Cout * 4;
+  return fs_wgrad_ws_slabs(g_conv_precision, g_deterministic != 0, Cin, Cout, R, S, stride, pad, dil) * (long)R * S * Cin * Cout * 4;
 }
 // include/fovealseg.h: scratch of fs_linear_bwd_weight_bias (dW slabs, then 4 bias slabs per dW slab)
 long fs_linear_bwd_weight_bias_ws_bytes(int Cin, int Cout) {
   if (!g_deterministic || Cin <= 0 || Cout <= 0) return 0;
-  const long cap = wgrad_slab_cap(Cin, Cout, 1, 1, 1, 0, 1);
-  return cap * ((long)Cin * Cout + 4L * Cout) * 4;
+  return fs_wgrad_slab_cap(g_conv_precision, Cin, Cout, 1, 1, 1, 0, 1) * ((long)Cin * Cout + 4L * Cout) * 4;
 }
 
 // include/fovealseg.h: fs_set_conv_precision / fs_get_conv_precision (host-side switch, no launch)
@@ -1521,7 +1518,6 @@ int fs_conv2d_bwd_data_bnsum(const float* dy, const float* w, float* dx, int B, 
   return conv2d_bwd_data_impl(dy, w, dx, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws, ws_bytes, w_amax, &bn, slab, stream);
 }
 
-// include/fovealseg.h: fs_conv2d_bwd_weight   (dw is overwritten, or added to when accumulate != 0)
 // include/fovealseg.h: fs_linear_bwd_weight_bias_ok -- 1 when the fused launch below exists for this shape in the current mode
 int fs_linear_bwd_weight_bias_ok(long rows, int Cin, int Cout) { return fs_linear_wgrad_eligible(g_conv_precision, rows, Cin, Cout) ? 1 : 0; }
 
@@ -1530,121 +1526,57 @@ int fs_linear_bwd_weight_bias(const float* x, const float* dy, float* dw, float*
                               int accumulate_b, void* ws, long ws_bytes, hipStream_t stream) {
   FS_REQUIRE(x && dy && dw && dbias);
   FS_REQUIRE(fs_linear_bwd_weight_bias_ok(rows, Cin, Cout) == 1);
-  if (g_deterministic) {
-    // ordered split-K: partial dW tiles and partial bias sums in per-split slabs, summed in index order
-    const long n = (long)Cin * Cout, cap = wgrad_slab_cap(Cin, Cout, 1, 1, 1, 0, 1);
-    FS_REQUIRE(ws != nullptr && ws_bytes >= fs_linear_bwd_weight_bias_ws_bytes(Cin, Cout));
-    hipError_t e = hipMemsetAsync(ws, 0, (size_t)cap * (n + 4L * Cout) * 4, stream);
-    if (e != hipSuccess) return (int)e;
-    FsPartHost ph{static_cast<float*>(ws), n, cap, 0, 0};
-    float* bpart = static_cast<float*>(ws) + cap * n;
-    const int r = fs_linear_wgrad(x, dy, dw, dbias, rows, Cin, Cout, &ph, bpart, stream);
-    if (r != FS_OK) return r;
-    const int r2 = fs_wgrad_reduce(ph.base, ph.used, n, dw, accumulate_w, stream);
-    if (r2 != FS_OK) return r2;
-    return fs_wgrad_reduce(bpart, 4 * ph.used, Cout, dbias, accumulate_b, stream);
-  }
-  if (!accumulate_w) {
-    const hipError_t e = hipMemsetAsync(dw, 0, sizeof(float) * (size_t)Cin * Cout, stream);
-    if (e != hipSuccess) return (int)e;
-  }
-  if (!accumulate_b) {
-    const hipError_t e = hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)Cout, stream);
-    if (e != hipSuccess) return (int)e;
-  }
-  return fs_linear_wgrad(x, dy, dw, dbias, rows, Cin, Cout, nullptr, nullptr, stream);
+  const FsWgradPlan p = fs_linear_wgrad_plan(g_deterministic != 0, accumulate_w != 0, rows, Cin, Cout);
+  // ordered split-K: partial dW tiles and, behind them, partial bias sums in per-split slabs, both summed in index order
+  const bool slabs = p.accum == FS_WG_SLABS_ZEROED;
+  FS_REQUIRE(p.ok && (!slabs || (ws != nullptr && ws_bytes >= fs_linear_bwd_weight_bias_ws_bytes(Cin, Cout))));
+  const long n = (long)Cin * Cout;
+  float* bpart = slabs ? static_cast<float*>(ws) + p.cap * n : nullptr;
+  const int r = wgrad_accumulate(p, dw, n, accumulate_w, ws, (size_t)p.cap * (n + 4L * Cout) * 4, stream, [&](FsPart part) {
+    if (!slabs && !accumulate_b) {
+      const hipError_t e = hipMemsetAsync(dbias, 0, sizeof(float) * (size_t)Cout, stream);
+      if (e != hipSuccess) return (int)e;
+    }
+    return fs_wgrad_launch(p, x, dy, dw, dbias, part, bpart, (int)rows, 1, 1, Cin, 1, 1, Cout, 1, 1, 1, 0, stream);
+  });
+  if (r != FS_OK || !slabs) return r;
+  return fs_wgrad_reduce(bpart, 4 * p.slabs, Cout, dbias, accumulate_b, stream);
 }
 
-static int conv2d_bwd_weight_impl(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Ho, int Wo,
-                                  int Cout, int R, int S, int stride, int pad, int dil, FsPartHost* ph, hipStream_t stream);
+// include/fovealseg.h: fs_conv2d_bwd_weight_plan -- what fs_conv2d_bwd_weight would do with these arguments (host-side, no launch)
+int fs_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil, long ws_bytes,
+                              int* out) {
+  if (out == nullptr) return 0;
+  for (int i = 0; i < 6; ++i) out[i] = 0;
+  if (!wgrad_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)) return 0;
+  const FsWgradPlan p = fs_wgrad_plan(g_conv_precision, g_deterministic != 0, false, ws_bytes > 0, ws_bytes, B, H, W, Cin, Ho, Wo, Cout, R, S,
+                                      stride, pad, dil);
+  out[0] = p.route; out[1] = p.accum; out[2] = p.nlaunch; out[3] = (int)p.wgs; out[4] = p.threads; out[5] = p.slabs;
+  return p.ok ? 1 : 0;
+}
 
+// include/fovealseg.h: fs_conv2d_bwd_weight   (dw is overwritten, or added to when accumulate != 0)
 int fs_conv2d_bwd_weight(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Ho, int Wo,
                          int Cout, int R, int S, int stride, int pad, int dil, int accumulate, void* ws, long ws_bytes, hipStream_t stream) {
-  FS_REQUIRE(x && dy && dw && B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0);
-  FS_REQUIRE(dil >= 1 && Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1);
-  if (g_deterministic) {
-    // ordered split-K: every split's partial tile goes to its own slab of ws (zeroed: a split without pixels writes nothing), the slabs
-    // are summed in index order -- and dw itself is only touched by that sum, so no memset of it
-    const long n = (long)R * S * Cin * Cout, cap = wgrad_slab_cap(Cin, Cout, R, S, stride, pad, dil);
-    FS_REQUIRE(ws != nullptr && ws_bytes >= cap * n * 4);
-    hipError_t e = hipMemsetAsync(ws, 0, (size_t)cap * n * 4, stream);
-    if (e != hipSuccess) return (int)e;
-    FsPartHost ph{static_cast<float*>(ws), n, cap, 0, 0};
-    const int r = conv2d_bwd_weight_impl(x, dy, dw, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, &ph, stream);
-    if (r != FS_OK) return r;
-    return fs_wgrad_reduce(ph.base, ph.used, n, dw, accumulate, stream);
-  }
-  if (ws != nullptr && wgrad_store_route(Cin, Cout, R, S, stride, pad, dil) &&
-      fits32((size_t)B * H * W * Cin) && fits32((size_t)B * Ho * Wo * Cout)) {
-    const long n = (long)R * S * Cin * Cout, cap = wgrad_slab_cap(Cin, Cout, R, S, stride, pad, dil);
-    if (ws_bytes >= cap * n * 4) {
-      FsPartHost ph{static_cast<float*>(ws), n, cap, 0, 1};
-      const int r = fs_wgrad_split(g_conv_precision, x, dy, dw, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, &ph, stream);
-      if (r != FS_OK) return r;
-      return fs_wgrad_reduce(ph.base, ph.used, n, dw, accumulate, stream);
+  FS_REQUIRE(x && dy && dw && wgrad_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil));
+  const FsWgradPlan p = fs_wgrad_plan(g_conv_precision, g_deterministic != 0, accumulate != 0, ws != nullptr, ws_bytes, B, H, W, Cin, Ho, Wo, Cout,
+                                      R, S, stride, pad, dil);
+  FS_REQUIRE(p.ok);      // deterministic mode without scratch for the shape's slab cap: never the atomics silently
+  const long n = (long)R * S * Cin * Cout;
+  return wgrad_accumulate(p, dw, n, accumulate, ws, (size_t)p.cap * n * 4, stream, [&](FsPart part) {
+    const WgradArgs a{x, dy, dw, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, p.step[0].per_split, cdiv(Cin, 64) * cdiv(Cout, 64),
+                      R * S, p.step[0].nsplit, part};      // the fp32 kernels of this file
+    const dim3 grid((unsigned)p.wgs);
+    switch (p.route) {
+      case FS_WG_TAPS3: hipLaunchKernelGGL(conv_wgrad_taps_kernel<3>, grid, dim3(256), 0, stream, a); break;
+      case FS_WG_TAPS9: hipLaunchKernelGGL(conv_wgrad_taps_kernel<9>, grid, dim3(256), 0, stream, a); break;
+      case FS_WG_GENERIC_VEC: hipLaunchKernelGGL(conv_wgrad_kernel<true>, grid, dim3(256), 0, stream, a); break;
+      case FS_WG_GENERIC: hipLaunchKernelGGL(conv_wgrad_kernel<false>, grid, dim3(256), 0, stream, a); break;
+      default: return fs_wgrad_launch(p, x, dy, dw, nullptr, part, nullptr, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, stream);
     }
-  }
-  if (!accumulate) {         // every kernel below adds its split-K partials atomically: dw = 0 first, unless the caller accumulates
-    hipError_t e = hipMemsetAsync(dw, 0, sizeof(float) * (size_t)R * S * Cin * Cout, stream);
-    if (e != hipSuccess) return (int)e;
-  }
-  return conv2d_bwd_weight_impl(x, dy, dw, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, nullptr, stream);
-}
-
-static int part_of(FsPartHost* ph, long nslab, FsPart& out) {
-  out = FsPart{nullptr, 0};
-  if (ph == nullptr || ph->base == nullptr) return FS_OK;
-  if (nslab > ph->cap) return FS_ERR_ARG;
-  if (nslab > ph->used) ph->used = (int)nslab;
-  out = FsPart{ph->base, ph->stride};
-  return FS_OK;
-}
-
-static int conv2d_bwd_weight_impl(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Ho, int Wo,
-                                  int Cout, int R, int S, int stride, int pad, int dil, FsPartHost* ph, hipStream_t stream) {
-  const long P = (long)B * Ho * Wo;
-  if (g_conv_precision >= 1 && fs_wgrad_split_eligible(Cin, Cout, R, S, stride, pad, dil) &&
-      fits32((size_t)B * H * W * Cin) && fits32((size_t)P * Cout))
-    return fs_wgrad_split(g_conv_precision, x, dy, dw, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, ph, stream);
-  const int tiles = cdiv(Cin, 64) * cdiv(Cout, 64);
-  // one filter row per workgroup for narrow layers (more workgroups, fewer atomics each), the whole 3x3
-  // filter per workgroup once there are >= 9 channel tiles (measured: 64^2/128^2 87-90 TF with 3,
-  // 192^2 106 TF / 960x240 87 TF / 512^2 87 TF with 9; per-tap kernel 71-83 TF).
-  const int wg_mode = tiles >= 9 ? 9 : 3;
-  if (R == 3 && S == 3 && (Cin % 4 == 0) && (Cout % 4 == 0) &&
-      fits32((size_t)B * H * W * Cin) && fits32((size_t)P * Cout)) {
-    const int ng = 9 / wg_mode;
-    long ns = (1024 + (long)tiles * ng - 1) / ((long)tiles * ng);
-    long mx = (P + 127) / 128;
-    if (ns > mx) ns = mx;
-    if (ns < 1) ns = 1;
-    long pp = (P + ns - 1) / ns;
-    pp = ((pp + BK - 1) / BK) * BK;
-    ns = (P + pp - 1) / pp;
-    WgradArgs a{x, dy, dw, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, (int)pp, tiles, 9, (int)ns, FsPart{nullptr, 0}};
-    if (part_of(ph, ns, a.part) != FS_OK) return FS_ERR_ARG;
-    dim3 grid((unsigned)(tiles * ng * ns));
-    if (wg_mode == 3) hipLaunchKernelGGL(conv_wgrad_taps_kernel<3>, grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL(conv_wgrad_taps_kernel<9>, grid, dim3(256), 0, stream, a);
     FS_LAUNCH_CHECK();
-    return FS_OK;
-  }
-  long nsplit = (2048 + (long)tiles * R * S - 1) / ((long)tiles * R * S);
-  long maxsplit = (P + 255) / 256;
-  if (nsplit > maxsplit) nsplit = maxsplit;
-  if (nsplit < 1) nsplit = 1;
-  long pps = (P + nsplit - 1) / nsplit;
-  pps = ((pps + BK - 1) / BK) * BK;
-  nsplit = (P + pps - 1) / pps;
-  WgradArgs a{x, dy, dw, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, (int)pps, tiles, R * S, (int)nsplit, FsPart{nullptr, 0}};
-  if (part_of(ph, nsplit, a.part) != FS_OK) return FS_ERR_ARG;
-  dim3 grid((unsigned)(tiles * R * S * nsplit));
-  if ((Cin % 4 == 0) && (Cout % 4 == 0))
-    hipLaunchKernelGGL(conv_wgrad_kernel<true>, grid, dim3(256), 0, stream, a);
-  else
-    hipLaunchKernelGGL(conv_wgrad_kernel<false>, grid, dim3(256), 0, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
+    return (int)FS_OK;
+  });
 }
 
 }  // extern "C"

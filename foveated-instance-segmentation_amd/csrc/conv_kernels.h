@@ -94,19 +94,56 @@ __device__ __forceinline__ void fs_wgrad_out(float* dw, const FsPart p, int slab
 bool fs_deterministic();
 // dw[i] = (accumulate ? dw[i] : 0) + part[0][i] + part[1][i] + ... + part[nslab-1][i], in that order
 int fs_wgrad_reduce(float* part, int nslab, long n, float* dw, int accumulate, hipStream_t stream);
-// host-side bookkeeping of one bwd-weight call in deterministic mode: slabs available / slabs the launches used
-struct FsPartHost { float* base; long stride; long cap; int used; int force_planes; };      // force_planes: the strided 3x3 layer must take the one-launch kernel (every slab element written: no memset)
 
-// ---- conv_wgrad.hip: split-precision weight gradient, one launch per tap class (dw zeroed by the caller or accumulated into) ----
+// ---- conv_wgrad.hip: the bwd-weight plan, and the split-precision weight gradient kernels it launches ----
 // any square filter / stride whose tap classes have at most 2 taps per dimension (3x3 s2/s4, 1x1 any stride), plus 3x3 s1
 bool fs_wgrad_split_eligible(int Cin, int Cout, int R, int S, int stride, int pad, int dil);
 bool fs_wgrad_gather_s2(int Cin, int R, int S, int stride);
 bool fs_linear_wgrad_eligible(int mode, long rows, int Cin, int Cout);
-// part (nullable): deterministic mode.  fs_linear_wgrad: bpart (nullable) = slabs of Cout floats for the bias column sums, 4 per split.
-int fs_linear_wgrad(const float* x, const float* dy, float* dw, float* dbias, long rows, int Cin, int Cout, FsPartHost* part, float* bpart,
-                    hipStream_t stream);
-int fs_wgrad_split(int mode, const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S,
-                   int stride, int pad, FsPartHost* part, hipStream_t stream);
+// public ids (include/fovealseg.h fs_conv2d_bwd_weight_plan); fs_wgrad_plan has the order in which they are tried
+enum FsWgradRoute {
+  FS_WG_GENERIC = 0,      // conv_wgrad_kernel<false>  (conv.hip)
+  FS_WG_GENERIC_VEC = 1,  // conv_wgrad_kernel<true>   (conv.hip)
+  FS_WG_TAPS3 = 2,        // conv_wgrad_taps_kernel<3> (conv.hip)
+  FS_WG_TAPS9 = 3,        // conv_wgrad_taps_kernel<9> (conv.hip)
+  FS_WG_CLASS33 = 4,      // conv_wgrad_class_kernel<P, 3, 3>, one launch
+  FS_WG_WINO = 5,         // conv_wgrad_wino_kernel
+  FS_WG_LINEAR = 6,       // linear_wgrad_kernel over plain rows
+  FS_WG_GATHER = 7,       // linear_wgrad_kernel over gathered rows, all taps in one launch
+  FS_WG_PLANES = 8,       // conv_wgrad_planes_kernel
+  FS_WG_CLASSES = 9,      // conv_wgrad_class_kernel<P, 1..2, 1..2>, one launch per tap class
+  FS_WG_NROUTES
+};
+enum FsWgradAccum {
+  FS_WG_ATOMIC_ZEROED = 0,  // fp32 atomics into dW after a memset of it
+  FS_WG_ATOMIC_ADD = 1,     // fp32 atomics into the caller's accumulating dW
+  FS_WG_SLABS_ZEROED = 2,   // memset of `cap` slabs, plain stores, ordered reduce (deterministic mode: a split without pixels writes nothing)
+  FS_WG_SLABS_STORED = 3    // plain stores into slabs the launch writes completely, ordered reduce
+};
+// one launch: patch shape (rows x columns; the transform-domain kernel: rows x pixel pairs; 0 where the kernel has none), split count, and
+// patches (rows of the linear kernel, pixels of the fp32 kernels) per split
+struct FsWgradStep { int Ph, Pw, nsplit, per_split; };
+struct FsWgradPlan {
+  bool ok;               // the launch is accepted: a known kernel, and where it writes slabs they fit `cap` and the scratch holds `cap` slabs
+  int mode;              // precision mode the plan was made for
+  int route, accum;      // FsWgradRoute, FsWgradAccum
+  int tile;              // LINEAR / GATHER: tile variant of linear_wgrad_kernel, 1-4
+  int prio;              // class kernel: WgArgs::prio
+  int nlaunch;           // conv kernel launches (memsets and the reduce not counted)
+  FsWgradStep step[9];
+  long wgs;              // workgroups of all launches together
+  int threads;           // per workgroup
+  int slabs;             // slab rows the launches write = slabs the reduce sums; 0 with atomics
+  long cap;              // fs_wgrad_slab_cap of the shape: slabs the scratch must hold (and that SLABS_ZEROED zeroes)
+};
+long fs_wgrad_slab_cap(int mode, int Cin, int Cout, int R, int S, int stride, int pad, int dil);
+// slabs of R*S*Cin*Cout floats a caller must provide for this layer: the cap in deterministic mode and for the layers that store, else 0
+long fs_wgrad_ws_slabs(int mode, bool det, int Cin, int Cout, int R, int S, int stride, int pad, int dil);
+FsWgradPlan fs_wgrad_plan(int mode, bool det, bool accumulate, bool has_ws, long ws_bytes, int B, int H, int W, int Cin, int Ho, int Wo, int Cout,
+                          int R, int S, int stride, int pad, int dil);
+FsWgradPlan fs_linear_wgrad_plan(bool det, bool accumulate, long rows, int Cin, int Cout);
+int fs_wgrad_launch(const FsWgradPlan& p, const float* x, const float* dy, float* dw, float* dbias, FsPart part, float* bpart, int B, int H, int W,
+                    int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, hipStream_t stream);
 
 // ---- conv_s2bwd.hip: bwd-data of a 3x3 / stride 2 / pad 1 convolution, the four output parities in one launch ----
 bool fs_s2bwd_eligible(int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil);

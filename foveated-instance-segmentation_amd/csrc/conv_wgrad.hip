@@ -23,6 +23,7 @@
 #include <stdio.h>
 #include <math.h>
 #include <stdlib.h>
+#include "conv_wgrad_diag.h"
 
 namespace {
 
@@ -946,63 +947,6 @@ static int splitk_model(long rounds, int ntile, double t_round_us, double tile_k
   return n < 1.0 ? 1 : (n > 4096.0 ? 4096 : (int)(n + 0.5));
 }
 
-// deterministic mode: the launch's slabs must fit the caller's workspace; note how many it used
-static int part_claim(FsPartHost* ph, int nslab, FsPart& out) {
-  out.base = nullptr; out.stride = 0;
-  if (ph == nullptr || ph->base == nullptr) return FS_OK;
-  if (nslab > ph->cap) return FS_ERR_ARG;
-  if (nslab > ph->used) ph->used = nslab;
-  out.base = ph->base; out.stride = ph->stride;
-  return FS_OK;
-}
-
-template <class P, int WM, int WN, int MI, int NI>
-int launch_linear_wgrad(LwArgs a, int target, FsPartHost* ph, hipStream_t stream) {
-  a.tiles_ci = cdiv(a.Cin, WM * MI * 32); a.tiles_co = cdiv(a.Cout, WN * NI * 32);
-  const int ntile = a.tiles_ci * a.tiles_co;
-  int nsplit = target / ntile;
-  if (nsplit < 1) nsplit = 1;
-  {
-    const int nm = splitk_model(cdiv(a.rows, 32), ntile, 1.0, WM * MI * WN * NI * 4.0);      // a 32-row chunk ~ 1 us; tile = 32 x 32 x 4 B per block pair
-    if (nm < nsplit) nsplit = nm;
-  }
-  a.rows_per_split = cdiv(cdiv(a.rows, nsplit), 32) * 32;
-  nsplit = cdiv(a.rows, a.rows_per_split);
-  if (part_claim(ph, nsplit, a.part) != FS_OK) return FS_ERR_ARG;
-  if (a.part.base == nullptr) a.bpart = nullptr;
-  const int ntap = a.ntap > 0 ? a.ntap : 1;
-  hipLaunchKernelGGL((linear_wgrad_kernel<P, WM, WN, MI, NI>), dim3((unsigned)(ntile * nsplit * ntap)), dim3(256), 0, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
-// Tile and split choice, from a sweep over the SegFormer-B5 and HRNet 1x1 layers (profiles/r03/linear_wgrad_sweep.txt): narrow operands
-// take a 64-wide tile on their side; wide layers take 128 x 128 over 512 workgroups while a split still sees >= 512 rows (the row loop
-// dominates), otherwise 64 x 64 over 1024 (a quarter of the atomics per workgroup: the epilogue dominates).
-int run_linear_wgrad(LwArgs l, FsPartHost* ph, hipStream_t stream) {
-  static const int force = FS_ENV_INT("FS_LW_TILE", 0);       // kernel A/B builds only (common.h), read once
-  static const int force_wgs = FS_ENV_INT("FS_LW_WGS", 0);
-  int tile, target = 512;
-  if (l.Cin <= 64 && l.Cout <= 64) tile = 1;
-  else if (l.Cin <= 64) tile = 2;
-  else if (l.Cout <= 64) tile = 3;
-  else {
-    const int ntile = cdiv(l.Cin, 128) * cdiv(l.Cout, 128);
-    const int nsplit = 512 / ntile > 0 ? 512 / ntile : 1;
-    tile = l.rows / nsplit >= 512 ? 4 : 1;
-    if (tile == 1) target = 1024;
-  }
-  if (l.ntap > 0) target = 1024 / l.ntap > 64 ? 1024 / l.ntap : 64;      // gathered rows: ~1000 workgroups over all taps together
-  if (force >= 1 && force <= 4) tile = force;
-  if (force_wgs > 0) target = force_wgs;
-  switch (tile) {
-    case 1: return launch_linear_wgrad<PrecX3, 2, 2, 1, 1>(l, target, ph, stream);      //  64 x  64
-    case 2: return launch_linear_wgrad<PrecX3, 1, 4, 2, 1>(l, target, ph, stream);      //  64 x 128
-    case 3: return launch_linear_wgrad<PrecX3, 4, 1, 1, 2>(l, target, ph, stream);      // 128 x  64
-    default: return launch_linear_wgrad<PrecX3, 2, 2, 2, 2>(l, target, ph, stream);     // 128 x 128
-  }
-}
-
 // Ph rows x PP pairs <= 32 pairs, (Ph + 2) PP <= 48 slots, PP >= 1: fewest patches, then largest fill
 void choose_wgrad_wino_patch(int H, int W, int& Ph, int& PP) {
   const int wp = W / 2;
@@ -1032,111 +976,6 @@ void choose_wgrad_patch(int H, int W, int NR, int NS, int& Ph, int& Pw) {
     }
 }
 
-}  // namespace
-
-namespace {
-template <class P, int NR, int NS>
-int launch_class(WgArgs a, int ntile, FsPartHost* ph, hipStream_t stream) {
-  choose_wgrad_patch(a.H, a.W, NR, NS, a.Ph, a.Pw);
-  a.tiles_y = cdiv(a.H, a.Ph); a.tiles_x = cdiv(a.W, a.Pw);
-  a.magic_wh = div_magic1(a.Pw + NS - 1); a.magic_pw = div_magic1(a.Pw);
-  a.npatch = a.B * a.tiles_y * a.tiles_x;
-  // 512 patch streams = 8 waves on every CU, never a short second round: 512 workgroups (two per CU).
-  // (A wave-specialised variant -- 4 producer + 4 consumer waves, double-buffered LDS, one workgroup per CU -- measured
-  // +14 % on this kernel alone and -1 % on the training step, where kernels of other HRNet branches share the CUs.)
-  int nsplit = 512 / ntile;
-  if (nsplit < 1) nsplit = 1;
-  if (nsplit > a.npatch) nsplit = a.npatch;
-  {
-    const int nm = splitk_model(a.npatch, ntile, 0.75 * NR * NS, 16.0 * NR * NS);      // ~0.75 us and 16 KB per tap and patch round
-    if (nm < nsplit) nsplit = nm;
-  }
-  a.patches_per_split = cdiv(a.npatch, nsplit);
-  nsplit = cdiv(a.npatch, a.patches_per_split);
-  if (part_claim(ph, nsplit, a.part) != FS_OK) return FS_ERR_ARG;
-  {
-    // kernel A/B builds only.  Measured (profiles/r04/wgrad_phase_trace.txt): the rounds of the two workgroups of a CU even out (14 500 /
-    // 25 000 -> 15 900 cycles each) and the MFMA loops of the launch end 18 % earlier -- but then all 512 workgroups reach their split-K
-    // atomics together instead of half of them early, the launch takes 4 % LONGER alone and the training step is unchanged (the
-    // step follows its switching work, not its stalls: DESIGN.md 4c): off.
-    static const int prio = FS_ENV_INT("FS_WGRAD_PRIO", 0);
-    a.prio = prio;
-  }
-#ifdef FS_WGRAD_TRACE
-  static long long* dbg = nullptr;
-  const long nwg = (long)ntile * nsplit;
-  const bool traced = NR == 3 && NS == 3 && nwg <= 4096 && a.patches_per_split >= 6;
-  if (traced) {
-    if (dbg == nullptr && hipMalloc(&dbg, sizeof(long long) * 4096 * 4 * 4 * 8) != hipSuccess) return FS_ERR_ARG;
-    if (hipMemsetAsync(dbg, 0, sizeof(long long) * nwg * 4 * 4 * 8, stream) != hipSuccess) return FS_ERR_ARG;
-  }
-  a.dbg = traced ? dbg : nullptr;
-#endif
-  hipLaunchKernelGGL((conv_wgrad_class_kernel<P, NR, NS>), dim3((unsigned)(ntile * nsplit)), dim3(256), 0, stream, a);
-  FS_LAUNCH_CHECK();
-#ifdef FS_WGRAD_TRACE
-  if (traced) {
-    static long long host[4096 * 4 * 4 * 8];
-    if (hipStreamSynchronize(stream) != hipSuccess || hipMemcpy(host, dbg, sizeof(long long) * nwg * 128, hipMemcpyDeviceToHost) != hipSuccess) return FS_ERR_ARG;
-    // phases: [0->1] address + issue loads, [1->2] barrier (partners still multiplying), [2->3] loads landed, [3->4] split + LDS stores,
-    // [4->5] barrier, [5->6] MFMA loop, [6->0'] loop overhead to the next round's top; per wave, rounds 2..4 (round 5 has no successor stamp)
-    double sum[8] = {0}, skew_mfma = 0, round_len = 0; long n = 0, nr = 0;
-    double par_mfma[2] = {0, 0}, par_round[2] = {0, 0}, par_start[2] = {0, 0}; long par_n[2] = {0, 0};
-    long long tmin = 0;
-    for (long w_ = 0; w_ < nwg; ++w_) { const long long v = host[(w_ * 4 * 4) * 8]; if (v != 0 && (tmin == 0 || v < tmin)) tmin = v; }
-    for (long w_ = 0; w_ < nwg; ++w_) {
-      for (int it = 0; it < 3; ++it) {
-        long long end_min = 0, end_max = 0;
-        for (int wv = 0; wv < 4; ++wv) {
-          const long long* t = host + ((w_ * 4 + wv) * 4 + it) * 8;
-          const long long* tn = t + 8;
-          if (t[0] == 0 || t[6] == 0 || tn[0] == 0) continue;
-          for (int i = 0; i < 6; ++i) sum[i] += (double)(t[i + 1] - t[i]);
-          sum[6] += (double)(tn[0] - t[6]);
-          round_len += (double)(tn[0] - t[0]);
-          {
-            const int par = (int)((unsigned)host[((w_ * 4 + wv) * 4) * 8 + 7] & 1u);
-            par_mfma[par] += (double)(t[6] - t[5]); par_round[par] += (double)(tn[0] - t[0]); ++par_n[par];
-            if (it == 0) par_start[par] += (double)(t[0] - tmin);
-          }
-          ++n;
-          if (wv == 0 || t[6] < end_min) end_min = t[6];
-          if (wv == 0 || t[6] > end_max) end_max = t[6];
-        }
-        skew_mfma += (double)(end_max - end_min); ++nr;
-      }
-    }
-    {
-      long hist[16] = {0}; long same = 0, pairs = 0;
-      static int cu_slot[8][16][16][4];      // [xcc guess = wg % 8][se][cu][simd] -> last wave_id seen
-      for (auto& a0 : cu_slot) for (auto& a1 : a0) for (auto& a2 : a1) for (int& v : a2) v = -1;
-      for (long w_ = 0; w_ < nwg; ++w_)
-        for (int wv = 0; wv < 4; ++wv) {
-          const unsigned id = (unsigned)host[((w_ * 4 + wv) * 4) * 8 + 7];
-          const int wid = id & 15, simd = (id >> 4) & 3, cu = (id >> 8) & 15, se = (id >> 13) & 7;
-          ++hist[wid];
-          int& prev = cu_slot[w_ % 8][se][cu][simd];
-          if (prev >= 0) { ++pairs; if ((prev & 1) == (wid & 1)) ++same; }
-          prev = wid;
-        }
-      fprintf(stderr, "wgrad trace: wave_id histogram");
-      for (int i = 0; i < 16; ++i) if (hist[i]) fprintf(stderr, " %d:%ld", i, hist[i]);
-      fprintf(stderr, " | SIMDs with two traced waves %ld, of them with EQUAL slot parity %ld\n", pairs, same);
-    }
-    if (n > 0) {
-      fprintf(stderr, "wgrad trace B%d %dx%d %d->%d patches/split %d grid %ld: round %.0f cyc =", a.B, a.H, a.W, a.Cin, a.Cout, a.patches_per_split, nwg, round_len / n);
-      const char* nm[7] = {"issue", "barrier1", "loads", "split", "barrier2", "mfma", "next"};
-      for (int i = 0; i < 7; ++i) fprintf(stderr, " %s %.0f", nm[i], sum[i] / n);
-      fprintf(stderr, " | spread of the four waves' MFMA-loop ends %.0f", skew_mfma / nr);
-      for (int par = 0; par < 2; ++par)
-        if (par_n[par]) fprintf(stderr, " | slot %d: mfma %.0f round %.0f round-2 top at +%.0f", par, par_mfma[par] / par_n[par], par_round[par] / par_n[par], par_start[par] * 3 / par_n[par]);
-      fprintf(stderr, "\n");
-    }
-  }
-#endif
-  return FS_OK;
-}
-
 // Plane table of a 3x3 filter with stride st (2 or 3) for a Ph x Pw patch; returns the slot count
 static int planes_plan(MpArgs& a) {
   const int st = a.st, nres = st < 3 ? st : 3;
@@ -1161,77 +1000,138 @@ static int planes_plan(MpArgs& a) {
 }
 
 // Ph x Pw <= 32 dY pixels, all planes together <= 160 slots: fewest patches x (k-steps + 1.5), as choose_wgrad_patch
-static bool choose_planes_patch(MpArgs& a) {
+static bool choose_planes_patch(int H, int W, int st, int& Ph, int& Pw) {
+  MpArgs a;
+  a.st = st;
   long best = -1;
-  int bh = 0, bw = 0;
-  for (int pw = 2; pw <= MP_YP && pw <= a.W + 1; ++pw)
-    for (int ph = 1; ph <= MP_YP && ph <= a.H + 1; ++ph) {
+  for (int pw = 2; pw <= MP_YP && pw <= W + 1; ++pw)
+    for (int ph = 1; ph <= MP_YP && ph <= H + 1; ++ph) {
       if (ph * pw > MP_YP) continue;
       a.Ph = ph; a.Pw = pw;
       if (planes_plan(a) > MP_XS) continue;
-      const long patches = (long)cdiv(a.H, ph) * cdiv(a.W, pw);
+      const long patches = (long)cdiv(H, ph) * cdiv(W, pw);
       const long cost = patches * (2 * cdiv(ph * pw, 16) + 3) * 10000 + ((pw & 3) ? 5000 : 0) + a.nslots;
-      if (best < 0 || cost < best) { best = cost; bh = ph; bw = pw; }
+      if (best < 0 || cost < best) { best = cost; Ph = ph; Pw = pw; }
     }
-  if (best < 0) return false;
-  a.Ph = bh; a.Pw = bw;
-  planes_plan(a);
-  return true;
+  return best >= 0;
 }
 
-template <class P>
-int launch_planes(MpArgs a, FsPartHost* ph, hipStream_t stream) {
-  if (!choose_planes_patch(a)) return FS_ERR_ARG;
-  a.tiles_y = cdiv(a.H, a.Ph); a.tiles_x = cdiv(a.W, a.Pw);
-  a.magic_pw = div_magic1(a.Pw);
-  a.npatch = a.B * a.tiles_y * a.tiles_x;
-  const int ntile = a.tiles_ci * a.tiles_co;
-  static const int target = FS_ENV_INT("FS_WGRAD_S2_WGS", 512);      // kernel A/B builds only
+bool fits32(size_t elements) { return elements * 4 < 4294967000UL; }      // 32-bit byte offsets in the buffer descriptors
+
+// ---- the plan: one step per launch -------------------------------------------------------------------------------------------------
+
+// `target` workgroups over ntile channel tiles, at most one split per patch, fewer where the split-K model says so (model_us / model_kb:
+// time of one patch round and KB of one workgroup's tile; 0 = no model)
+FsWgradStep patch_split(int Ph, int Pw, int npatch, int ntile, int target, double model_us, double model_kb) {
   int nsplit = target / ntile;
   if (nsplit < 1) nsplit = 1;
-  if (nsplit > a.npatch) nsplit = a.npatch;
-  a.patches_per_split = cdiv(a.npatch, nsplit);
-  nsplit = cdiv(a.npatch, a.patches_per_split);
-  if (part_claim(ph, nsplit, a.part) != FS_OK) return FS_ERR_ARG;
-  hipLaunchKernelGGL((conv_wgrad_planes_kernel<P>), dim3((unsigned)(ntile * nsplit)), dim3(256), 0, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
+  if (nsplit > npatch) nsplit = npatch;
+  if (model_us > 0.0) {
+    const int nm = splitk_model(npatch, ntile, model_us, model_kb);
+    if (nm < nsplit) nsplit = nm;
+  }
+  const int per = cdiv(npatch, nsplit);
+  return FsWgradStep{Ph, Pw, cdiv(npatch, per), per};
 }
 
-template <class P>
-int run_classes(WgArgs& a, int ntile, int R, int S, int stride, int pad, FsPartHost* ph, hipStream_t stream) {
-  for (int r0 = 0; r0 < stride && r0 < R; ++r0)
-    for (int s0 = 0; s0 < stride && s0 < S; ++s0) {
-      const int nR = (R - r0 + stride - 1) / stride, nS = (S - s0 + stride - 1) / stride;
-      a.cy = r0 - pad; a.cx = s0 - pad; a.rbase = r0; a.rstep = stride; a.sbase = s0; a.sstep = stride;
-      int e = FS_ERR_ARG;
-      if (nR == 3 && nS == 3) e = launch_class<P, 3, 3>(a, ntile, ph, stream);
-      else if (nR == 2 && nS == 2) e = launch_class<P, 2, 2>(a, ntile, ph, stream);
-      else if (nR == 2 && nS == 1) e = launch_class<P, 2, 1>(a, ntile, ph, stream);
-      else if (nR == 1 && nS == 2) e = launch_class<P, 1, 2>(a, ntile, ph, stream);
-      else if (nR == 1 && nS == 1) e = launch_class<P, 1, 1>(a, ntile, ph, stream);
-      if (e != FS_OK) return e;
-    }
-  return FS_OK;
+// the fp32 kernels of conv.hip: about `target` workgroups over `groups` (channel tile, tap group) pairs, at least min_pixels output pixels
+// per split, whole K-steps of 32 pixels
+FsWgradStep pixel_split(long P, long groups, long target, long min_pixels) {
+  long ns = (target + groups - 1) / groups;
+  const long mx = (P + min_pixels - 1) / min_pixels;
+  if (ns > mx) ns = mx;
+  if (ns < 1) ns = 1;
+  long pp = (P + ns - 1) / ns;
+  pp = ((pp + 31) / 32) * 32;
+  return FsWgradStep{0, 0, (int)((P + pp - 1) / pp), (int)pp};
 }
+
+constexpr long NO_SPLIT_LIMIT = 1L << 40;
+// linear_wgrad_kernel's tile variants: 1 = 64 x 64, 2 = 64 x 128, 3 = 128 x 64, 4 = 128 x 128 (Cin x Cout)
+constexpr int LW_TILE_CI[5] = {0, 64, 64, 128, 128}, LW_TILE_CO[5] = {0, 64, 128, 64, 128};
+
+// Tile and split choice, from a sweep over the SegFormer-B5 and HRNet 1x1 layers (profiles/r03/linear_wgrad_sweep.txt): narrow operands
+// take a 64-wide tile on their side; wide layers take 128 x 128 over 512 workgroups while a split still sees >= 512 rows (the row loop
+// dominates), otherwise 64 x 64 over 1024 (a quarter of the atomics per workgroup: the epilogue dominates).
+// max_split: the slabs the caller's scratch holds where the splits go to slabs (the gathered-row target below is not bounded by
+// fs_wgrad_slab_cap on 128 x 128 tiles), else no limit.
+void plan_linear(FsWgradPlan& p, long rows, int Cin, int Cout, int ntap, long max_split) {
+  static const int force = FS_ENV_INT("FS_LW_TILE", 0);       // kernel A/B builds only (common.h), read once
+  static const int force_wgs = FS_ENV_INT("FS_LW_WGS", 0);
+  int tile, target = 512;
+  if (Cin <= 64 && Cout <= 64) tile = 1;
+  else if (Cin <= 64) tile = 2;
+  else if (Cout <= 64) tile = 3;
+  else {
+    const int ntile = cdiv(Cin, 128) * cdiv(Cout, 128);
+    const int nsplit = 512 / ntile > 0 ? 512 / ntile : 1;
+    tile = (int)rows / nsplit >= 512 ? 4 : 1;
+    if (tile == 1) target = 1024;
+  }
+  if (ntap > 0) target = 1024 / ntap > 64 ? 1024 / ntap : 64;      // gathered rows: ~1000 workgroups over all taps together
+  if (force >= 1 && force <= 4) tile = force;
+  if (force_wgs > 0) target = force_wgs;
+  const int ntile = cdiv(Cin, LW_TILE_CI[tile]) * cdiv(Cout, LW_TILE_CO[tile]);
+  int nsplit = target / ntile;
+  if (nsplit < 1) nsplit = 1;
+  {
+    // a 32-row chunk ~ 1 us; tile = 32 x 32 x 4 B per block pair
+    const int nm = splitk_model(cdiv((int)rows, 32), ntile, 1.0, (LW_TILE_CI[tile] / 32) * (LW_TILE_CO[tile] / 32) * 4.0);
+    if (nm < nsplit) nsplit = nm;
+  }
+  if (nsplit > max_split) nsplit = (int)max_split;
+  const int per = cdiv(cdiv((int)rows, nsplit), 32) * 32;
+  p.tile = tile;
+  p.nlaunch = 1;
+  p.step[0] = FsWgradStep{0, 0, cdiv((int)rows, per), per};
+  p.wgs = (long)ntile * p.step[0].nsplit * (ntap > 0 ? ntap : 1);
+  p.threads = 256;
+  p.slabs = p.step[0].nsplit;
+}
+
+// the transform-domain kernel's launch: one 512-thread workgroup per CU
+FsWgradStep plan_wino_step(int B, int H, int W, int ntile) {
+  int Ph, PP;
+  choose_wgrad_wino_patch(H, W, Ph, PP);
+  return patch_split(Ph, PP, B * cdiv(H, Ph) * cdiv(W / 2, PP), ntile, 256, 0.0, 0.0);
+}
+
+// Strided 3x3 layers (one round of <= 512 workgroups: ~50-85 us of patch rounds, then ~80 us of split-K atomics with nothing left to
+// overlap them): partial tiles by plain stores into per-split slabs + one ordered reduce launch instead of the atomics, in the default
+// mode too -- the machinery of deterministic mode, without the memset (the one-launch kernel writes every element of every slab it uses).
+bool wgrad_stores(int mode, int Cin, int Cout, int R, int S, int stride, int pad, int dil) {
+  static const int pol = FS_ENV_INT("FS_WGRAD_STORE", 1);      // kernel A/B builds only: 0 atomics everywhere, 2 also the 3x3 stride-1 class kernel
+  if (pol == 0 || mode < 1 || R != 3 || S != 3 || !fs_wgrad_split_eligible(Cin, Cout, R, S, stride, pad, dil)) return false;
+  if (mode == 1 && fs_wgrad_gather_s2(Cin, R, S, stride) && pol != 3) return false;      // those run as gathered-row GEMMs (step 6 of the plan)
+  return stride == 2 || stride == 3 || (pol == 2 && stride == 1 && pad == 1);
+}
+
 }  // namespace
+
+// slabs one bwd-weight call can need: an upper bound of the split counts fs_wgrad_plan chooses, from the layer's shape alone (the scratch
+// is sized before batch and image size are known); tests/test_wgrad_dispatch_table.py holds the plan to it
+long fs_wgrad_slab_cap(int mode, int Cin, int Cout, int R, int S, int stride, int pad, int dil) {
+  const long tiles = (long)cdiv(Cin, 64) * cdiv(Cout, 64);
+  if (mode >= 1 && fs_wgrad_split_eligible(Cin, Cout, R, S, stride, pad, dil)) {
+    if ((R == 1 && S == 1 && stride == 1 && pad == 0) || (stride >= R && stride >= S))
+      return 2048 / tiles + 2;      // linear_wgrad_kernel (plain or gathered rows): up to 1024 workgroups of 64 x 64 tiles, 512 of wider ones
+    return 512 / tiles + 2;                                                      // class kernels: 512 workgroups; transform-domain kernel: 2 x 256
+  }
+  if (R == 3 && S == 3 && Cin % 4 == 0 && Cout % 4 == 0) return 1024 / tiles + 2;
+  return 2048 / (tiles * R * S) + 2;
+}
+
+long fs_wgrad_ws_slabs(int mode, bool det, int Cin, int Cout, int R, int S, int stride, int pad, int dil) {
+  return det || wgrad_stores(mode, Cin, Cout, R, S, stride, pad, dil) ? fs_wgrad_slab_cap(mode, Cin, Cout, R, S, stride, pad, dil) : 0;
+}
 
 // dW and dbias of a linear layer in one launch (bf16x3 only; include/fovealseg.h fs_linear_bwd_weight_bias)
 bool fs_linear_wgrad_eligible(int mode, long rows, int Cin, int Cout) {
   return mode == 1 && rows > 0 && Cin % 4 == 0 && Cout % 4 == 0 && Cin >= 16 && Cout >= 16 &&
          (size_t)rows * Cin * 4 < 4294967000UL && (size_t)rows * Cout * 4 < 4294967000UL;
 }
-int fs_linear_wgrad(const float* x, const float* dy, float* dw, float* dbias, long rows, int Cin, int Cout, FsPartHost* part, float* bpart,
-                    hipStream_t stream) {
-  LwArgs l;
-  l.x = x; l.dy = dy; l.dw = dw; l.dbias = dbias; l.rows = (int)rows; l.Cin = Cin; l.Cout = Cout;
-  l.x_bytes = (unsigned)((size_t)rows * Cin * 4); l.dy_bytes = (unsigned)((size_t)rows * Cout * 4);
-  l.part = FsPart{nullptr, 0}; l.bpart = dbias != nullptr ? bpart : nullptr;
-  l.ntap = 0; l.S = 1; l.Ho = l.Wo = l.Hx = l.Wx = 1; l.st = 1; l.pad = 0;
-  return run_linear_wgrad(l, part, stream);
-}
 
-// strided 3x3 layers whose bwd-weight runs as nine gathered-row GEMMs (policy above); conv.hip keeps them off the store + reduce route
+// strided 3x3 layers whose bwd-weight runs as nine gathered-row GEMMs (step 6 of the plan)
 bool fs_wgrad_gather_s2(int Cin, int R, int S, int stride) { return R == 3 && S == 3 && (stride == 2 || stride == 3) && Cin <= 64; }
 
 bool fs_wgrad_split_eligible(int Cin, int Cout, int R, int S, int stride, int pad, int dil) {
@@ -1242,96 +1142,287 @@ bool fs_wgrad_split_eligible(int Cin, int Cout, int R, int S, int stride, int pa
   return nr <= 2 && (stride < R ? stride : R) <= 3;                        // classes of 1 or 2 taps per dimension, at most 9 classes
 }
 
-// dW of any conv2d with square filter: one launch per tap class (dw zeroed by the caller or accumulated into).  mode: 1 = bf16x3, 2 = f16x2
-int fs_wgrad_split(int mode, const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S,
-                   int stride, int pad, FsPartHost* ph, hipStream_t stream) {
-  if ((size_t)B * H * W * Cin * 4 >= 4294967000UL || (size_t)B * Ho * Wo * Cout * 4 >= 4294967000UL) return FS_ERR_ARG;
-  WgArgs a;
-  a.part = FsPart{nullptr, 0};
-  a.x = x; a.dy = dy; a.dw = dw;
-  a.B = B; a.H = Ho; a.W = Wo; a.Hx = H; a.Wx = W; a.Cin = Cin; a.Cout = Cout;
-  a.sm = stride; a.S = S;
-  a.tiles_ci = cdiv(Cin, 64); a.tiles_co = cdiv(Cout, 64);
-  a.x_bytes = (unsigned)((size_t)B * H * W * Cin * 4);
-  a.dy_bytes = (unsigned)((size_t)B * Ho * Wo * Cout * 4);
-  const int ntile = a.tiles_ci * a.tiles_co;
-  static const int wino_pol = FS_ENV_INT("FS_WGRAD_WINO", 1);      // kernel A/B builds only: 0 never, 2 always
-  const bool wino_wgrad = wino_pol != 0, wino_wgrad_all = wino_pol == 2;
-  if (mode == 1 && wino_wgrad && R == 3 && S == 3 && stride == 1 && pad == 1 && H == Ho && W == Wo && W % 2 == 0 && W >= 2) {
-    // bf16x3, even width: the transform-domain kernel (2/3 of the MFMAs)
-    WwArgs w;
-    w.x = x; w.dy = dy; w.dw = dw; w.B = B; w.H = H; w.W = W; w.Cin = Cin; w.Cout = Cout;
-    choose_wgrad_wino_patch(H, W, w.Ph, w.PP);
-    w.tiles_y = cdiv(H, w.Ph); w.tiles_x = cdiv(W / 2, w.PP);
-    w.npatch = B * w.tiles_y * w.tiles_x;
-    w.tiles_ci = a.tiles_ci; w.tiles_co = a.tiles_co;
-    w.x_bytes = a.x_bytes; w.dy_bytes = a.dy_bytes;
-    w.magic_pp = div_magic1(w.PP);
-    int nsplit = 256 / ntile;                  // one 512-thread workgroup per CU
-    if (nsplit < 1) nsplit = 1;
-    if (nsplit > w.npatch) nsplit = w.npatch;
-    w.patches_per_split = cdiv(w.npatch, nsplit);
-    nsplit = cdiv(w.npatch, w.patches_per_split);
-    // Measured against conv_wgrad_class_kernel in one gpurun call (us, bf16x3, B = 64): 64->64 @ 80x80 207 vs 183, 128->128 @ 40x40 195 vs
-    // 178, 256->256 @ 20x20 218 vs 191, 512->512 @ 10x10 217 vs 209 -- SLOWER where a workgroup sees few patches (one 8-wave workgroup per
-    // CU pays more per barrier round than two independent 4-wave ones, and the doubled split work is not hidden) -- but 960->240 @ 80x80
-    // 7.0 vs 8.1 ms: long pixel loops per channel tile.  So only layers with >= 64 patches per workgroup come here (the C1 heads: 960 -> 240 at B >= 4).
-    if (w.patches_per_split < 64 && !wino_wgrad_all) goto direct;
-    if (part_claim(ph, 2 * nsplit, w.part) != FS_OK) return FS_ERR_ARG;
-    constexpr int lds = PrecX3::NPL * (XT_PLANE + DM_PLANE);
-    {
-      static unsigned long long done = 0ull;
-      int dev = 0;
-      if (hipGetDevice(&dev) != hipSuccess) return FS_ERR_ARG;
-      if (dev < 0 || dev >= 64 || !((done >> dev) & 1ull)) {
-        const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_wino_kernel<PrecX3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-        if (attr != hipSuccess) return (int)attr;
-        if (dev >= 0 && dev < 64) done |= 1ull << dev;
-      }
-    }
-    hipLaunchKernelGGL((conv_wgrad_wino_kernel<PrecX3>), dim3((unsigned)(ntile * nsplit)), dim3(512), lds, stream, w);
-    FS_LAUNCH_CHECK();
-    return FS_OK;
-  }
-direct:
-  static const bool linear_on = FS_ENV_INT("FS_WGRAD_LINEAR", 1) != 0;      // kernel A/B builds only
-  if (mode == 1 && linear_on && R == 1 && S == 1 && stride == 1 && pad == 0 && H == Ho && W == Wo) {
-    LwArgs l;
-    l.x = x; l.dy = dy; l.dw = dw; l.dbias = nullptr; l.rows = B * H * W; l.Cin = Cin; l.Cout = Cout;
-    l.x_bytes = a.x_bytes; l.dy_bytes = a.dy_bytes;
-    l.part = FsPart{nullptr, 0}; l.bpart = nullptr;
-    l.ntap = 0; l.S = 1; l.Ho = l.Wo = l.Hx = l.Wx = 1; l.st = 1; l.pad = 0;
-    return run_linear_wgrad(l, ph, stream);
-  }
+// THE dispatch decision for one bwd-weight problem: kernel, accumulation, patch and split count of every launch, slab rows.  The kernel
+// A/B switches of -DFS_EXPERIMENTS builds (FS_WGRAD_*, FS_LW_*) are read here (and in the helpers above) and nowhere else.
+// Accumulation: deterministic mode -> zeroed slabs + ordered reduce; else, with scratch for the shape's slab cap, the layers of
+// wgrad_stores -> slabs written by plain stores + ordered reduce; else atomics (into a zeroed dW unless the caller accumulates).
+// Route, first match wins:
+//   -- mode 0, or a shape outside fs_wgrad_split_eligible, or a tensor of 4 GB and more: the fp32 kernels of conv.hip --
+//   1. TAPS9, TAPS3         3x3 with channel counts that are multiples of 4 (any stride / dilation), both tensors below 4 GB
+//   2. GENERIC_VEC, GENERIC anything else; float4 loads where the channel counts are multiples of 4
+//   -- split precision --
+//   3. WINO      bf16x3, 3x3 / stride 1 / pad 1, even width, >= 64 patches per workgroup: the transform-domain kernel
+//   4. LINEAR    bf16x3, 1x1 / stride 1 / pad 0: the linear layer's GEMM
+//   5. GATHER    bf16x3, stride >= filter (every tap class is a single tap), and strided 3x3 layers with <= 64 input channels unless
+//                they store: R * S GEMMs over gathered rows in one launch
+//   6. PLANES    3x3 / stride 2 or 3 that stores, or has a single channel tile: all nine taps in one launch over parity planes
+//   7. CLASS33   3x3 / stride 1: one launch of the nine-accumulator class kernel
+//   8. CLASSES   one launch per tap class (1 or 2 taps per dimension)
+FsWgradPlan fs_wgrad_plan(int mode, bool det, bool accumulate, bool has_ws, long ws_bytes, int B, int H, int W, int Cin, int Ho, int Wo, int Cout,
+                          int R, int S, int stride, int pad, int dil) {
+  static const int wino_pol = FS_ENV_INT("FS_WGRAD_WINO", 1);           // kernel A/B builds only: 0 never, 2 always
+  static const bool linear_on = FS_ENV_INT("FS_WGRAD_LINEAR", 1) != 0;  // kernel A/B builds only
+  static const int gather_pol = FS_ENV_INT("FS_WGRAD_GATHER", 1);       // kernel A/B builds only: 0 off, 2 = every strided layer
+  static const int planes_pol = FS_ENV_INT("FS_WGRAD_PLANES", 1);       // kernel A/B builds only: 1 = single-tile layers, 2 = every strided 3x3, 0 = off
+  static const int planes_wgs = FS_ENV_INT("FS_WGRAD_S2_WGS", 512);     // kernel A/B builds only
+  // kernel A/B builds only.  Measured (profiles/r04/wgrad_phase_trace.txt): the rounds of the two workgroups of a CU even out (14 500 /
+  // 25 000 -> 15 900 cycles each) and the MFMA loops of the launch end 18 % earlier -- but then all 512 workgroups reach their split-K
+  // atomics together instead of half of them early, the launch takes 4 % LONGER alone and the training step is unchanged (the
+  // step follows its switching work, not its stalls: DESIGN.md 4c): off.
+  static const int prio = FS_ENV_INT("FS_WGRAD_PRIO", 0);
+
+  FsWgradPlan p{};
+  p.mode = mode; p.prio = prio; p.threads = 256;
+  const long P = (long)B * Ho * Wo, n = (long)R * S * Cin * Cout;
+  const int ntile = cdiv(Cin, 64) * cdiv(Cout, 64);
+  const bool aligned = Cin % 4 == 0 && Cout % 4 == 0;
+  const bool below4g = fits32((size_t)B * H * W * Cin) && fits32((size_t)P * Cout);
+  const bool split = mode >= 1 && below4g && fs_wgrad_split_eligible(Cin, Cout, R, S, stride, pad, dil);
+  const bool same_size = H == Ho && W == Wo;
+
+  p.cap = fs_wgrad_slab_cap(mode, Cin, Cout, R, S, stride, pad, dil);
+  const bool room = has_ws && ws_bytes >= p.cap * n * 4;
+  const bool store = !det && split && room && wgrad_stores(mode, Cin, Cout, R, S, stride, pad, dil);
+  p.accum = det ? FS_WG_SLABS_ZEROED : store ? FS_WG_SLABS_STORED : accumulate ? FS_WG_ATOMIC_ADD : FS_WG_ATOMIC_ZEROED;
+
+  // Measured against conv_wgrad_class_kernel in one run (us, bf16x3, B = 64): 64->64 @ 80x80 207 vs 183, 128->128 @ 40x40 195 vs
+  // 178, 256->256 @ 20x20 218 vs 191, 512->512 @ 10x10 217 vs 209 -- SLOWER where a workgroup sees few patches (one 8-wave workgroup per
+  // CU pays more per barrier round than two independent 4-wave ones, and the doubled split work is not hidden) -- but 960->240 @ 80x80
+  // 7.0 vs 8.1 ms: long pixel loops per channel tile.  So only layers with >= 64 patches per workgroup come here (the C1 heads: 960 -> 240 at B >= 4).
+  FsWgradStep wino{};
+  if (split && mode == 1 && wino_pol != 0 && R == 3 && S == 3 && stride == 1 && pad == 1 && same_size && W % 2 == 0 && W >= 2)
+    wino = plan_wino_step(B, H, W, ntile);
   // ... and so do strided 3x3 layers with <= 64 input channels: there the nine-accumulator kernels are bound by their split-K reduction
   // (512 x 147 KB), while nine GEMMs over gathered rows have 32 KB tiles, prefetch their next chunk during the MFMA phase and read X only
   // 2.25 times (each tap a quarter of the pixels).  Same-box A/B (profiles/r04/wgrad_gather_s2_ab.txt, us): 64 -> 64 @ 80x80 104 -> 75,
   // 64 -> 128 173 -> 138, 64 -> 256 @ 40x40 100 -> 75; 128 -> 256 155 -> 151, 256 -> 512 157 -> 162, 512 -> 512 268 -> 356 (those stay).
-  static const int gather_pol = FS_ENV_INT("FS_WGRAD_GATHER", 1);      // kernel A/B builds only: 0 off, 2 = every strided layer
-  const bool gather_s2 = stride > 1 && (gather_pol == 2 || fs_wgrad_gather_s2(Cin, R, S, stride)) && !(ph != nullptr && ph->force_planes);
-  if (mode == 1 && gather_pol != 0 && ((stride >= R && stride >= S) || gather_s2) && R * S <= 16 &&
-      (R > 1 || stride > 1) && (long)B * Ho * Wo < 2000000000L / (Cin > Cout ? Cin : Cout)) {
-    // every tap class is a single tap (3x3 stride 4, 1x1 stride 2 ...): R * S linear layers over gathered X rows, one launch
-    LwArgs l;
-    l.x = x; l.dy = dy; l.dw = dw; l.dbias = nullptr; l.rows = B * Ho * Wo; l.Cin = Cin; l.Cout = Cout;
-    l.x_bytes = a.x_bytes; l.dy_bytes = a.dy_bytes;
-    l.part = FsPart{nullptr, 0}; l.bpart = nullptr;
-    l.ntap = R * S; l.S = S; l.Ho = Ho; l.Wo = Wo; l.Hx = H; l.Wx = W; l.st = stride; l.pad = pad;
-    return run_linear_wgrad(l, ph, stream);
-  }
-  // Measured in one gpurun call against the per-class launches (profiles/r04/wgrad_s2_planes_ab.txt, us, bf16x3, B = 64): 64 -> 64 @ 80x80
+  const bool gather_s2 = stride > 1 && (gather_pol == 2 || fs_wgrad_gather_s2(Cin, R, S, stride)) && !store;
+  // Measured in one run against the per-class launches (profiles/r04/wgrad_s2_planes_ab.txt, us, bf16x3, B = 64): 64 -> 64 @ 80x80
   // 164 -> 123, but 64 -> 128 @ 80x80 158-165 -> 166-172, 128 -> 256 @ 40x40 167 -> 174, 256 -> 512 @ 20x20 176 -> 177: the launch is one
   // round of 512 workgroups whose time is (patch rounds per workgroup) x ~7 us of load -> split -> barrier -> MFMA latency plus ~80 us
   // of split-K atomics (512 x 147 KB at the L2's one dword per channel and clock), and neither term depends on how the taps are grouped;
-  // only a single channel tile (twice the splits, half the rounds) gains.  planes policy 1 = those layers, 2 = every strided 3x3, 0 = off.
-  static const int planes_pol = FS_ENV_INT("FS_WGRAD_PLANES", 1);      // kernel A/B builds only
-  if (((planes_pol != 0 && (planes_pol == 2 || ntile == 1)) || (ph != nullptr && ph->force_planes)) && R == 3 && S == 3 && (stride == 2 || stride == 3)) {
-    // all nine taps of a strided 3x3 filter in one launch (parity planes of the X halo in LDS)
-    MpArgs m;
-    m.x = x; m.dy = dy; m.dw = dw; m.B = B; m.H = Ho; m.W = Wo; m.Hx = H; m.Wx = W; m.Cin = Cin; m.Cout = Cout;
-    m.st = stride; m.pad = pad; m.tiles_ci = a.tiles_ci; m.tiles_co = a.tiles_co;
-    m.x_bytes = a.x_bytes; m.dy_bytes = a.dy_bytes; m.part = FsPart{nullptr, 0};
-    return mode == 2 ? launch_planes<PrecF16>(m, ph, stream) : launch_planes<PrecX3>(m, ph, stream);
+  // only a single channel tile (twice the splits, half the rounds) gains.  A layer that stores needs the one launch: it writes every
+  // element of every slab it uses, so the slabs need no memset.
+  const bool planes = store || (planes_pol != 0 && (planes_pol == 2 || ntile == 1));
+
+  if (!split) {
+    // one filter row per workgroup for narrow layers (more workgroups, fewer atomics each), the whole 3x3
+    // filter per workgroup once there are >= 9 channel tiles (measured: 64^2/128^2 87-90 TF with 3,
+    // 192^2 106 TF / 960x240 87 TF / 512^2 87 TF with 9; per-tap kernel 71-83 TF).
+    if (R == 3 && S == 3 && aligned && below4g) p.route = ntile >= 9 ? FS_WG_TAPS9 : FS_WG_TAPS3;
+    else p.route = aligned ? FS_WG_GENERIC_VEC : FS_WG_GENERIC;
+  } else if (wino.nsplit > 0 && (wino.per_split >= 64 || wino_pol == 2)) p.route = FS_WG_WINO;
+  else if (mode == 1 && linear_on && R == 1 && S == 1 && stride == 1 && pad == 0 && same_size) p.route = FS_WG_LINEAR;
+  else if (mode == 1 && gather_pol != 0 && ((stride >= R && stride >= S) || gather_s2) && R * S <= 16 && (R > 1 || stride > 1) &&
+           P < 2000000000L / (Cin > Cout ? Cin : Cout)) p.route = FS_WG_GATHER;
+  else if (planes && R == 3 && S == 3 && (stride == 2 || stride == 3)) p.route = FS_WG_PLANES;
+  else p.route = R == 3 && stride == 1 ? FS_WG_CLASS33 : FS_WG_CLASSES;
+
+  p.nlaunch = 1;
+  switch (p.route) {
+    case FS_WG_GENERIC:
+    case FS_WG_GENERIC_VEC:
+      p.step[0] = pixel_split(P, (long)ntile * R * S, 2048, 256);
+      p.wgs = (long)ntile * R * S * p.step[0].nsplit;
+      break;
+    case FS_WG_TAPS3:
+    case FS_WG_TAPS9: {
+      const int groups = p.route == FS_WG_TAPS3 ? 3 : 1;      // workgroups per channel tile and split
+      p.step[0] = pixel_split(P, (long)ntile * groups, 1024, 128);
+      p.wgs = (long)ntile * groups * p.step[0].nsplit;
+      break;
+    }
+    case FS_WG_WINO:
+      p.step[0] = wino;
+      p.wgs = (long)ntile * wino.nsplit;
+      p.threads = 512;
+      break;
+    case FS_WG_LINEAR: plan_linear(p, (long)B * H * W, Cin, Cout, 0, det || store ? p.cap : NO_SPLIT_LIMIT); break;
+    case FS_WG_GATHER: plan_linear(p, P, Cin, Cout, R * S, det || store ? p.cap : NO_SPLIT_LIMIT); break;
+    case FS_WG_PLANES: {
+      int Ph = 0, Pw = 0;
+      if (!choose_planes_patch(Ho, Wo, stride, Ph, Pw)) return p;      // not ok
+      p.step[0] = patch_split(Ph, Pw, B * cdiv(Ho, Ph) * cdiv(Wo, Pw), ntile, planes_wgs, 0.0, 0.0);
+      p.wgs = (long)ntile * p.step[0].nsplit;
+      break;
+    }
+    default:      // FS_WG_CLASS33, FS_WG_CLASSES: the tap classes (r0, s0) = filter taps r0, r0 + stride, ... in fs_wgrad_launch's order
+      // 512 patch streams = 8 waves on every CU, never a short second round: 512 workgroups (two per CU).
+      // (A wave-specialised variant -- 4 producer + 4 consumer waves, double-buffered LDS, one workgroup per CU -- measured
+      // +14 % on this kernel alone and -1 % on the training step, where kernels of other HRNet branches share the CUs.)
+      p.nlaunch = 0;
+      for (int r0 = 0; r0 < stride && r0 < R; ++r0)
+        for (int s0 = 0; s0 < stride && s0 < S; ++s0) {
+          const int nR = (R - r0 + stride - 1) / stride, nS = (S - s0 + stride - 1) / stride;
+          if (!((nR == 3 && nS == 3) || (nR <= 2 && nS <= 2))) return p;      // no such class kernel: not ok
+          int Ph, Pw;
+          choose_wgrad_patch(Ho, Wo, nR, nS, Ph, Pw);
+          // ~0.75 us and 16 KB per tap and patch round
+          p.step[p.nlaunch] = patch_split(Ph, Pw, B * cdiv(Ho, Ph) * cdiv(Wo, Pw), ntile, 512, 0.75 * nR * nS, 16.0 * nR * nS);
+          p.wgs += (long)ntile * p.step[p.nlaunch].nsplit;
+          ++p.nlaunch;
+        }
+      break;
   }
-  return mode == 2 ? run_classes<PrecF16>(a, ntile, R, S, stride, pad, ph, stream) : run_classes<PrecX3>(a, ntile, R, S, stride, pad, ph, stream);
+  for (int i = 0; i < p.nlaunch; ++i)
+    if (p.step[i].nsplit > p.slabs) p.slabs = p.step[i].nsplit;
+  if (p.route == FS_WG_WINO) p.slabs *= 2;      // the two component-pair waves of a workgroup write a slab each
+  const bool slabs = p.accum == FS_WG_SLABS_ZEROED || p.accum == FS_WG_SLABS_STORED;
+  if (!slabs) p.slabs = 0;
+  p.ok = !slabs || (room && p.slabs <= p.cap);
+  return p;
+}
+
+// fs_linear_bwd_weight_bias: the LINEAR route over `rows` rows, whatever the switches say (the caller checks its scratch: dW slabs + bias slabs)
+FsWgradPlan fs_linear_wgrad_plan(bool det, bool accumulate, long rows, int Cin, int Cout) {
+  FsWgradPlan p{};
+  p.mode = 1; p.route = FS_WG_LINEAR;
+  p.accum = det ? FS_WG_SLABS_ZEROED : accumulate ? FS_WG_ATOMIC_ADD : FS_WG_ATOMIC_ZEROED;
+  p.cap = fs_wgrad_slab_cap(1, Cin, Cout, 1, 1, 1, 0, 1);
+  plan_linear(p, rows, Cin, Cout, 0, det ? p.cap : NO_SPLIT_LIMIT);
+  if (!det) p.slabs = 0;
+  p.ok = p.slabs <= p.cap;
+  return p;
+}
+
+// ---- the launches of a plan -----------------------------------------------------------------------------------------------------------
+namespace {
+
+template <class P, int NR, int NS>
+int launch_class(WgArgs a, int ntile, const FsWgradStep& s, hipStream_t stream) {
+  a.Ph = s.Ph; a.Pw = s.Pw;
+  a.tiles_y = cdiv(a.H, a.Ph); a.tiles_x = cdiv(a.W, a.Pw);
+  a.magic_wh = div_magic1(a.Pw + NS - 1); a.magic_pw = div_magic1(a.Pw);
+  a.npatch = a.B * a.tiles_y * a.tiles_x;
+  a.patches_per_split = s.per_split;
+  const int nsplit = s.nsplit;
+#ifdef FS_WGRAD_TRACE
+  const bool traced = NR == 3 && NS == 3;
+  a.dbg = nullptr;
+  if (traced && wgrad_trace_begin(a, ntile, nsplit, stream) != FS_OK) return FS_ERR_ARG;
+#endif
+  hipLaunchKernelGGL((conv_wgrad_class_kernel<P, NR, NS>), dim3((unsigned)(ntile * nsplit)), dim3(256), 0, stream, a);
+  FS_LAUNCH_CHECK();
+#ifdef FS_WGRAD_TRACE
+  if (traced && wgrad_trace_report(a, ntile, nsplit, stream) != FS_OK) return FS_ERR_ARG;
+#endif
+  return FS_OK;
+}
+
+template <class P>
+int launch_classes(const FsWgradPlan& p, WgArgs& a, int ntile, int R, int S, int stride, int pad, hipStream_t stream) {
+  int i = 0;
+  for (int r0 = 0; r0 < stride && r0 < R; ++r0)
+    for (int s0 = 0; s0 < stride && s0 < S; ++s0, ++i) {
+      const int nR = (R - r0 + stride - 1) / stride, nS = (S - s0 + stride - 1) / stride;
+      a.cy = r0 - pad; a.cx = s0 - pad; a.rbase = r0; a.rstep = stride; a.sbase = s0; a.sstep = stride;
+      int e = FS_ERR_ARG;
+      if (nR == 3 && nS == 3) e = launch_class<P, 3, 3>(a, ntile, p.step[i], stream);
+      else if (nR == 2 && nS == 2) e = launch_class<P, 2, 2>(a, ntile, p.step[i], stream);
+      else if (nR == 2 && nS == 1) e = launch_class<P, 2, 1>(a, ntile, p.step[i], stream);
+      else if (nR == 1 && nS == 2) e = launch_class<P, 1, 2>(a, ntile, p.step[i], stream);
+      else if (nR == 1 && nS == 1) e = launch_class<P, 1, 1>(a, ntile, p.step[i], stream);
+      if (e != FS_OK) return e;
+    }
+  return FS_OK;
+}
+
+template <class P>
+int launch_planes(MpArgs a, const FsWgradStep& s, hipStream_t stream) {
+  a.Ph = s.Ph; a.Pw = s.Pw;
+  planes_plan(a);
+  a.tiles_y = cdiv(a.H, a.Ph); a.tiles_x = cdiv(a.W, a.Pw);
+  a.magic_pw = div_magic1(a.Pw);
+  a.npatch = a.B * a.tiles_y * a.tiles_x;
+  a.patches_per_split = s.per_split;
+  hipLaunchKernelGGL((conv_wgrad_planes_kernel<P>), dim3((unsigned)(a.tiles_ci * a.tiles_co * s.nsplit)), dim3(256), 0, stream, a);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+template <int WM, int WN, int MI, int NI>
+int launch_linear(LwArgs a, const FsWgradStep& s, hipStream_t stream) {
+  a.tiles_ci = cdiv(a.Cin, WM * MI * 32); a.tiles_co = cdiv(a.Cout, WN * NI * 32);
+  a.rows_per_split = s.per_split;
+  const int ntap = a.ntap > 0 ? a.ntap : 1;
+  hipLaunchKernelGGL((linear_wgrad_kernel<PrecX3, WM, WN, MI, NI>), dim3((unsigned)(a.tiles_ci * a.tiles_co * s.nsplit * ntap)), dim3(256), 0, stream, a);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+}  // namespace
+
+// Run the launches of a plan of fs_wgrad_plan / fs_linear_wgrad_plan (every route but the fp32 kernels of conv.hip).  part: the slabs of a
+// plan that accumulates in slabs, else {nullptr, 0}; dbias / bpart: fs_linear_bwd_weight_bias only.
+int fs_wgrad_launch(const FsWgradPlan& p, const float* x, const float* dy, float* dw, float* dbias, FsPart part, float* bpart, int B, int H, int W,
+                    int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, hipStream_t stream) {
+  const int tiles_ci = cdiv(Cin, 64), tiles_co = cdiv(Cout, 64), ntile = tiles_ci * tiles_co;
+  const unsigned x_bytes = (unsigned)((size_t)B * H * W * Cin * 4), dy_bytes = (unsigned)((size_t)B * Ho * Wo * Cout * 4);
+  switch (p.route) {
+    case FS_WG_LINEAR:
+    case FS_WG_GATHER: {
+      LwArgs l;
+      l.x = x; l.dy = dy; l.dw = dw; l.dbias = dbias; l.rows = B * Ho * Wo; l.Cin = Cin; l.Cout = Cout;
+      l.x_bytes = x_bytes; l.dy_bytes = dy_bytes;
+      l.part = part; l.bpart = dbias != nullptr && part.base != nullptr ? bpart : nullptr;
+      l.ntap = 0; l.S = 1; l.Ho = l.Wo = l.Hx = l.Wx = 1; l.st = 1; l.pad = 0;
+      if (p.route == FS_WG_GATHER) {
+        // every tap class is a single tap (3x3 stride 4, 1x1 stride 2 ...): R * S linear layers over gathered X rows, one launch
+        l.ntap = R * S; l.S = S; l.Ho = Ho; l.Wo = Wo; l.Hx = H; l.Wx = W; l.st = stride; l.pad = pad;
+      }
+      switch (p.tile) {
+        case 1: return launch_linear<2, 2, 1, 1>(l, p.step[0], stream);      //  64 x  64
+        case 2: return launch_linear<1, 4, 2, 1>(l, p.step[0], stream);      //  64 x 128
+        case 3: return launch_linear<4, 1, 1, 2>(l, p.step[0], stream);      // 128 x  64
+        default: return launch_linear<2, 2, 2, 2>(l, p.step[0], stream);     // 128 x 128
+      }
+    }
+    case FS_WG_WINO: {
+      WwArgs w;
+      w.x = x; w.dy = dy; w.dw = dw; w.B = B; w.H = H; w.W = W; w.Cin = Cin; w.Cout = Cout;
+      w.tiles_ci = tiles_ci; w.tiles_co = tiles_co;
+      w.x_bytes = x_bytes; w.dy_bytes = dy_bytes; w.part = part;
+      const FsWgradStep& s = p.step[0];
+      w.Ph = s.Ph; w.PP = s.Pw;
+      w.tiles_y = cdiv(H, w.Ph); w.tiles_x = cdiv(W / 2, w.PP);
+      w.npatch = B * w.tiles_y * w.tiles_x;
+      w.magic_pp = div_magic1(w.PP);
+      w.patches_per_split = s.per_split;
+      constexpr int lds = PrecX3::NPL * (XT_PLANE + DM_PLANE);
+      {
+        static unsigned long long done = 0ull;
+        int dev = 0;
+        if (hipGetDevice(&dev) != hipSuccess) return FS_ERR_ARG;
+        if (dev < 0 || dev >= 64 || !((done >> dev) & 1ull)) {
+          const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_wino_kernel<PrecX3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+          if (attr != hipSuccess) return (int)attr;
+          if (dev >= 0 && dev < 64) done |= 1ull << dev;
+        }
+      }
+      hipLaunchKernelGGL((conv_wgrad_wino_kernel<PrecX3>), dim3((unsigned)(ntile * s.nsplit)), dim3(512), lds, stream, w);
+      FS_LAUNCH_CHECK();
+      return FS_OK;
+    }
+    case FS_WG_PLANES: {
+      // all nine taps of a strided 3x3 filter in one launch (parity planes of the X halo in LDS)
+      MpArgs m;
+      m.x = x; m.dy = dy; m.dw = dw; m.B = B; m.H = Ho; m.W = Wo; m.Hx = H; m.Wx = W; m.Cin = Cin; m.Cout = Cout;
+      m.st = stride; m.pad = pad; m.tiles_ci = tiles_ci; m.tiles_co = tiles_co;
+      m.x_bytes = x_bytes; m.dy_bytes = dy_bytes; m.part = part;
+      return p.mode == 2 ? launch_planes<PrecF16>(m, p.step[0], stream) : launch_planes<PrecX3>(m, p.step[0], stream);
+    }
+    case FS_WG_CLASS33:
+    case FS_WG_CLASSES: {
+      WgArgs a;
+      a.part = part;
+      a.x = x; a.dy = dy; a.dw = dw;
+      a.B = B; a.H = Ho; a.W = Wo; a.Hx = H; a.Wx = W; a.Cin = Cin; a.Cout = Cout;
+      a.sm = stride; a.S = S;
+      a.tiles_ci = tiles_ci; a.tiles_co = tiles_co;
+      a.x_bytes = x_bytes; a.dy_bytes = dy_bytes;
+      a.prio = p.prio;
+      return p.mode == 2 ? launch_classes<PrecF16>(p, a, ntile, R, S, stride, pad, stream) : launch_classes<PrecX3>(p, a, ntile, R, S, stride, pad, stream);
+    }
+    default: return FS_ERR_ARG;      // the fp32 kernels are launched where they live (conv.hip)
+  }
 }

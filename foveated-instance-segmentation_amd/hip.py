@@ -109,6 +109,7 @@ HOST_ONLY = ("fs_set_conv_precision", "fs_get_conv_precision", "fs_conv2d_worksp
              "fs_bn_bwd_slabs", "fs_dwconv3_wgrad_lanes", "fs_conv2d_bwd_data_bnsum_slabs",
              "fs_conv2d_fwd_affine_act_ok", "fs_conv2d_fwd_residual_ok", "fs_linear_bwd_weight_bias_ok", "fs_attention_split_ws_bytes", "fs_attention_bwd_split_ws_bytes", "fs_attention_mask_words", "fs_attention_bwd_split_parts_offset",
              "fs_stream_wait", "fs_set_deterministic", "fs_get_deterministic", "fs_conv2d_bwd_weight_ws_bytes", "fs_linear_bwd_weight_bias_ws_bytes",
+             "fs_conv2d_bwd_weight_plan",
              "fs_colsum_scratch_floats", "fs_bn_stats_scratch_doubles", "fs_mask_head_bwd_scratch_floats", "fs_layernorm_bwd_scratch_floats",
              "fs_conv2d_pack_persistent", "fs_conv2d_ws_mode",
              "fs_edge_loss_stats_floats", "fs_compress_softmax_bwd_scratch_floats", "fs_gauss_grid_bwd_scratch_floats",
@@ -171,6 +172,8 @@ def load():
     lib.fs_get_deterministic.argtypes = []
     lib.fs_conv2d_bwd_weight_ws_bytes.restype = _L
     lib.fs_conv2d_bwd_weight_ws_bytes.argtypes = [_I] * 7
+    lib.fs_conv2d_bwd_weight_plan.restype = _I
+    lib.fs_conv2d_bwd_weight_plan.argtypes = [_I] * 12 + [_L, ctypes.POINTER(_I)]
     lib.fs_linear_bwd_weight_bias_ws_bytes.restype = _L
     lib.fs_linear_bwd_weight_bias_ws_bytes.argtypes = [_I] * 2
     lib.fs_conv2d_workspace_bytes.restype = _L

@@ -256,6 +256,19 @@ int fs_linear_bwd_weight_bias(const float* x, const float* dy, float* dw, float*
  * fs_conv2d_bwd_weight_ws_bytes (0 outside that mode; ws may then be NULL).  In deterministic mode a missing or short scratch is
  * FS_ERR_ARG: the call never falls back to the atomics silently. */
 long fs_conv2d_bwd_weight_ws_bytes(int Cin, int Cout, int R, int S, int stride, int pad, int dil);
+/* What fs_conv2d_bwd_weight does with this problem under the current precision and deterministic modes and ws_bytes of scratch
+ * (ws_bytes > 0 stands for "scratch given"; accumulate = 0).  Returns 1 when the call would be accepted, else 0.  out[6] receives
+ *   out[0] route: 0 = generic kernel, 1 = generic kernel with float4 loads (channel counts multiples of 4), 2 / 3 = fp32 3x3 kernel with 3 / 9
+ *          taps per workgroup, 4 = split-precision 3x3 stride-1 class kernel, 5 = transform-domain 3x3 kernel, 6 = linear-layer GEMM
+ *          (1x1 / stride 1), 7 = one GEMM per tap over gathered rows in one launch, 8 = strided 3x3 over parity planes in one launch,
+ *          9 = one launch per tap class;
+ *   out[1] accumulation over the pixel splits: 0 = atomics into dw after a memset of it, 1 = atomics into an accumulating dw (reported by
+ *          calls with accumulate != 0 only), 2 = zeroed slabs in ws + ordered sum, 3 = slabs written without a memset + ordered sum;
+ *   out[2] convolution kernel launches (memsets and the sum not counted), out[3] their workgroups together, out[4] threads per workgroup,
+ *   out[5] slab rows of R*S*Cin*Cout floats the launches write in ws (0 with atomics).
+ * All zero for an invalid shape.  Host-side, no launch. */
+int fs_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil, long ws_bytes,
+                              int* out);
 int fs_conv2d_bwd_weight(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Ho, int Wo, int Cout,
                          int R, int S, int stride, int pad, int dil, int accumulate, void* ws, long ws_bytes, fs_stream_t stream);
 

@@ -135,6 +135,10 @@ CONV_CASES = [
     (2, 16, 16, 64, 64, 1, 4, True),        # ... 1x1 stride 4
     (2, 17, 17, 192, 32, 3, 3, False),      # ... stride = filter size, three rounds per tap
     (2, 18, 21, 96, 128, 3, 3, False),      # bwd-data of such layers with 64-aligned OUTPUT channels: one GEMM per tap, rows scattered to dX
+    (1, 10, 10, 192, 192, 3, 1, False),     # nine channel tiles: bwd-weight in f32 with all nine taps per workgroup
+    (2, 12, 12, 16, 16, 5, 1, False),       # 5x5 with aligned channels: bwd-weight on the generic kernel's float4 form in every mode
+    (4, 64, 64, 512, 512, 1, 1, False),     # 1x1, >= 512 rows per split: bwd-weight on the linear GEMM's 128 x 128 tile
+    (1, 10, 10, 512, 512, 1, 1, False),     # ... few rows on a wide layer: its 64 x 64 tile over 1024 workgroups
 ]
 
 
@@ -173,6 +177,9 @@ def test_conv_fwd_bwd(case, prec):
 DET_WGRAD_CASES = [
     (8, 40, 40, 64, 64, 3, 1), (4, 40, 40, 64, 128, 3, 2), (4, 40, 40, 64, 64, 3, 2), (2, 40, 40, 96, 64, 3, 4), (4, 80, 80, 192, 24, 3, 1),
     (4, 40, 40, 64, 256, 1, 1), (4, 20, 20, 256, 64, 1, 1), (2, 16, 16, 64, 64, 1, 2), (3, 1, 1, 512, 51, 1, 1), (2, 23, 17, 3, 64, 7, 2),
+    (2, 16, 16, 128, 128, 4, 2),                                        # four tap classes of 2 x 2 taps, one launch each
+    (4, 64, 64, 512, 512, 3, 1), (3, 64, 64, 512, 512, 3, 1),           # bf16x3: 64 / 48 patches per workgroup = either side of the transform-domain kernel's threshold
+    (1, 256, 256, 1024, 1024, 1, 2),                                    # bf16x3: gathered rows on 128 x 128 tiles want 11 splits, the slab cap is 10: bounded by it
 ]
 
 
@@ -217,6 +224,88 @@ def test_bwd_weight_deterministic_mode(case, prec):
         H_.set_deterministic(False)
     if not (k == 3 and s in (2, 3) and prec != "f32"):          # (strided 3x3 layers take the store + ordered-reduce route in every mode)
         assert int(H_.load().fs_conv2d_bwd_weight_ws_bytes(Ci, Co, k, k, s, pad, 1)) == 0
+
+
+def _wgrad_plan(case, ws_bytes=None):
+    """fs_conv2d_bwd_weight_plan of a (B, H, W, Cin, Cout, k, stride[, bias[, dil]]) case under the current modes, with the scratch
+    ops.conv2d_bwd_weight passes (what fs_conv2d_bwd_weight_ws_bytes asks for): (ok, route, accum, launches, workgroups, threads, slabs)."""
+    import ctypes
+    B, H, W, Ci, Co, k, s = case[:7]
+    dil = case[8] if len(case) > 8 else 1
+    pad = dil * (k // 2)
+    Ho, Wo = (H + 2 * pad - dil * (k - 1) - 1) // s + 1, (W + 2 * pad - dil * (k - 1) - 1) // s + 1
+    lib = fovealseg.hip.load()
+    if ws_bytes is None:
+        ws_bytes = int(lib.fs_conv2d_bwd_weight_ws_bytes(Ci, Co, k, k, s, pad, dil))
+    out = (ctypes.c_int * 6)()
+    ok = lib.fs_conv2d_bwd_weight_plan(B, H, W, Ci, Ho, Wo, Co, k, k, s, pad, dil, ws_bytes, out)
+    return (ok,) + tuple(out)
+
+
+# The store + ordered-reduce route of strided 3x3 layers in the default mode: the one-launch kernel writes every element of every slab
+# it uses, so there is no memset -- and the plan's slab count can be observed: exactly that many rows of a sentinel-filled scratch change.
+STORE_WGRAD_CASES = [((2, 20, 20, 128, 256, 3, 2), "bf16x3"), ((2, 20, 20, 128, 256, 3, 2), "f16x2"), ((3, 21, 19, 48, 64, 3, 2), "f16x2")]
+
+
+@pytest.mark.parametrize("case,mode", STORE_WGRAD_CASES)
+def test_bwd_weight_store_route_writes_the_plans_slab_rows(case, mode):
+    B, H, W, Ci, Co, k, s = case
+    H_ = fovealseg.hip
+    H_.set_conv_precision(mode)
+    try:
+        assert not H_.get_deterministic()
+        g = torch.Generator().manual_seed(Ci + Co + H)
+        x = torch.randn(B, Ci, H, W, generator=g)
+        x64 = x.double()
+        w64 = torch.zeros(Co, Ci, k, k, dtype=torch.float64, requires_grad=True)
+        y64 = F.conv2d(x64, w64, None, s, 1)
+        cot = torch.randn(y64.shape, generator=g)
+        y64.backward(cot.double())
+        xd, dyd = nhwc(x), nhwc(cot)
+        Ho, Wo = y64.shape[2:]
+        n = k * k * Ci * Co
+        nb = int(H_.load().fs_conv2d_bwd_weight_ws_bytes(Ci, Co, k, k, s, 1, 1))
+        ok, route, accum, launches, workgroups, threads, slabs = _wgrad_plan(case)
+        assert ok == 1 and accum == 3 and launches == 1 and 0 < slabs <= nb // (4 * n)
+        sentinel = -0x12345678                                                      # as float bits: a negative number no sum of this test equals
+        ws = torch.full((nb // (4 * n), n), sentinel, dtype=torch.int32, device=DEV)
+        dw = torch.empty(k, k, Ci, Co, device=DEV)
+        H_.call("fs_conv2d_bwd_weight", H_.ptr(xd), H_.ptr(dyd), H_.ptr(dw), B, H, W, Ci, Ho, Wo, Co, k, k, s, 1, 1, 0, H_.ptr(ws), nb)
+        written = int((ws != sentinel).any(dim=1).sum())
+        print(f"{case} {mode}: plan slabs {slabs}, rows written {written}, dW error {relerr(dw.cpu(), w64.grad.permute(2, 3, 1, 0)):.2e}")
+        assert written == slabs
+        assert relerr(dw.cpu(), w64.grad.permute(2, 3, 1, 0)) <= 5e-5
+    finally:
+        H_.set_conv_precision(H_.default_conv_precision())
+
+
+def test_bwd_weight_cases_reach_every_route():
+    """The case lists of test_conv_fwd_bwd, test_bwd_weight_deterministic_mode, test_conv_fwd_bwd_production_sizes and the test above
+    reach, by the library's own account, every bwd-weight route and every accumulation kind the query reports (host-side: no launch).
+    Kind 1, atomics into an accumulating dW, is what the accumulate=True calls of those tests take where the query says 0."""
+    H_ = fovealseg.hip
+    seen = {}
+    try:
+        for mode in ("f32", "bf16x3", "f16x2"):
+            H_.set_conv_precision(mode)
+            for det, cases in ((False, CONV_CASES + DET_WGRAD_CASES + CONV_CASES_FULLRES + [c for c, _ in STORE_WGRAD_CASES]), (True, DET_WGRAD_CASES)):
+                H_.set_deterministic(det)
+                for case in cases:
+                    ok, route, accum = _wgrad_plan(case)[:3]
+                    assert ok == 1, (case, mode, det)
+                    seen.setdefault((route, accum), (case, mode, det))
+    finally:
+        H_.set_deterministic(False)
+        H_.set_conv_precision(H_.default_conv_precision())
+    assert {r for r, _ in seen} == set(range(10)), seen
+    assert {a for _, a in seen} == {0, 2, 3}, seen
+    # the transform-domain kernel's threshold lies between the two 512 -> 512 cases of DET_WGRAD_CASES
+    H_.set_conv_precision("bf16x3")
+    try:
+        assert _wgrad_plan((4, 64, 64, 512, 512, 3, 1))[1] == 5 and _wgrad_plan((3, 64, 64, 512, 512, 3, 1))[1] == 4
+        assert _wgrad_plan((4, 64, 64, 512, 512, 1, 1))[1:5] == (6, 0, 1, 16 * 22) and _wgrad_plan((1, 10, 10, 512, 512, 1, 1))[1:5] == (6, 0, 1, 64 * 2)
+    finally:
+        H_.set_conv_precision(H_.default_conv_precision())
 
 
 # Weight packs that outlive the call (include/fovealseg.h: fs_conv2d_pack / fs_conv2d_ws_mode; ops._pack_for, ops.repack_weights).
