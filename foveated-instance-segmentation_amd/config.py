@@ -70,5 +70,6 @@ def lvis50_cfg() -> CfgNode:
         fov_scale_lr="", fov_scale_pow=1, fov_scale_seg_only=False,
         epoch_iters=744, num_epoch=150, start_epoch=0, max_iters=744 * 150, disp_iter=20, seed=304,
         running_lr_encoder=2e-5, running_lr_decoder=2e-5, running_lr_foveater=2e-5)
-    C.VAL = CfgNode(y_sampled_reverse=False, no_upsample=True, checkpoint="epoch_last.pth")
+    C.VAL = CfgNode(y_sampled_reverse=False, no_upsample=True, checkpoint="epoch_last.pth",
+                    trimap=False, trimap_dia_factor=5, trimap_visual_check=False)
     return C

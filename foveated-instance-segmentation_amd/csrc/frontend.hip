@@ -1066,12 +1066,31 @@ __device__ __forceinline__ void count_pixel(AccCount& n, int a, float yv, long l
 // grid = B * blocks_per_image workgroups; workgroup (b, chunk) counts UACC_CHUNK consecutive pixels of image b into ONE record of
 // rec (plain stores: no zero-initialised scratch, no global atomics).  VEC: Ws % 4 == 0 and 16-byte aligned owner / y / labels, so
 // that four neighbours are one row's and load as one dwordx4 each.  labels (nullable) receives unwarp_label_kernel's class map.
-template <bool VEC>
+// TRIM (fs_unwarp_trimap): the pixel's band byte (fs_trimap_bands) buckets three more predicates -- in a band, class right, foreground /
+// background right -- into trec; without it the body is fs_unwarp_accuracy's count pass as it was.
+constexpr int TRIM_BUCKETS = 8;                        // band indices 0 .. D, D <= 7
+constexpr int TRIM_REC = TRIM_BUCKETS * 3;             // ints per workgroup record: (total, cls_ok, bin_ok) per bucket, six 16-byte rows
+// one LDS add per banded pixel: three 10-bit fields of its wave's bucket word (a wave counts at most 256 pixels)
+__device__ __forceinline__ void trim_pixel(unsigned int* __restrict__ tbw, unsigned int bi, int a, float yv, long long cl, int bg) {
+  if (bi >= (unsigned int)TRIM_BUCKETS) return;        // 255: in no band
+  const long long t = (long long)yv;
+  const long long g = t * cl + (1 - t) * (long long)bg;
+  const unsigned int eq = (long long)a == g, bin = (a == bg) == (g == bg);
+  atomicAdd(tbw + bi, 1u | eq << 10 | bin << 20);
+}
+template <bool VEC, bool TRIM>
 __global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
                                                            const float* __restrict__ yl, const long long* __restrict__ cls_label,
                                                            long long* __restrict__ labels, int* __restrict__ rec, int Hs, int Ws, int hw,
-                                                           int K, int blocks_per_image) {
+                                                           int K, int blocks_per_image, const unsigned char* __restrict__ band,
+                                                           int* __restrict__ trec) {
   __shared__ int part[4][6];
+  __shared__ unsigned int tb[4][TRIM_BUCKETS];         // TRIM: one bucket row per wave
+  if (TRIM) {
+    if (threadIdx.x < 4 * TRIM_BUCKETS) tb[threadIdx.x / TRIM_BUCKETS][threadIdx.x % TRIM_BUCKETS] = 0u;
+    __syncthreads();
+  }
+  unsigned int* tbw = tb[threadIdx.x >> 6];
   const int b = blockIdx.x / blocks_per_image, chunk = blockIdx.x - b * blocks_per_image;
   const int per = Hs * Ws;
   const long base = (long)b * per;
@@ -1103,6 +1122,11 @@ __global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict
       const int a0 = db[q[0]], a1 = db[q[1]], a2 = db[q[2]], a3 = db[q[3]];
       count_pixel(n, a0, y4.x, cl, bg); count_pixel(n, a1, y4.y, cl, bg);
       count_pixel(n, a2, y4.z, cl, bg); count_pixel(n, a3, y4.w, cl, bg);
+      if (TRIM) {
+        const unsigned int b4 = *reinterpret_cast<const unsigned int*>(band + base + p);
+        trim_pixel(tbw, b4 & 255u, a0, y4.x, cl, bg); trim_pixel(tbw, (b4 >> 8) & 255u, a1, y4.y, cl, bg);
+        trim_pixel(tbw, (b4 >> 16) & 255u, a2, y4.z, cl, bg); trim_pixel(tbw, b4 >> 24, a3, y4.w, cl, bg);
+      }
       if (labels != nullptr) {
         longlong2* lp = reinterpret_cast<longlong2*>(labels + base + p);
         lp[0] = make_longlong2(a0, a1); lp[1] = make_longlong2(a2, a3);
@@ -1116,6 +1140,7 @@ __global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict
       const int y = p / Ws, x = p - y * Ws;
       const int a = unwarp_class_at(ob, rx, db, ob[p], y, x, Hs, Ws, hw);
       count_pixel(n, a, yb[p], cl, bg);
+      if (TRIM) trim_pixel(tbw, band[base + p], a, yb[p], cl, bg);
       if (labels != nullptr) labels[base + p] = (long long)a;
     }
   }
@@ -1137,6 +1162,33 @@ __global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict
     int4* r = reinterpret_cast<int4*>(rec + (long)blockIdx.x * UACC_REC);
     r[0] = make_int4(s[0], s[1], s[2], s[3]);
     r[1] = make_int4(s[4], s[5], 0, 0);
+  }
+  if (TRIM && threadIdx.x < TRIM_REC) {
+    const int bi = threadIdx.x / 3, sh = 10 * (threadIdx.x % 3);
+    int t = 0;
+#pragma unroll
+    for (int wv = 0; wv < 4; ++wv) t += (int)((tb[wv][bi] >> sh) & 1023u);
+    trec[(long)blockIdx.x * TRIM_REC + threadIdx.x] = t;
+  }
+}
+// trim[b, i, 0..3) = (total, cls_ok, bin_ok) of band i = the buckets 0 .. i of image b's records summed; one workgroup per image
+__global__ __launch_bounds__(256) void unwarp_trim_finalize_kernel(const int* __restrict__ trec, long long* __restrict__ trim,
+                                                                   int blocks_per_image, int D) {
+  constexpr int G = 256 / TRIM_REC;                    // record rows in flight: thread (g, q) sums field q of rows g, g + G, ...
+  __shared__ long long red[G][TRIM_REC];
+  const int b = blockIdx.x, q = threadIdx.x % TRIM_REC, g = threadIdx.x / TRIM_REC;
+  if (g < G) {
+    long long s = 0;
+    for (int j = g; j < blocks_per_image; j += G) s += trec[((long)b * blocks_per_image + j) * TRIM_REC + q];
+    red[g][q] = s;
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 3 * (D + 1)) {
+    const int i = threadIdx.x / 3, f = threadIdx.x % 3;
+    long long c = 0;
+    for (int k = 0; k <= i; ++k)
+      for (int r = 0; r < G; ++r) c += red[r][k * 3 + f];
+    trim[((long)b * (D + 1) + i) * 3 + f] = c;
   }
 }
 // counts[b, 0..6) = the sum of image b's records; one workgroup per image
@@ -1169,6 +1221,157 @@ __global__ __launch_bounds__(256) void unwarp_accuracy_kernel(const long long* _
   if (threadIdx.x < 4) {
     const int j = threadIdx.x;
     acc[j] = (float)((j == 0 ? a[0] : j == 1 ? a[1] : j == 2 ? a[2] : a[3]) / (double)B);
+  }
+}
+
+// ---- trimap bands: which band of width 1, 2, 4 .. 2^D around the label's boundary a pixel lies in (eval.py:41-67) -------------------
+// The reference dilates PIL's FIND_EDGES of the label 2^i times with scipy's cross element: an L1 distance threshold.  Here: seed =
+// background pixel (t = (long)y == 0) with a foreground 8-neighbour (outside the image counts as background; with `frame` every
+// background pixel of the outer ring is a seed, PIL copying the ring through unfiltered), d = L1 distance to the nearest seed, band =
+// the smallest i with d <= 2^i, 255 if none.  The L1 distance separates: a row pass, then a column pass over its result.  Only
+// d <= 2^D matters, so both passes keep bytes capped at 2^D + 1 and look no further than 2^D: a tile with that halo needs no carry.
+// Inside a tile the 1-D pass is D + 1 doubling steps f[j] = min(f[j], f[j -+ s] + s), s = 1, 2 .. 2^D: a run of steps costs at least the
+// offset it covers and the binary digits of an offset cost exactly it, so after them f[j] = min over |o| < 2^(D+1) of g[j+o] + |o|,
+// exact; what a step reads from beyond the tile is missing, which only ever leaves an upper bound standing beside the exact one.
+constexpr int TRI_MAX_D = 7;
+constexpr int TRI_MAX_HALO = 1 << TRI_MAX_D;
+constexpr int TRI_RG = 8;                              // row pass: rows per workgroup (ten rows of y read for eight written)
+constexpr int TRI_SEG = 1024;                          // row pass: columns per workgroup
+constexpr int TRI_MAX_HW = TRI_MAX_HALO / 64 + 1;      // row pass: 64-column words of halo on either side (64 * words > 2^D)
+constexpr int TRI_NWORDS = TRI_SEG / 64 + 2 * TRI_MAX_HW;
+constexpr int TRI_CW = 64;                             // column pass: columns per workgroup (sixteen 4-byte words a row)
+constexpr int TRI_CH = 128;                            // column pass: rows per workgroup
+constexpr int TRI_FAR = 1 << 20;
+// row pass: inter[b, v, u] (row pitch P, a multiple of 4) = min(2^D + 1, distance along row v to the nearest seed).  A row is a string
+// of bits, 64 columns a word: a wave's ballot makes a word of foreground bits from one coalesced read of y, the seed rule is shifts
+// and ORs of three rows' words, and a pixel's distance is a count of leading / trailing zeros from its bit.
+__global__ __launch_bounds__(256) void trimap_row_kernel(const float* __restrict__ y, unsigned char* __restrict__ inter, int Hs, int Ws, int P,
+                                                         int D, int frame, int rgs, int segs) {
+  __shared__ unsigned long long fgw[TRI_RG + 2][TRI_NWORDS];
+  __shared__ unsigned long long sdw[TRI_RG][TRI_NWORDS];
+  const int seg = blockIdx.x % segs, rg = (blockIdx.x / segs) % rgs, b = blockIdx.x / (segs * rgs);
+  const int halo = 1 << D, cap = halo + 1, hw = halo / 64 + 1;
+  const int segw = min(TRI_SEG, Ws - seg * TRI_SEG), nwords = (segw + 63) / 64 + 2 * hw;
+  const int x0 = seg * TRI_SEG - 64 * hw, v0 = rg * TRI_RG;     // bit j of word k of a row is image column x0 + 64 k + j
+  const int rows = min(TRI_RG, Hs - v0);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* yb = y + (long)b * Hs * Ws;
+  for (int it = wave; it < (rows + 2) * nwords; it += 4) {
+    const int r = it / nwords, k = it - r * nwords;
+    const int v = v0 - 1 + r, u = x0 + 64 * k + lane;
+    bool f = false;
+    if (v >= 0 && v < Hs && u >= 0 && u < Ws) f = (long long)yb[(long)v * Ws + u] != 0;
+    const unsigned long long bits = __ballot(f);
+    if (lane == 0) fgw[r][k] = bits;
+  }
+  __syncthreads();
+  for (int it = threadIdx.x; it < rows * nwords; it += 256) {
+    const int r = it / nwords, k = it - r * nwords;
+    const int v = v0 + r, ulo = x0 + 64 * k;
+    const unsigned long long a = fgw[r][k] | fgw[r + 1][k] | fgw[r + 2][k];
+    const unsigned long long al = k > 0 ? fgw[r][k - 1] | fgw[r + 1][k - 1] | fgw[r + 2][k - 1] : 0ull;
+    const unsigned long long ar = k + 1 < nwords ? fgw[r][k + 1] | fgw[r + 1][k + 1] | fgw[r + 2][k + 1] : 0ull;
+    // the region's two outermost columns miss a neighbour; they lie 64 * hw > 2^D columns from the segment and cannot matter
+    unsigned long long take = a | a << 1 | al >> 63 | a >> 1 | ar << 63;
+    if (frame) {
+      if (v == 0 || v == Hs - 1) take = ~0ull;
+      if (ulo <= 0 && 0 < ulo + 64) take |= 1ull << (0 - ulo);
+      if (ulo <= Ws - 1 && Ws - 1 < ulo + 64) take |= 1ull << (Ws - 1 - ulo);
+    }
+    const int lo = max(0, -ulo), hi = min(64, Ws - ulo);          // the word's columns inside the image: bits lo .. hi - 1
+    unsigned long long in = 0ull;
+    if (hi > lo) in = (hi - lo == 64 ? ~0ull : (1ull << (hi - lo)) - 1ull) << lo;
+    sdw[r][k] = ~fgw[r + 1][k] & take & in;
+  }
+  __syncthreads();
+  // four columns a thread and a store; the pitch's padding takes whatever lies beside the row, and the column pass never shows it
+  const int words = (segw + 3) >> 2;
+  if ((int)threadIdx.x >= words) return;
+  const int c0 = 64 * hw + 4 * (int)threadIdx.x, w = c0 >> 6;
+  for (int r = 0; r < rows; ++r) {
+    const unsigned long long* s = sdw[r];
+    const unsigned long long cw = w < nwords ? s[w] : 0ull;
+    int before = TRI_FAR, after = TRI_FAR;                       // from bit 0 / bit 63 of word w to the nearest seed in the words beside it
+    for (int k = 1; k <= hw; ++k)
+      if (w - k >= 0 && s[w - k] != 0ull) { before = 64 * (k - 1) + 1 + __builtin_clzll(s[w - k]); break; }
+    for (int k = 1; k <= hw; ++k)
+      if (w + k < nwords && s[w + k] != 0ull) { after = 64 * (k - 1) + 1 + __builtin_ctzll(s[w + k]); break; }
+    unsigned int wd = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int bb = (c0 & 63) + q;
+      const unsigned long long ml = cw & (~0ull >> (63 - bb)), mr = cw & (~0ull << bb);
+      const int dl = ml != 0ull ? bb - (63 - __builtin_clzll(ml)) : bb + before;
+      const int dr = mr != 0ull ? __builtin_ctzll(mr) - bb : 63 - bb + after;
+      wd |= (unsigned int)min(min(dl, dr), cap) << (8 * q);
+    }
+    reinterpret_cast<unsigned int*>(inter + ((long)b * Hs + v0 + r) * P + seg * TRI_SEG)[threadIdx.x] = wd;
+  }
+}
+// column pass: band[b, v, u] from min(2^D + 1, min over dv of inter[b, v + dv, u] + |dv|); a thread holds four neighbouring columns
+__global__ __launch_bounds__(256) void trimap_col_kernel(const unsigned char* __restrict__ inter, unsigned char* __restrict__ band, int Hs, int Ws,
+                                                         int P, int D, int vec, int rts, int cts) {
+  extern __shared__ unsigned int tri_dist[];                   // [2][TRI_CH + 2 * 2^D][TRI_CW / 4]: sized by the launch, for occupancy at small D
+  constexpr int WPR = TRI_CW / 4;
+  const int ct = blockIdx.x % cts, rt = (blockIdx.x / cts) % rts, b = blockIdx.x / (cts * rts);
+  const int halo = 1 << D, cap = halo + 1, nrmax = TRI_CH + 2 * halo;
+  const int v0 = rt * TRI_CH, th = min(TRI_CH, Hs - v0), nr = th + 2 * halo;
+  const int wl = threadIdx.x % WPR, rl = threadIdx.x / WPR;      // this thread's word of a row, and its first row
+  const int u0 = ct * TRI_CW + 4 * wl;
+  auto dist = [&](int buf, int r) -> unsigned int& { return tri_dist[(buf * nrmax + r) * WPR + wl]; };
+  const bool live = u0 < P;
+  const unsigned char* ib = inter + (long)b * Hs * P;
+  bool seen = false;
+#pragma unroll 4
+  for (int r = rl; r < nr; r += 256 / WPR) {
+    const int v = v0 - halo + r;
+    unsigned int wd = (unsigned int)cap * 0x01010101u;           // outside the image: no seed
+    if (live && v >= 0 && v < Hs) wd = *reinterpret_cast<const unsigned int*>(ib + (long)v * P + u0);
+    dist(0, r) = wd;
+    seen |= live && wd != (unsigned int)cap * 0x01010101u;
+  }
+  unsigned char* bb = band + (long)b * Hs * Ws;
+  auto store = [&](int v, unsigned int o) {
+    if (vec) {
+      *reinterpret_cast<unsigned int*>(bb + (long)v * Ws + u0) = o;
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (u0 + q < Ws) bb[(long)v * Ws + u0 + q] = (unsigned char)(o >> (8 * q));
+    }
+  };
+  if (!__syncthreads_or(seen)) {                                 // no seed within 2^D of any row this tile read: in no band
+    if (live)
+      for (int r = halo + rl; r < halo + th; r += 256 / WPR) store(v0 - halo + r, 0xFFFFFFFFu);
+    return;
+  }
+  int cur = 0;
+  for (int s = 1; s <= halo; s <<= 1) {
+    for (int r = rl; r < nr; r += 256 / WPR) {
+      const unsigned int a = dist(cur, r);
+      const unsigned int up = r >= s ? dist(cur, r - s) : 0xFFFFFFFFu, dn = r + s < nr ? dist(cur, r + s) : 0xFFFFFFFFu;
+      unsigned int wd = 0;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int m = min(min((int)((a >> (8 * q)) & 255u), cap), min((int)((up >> (8 * q)) & 255u), (int)((dn >> (8 * q)) & 255u)) + s);
+        wd |= (unsigned int)m << (8 * q);
+      }
+      dist(cur ^ 1, r) = wd;
+    }
+    __syncthreads();
+    cur ^= 1;
+  }
+  if (!live) return;
+  for (int r = halo + rl; r < halo + th; r += 256 / WPR) {
+    const unsigned int wd = dist(cur, r);
+    unsigned int o = 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int d = (int)((wd >> (8 * q)) & 255u);
+      const unsigned int i = d > halo ? 255u : d <= 1 ? 0u : (unsigned int)(32 - __clz(d - 1));
+      o |= i << (8 * q);
+    }
+    store(v0 - halo + r, o);
   }
 }
 
@@ -1540,8 +1743,10 @@ long fs_unwarp_accuracy_scratch_ints(int B, int h, int w, int Hs, int Ws) {
   return unwarp_accuracy_rec_offset(B, h, w, Hs, Ws) + (long)B * bpi * UACC_REC;
 }
 
-int fs_unwarp_accuracy(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
-                       float* acc, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws, hipStream_t stream) {
+// fs_unwarp_accuracy's launches; with band / trec / trim (all or none) the count pass is the bucketing one and trim is summed after it
+static int unwarp_accuracy_launch(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label,
+                                  long long* counts, float* acc, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws,
+                                  const unsigned char* band, int* trec, long long* trim, int D, hipStream_t stream) {
   FS_REQUIRE(cls && m && grid && y && cls_label && counts && acc && scratch && B > 0 && K >= 2 && K <= UNWARP_MAX_K && h > 0 && w > 0 &&
              Hs > 0 && Ws > 0);
   // one row in LDS; int pixel / point indices, the count pass's included (a workgroup's last trip may start up to a chunk past the end)
@@ -1565,18 +1770,82 @@ int fs_unwarp_accuracy(const float* cls, const float* m, const float* grid, cons
   hipLaunchKernelGGL(fill_row_nearest_kernel, dim3((unsigned)((long)B * Hs)), dim3(256), (size_t)Ws * sizeof(int), stream, owner, rowx, Ws);
   FS_LAUNCH_CHECK();
   const bool vec = Ws % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)labels & 15) == 0;
-  if (vec)
-    hipLaunchKernelGGL(unwarp_count_kernel<true>, dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels, rec,
-                       Hs, Ws, h * w, K, (int)cpi);
-  else
-    hipLaunchKernelGGL(unwarp_count_kernel<false>, dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels, rec,
-                       Hs, Ws, h * w, K, (int)cpi);
+  if (band == nullptr) {
+    if (vec)
+      hipLaunchKernelGGL((unwarp_count_kernel<true, false>), dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
+                         rec, Hs, Ws, h * w, K, (int)cpi, nullptr, nullptr);
+    else
+      hipLaunchKernelGGL((unwarp_count_kernel<false, false>), dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
+                         rec, Hs, Ws, h * w, K, (int)cpi, nullptr, nullptr);
+  } else if (vec && ((uintptr_t)band & 3) == 0) {
+    hipLaunchKernelGGL((unwarp_count_kernel<true, true>), dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
+                       rec, Hs, Ws, h * w, K, (int)cpi, band, trec);
+  } else {
+    hipLaunchKernelGGL((unwarp_count_kernel<false, true>), dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
+                       rec, Hs, Ws, h * w, K, (int)cpi, band, trec);
+  }
   FS_LAUNCH_CHECK();
   hipLaunchKernelGGL(unwarp_count_finalize_kernel, dim3((unsigned)B), dim3(256), 0, stream, rec, counts, (int)cpi);
   FS_LAUNCH_CHECK();
   hipLaunchKernelGGL(unwarp_accuracy_kernel, dim3(1), dim3(256), 0, stream, counts, acc, B);
   FS_LAUNCH_CHECK();
+  if (band != nullptr) {
+    hipLaunchKernelGGL(unwarp_trim_finalize_kernel, dim3((unsigned)B), dim3(256), 0, stream, trec, trim, (int)cpi, D);
+    FS_LAUNCH_CHECK();
+  }
   return FS_OK;
+}
+
+int fs_unwarp_accuracy(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
+                       float* acc, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws, hipStream_t stream) {
+  return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, nullptr, nullptr, nullptr, 0, stream);
+}
+
+// include/fovealseg.h: ints of scratch fs_trimap_bands needs (the row pass's byte map, its rows pitched to four bytes)
+static long trimap_pitch(int Ws) { return ((long)Ws + 3) & ~3L; }
+long fs_trimap_bands_scratch_ints(int B, int Hs, int Ws) { return (B > 0 && Hs > 0 && Ws > 0) ? (long)B * Hs * trimap_pitch(Ws) / 4 : 0; }
+
+int fs_trimap_bands(const float* y, unsigned char* band, int* scratch, int B, int Hs, int Ws, int D, int frame, hipStream_t stream) {
+  FS_REQUIRE(y && band && scratch && B > 0 && Hs > 0 && Ws > 0 && D >= 0 && D <= TRI_MAX_D && (frame == 0 || frame == 1));
+  const long P = trimap_pitch(Ws);
+  const long rgs = cdiv(Hs, TRI_RG), segs = cdiv(Ws, TRI_SEG), rts = cdiv(Hs, TRI_CH), cts = cdiv(P, TRI_CW);
+  FS_REQUIRE(P < 2147483647L && (long)B * rgs * segs <= 16777215L && (long)B * rts * cts <= 16777215L);      // fewer than 2^32 work-items
+  unsigned char* inter = reinterpret_cast<unsigned char*>(scratch);
+  hipLaunchKernelGGL(trimap_row_kernel, dim3((unsigned)(B * rgs * segs)), dim3(256), 0, stream, y, inter, Hs, Ws, (int)P, D, frame, (int)rgs,
+                     (int)segs);
+  FS_LAUNCH_CHECK();
+  const int vec = Ws % 4 == 0 && ((uintptr_t)band & 3) == 0;
+  hipLaunchKernelGGL(trimap_col_kernel, dim3((unsigned)(B * rts * cts)), dim3(256), 2 * (TRI_CH + (2 << D)) * TRI_CW, stream, inter, band, Hs, Ws, (int)P, D, vec, (int)rts,
+                     (int)cts);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+// scratch of fs_unwarp_trimap (ints): fs_unwarp_accuracy's, then the bucket records of the count pass, the band bytes, fs_trimap_bands' own
+static long unwarp_trimap_trec_offset(int B, int h, int w, int Hs, int Ws) { return (fs_unwarp_accuracy_scratch_ints(B, h, w, Hs, Ws) + 3) & ~3L; }
+static long unwarp_trimap_band_offset(int B, int h, int w, int Hs, int Ws) {
+  const long cpi = ((long)Hs * Ws + UACC_CHUNK - 1) / UACC_CHUNK;
+  return unwarp_trimap_trec_offset(B, h, w, Hs, Ws) + (long)B * cpi * TRIM_REC;
+}
+static long unwarp_trimap_inter_offset(int B, int h, int w, int Hs, int Ws) {
+  return unwarp_trimap_band_offset(B, h, w, Hs, Ws) + ((((long)B * Hs * Ws + 3) / 4 + 3) & ~3L);
+}
+long fs_unwarp_trimap_scratch_ints(int B, int h, int w, int Hs, int Ws) {
+  if (!(B > 0 && h > 0 && w > 0 && Hs > 0 && Ws > 0)) return 0;
+  return unwarp_trimap_inter_offset(B, h, w, Hs, Ws) + fs_trimap_bands_scratch_ints(B, Hs, Ws);
+}
+
+int fs_unwarp_trimap(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
+                     float* acc, long long* trim, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws, int D, int frame,
+                     hipStream_t stream) {
+  FS_REQUIRE(cls && m && grid && y && cls_label && counts && acc && trim && scratch && B > 0 && K >= 2 && K <= UNWARP_MAX_K && h > 0 && w > 0 &&
+             Hs > 0 && Ws > 0 && D >= 0 && D <= TRI_MAX_D && (frame == 0 || frame == 1));
+  FS_REQUIRE(Ws <= 16384 && (long)h * w < 2147483647L && (long)Hs * Ws < 2147483647L - UACC_CHUNK && ((uintptr_t)scratch & 15) == 0);
+  unsigned char* band = reinterpret_cast<unsigned char*>(scratch + unwarp_trimap_band_offset(B, h, w, Hs, Ws));
+  const int r = fs_trimap_bands(y, band, scratch + unwarp_trimap_inter_offset(B, h, w, Hs, Ws), B, Hs, Ws, D, frame, stream);
+  if (r != FS_OK) return r;
+  return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, band,
+                                scratch + unwarp_trimap_trec_offset(B, h, w, Hs, Ws), trim, D, stream);
 }
 
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, hipStream_t stream) {

@@ -240,7 +240,7 @@ class DeformSegmentationModule(nn.Module):
         return labels
 
     @torch.no_grad()
-    def evaluate(self, img, focus, seg_label, cls_label, seg_size=None, return_labels=False):
+    def evaluate(self, img, focus, seg_label, cls_label, seg_size=None, return_labels=False, trimap=None, trimap_frame=True):
         """Full-resolution scoring without the loss: predict's stages, then the four accuracies of forward's MODEL.upsample branch
         (models/models.py:378-474,869-873,1074-1083) taken against the label in the pass that would have written the class map
         (ops.unwarp_accuracy / fs_unwarp_accuracy): no (B,K,H,W) prediction, no class map and no ground-truth tensor exist.
@@ -250,7 +250,16 @@ class DeformSegmentationModule(nn.Module):
         batch means forward(is_inference=True) reports, and counts (B,6) int64 = cls_fg, bin_fg, union_fg, cls_bg, bin_bg, union_bg per
         image (train.FullResMeter accumulates them into dataset-level scores); with return_labels, predict's class map as a sixth
         element.  seg_size defaults to the label's size and may not differ from it.  Eval mode only; no argument is written to,
-        nothing in the module changes, and a NaN saliency map is reported as in predict."""
+        nothing in the module changes, and a NaN saliency map is reported as in predict.
+
+        trimap (None, or VAL.trimap_dia_factor: an int 0 .. 7) adds the reference's trimap boundary accuracy (eval.py:41-67), counted
+        in the same pass (ops.unwarp_trimap): the last element of the result is then trim (B, trimap + 1, 3) int64 = per image and band
+        the pixels in the band, those with the right class, those right on foreground versus background.  Band i is every pixel within
+        2**i city-block steps of the label's boundary -- the background pixels that touch the foreground and, with trimap_frame (the
+        reference's PIL filter, bit for bit), the background pixels of the image's outer ring; trimap_frame=False reads the boundary
+        alone.  Constant-label rule: an image without any boundary pixel (a constant label with trimap_frame=False, an all-foreground
+        one with it) has empty bands and all-zero counters -- the reference divides 0 by 0 there -- and ops.trimap_from_counts /
+        train.TrimapMeter leave it out of the mean.  With trimap=None the call is unchanged."""
         if seg_label.dim() not in (3, 4) or (seg_label.dim() == 4 and seg_label.shape[1] != 1):
             raise ValueError(f"seg_label must be (B,H,W) or (B,1,H,W), got {tuple(seg_label.shape)}")
         label_size = (int(seg_label.shape[-2]), int(seg_label.shape[-1]))
@@ -259,10 +268,15 @@ class DeformSegmentationModule(nn.Module):
         if seg_label.shape[0] != img.shape[0] or cls_label.shape[0] != img.shape[0]:
             raise ValueError(f"seg_label {tuple(seg_label.shape)} and cls_label {tuple(cls_label.shape)} must have img's batch size {img.shape[0]}")
         cls, m, grid, _ = self._head_parts(img, focus, label_size, "evaluate")
-        out = ops.unwarp_accuracy(cls, m, grid, seg_label, cls_label, return_labels=return_labels)
+        if trimap is None:
+            out = ops.unwarp_accuracy(cls, m, grid, seg_label, cls_label, return_labels=return_labels)
+            counts, acc = out[0], out[1]
+            res = (acc[0], acc[1], acc[2], acc[3], counts)
+            return res + (out[2],) if return_labels else res
+        out = ops.unwarp_trimap(cls, m, grid, seg_label, cls_label, dia_factor=trimap, frame=trimap_frame, return_labels=return_labels)
         counts, acc = out[0], out[1]
         res = (acc[0], acc[1], acc[2], acc[3], counts)
-        return res + (out[2],) if return_labels else res
+        return res + (out[3], out[2]) if return_labels else res + (out[2],)
 
     def forward(self, feed_dict, *, writer=None, segSize=None, F_Xlr_acc_map=False, count=None, epoch=None,
                 feed_dict_info=None, feed_batch_count=None, cur_iter=None, is_inference=False, rank=None):

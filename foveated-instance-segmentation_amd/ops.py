@@ -1514,6 +1514,74 @@ def unwarp_accuracy(cls, m, grid, y, cls_label, return_labels=False):
     return (counts, acc, labels) if return_labels else (counts, acc)
 
 
+def _trimap_args(dia_factor, frame):
+    D = int(dia_factor)
+    if not 0 <= D <= 7:
+        raise ValueError(f"dia_factor must be 0 .. 7 (band widths 1 .. 2**dia_factor), got {dia_factor}")
+    return D, 1 if frame else 0
+
+
+def trimap_bands(y, dia_factor=5, frame=True):
+    """Which trimap band every pixel of the label mask lies in (eval.py:41-67; VAL.trimap_dia_factor): uint8 (B,Hs,Ws), the smallest
+    i <= dia_factor such that the pixel is within 2**i city-block steps of the label's boundary, 255 if none, so that band i of the
+    reference (FIND_EDGES, then binary_dilation(iterations=2**i)) is `bands <= i` (fs_trimap_bands).  y (B,Hs,Ws) or (B,1,Hs,Ws), read
+    as t = y.long().  A boundary seed is a background pixel (t == 0) with a foreground 8-neighbour; frame=True also seeds every
+    background pixel of the outer one-pixel ring, as PIL's filter does -- the reference bit for bit -- and frame=False is the
+    neighbour rule alone, pixels outside the image being background.  No autograd."""
+    D, fr = _trimap_args(dia_factor, frame)
+    if y.dim() == 4 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.dim() != 3 or y.numel() == 0:
+        raise ValueError(f"y {tuple(y.shape)} must be a non-empty (B, Hs, Ws) or (B, 1, Hs, Ws)")
+    B, Hs, Ws = (int(v) for v in y.shape)
+    band = torch.empty(B, Hs, Ws, device=y.device, dtype=torch.uint8)
+    scratch = torch.empty(hip.query("fs_trimap_bands_scratch_ints", B, Hs, Ws), device=y.device, dtype=torch.int32)
+    hip.call("fs_trimap_bands", hip.ptr(y.float().contiguous()), hip.ptr(band), hip.ptr(scratch), B, Hs, Ws, D, fr)
+    return band
+
+
+def unwarp_trimap(cls, m, grid, y, cls_label, dia_factor=5, frame=True, return_labels=False):
+    """unwarp_accuracy with the trimap boundary accuracies of eval.py:41-67 counted in the same gather pass (fs_unwarp_trimap).
+    Arguments and checks are unwarp_accuracy's; dia_factor / frame are trimap_bands'.  Returns (counts, acc, trim[, labels]): counts,
+    acc and labels are unwarp_accuracy's bit for bit, trim (B, dia_factor + 1, 3) int64 holds per image and band width 2**i the number of
+    pixels in the band, of those whose predicted class equals the ground truth (the reference's acc_sum) and of those that agree with
+    it on foreground versus background.  An image without a boundary seed (a constant label with frame=False, an all-foreground one
+    with frame=True) has all-zero rows: the reference divides 0 by 0 there, trimap_from_counts and train.TrimapMeter leave it out."""
+    D, fr = _trimap_args(dia_factor, frame)
+    B, K = cls.shape
+    _, h, w, _ = grid.shape
+    if tuple(m.shape) != (B, h, w):
+        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
+    if y.dim() == 4 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.dim() != 3 or y.shape[0] != B:
+        raise ValueError(f"y {tuple(y.shape)} must be (B, Hs, Ws) or (B, 1, Hs, Ws) with B = {B}")
+    Hs, Ws = int(y.shape[1]), int(y.shape[2])
+    if cls_label.dim() == 2 and cls_label.shape[1] == 1:
+        cls_label = cls_label[:, 0]
+    if tuple(cls_label.shape) != (B,):
+        raise ValueError(f"cls_label {tuple(cls_label.shape)} must be (B,) or (B, 1) with B = {B}")
+    counts = torch.empty(B, 6, device=cls.device, dtype=torch.int64)
+    acc = torch.empty(4, device=cls.device, dtype=torch.float32)
+    trim = torch.empty(B, D + 1, 3, device=cls.device, dtype=torch.int64)
+    labels = torch.empty(B, Hs, Ws, device=cls.device, dtype=torch.int64) if return_labels else None
+    scratch = torch.empty(hip.query("fs_unwarp_trimap_scratch_ints", B, h, w, Hs, Ws), device=cls.device, dtype=torch.int32)
+    hip.call("fs_unwarp_trimap", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()),
+             hip.ptr(y.float().contiguous()), hip.ptr(cls_label.long().contiguous()), hip.ptr(counts), hip.ptr(acc), hip.ptr(trim),
+             hip.ptr(labels), hip.ptr(scratch), B, K, h, w, Hs, Ws, D, fr)
+    return (counts, acc, trim, labels) if return_labels else (counts, acc, trim)
+
+
+def trimap_from_counts(trim):
+    """(B, D+1, 3) trim counters (unwarp_trimap's, on any device) -> (B, D+1, 2) fp64: per image and band width the class accuracy
+    cls_ok / (total + 1e-10) -- the reference's Python-float quotient, eval.py:64 -- and the foreground / background accuracy
+    bin_ok / (total + 1e-10).  An empty band gives 0; `trim[..., 0] > 0` tells which images count (see unwarp_trimap)."""
+    if trim.dim() != 3 or trim.shape[2] != 3:
+        raise ValueError(f"trim must be (B, D+1, 3), got {tuple(trim.shape)}")
+    t = trim.to(torch.float64)
+    return t[..., 1:] / (t[..., :1] + 1e-10)
+
+
 def image_accuracies_from_counts(counts):
     """(B,6) counts -> (B,4) fp32 per-image acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg (models/models.py:378-474): plain torch, any device."""
     c = counts.to(torch.float32)

@@ -356,15 +356,21 @@ def eval_step(module, batch):
 
 
 @torch.no_grad()
-def evaluate_step(module, batch, meter=None):
+def evaluate_step(module, batch, meter=None, trimap_meter=None):
     """Full-resolution scoring of one batch without the loss: module.evaluate on (X, Fp, Y, cls) (module.eval() by caller), the way
     eval_step wraps forward.  Returns evaluate's (acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg, counts); a FullResMeter given as `meter`
-    takes the counts (no host read)."""
+    takes the counts (no host read).  With a TrimapMeter as `trimap_meter` the call is evaluate(trimap=trimap_meter.dia_factor,
+    trimap_frame=trimap_meter.frame): the result ends with the trim counters, which that meter takes."""
     X, Fp, Y, cls = batch
-    out = module.evaluate(X[:, :3], Fp, Y, cls)
+    if trimap_meter is None:
+        out = module.evaluate(X[:, :3], Fp, Y, cls)
+    else:
+        out = module.evaluate(X[:, :3], Fp, Y, cls, trimap=trimap_meter.dia_factor, trimap_frame=trimap_meter.frame)
     module.check_nan()
     if meter is not None:
         meter.update(out[4])
+    if trimap_meter is not None:
+        trimap_meter.update(out[5])
     return out
 
 
@@ -467,6 +473,53 @@ class FullResMeter:
         res["iou_bin_fg"] = c[1] / c[2] if c[2] > 0 else 0.0
         res["counts"], res["images"] = c, int(n)
         return res
+
+
+class TrimapMeter:
+    """Dataset-level trimap boundary accuracy (eval.py:41-67,258-262,295-310) from the trim counters of module.evaluate(trimap=...) /
+    ops.unwarp_trimap.  `update(trim)` adds a batch's (B, dia_factor + 1, 3) int64 counters into device-resident sums -- the counters, the
+    per-image accuracies (fp64) and, per band width, the number of images with a non-empty band -- without a host read;
+    `result(reduce=True)` makes ONE all-reduce over the ranks and ONE host read.  Per width 2**i it returns `acc` / `acc_bin`, the
+    reference's mean over images of cls_ok / (total + 1e-10) and its foreground / background counterpart, over the images whose band is
+    not empty (an image without a boundary pixel has none: the reference divides 0 by 0 there); `pooled` / `pooled_bin`, sum cls_ok /
+    sum total and sum bin_ok / sum total, in which an image weighs by its band's pixels; the raw `counts` (D+1 rows of total, cls_ok,
+    bin_ok); `images` per width and `widths`.  `frame` is evaluate's trimap_frame."""
+
+    def __init__(self, device, dia_factor=5, frame=True):
+        self.dia_factor, self.frame = int(dia_factor), bool(frame)
+        if not 0 <= self.dia_factor <= 7:
+            raise ValueError(f"dia_factor must be 0 .. 7, got {dia_factor}")
+        n = self.dia_factor + 1
+        self.counts = torch.zeros(n, 3, device=device, dtype=torch.int64)
+        self.sums = torch.zeros(n, 3, device=device, dtype=torch.float64)        # per width: sum of cls acc, of bin acc, image count
+
+    def update(self, trim):
+        from . import ops
+        if trim.dim() != 3 or tuple(trim.shape[1:]) != (self.dia_factor + 1, 3):
+            raise ValueError(f"trim must be (B, {self.dia_factor + 1}, 3), got {tuple(trim.shape)}")
+        trim = trim.to(device=self.counts.device, dtype=torch.int64)
+        self.counts.add_(trim.sum(0))
+        seen = (trim[..., 0] > 0).double()
+        self.sums[:, :2].add_((ops.trimap_from_counts(trim) * seen[..., None]).sum(0))
+        self.sums[:, 2].add_(seen.sum(0))
+
+    def result(self, reduce=True):
+        # one fp64 vector, as FullResMeter.result: each int64 sum as two 32-bit halves, whose sums over the ranks stay exact in fp64
+        c = self.counts.reshape(-1)
+        tot = torch.cat([(c >> 32).double(), (c & 0xFFFFFFFF).double(), self.sums.reshape(-1)])
+        if reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(tot, op=dist.ReduceOp.SUM)
+        tot = tot.cpu().tolist()
+        n = self.dia_factor + 1
+        cnt = [[(int(tot[i * 3 + f]) << 32) + int(tot[3 * n + i * 3 + f]) for f in range(3)] for i in range(n)]
+        sums = [tot[6 * n + 3 * i: 6 * n + 3 * i + 3] for i in range(n)]
+        nan = float("nan")
+        return {"widths": [2 ** i for i in range(n)],
+                "acc": [s[0] / s[2] if s[2] > 0 else nan for s in sums],
+                "acc_bin": [s[1] / s[2] if s[2] > 0 else nan for s in sums],
+                "pooled": [c[1] / c[0] if c[0] > 0 else nan for c in cnt],
+                "pooled_bin": [c[2] / c[0] if c[0] > 0 else nan for c in cnt],
+                "counts": cnt, "images": [int(s[2]) for s in sums]}
 
 
 # ----------------------------------------------------------------------------------------------

@@ -121,6 +121,25 @@ long fs_unwarp_accuracy_scratch_ints(int B, int h, int w, int Hs, int Ws);
 int fs_unwarp_accuracy(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label,
                        long long* counts, float* acc, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws,
                        fs_stream_t stream);
+/* Trimap bands (eval.py:41-67, trim_accuracy): band (B,Hs,Ws) bytes = for every pixel the smallest i <= D such that the pixel lies
+ * within 2^i city-block steps of the label's boundary, 255 if none -- the reference's FIND_EDGES + binary_dilation(iterations=2**i)
+ * masks, i = 0 .. D, as one map.  y (B,Hs,Ws) fp32 label mask, t = (long)y.  A seed is a background pixel (t == 0) with a foreground
+ * (t != 0) 8-neighbour, pixels outside the image being background; frame = 1 also makes every background pixel of the outer one-pixel
+ * ring a seed, as PIL's filter does (the reference bit for bit), frame = 0 is the neighbour rule alone.  Exact: two separable passes
+ * of capped L1 distances.  scratch = fs_trimap_bands_scratch_ints(B, Hs, Ws) ints.  FS_ERR_ARG for a null pointer, D outside 0..7,
+ * frame outside {0, 1}, non-positive sizes. */
+long fs_trimap_bands_scratch_ints(int B, int Hs, int Ws);
+int fs_trimap_bands(const float* y, unsigned char* band, int* scratch, int B, int Hs, int Ws, int D, int frame, fs_stream_t stream);
+/* fs_unwarp_accuracy with the trimap boundary accuracies of eval.py:41-67 counted in the same gather pass: counts, acc and labels
+ * are fs_unwarp_accuracy's bit for bit; trim (B,D+1,3) int64 = per image and band i (fs_trimap_bands of y, made here): the pixels in
+ * the band, those whose predicted class equals gt (the reference's acc_sum), those that agree with gt on foreground versus
+ * background.  An image without a seed (constant label with frame = 0, all foreground with frame = 1) has all-zero rows, where the
+ * reference divides 0 by 0.  Integer sums of per-workgroup records, as counts.  scratch = fs_unwarp_trimap_scratch_ints(B, h, w,
+ * Hs, Ws) ints, 16-byte aligned.  FS_ERR_ARG as fs_unwarp_accuracy and fs_trimap_bands, and for a null trim. */
+long fs_unwarp_trimap_scratch_ints(int B, int h, int w, int Hs, int Ws);
+int fs_unwarp_trimap(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
+                     float* acc, long long* trim, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws, int D,
+                     int frame, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
