@@ -109,6 +109,19 @@ __device__ __forceinline__ T block_sum(T v, T* red) {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Dynamic LDS above the 64 KB default is a per-device function attribute: set it for kernel `fn` on the current device unless `done`
+// (the call site's mask of devices 0-63, one static per kernel) says it has been.  Call before every launch that asks for `bytes`.
+static inline int fs_lds_opt_in(const void* fn, int bytes, unsigned long long& done) {
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return FS_ERR_ARG;
+  if (dev < 0 || dev >= 64 || !((done >> dev) & 1ull)) {
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return (int)e;
+    if (dev >= 0 && dev < 64) done |= 1ull << dev;
+  }
+  return FS_OK;
+}
+
 // out[i] = (accumulate ? out[i] : 0) + part[0][i] + part[1][i] + ... + part[nslab-1][i], in that order (elementwise.hip).  The second stage
 // of every cross-workgroup sum of the library: per-workgroup partials are written with plain stores and added here in index order, so
 // no result depends on the order in which workgroups finish.

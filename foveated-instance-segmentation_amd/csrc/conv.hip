@@ -39,23 +39,8 @@ __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned by
   return __builtin_bit_cast(f32x4, v);
 }
 
-struct ConvArgs {
-  const float* src;   // fwd: X (B,Hs,Ws,Cs)      bwd-data: dY
-  const float* w;     // [R][S][Cin][Cout]
-  const float* bias;  // fwd only, may be null
-  float* dst;         // fwd: Y (B,Hd,Wd,Cd)      bwd-data: dX
-  int B, Hs, Ws, Cs, Hd, Wd, Cd;
-  int R, S, stride, pad, dil;
-  int transposed;     // 0 = forward, 1 = bwd-data
-  float drop_scale;   // 1/(1-p)
-  uint32_t drop_thresh, drop_key;   // thresh 0 = no dropout
-  hipStream_t stream_ = nullptr;    // host only
-  float* stats_ = nullptr;          // host only: BN partial-sum slab (affine forward)
-  const FsBnSums* bn_ = nullptr;    // host only: bwd-data writes the consumer BatchNorm's backward sums into stats_ (F(2,3) kernels)
-  void* ws_ = nullptr;              // host only: caller's scratch for the pre-split weight pack (may be null)
-  long ws_bytes_ = 0;
-  const unsigned* w_amax_ = nullptr;   // host only: max|w| bits kept by the caller (f16x2 mode), may be null
-};
+// The generic kernel takes the problem by value: the bytes of FsConvProblem (conv_kernels.h) under the name its symbol carries.
+struct ConvArgs : FsConvProblem {};
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(ConvArgs a) {
@@ -1001,8 +986,6 @@ int launch_affine_one(AffArgs& a, hipStream_t stream) {
 // Every kernel but the generic one addresses a tensor with 32-bit BYTE offsets (raw buffer resources, 32-bit store offsets in the
 // epilogues), so it takes tensors below 4 GB only -- 2^30 elements, not 2^31.
 bool fits32(size_t elements) { return elements * 4 < 4294967000UL; }
-size_t src_elems(const ConvArgs& c) { return (size_t)c.B * c.Hs * c.Ws * c.Cs; }
-size_t dst_elems(const ConvArgs& c) { return (size_t)c.B * c.Hd * c.Wd * c.Cd; }
 
 // One value per launch path of launch_conv.
 enum Route { GENERIC, PLAIN, HALO, WINO_F23, WINO_F43, TAPSET_FWD, TAPSET_BWD1, POINTWISE, GATHER, SCATTER, S2FWD, S2BWD, PARITY };
@@ -1047,7 +1030,7 @@ bool tapset_shape_ok(int Cs, int Cd, int R, int S, int stride, int dil) {
          ((R + stride - 1) / stride) * ((S + stride - 1) / stride) <= 64;
 }
 
-void conv_families(const ConvArgs& c, FamilyFit (&f)[N_FAMILIES]) {
+void conv_families(const FsConvProblem& c, FamilyFit (&f)[N_FAMILIES]) {
   static const bool s2fwd_on = FS_ENV_INT("FS_S2FWD", 1) != 0, s2bwd_on = FS_ENV_INT("FS_S2BWD", 1) != 0;
   static const bool pointwise_on = FS_ENV_INT("FS_POINTWISE", 1) != 0, gather_on = FS_ENV_INT("FS_PW_GATHER", 1) != 0;
   const int m = g_conv_precision;
@@ -1090,15 +1073,15 @@ void conv_families(const ConvArgs& c, FamilyFit (&f)[N_FAMILIES]) {
 //   8. S2BWD      3x3 / stride 2 / pad 1 bwd-data
 //   9. SCATTER    bwd-data, stride >= filter
 //  10. PARITY     any other strided bwd-data: one dense sub-problem per output parity class
-ConvPlan plan_conv(const ConvArgs& c, unsigned want) {
+ConvPlan plan_conv(const FsConvProblem& c, unsigned want) {
   const int m = g_conv_precision;
   const bool fwd = !c.transposed;
   FamilyFit f[N_FAMILIES];
   conv_families(c, f);
-  const bool split = m >= 1 && c.ws_ != nullptr && fits32(dst_elems(c));
+  const bool split = m >= 1 && c.ws_ != nullptr && fits32(c.dst_elems());
   auto has = [&](Family k) { return split && f[k].shape_ok && c.ws_bytes_ >= f[k].pack; };
   Route r;
-  if (c.Cs % 4 != 0 || c.Cd % 4 != 0 || c.R * c.S > 32 || !fits32(src_elems(c))) r = GENERIC;
+  if (c.Cs % 4 != 0 || c.Cd % 4 != 0 || c.R * c.S > 32 || !fits32(c.src_elems())) r = GENERIC;
   else if (has(F_S2FWD)) r = S2FWD;
   else if (has(F_HALO)) {
     const bool wino = has(F_WINO) && fs_wino_eligible(m, c.B, c.Hd, c.Wd, c.Cs, c.Cd);
@@ -1134,20 +1117,20 @@ ConvPlan plan_conv(const ConvArgs& c, unsigned want) {
   return p;
 }
 
-int launch_generic(const ConvArgs& c) {
+int launch_generic(const FsConvProblem& c) {
   if (c.stats_ != nullptr) return FS_ERR_ARG;      // no BatchNorm partials in its epilogue
   dim3 grid(cdiv((long)c.B * c.Hd * c.Wd, BM), cdiv(c.Cd, BN));
   if (c.Cs % 4 == 0 && c.Cd % 4 == 0)
-    hipLaunchKernelGGL(conv_igemm_kernel<true>, grid, dim3(256), 0, c.stream_, c);
+    hipLaunchKernelGGL(conv_igemm_kernel<true>, grid, dim3(256), 0, c.stream_, ConvArgs{c});
   else
-    hipLaunchKernelGGL(conv_igemm_kernel<false>, grid, dim3(256), 0, c.stream_, c);
+    hipLaunchKernelGGL(conv_igemm_kernel<false>, grid, dim3(256), 0, c.stream_, ConvArgs{c});
   FS_LAUNCH_CHECK();
   return FS_OK;
 }
 
 // dX pixels (y, x) whose class (y % stride, x % stride) is in `classes` <- 0: the classes no tap reaches (stride > filter size: 7 of 16 for
 // 3x3 stride 4, 15 of 16 for 1x1 stride 4), one store-only launch instead of one conv launch each (1x1 stride 4, 1.57 GB of dX: 1.13 -> 0.55 ms)
-int zero_classes(const ConvArgs& c, unsigned classes) {
+int zero_classes(const FsConvProblem& c, unsigned classes) {
   if (classes == 0u) return FS_OK;
   const long n4 = (long)c.B * c.Hd * c.Wd * (c.Cd / 4);
   long blocks = (n4 + 255) / 256;
@@ -1157,21 +1140,18 @@ int zero_classes(const ConvArgs& c, unsigned classes) {
   return FS_OK;
 }
 
-FsTapsetProblem tapset_base(const ConvArgs& c) {
-  FsTapsetProblem p{};
-  p.src = c.src; p.w = c.w; p.bias = c.bias; p.dst = c.dst; p.stats = c.stats_; p.ws = c.ws_; p.w_amax = c.w_amax_;
-  p.B = c.B; p.Hs = c.Hs; p.Ws = c.Ws; p.Cs = c.Cs; p.Hd = c.Hd; p.Wd = c.Wd; p.Cd = c.Cd;
-  p.Cin = c.transposed ? c.Cd : c.Cs; p.Cout = c.transposed ? c.Cs : c.Cd; p.R = c.R; p.S = c.S;
-  p.transposed = c.transposed;
-  p.drop_scale = c.drop_scale; p.drop_thresh = c.drop_thresh; p.drop_key = c.drop_key;
-  p.Hq = c.Hd; p.Wq = c.Wd; p.os = 1; p.oy0 = 0; p.ox0 = 0; p.sm = 1;
-  return p;
+// the whole problem as the aligned implicit-GEMM kernels of this file take it (launch_parity narrows it to one parity class)
+AffArgs affine_args(const FsConvProblem& c) {
+  return AffArgs{c.src, c.w, c.bias, c.dst, c.B, c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd, c.R, c.S, c.stride, c.pad, c.dil, c.transposed,
+                 c.drop_scale, c.drop_thresh, c.drop_key, (unsigned)(c.src_elems() * 4), (unsigned)((size_t)c.R * c.S * c.Cs * c.Cd * 4),
+                 fits32(c.dst_elems()) ? (unsigned)(c.dst_elems() * 4) : 0u,
+                 c.Hd, c.Wd, 1, 0, 0, 0, 0, 1, c.R, c.S, c.pad, c.pad, 0, 0, c.stats_};
 }
 
 // stride>1 bwd-data: one dense sub-problem per output parity class (oy0, ox0).  dX pixel y receives
 // tap r iff (y + pad - r) % stride == 0, i.e. r = r0 + stride*t with r0 = (oy0 + pad) % stride, and then
 // reads dY row (y + pad - r)/stride = py + (oy0 + pad - r0)/stride - t.
-int launch_parity(const ConvArgs& c, const AffArgs& a, bool tapset) {
+int launch_parity(const FsConvProblem& c, const AffArgs& a, bool tapset) {
   const int st = c.stride;
   const bool fill_ok = st * st <= 32 && c.Cd % 4 == 0 && c.bias == nullptr;
   unsigned empty_classes = 0u;
@@ -1190,11 +1170,11 @@ int launch_parity(const ConvArgs& c, const AffArgs& a, bool tapset) {
       int e;
       if (b.nR * b.nS > 1 && tapset) {       // single-tap sub-problems: no reuse, the plain kernel is faster
         // dY row of tap t is py + cy - t: in increasing source order tr = nR-1-t, filter row r0 + st*(nR-1-tr)
-        FsTapsetProblem p = tapset_base(c);
+        FsTapsetProblem p(c);
         p.Hq = b.Hq; p.Wq = b.Wq; p.os = st; p.oy0 = oy0; p.ox0 = ox0;
         p.ncls = 1;
         p.cls[0] = FsTapClass{b.cy - (b.nR - 1), b.cx - (b.nS - 1), b.nR, b.nS, b.r0 + st * (b.nR - 1), -st, b.s0 + st * (b.nS - 1), -st};
-        e = fs_tapset_conv(g_conv_precision, p, c.stream_);
+        e = fs_tapset_conv(g_conv_precision, p);
       } else {
         e = launch_affine_one(b, c.stream_);
       }
@@ -1203,79 +1183,63 @@ int launch_parity(const ConvArgs& c, const AffArgs& a, bool tapset) {
   return zero_classes(c, empty_classes);
 }
 
-int launch_conv(const ConvArgs& c, unsigned want = 0u) {
+int launch_conv(const FsConvProblem& c, unsigned want = 0u) {
   const ConvPlan plan = plan_conv(c, want);
   if (!plan.ok) return FS_ERR_ARG;                                  // the matching _ok / _slabs query reported 0 for this problem
   if (fs_ws_mode_tls != 0 && !plan.persistent) return FS_ERR_ARG;   // no weight pack that outlives a call
   const int m = g_conv_precision, st = c.stride;
-  const int Cin = c.transposed ? c.Cd : c.Cs, Cout = c.transposed ? c.Cs : c.Cd;
-  AffArgs a{c.src, c.w, c.bias, c.dst, c.B, c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd, c.R, c.S, c.stride, c.pad, c.dil, c.transposed,
-            c.drop_scale, c.drop_thresh, c.drop_key, (unsigned)(src_elems(c) * 4), (unsigned)((size_t)c.R * c.S * c.Cs * c.Cd * 4),
-            fits32(dst_elems(c)) ? (unsigned)(dst_elems(c) * 4) : 0u,
-            c.Hd, c.Wd, 1, 0, 0, 0, 0, 1, c.R, c.S, c.pad, c.pad, 0, 0, c.stats_};
   switch (plan.route) {
     case GENERIC: return launch_generic(c);
-    case PLAIN: return launch_affine_one(a, c.stream_);
-    case S2FWD:
-      return fs_s2fwd_conv(m, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd, c.drop_scale,
-                           c.drop_thresh, c.drop_key, c.stream_);
+    case PLAIN: {
+      AffArgs a = affine_args(c);
+      return launch_affine_one(a, c.stream_);
+    }
+    case S2FWD: return fs_s2fwd_conv(m, c);
     case WINO_F23:
-    case WINO_F43:      // fs_wino_conv3x3 hands the F(4,3) problems on to conv_wino4.hip
-      return fs_wino_conv3x3(m, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cs, c.Cd, Cin, Cout, c.transposed,
-                             c.drop_scale, c.drop_thresh, c.drop_key, c.bn_, c.stream_);
-    case HALO:
-      return fs_halo_conv3x3(m, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cs, c.Cd, Cin, Cout, c.transposed,
-                             c.drop_scale, c.drop_thresh, c.drop_key, c.stream_);
+    case WINO_F43: return fs_wino_conv3x3(m, c);      // hands the F(4,3) problems on to conv_wino4.hip
+    case HALO: return fs_halo_conv3x3(m, c);
     case TAPSET_FWD: {
-      FsTapsetProblem p = tapset_base(c);
+      FsTapsetProblem p(c);
       p.sm = st;
-      p.ncls = 0;
       for (int r0 = 0; r0 < st && r0 < c.R; ++r0)
         for (int s0 = 0; s0 < st && s0 < c.S; ++s0)
           p.cls[p.ncls++] = FsTapClass{r0 - c.pad, s0 - c.pad, (c.R - r0 + st - 1) / st, (c.S - s0 + st - 1) / st, r0, st, s0, st};
-      return fs_tapset_conv(m, p, c.stream_);
+      return fs_tapset_conv(m, p);
     }
     case TAPSET_BWD1: {
-      FsTapsetProblem p = tapset_base(c);
+      FsTapsetProblem p(c);
       p.ncls = 1;
       p.cls[0] = FsTapClass{c.pad - (c.R - 1), c.pad - (c.S - 1), c.R, c.S, c.R - 1, -1, c.S - 1, -1};
-      return fs_tapset_conv(m, p, c.stream_);
+      return fs_tapset_conv(m, p);
     }
-    case POINTWISE:
-      return fs_pointwise_conv(m, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, (long)c.B * c.Hd * c.Wd, c.Cs, c.Cd, Cin, Cout,
-                               c.transposed, c.drop_scale, c.drop_thresh, c.drop_key, c.bn_, c.stream_);
-    case GATHER:
-      return fs_pointwise_gather_conv(m, c.src, c.w, c.bias, c.dst, c.stats_, c.ws_, c.w_amax_, c.B, c.Hs, c.Ws, c.Cs, c.Hd, c.Wd, c.Cd, c.R, c.S,
-                                      st, c.pad, c.drop_scale, c.drop_thresh, c.drop_key, c.stream_);
-    case S2BWD:
-      return fs_s2bwd_conv(m, c.src, c.w, c.dst, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cd, c.Hs, c.Ws, c.Cs, c.bn_, c.stats_, c.stream_);
+    case POINTWISE: return fs_pointwise_conv(m, c);
+    case GATHER: return fs_pointwise_gather_conv(m, c);
+    case S2BWD: return fs_s2bwd_conv(m, c);
     case SCATTER: {
       unsigned empty = 0u;
       for (int oy0 = 0; oy0 < st; ++oy0)
         for (int ox0 = 0; ox0 < st; ++ox0)
           if ((oy0 + c.pad) % st >= c.R || (ox0 + c.pad) % st >= c.S) empty |= 1u << (oy0 * st + ox0);
       const int e = zero_classes(c, empty);
-      if (e != FS_OK) return e;
-      return fs_pointwise_scatter_conv(m, c.src, c.w, c.dst, c.ws_, c.w_amax_, c.B, c.Hd, c.Wd, c.Cd, c.Hs, c.Ws, c.Cs, c.R, c.S, st, c.pad,
-                                       c.stream_);
+      return e != FS_OK ? e : fs_pointwise_scatter_conv(m, c);
     }
-    case PARITY: return launch_parity(c, a, plan.tapset);
+    case PARITY: return launch_parity(c, affine_args(c), plan.tapset);
   }
   return FS_ERR_ARG;
 }
 
-// ---- what the entry points share: argument checks, ConvArgs from the C-ABI arguments, dropout rate -> threshold ------------------------
+// ---- what the entry points share: argument checks, FsConvProblem from the C-ABI arguments, dropout rate -> threshold -------------------
 bool conv_shape_ok(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil) {
   return B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0 && dil >= 1 &&
          Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1;
 }
 
 // transposed = 0: src = X (B,H,W,Cin), dst = Y (B,Ho,Wo,Cout);  1 (bwd-data): src = dY, dst = dX
-ConvArgs conv_args(const float* src, const float* w, const float* bias, float* dst, int B, int H, int W, int Cin, int Ho, int Wo, int Cout,
-                   int R, int S, int stride, int pad, int dil, int transposed, void* ws, long ws_bytes, const unsigned* w_amax,
-                   hipStream_t stream) {
-  ConvArgs a = transposed ? ConvArgs{src, w, bias, dst, B, Ho, Wo, Cout, H, W, Cin, R, S, stride, pad, dil, 1, 1.f, 0u, 0u}
-                          : ConvArgs{src, w, bias, dst, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, 0u};
+FsConvProblem conv_args(const float* src, const float* w, const float* bias, float* dst, int B, int H, int W, int Cin, int Ho, int Wo, int Cout,
+                        int R, int S, int stride, int pad, int dil, int transposed, void* ws, long ws_bytes, const unsigned* w_amax,
+                        hipStream_t stream) {
+  FsConvProblem a = transposed ? FsConvProblem{src, w, bias, dst, B, Ho, Wo, Cout, H, W, Cin, R, S, stride, pad, dil, 1, 1.f, 0u, 0u}
+                               : FsConvProblem{src, w, bias, dst, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, 1.f, 0u, 0u};
   a.stream_ = stream;
   a.ws_ = ws; a.ws_bytes_ = ws_bytes; a.w_amax_ = w_amax;
   return a;
@@ -1302,11 +1266,6 @@ bool fs_deterministic() { return g_deterministic != 0; }
 
 int fs_wgrad_reduce(float* part, int nslab, long n, float* dw, int accumulate, hipStream_t stream) {
   return fs_slab_reduce_inplace(part, nslab, n, dw, accumulate, stream);
-}
-
-static bool wgrad_shape_ok(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil) {
-  return B > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && R > 0 && S > 0 && stride > 0 && dil >= 1 &&
-         Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1;
 }
 
 // How a bwd-weight plan (conv_kernels.h FsWgradPlan) accumulates over its pixel splits, around the launches run(part) issues: dW, or
@@ -1399,8 +1358,8 @@ int fs_conv2d_pack(const float* w, int B, int H, int W, int Cin, int Ho, int Wo,
   FS_REQUIRE(w && ws && ws_bytes > 0 && conv_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil));
   // src / dst are never dereferenced: every family returns after its pack launch in this mode (launch_conv refuses the routes without a
   // persistent pack before anything is launched)
-  const ConvArgs a = conv_args(reinterpret_cast<const float*>(ws), w, nullptr, reinterpret_cast<float*>(ws), B, H, W, Cin, Ho, Wo, Cout, R, S,
-                               stride, pad, dil, transposed, ws, ws_bytes, w_amax, stream);
+  const FsConvProblem a = conv_args(reinterpret_cast<const float*>(ws), w, nullptr, reinterpret_cast<float*>(ws), B, H, W, Cin, Ho, Wo, Cout, R, S,
+                                    stride, pad, dil, transposed, ws, ws_bytes, w_amax, stream);
   const int old = fs_ws_mode_tls;
   fs_ws_mode_tls = FS_WS_PACK_ONLY;
   const int e = launch_conv(a);
@@ -1421,7 +1380,7 @@ int fs_conv2d_fwd(const float* x, const float* w, const float* bias, float* y, i
                   void* ws, long ws_bytes, const unsigned* w_amax, hipStream_t stream) {
   FS_REQUIRE(x && w && y && conv_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil));
   FS_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (long)B * Ho * Wo * Cout < 4294967296L);
-  ConvArgs a = conv_args(x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
+  FsConvProblem a = conv_args(x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
   a.drop_key = drop_key;
   drop_rate(drop_p, a.drop_scale, a.drop_thresh);
   return launch_conv(a);
@@ -1440,7 +1399,7 @@ int fs_conv2d_fwd_residual(const float* x, const float* w, const float* bias, co
                            uint32_t droppath_key, long rows_per_sample, void* ws, long ws_bytes, const unsigned* w_amax, hipStream_t stream) {
   FS_REQUIRE(x && w && res && y && drop_p >= 0.f && drop_p < 1.f && droppath_p >= 0.f && droppath_p < 1.f);
   FS_REQUIRE(fs_conv2d_fwd_residual_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, rows_per_sample, ws_bytes) == 1);
-  ConvArgs a = conv_args(x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
+  FsConvProblem a = conv_args(x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
   a.drop_key = drop_key;
   drop_rate(drop_p, a.drop_scale, a.drop_thresh);
   FsBnSums bn{nullptr, nullptr, nullptr, nullptr, res, nullptr, nullptr, nullptr, nullptr, 0, 1.f, 0u, droppath_key, (int)rows_per_sample};
@@ -1463,7 +1422,7 @@ int fs_conv2d_fwd_affine_act(const float* x, const float* w, const float* bias, 
   FS_REQUIRE(x && w && z && scale && shift && act >= 0 && act <= 2);
   FS_REQUIRE(fs_conv2d_fwd_affine_act_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes) == 1);
   FS_REQUIRE(Ho == (H + 2 * pad - dil * (R - 1) - 1) / stride + 1 && Wo == (W + 2 * pad - dil * (S - 1) - 1) / stride + 1);
-  ConvArgs a = conv_args(x, w, bias, z, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
+  FsConvProblem a = conv_args(x, w, bias, z, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
   const FsBnSums ep{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, scale, shift, res, act};
   a.bn_ = &ep;
   return launch_conv(a, EX_AFFINE_ACT);
@@ -1476,7 +1435,7 @@ int fs_conv2d_fwd_stats(const float* x, const float* w, const float* bias, float
                         void* ws, long ws_bytes, const unsigned* w_amax, hipStream_t stream) {
   FS_REQUIRE(x && w && y && stats && conv_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil));
   FS_REQUIRE(drop_p >= 0.f && drop_p < 1.f && (long)B * Ho * Wo * Cout < 4294967296L);
-  ConvArgs a = conv_args(x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
+  FsConvProblem a = conv_args(x, w, bias, y, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0, ws, ws_bytes, w_amax, stream);
   a.stats_ = stats;
   a.drop_key = drop_key;
   drop_rate(drop_p, a.drop_scale, a.drop_thresh);
@@ -1488,7 +1447,7 @@ static int conv2d_bwd_data_impl(const float* dy, const float* w, float* dx, int 
                                 int Cout, int R, int S, int stride, int pad, int dil, void* ws, long ws_bytes, const unsigned* w_amax,
                                 const FsBnSums* bn, float* slab, hipStream_t stream) {
   FS_REQUIRE(dy && w && dx && conv_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil) && (stride == 1 || dil == 1));
-  ConvArgs a = conv_args(dy, w, nullptr, dx, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 1, ws, ws_bytes, w_amax, stream);
+  FsConvProblem a = conv_args(dy, w, nullptr, dx, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 1, ws, ws_bytes, w_amax, stream);
   a.bn_ = bn; a.stats_ = slab;
   return launch_conv(a, bn == nullptr ? 0u : (bn->y ? EX_BNSUM : 0u) | (bn->add_src ? EX_ADDEND : 0u));
 }
@@ -1548,7 +1507,7 @@ int fs_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Ho, int Wo, int 
                               int* out) {
   if (out == nullptr) return 0;
   for (int i = 0; i < 6; ++i) out[i] = 0;
-  if (!wgrad_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)) return 0;
+  if (!conv_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)) return 0;
   const FsWgradPlan p = fs_wgrad_plan(g_conv_precision, g_deterministic != 0, false, ws_bytes > 0, ws_bytes, B, H, W, Cin, Ho, Wo, Cout, R, S,
                                       stride, pad, dil);
   out[0] = p.route; out[1] = p.accum; out[2] = p.nlaunch; out[3] = (int)p.wgs; out[4] = p.threads; out[5] = p.slabs;
@@ -1558,7 +1517,7 @@ int fs_conv2d_bwd_weight_plan(int B, int H, int W, int Cin, int Ho, int Wo, int 
 // include/fovealseg.h: fs_conv2d_bwd_weight   (dw is overwritten, or added to when accumulate != 0)
 int fs_conv2d_bwd_weight(const float* x, const float* dy, float* dw, int B, int H, int W, int Cin, int Ho, int Wo,
                          int Cout, int R, int S, int stride, int pad, int dil, int accumulate, void* ws, long ws_bytes, hipStream_t stream) {
-  FS_REQUIRE(x && dy && dw && wgrad_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil));
+  FS_REQUIRE(x && dy && dw && conv_shape_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil));
   const FsWgradPlan p = fs_wgrad_plan(g_conv_precision, g_deterministic != 0, accumulate != 0, ws != nullptr, ws_bytes, B, H, W, Cin, Ho, Wo, Cout,
                                       R, S, stride, pad, dil);
   FS_REQUIRE(p.ok);      // deterministic mode without scratch for the shape's slab cap: never the atomics silently

@@ -20,8 +20,7 @@
 //   * weights: one exponent per weight tensor (kept by the caller, fs_weight_amax_segments, or from an atomic-max pre-pass
 //     into the pack header); the pack kernel writes the planes already scaled.
 // The final result is acc * 2^(E-14) * 2^(Ew-14), applied in the epilogue.
-#include "conv_split.h"
-#include "conv_kernels.h"
+#include "conv_run.h"
 
 namespace {
 
@@ -413,25 +412,6 @@ static void halo_plan(int B, int H, int W, int& Ph, int& Pw, int& stacked, int& 
   }
 }
 
-template <class P>
-static int run_halo(HaloArgs& a, const float* w, void* ws, const unsigned* w_amax, int Cin, int Cout, int transposed, int nw,
-                    hipStream_t stream) {
-  int e = FS_OK;
-  a.ew = P::SCALED ? fs_f16_weight_amax(w, (long)9 * Cin * Cout, ws, w_amax, stream, &e) : nullptr;
-  if (e != FS_OK) return e;
-  const long total = (long)a.nchunk * 18 * a.Npad;
-  if (fs_ws_mode_tls != FS_WS_RUN_ONLY) {
-    hipLaunchKernelGGL((conv_pack_kernel<P>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, reinterpret_cast<unsigned char*>(ws),
-                       a.ew, Cin, Cout, transposed, a.Cs, a.Cd, a.Npad, total);
-    FS_LAUNCH_CHECK();
-  }
-  if (fs_ws_mode_tls == FS_WS_PACK_ONLY) return FS_OK;
-  if (nw == 2) hipLaunchKernelGGL((conv3x3_halo_kernel<P, 2>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((conv3x3_halo_kernel<P, 1>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
 bool fs_halo_eligible(int H, int W, int Cs, int Cd, int R, int S, int stride, int pad, int dil) {
   (void)H; (void)W;
   return R == 3 && S == 3 && stride == 1 && pad == 1 && dil == 1 && Cs % 4 == 0 && Cd % 4 == 0 && Cs >= 32;
@@ -449,11 +429,10 @@ long fs_halo_pack_bytes(int mode, int Cs, int Cd) {
   return HDR + nchunk * 18 * npl * Npad * 16 * 2;
 }
 
-int fs_halo_conv3x3(int mode, const float* src, const float* w, const float* bias, float* dst, float* stats, void* ws, const unsigned* w_amax,
-                    int B, int H, int W, int Cs, int Cd, int Cin, int Cout, int transposed, float drop_scale, uint32_t drop_thresh,
-                    uint32_t drop_key, hipStream_t stream) {
+int fs_halo_conv3x3(int mode, const FsConvProblem& c) {
+  const int B = c.B, H = c.Hd, W = c.Wd, Cs = c.Cs, Cd = c.Cd;
   HaloArgs a;
-  a.src = src; a.ws = reinterpret_cast<const unsigned char*>(ws); a.bias = bias; a.dst = dst; a.stats = stats;
+  a.src = c.src; a.ws = reinterpret_cast<const unsigned char*>(c.ws_); a.bias = c.bias; a.dst = c.dst; a.stats = c.stats_;
   a.B = B; a.H = H; a.W = W; a.Cs = Cs; a.Cd = Cd;
   const int nwp = halo_nw(Cd);
   a.Npad = ((Cd + 64 * nwp - 1) / (64 * nwp)) * 64 * nwp;      // row count of the pack (fs_halo_pack_bytes)
@@ -467,12 +446,20 @@ int fs_halo_conv3x3(int mode, const float* src, const float* w, const float* bia
   a.ny = nw == 2 ? a.Npad / 128 : (Cd + 63) / 64;
   a.magic_pw = div_magic(a.Pw);
   a.magic_wh = div_magic(a.Pw + 2);
-  a.src_bytes = (unsigned)((size_t)B * H * W * Cs * 4);
-  a.dst_bytes = (unsigned)((size_t)B * H * W * Cd * 4);
-  const long pack_bytes = fs_halo_pack_bytes(mode, Cs, Cd);
-  if (pack_bytes >= 2147483647L || (size_t)B * H * W * Cs * 4 >= 4294967000UL || (size_t)B * H * W * Cd * 4 >= 4294967000UL) return FS_ERR_ARG;
-  a.ws_bytes = (unsigned)pack_bytes;
-  a.drop_scale = drop_scale; a.drop_thresh = drop_thresh; a.drop_key = drop_key;
-  return mode == 2 ? run_halo<PrecF16>(a, w, ws, w_amax, Cin, Cout, transposed, nw, stream)
-                   : run_halo<PrecX3>(a, w, ws, w_amax, Cin, Cout, transposed, nw, stream);
+  if (!fs_sizes32(fs_halo_pack_bytes(mode, Cs, Cd), c.src_elems(), c.dst_elems(), a.src_bytes, a.dst_bytes, a.ws_bytes)) return FS_ERR_ARG;
+  a.drop_scale = c.drop_scale; a.drop_thresh = c.drop_thresh; a.drop_key = c.drop_key;
+  const long total = (long)a.nchunk * 18 * a.Npad;
+  return fs_pack_then_run(
+      mode, c,
+      [&](auto prec, const unsigned* ew) {
+        hipLaunchKernelGGL((conv_pack_kernel<decltype(prec)>), fs_pack_grid(total), dim3(256), 0, c.stream_, c.w, reinterpret_cast<unsigned char*>(c.ws_),
+                           ew, c.Cin(), c.Cout(), c.transposed, a.Cs, a.Cd, a.Npad, total);
+      },
+      [&](auto prec, const unsigned* ew) {
+        typedef decltype(prec) P;
+        a.ew = ew;
+        if (nw == 2) hipLaunchKernelGGL((conv3x3_halo_kernel<P, 2>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, c.stream_, a);
+        else hipLaunchKernelGGL((conv3x3_halo_kernel<P, 1>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, c.stream_, a);
+        return FS_OK;
+      });
 }

@@ -1,8 +1,36 @@
-// Internal interface between conv.hip (C-ABI entry points, kernel selection) and the split-precision kernel families
-// (conv_halo.hip, conv_tapset.hip, conv_wgrad.hip).  Not part of include/fovealseg.h.
+// Internal interface between conv.hip (C-ABI entry points, kernel selection: plan_conv) and the split-precision kernel families it hands
+// a problem to -- forward / bwd-data: conv_halo.hip, conv_wino.hip, conv_wino4.hip, conv_tapset.hip, conv_pointwise.hip, conv_s2fwd.hip,
+// conv_s2bwd.hip; bwd-weight: conv_wgrad.hip.  Every forward / bwd-data family takes (mode, FsConvProblem) and runs its weight pack and
+// its kernel through fs_pack_then_run (conv_run.h).  Not part of include/fovealseg.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+struct FsBnSums;
+// One forward / bwd-data problem as conv.hip's entry points state it and every family receives it.  NHWC fp32 tensors.  The generic
+// kernel of conv.hip takes these bytes by value (as its ConvArgs), so the fields keep their order and the host-only ones stay behind.
+struct FsConvProblem {
+  const float* src;   // fwd: X (B,Hs,Ws,Cs)      bwd-data: dY
+  const float* w;     // [R][S][Cin][Cout]
+  const float* bias;  // fwd only, may be null
+  float* dst;         // fwd: Y (B,Hd,Wd,Cd)      bwd-data: dX
+  int B, Hs, Ws, Cs, Hd, Wd, Cd;
+  int R, S, stride, pad, dil;
+  int transposed;     // 0 = forward (K = Cin, N = Cout), 1 = bwd-data (K = Cout, N = Cin)
+  float drop_scale;   // 1/(1-p)
+  uint32_t drop_thresh, drop_key;   // thresh 0 = no dropout
+  hipStream_t stream_ = nullptr;    // host only
+  float* stats_ = nullptr;          // host only: BN partial-sum slab (forward); bwd-data: where the sums bn_ asks for go
+  const FsBnSums* bn_ = nullptr;    // host only: extras fused into the epilogue (FsBnSums below), may be null
+  void* ws_ = nullptr;              // host only: caller's scratch for the pre-split weight pack (may be null)
+  long ws_bytes_ = 0;
+  const unsigned* w_amax_ = nullptr;   // host only: max|w| bits kept by the caller (f16x2 mode), may be null
+  int Cin() const { return transposed ? Cd : Cs; }      // the logical weight shape
+  int Cout() const { return transposed ? Cs : Cd; }
+  long w_elems() const { return (long)R * S * Cs * Cd; }
+  size_t src_elems() const { return (size_t)B * Hs * Ws * Cs; }
+  size_t dst_elems() const { return (size_t)B * Hd * Wd * Cd; }
+};
 
 // ---- conv_halo.hip: halo-tiled 3x3 / stride 1 / pad 1 kernel.  mode: 1 = bf16x3, 2 = f16x2 (conv_split.h) ----------------
 // 3x3, stride 1, pad 1, dilation 1, channel counts multiples of 4, K >= 32
@@ -11,17 +39,15 @@ bool fs_halo_eligible(int H, int W, int Cs, int Cd, int R, int S, int stride, in
 long fs_halo_pack_bytes(int mode, int Cs, int Cd);
 // number of pixel tiles (= BatchNorm partial-sum slabs) the kernel uses for a (B,H,W) output
 int fs_halo_stats_slabs(int B, int H, int W);
-// pack w (RSCK fp32, logical Cin x Cout) into ws, then run the conv.  transposed = 1: bwd-data (src = dY with Cs = Cout channels,
-// dst = dX with Cd = Cin channels).  stats may be null.  w_amax: max|w| bits kept by the caller, or null (f16x2 only).
-int fs_halo_conv3x3(int mode, const float* src, const float* w, const float* bias, float* dst, float* stats, void* ws, const unsigned* w_amax,
-                    int B, int H, int W, int Cs, int Cd, int Cin, int Cout, int transposed, float drop_scale, uint32_t drop_thresh,
-                    uint32_t drop_key, hipStream_t stream);
+// pack c.w into c.ws_, then run the conv (source and destination have one size).  c.stats_ may be null.
+int fs_halo_conv3x3(int mode, const FsConvProblem& c);
 // where the f16x2 kernels read max |w| (float bits) of a weight tensor: w_amax when the caller maintains it, else the first
 // word of ws, filled here by a memset + atomic-max kernel.
 const unsigned* fs_f16_weight_amax(const float* w, long n, void* ws, const unsigned* w_amax, hipStream_t stream, int* err);
 // How the calling thread's next conv entry point treats `ws` (fs_conv2d_ws_mode / fs_conv2d_pack, include/fovealseg.h): 0 = pack the
 // weights into ws, then run (the default); FS_WS_RUN_ONLY = ws already holds this layer's pack for this shape and precision (the pack
-// launch is skipped); FS_WS_PACK_ONLY = run the pack launch and return.  Every kernel family with a weight pack honours it.
+// launch is skipped); FS_WS_PACK_ONLY = run the pack launch and return.  Read by fs_pack_then_run (conv_run.h), which every kernel family
+// with a weight pack goes through, by fs_f16_weight_amax and by conv.hip's entry points.
 extern thread_local int fs_ws_mode_tls;
 #define FS_WS_RUN_ONLY 1
 #define FS_WS_PACK_ONLY 2
@@ -41,9 +67,7 @@ struct FsBnSums {
 bool fs_wino_eligible(int mode, int B, int H, int W, int Cs, int Cd);
 long fs_wino_pack_bytes(int mode, int Cs, int Cd);
 int fs_wino_stats_slabs(int mode, int B, int H, int W, int Cs, int Cd);
-int fs_wino_conv3x3(int mode, const float* src, const float* w, const float* bias, float* dst, float* stats, void* ws, const unsigned* w_amax,
-                    int B, int H, int W, int Cs, int Cd, int Cin, int Cout, int transposed, float drop_scale, uint32_t drop_thresh,
-                    uint32_t drop_key, const FsBnSums* bn, hipStream_t stream);
+int fs_wino_conv3x3(int mode, const FsConvProblem& c);      // hands the problems fs_wino_takes_f43 names on to fs_wino4_conv3x3
 
 // ---- conv_wino4.hip (round 5): the same problem class with F(4,3) along the row (18 MFMA steps per four output pixels instead of 24):
 // bf16x3 only, W a multiple of 4.  fs_wino_conv3x3 / fs_wino_pack_bytes / fs_wino_stats_slabs route to it where fs_wino4_selected holds.
@@ -51,28 +75,21 @@ bool fs_wino_takes_f43(int mode, int B, int H, int W, int Cs, int Cd);      // c
 bool fs_wino4_eligible(int mode, int B, int H, int W, int Cs, int Cd);
 long fs_wino4_pack_bytes(int mode, int Cs, int Cd);
 int fs_wino4_stats_slabs(int B, int H, int W, int Cs, int Cd);
-int fs_wino4_conv3x3(int mode, const float* src, const float* w, const float* bias, float* dst, float* stats, void* ws, int B, int H, int W, int Cs,
-                     int Cd, int Cin, int Cout, int transposed, float drop_scale, uint32_t drop_thresh, uint32_t drop_key, const FsBnSums* bn,
-                     hipStream_t stream);
+int fs_wino4_conv3x3(int mode, const FsConvProblem& c);
 
 // ---- conv_pointwise.hip: 1x1 / stride 1 / pad 0 as a GEMM with pre-split weights (forward and bwd-data).  mode: 1 = bf16x3, 2 = f16x2 ----
 bool fs_pointwise_eligible(int Cs, int Cd, int R, int S, int stride, int pad, int dil);
 long fs_pointwise_pack_bytes(int mode, int Cs, int Cd);
 // forward of a stride >= filter convolution as one GEMM over gathered rows (K = R*S*Cin; pack bytes = fs_pointwise_pack_bytes(mode, K, Cout))
 bool fs_pointwise_gather_eligible(int Cin, int Cout, int R, int S, int stride, int dil);
-int fs_pointwise_gather_conv(int mode, const float* x, const float* w, const float* bias, float* y, float* stats, void* ws, const unsigned* w_amax,
-                             int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, float drop_scale,
-                             uint32_t drop_thresh, uint32_t drop_key, hipStream_t stream);
+int fs_pointwise_gather_conv(int mode, const FsConvProblem& c);
 // bwd-data of those layers: one GEMM per tap whose rows are scattered to the tap's residue class of dX (the caller zero-fills the classes no
 // tap reaches); pack bytes = fs_pointwise_pack_bytes(mode, Cout, Cin)
 bool fs_pointwise_scatter_eligible(int Cin, int Cout, int R, int S, int stride, int dil);
-int fs_pointwise_scatter_conv(int mode, const float* dy, const float* w, float* dx, void* ws, const unsigned* w_amax, int B, int H, int W,
-                              int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, hipStream_t stream);
-// M = B*H*W rows; transposed = 1: bwd-data (src = dY with Cs = Cout channels, dst = dX with Cd = Cin).  stats: [ceil(M/128)][Cd][2] or null.
-// bn (bwd-data only, may be null): stats then receives the BatchNorm-backward sums of the layer that produced x, and / or a second gradient joins dst
-int fs_pointwise_conv(int mode, const float* src, const float* w, const float* bias, float* dst, float* stats, void* ws, const unsigned* w_amax,
-                      long M, int Cs, int Cd, int Cin, int Cout, int transposed, float drop_scale, uint32_t drop_thresh, uint32_t drop_key,
-                      const FsBnSums* bn, hipStream_t stream);
+int fs_pointwise_scatter_conv(int mode, const FsConvProblem& c);
+// M = B*Hd*Wd rows.  c.stats_: [ceil(M/128)][Cd][2] or null.  c.bn_ (may be null): in bwd-data stats_ then receives the BatchNorm-backward
+// sums of the layer that produced x, and / or a second gradient joins dst; forward: the residual + DropPath epilogue
+int fs_pointwise_conv(int mode, const FsConvProblem& c);
 int fs_pointwise_stats_slabs(long M);
 
 // ---- deterministic split-K (include/fovealseg.h fs_set_deterministic) ----------------------------------------------------------
@@ -148,32 +165,27 @@ int fs_wgrad_launch(const FsWgradPlan& p, const float* x, const float* dy, float
 // ---- conv_s2bwd.hip: bwd-data of a 3x3 / stride 2 / pad 1 convolution, the four output parities in one launch ----
 bool fs_s2bwd_eligible(int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil);
 long fs_s2bwd_pack_bytes(int mode, int Cin, int Cout);
-// bn (may be null): slab[fs_s2bwd_stats_slabs][Cin][2] receives the BatchNorm-backward sums of the layer that produced x, and / or a second gradient joins dX
+// c.bn_ (may be null): c.stats_[fs_s2bwd_stats_slabs][Cin][2] receives the BatchNorm-backward sums of the layer that produced x, and / or a
+// second gradient joins dX
 int fs_s2bwd_stats_slabs(int B, int Ho, int Wo);
-int fs_s2bwd_conv(int mode, const float* dy, const float* w, float* dx, void* ws, const unsigned* w_amax, int B, int H, int W, int Cin, int Ho,
-                  int Wo, int Cout, const FsBnSums* bn, float* slab, hipStream_t stream);
+int fs_s2bwd_conv(int mode, const FsConvProblem& c);
 
 // ---- conv_s2fwd.hip: forward of a 3x3 / stride 2 / pad 1 convolution, the four input parity planes in one LDS refill per chunk ----
 bool fs_s2fwd_eligible(int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil);
 long fs_s2fwd_pack_bytes(int mode, int Cin, int Cout);
 int fs_s2fwd_slabs(int B, int Ho, int Wo);          // BatchNorm partial-sum slabs (= pixel tiles) of the stats variant
-int fs_s2fwd_conv(int mode, const float* x, const float* w, const float* bias, float* y, float* stats, void* ws, const unsigned* w_amax,
-                  int B, int H, int W, int Cin, int Ho, int Wo, int Cout, float drop_scale, uint32_t drop_thresh, uint32_t drop_key,
-                  hipStream_t stream);
+int fs_s2fwd_conv(int mode, const FsConvProblem& c);
 
 // conv_tapset.hip: general halo-tiled split-precision convolution over a list of tap classes.
 //   source row of (loop row oy, class tap tr) = sm*(oy + tr) + cy,  filter row r = rbase + rstep*tr  (columns alike)
 struct FsTapClass { int cy, cx, nR, nS, rbase, rstep, sbase, sstep; };
-struct FsTapsetProblem {
-  const float* src; const float* w; const float* bias; float* dst; float* stats; void* ws; const unsigned* w_amax;
-  int B, Hs, Ws, Cs, Hd, Wd, Cd;     // source / destination tensors (NHWC)
-  int Cin, Cout, R, S;               // logical weight shape [R][S][Cin][Cout]
-  int transposed;                    // 0: K = Cin, N = Cout;  1 (bwd-data): K = Cout, N = Cin
-  int Hq, Wq, os, oy0, ox0, sm;      // loop grid; destination pixel = (oy*os + oy0, ox*os + ox0)
-  int ncls; FsTapClass cls[9];
-  float drop_scale; uint32_t drop_thresh, drop_key;
+// the problem plus what this family adds: the loop grid (by default the whole destination) and the tap classes
+struct FsTapsetProblem : FsConvProblem {
+  explicit FsTapsetProblem(const FsConvProblem& c) : FsConvProblem(c), Hq(c.Hd), Wq(c.Wd) {}
+  int Hq, Wq, os = 1, oy0 = 0, ox0 = 0, sm = 1;      // destination pixel = (oy*os + oy0, ox*os + ox0), oy < Hq, ox < Wq
+  int ncls = 0; FsTapClass cls[9];
 };
 long fs_tapset_pack_bytes(int mode, int Cs, int Cd, int total_taps);
 int fs_tapset_slabs(int B, int Hq, int Wq, int maxR, int maxS);
-int fs_tapset_conv(int mode, const FsTapsetProblem& p, hipStream_t stream);      // mode: 1 = bf16x3, 2 = f16x2
+int fs_tapset_conv(int mode, const FsTapsetProblem& p);      // mode: 1 = bf16x3, 2 = f16x2
 void fs_tapset_patch(int Hq, int Wq, int maxR, int maxS, int* Ph, int* Pw);

@@ -12,8 +12,7 @@
 //     one exponent per weight tensor; result = acc * 2^(E-14) * 2^(Ew-14).
 // The plain kernel (conv_igemm_split_kernel) splits both operands inside the kernel for every 32-channel stage and re-reads the
 // A tile once per 64 output channels: 60 VALU instructions per MFMA on 64->256 @ 80x80 (profiles/r01/pmc/...shape5.txt).
-#include "conv_split.h"
-#include "conv_kernels.h"
+#include "conv_run.h"
 
 namespace {
 
@@ -78,7 +77,7 @@ __global__ __launch_bounds__(256) void conv1x1_pack_kernel(const float* __restri
   }
 }
 
-// DB (bf16x3, kernel A/B builds only -- measured slower, see run_pointwise): the two LDS chunk images are a double buffer -- while the
+// DB (bf16x3, kernel A/B builds only -- measured slower, see pw_run): the two LDS chunk images are a double buffer -- while the
 // MFMAs of 32-channel chunk c run on one image, chunk c + 1 (loaded one round earlier) is split and stored into the other, half of it
 // behind each k16 step; ONE barrier per chunk instead of load -> barrier -> split + store -> barrier -> MFMAs per pair of chunks.
 template <class P, int NW, bool DB, bool BN = false>
@@ -498,44 +497,63 @@ __global__ __launch_bounds__(256, 2) void conv1x1_gemm_kernel(PwArgs a) {
 
 static inline int pw_nw(int Cd) { return Cd >= 128 ? 2 : 1; }
 
-template <class P>
-static int run_pointwise(PwArgs& a, const float* w, void* ws, const unsigned* w_amax, int Cin, int Cout, int transposed, int nw, hipStream_t stream) {
-  int e = FS_OK;
-  a.ew = P::SCALED ? fs_f16_weight_amax(w, (long)Cin * Cout, ws, w_amax, stream, &e) : nullptr;
-  if (e != FS_OK) return e;
+// Kernel arguments of the GEMM  dst[M][Ns] = rows of src [.][Ks] x pack  on c's tensors: bias, stats and dropout as c states them, the
+// fused extras off, plain rows (no gather, no scatter); nchunk = K chunks of 32.  The column tiling follows with pw_columns.
+static PwArgs pw_args(const FsConvProblem& c, long M, int Ks, int Ns, int nchunk) {
+  PwArgs a;
+  a.src = c.src; a.ws = reinterpret_cast<const unsigned char*>(c.ws_); a.bias = c.bias; a.dst = c.dst; a.stats = c.stats_;
+  fs_fill_bwd_extras(a, nullptr);
+  a.dp_scale = 1.f; a.dp_thresh = 0u; a.dp_key = 0u; a.dp_rows = 0;
+  a.M = M; a.Cs = Ks; a.Cd = Ns;
+  const int nwp = pw_nw(Ns);
+  a.Npad = ((Ns + 64 * nwp - 1) / (64 * nwp)) * 64 * nwp;
+  a.nchunk = nchunk;
+  a.nx = cdiv(M, ROWS);
+  a.drop_scale = c.drop_scale; a.drop_thresh = c.drop_thresh; a.drop_key = c.drop_key;
+  a.ntap = 0; a.S = 1; a.Hx = a.Wx = a.Ho = a.Wo = 1; a.st = 1; a.pad = 0; a.Cin = Ks; a.rounds_per_tap = 1;
+  a.sc_on = 0; a.sc_st = 1; a.sc_dy = a.sc_dx = 0; a.sc_H = a.sc_W = 1;
+  return a;
+}
+// nw = 32-column sub-tiles per wave: 128- or 64-column workgroups
+static void pw_columns(PwArgs& a, int nw) { a.ny = nw == 2 ? a.Npad / 128 : (a.Cd + 63) / 64; }
+
+// pack c.w as a [Kin][c.Cout()] matrix (c.transposed: read it transposed), then the GEMM a describes
+static int pw_run(int mode, const FsConvProblem& c, PwArgs& a, int Kin, int nw) {
   const long total = (long)a.nchunk * 2 * a.Npad;
-  if (fs_ws_mode_tls != FS_WS_RUN_ONLY) {
-    hipLaunchKernelGGL((conv1x1_pack_kernel<P>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, reinterpret_cast<unsigned char*>(ws), a.ew,
-                       Cin, Cout, transposed, a.Cs, a.Cd, a.Npad, total);
-    FS_LAUNCH_CHECK();
-  }
-  if (fs_ws_mode_tls == FS_WS_PACK_ONLY) return FS_OK;
+  return fs_pack_then_run(
+      mode, c,
+      [&](auto prec, const unsigned* ew) {
+        hipLaunchKernelGGL((conv1x1_pack_kernel<decltype(prec)>), fs_pack_grid(total), dim3(256), 0, c.stream_, c.w,
+                           reinterpret_cast<unsigned char*>(c.ws_), ew, Kin, c.Cout(), c.transposed, a.Cs, a.Cd, a.Npad, total);
+      },
+      [&](auto prec, const unsigned* ew) {
+        typedef decltype(prec) P;
+        a.ew = ew;
+        const dim3 grid((unsigned)(a.nx * a.ny));
 #ifdef FS_EXPERIMENTS
-  // the double-buffered chunk loop (bf16x3), measured and rejected (profiles/r04/pw_db_ab.txt: 960 -> 512 3x3 s4 forward 1 273 -> 1 360 us,
-  // configs[3] -1.2 %, configs[4] -4 % with the split + store behind each step's 24 MFMAs; 1 225 -> 1 284 us, -2 %, -3 % with it interleaved
-  // between the MFMAs by sched_group_barrier, the form kept here): two workgroups per CU alternating whole phases beat one wave
-  // interleaving its own.  Only the A/B build carries it (FS_PW_DB=1 from three chunks up, 2 always)
-  static const int db_pol = FS_ENV_INT("FS_PW_DB", 0);
-  const bool db = !P::SCALED && (db_pol == 2 || (db_pol == 1 && a.nchunk >= 3));
-  if constexpr (!P::SCALED) {
-    if (db) {
-      if (nw == 2) hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 2, true>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-      else hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 1, true>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-      FS_LAUNCH_CHECK();
-      return FS_OK;
-    }
-  }
+        // the double-buffered chunk loop (bf16x3), measured and rejected (profiles/r04/pw_db_ab.txt: 960 -> 512 3x3 s4 forward 1 273 -> 1 360 us,
+        // configs[3] -1.2 %, configs[4] -4 % with the split + store behind each step's 24 MFMAs; 1 225 -> 1 284 us, -2 %, -3 % with it interleaved
+        // between the MFMAs by sched_group_barrier, the form kept here): two workgroups per CU alternating whole phases beat one wave
+        // interleaving its own.  Only the A/B build carries it (FS_PW_DB=1 from three chunks up, 2 always)
+        static const int db_pol = FS_ENV_INT("FS_PW_DB", 0);
+        const bool db = !P::SCALED && (db_pol == 2 || (db_pol == 1 && a.nchunk >= 3));
+        if constexpr (!P::SCALED) {
+          if (db) {
+            if (nw == 2) hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 2, true>), grid, dim3(256), 0, c.stream_, a);
+            else hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 1, true>), grid, dim3(256), 0, c.stream_, a);
+            return FS_OK;
+          }
+        }
 #endif
-  if (a.bn_y != nullptr || a.add_src != nullptr) {
-    if (nw == 2) hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 2, false, true>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 1, false, true>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-    FS_LAUNCH_CHECK();
-    return FS_OK;
-  }
-  if (nw == 2) hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 2, false>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 1, false>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
+        if (a.bn_y != nullptr || a.add_src != nullptr) {
+          if (nw == 2) hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 2, false, true>), grid, dim3(256), 0, c.stream_, a);
+          else hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 1, false, true>), grid, dim3(256), 0, c.stream_, a);
+        } else {
+          if (nw == 2) hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 2, false>), grid, dim3(256), 0, c.stream_, a);
+          else hipLaunchKernelGGL((conv1x1_gemm_kernel<P, 1, false>), grid, dim3(256), 0, c.stream_, a);
+        }
+        return FS_OK;
+      });
 }
 
 }  // namespace
@@ -553,43 +571,29 @@ long fs_pointwise_pack_bytes(int mode, int Cs, int Cd) {
 // rows of the [rows][Cd][2] slab the epilogue's column sums go to: one per 128-row tile
 int fs_pointwise_stats_slabs(long M) { return (int)cdiv(M, ROWS); }
 
-int fs_pointwise_conv(int mode, const float* src, const float* w, const float* bias, float* dst, float* stats, void* ws, const unsigned* w_amax,
-                      long M, int Cs, int Cd, int Cin, int Cout, int transposed, float drop_scale, uint32_t drop_thresh, uint32_t drop_key,
-                      const FsBnSums* bn, hipStream_t stream) {
-  PwArgs a;
-  a.src = src; a.ws = reinterpret_cast<const unsigned char*>(ws); a.bias = bias; a.dst = dst; a.stats = stats;
-  if (bn != nullptr && bn->y != nullptr && (!transposed || stats == nullptr)) return FS_ERR_ARG;      // the sums are a bwd-data extra
-  if (bn != nullptr && bn->dp_thresh != 0u && (transposed || bn->add_src == nullptr || bn->dp_rows < ROWS)) return FS_ERR_ARG;
-  a.bn_y = bn ? bn->y : nullptr; a.bn_mask = bn ? bn->mask : nullptr; a.bn_mean = bn ? bn->mean : nullptr; a.bn_invstd = bn ? bn->invstd : nullptr;
-  a.add_src = bn ? bn->add_src : nullptr; a.add_mask = bn ? bn->add_mask : nullptr;
-  a.dp_scale = bn ? bn->dp_scale : 1.f; a.dp_thresh = bn ? bn->dp_thresh : 0u; a.dp_key = bn ? bn->dp_key : 0u; a.dp_rows = bn ? bn->dp_rows : 0;
-  a.M = M; a.Cs = Cs; a.Cd = Cd;
-  const int nwp = pw_nw(Cd);
-  a.Npad = ((Cd + 64 * nwp - 1) / (64 * nwp)) * 64 * nwp;
-  a.nchunk = (Cs + 31) / 32;
-  a.nx = cdiv(M, ROWS);
+int fs_pointwise_conv(int mode, const FsConvProblem& c) {
+  const FsBnSums* bn = c.bn_;
+  const long M = (long)c.B * c.Hd * c.Wd;
+  const int Cd = c.Cd;
+  if (bn != nullptr && bn->y != nullptr && (!c.transposed || c.stats_ == nullptr)) return FS_ERR_ARG;      // the sums are a bwd-data extra
+  if (bn != nullptr && bn->dp_thresh != 0u && (c.transposed || bn->add_src == nullptr || bn->dp_rows < ROWS)) return FS_ERR_ARG;
+  PwArgs a = pw_args(c, M, c.Cs, Cd, (c.Cs + 31) / 32);
+  fs_fill_bwd_extras(a, bn);
+  if (bn != nullptr) { a.dp_scale = bn->dp_scale; a.dp_thresh = bn->dp_thresh; a.dp_key = bn->dp_key; a.dp_rows = bn->dp_rows; }
   // 128-column workgroups (two sub-tiles per wave, the A tile split once for twice the MFMAs) or 64-column ones: whichever needs less
   // time by rounds of 512 resident workgroups x cost of a workgroup per chunk (a refill ~ 1 000 cycles + 768 cycles of MFMAs per 64 columns).
   // N = 320 (the Mix-Transformer's stage-3 width) is the case that matters: 128-column tiles pad it to 384 and leave 600 workgroups =
   // 1.17 rounds, 64-column tiles give 1 000 workgroups of 0.7x the work each (1280 -> 320 forward: 129 TF against 163 for 320 -> 1280).
   int nw = 1;
-  if (nwp == 2) {
+  if (pw_nw(Cd) == 2) {
     const long wg2 = (long)a.nx * (a.Npad / 128), wg1 = (long)a.nx * ((Cd + 63) / 64);
     const long cost2 = ((wg2 + 511) / 512) * (1000 + 2 * 768), cost1 = ((wg1 + 511) / 512) * (1000 + 768);
     static const int force = FS_ENV_INT("FS_PW_NW", 0);      // kernel A/B builds only: 1 / 2 force the tiling
     nw = force == 1 ? 1 : (force == 2 ? 2 : ((wg2 >= 440 && cost2 <= cost1) ? 2 : 1));
   }
-  a.ny = nw == 2 ? a.Npad / 128 : (Cd + 63) / 64;
-  const long pack_bytes = fs_pointwise_pack_bytes(mode, Cs, Cd);
-  if (pack_bytes >= 2147483647L || (size_t)M * Cs * 4 >= 4294967000UL || (size_t)M * Cd * 4 >= 4294967000UL) return FS_ERR_ARG;
-  a.src_bytes = (unsigned)((size_t)M * Cs * 4);
-  a.dst_bytes = (unsigned)((size_t)M * Cd * 4);
-  a.ws_bytes = (unsigned)pack_bytes;
-  a.drop_scale = drop_scale; a.drop_thresh = drop_thresh; a.drop_key = drop_key;
-  a.ntap = 0; a.S = 1; a.Hx = a.Wx = a.Ho = a.Wo = 1; a.st = 1; a.pad = 0; a.Cin = Cs; a.rounds_per_tap = 1;
-  a.sc_on = 0; a.sc_st = 1; a.sc_dy = a.sc_dx = 0; a.sc_H = a.sc_W = 1;
-  return mode == 2 ? run_pointwise<PrecF16>(a, w, ws, w_amax, Cin, Cout, transposed, nw, stream)
-                   : run_pointwise<PrecX3>(a, w, ws, w_amax, Cin, Cout, transposed, nw, stream);
+  pw_columns(a, nw);
+  if (!fs_sizes32(fs_pointwise_pack_bytes(mode, c.Cs, Cd), (size_t)M * c.Cs, (size_t)M * Cd, a.src_bytes, a.dst_bytes, a.ws_bytes)) return FS_ERR_ARG;
+  return pw_run(mode, c, a, c.Cin(), nw);
 }
 
 // Forward of a convolution whose stride is at least its filter size (HRNet's C1 classification branch: 960 -> 512, 3x3, stride 4; the
@@ -600,32 +604,17 @@ bool fs_pointwise_gather_eligible(int Cin, int Cout, int R, int S, int stride, i
   return stride >= R && stride >= S && stride > 1 && dil == 1 && Cin % 64 == 0 && Cout % 4 == 0 && R * S <= 9;
 }
 
-int fs_pointwise_gather_conv(int mode, const float* x, const float* w, const float* bias, float* y, float* stats, void* ws, const unsigned* w_amax,
-                             int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, float drop_scale,
-                             uint32_t drop_thresh, uint32_t drop_key, hipStream_t stream) {
-  if (!fs_pointwise_gather_eligible(Cin, Cout, R, S, stride, 1)) return FS_ERR_ARG;
-  PwArgs a;
-  const int K = R * S * Cin;
-  a.src = x; a.ws = reinterpret_cast<const unsigned char*>(ws); a.bias = bias; a.dst = y; a.stats = stats;
-  a.bn_y = nullptr; a.bn_mask = nullptr; a.bn_mean = nullptr; a.bn_invstd = nullptr; a.add_src = nullptr; a.add_mask = nullptr;
-  a.dp_scale = 1.f; a.dp_thresh = 0u; a.dp_key = 0u; a.dp_rows = 0;
-  a.M = (long)B * Ho * Wo; a.Cs = K; a.Cd = Cout;
-  const int nwp = pw_nw(Cout);
-  a.Npad = ((Cout + 64 * nwp - 1) / (64 * nwp)) * 64 * nwp;
-  a.nchunk = K / 32;
-  a.nx = cdiv(a.M, ROWS);
-  const int nw = nwp;
-  a.ny = nw == 2 ? a.Npad / 128 : (Cout + 63) / 64;
-  const long pack_bytes = fs_pointwise_pack_bytes(mode, K, Cout);
-  if (pack_bytes >= 2147483647L || (size_t)B * H * W * Cin * 4 >= 4294967000UL || (size_t)a.M * Cout * 4 >= 4294967000UL) return FS_ERR_ARG;
-  a.src_bytes = (unsigned)((size_t)B * H * W * Cin * 4);
-  a.dst_bytes = (unsigned)((size_t)a.M * Cout * 4);
-  a.ws_bytes = (unsigned)pack_bytes;
-  a.drop_scale = drop_scale; a.drop_thresh = drop_thresh; a.drop_key = drop_key;
-  a.ntap = R * S; a.S = S; a.Hx = H; a.Wx = W; a.Ho = Ho; a.Wo = Wo; a.st = stride; a.pad = pad; a.Cin = Cin; a.rounds_per_tap = Cin / (32 * RC);
-  a.sc_on = 0; a.sc_st = 1; a.sc_dy = a.sc_dx = 0; a.sc_H = a.sc_W = 1;
-  return mode == 2 ? run_pointwise<PrecF16>(a, w, ws, w_amax, K, Cout, 0, nw, stream)
-                   : run_pointwise<PrecX3>(a, w, ws, w_amax, K, Cout, 0, nw, stream);
+int fs_pointwise_gather_conv(int mode, const FsConvProblem& c) {
+  const int Cin = c.Cs, Cout = c.Cd;
+  if (c.transposed || !fs_pointwise_gather_eligible(Cin, Cout, c.R, c.S, c.stride, 1)) return FS_ERR_ARG;
+  const int K = c.R * c.S * Cin;
+  PwArgs a = pw_args(c, (long)c.B * c.Hd * c.Wd, K, Cout, K / 32);
+  const int nw = pw_nw(Cout);
+  pw_columns(a, nw);
+  if (!fs_sizes32(fs_pointwise_pack_bytes(mode, K, Cout), c.src_elems(), c.dst_elems(), a.src_bytes, a.dst_bytes, a.ws_bytes)) return FS_ERR_ARG;
+  a.ntap = c.R * c.S; a.S = c.S; a.Hx = c.Hs; a.Wx = c.Ws; a.Ho = c.Hd; a.Wo = c.Wd; a.st = c.stride; a.pad = c.pad; a.Cin = Cin;
+  a.rounds_per_tap = Cin / (32 * RC);
+  return pw_run(mode, c, a, K, nw);
 }
 
 // bwd-data of the same layers: an input pixel receives at most ONE tap, so dX = nine (R*S) GEMMs  dY[rows][Cout] W_tap^T[Cout][Cin]  whose
@@ -634,38 +623,29 @@ bool fs_pointwise_scatter_eligible(int Cin, int Cout, int R, int S, int stride, 
   return stride >= R && stride >= S && stride > 1 && dil == 1 && Cout % 64 == 0 && Cin % 4 == 0 && Cin >= 32 && R * S <= 9;
 }
 
-int fs_pointwise_scatter_conv(int mode, const float* dy, const float* w, float* dx, void* ws, const unsigned* w_amax, int B, int H, int W,
-                              int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, hipStream_t stream) {
-  if (!fs_pointwise_scatter_eligible(Cin, Cout, R, S, stride, 1)) return FS_ERR_ARG;
-  const long pack_bytes = fs_pointwise_pack_bytes(mode, Cout, Cin);
-  if (pack_bytes >= 2147483647L || (size_t)B * H * W * Cin * 4 >= 4294967000UL || (size_t)B * Ho * Wo * Cout * 4 >= 4294967000UL) return FS_ERR_ARG;
-  for (int r = 0; r < R; ++r)
-    for (int s_ = 0; s_ < S; ++s_) {
+int fs_pointwise_scatter_conv(int mode, const FsConvProblem& c) {
+  const int H = c.Hd, W = c.Wd, Cin = c.Cd, Ho = c.Hs, Wo = c.Ws, Cout = c.Cs, stride = c.stride, pad = c.pad;
+  if (!c.transposed || !fs_pointwise_scatter_eligible(Cin, Cout, c.R, c.S, stride, 1)) return FS_ERR_ARG;
+  // the sub-problem of one tap: its 1x1 slice of the weights, no bias, stats or dropout; the tensors stay the parent's
+  FsConvProblem t = c;
+  t.R = t.S = 1; t.bias = nullptr; t.stats_ = nullptr; t.drop_scale = 1.f; t.drop_thresh = 0u; t.drop_key = 0u;
+  const int nwp = pw_nw(Cin);
+  unsigned src_bytes, dst_bytes, ws_bytes;
+  if (!fs_sizes32(fs_pointwise_pack_bytes(mode, Cout, Cin), c.src_elems(), c.dst_elems(), src_bytes, dst_bytes, ws_bytes)) return FS_ERR_ARG;
+  for (int r = 0; r < c.R; ++r)
+    for (int s_ = 0; s_ < c.S; ++s_) {
       // rows: every (oy, ox) whose pixel (oy * st + r - pad, ox * st + s - pad) can lie inside dX, also past the last real dY row / column
       const int dyo = r - pad, dxo = s_ - pad;
       const int He = dyo > H - 1 ? 0 : (H - 1 - dyo) / stride + 1, We = dxo > W - 1 ? 0 : (W - 1 - dxo) / stride + 1;
       if (He <= 0 || We <= 0) continue;
-      PwArgs a;
-      a.src = dy; a.ws = reinterpret_cast<const unsigned char*>(ws); a.bias = nullptr; a.dst = dx; a.stats = nullptr;
-      a.bn_y = nullptr; a.bn_mask = nullptr; a.bn_mean = nullptr; a.bn_invstd = nullptr; a.add_src = nullptr; a.add_mask = nullptr;
-      a.dp_scale = 1.f; a.dp_thresh = 0u; a.dp_key = 0u; a.dp_rows = 0;
-  a.dp_scale = 1.f; a.dp_thresh = 0u; a.dp_key = 0u; a.dp_rows = 0;
-      a.M = (long)B * He * We; a.Cs = Cout; a.Cd = Cin;
-      const int nwp = pw_nw(Cin);
-      a.Npad = ((Cin + 64 * nwp - 1) / (64 * nwp)) * 64 * nwp;
-      a.nchunk = Cout / 32;
-      a.nx = cdiv(a.M, ROWS);
-      a.ny = nwp == 2 ? a.Npad / 128 : (Cin + 63) / 64;
-      a.src_bytes = (unsigned)((size_t)B * Ho * Wo * Cout * 4);
-      a.dst_bytes = (unsigned)((size_t)B * H * W * Cin * 4);
-      a.ws_bytes = (unsigned)pack_bytes;
-      a.drop_scale = 1.f; a.drop_thresh = 0u; a.drop_key = 0u;
+      t.w = c.w + (long)(r * c.S + s_) * Cin * Cout;
+      PwArgs a = pw_args(t, (long)c.B * He * We, Cout, Cin, Cout / 32);
+      pw_columns(a, nwp);
+      a.src_bytes = src_bytes; a.dst_bytes = dst_bytes; a.ws_bytes = ws_bytes;
       // the A rows: the (Ho x Wo) dY image read on the extended (He x We) grid, "stride 1, pad 0, one tap"
-      a.ntap = 1; a.S = 1; a.Hx = Ho; a.Wx = Wo; a.Ho = He; a.Wo = We; a.st = 1; a.pad = 0; a.Cin = Cout; a.rounds_per_tap = Cout / (32 * RC);
+      a.ntap = 1; a.Hx = Ho; a.Wx = Wo; a.Ho = He; a.Wo = We; a.rounds_per_tap = Cout / (32 * RC);
       a.sc_on = 1; a.sc_st = stride; a.sc_dy = dyo; a.sc_dx = dxo; a.sc_H = H; a.sc_W = W;
-      const float* wt = w + (long)(r * S + s_) * Cin * Cout;
-      const int e = mode == 2 ? run_pointwise<PrecF16>(a, wt, ws, w_amax, Cin, Cout, 1, nwp, stream)
-                              : run_pointwise<PrecX3>(a, wt, ws, w_amax, Cin, Cout, 1, nwp, stream);
+      const int e = pw_run(mode, t, a, Cin, nwp);
       if (e != FS_OK) return e;
     }
   return FS_OK;

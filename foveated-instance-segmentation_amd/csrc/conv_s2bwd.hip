@@ -10,8 +10,7 @@
 // 32-channel chunk and runs all nine (parity, tap) products on it: 108 MFMAs per wave and refill in bf16x3, one pack kernel, one
 // launch of B * tiles * (Cin / 64) workgroups.  Weights come pre-split in consumption order (chunk, product, k16 step) as 16-byte
 // global loads straight into the B operand registers, as in the other halo-tiled kernels.
-#include "conv_split.h"
-#include "conv_kernels.h"
+#include "conv_run.h"
 
 namespace {
 
@@ -373,24 +372,6 @@ void s2bwd_patch(int Hq, int Wq, int* Ph, int* Pw) {
     }
 }
 
-template <class P>
-int run_s2bwd(S2Args& a, const float* w, void* ws, const unsigned* w_amax, int Cin, int Cout, hipStream_t stream) {
-  int e = FS_OK;
-  a.ew = P::SCALED ? fs_f16_weight_amax(w, 9L * Cin * Cout, ws, w_amax, stream, &e) : nullptr;
-  if (e != FS_OK) return e;
-  const long total = (long)a.nchunk * 18 * a.Npad;
-  if (fs_ws_mode_tls != FS_WS_RUN_ONLY) {
-    hipLaunchKernelGGL((conv_s2bwd_pack_kernel<P>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, reinterpret_cast<unsigned char*>(ws), a.ew,
-                       Cin, Cout, a.Npad, total);
-    FS_LAUNCH_CHECK();
-  }
-  if (fs_ws_mode_tls == FS_WS_PACK_ONLY) return FS_OK;
-  if (a.bn_y != nullptr || a.add_src != nullptr) hipLaunchKernelGGL((conv_s2bwd_kernel<P, true>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL((conv_s2bwd_kernel<P, false>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
 }  // namespace
 
 bool fs_s2bwd_eligible(int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil) {
@@ -411,14 +392,15 @@ int fs_s2bwd_stats_slabs(int B, int Ho, int Wo) {
   return B * cdiv(Ho, Ph) * cdiv(Wo, Pw);
 }
 
-int fs_s2bwd_conv(int mode, const float* dy, const float* w, float* dx, void* ws, const unsigned* w_amax, int B, int H, int W, int Cin, int Ho,
-                  int Wo, int Cout, const FsBnSums* bn, float* slab, hipStream_t stream) {
+int fs_s2bwd_conv(int mode, const FsConvProblem& c) {
+  const FsBnSums* bn = c.bn_;
+  const int B = c.B, Cin = c.Cd, Ho = c.Hs, Wo = c.Ws, Cout = c.Cs;
   S2Args a;
-  if (bn != nullptr && bn->y != nullptr && slab == nullptr) return FS_ERR_ARG;
-  a.bn_y = bn ? bn->y : nullptr; a.bn_mask = bn ? bn->mask : nullptr; a.bn_mean = bn ? bn->mean : nullptr; a.bn_invstd = bn ? bn->invstd : nullptr;
-  a.add_src = bn ? bn->add_src : nullptr; a.add_mask = bn ? bn->add_mask : nullptr; a.stats = (bn != nullptr && bn->y != nullptr) ? slab : nullptr;
-  a.src = dy; a.ws = reinterpret_cast<const unsigned char*>(ws); a.dst = dx;
-  a.B = B; a.Hs = Ho; a.Ws = Wo; a.Cs = Cout; a.Hd = H; a.Wd = W; a.Cd = Cin;
+  if (bn != nullptr && bn->y != nullptr && c.stats_ == nullptr) return FS_ERR_ARG;
+  fs_fill_bwd_extras(a, bn);
+  a.stats = (bn != nullptr && bn->y != nullptr) ? c.stats_ : nullptr;
+  a.src = c.src; a.ws = reinterpret_cast<const unsigned char*>(c.ws_); a.dst = c.dst;
+  a.B = B; a.Hs = Ho; a.Ws = Wo; a.Cs = Cout; a.Hd = c.Hd; a.Wd = c.Wd; a.Cd = Cin;
   a.Npad = ((Cin + 63) / 64) * 64;
   a.nchunk = (Cout + 31) / 32;
   s2bwd_patch(Ho, Wo, &a.Ph, &a.Pw);
@@ -426,10 +408,20 @@ int fs_s2bwd_conv(int mode, const float* dy, const float* w, float* dx, void* ws
   a.magic_pw = div_magic1(a.Pw); a.magic_wh = div_magic1(a.Pw + 1);
   a.nx = B * a.tiles_y * a.tiles_x;
   a.ny = a.Npad / 64;
-  const long pack_bytes = fs_s2bwd_pack_bytes(mode, Cin, Cout);
-  if (pack_bytes >= 2147483647L || (size_t)B * Ho * Wo * Cout * 4 >= 4294967000UL || (size_t)B * H * W * Cin * 4 >= 4294967000UL) return FS_ERR_ARG;
-  a.src_bytes = (unsigned)((size_t)B * Ho * Wo * Cout * 4);
-  a.dst_bytes = (unsigned)((size_t)B * H * W * Cin * 4);
-  a.wp_bytes = (unsigned)pack_bytes;
-  return mode == 2 ? run_s2bwd<PrecF16>(a, w, ws, w_amax, Cin, Cout, stream) : run_s2bwd<PrecX3>(a, w, ws, w_amax, Cin, Cout, stream);
+  if (!fs_sizes32(fs_s2bwd_pack_bytes(mode, Cin, Cout), c.src_elems(), c.dst_elems(), a.src_bytes, a.dst_bytes, a.wp_bytes)) return FS_ERR_ARG;
+  const long total = (long)a.nchunk * 18 * a.Npad;
+  return fs_pack_then_run(
+      mode, c,
+      [&](auto prec, const unsigned* ew) {
+        hipLaunchKernelGGL((conv_s2bwd_pack_kernel<decltype(prec)>), fs_pack_grid(total), dim3(256), 0, c.stream_, c.w,
+                           reinterpret_cast<unsigned char*>(c.ws_), ew, Cin, Cout, a.Npad, total);
+      },
+      [&](auto prec, const unsigned* ew) {
+        typedef decltype(prec) P;
+        a.ew = ew;
+        const dim3 grid((unsigned)(a.nx * a.ny));
+        if (a.bn_y != nullptr || a.add_src != nullptr) hipLaunchKernelGGL((conv_s2bwd_kernel<P, true>), grid, dim3(256), 0, c.stream_, a);
+        else hipLaunchKernelGGL((conv_s2bwd_kernel<P, false>), grid, dim3(256), 0, c.stream_, a);
+        return FS_OK;
+      });
 }

@@ -9,8 +9,7 @@
 // groups of the other halo kernels at a per-tap constant offset -- and all nine taps run on one refill: 108 * NW MFMAs per wave between
 // two barriers in bf16x3 (NW = 2: 128-column workgroups on layers with >= 128 output channels).  Same epilogue as the tap-class kernel
 // (bias, dropout hash, BatchNorm partial sums per workgroup).  Counterpart of conv_s2bwd.hip.
-#include "conv_split.h"
-#include "conv_kernels.h"
+#include "conv_run.h"
 
 namespace {
 
@@ -319,37 +318,6 @@ void s2fwd_patch(int Ho, int Wo, int* Ph, int* Pw) {
     }
 }
 
-template <class P>
-int run_s2fwd(F2Args& a, const float* w, void* ws, const unsigned* w_amax, int Cin, int Cout, int nw, hipStream_t stream) {
-  int e = FS_OK;
-  a.ew = P::SCALED ? fs_f16_weight_amax(w, 9L * Cin * Cout, ws, w_amax, stream, &e) : nullptr;
-  if (e != FS_OK) return e;
-  const long total = (long)a.nchunk * 18 * a.Npad;
-  if (fs_ws_mode_tls != FS_WS_RUN_ONLY) {
-    hipLaunchKernelGGL((conv_s2fwd_pack_kernel<P>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, reinterpret_cast<unsigned char*>(ws), a.ew,
-                       Cin, Cout, a.Npad, total);
-    FS_LAUNCH_CHECK();
-  }
-  if (fs_ws_mode_tls == FS_WS_PACK_ONLY) return FS_OK;
-  constexpr int lds = P::NPL * PLANE * 2;
-  {
-    static unsigned long long done[2] = {0ull, 0ull};        // the dynamic-LDS opt-in (above 64 KB) is a per-device function attribute
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return FS_ERR_ARG;
-    const int which = nw == 2 ? 1 : 0;
-    if (dev < 0 || dev >= 64 || !((done[which] >> dev) & 1ull)) {
-      const void* fn = nw == 2 ? reinterpret_cast<const void*>(&conv_s2fwd_kernel<P, 2>) : reinterpret_cast<const void*>(&conv_s2fwd_kernel<P, 1>);
-      const hipError_t attr = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (attr != hipSuccess) return (int)attr;
-      if (dev >= 0 && dev < 64) done[which] |= 1ull << dev;
-    }
-  }
-  if (nw == 2) hipLaunchKernelGGL((conv_s2fwd_kernel<P, 2>), dim3((unsigned)(a.nx * a.ny)), dim3(256), lds, stream, a);
-  else hipLaunchKernelGGL((conv_s2fwd_kernel<P, 1>), dim3((unsigned)(a.nx * a.ny)), dim3(256), lds, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
 }  // namespace
 
 bool fs_s2fwd_eligible(int H, int W, int Cin, int Ho, int Wo, int Cout, int R, int S, int stride, int pad, int dil) {
@@ -368,12 +336,11 @@ int fs_s2fwd_slabs(int B, int Ho, int Wo) {
   return B * cdiv(Ho, Ph) * cdiv(Wo, Pw);
 }
 
-int fs_s2fwd_conv(int mode, const float* x, const float* w, const float* bias, float* y, float* stats, void* ws, const unsigned* w_amax,
-                  int B, int H, int W, int Cin, int Ho, int Wo, int Cout, float drop_scale, uint32_t drop_thresh, uint32_t drop_key,
-                  hipStream_t stream) {
+int fs_s2fwd_conv(int mode, const FsConvProblem& c) {
+  const int B = c.B, Cin = c.Cs, Ho = c.Hd, Wo = c.Wd, Cout = c.Cd;
   F2Args a;
-  a.src = x; a.ws = reinterpret_cast<const unsigned char*>(ws); a.bias = bias; a.dst = y; a.stats = stats;
-  a.B = B; a.Hs = H; a.Ws = W; a.Cs = Cin; a.Hd = Ho; a.Wd = Wo; a.Cd = Cout;
+  a.src = c.src; a.ws = reinterpret_cast<const unsigned char*>(c.ws_); a.bias = c.bias; a.dst = c.dst; a.stats = c.stats_;
+  a.B = B; a.Hs = c.Hs; a.Ws = c.Ws; a.Cs = Cin; a.Hd = Ho; a.Wd = Wo; a.Cd = Cout;
   a.Npad = ((Cout + 127) / 128) * 128;
   a.nchunk = (Cin + 31) / 32;
   s2fwd_patch(Ho, Wo, &a.Ph, &a.Pw);
@@ -390,11 +357,25 @@ int fs_s2fwd_conv(int mode, const float* x, const float* w, const float* bias, f
   static const int nw_pol = FS_ENV_INT("FS_S2FWD_NW", 1);      // kernel A/B builds only: 0 never, 2 whenever Cout >= 128
   const int nw = (nw_pol != 0 && Cout >= 128 && (nw_pol == 2 || (long)a.nx * (a.Npad / 128) >= 440)) ? 2 : 1;
   a.ny = nw == 2 ? a.Npad / 128 : (Cout + 63) / 64;
-  const long pack_bytes = fs_s2fwd_pack_bytes(mode, Cin, Cout);
-  if (pack_bytes >= 2147483647L || (size_t)B * H * W * Cin * 4 >= 4294967000UL || (size_t)B * Ho * Wo * Cout * 4 >= 4294967000UL) return FS_ERR_ARG;
-  a.src_bytes = (unsigned)((size_t)B * H * W * Cin * 4);
-  a.dst_bytes = (unsigned)((size_t)B * Ho * Wo * Cout * 4);
-  a.wp_bytes = (unsigned)pack_bytes;
-  a.drop_scale = drop_scale; a.drop_thresh = drop_thresh; a.drop_key = drop_key;
-  return mode == 2 ? run_s2fwd<PrecF16>(a, w, ws, w_amax, Cin, Cout, nw, stream) : run_s2fwd<PrecX3>(a, w, ws, w_amax, Cin, Cout, nw, stream);
+  if (!fs_sizes32(fs_s2fwd_pack_bytes(mode, Cin, Cout), c.src_elems(), c.dst_elems(), a.src_bytes, a.dst_bytes, a.wp_bytes)) return FS_ERR_ARG;
+  a.drop_scale = c.drop_scale; a.drop_thresh = c.drop_thresh; a.drop_key = c.drop_key;
+  const long total = (long)a.nchunk * 18 * a.Npad;
+  return fs_pack_then_run(
+      mode, c,
+      [&](auto prec, const unsigned* ew) {
+        hipLaunchKernelGGL((conv_s2fwd_pack_kernel<decltype(prec)>), fs_pack_grid(total), dim3(256), 0, c.stream_, c.w,
+                           reinterpret_cast<unsigned char*>(c.ws_), ew, Cin, Cout, a.Npad, total);
+      },
+      [&](auto prec, const unsigned* ew) {
+        typedef decltype(prec) P;
+        a.ew = ew;
+        constexpr int lds = P::NPL * PLANE * 2;
+        static unsigned long long done[2] = {0ull, 0ull};
+        const void* fn = nw == 2 ? reinterpret_cast<const void*>(&conv_s2fwd_kernel<P, 2>) : reinterpret_cast<const void*>(&conv_s2fwd_kernel<P, 1>);
+        const int e = fs_lds_opt_in(fn, lds, done[nw == 2 ? 1 : 0]);
+        if (e != FS_OK) return e;
+        if (nw == 2) hipLaunchKernelGGL((conv_s2fwd_kernel<P, 2>), dim3((unsigned)(a.nx * a.ny)), dim3(256), lds, c.stream_, a);
+        else hipLaunchKernelGGL((conv_s2fwd_kernel<P, 1>), dim3((unsigned)(a.nx * a.ny)), dim3(256), lds, c.stream_, a);
+        return FS_OK;
+      });
 }

@@ -10,8 +10,7 @@
 // shifted slot offsets.  Weights come pre-split from conv_tapset_pack_kernel in consumption order (scaled by the tensor exponent in f16x2; the running
 // activation exponent of conv_halo.hip is updated at every LDS refill), as 16-byte
 // global loads straight into MFMA B fragments.  Same tiling as conv_halo.hip (128 x 64 tile, wave tile 64 x 32).
-#include "conv_split.h"
-#include "conv_kernels.h"
+#include "conv_run.h"
 
 namespace {
 
@@ -375,33 +374,9 @@ int fs_tapset_slabs(int B, int Hq, int Wq, int maxR, int maxS) {
   return B * cdiv(Hq, Ph) * cdiv(Wq, Pw);
 }
 
-namespace {
-template <class P>
-int run_tapset(TsArgs& a, const FsTapsetProblem& p, hipStream_t stream) {
-  int e = FS_OK;
-  a.ew = P::SCALED ? fs_f16_weight_amax(p.w, (long)p.R * p.S * p.Cin * p.Cout, p.ws, p.w_amax, stream, &e) : nullptr;
-  if (e != FS_OK) return e;
-  const long total = (long)a.ttot * 2 * a.Npad;
-  if (fs_ws_mode_tls != FS_WS_RUN_ONLY) {
-    hipLaunchKernelGGL((conv_tapset_pack_kernel<P>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, p.w,
-                       reinterpret_cast<unsigned char*>(p.ws), a.ew, p.Cin, p.Cout, p.S, p.transposed, p.Cs, p.Cd, a.Npad, a.nchunk, a.ncls,
-                       a.cls[0], a.cls[1], a.cls[2], a.cls[3], a.cls[4], a.cls[5], a.cls[6], a.cls[7], a.cls[8], total);
-    FS_LAUNCH_CHECK();
-  }
-  if (fs_ws_mode_tls == FS_WS_PACK_ONLY) return FS_OK;
-#ifdef FS_EXPERIMENTS          // the 128-column form is measured-and-rejected (below): only the A/B build carries it
-  if (a.nw == 2) hipLaunchKernelGGL((conv_tapset_kernel<P, 2>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-  else
-#endif
-  hipLaunchKernelGGL((conv_tapset_kernel<P, 1>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-}  // namespace
-
-int fs_tapset_conv(int mode, const FsTapsetProblem& p, hipStream_t stream) {
+int fs_tapset_conv(int mode, const FsTapsetProblem& p) {
   TsArgs a;
-  a.src = p.src; a.ws = reinterpret_cast<const unsigned char*>(p.ws); a.bias = p.bias; a.dst = p.dst; a.stats = p.stats;
+  a.src = p.src; a.ws = reinterpret_cast<const unsigned char*>(p.ws_); a.bias = p.bias; a.dst = p.dst; a.stats = p.stats_;
   a.B = p.B; a.Hs = p.Hs; a.Ws = p.Ws; a.Cs = p.Cs; a.Hd = p.Hd; a.Wd = p.Wd; a.Cd = p.Cd;
   a.Hq = p.Hq; a.Wq = p.Wq; a.os = p.os; a.oy0 = p.oy0; a.ox0 = p.ox0; a.sm = p.sm;
   a.ncls = p.ncls;
@@ -434,12 +409,25 @@ int fs_tapset_conv(int mode, const FsTapsetProblem& p, hipStream_t stream) {
   static const int nw_pol = FS_ENV_INT("FS_TAPSET_NW", 0);
   a.nw = (nw_pol != 0 && p.Cd >= 128 && (nw_pol == 2 || (long)a.nx * (a.Npad / 128) >= 440)) ? 2 : 1;
   a.ny = a.nw == 2 ? a.Npad / 128 : (p.Cd + 63) / 64;
-  const long pack_bytes = fs_tapset_pack_bytes(mode, p.Cs, p.Cd, total_taps);
-  if (pack_bytes >= 2147483647L || (size_t)p.B * p.Hs * p.Ws * p.Cs * 4 >= 4294967000UL || (size_t)p.B * p.Hd * p.Wd * p.Cd * 4 >= 4294967000UL)
+  if (!fs_sizes32(fs_tapset_pack_bytes(mode, p.Cs, p.Cd, total_taps), p.src_elems(), p.dst_elems(), a.src_bytes, a.dst_bytes, a.wp_bytes))
     return FS_ERR_ARG;
-  a.src_bytes = (unsigned)((size_t)p.B * p.Hs * p.Ws * p.Cs * 4);
-  a.dst_bytes = (unsigned)((size_t)p.B * p.Hd * p.Wd * p.Cd * 4);
-  a.wp_bytes = (unsigned)pack_bytes;
   a.drop_scale = p.drop_scale; a.drop_thresh = p.drop_thresh; a.drop_key = p.drop_key;
-  return mode == 2 ? run_tapset<PrecF16>(a, p, stream) : run_tapset<PrecX3>(a, p, stream);
+  const long total = (long)a.ttot * 2 * a.Npad;
+  return fs_pack_then_run(
+      mode, p,
+      [&](auto prec, const unsigned* ew) {
+        hipLaunchKernelGGL((conv_tapset_pack_kernel<decltype(prec)>), fs_pack_grid(total), dim3(256), 0, p.stream_, p.w,
+                           reinterpret_cast<unsigned char*>(p.ws_), ew, p.Cin(), p.Cout(), p.S, p.transposed, p.Cs, p.Cd, a.Npad, a.nchunk, a.ncls,
+                           a.cls[0], a.cls[1], a.cls[2], a.cls[3], a.cls[4], a.cls[5], a.cls[6], a.cls[7], a.cls[8], total);
+      },
+      [&](auto prec, const unsigned* ew) {
+        typedef decltype(prec) P;
+        a.ew = ew;
+#ifdef FS_EXPERIMENTS          // the 128-column form is measured-and-rejected (above): only the A/B build carries it
+        if (a.nw == 2) hipLaunchKernelGGL((conv_tapset_kernel<P, 2>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, p.stream_, a);
+        else
+#endif
+        hipLaunchKernelGGL((conv_tapset_kernel<P, 1>), dim3((unsigned)(a.nx * a.ny)), dim3(256), 0, p.stream_, a);
+        return FS_OK;
+      });
 }

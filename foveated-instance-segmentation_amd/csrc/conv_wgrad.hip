@@ -1389,16 +1389,9 @@ int fs_wgrad_launch(const FsWgradPlan& p, const float* x, const float* dy, float
       w.magic_pp = div_magic1(w.PP);
       w.patches_per_split = s.per_split;
       constexpr int lds = PrecX3::NPL * (XT_PLANE + DM_PLANE);
-      {
-        static unsigned long long done = 0ull;
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return FS_ERR_ARG;
-        if (dev < 0 || dev >= 64 || !((done >> dev) & 1ull)) {
-          const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_wgrad_wino_kernel<PrecX3>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-          if (attr != hipSuccess) return (int)attr;
-          if (dev >= 0 && dev < 64) done |= 1ull << dev;
-        }
-      }
+      static unsigned long long lds_done = 0ull;
+      const int e = fs_lds_opt_in(reinterpret_cast<const void*>(&conv_wgrad_wino_kernel<PrecX3>), lds, lds_done);
+      if (e != FS_OK) return e;
       hipLaunchKernelGGL((conv_wgrad_wino_kernel<PrecX3>), dim3((unsigned)(ntile * s.nsplit)), dim3(512), lds, stream, w);
       FS_LAUNCH_CHECK();
       return FS_OK;

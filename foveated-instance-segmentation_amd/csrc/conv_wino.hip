@@ -22,8 +22,7 @@
 //   Epilogue: every wave writes its two partial inverse-transform sums (even pixel / odd pixel) to LDS in accumulator order and the
 //   wave that owns a pixel parity reads them back as [pixel][4 channels] rows: 16-byte global stores (8 per wave instead of 64 dword
 //   stores; round 3), bias / dropout / BatchNorm partial sums on those rows.
-#include "conv_split.h"
-#include "conv_kernels.h"
+#include "conv_run.h"
 #include "conv_wino_diag.h"
 
 #include <cstdio>
@@ -962,53 +961,6 @@ bool wino_use8(int mode, int Cs, int Cd) {
   return pol == 2 || Cs >= 256;
 }
 
-template <class P>
-int run_wino(WinoArgs& a, const float* w, void* ws, const unsigned* w_amax, int Cin, int Cout, int transposed, hipStream_t stream) {
-  int e = FS_OK;
-  a.ew = P::SCALED ? fs_f16_weight_amax(w, (long)9 * Cin * Cout, ws, w_amax, stream, &e) : nullptr;
-  if (e != FS_OK) return e;
-  const long total = (long)a.nchunk * 12 * a.Npad;
-  if (fs_ws_mode_tls != FS_WS_RUN_ONLY) {
-    hipLaunchKernelGGL((wino_pack_kernel<P>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, reinterpret_cast<unsigned char*>(ws),
-                       a.ew, Cin, Cout, transposed, a.Cs, a.Cd, a.Npad, total);
-    FS_LAUNCH_CHECK();
-  }
-  if (fs_ws_mode_tls == FS_WS_PACK_ONLY) return FS_OK;
-  const long ntile = (long)a.nx * a.ny;
-  const int slots = wino_grid_slots();
-  // the dynamic-LDS opt-in (above the 64 KB default) is a per-device function attribute: set it once on every device used
-  constexpr int lds = wino_lds_bytes<P>();
-  constexpr int lds8 = 2 * P::NPL * PLANE * 2 + 2 * 64 * 4;
-  {
-    static unsigned long long done = 0ull;            // one mask per precision (template instance)
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return FS_ERR_ARG;
-    if (dev < 0 || dev >= 64 || !((done >> dev) & 1ull)) {
-      hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino_kernel<P>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (attr != hipSuccess) return (int)attr;
-      if constexpr (!P::SCALED) {
-        attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino8_kernel<P>), hipFuncAttributeMaxDynamicSharedMemorySize, lds8);
-        if (attr != hipSuccess) return (int)attr;
-      }
-      if (dev >= 0 && dev < 64) done |= 1ull << dev;
-    }
-  }
-  if constexpr (!P::SCALED) {
-    if (a.ny * 128 == a.Npad && wino_use8(1, a.Cs, a.Cd)) {       // planned for 128-column workgroups (fs_wino_conv3x3)
-      const unsigned grid8 = (unsigned)(ntile < slots / 2 ? ntile : slots / 2);
-      hipLaunchKernelGGL((conv3x3_wino8_kernel<P>), dim3(grid8), dim3(512), lds8, stream, a);
-      FS_LAUNCH_CHECK();
-      return FS_OK;
-    }
-  }
-  const unsigned grid = (unsigned)(ntile < slots ? ntile : slots);
-  WINO_DIAG_BEFORE_LAUNCH(a, grid, stream);
-  hipLaunchKernelGGL((conv3x3_wino_kernel<P>), dim3(grid), dim3(256), lds, stream, a);
-  FS_LAUNCH_CHECK();
-  WINO_DIAG_AFTER_LAUNCH(a, grid, ntile, stream);
-  return FS_OK;
-}
-
 }  // namespace
 
 // f16x2 spends half the MFMAs per product, so the doubled split work of the transform only pays from 4 channel chunks up
@@ -1048,16 +1000,13 @@ int fs_wino_stats_slabs(int mode, int B, int H, int W, int Cs, int Cd) {
   return wino_use8(mode, Cs, Cd) ? 2 * nx : nx;        // the eight-wave kernel writes one row per (pixel tile, pixel parity)
 }
 
-int fs_wino_conv3x3(int mode, const float* src, const float* w, const float* bias, float* dst, float* stats, void* ws, const unsigned* w_amax,
-                    int B, int H, int W, int Cs, int Cd, int Cin, int Cout, int transposed, float drop_scale, uint32_t drop_thresh,
-                    uint32_t drop_key, const FsBnSums* bn, hipStream_t stream) {
-  if (wino4_selected(mode, B, H, W, Cs, Cd))
-    return fs_wino4_conv3x3(mode, src, w, bias, dst, stats, ws, B, H, W, Cs, Cd, Cin, Cout, transposed, drop_scale, drop_thresh, drop_key, bn, stream);
+int fs_wino_conv3x3(int mode, const FsConvProblem& c) {
+  const int B = c.B, H = c.Hd, W = c.Wd, Cs = c.Cs, Cd = c.Cd;
+  if (wino4_selected(mode, B, H, W, Cs, Cd)) return fs_wino4_conv3x3(mode, c);
   WinoArgs a;
-  a.bn_y = bn ? bn->y : nullptr; a.bn_mask = bn ? bn->mask : nullptr; a.bn_mean = bn ? bn->mean : nullptr; a.bn_invstd = bn ? bn->invstd : nullptr;
-  a.add_src = bn ? bn->add_src : nullptr; a.add_mask = bn ? bn->add_mask : nullptr;
-  a.ep_scale = bn ? bn->ep_scale : nullptr; a.ep_shift = bn ? bn->ep_shift : nullptr; a.ep_res = bn ? bn->ep_res : nullptr; a.ep_act = bn ? bn->ep_act : 0;
-  a.src = src; a.ws = reinterpret_cast<const unsigned char*>(ws); a.bias = bias; a.dst = dst; a.stats = stats;
+  fs_fill_bwd_extras(a, c.bn_);
+  fs_fill_fwd_epilogue(a, c.bn_);
+  a.src = c.src; a.ws = reinterpret_cast<const unsigned char*>(c.ws_); a.bias = c.bias; a.dst = c.dst; a.stats = c.stats_;
   a.B = B; a.H = H; a.W = W; a.Cs = Cs; a.Cd = Cd;
   const int ncol = wino_use8(mode, Cs, Cd) ? 128 : 64;      // columns per workgroup
   a.Npad = ((Cd + ncol - 1) / ncol) * ncol;
@@ -1070,17 +1019,43 @@ int fs_wino_conv3x3(int mode, const float* src, const float* w, const float* bia
   a.magic_ny = div_magic1(a.ny);
   a.magic_tx = div_magic1(a.tiles_x);
   const long pack_bytes = HDR + (long)a.nchunk * 24 * (mode == 2 ? 2 : 3) * (((Cd + 127) / 128) * 128) * 16 * 2;
-  if (!fs_wino_eligible(mode, B, H, W, Cs, Cd) || pack_bytes >= 2147483647L || (size_t)B * H * W * Cs * 4 >= 4294967000UL ||
-      (size_t)B * H * W * Cd * 4 >= 4294967000UL || (long)a.nx * a.ny >= 65536)
+  if (!fs_wino_eligible(mode, B, H, W, Cs, Cd) || (long)a.nx * a.ny >= 65536 ||
+      !fs_sizes32(pack_bytes, c.src_elems(), c.dst_elems(), a.src_bytes, a.dst_bytes, a.ws_bytes))
     return FS_ERR_ARG;
-  a.src_bytes = (unsigned)((size_t)B * H * W * Cs * 4);
-  a.dst_bytes = (unsigned)((size_t)B * H * W * Cd * 4);
-  a.ws_bytes = (unsigned)pack_bytes;
-  a.drop_scale = drop_scale; a.drop_thresh = drop_thresh; a.drop_key = drop_key;
+  a.drop_scale = c.drop_scale; a.drop_thresh = c.drop_thresh; a.drop_key = c.drop_key;
   {
     static const int prio = FS_ENV_INT("FS_WINO_PRIO", 0);      // kernel A/B builds only
     a.prio = prio;
   }
-  return mode == 2 ? run_wino<PrecF16>(a, w, ws, w_amax, Cin, Cout, transposed, stream)
-                   : run_wino<PrecX3>(a, w, ws, w_amax, Cin, Cout, transposed, stream);
+  const long total = (long)a.nchunk * 12 * a.Npad;
+  return fs_pack_then_run(
+      mode, c,
+      [&](auto prec, const unsigned* ew) {
+        hipLaunchKernelGGL((wino_pack_kernel<decltype(prec)>), fs_pack_grid(total), dim3(256), 0, c.stream_, c.w, reinterpret_cast<unsigned char*>(c.ws_),
+                           ew, c.Cin(), c.Cout(), c.transposed, a.Cs, a.Cd, a.Npad, total);
+      },
+      [&](auto prec, const unsigned* ew) {
+        typedef decltype(prec) P;
+        a.ew = ew;
+        const long ntile = (long)a.nx * a.ny;
+        const int slots = wino_grid_slots();
+        if (P::SCALED || ncol == 64) {
+          constexpr int lds = wino_lds_bytes<P>();
+          static unsigned long long lds_done = 0ull;            // one mask per precision (an instance of this lambda each)
+          const int e = fs_lds_opt_in(reinterpret_cast<const void*>(&conv3x3_wino_kernel<P>), lds, lds_done);
+          if (e != FS_OK) return e;
+          const unsigned grid = (unsigned)(ntile < slots ? ntile : slots);
+          WINO_DIAG_BEFORE_LAUNCH(a, grid, c.stream_);
+          hipLaunchKernelGGL((conv3x3_wino_kernel<P>), dim3(grid), dim3(256), lds, c.stream_, a);
+          WINO_DIAG_AFTER_LAUNCH(a, grid, ntile, c.stream_);
+        } else if constexpr (!P::SCALED) {      // 128-column workgroups: the eight-wave kernel (bf16x3 only, wino_use8)
+          constexpr int lds8 = 2 * P::NPL * PLANE * 2 + 2 * 64 * 4;
+          static unsigned long long lds8_done = 0ull;
+          const int e = fs_lds_opt_in(reinterpret_cast<const void*>(&conv3x3_wino8_kernel<P>), lds8, lds8_done);
+          if (e != FS_OK) return e;
+          const unsigned grid8 = (unsigned)(ntile < slots / 2 ? ntile : slots / 2);
+          hipLaunchKernelGGL((conv3x3_wino8_kernel<P>), dim3(grid8), dim3(512), lds8, c.stream_, a);
+        }
+        return FS_OK;
+      });
 }

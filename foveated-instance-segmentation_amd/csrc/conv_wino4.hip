@@ -31,8 +31,7 @@
 //   exchange buffer; two workgroups per CU.  Batch tiling, persistent tile walk, pack order, epilogue (bias, dropout hash, BatchNorm
 //   partial sums, bwd-data extras, inference affine) as in conv_wino.hip: an output pixel is (quad, o = 0..3), the wave of triple t
 //   stores outputs 2t and 2t + 1 of its column half.
-#include "conv_split.h"
-#include "conv_kernels.h"
+#include "conv_run.h"
 
 namespace {
 
@@ -898,15 +897,13 @@ int fs_wino4_stats_slabs(int B, int H, int W, int Cs, int Cd) {
   return wino4_use8(Cs, Cd) ? 2 * nx : nx;        // the eight-wave kernel writes one row per (pixel tile, output pair)
 }
 
-int fs_wino4_conv3x3(int mode, const float* src, const float* w, const float* bias, float* dst, float* stats, void* ws, int B, int H, int W, int Cs,
-                     int Cd, int Cin, int Cout, int transposed, float drop_scale, uint32_t drop_thresh, uint32_t drop_key, const FsBnSums* bn,
-                     hipStream_t stream) {
+int fs_wino4_conv3x3(int mode, const FsConvProblem& c) {
   typedef PrecX3 P;
+  const int B = c.B, H = c.Hd, W = c.Wd, Cs = c.Cs, Cd = c.Cd;
   W4Args a;
-  a.bn_y = bn ? bn->y : nullptr; a.bn_mask = bn ? bn->mask : nullptr; a.bn_mean = bn ? bn->mean : nullptr; a.bn_invstd = bn ? bn->invstd : nullptr;
-  a.add_src = bn ? bn->add_src : nullptr; a.add_mask = bn ? bn->add_mask : nullptr;
-  a.ep_scale = bn ? bn->ep_scale : nullptr; a.ep_shift = bn ? bn->ep_shift : nullptr; a.ep_res = bn ? bn->ep_res : nullptr; a.ep_act = bn ? bn->ep_act : 0;
-  a.src = src; a.ws = reinterpret_cast<const unsigned char*>(ws); a.bias = bias; a.dst = dst; a.stats = stats;
+  fs_fill_bwd_extras(a, c.bn_);
+  fs_fill_fwd_epilogue(a, c.bn_);
+  a.src = c.src; a.ws = reinterpret_cast<const unsigned char*>(c.ws_); a.bias = c.bias; a.dst = c.dst; a.stats = c.stats_;
   a.B = B; a.H = H; a.W = W; a.Cs = Cs; a.Cd = Cd;
   const bool eight = wino4_use8(Cs, Cd);
   const int ncol = eight ? 128 : 64;              // columns per workgroup
@@ -919,48 +916,39 @@ int fs_wino4_conv3x3(int mode, const float* src, const float* w, const float* bi
   a.magic_pq = div_magic(a.PQ);
   a.magic_ny = div_magic1(a.ny);
   a.magic_tx = div_magic1(a.tiles_x);
-  const long pack_bytes = fs_wino4_pack_bytes(mode, Cs, Cd);
-  if (!fs_wino4_eligible(mode, B, H, W, Cs, Cd) || pack_bytes >= 2147483647L || (size_t)B * H * W * Cs * 4 >= 4294967000UL ||
-      (size_t)B * H * W * Cd * 4 >= 4294967000UL || (long)a.nx * a.ny >= 65536 || (long)a.nchunk * NSTEP + 8 >= 16384)
+  // the step-count limit is this kernel's own: a refusal, like the others (fs_wino_conv3x3 does not fall back to F(2,3))
+  if (!fs_wino4_eligible(mode, B, H, W, Cs, Cd) || (long)a.nx * a.ny >= 65536 || (long)a.nchunk * NSTEP + 8 >= 16384 ||
+      !fs_sizes32(fs_wino4_pack_bytes(mode, Cs, Cd), c.src_elems(), c.dst_elems(), a.src_bytes, a.dst_bytes, a.ws_bytes))
     return FS_ERR_ARG;
-  a.src_bytes = (unsigned)((size_t)B * H * W * Cs * 4);
-  a.dst_bytes = (unsigned)((size_t)B * H * W * Cd * 4);
-  a.ws_bytes = (unsigned)pack_bytes;
-  a.drop_scale = drop_scale; a.drop_thresh = drop_thresh; a.drop_key = drop_key;
+  a.drop_scale = c.drop_scale; a.drop_thresh = c.drop_thresh; a.drop_key = c.drop_key;
   const long total = (long)a.nchunk * 12 * a.Npad;
-  if (fs_ws_mode_tls != FS_WS_RUN_ONLY) {
-    hipLaunchKernelGGL((wino4_pack_kernel<P>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, w, reinterpret_cast<unsigned char*>(ws),
-                       Cin, Cout, transposed, a.Cs, a.Cd, a.Npad, total);
-    FS_LAUNCH_CHECK();
-  }
-  if (fs_ws_mode_tls == FS_WS_PACK_ONLY) return FS_OK;
-  // weight-fragment ring: three slots, fragments two steps ahead (a six-slot ring measured +-1 % on the short-K layers and -11 % on
-  // 960 -> 240 with the 60 registers it costs, profiles/r05/wino4_ab.txt)
-  constexpr int RD = 3;
-  constexpr int lds = wino4_lds_bytes<P>();
-  constexpr int lds8 = 2 * XCH_BYTES + 2 * NQ * 4;
-  {
-    static unsigned long long done = 0ull;            // the dynamic-LDS opt-in is a per-device function attribute
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return FS_ERR_ARG;
-    if (dev < 0 || dev >= 64 || !((done >> dev) & 1ull)) {
-      hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino4_kernel<P, RD>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-      if (attr != hipSuccess) return (int)attr;
-      attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_wino48_kernel<P>), hipFuncAttributeMaxDynamicSharedMemorySize, lds8);
-      if (attr != hipSuccess) return (int)attr;
-      if (dev >= 0 && dev < 64) done |= 1ull << dev;
-    }
-  }
-  const long ntile = (long)a.nx * a.ny;
-  const int slots = wino4_grid_slots();
-  if (eight) {
-    const unsigned grid8 = (unsigned)(ntile < slots / 2 ? ntile : slots / 2);
-    hipLaunchKernelGGL((conv3x3_wino48_kernel<P>), dim3(grid8), dim3(512), lds8, stream, a);
-    FS_LAUNCH_CHECK();
-    return FS_OK;
-  }
-  const unsigned grid = (unsigned)(ntile < slots ? ntile : slots);
-  hipLaunchKernelGGL((conv3x3_wino4_kernel<P, RD>), dim3(grid), dim3(256), lds, stream, a);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
+  return fs_pack_then_run_as<P>(      // bf16x3 only (fs_wino4_eligible)
+      c,
+      [&](P, const unsigned*) {
+        hipLaunchKernelGGL((wino4_pack_kernel<P>), fs_pack_grid(total), dim3(256), 0, c.stream_, c.w, reinterpret_cast<unsigned char*>(c.ws_),
+                           c.Cin(), c.Cout(), c.transposed, a.Cs, a.Cd, a.Npad, total);
+      },
+      [&](P, const unsigned*) {
+        const long ntile = (long)a.nx * a.ny;
+        const int slots = wino4_grid_slots();
+        if (!eight) {
+          // weight-fragment ring: three slots, fragments two steps ahead (a six-slot ring measured +-1 % on the short-K layers and -11 % on
+          // 960 -> 240 with the 60 registers it costs, profiles/r05/wino4_ab.txt)
+          constexpr int RD = 3;
+          constexpr int lds = wino4_lds_bytes<P>();
+          static unsigned long long lds_done = 0ull;
+          const int e = fs_lds_opt_in(reinterpret_cast<const void*>(&conv3x3_wino4_kernel<P, RD>), lds, lds_done);
+          if (e != FS_OK) return e;
+          const unsigned grid = (unsigned)(ntile < slots ? ntile : slots);
+          hipLaunchKernelGGL((conv3x3_wino4_kernel<P, RD>), dim3(grid), dim3(256), lds, c.stream_, a);
+        } else {
+          constexpr int lds8 = 2 * XCH_BYTES + 2 * NQ * 4;
+          static unsigned long long lds8_done = 0ull;
+          const int e = fs_lds_opt_in(reinterpret_cast<const void*>(&conv3x3_wino48_kernel<P>), lds8, lds8_done);
+          if (e != FS_OK) return e;
+          const unsigned grid8 = (unsigned)(ntile < slots / 2 ? ntile : slots / 2);
+          hipLaunchKernelGGL((conv3x3_wino48_kernel<P>), dim3(grid8), dim3(512), lds8, c.stream_, a);
+        }
+        return FS_OK;
+      });
 }

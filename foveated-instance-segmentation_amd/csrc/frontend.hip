@@ -1556,22 +1556,11 @@ int fs_edge_loss_bwd(const float* xs, const float* t, long n, float coef, const 
   return FS_OK;
 }
 
-static int gg_set_lds(const void* fn, int bytes, unsigned long long& done) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return FS_ERR_ARG;
-  if (dev < 0 || dev >= 64 || !((done >> dev) & 1ull)) {        // the dynamic-LDS opt-in is a per-device function attribute
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (e != hipSuccess) return (int)e;
-    if (dev >= 0 && dev < 64) done |= 1ull << dev;
-  }
-  return FS_OK;
-}
-
 extern "C++" {
 template <int MODE>
 static int gauss_grid_fwd_launch(const float* xs, const double* g1d, float* grid, int B, int hs, int ws, int pad, hipStream_t stream) {
   static unsigned long long done = 0ull;
-  const int r = gg_set_lds((const void*)gauss_grid_fwd_kernel<MODE>, 3 * GMAX * (int)sizeof(float), done);
+  const int r = fs_lds_opt_in((const void*)gauss_grid_fwd_kernel<MODE>, 3 * GMAX * (int)sizeof(float), done);
   if (r != FS_OK) return r;
   hipLaunchKernelGGL(gauss_grid_fwd_kernel<MODE>, dim3(B * GG_BANDS), dim3(1024), 3 * GMAX * sizeof(float), stream, xs, g1d, grid, hs, ws, pad);
   FS_LAUNCH_CHECK();
@@ -1601,9 +1590,9 @@ template <int MODE>
 static int gauss_grid_bwd_launch(const float* xs, const double* g1d, const float* dgrid, float* dxs, int B, int hs, int ws, int pad,
                                  float* scratch, hipStream_t stream) {
   static unsigned long long done1 = 0ull, done2 = 0ull;
-  int r = gg_set_lds((const void*)gauss_grid_bwd1_kernel<MODE>, 3 * GMAX * (int)sizeof(float), done1);
+  int r = fs_lds_opt_in((const void*)gauss_grid_bwd1_kernel<MODE>, 3 * GMAX * (int)sizeof(float), done1);
   if (r != FS_OK) return r;
-  r = gg_set_lds((const void*)gauss_grid_bwd2_kernel<MODE>, 5 * GMAX * (int)sizeof(float), done2);
+  r = fs_lds_opt_in((const void*)gauss_grid_bwd2_kernel<MODE>, 5 * GMAX * (int)sizeof(float), done2);
   if (r != FS_OK) return r;
   hipLaunchKernelGGL(gauss_grid_bwd1_kernel<MODE>, dim3(B * GG_BANDS), dim3(1024), 3 * GMAX * sizeof(float), stream, xs, g1d, dgrid, scratch, hs, ws, pad);
   FS_LAUNCH_CHECK();

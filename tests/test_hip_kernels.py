@@ -3,7 +3,9 @@ the committed golden fixtures.  Run on the MI355X box:  python -m pytest tests -
 Tolerances: bit-exact for integer/index work and grid_sample forward; fp32 otherwise, stated per test.
 """
 import copy
+import json
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -309,15 +311,11 @@ def test_bwd_weight_cases_reach_every_route():
 
 
 # Weight packs that outlive the call (include/fovealseg.h: fs_conv2d_pack / fs_conv2d_ws_mode; ops._pack_for, ops.repack_weights).
-PACK_CASES = [
-    (4, 16, 16, 64, 64, 3, 1),       # F(2,3) kernel (even width)
-    (2, 15, 15, 64, 64, 3, 1),       # halo-tiled kernel (odd width)
-    (2, 20, 20, 256, 256, 3, 1),     # eight-wave F(2,3) form in bf16x3
-    (4, 16, 16, 64, 128, 3, 2),      # stride 2: parity-plane forward, four-parity bwd-data
-    (4, 16, 16, 64, 256, 1, 1),      # 1x1 GEMM kernel
-    (2, 16, 16, 32, 64, 5, 1),       # tap-class kernel (5x5)
-    (2, 16, 16, 64, 64, 3, 3),       # stride 3: bwd-data re-packs per parity class -> no persistent pack
-]
+# The cases, and the fs_conv2d_kernel_choice id each is there for per precision mode and direction, live beside the recorder of the pack
+# hashes (tools/record_conv_pack_hashes.py), which walks the same list.
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+import record_conv_pack_hashes as pack_rec  # noqa: E402
+from record_conv_pack_hashes import PACK_CASES, PACK_CHOICE  # noqa: E402
 
 
 @pytest.mark.parametrize("case", PACK_CASES)
@@ -356,6 +354,7 @@ def test_persistent_weight_pack(case, prec):
         ref = run(w, torch.empty(n, device=DEV, dtype=torch.uint8), False)
         persistent = int(lib.fs_conv2d_pack_persistent(*shape, transposed, n))
         choice = int(lib.fs_conv2d_kernel_choice(*shape, transposed, n))
+        assert choice == PACK_CHOICE[case][prec][transposed], (choice, transposed)      # the route this case is there for
         if not persistent:
             assert choice in (0, 1, 3), choice
             with pytest.raises(H_.HipLibraryError):
@@ -374,6 +373,21 @@ def test_persistent_weight_pack(case, prec):
         fresh = run(w2, ws, False)                               # the default mode re-packs
         assert relerr(fresh, 1.5 * ref) <= 1e-5
         assert int(lib.fs_conv2d_ws_mode(0)) == 0
+
+
+def test_weight_pack_bytes_match_recorded_hashes():
+    """The bytes fs_conv2d_pack writes: for every PACK_CASES entry x {bf16x3, f16x2} x direction with a persistent pack, the SHA-256 of
+    the scratch (pre-filled with 0xA5, weights from a seeded CPU generator) equals tests/golden/conv_pack_hashes.json, recorded by
+    tools/record_conv_pack_hashes.py from the library as it stood before the pack-then-run protocol moved into one driver."""
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_pack_hashes.json")) as f:
+        want = json.load(f)
+    # not hollow: both modes and directions, and every family with a persistent pack (ids 2-8), have a recorded pack
+    ids = {PACK_CHOICE[c][p][t] for c in PACK_CASES for p in pack_rec.PRECISIONS for t in (0, 1) if pack_rec.case_key(c, p, t) in want}
+    assert ids == {2, 3, 4, 5, 6, 7, 8}, ids
+    got = pack_rec.pack_hashes(fovealseg.hip)
+    assert got.keys() == want.keys(), sorted(got.keys() ^ want.keys())
+    bad = sorted(k for k in want if got[k] != want[k])
+    assert not bad, bad
 
 
 def test_weight_packs_follow_every_arena_rewrite():
