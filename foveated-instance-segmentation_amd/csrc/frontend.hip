@@ -1078,18 +1078,55 @@ __device__ __forceinline__ void trim_pixel(unsigned int* __restrict__ tbw, unsig
   const unsigned int eq = (long long)a == g, bin = (a == bg) == (g == bg);
   atomicAdd(tbw + bi, 1u | eq << 10 | bin << 20);
 }
-template <bool VEC, bool TRIM>
+// AREA (fs_unwarp_class_areas): the per-class areas of utils.intersectionAndUnion (utils.py:289-317) for two class maps against the
+// ground truth g of count_pixel -- the predicted class a = dec[q] of the feeding point q, and the CEILING class a' = gs[q], gs[p] =
+// ts[p]*cl + (1 - ts[p])*(K-1) with ts[p] grid_sample_label_kernel's value of point p bit for bit (the training label of that point;
+// background for the point h*w of an image without any claim).  This is the reference's VAL.y_sampled_reverse, "intrinsic upsampling
+// error IoU(Y', Y)" (models/models_instance.py:909-918, eval.py:220-244): the label after the sampler and the nearest un-warp, scored
+// against itself.  The ceiling is the label of the feeding point ITSELF, not the reference's F.grid_sample(mode='nearest') at the
+// inverse coordinate: that coordinate is xi - 0.5 up to fp32 rounding, so the reference's value is a round-half-to-even tie decided
+// by rounding noise between the point and its left / upper neighbour.
+// ts rides in bit DEC_TS_BIT of dec, set by class_area_sampled_kernel after unwarp_decide_kernel and masked in the AREA instantiations
+// only; the others never see it (their launcher does not run that kernel) and stay the instruction streams they were.
+// g and a' are cl or K-1, and almost every a is: those two HOT classes are counted in registers -- eight predicates in three words of
+// 10-bit fields, a thread adding at most four pixels and a wave 256 -- reduced by shuffles and LDS into one AREA_REC-int record per
+// workgroup (arec, two 16-byte stores).  A predicted class other than the two goes to a per-workgroup LDS histogram of K bins (zeroed
+// at entry), whose non-zero bins are added with 32-bit integer global atomics into atab (B, K), zeroed by the launcher: atab holds
+// SUMS, not records.  A workgroup without such a pixel (the usual case) skips the flush.  Integer sums: the same bits in any order.
+constexpr int DEC_TS_BIT = 30;
+constexpr int DEC_CLASS_MASK = (1 << DEC_TS_BIT) - 1;
+constexpr int AREA_REC = 8;                            // t, a==cl & t, a==bg & !t | a==cl (not bg), a==bg, ts | ts & t, !ts & !t
+struct AreaWords { unsigned int w[3]; unsigned int cold; };
+// d = dec word of the feeding point (class | ts << DEC_TS_BIT); returns the class
+__device__ __forceinline__ int area_pixel(AreaWords& r, int* __restrict__ hist, int d, float yv, long long cl, int bg) {
+  const int a = d & DEC_CLASS_MASK;
+  const unsigned int ts = (unsigned int)d >> DEC_TS_BIT;
+  const unsigned int t = (long long)yv != 0;
+  const unsigned int acl = (long long)a == cl, abg = a == bg;
+  r.w[0] += t | (acl & t) << 10 | (abg & (t ^ 1u)) << 20;
+  r.w[1] += (acl & (abg ^ 1u)) | abg << 10 | ts << 20;
+  r.w[2] += (ts & t) | ((ts | t) ^ 1u) << 10;
+  if (!(acl | abg)) { atomicAdd(hist + a, 1); r.cold = 1u; }
+  return a;
+}
+template <bool VEC, bool TRIM, bool AREA>
 __global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
                                                            const float* __restrict__ yl, const long long* __restrict__ cls_label,
                                                            long long* __restrict__ labels, int* __restrict__ rec, int Hs, int Ws, int hw,
                                                            int K, int blocks_per_image, const unsigned char* __restrict__ band,
-                                                           int* __restrict__ trec) {
+                                                           int* __restrict__ trec, int* __restrict__ arec, int* __restrict__ atab) {
   __shared__ int part[4][6];
   __shared__ unsigned int tb[4][TRIM_BUCKETS];         // TRIM: one bucket row per wave
+  __shared__ int hist[AREA ? UNWARP_MAX_K : 1];        // AREA: predicted classes other than cl and K-1
+  __shared__ int apart[4][AREA_REC];
+  if (AREA) {
+    for (int k = threadIdx.x; k < K; k += 256) hist[k] = 0;
+  }
   if (TRIM) {
     if (threadIdx.x < 4 * TRIM_BUCKETS) tb[threadIdx.x / TRIM_BUCKETS][threadIdx.x % TRIM_BUCKETS] = 0u;
-    __syncthreads();
   }
+  if (TRIM || AREA) __syncthreads();
+  AreaWords aw = {{0u, 0u, 0u}, 0u};
   unsigned int* tbw = tb[threadIdx.x >> 6];
   const int b = blockIdx.x / blocks_per_image, chunk = blockIdx.x - b * blocks_per_image;
   const int per = Hs * Ws;
@@ -1119,7 +1156,11 @@ __global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict
         for (int k = 0; k < 4; ++k)
           if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
       }
-      const int a0 = db[q[0]], a1 = db[q[1]], a2 = db[q[2]], a3 = db[q[3]];
+      int a0 = db[q[0]], a1 = db[q[1]], a2 = db[q[2]], a3 = db[q[3]];
+      if (AREA) {
+        a0 = area_pixel(aw, hist, a0, y4.x, cl, bg); a1 = area_pixel(aw, hist, a1, y4.y, cl, bg);
+        a2 = area_pixel(aw, hist, a2, y4.z, cl, bg); a3 = area_pixel(aw, hist, a3, y4.w, cl, bg);
+      }
       count_pixel(n, a0, y4.x, cl, bg); count_pixel(n, a1, y4.y, cl, bg);
       count_pixel(n, a2, y4.z, cl, bg); count_pixel(n, a3, y4.w, cl, bg);
       if (TRIM) {
@@ -1138,7 +1179,8 @@ __global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict
       const int p = p0 + j * 256 + (int)threadIdx.x;
       if (p >= per) break;
       const int y = p / Ws, x = p - y * Ws;
-      const int a = unwarp_class_at(ob, rx, db, ob[p], y, x, Hs, Ws, hw);
+      int a = unwarp_class_at(ob, rx, db, ob[p], y, x, Hs, Ws, hw);
+      if (AREA) a = area_pixel(aw, hist, a, yb[p], cl, bg);
       count_pixel(n, a, yb[p], cl, bg);
       if (TRIM) trim_pixel(tbw, band[base + p], a, yb[p], cl, bg);
       if (labels != nullptr) labels[base + p] = (long long)a;
@@ -1169,6 +1211,117 @@ __global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict
 #pragma unroll
     for (int wv = 0; wv < 4; ++wv) t += (int)((tb[wv][bi] >> sh) & 1023u);
     trec[(long)blockIdx.x * TRIM_REC + threadIdx.x] = t;
+  }
+  if (AREA) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) aw.w[q] += __shfl_xor(aw.w[q], o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+      int* ap = apart[threadIdx.x >> 6];
+#pragma unroll
+      for (int f = 0; f < AREA_REC; ++f) ap[f] = (int)((aw.w[f / 3] >> (10 * (f % 3))) & 1023u);
+    }
+    // the barrier also ends the histogram's adds; no workgroup leaves before it (the trips above end by break, not return)
+    const int cold = __syncthreads_or((int)aw.cold);
+    if (threadIdx.x == 0) {
+      int s[AREA_REC];
+#pragma unroll
+      for (int f = 0; f < AREA_REC; ++f) s[f] = (apart[0][f] + apart[1][f]) + (apart[2][f] + apart[3][f]);
+      int4* r = reinterpret_cast<int4*>(arec + (long)blockIdx.x * AREA_REC);
+      r[0] = make_int4(s[0], s[1], s[2], s[3]);
+      r[1] = make_int4(s[4], s[5], s[6], s[7]);
+    }
+    if (cold) {
+      for (int k = threadIdx.x; k < K; k += 256) {
+        const int v = hist[k];
+        if (v != 0) atomicAdd(atab + (long)b * K + k, v);
+      }
+    }
+  }
+}
+// Class areas in the sampled space (eval.py:197, pred_deformed against y_sampled), and the ceiling bit of dec.  One workgroup per
+// image.  At grid point p < h*w the prediction is pred[b,k,p] = cls[b,k] for k < K-1 and fmul(cls[b,K-1], m[b,p]) for K-1 -- one
+// rounded multiply, as pred_assemble_fwd_kernel's -- and its class the first maximal k, NaN counting as maximal (torch.max).  The
+// planes below K-1 are constant, so their first maximum kb is one per image and a point's class is kb or K-1; its label gs[p] is cl
+// or K-1.  Only those classes can occur: four block-wide counts make every row of areas[b,2], and no histogram is needed.  ts[p] =
+// (long)bilinear(y, grid[p]) is grid_sample_label_kernel's sequence (make_taps + sample_plane); it is or-ed into bit DEC_TS_BIT of
+// dec[b,p] for the AREA count pass.  dec[b,h*w] keeps a clear bit: background.
+__global__ __launch_bounds__(256) void class_area_sampled_kernel(const float* __restrict__ cls, const float* __restrict__ m,
+                                                                 const float* __restrict__ grid, const float* __restrict__ yl,
+                                                                 const long long* __restrict__ cls_label, int* __restrict__ dec,
+                                                                 long long* __restrict__ areas, int K, int hw, int Hs, int Ws) {
+  __shared__ float cs[UNWARP_MAX_K];
+  __shared__ int kbest;
+  __shared__ long long red[16];
+  const int b = blockIdx.x;
+  for (int k = threadIdx.x; k < K; k += 256) cs[k] = cls[(long)b * K + k];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float best = 0.f;
+    int arg = 0;
+    for (int k = 0; k < K - 1; ++k) {
+      const float v = cs[k];
+      if (k == 0 || v > best || (v != v && best == best)) { best = v; arg = k; }
+    }
+    kbest = arg;
+  }
+  __syncthreads();
+  const int kb = kbest, bg = K - 1;
+  const float best = cs[kb], c = cs[bg];
+  const long long cl = cls_label[b];
+  const float* mp = m + (long)b * hw;
+  const float* gp = grid + 2 * (long)b * hw;
+  const float* yb = yl + (long)b * Hs * Ws;
+  int* db = dec + (long)b * (hw + 1);
+  long long n[4] = {0, 0, 0, 0};                       // class K-1, ts, class == cl & ts, class == K-1 & !ts
+  for (int p = threadIdx.x; p < hw; p += 256) {
+    const Taps t = make_taps(gp[2 * p], gp[2 * p + 1], Hs, Ws);
+    const int ts = (long long)sample_plane(yb, Ws, t) != 0;
+    db[p] |= ts << DEC_TS_BIT;
+    const float v = __fmul_rn(c, mp[p]);
+    const int a = (v > best || (v != v && best == best)) ? bg : kb;
+    n[0] += a == bg; n[1] += ts; n[2] += ((long long)a == cl) & ts; n[3] += (a == bg) & (ts ^ 1);
+  }
+  for (int q = 0; q < 4; ++q) n[q] = block_sum<long long>(n[q], red);
+  long long* out = areas + ((long)b * 3 + 2) * K * 3;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const bool iscl = (long long)k == cl, isbg = k == bg;
+    out[3 * k + 0] = (iscl ? n[2] : 0) + (isbg ? n[3] : 0);
+    out[3 * k + 1] = (k == kb ? (long long)hw - n[0] : 0) + (isbg ? n[0] : 0);
+    out[3 * k + 2] = (iscl ? n[1] : 0) + (isbg ? (long long)hw - n[1] : 0);
+  }
+}
+// areas[b, 0] (prediction) and areas[b, 1] (ceiling) at full resolution = image b's hot records summed, the rows of the two hot
+// classes made from them by equality (cl == K-1 merges into one row, cl outside 0 .. K-1 has none), plus atab's other predicted
+// classes; one workgroup per image.  Record fields: AREA_REC.
+__global__ __launch_bounds__(256) void unwarp_area_finalize_kernel(const int* __restrict__ arec, const int* __restrict__ atab,
+                                                                   const long long* __restrict__ cls_label, long long* __restrict__ areas,
+                                                                   int K, int blocks_per_image, long long per) {
+  __shared__ long long red[16];
+  const int b = blockIdx.x;
+  const int4* r = reinterpret_cast<const int4*>(arec + (long)b * blocks_per_image * AREA_REC);
+  long long c[AREA_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int j = threadIdx.x; j < blocks_per_image; j += 256) {
+    const int4 lo = r[2 * j], hi = r[2 * j + 1];
+    c[0] += lo.x; c[1] += lo.y; c[2] += lo.z; c[3] += lo.w; c[4] += hi.x; c[5] += hi.y; c[6] += hi.z; c[7] += hi.w;
+  }
+  for (int q = 0; q < AREA_REC; ++q) c[q] = block_sum<long long>(c[q], red);
+  const long long cl = cls_label[b];
+  const int bg = K - 1;
+  long long* o0 = areas + (long)b * 3 * K * 3;
+  long long* o1 = o0 + (long)K * 3;
+  for (int k = threadIdx.x; k < K; k += 256) {
+    const bool iscl = (long long)k == cl, isbg = k == bg;
+    const long long lab = (iscl ? c[0] : 0) + (isbg ? per - c[0] : 0);
+    o0[3 * k + 0] = (iscl ? c[1] : 0) + (isbg ? c[2] : 0);
+    o0[3 * k + 1] = (long long)atab[(long)b * K + k] + ((iscl && !isbg) ? c[3] : 0) + (isbg ? c[4] : 0);
+    o0[3 * k + 2] = lab;
+    // the ceiling predicts cl where ts, K-1 elsewhere: with cl == K-1 every pixel is predicted, labelled and right in that one row
+    o1[3 * k + 0] = (iscl && isbg) ? per : (iscl ? c[6] : 0) + (isbg ? c[7] : 0);
+    o1[3 * k + 1] = (iscl ? c[5] : 0) + (isbg ? per - c[5] : 0);
+    o1[3 * k + 2] = lab;
   }
 }
 // trim[b, i, 0..3) = (total, cls_ok, bin_ok) of band i = the buckets 0 .. i of image b's records summed; one workgroup per image
@@ -1732,10 +1885,34 @@ long fs_unwarp_accuracy_scratch_ints(int B, int h, int w, int Hs, int Ws) {
   return unwarp_accuracy_rec_offset(B, h, w, Hs, Ws) + (long)B * bpi * UACC_REC;
 }
 
-// fs_unwarp_accuracy's launches; with band / trec / trim (all or none) the count pass is the bucketing one and trim is summed after it
+// fs_unwarp_accuracy's launches; with band / trec / trim (all or none) the count pass is the bucketing one and trim is summed after it;
+// with areas / arec / atab (all or none) it is the AREA one: class_area_sampled_kernel tags dec and writes areas[:,2] before it, atab
+// is zeroed for it and unwarp_area_finalize_kernel writes areas[:,0:2] after it
+extern "C++" {
+template <bool AREA>
+static void unwarp_count_launch(bool vec, long wgs, hipStream_t stream, const int* owner, const int* rowx, const int* dec, const float* y,
+                                const long long* cls_label, long long* labels, int* rec, int Hs, int Ws, int hw, int K, int cpi,
+                                const unsigned char* band, int* trec, int* arec, int* atab) {
+  if (band == nullptr) {
+    if (vec)
+      hipLaunchKernelGGL((unwarp_count_kernel<true, false, AREA>), dim3((unsigned)wgs), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
+                         rec, Hs, Ws, hw, K, cpi, nullptr, nullptr, arec, atab);
+    else
+      hipLaunchKernelGGL((unwarp_count_kernel<false, false, AREA>), dim3((unsigned)wgs), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
+                         rec, Hs, Ws, hw, K, cpi, nullptr, nullptr, arec, atab);
+  } else if (vec && ((uintptr_t)band & 3) == 0) {
+    hipLaunchKernelGGL((unwarp_count_kernel<true, true, AREA>), dim3((unsigned)wgs), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
+                       rec, Hs, Ws, hw, K, cpi, band, trec, arec, atab);
+  } else {
+    hipLaunchKernelGGL((unwarp_count_kernel<false, true, AREA>), dim3((unsigned)wgs), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
+                       rec, Hs, Ws, hw, K, cpi, band, trec, arec, atab);
+  }
+}
+}  // extern "C++"
 static int unwarp_accuracy_launch(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label,
                                   long long* counts, float* acc, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws,
-                                  const unsigned char* band, int* trec, long long* trim, int D, hipStream_t stream) {
+                                  const unsigned char* band, int* trec, long long* trim, int D, long long* areas, int* arec, int* atab,
+                                  hipStream_t stream) {
   FS_REQUIRE(cls && m && grid && y && cls_label && counts && acc && scratch && B > 0 && K >= 2 && K <= UNWARP_MAX_K && h > 0 && w > 0 &&
              Hs > 0 && Ws > 0);
   // one row in LDS; int pixel / point indices, the count pass's included (a workgroup's last trip may start up to a chunk past the end)
@@ -1752,6 +1929,12 @@ static int unwarp_accuracy_launch(const float* cls, const float* m, const float*
   FS_REQUIRE(((uintptr_t)scratch & 15) == 0);          // the records are stored and read 16 bytes at a time
   hipLaunchKernelGGL(unwarp_decide_kernel, dim3((unsigned)(B * bpi)), dim3(256), 0, stream, cls, m, dec, K, h, w, (int)bpi);
   FS_LAUNCH_CHECK();
+  if (areas != nullptr) {
+    hipLaunchKernelGGL(class_area_sampled_kernel, dim3((unsigned)B), dim3(256), 0, stream, cls, m, grid, y, cls_label, dec, areas, K, h * w, Hs, Ws);
+    FS_LAUNCH_CHECK();
+    const hipError_t ea = hipMemsetAsync(atab, 0, sizeof(int) * (size_t)B * K, stream);
+    if (ea != hipSuccess) return (int)ea;
+  }
   hipError_t e = hipMemsetAsync(owner, 0xFF, sizeof(int) * (size_t)n, stream);      // -1
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(inverse_owner_kernel, dim3(cdiv((long)B * h * w, 256)), dim3(256), 0, stream, grid, owner, B, h * w, Hs, Ws);
@@ -1759,20 +1942,10 @@ static int unwarp_accuracy_launch(const float* cls, const float* m, const float*
   hipLaunchKernelGGL(fill_row_nearest_kernel, dim3((unsigned)((long)B * Hs)), dim3(256), (size_t)Ws * sizeof(int), stream, owner, rowx, Ws);
   FS_LAUNCH_CHECK();
   const bool vec = Ws % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)labels & 15) == 0;
-  if (band == nullptr) {
-    if (vec)
-      hipLaunchKernelGGL((unwarp_count_kernel<true, false>), dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
-                         rec, Hs, Ws, h * w, K, (int)cpi, nullptr, nullptr);
-    else
-      hipLaunchKernelGGL((unwarp_count_kernel<false, false>), dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
-                         rec, Hs, Ws, h * w, K, (int)cpi, nullptr, nullptr);
-  } else if (vec && ((uintptr_t)band & 3) == 0) {
-    hipLaunchKernelGGL((unwarp_count_kernel<true, true>), dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
-                       rec, Hs, Ws, h * w, K, (int)cpi, band, trec);
-  } else {
-    hipLaunchKernelGGL((unwarp_count_kernel<false, true>), dim3((unsigned)(B * cpi)), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
-                       rec, Hs, Ws, h * w, K, (int)cpi, band, trec);
-  }
+  if (areas == nullptr)
+    unwarp_count_launch<false>(vec, B * cpi, stream, owner, rowx, dec, y, cls_label, labels, rec, Hs, Ws, h * w, K, (int)cpi, band, trec, nullptr, nullptr);
+  else
+    unwarp_count_launch<true>(vec, B * cpi, stream, owner, rowx, dec, y, cls_label, labels, rec, Hs, Ws, h * w, K, (int)cpi, band, trec, arec, atab);
   FS_LAUNCH_CHECK();
   hipLaunchKernelGGL(unwarp_count_finalize_kernel, dim3((unsigned)B), dim3(256), 0, stream, rec, counts, (int)cpi);
   FS_LAUNCH_CHECK();
@@ -1782,12 +1955,17 @@ static int unwarp_accuracy_launch(const float* cls, const float* m, const float*
     hipLaunchKernelGGL(unwarp_trim_finalize_kernel, dim3((unsigned)B), dim3(256), 0, stream, trec, trim, (int)cpi, D);
     FS_LAUNCH_CHECK();
   }
+  if (areas != nullptr) {
+    hipLaunchKernelGGL(unwarp_area_finalize_kernel, dim3((unsigned)B), dim3(256), 0, stream, arec, atab, cls_label, areas, K, (int)cpi, (long long)per);
+    FS_LAUNCH_CHECK();
+  }
   return FS_OK;
 }
 
 int fs_unwarp_accuracy(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
                        float* acc, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws, hipStream_t stream) {
-  return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, nullptr, nullptr, nullptr, 0, stream);
+  return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
+                                nullptr, stream);
 }
 
 // include/fovealseg.h: ints of scratch fs_trimap_bands needs (the row pass's byte map, its rows pitched to four bytes)
@@ -1834,7 +2012,38 @@ int fs_unwarp_trimap(const float* cls, const float* m, const float* grid, const 
   const int r = fs_trimap_bands(y, band, scratch + unwarp_trimap_inter_offset(B, h, w, Hs, Ws), B, Hs, Ws, D, frame, stream);
   if (r != FS_OK) return r;
   return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, band,
-                                scratch + unwarp_trimap_trec_offset(B, h, w, Hs, Ws), trim, D, stream);
+                                scratch + unwarp_trimap_trec_offset(B, h, w, Hs, Ws), trim, D, nullptr, nullptr, nullptr, stream);
+}
+
+// scratch of fs_unwarp_class_areas (ints): fs_unwarp_trimap's (trim or not), then (16-byte aligned) the hot-class records of the count
+// pass, one per workgroup, then atab (B, K): the SUMS over each image's workgroups of the other predicted classes' pixels
+static long unwarp_areas_arec_offset(int B, int h, int w, int Hs, int Ws) { return (fs_unwarp_trimap_scratch_ints(B, h, w, Hs, Ws) + 3) & ~3L; }
+static long unwarp_areas_atab_offset(int B, int h, int w, int Hs, int Ws) {
+  const long cpi = ((long)Hs * Ws + UACC_CHUNK - 1) / UACC_CHUNK;
+  return unwarp_areas_arec_offset(B, h, w, Hs, Ws) + (long)B * cpi * AREA_REC;
+}
+long fs_unwarp_class_areas_scratch_ints(int B, int K, int h, int w, int Hs, int Ws) {
+  if (!(B > 0 && K > 0 && h > 0 && w > 0 && Hs > 0 && Ws > 0)) return 0;
+  return unwarp_areas_atab_offset(B, h, w, Hs, Ws) + (long)B * K;
+}
+
+int fs_unwarp_class_areas(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
+                          float* acc, long long* areas, long long* trim, long long* labels, int* scratch, int B, int K, int h, int w, int Hs,
+                          int Ws, int D, int frame, hipStream_t stream) {
+  FS_REQUIRE(cls && m && grid && y && cls_label && counts && acc && areas && scratch && B > 0 && K >= 2 && K <= UNWARP_MAX_K && h > 0 && w > 0 &&
+             Hs > 0 && Ws > 0);
+  FS_REQUIRE(Ws <= 16384 && (long)h * w < 2147483647L && (long)Hs * Ws < 2147483647L - UACC_CHUNK && ((uintptr_t)scratch & 15) == 0);
+  int* arec = scratch + unwarp_areas_arec_offset(B, h, w, Hs, Ws);
+  int* atab = scratch + unwarp_areas_atab_offset(B, h, w, Hs, Ws);
+  if (trim == nullptr)
+    return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, nullptr, nullptr, nullptr, 0, areas,
+                                  arec, atab, stream);
+  FS_REQUIRE(D >= 0 && D <= TRI_MAX_D && (frame == 0 || frame == 1));
+  unsigned char* band = reinterpret_cast<unsigned char*>(scratch + unwarp_trimap_band_offset(B, h, w, Hs, Ws));
+  const int r = fs_trimap_bands(y, band, scratch + unwarp_trimap_inter_offset(B, h, w, Hs, Ws), B, Hs, Ws, D, frame, stream);
+  if (r != FS_OK) return r;
+  return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, band,
+                                scratch + unwarp_trimap_trec_offset(B, h, w, Hs, Ws), trim, D, areas, arec, atab, stream);
 }
 
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, hipStream_t stream) {

@@ -240,7 +240,7 @@ class DeformSegmentationModule(nn.Module):
         return labels
 
     @torch.no_grad()
-    def evaluate(self, img, focus, seg_label, cls_label, seg_size=None, return_labels=False, trimap=None, trimap_frame=True):
+    def evaluate(self, img, focus, seg_label, cls_label, seg_size=None, return_labels=False, class_areas=False, trimap=None, trimap_frame=True):
         """Full-resolution scoring without the loss: predict's stages, then the four accuracies of forward's MODEL.upsample branch
         (models/models.py:378-474,869-873,1074-1083) taken against the label in the pass that would have written the class map
         (ops.unwarp_accuracy / fs_unwarp_accuracy): no (B,K,H,W) prediction, no class map and no ground-truth tensor exist.
@@ -259,7 +259,16 @@ class DeformSegmentationModule(nn.Module):
         reference's PIL filter, bit for bit), the background pixels of the image's outer ring; trimap_frame=False reads the boundary
         alone.  Constant-label rule: an image without any boundary pixel (a constant label with trimap_frame=False, an all-foreground
         one with it) has empty bands and all-zero counters -- the reference divides 0 by 0 there -- and ops.trimap_from_counts /
-        train.TrimapMeter leave it out of the mean.  With trimap=None the call is unchanged."""
+        train.TrimapMeter leave it out of the mean.  With trimap=None the call is unchanged.
+
+        class_areas=True adds the per-class areas of the reference's evaluation summary (eval.py:218-257,313-322; utils.py:289-317),
+        counted in the same pass (ops.unwarp_class_areas): the LAST element of the result, after labels and trim where those are
+        present, is then areas (B, 3, num_class, 3) int64 = per image, space and class (inter, pred, lab), union = pred + lab - inter.
+        Space 0 scores the full-resolution prediction (the paper's IoU / Dice, VAL.report_per_img_iou per image), space 1 the sampling
+        ceiling (VAL.y_sampled_reverse, IoU(Y', Y): every pixel takes the sampled label of the grid point that feeds it -- what a
+        perfect network behind this sampler would score), space 2 the prediction in the sampled space (Mean IoU_deformed); the lab
+        rows of spaces 0 and 2 are the label distribution before and after sampling.  ops.class_scores_from_areas makes IoU and Dice,
+        train.ClassIoUMeter the dataset-level summary.  With the default the call, its result and its launches are unchanged."""
         if seg_label.dim() not in (3, 4) or (seg_label.dim() == 4 and seg_label.shape[1] != 1):
             raise ValueError(f"seg_label must be (B,H,W) or (B,1,H,W), got {tuple(seg_label.shape)}")
         label_size = (int(seg_label.shape[-2]), int(seg_label.shape[-1]))
@@ -268,6 +277,10 @@ class DeformSegmentationModule(nn.Module):
         if seg_label.shape[0] != img.shape[0] or cls_label.shape[0] != img.shape[0]:
             raise ValueError(f"seg_label {tuple(seg_label.shape)} and cls_label {tuple(cls_label.shape)} must have img's batch size {img.shape[0]}")
         cls, m, grid, _ = self._head_parts(img, focus, label_size, "evaluate")
+        if class_areas:
+            out = ops.unwarp_class_areas(cls, m, grid, seg_label, cls_label, dia_factor=trimap, frame=trimap_frame, return_labels=return_labels)
+            counts, acc = out[0], out[1]
+            return (acc[0], acc[1], acc[2], acc[3], counts) + tuple(reversed(out[3:])) + (out[2],)
         if trimap is None:
             out = ops.unwarp_accuracy(cls, m, grid, seg_label, cls_label, return_labels=return_labels)
             counts, acc = out[0], out[1]

@@ -1582,6 +1582,53 @@ def trimap_from_counts(trim):
     return t[..., 1:] / (t[..., :1] + 1e-10)
 
 
+def unwarp_class_areas(cls, m, grid, y, cls_label, dia_factor=None, frame=True, return_labels=False):
+    """unwarp_accuracy with the per-class areas of the reference's evaluation summary (eval.py:218-257,313-322; utils.intersectionAndUnion,
+    utils.py:289-317) counted in the same gather pass (fs_unwarp_class_areas).  Arguments and checks are unwarp_trimap's; dia_factor=None
+    leaves the trimap out.  Returns (counts, acc, areas[, trim][, labels]): counts, acc, trim and labels are unwarp_accuracy's /
+    unwarp_trimap's bit for bit; areas (B, 3, K, 3) int64 holds per image, space and class (inter, pred, lab), the union being
+    pred + lab - inter.  Space 0 is the prediction at full resolution (unwarp_labels against the ground truth), space 1 the sampling
+    ceiling -- the label after the sampler and the nearest un-warp against itself (VAL.y_sampled_reverse, models/models_instance.py:909-918):
+    every pixel takes grid_sample_label's value of the grid point that feeds it -- and space 2 the prediction in the sampled space
+    (PredAssemble(cls, m).argmax(1) against the sampled ground truth).  A cls_label outside 0 .. K-1 has no lab / inter row."""
+    with_trim = dia_factor is not None
+    D, fr = _trimap_args(dia_factor, frame) if with_trim else (0, 0)
+    B, K = cls.shape
+    _, h, w, _ = grid.shape
+    if tuple(m.shape) != (B, h, w):
+        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
+    if y.dim() == 4 and y.shape[1] == 1:
+        y = y[:, 0]
+    if y.dim() != 3 or y.shape[0] != B:
+        raise ValueError(f"y {tuple(y.shape)} must be (B, Hs, Ws) or (B, 1, Hs, Ws) with B = {B}")
+    Hs, Ws = int(y.shape[1]), int(y.shape[2])
+    if cls_label.dim() == 2 and cls_label.shape[1] == 1:
+        cls_label = cls_label[:, 0]
+    if tuple(cls_label.shape) != (B,):
+        raise ValueError(f"cls_label {tuple(cls_label.shape)} must be (B,) or (B, 1) with B = {B}")
+    counts = torch.empty(B, 6, device=cls.device, dtype=torch.int64)
+    acc = torch.empty(4, device=cls.device, dtype=torch.float32)
+    areas = torch.empty(B, 3, K, 3, device=cls.device, dtype=torch.int64)
+    trim = torch.empty(B, D + 1, 3, device=cls.device, dtype=torch.int64) if with_trim else None
+    labels = torch.empty(B, Hs, Ws, device=cls.device, dtype=torch.int64) if return_labels else None
+    scratch = torch.empty(hip.query("fs_unwarp_class_areas_scratch_ints", B, K, h, w, Hs, Ws), device=cls.device, dtype=torch.int32)
+    hip.call("fs_unwarp_class_areas", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()),
+             hip.ptr(y.float().contiguous()), hip.ptr(cls_label.long().contiguous()), hip.ptr(counts), hip.ptr(acc), hip.ptr(areas),
+             hip.ptr(trim), hip.ptr(labels), hip.ptr(scratch), B, K, h, w, Hs, Ws, D, fr)
+    return (counts, acc, areas) + ((trim,) if with_trim else ()) + ((labels,) if return_labels else ())
+
+
+def class_scores_from_areas(areas):
+    """(..., K, 3) class areas (unwarp_class_areas', on any device; summed over a dataset or not) -> (iou, dice), each (..., K) fp64:
+    iou = inter / (union + 1e-10) and dice = 2 * inter / (union + inter + 1e-10) with union = pred + lab - inter -- the reference's
+    expressions (eval.py:252, 313-315).  A class with an empty union scores 0."""
+    if areas.dim() < 2 or areas.shape[-1] != 3:
+        raise ValueError(f"areas must be (..., K, 3), got {tuple(areas.shape)}")
+    a = areas.to(torch.float64)
+    inter, union = a[..., 0], a[..., 1] + a[..., 2] - a[..., 0]
+    return inter / (union + 1e-10), 2 * inter / (union + inter + 1e-10)
+
+
 def image_accuracies_from_counts(counts):
     """(B,6) counts -> (B,4) fp32 per-image acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg (models/models.py:378-474): plain torch, any device."""
     c = counts.to(torch.float32)

@@ -356,21 +356,25 @@ def eval_step(module, batch):
 
 
 @torch.no_grad()
-def evaluate_step(module, batch, meter=None, trimap_meter=None):
+def evaluate_step(module, batch, meter=None, trimap_meter=None, class_meter=None):
     """Full-resolution scoring of one batch without the loss: module.evaluate on (X, Fp, Y, cls) (module.eval() by caller), the way
     eval_step wraps forward.  Returns evaluate's (acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg, counts); a FullResMeter given as `meter`
     takes the counts (no host read).  With a TrimapMeter as `trimap_meter` the call is evaluate(trimap=trimap_meter.dia_factor,
-    trimap_frame=trimap_meter.frame): the result ends with the trim counters, which that meter takes."""
+    trimap_frame=trimap_meter.frame): the result ends with the trim counters, which that meter takes.  With a ClassIoUMeter as
+    `class_meter` the call has class_areas=True as well: the class areas come last in the result and go to that meter."""
     X, Fp, Y, cls = batch
+    extra = {} if class_meter is None else {"class_areas": True}
     if trimap_meter is None:
-        out = module.evaluate(X[:, :3], Fp, Y, cls)
+        out = module.evaluate(X[:, :3], Fp, Y, cls, **extra)
     else:
-        out = module.evaluate(X[:, :3], Fp, Y, cls, trimap=trimap_meter.dia_factor, trimap_frame=trimap_meter.frame)
+        out = module.evaluate(X[:, :3], Fp, Y, cls, trimap=trimap_meter.dia_factor, trimap_frame=trimap_meter.frame, **extra)
     module.check_nan()
     if meter is not None:
         meter.update(out[4])
     if trimap_meter is not None:
         trimap_meter.update(out[5])
+    if class_meter is not None:
+        class_meter.update(out[-1])
     return out
 
 
@@ -520,6 +524,65 @@ class TrimapMeter:
                 "pooled": [c[1] / c[0] if c[0] > 0 else nan for c in cnt],
                 "pooled_bin": [c[2] / c[0] if c[0] > 0 else nan for c in cnt],
                 "counts": cnt, "images": [int(s[2]) for s in sums]}
+
+
+class ClassIoUMeter:
+    """Dataset-level per-class IoU / Dice (eval.py:218-257,313-331) from the class areas of module.evaluate(class_areas=True) /
+    ops.unwarp_class_areas.  `update(areas)` adds a batch's (B, 3, num_class, 3) int64 areas into device-resident sums -- the areas, the
+    per-image label shares (fp64) and the number of images -- without a host read; `result(reduce=True)` makes ONE all-reduce over the
+    ranks and ONE host read.  For each space of SPACES it returns `iou` / `dice` [K] from the summed areas (the reference's
+    intersection_meter.sum / (union_meter.sum + 1e-10) and its Dice), `miou` / `mdice`, their means over all K classes (the reference's
+    iou.mean()), `miou_present`, the mean over the classes whose summed union is not empty (nan without one), and the raw `areas`
+    (K rows of inter, pred, lab).  Beside them: `label_share_full` / `label_share_sampled` [K], the mean over images of each class's
+    share of the labelled pixels before and after sampling, in percent, and `label_share_shift`, sampled minus full (eval.py:326-328);
+    `images`."""
+
+    SPACES = ("full", "ceiling", "sampled")
+
+    def __init__(self, device, num_class):
+        self.num_class = int(num_class)
+        if self.num_class < 2:
+            raise ValueError(f"num_class must be at least 2, got {num_class}")
+        self.areas = torch.zeros(3, self.num_class, 3, device=device, dtype=torch.int64)
+        self.sums = torch.zeros(2 * self.num_class + 1, device=device, dtype=torch.float64)      # label shares full, sampled; image count
+
+    def update(self, areas):
+        K = self.num_class
+        if areas.dim() != 4 or tuple(areas.shape[1:]) != (3, K, 3):
+            raise ValueError(f"areas must be (B, 3, {K}, 3), got {tuple(areas.shape)}")
+        areas = areas.to(device=self.areas.device, dtype=torch.int64)
+        self.areas.add_(areas.sum(0))
+        lab = areas[:, (0, 2), :, 2].double()                                    # (B, 2, K)
+        share = lab / lab.sum(2, keepdim=True).clamp_(min=1.0)                   # an image without a labelled pixel in range: all 0
+        self.sums[:2 * K].add_(share.sum(0).reshape(-1))
+        self.sums[2 * K:].add_(float(areas.shape[0]))
+
+    def result(self, reduce=True):
+        # one fp64 vector, as FullResMeter.result: each int64 sum as two 32-bit halves, whose sums over the ranks stay exact in fp64
+        K = self.num_class
+        c = self.areas.reshape(-1)
+        tot = torch.cat([(c >> 32).double(), (c & 0xFFFFFFFF).double(), self.sums])
+        if reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(tot, op=dist.ReduceOp.SUM)
+        tot = tot.cpu().tolist()
+        n9 = 9 * K
+        nan = float("nan")
+        res = {}
+        for s, name in enumerate(self.SPACES):
+            rows = [[(int(tot[(s * K + k) * 3 + f]) << 32) + int(tot[n9 + (s * K + k) * 3 + f]) for f in range(3)] for k in range(K)]
+            union = [r[1] + r[2] - r[0] for r in rows]
+            iou = [r[0] / (u + 1e-10) for r, u in zip(rows, union)]
+            dice = [2 * r[0] / (u + r[0] + 1e-10) for r, u in zip(rows, union)]
+            present = [v for v, u in zip(iou, union) if u > 0]
+            res[name] = {"iou": iou, "dice": dice, "miou": sum(iou) / K, "mdice": sum(dice) / K,
+                         "miou_present": sum(present) / len(present) if present else nan, "areas": rows}
+        n = tot[2 * n9 + 2 * K]
+        full = [100.0 * v / n if n > 0 else nan for v in tot[2 * n9: 2 * n9 + K]]
+        samp = [100.0 * v / n if n > 0 else nan for v in tot[2 * n9 + K: 2 * n9 + 2 * K]]
+        res["label_share_full"], res["label_share_sampled"] = full, samp
+        res["label_share_shift"] = [b - a for a, b in zip(full, samp)]
+        res["images"] = int(n)
+        return res
 
 
 # ----------------------------------------------------------------------------------------------

@@ -140,6 +140,28 @@ long fs_unwarp_trimap_scratch_ints(int B, int h, int w, int Hs, int Ws);
 int fs_unwarp_trimap(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
                      float* acc, long long* trim, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws, int D,
                      int frame, fs_stream_t stream);
+/* fs_unwarp_accuracy with the per-class areas of the reference's evaluation summary (eval.py:218-257,313-322; utils.py:289-317,
+ * intersectionAndUnion with ignore_index = none) counted in the same gather pass.  areas (B,3,K,3) int64: per image, space and class
+ * k the triple (inter, pred, lab) = #(a == k and g == k), #(a == k), #(g == k) of a class map a against its ground truth g; the
+ * union is pred + lab - inter (utils.py:312), left to the caller.  Space 0: a = fs_unwarp_labels' class, g = t*cls_label + (1-t)*(K-1),
+ * t = (long)y, over the Hs*Ws pixels.  Space 1, the sampling ceiling (VAL.y_sampled_reverse, "intrinsic upsampling error IoU(Y', Y)",
+ * models/models_instance.py:909-918): a = gs[q] of the grid point q that feeds the pixel, gs[p] = ts*cls_label + (1-ts)*(K-1) with
+ * ts = (long)bilinear(y, grid[p]), fs_grid_sample_label's value bit for bit, against the same g; background in an image without a
+ * claimed pixel.  It is the label of the feeding point itself, NOT the reference's F.grid_sample(mode='nearest') at the inverse
+ * coordinate: that coordinate is xi - 0.5 up to fp32 rounding, a round-half-to-even tie decided by rounding noise.  Space 2, the
+ * sampled space: a = first maximal k of the low-resolution prediction at grid point p (cls[b,k] for k < K-1, cls[b,K-1] * m[b,p],
+ * one rounded multiply; NaN maximal, as torch.max, eval.py:197), g = gs[p], over the h*w points.  Rows are defined by equality: a
+ * cls_label outside 0 .. K-1 has no lab / inter row (np.histogram's range drops it), cls_label == K-1 merges into the background
+ * row.  y reads as 0 or 1 after truncation; other values are not defined.  counts, acc and labels are fs_unwarp_accuracy's bit for
+ * bit.  trim nullable: given, it is fs_unwarp_trimap's bit for bit (bands made here, D and frame as there); null, D and frame are
+ * ignored.  Integer sums throughout: the two hot classes (cls_label, K-1) in per-workgroup records, every other predicted class
+ * through an LDS histogram and 32-bit integer atomics into a zeroed (B,K) table of sums in scratch; bit-reproducible.  scratch =
+ * fs_unwarp_class_areas_scratch_ints(B, K, h, w, Hs, Ws) ints, 16-byte aligned.  FS_ERR_ARG as fs_unwarp_accuracy (and
+ * fs_unwarp_trimap with trim), and for a null areas. */
+long fs_unwarp_class_areas_scratch_ints(int B, int K, int h, int w, int Hs, int Ws);
+int fs_unwarp_class_areas(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label,
+                          long long* counts, float* acc, long long* areas, long long* trim, long long* labels, int* scratch,
+                          int B, int K, int h, int w, int Hs, int Ws, int D, int frame, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
