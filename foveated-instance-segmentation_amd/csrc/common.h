@@ -17,6 +17,13 @@
     if (!(cond)) return FS_ERR_ARG; \
   } while (0)
 
+// a step that returns a status of its own: pass on anything but FS_OK
+#define FS_TRY(call)                 \
+  do {                               \
+    const int _r = (call);           \
+    if (_r != FS_OK) return _r;      \
+  } while (0)
+
 // Kernel-experiment switches (which of two measured variants a shape takes) exist only in builds made with -DFS_EXPERIMENTS
 // (`FS_BUILD_EXPERIMENTS=1 python build.py` -> ab/libfovealseg_experiments.so, loaded through FS_HIP_LIB for same-box A/B runs).
 // In the shipped library the macro is its default, a compile-time constant: no getenv, and the branch not taken is dead code.

@@ -5,7 +5,10 @@
 //   K5  non-uniform bilinear grid_sample (image -> NHWC, label -> int64)    (models/models.py:880,909,951)
 //   K6  grid_sample backward w.r.t. the grid (+ scatter-add w.r.t. input)
 //   K11 area pooling of the full-resolution mask + min/max-normalised MSE   (models/models.py:730,889-898)
+// and, in front of and behind the sampler, the device ingest of a decoded sample and the bilinear up-sampling of the
+// grid to the task size (models/models.py:621-631).  The way back -- inverse warp, hole filling, full-resolution evaluation -- is unwarp.hip.
 #include "common.h"
+#include "grid_taps.h"
 
 namespace {
 
@@ -691,46 +694,8 @@ __global__ __launch_bounds__(1024) void gauss_grid_bwd2_kernel(const float* __re
 }
 
 // ------------------------------------------------------------------------------------------
-// K5 / K6: grid_sample, bilinear, zeros padding, align_corners=False.  Arithmetic follows the
-// bit-exact recipe of SURVEY.md §8(a)-A12 (verified against ATen's CPU kernel by the goldens):
-//   ix = fma(gx+1, W/2, -0.5); w = ix-floor(ix); weights nw=(1-n)(1-w) ...; acc = nw*v_nw;
-//   acc = fma(v_ne,ne,acc); acc = fma(v_sw,sw,acc); acc = fma(v_se,se,acc).
-// Explicit __f*_rn intrinsics keep hipcc from re-associating or contracting differently.
+// K5 / K6: grid_sample, bilinear, zeros padding, align_corners=False (the taps and their bit-exact recipe: grid_taps.h)
 // ------------------------------------------------------------------------------------------
-struct Taps {
-  int x0, y0;
-  float nw, ne, sw, se;
-  bool okx0, okx1, oky0, oky1;
-  float w, n, e, s;   // fractional parts (east/south weights) and their complements
-};
-__device__ __forceinline__ Taps make_taps(float gx, float gy, int H, int W) {
-  Taps t;
-  const float ix = __fmaf_rn(__fadd_rn(gx, 1.f), (float)W * 0.5f, -0.5f);
-  const float iy = __fmaf_rn(__fadd_rn(gy, 1.f), (float)H * 0.5f, -0.5f);
-  const float fx = floorf(ix), fy = floorf(iy);
-  t.w = __fsub_rn(ix, fx); t.e = __fsub_rn(1.f, t.w);
-  t.n = __fsub_rn(iy, fy); t.s = __fsub_rn(1.f, t.n);
-  t.nw = __fmul_rn(t.s, t.e); t.ne = __fmul_rn(t.s, t.w);
-  t.sw = __fmul_rn(t.n, t.e); t.se = __fmul_rn(t.n, t.w);
-  // floor of a possibly huge/NaN coordinate: clamp before the int conversion
-  const float cx = fminf(fmaxf(fx, -2.f), (float)W + 1.f), cy = fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-  t.x0 = (int)cx; t.y0 = (int)cy;
-  t.okx0 = (t.x0 >= 0) & (t.x0 < W); t.okx1 = (t.x0 + 1 >= 0) & (t.x0 + 1 < W);
-  t.oky0 = (t.y0 >= 0) & (t.y0 < H); t.oky1 = (t.y0 + 1 >= 0) & (t.y0 + 1 < H);
-  return t;
-}
-__device__ __forceinline__ float sample_plane(const float* __restrict__ p, int W, const Taps& t) {
-  const float vnw = (t.oky0 & t.okx0) ? p[(long)t.y0 * W + t.x0] : 0.f;
-  const float vne = (t.oky0 & t.okx1) ? p[(long)t.y0 * W + t.x0 + 1] : 0.f;
-  const float vsw = (t.oky1 & t.okx0) ? p[(long)(t.y0 + 1) * W + t.x0] : 0.f;
-  const float vse = (t.oky1 & t.okx1) ? p[(long)(t.y0 + 1) * W + t.x0 + 1] : 0.f;
-  float acc = __fmul_rn(vnw, t.nw);
-  acc = __fmaf_rn(vne, t.ne, acc);
-  acc = __fmaf_rn(vsw, t.sw, acc);
-  acc = __fmaf_rn(vse, t.se, acc);
-  return acc;
-}
-
 // x (B,C,H,W) NCHW -> out (B,h,w,C) NHWC  [nhwc_out=1]  or (B,C,h,w) NCHW [nhwc_out=0]
 __global__ __launch_bounds__(256) void grid_sample_fwd_kernel(const float* __restrict__ x, const float* __restrict__ grid,
                                                               float* __restrict__ out, int B, int C, int H, int W, int h,
@@ -801,730 +766,6 @@ __global__ __launch_bounds__(256) void grid_sample_bwd_input_kernel(const float*
     if (t.oky0 & t.okx1) atomicAdd(&p[(long)t.y0 * W + t.x0 + 1], go * t.ne);
     if (t.oky1 & t.okx0) atomicAdd(&p[(long)(t.y0 + 1) * W + t.x0], go * t.sw);
     if (t.oky1 & t.okx1) atomicAdd(&p[(long)(t.y0 + 1) * W + t.x0 + 1], go * t.se);
-  }
-}
-
-// integer index maps of the inverse deformation (models/models.py:644-645): trunc toward zero
-__global__ void inverse_index_kernel(const float* __restrict__ grid, long long* __restrict__ u, long long* __restrict__ v,
-                                     long n, int H, int W) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const float gx = grid[2 * i], gy = grid[2 * i + 1];
-  const float fu = __fmul_rn(__fmul_rn(__fadd_rn(gx, 1.f), 0.5f), (float)(W - 1));
-  const float fv = __fmul_rn(__fmul_rn(__fadd_rn(gy, 1.f), 0.5f), (float)(H - 1));
-  u[i] = (long long)(int)fu;
-  v[i] = (long long)(int)fv;
-}
-
-// ---- inverse (un-foveating) warp, SURVEY §8(f)-3 -------------------------------------------------------------------
-// models/models.py:639-655: every grid point i = (yi, xi) of the (h,w) sampling grid claims the full-resolution pixel
-// (v,u) it was sampled from; duplicate claims resolve as ATen-CPU index_put_ does (the LAST index wins = largest i).
-__global__ void inverse_owner_kernel(const float* __restrict__ grid, int* __restrict__ owner, int B, int hw, int Hs, int Ws) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)B * hw) return;
-  const int b = (int)(i / hw), p = (int)(i - (long)b * hw);
-  const float gx = grid[2 * i], gy = grid[2 * i + 1];
-  const int u = (int)__fmul_rn(__fmul_rn(__fadd_rn(gx, 1.f), 0.5f), (float)(Ws - 1));
-  const int v = (int)__fmul_rn(__fmul_rn(__fadd_rn(gy, 1.f), 0.5f), (float)(Hs - 1));
-  if (u < 0 || u >= Ws || v < 0 || v >= Hs) return;
-  atomicMax(&owner[((long)b * Hs + v) * Ws + u], p);
-}
-// grid_inv[b,v,u] = (xi/w*2-1, yi/h*2-1) of the owning grid point, 0 where nobody claims the pixel (the reference writes NaN
-// and replaces it by 0 before sampling, models.py:931-932; the hole mask is owner < 0).
-__global__ void inverse_grid_kernel(const int* __restrict__ owner, float* __restrict__ inv, long n, int h, int w) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int p = owner[i];
-  float gx = 0.f, gy = 0.f;
-  if (p >= 0) {
-    const int yi = p / w, xi = p - yi * w;
-    gx = __fsub_rn(__fmul_rn(__fdiv_rn((float)xi, (float)w), 2.f), 1.f);
-    gy = __fsub_rn(__fmul_rn(__fdiv_rn((float)yi, (float)h), 2.f), 1.f);
-  }
-  inv[2 * i] = gx; inv[2 * i + 1] = gy;
-}
-// Nearest-valid fill (models.py:159-286 with rev_deform_interp='nearest'): exact Euclidean nearest claimed pixel, ties to
-// the smallest (row, col).  Pass A: nearest claimed column in the same row; pass B: minimise (y-y')^2 + (x-x'(y'))^2 over rows.
-__global__ __launch_bounds__(256) void fill_row_nearest_kernel(const int* __restrict__ owner, int* __restrict__ rowx, int Ws) {
-  extern __shared__ int rowbuf[];                      // [Ws]: claimed flag, then nearest claimed column
-  __shared__ int carryL[256], carryR[256];
-  const int tid = threadIdx.x;
-  const long row = blockIdx.x;
-  const int* o = owner + row * Ws;
-  int* r = rowx + row * Ws;
-  int any = 0;
-  for (int x = tid; x < Ws; x += 256) { const int c = o[x] >= 0; rowbuf[x] = c; any |= c; }
-  // most rows of a strongly magnified image hold no claimed pixel at all
-  if (!__syncthreads_or(any)) {
-    for (int x = tid; x < Ws; x += 256) r[x] = -1;
-    return;
-  }
-  // thread t owns the columns [x0, x1): last / first claimed column of the segment, then a scan over the 256 segments
-  const int seg = (Ws + 255) / 256;
-  const int x0 = tid * seg < Ws ? tid * seg : Ws, x1 = x0 + seg < Ws ? x0 + seg : Ws;
-  int last = -1, first = 0x7fffffff;
-  for (int x = x0; x < x1; ++x)
-    if (rowbuf[x]) { last = x; if (first == 0x7fffffff) first = x; }
-  carryL[tid] = last; carryR[tid] = first;
-  __syncthreads();
-  for (int off = 1; off < 256; off <<= 1) {
-    int l = carryL[tid], rr = carryR[tid];
-    if (tid >= off) { const int v = carryL[tid - off]; l = v > l ? v : l; }
-    if (tid + off < 256) { const int v = carryR[tid + off]; rr = v < rr ? v : rr; }
-    __syncthreads();
-    carryL[tid] = l; carryR[tid] = rr;
-    __syncthreads();
-  }
-  int left = tid > 0 ? carryL[tid - 1] : -1;
-  int right = tid < 255 ? carryR[tid + 1] : 0x7fffffff;
-  for (int x = x0; x < x1; ++x) {                      // nearest claimed column at or left of x
-    if (rowbuf[x]) left = x;
-    rowbuf[x] = left;
-  }
-  for (int x = x1 - 1; x >= x0; --x) {                 // ... against the nearest at or right of x; a tie goes to the left one
-    const int l = rowbuf[x];
-    if (l == x) right = x;
-    int best;
-    if (l < 0) best = right == 0x7fffffff ? -1 : right;
-    else if (right == 0x7fffffff) best = l;
-    else best = (x - l) <= (right - x) ? l : right;
-    rowbuf[x] = best;
-  }
-  __syncthreads();
-  for (int x = tid; x < Ws; x += 256) r[x] = rowbuf[x];
-}
-// pixel index y'*Ws+x' of the claimed pixel nearest to (y, x), -1 when the image has none; rx = the image's rows of fill_row_nearest_kernel
-__device__ __forceinline__ int nearest_claimed(const int* __restrict__ rx, int y, int x, int Hs, int Ws) {
-  long best = -1;
-  int bsrc = -1;
-  for (int d = 0; d < Hs; ++d) {                       // rows by increasing |y - y'|: stop once dy^2 alone exceeds the best
-    if (best >= 0 && (long)d * d > best) break;
-    for (int sgn = 0; sgn < 2; ++sgn) {
-      const int yy = sgn == 0 ? y - d : y + d;
-      if (yy < 0 || yy >= Hs || (d == 0 && sgn == 1)) continue;
-      const int xx = rx[(long)yy * Ws + x];
-      if (xx < 0) continue;
-      const long dd = (long)d * d + (long)(x - xx) * (x - xx);
-      const int cand = yy * Ws + xx;
-      if (best < 0 || dd < best || (dd == best && cand < bsrc)) { best = dd; bsrc = cand; }
-    }
-  }
-  return bsrc;
-}
-__global__ void fill_col_nearest_kernel(const int* __restrict__ rowx, int* __restrict__ src, long n, int Hs, int Ws) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const long per = (long)Hs * Ws;
-  const long b = i / per;
-  const long rem = i - b * per;
-  const int y = (int)(rem / Ws), x = (int)(rem - (long)y * Ws);
-  src[i] = nearest_claimed(rowx + b * per, y, x, Hs, Ws);
-}
-__global__ void fill_copy_kernel(float* __restrict__ vals, const int* __restrict__ owner, const int* __restrict__ src, int C, long per,
-                                 long n) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;       // over (b, pixel): the source index is looked up once for all classes
-  if (i >= n) return;
-  if (owner[i] >= 0) return;                           // claimed pixels keep their sampled value
-  const int sp = src[i];
-  if (sp < 0) return;                                  // image without any claimed pixel
-  const long b = i / per;
-  const long pix = i - b * per;
-  float* v = vals + b * C * per;
-  int c = 0;
-  for (; c + 4 <= C; c += 4) {                          // four independent gathers in flight per trip
-    const float a0 = v[(c + 0) * per + sp], a1 = v[(c + 1) * per + sp], a2 = v[(c + 2) * per + sp], a3 = v[(c + 3) * per + sp];
-    v[(c + 0) * per + pix] = a0; v[(c + 1) * per + pix] = a1; v[(c + 2) * per + pix] = a2; v[(c + 3) * per + pix] = a3;
-  }
-  for (; c < C; ++c) v[c * per + pix] = v[c * per + sp];
-}
-
-// ---- class map at full resolution without the (B,K,Hs,Ws) prediction ----------------------------------------------------------------
-// The C1 prediction is pred[b,k] = cls[b,k] (k < K-1, one constant plane) and pred[b,K-1] = cls[b,K-1] * m[b] (fs_pred_assemble_fwd).
-// Through the inverse warp every full-resolution pixel carries the sample of pred at ONE grid point's inverse coordinate: its owner's
-// if claimed, its nearest claimed pixel's owner's if a hole, (0,0) in an image without any claim.  So argmax_k of unwarp_nearest(pred)
-// is a per-grid-point decision gathered through the owner map; both kernels repeat the float operations of the unfused route exactly.
-constexpr int UNWARP_MAX_K = 1024;
-// dec[b,p] = argmax_k of grid_sample(pred[b], inverse coordinate of point p) for p < h*w, and of the sample at (0,0) for p = h*w
-__global__ __launch_bounds__(256) void unwarp_decide_kernel(const float* __restrict__ cls, const float* __restrict__ m, int* __restrict__ dec,
-                                                            int K, int h, int w, int blocks_per_image) {
-  __shared__ float cs[UNWARP_MAX_K];
-  const int b = blockIdx.x / blocks_per_image;
-  const int hw = h * w;
-  for (int k = threadIdx.x; k < K; k += 256) cs[k] = cls[(long)b * K + k];
-  __syncthreads();
-  const int p = (blockIdx.x - b * blocks_per_image) * 256 + threadIdx.x;
-  if (p > hw) return;
-  float gx = 0.f, gy = 0.f;                            // the coordinate inverse_grid_kernel writes for this point / for a hole
-  if (p < hw) {
-    const int yi = p / w, xi = p - yi * w;
-    gx = __fsub_rn(__fmul_rn(__fdiv_rn((float)xi, (float)w), 2.f), 1.f);
-    gy = __fsub_rn(__fmul_rn(__fdiv_rn((float)yi, (float)h), 2.f), 1.f);
-  }
-  const Taps t = make_taps(gx, gy, h, w);
-  const bool inw = t.oky0 & t.okx0, ine = t.oky0 & t.okx1, isw = t.oky1 & t.okx0, ise = t.oky1 & t.okx1;
-  // sample_plane's sequence; a constant plane reads c at every in-bounds tap, 0 outside
-  auto sample4 = [&](float vnw, float vne, float vsw, float vse) {
-    float acc = __fmul_rn(vnw, t.nw);
-    acc = __fmaf_rn(vne, t.ne, acc);
-    acc = __fmaf_rn(vsw, t.sw, acc);
-    return __fmaf_rn(vse, t.se, acc);
-  };
-  // torch.argmax: the first maximal index; NaN counts as the maximum
-  float best = 0.f;
-  int arg = 0;
-  for (int k = 0; k < K - 1; ++k) {
-    const float c = cs[k];
-    const float v = sample4(inw ? c : 0.f, ine ? c : 0.f, isw ? c : 0.f, ise ? c : 0.f);
-    if (k == 0 || v > best || (v != v && best == best)) { best = v; arg = k; }
-  }
-  const float c = cs[K - 1];
-  const float* mp = m + (long)b * hw;
-  const float v = sample4(inw ? __fmul_rn(c, mp[t.y0 * w + t.x0]) : 0.f, ine ? __fmul_rn(c, mp[t.y0 * w + t.x0 + 1]) : 0.f,
-                          isw ? __fmul_rn(c, mp[(t.y0 + 1) * w + t.x0]) : 0.f, ise ? __fmul_rn(c, mp[(t.y0 + 1) * w + t.x0 + 1]) : 0.f);
-  if (v > best || (v != v && best == best)) arg = K - 1;
-  dec[(long)b * (hw + 1) + p] = arg;
-}
-// labels[b,v,u] = dec[b, point feeding the pixel]: its owner; a hole's nearest claimed pixel's owner (fill_col_nearest_kernel's search);
-// dec[b,h*w] in an image without any claim.  hole (nullable) = the pixel has no owner.
-__global__ __launch_bounds__(256) void unwarp_label_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
-                                                           long long* __restrict__ labels, unsigned char* __restrict__ hole, long n, int Hs, int Ws,
-                                                           int hw) {
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const long per = (long)Hs * Ws;
-  const long b = i / per;
-  const int o = owner[i];
-  int q = o;
-  if (o < 0) {
-    const long rem = i - b * per;
-    const int y = (int)(rem / Ws), x = (int)(rem - (long)y * Ws);
-    const int src = nearest_claimed(rowx + b * per, y, x, Hs, Ws);
-    q = src >= 0 ? owner[b * per + src] : hw;
-  }
-  labels[i] = (long long)dec[b * (hw + 1) + q];
-  if (hole != nullptr) hole[i] = o < 0;
-}
-
-// ---- the four full-resolution accuracies without the class map ---------------------------------------------------------------------
-// unwarp_label_kernel's gather with the compare-and-count of seg_loss_fwd_kernel behind it: the predicted class of a pixel is
-// dec[point feeding it], its ground truth one read of the label mask (t = (long)y, gt = t*cls_label + (1-t)*(K-1), models.py:968),
-// and the six counters of models/models.py:378-474 are summed where the class would have been stored.
-// pixels per thread: one trip of four neighbours.  8 and 16 (fewer records) measured slower: 614 / 616 against 519 us at B = 64, 1024^2,
-// and 24 / 34 against 14 us at B = 1, where 256 workgroups a trip longer leave the CUs short of waves (profiles/r07)
-constexpr int UACC_PIX = 4;
-constexpr int UACC_CHUNK = 256 * UACC_PIX;             // pixels per workgroup, all of one image
-constexpr int UACC_REC = 8;                            // ints per workgroup record: the six counters + 2 of padding (two 16-byte stores)
-struct AccCount { int c[6]; };
-__device__ __forceinline__ int unwarp_class_at(const int* __restrict__ ob, const int* __restrict__ rx, const int* __restrict__ db, int o,
-                                               int y, int x, int Hs, int Ws, int hw) {
-  int q = o;
-  if (o < 0) {
-    const int src = nearest_claimed(rx, y, x, Hs, Ws);
-    q = src >= 0 ? ob[src] : hw;
-  }
-  return db[q];
-}
-// nearest_claimed for the four pixels (y, x .. x+3) of one row at once (x % 4 == 0, Ws % 4 == 0): one 16-byte read of rx per row serves
-// all four.  Every pixel sees its candidates in nearest_claimed's order and under its comparison; the rows past the point where
-// nearest_claimed would have stopped for it cannot win (dd >= d*d > best), so each src[k] is nearest_claimed's.  A claimed pixel
-// (hole bit clear) takes no part.
-__device__ __forceinline__ void nearest_claimed4(const int* __restrict__ rx, int y, int x, int Hs, int Ws, int holes, int src[4]) {
-  long best[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { best[k] = (holes >> k) & 1 ? -1 : 0; src[k] = -1; }
-  for (int d = 0; d < Hs; ++d) {
-    const long d2 = (long)d * d;
-    bool done = true;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) done = done && best[k] >= 0 && d2 > best[k];
-    if (done) break;
-    for (int sgn = 0; sgn < 2; ++sgn) {
-      const int yy = sgn == 0 ? y - d : y + d;
-      if (yy < 0 || yy >= Hs || (d == 0 && sgn == 1)) continue;
-      const int4 r = *reinterpret_cast<const int4*>(rx + (long)yy * Ws + x);
-      const int xs[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int xx = xs[k];
-        if (xx < 0) continue;
-        const long dx = (long)(x + k - xx);
-        const long dd = d2 + dx * dx;
-        const int cand = yy * Ws + xx;
-        if (best[k] < 0 || dd < best[k] || (dd == best[k] && cand < src[k])) { best[k] = dd; src[k] = cand; }
-      }
-    }
-  }
-}
-// head_loss.hip's predicates (seg_loss_fwd_kernel) on one pixel: a = predicted class, yv = the label mask's value
-__device__ __forceinline__ void count_pixel(AccCount& n, int a, float yv, long long cl, int bg) {
-  const long long t = (long long)yv;
-  const long long g = t * cl + (1 - t) * (long long)bg;
-  const bool vg = g < bg, vp = a < bg, bgg = g == bg, bgp = a == bg, eq = (long long)a == g;
-  n.c[0] += (vg && eq); n.c[1] += (vg && (vg == vp)); n.c[2] += (vg || vp);
-  n.c[3] += (bgg && eq); n.c[4] += (bgg && (bgg == bgp)); n.c[5] += (bgg || bgp);
-}
-// grid = B * blocks_per_image workgroups; workgroup (b, chunk) counts UACC_CHUNK consecutive pixels of image b into ONE record of
-// rec (plain stores: no zero-initialised scratch, no global atomics).  VEC: Ws % 4 == 0 and 16-byte aligned owner / y / labels, so
-// that four neighbours are one row's and load as one dwordx4 each.  labels (nullable) receives unwarp_label_kernel's class map.
-// TRIM (fs_unwarp_trimap): the pixel's band byte (fs_trimap_bands) buckets three more predicates -- in a band, class right, foreground /
-// background right -- into trec; without it the body is fs_unwarp_accuracy's count pass as it was.
-constexpr int TRIM_BUCKETS = 8;                        // band indices 0 .. D, D <= 7
-constexpr int TRIM_REC = TRIM_BUCKETS * 3;             // ints per workgroup record: (total, cls_ok, bin_ok) per bucket, six 16-byte rows
-// one LDS add per banded pixel: three 10-bit fields of its wave's bucket word (a wave counts at most 256 pixels)
-__device__ __forceinline__ void trim_pixel(unsigned int* __restrict__ tbw, unsigned int bi, int a, float yv, long long cl, int bg) {
-  if (bi >= (unsigned int)TRIM_BUCKETS) return;        // 255: in no band
-  const long long t = (long long)yv;
-  const long long g = t * cl + (1 - t) * (long long)bg;
-  const unsigned int eq = (long long)a == g, bin = (a == bg) == (g == bg);
-  atomicAdd(tbw + bi, 1u | eq << 10 | bin << 20);
-}
-// AREA (fs_unwarp_class_areas): the per-class areas of utils.intersectionAndUnion (utils.py:289-317) for two class maps against the
-// ground truth g of count_pixel -- the predicted class a = dec[q] of the feeding point q, and the CEILING class a' = gs[q], gs[p] =
-// ts[p]*cl + (1 - ts[p])*(K-1) with ts[p] grid_sample_label_kernel's value of point p bit for bit (the training label of that point;
-// background for the point h*w of an image without any claim).  This is the reference's VAL.y_sampled_reverse, "intrinsic upsampling
-// error IoU(Y', Y)" (models/models_instance.py:909-918, eval.py:220-244): the label after the sampler and the nearest un-warp, scored
-// against itself.  The ceiling is the label of the feeding point ITSELF, not the reference's F.grid_sample(mode='nearest') at the
-// inverse coordinate: that coordinate is xi - 0.5 up to fp32 rounding, so the reference's value is a round-half-to-even tie decided
-// by rounding noise between the point and its left / upper neighbour.
-// ts rides in bit DEC_TS_BIT of dec, set by class_area_sampled_kernel after unwarp_decide_kernel and masked in the AREA instantiations
-// only; the others never see it (their launcher does not run that kernel) and stay the instruction streams they were.
-// g and a' are cl or K-1, and almost every a is: those two HOT classes are counted in registers -- eight predicates in three words of
-// 10-bit fields, a thread adding at most four pixels and a wave 256 -- reduced by shuffles and LDS into one AREA_REC-int record per
-// workgroup (arec, two 16-byte stores).  A predicted class other than the two goes to a per-workgroup LDS histogram of K bins (zeroed
-// at entry), whose non-zero bins are added with 32-bit integer global atomics into atab (B, K), zeroed by the launcher: atab holds
-// SUMS, not records.  A workgroup without such a pixel (the usual case) skips the flush.  Integer sums: the same bits in any order.
-constexpr int DEC_TS_BIT = 30;
-constexpr int DEC_CLASS_MASK = (1 << DEC_TS_BIT) - 1;
-constexpr int AREA_REC = 8;                            // t, a==cl & t, a==bg & !t | a==cl (not bg), a==bg, ts | ts & t, !ts & !t
-struct AreaWords { unsigned int w[3]; unsigned int cold; };
-// d = dec word of the feeding point (class | ts << DEC_TS_BIT); returns the class
-__device__ __forceinline__ int area_pixel(AreaWords& r, int* __restrict__ hist, int d, float yv, long long cl, int bg) {
-  const int a = d & DEC_CLASS_MASK;
-  const unsigned int ts = (unsigned int)d >> DEC_TS_BIT;
-  const unsigned int t = (long long)yv != 0;
-  const unsigned int acl = (long long)a == cl, abg = a == bg;
-  r.w[0] += t | (acl & t) << 10 | (abg & (t ^ 1u)) << 20;
-  r.w[1] += (acl & (abg ^ 1u)) | abg << 10 | ts << 20;
-  r.w[2] += (ts & t) | ((ts | t) ^ 1u) << 10;
-  if (!(acl | abg)) { atomicAdd(hist + a, 1); r.cold = 1u; }
-  return a;
-}
-template <bool VEC, bool TRIM, bool AREA>
-__global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
-                                                           const float* __restrict__ yl, const long long* __restrict__ cls_label,
-                                                           long long* __restrict__ labels, int* __restrict__ rec, int Hs, int Ws, int hw,
-                                                           int K, int blocks_per_image, const unsigned char* __restrict__ band,
-                                                           int* __restrict__ trec, int* __restrict__ arec, int* __restrict__ atab) {
-  __shared__ int part[4][6];
-  __shared__ unsigned int tb[4][TRIM_BUCKETS];         // TRIM: one bucket row per wave
-  __shared__ int hist[AREA ? UNWARP_MAX_K : 1];        // AREA: predicted classes other than cl and K-1
-  __shared__ int apart[4][AREA_REC];
-  if (AREA) {
-    for (int k = threadIdx.x; k < K; k += 256) hist[k] = 0;
-  }
-  if (TRIM) {
-    if (threadIdx.x < 4 * TRIM_BUCKETS) tb[threadIdx.x / TRIM_BUCKETS][threadIdx.x % TRIM_BUCKETS] = 0u;
-  }
-  if (TRIM || AREA) __syncthreads();
-  AreaWords aw = {{0u, 0u, 0u}, 0u};
-  unsigned int* tbw = tb[threadIdx.x >> 6];
-  const int b = blockIdx.x / blocks_per_image, chunk = blockIdx.x - b * blocks_per_image;
-  const int per = Hs * Ws;
-  const long base = (long)b * per;
-  const int* ob = owner + base;
-  const int* rx = rowx + base;
-  const int* db = dec + (long)b * (hw + 1);
-  const float* yb = yl + base;
-  const long long cl = cls_label[b];
-  const int bg = K - 1;
-  AccCount n = {{0, 0, 0, 0, 0, 0}};
-  const int p0 = chunk * UACC_CHUNK;
-  if (VEC) {
-#pragma unroll 1
-    for (int j = 0; j < UACC_PIX / 4; ++j) {
-      const int p = p0 + (j * 256 + (int)threadIdx.x) * 4;
-      if (p >= per) break;                             // per % 4 == 0: the four pixels are in or out together
-      const int4 o4 = *reinterpret_cast<const int4*>(ob + p);
-      const float4 y4 = *reinterpret_cast<const float4*>(yb + p);
-      const int y = p / Ws, x = p - y * Ws;            // Ws % 4 == 0: one row
-      int q[4] = {o4.x, o4.y, o4.z, o4.w};
-      const int holes = (o4.x < 0) | (o4.y < 0) << 1 | (o4.z < 0) << 2 | (o4.w < 0) << 3;
-      if (holes) {
-        int src[4];
-        nearest_claimed4(rx, y, x, Hs, Ws, holes, src);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
-      }
-      int a0 = db[q[0]], a1 = db[q[1]], a2 = db[q[2]], a3 = db[q[3]];
-      if (AREA) {
-        a0 = area_pixel(aw, hist, a0, y4.x, cl, bg); a1 = area_pixel(aw, hist, a1, y4.y, cl, bg);
-        a2 = area_pixel(aw, hist, a2, y4.z, cl, bg); a3 = area_pixel(aw, hist, a3, y4.w, cl, bg);
-      }
-      count_pixel(n, a0, y4.x, cl, bg); count_pixel(n, a1, y4.y, cl, bg);
-      count_pixel(n, a2, y4.z, cl, bg); count_pixel(n, a3, y4.w, cl, bg);
-      if (TRIM) {
-        const unsigned int b4 = *reinterpret_cast<const unsigned int*>(band + base + p);
-        trim_pixel(tbw, b4 & 255u, a0, y4.x, cl, bg); trim_pixel(tbw, (b4 >> 8) & 255u, a1, y4.y, cl, bg);
-        trim_pixel(tbw, (b4 >> 16) & 255u, a2, y4.z, cl, bg); trim_pixel(tbw, b4 >> 24, a3, y4.w, cl, bg);
-      }
-      if (labels != nullptr) {
-        longlong2* lp = reinterpret_cast<longlong2*>(labels + base + p);
-        lp[0] = make_longlong2(a0, a1); lp[1] = make_longlong2(a2, a3);
-      }
-    }
-  } else {
-#pragma unroll 1
-    for (int j = 0; j < UACC_PIX; ++j) {
-      const int p = p0 + j * 256 + (int)threadIdx.x;
-      if (p >= per) break;
-      const int y = p / Ws, x = p - y * Ws;
-      int a = unwarp_class_at(ob, rx, db, ob[p], y, x, Hs, Ws, hw);
-      if (AREA) a = area_pixel(aw, hist, a, yb[p], cl, bg);
-      count_pixel(n, a, yb[p], cl, bg);
-      if (TRIM) trim_pixel(tbw, band[base + p], a, yb[p], cl, bg);
-      if (labels != nullptr) labels[base + p] = (long long)a;
-    }
-  }
-  // in the wave by shuffles, across the four waves through LDS; integers: the same record whatever the order
-#pragma unroll
-  for (int q = 0; q < 6; ++q) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n.c[q] += __shfl_xor(n.c[q], o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < 6; ++q) part[threadIdx.x >> 6][q] = n.c[q];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int s[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) s[q] = (part[0][q] + part[1][q]) + (part[2][q] + part[3][q]);
-    int4* r = reinterpret_cast<int4*>(rec + (long)blockIdx.x * UACC_REC);
-    r[0] = make_int4(s[0], s[1], s[2], s[3]);
-    r[1] = make_int4(s[4], s[5], 0, 0);
-  }
-  if (TRIM && threadIdx.x < TRIM_REC) {
-    const int bi = threadIdx.x / 3, sh = 10 * (threadIdx.x % 3);
-    int t = 0;
-#pragma unroll
-    for (int wv = 0; wv < 4; ++wv) t += (int)((tb[wv][bi] >> sh) & 1023u);
-    trec[(long)blockIdx.x * TRIM_REC + threadIdx.x] = t;
-  }
-  if (AREA) {
-#pragma unroll
-    for (int q = 0; q < 3; ++q) {
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) aw.w[q] += __shfl_xor(aw.w[q], o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-      int* ap = apart[threadIdx.x >> 6];
-#pragma unroll
-      for (int f = 0; f < AREA_REC; ++f) ap[f] = (int)((aw.w[f / 3] >> (10 * (f % 3))) & 1023u);
-    }
-    // the barrier also ends the histogram's adds; no workgroup leaves before it (the trips above end by break, not return)
-    const int cold = __syncthreads_or((int)aw.cold);
-    if (threadIdx.x == 0) {
-      int s[AREA_REC];
-#pragma unroll
-      for (int f = 0; f < AREA_REC; ++f) s[f] = (apart[0][f] + apart[1][f]) + (apart[2][f] + apart[3][f]);
-      int4* r = reinterpret_cast<int4*>(arec + (long)blockIdx.x * AREA_REC);
-      r[0] = make_int4(s[0], s[1], s[2], s[3]);
-      r[1] = make_int4(s[4], s[5], s[6], s[7]);
-    }
-    if (cold) {
-      for (int k = threadIdx.x; k < K; k += 256) {
-        const int v = hist[k];
-        if (v != 0) atomicAdd(atab + (long)b * K + k, v);
-      }
-    }
-  }
-}
-// Class areas in the sampled space (eval.py:197, pred_deformed against y_sampled), and the ceiling bit of dec.  One workgroup per
-// image.  At grid point p < h*w the prediction is pred[b,k,p] = cls[b,k] for k < K-1 and fmul(cls[b,K-1], m[b,p]) for K-1 -- one
-// rounded multiply, as pred_assemble_fwd_kernel's -- and its class the first maximal k, NaN counting as maximal (torch.max).  The
-// planes below K-1 are constant, so their first maximum kb is one per image and a point's class is kb or K-1; its label gs[p] is cl
-// or K-1.  Only those classes can occur: four block-wide counts make every row of areas[b,2], and no histogram is needed.  ts[p] =
-// (long)bilinear(y, grid[p]) is grid_sample_label_kernel's sequence (make_taps + sample_plane); it is or-ed into bit DEC_TS_BIT of
-// dec[b,p] for the AREA count pass.  dec[b,h*w] keeps a clear bit: background.
-__global__ __launch_bounds__(256) void class_area_sampled_kernel(const float* __restrict__ cls, const float* __restrict__ m,
-                                                                 const float* __restrict__ grid, const float* __restrict__ yl,
-                                                                 const long long* __restrict__ cls_label, int* __restrict__ dec,
-                                                                 long long* __restrict__ areas, int K, int hw, int Hs, int Ws) {
-  __shared__ float cs[UNWARP_MAX_K];
-  __shared__ int kbest;
-  __shared__ long long red[16];
-  const int b = blockIdx.x;
-  for (int k = threadIdx.x; k < K; k += 256) cs[k] = cls[(long)b * K + k];
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float best = 0.f;
-    int arg = 0;
-    for (int k = 0; k < K - 1; ++k) {
-      const float v = cs[k];
-      if (k == 0 || v > best || (v != v && best == best)) { best = v; arg = k; }
-    }
-    kbest = arg;
-  }
-  __syncthreads();
-  const int kb = kbest, bg = K - 1;
-  const float best = cs[kb], c = cs[bg];
-  const long long cl = cls_label[b];
-  const float* mp = m + (long)b * hw;
-  const float* gp = grid + 2 * (long)b * hw;
-  const float* yb = yl + (long)b * Hs * Ws;
-  int* db = dec + (long)b * (hw + 1);
-  long long n[4] = {0, 0, 0, 0};                       // class K-1, ts, class == cl & ts, class == K-1 & !ts
-  for (int p = threadIdx.x; p < hw; p += 256) {
-    const Taps t = make_taps(gp[2 * p], gp[2 * p + 1], Hs, Ws);
-    const int ts = (long long)sample_plane(yb, Ws, t) != 0;
-    db[p] |= ts << DEC_TS_BIT;
-    const float v = __fmul_rn(c, mp[p]);
-    const int a = (v > best || (v != v && best == best)) ? bg : kb;
-    n[0] += a == bg; n[1] += ts; n[2] += ((long long)a == cl) & ts; n[3] += (a == bg) & (ts ^ 1);
-  }
-  for (int q = 0; q < 4; ++q) n[q] = block_sum<long long>(n[q], red);
-  long long* out = areas + ((long)b * 3 + 2) * K * 3;
-  for (int k = threadIdx.x; k < K; k += 256) {
-    const bool iscl = (long long)k == cl, isbg = k == bg;
-    out[3 * k + 0] = (iscl ? n[2] : 0) + (isbg ? n[3] : 0);
-    out[3 * k + 1] = (k == kb ? (long long)hw - n[0] : 0) + (isbg ? n[0] : 0);
-    out[3 * k + 2] = (iscl ? n[1] : 0) + (isbg ? (long long)hw - n[1] : 0);
-  }
-}
-// areas[b, 0] (prediction) and areas[b, 1] (ceiling) at full resolution = image b's hot records summed, the rows of the two hot
-// classes made from them by equality (cl == K-1 merges into one row, cl outside 0 .. K-1 has none), plus atab's other predicted
-// classes; one workgroup per image.  Record fields: AREA_REC.
-__global__ __launch_bounds__(256) void unwarp_area_finalize_kernel(const int* __restrict__ arec, const int* __restrict__ atab,
-                                                                   const long long* __restrict__ cls_label, long long* __restrict__ areas,
-                                                                   int K, int blocks_per_image, long long per) {
-  __shared__ long long red[16];
-  const int b = blockIdx.x;
-  const int4* r = reinterpret_cast<const int4*>(arec + (long)b * blocks_per_image * AREA_REC);
-  long long c[AREA_REC] = {0, 0, 0, 0, 0, 0, 0, 0};
-  for (int j = threadIdx.x; j < blocks_per_image; j += 256) {
-    const int4 lo = r[2 * j], hi = r[2 * j + 1];
-    c[0] += lo.x; c[1] += lo.y; c[2] += lo.z; c[3] += lo.w; c[4] += hi.x; c[5] += hi.y; c[6] += hi.z; c[7] += hi.w;
-  }
-  for (int q = 0; q < AREA_REC; ++q) c[q] = block_sum<long long>(c[q], red);
-  const long long cl = cls_label[b];
-  const int bg = K - 1;
-  long long* o0 = areas + (long)b * 3 * K * 3;
-  long long* o1 = o0 + (long)K * 3;
-  for (int k = threadIdx.x; k < K; k += 256) {
-    const bool iscl = (long long)k == cl, isbg = k == bg;
-    const long long lab = (iscl ? c[0] : 0) + (isbg ? per - c[0] : 0);
-    o0[3 * k + 0] = (iscl ? c[1] : 0) + (isbg ? c[2] : 0);
-    o0[3 * k + 1] = (long long)atab[(long)b * K + k] + ((iscl && !isbg) ? c[3] : 0) + (isbg ? c[4] : 0);
-    o0[3 * k + 2] = lab;
-    // the ceiling predicts cl where ts, K-1 elsewhere: with cl == K-1 every pixel is predicted, labelled and right in that one row
-    o1[3 * k + 0] = (iscl && isbg) ? per : (iscl ? c[6] : 0) + (isbg ? c[7] : 0);
-    o1[3 * k + 1] = (iscl ? c[5] : 0) + (isbg ? per - c[5] : 0);
-    o1[3 * k + 2] = lab;
-  }
-}
-// trim[b, i, 0..3) = (total, cls_ok, bin_ok) of band i = the buckets 0 .. i of image b's records summed; one workgroup per image
-__global__ __launch_bounds__(256) void unwarp_trim_finalize_kernel(const int* __restrict__ trec, long long* __restrict__ trim,
-                                                                   int blocks_per_image, int D) {
-  constexpr int G = 256 / TRIM_REC;                    // record rows in flight: thread (g, q) sums field q of rows g, g + G, ...
-  __shared__ long long red[G][TRIM_REC];
-  const int b = blockIdx.x, q = threadIdx.x % TRIM_REC, g = threadIdx.x / TRIM_REC;
-  if (g < G) {
-    long long s = 0;
-    for (int j = g; j < blocks_per_image; j += G) s += trec[((long)b * blocks_per_image + j) * TRIM_REC + q];
-    red[g][q] = s;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < 3 * (D + 1)) {
-    const int i = threadIdx.x / 3, f = threadIdx.x % 3;
-    long long c = 0;
-    for (int k = 0; k <= i; ++k)
-      for (int r = 0; r < G; ++r) c += red[r][k * 3 + f];
-    trim[((long)b * (D + 1) + i) * 3 + f] = c;
-  }
-}
-// counts[b, 0..6) = the sum of image b's records; one workgroup per image
-__global__ __launch_bounds__(256) void unwarp_count_finalize_kernel(const int* __restrict__ rec, long long* __restrict__ counts,
-                                                                    int blocks_per_image) {
-  __shared__ long long red[16];
-  const int b = blockIdx.x;
-  const int4* r = reinterpret_cast<const int4*>(rec + (long)b * blocks_per_image * UACC_REC);
-  long long c[6] = {0, 0, 0, 0, 0, 0};
-  for (int j = threadIdx.x; j < blocks_per_image; j += 256) {
-    const int4 lo = r[2 * j], hi = r[2 * j + 1];
-    c[0] += lo.x; c[1] += lo.y; c[2] += lo.z; c[3] += lo.w; c[4] += hi.x; c[5] += hi.y;
-  }
-  for (int q = 0; q < 6; ++q) {
-    const long long s = block_sum<long long>(c[q], red);
-    if (threadIdx.x == 0) counts[(long)b * 6 + q] = s;
-  }
-}
-// acc[0..4) = acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg: seg_loss_finalize_kernel's arithmetic (head_loss.hip) on the integer counts
-__global__ __launch_bounds__(256) void unwarp_accuracy_kernel(const long long* __restrict__ counts, float* __restrict__ acc, int B) {
-  __shared__ double img[4][16];
-  double a[4] = {0, 0, 0, 0};
-  for (int b = threadIdx.x; b < B; b += blockDim.x) {
-    const long long* c = counts + (long)b * 6;
-    const float ufg = (float)c[2] + 1e-10f, ubg = (float)c[5] + 1e-10f;
-    const float cls_fg = (float)c[0] / ufg, bin_fg = (float)c[1] / ufg, cls_bg = (float)c[3] / ubg, bin_bg = (float)c[4] / ubg;
-    a[0] += cls_fg; a[1] += bin_fg; a[2] += cls_fg * 0.5f + cls_bg * 0.5f; a[3] += bin_fg * 0.5f + bin_bg * 0.5f;
-  }
-  for (int j = 0; j < 4; ++j) a[j] = block_sum<double>(a[j], img[j]);
-  if (threadIdx.x < 4) {
-    const int j = threadIdx.x;
-    acc[j] = (float)((j == 0 ? a[0] : j == 1 ? a[1] : j == 2 ? a[2] : a[3]) / (double)B);
-  }
-}
-
-// ---- trimap bands: which band of width 1, 2, 4 .. 2^D around the label's boundary a pixel lies in (eval.py:41-67) -------------------
-// The reference dilates PIL's FIND_EDGES of the label 2^i times with scipy's cross element: an L1 distance threshold.  Here: seed =
-// background pixel (t = (long)y == 0) with a foreground 8-neighbour (outside the image counts as background; with `frame` every
-// background pixel of the outer ring is a seed, PIL copying the ring through unfiltered), d = L1 distance to the nearest seed, band =
-// the smallest i with d <= 2^i, 255 if none.  The L1 distance separates: a row pass, then a column pass over its result.  Only
-// d <= 2^D matters, so both passes keep bytes capped at 2^D + 1 and look no further than 2^D: a tile with that halo needs no carry.
-// Inside a tile the 1-D pass is D + 1 doubling steps f[j] = min(f[j], f[j -+ s] + s), s = 1, 2 .. 2^D: a run of steps costs at least the
-// offset it covers and the binary digits of an offset cost exactly it, so after them f[j] = min over |o| < 2^(D+1) of g[j+o] + |o|,
-// exact; what a step reads from beyond the tile is missing, which only ever leaves an upper bound standing beside the exact one.
-constexpr int TRI_MAX_D = 7;
-constexpr int TRI_MAX_HALO = 1 << TRI_MAX_D;
-constexpr int TRI_RG = 8;                              // row pass: rows per workgroup (ten rows of y read for eight written)
-constexpr int TRI_SEG = 1024;                          // row pass: columns per workgroup
-constexpr int TRI_MAX_HW = TRI_MAX_HALO / 64 + 1;      // row pass: 64-column words of halo on either side (64 * words > 2^D)
-constexpr int TRI_NWORDS = TRI_SEG / 64 + 2 * TRI_MAX_HW;
-constexpr int TRI_CW = 64;                             // column pass: columns per workgroup (sixteen 4-byte words a row)
-constexpr int TRI_CH = 128;                            // column pass: rows per workgroup
-constexpr int TRI_FAR = 1 << 20;
-// row pass: inter[b, v, u] (row pitch P, a multiple of 4) = min(2^D + 1, distance along row v to the nearest seed).  A row is a string
-// of bits, 64 columns a word: a wave's ballot makes a word of foreground bits from one coalesced read of y, the seed rule is shifts
-// and ORs of three rows' words, and a pixel's distance is a count of leading / trailing zeros from its bit.
-__global__ __launch_bounds__(256) void trimap_row_kernel(const float* __restrict__ y, unsigned char* __restrict__ inter, int Hs, int Ws, int P,
-                                                         int D, int frame, int rgs, int segs) {
-  __shared__ unsigned long long fgw[TRI_RG + 2][TRI_NWORDS];
-  __shared__ unsigned long long sdw[TRI_RG][TRI_NWORDS];
-  const int seg = blockIdx.x % segs, rg = (blockIdx.x / segs) % rgs, b = blockIdx.x / (segs * rgs);
-  const int halo = 1 << D, cap = halo + 1, hw = halo / 64 + 1;
-  const int segw = min(TRI_SEG, Ws - seg * TRI_SEG), nwords = (segw + 63) / 64 + 2 * hw;
-  const int x0 = seg * TRI_SEG - 64 * hw, v0 = rg * TRI_RG;     // bit j of word k of a row is image column x0 + 64 k + j
-  const int rows = min(TRI_RG, Hs - v0);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const float* yb = y + (long)b * Hs * Ws;
-  for (int it = wave; it < (rows + 2) * nwords; it += 4) {
-    const int r = it / nwords, k = it - r * nwords;
-    const int v = v0 - 1 + r, u = x0 + 64 * k + lane;
-    bool f = false;
-    if (v >= 0 && v < Hs && u >= 0 && u < Ws) f = (long long)yb[(long)v * Ws + u] != 0;
-    const unsigned long long bits = __ballot(f);
-    if (lane == 0) fgw[r][k] = bits;
-  }
-  __syncthreads();
-  for (int it = threadIdx.x; it < rows * nwords; it += 256) {
-    const int r = it / nwords, k = it - r * nwords;
-    const int v = v0 + r, ulo = x0 + 64 * k;
-    const unsigned long long a = fgw[r][k] | fgw[r + 1][k] | fgw[r + 2][k];
-    const unsigned long long al = k > 0 ? fgw[r][k - 1] | fgw[r + 1][k - 1] | fgw[r + 2][k - 1] : 0ull;
-    const unsigned long long ar = k + 1 < nwords ? fgw[r][k + 1] | fgw[r + 1][k + 1] | fgw[r + 2][k + 1] : 0ull;
-    // the region's two outermost columns miss a neighbour; they lie 64 * hw > 2^D columns from the segment and cannot matter
-    unsigned long long take = a | a << 1 | al >> 63 | a >> 1 | ar << 63;
-    if (frame) {
-      if (v == 0 || v == Hs - 1) take = ~0ull;
-      if (ulo <= 0 && 0 < ulo + 64) take |= 1ull << (0 - ulo);
-      if (ulo <= Ws - 1 && Ws - 1 < ulo + 64) take |= 1ull << (Ws - 1 - ulo);
-    }
-    const int lo = max(0, -ulo), hi = min(64, Ws - ulo);          // the word's columns inside the image: bits lo .. hi - 1
-    unsigned long long in = 0ull;
-    if (hi > lo) in = (hi - lo == 64 ? ~0ull : (1ull << (hi - lo)) - 1ull) << lo;
-    sdw[r][k] = ~fgw[r + 1][k] & take & in;
-  }
-  __syncthreads();
-  // four columns a thread and a store; the pitch's padding takes whatever lies beside the row, and the column pass never shows it
-  const int words = (segw + 3) >> 2;
-  if ((int)threadIdx.x >= words) return;
-  const int c0 = 64 * hw + 4 * (int)threadIdx.x, w = c0 >> 6;
-  for (int r = 0; r < rows; ++r) {
-    const unsigned long long* s = sdw[r];
-    const unsigned long long cw = w < nwords ? s[w] : 0ull;
-    int before = TRI_FAR, after = TRI_FAR;                       // from bit 0 / bit 63 of word w to the nearest seed in the words beside it
-    for (int k = 1; k <= hw; ++k)
-      if (w - k >= 0 && s[w - k] != 0ull) { before = 64 * (k - 1) + 1 + __builtin_clzll(s[w - k]); break; }
-    for (int k = 1; k <= hw; ++k)
-      if (w + k < nwords && s[w + k] != 0ull) { after = 64 * (k - 1) + 1 + __builtin_ctzll(s[w + k]); break; }
-    unsigned int wd = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int bb = (c0 & 63) + q;
-      const unsigned long long ml = cw & (~0ull >> (63 - bb)), mr = cw & (~0ull << bb);
-      const int dl = ml != 0ull ? bb - (63 - __builtin_clzll(ml)) : bb + before;
-      const int dr = mr != 0ull ? __builtin_ctzll(mr) - bb : 63 - bb + after;
-      wd |= (unsigned int)min(min(dl, dr), cap) << (8 * q);
-    }
-    reinterpret_cast<unsigned int*>(inter + ((long)b * Hs + v0 + r) * P + seg * TRI_SEG)[threadIdx.x] = wd;
-  }
-}
-// column pass: band[b, v, u] from min(2^D + 1, min over dv of inter[b, v + dv, u] + |dv|); a thread holds four neighbouring columns
-__global__ __launch_bounds__(256) void trimap_col_kernel(const unsigned char* __restrict__ inter, unsigned char* __restrict__ band, int Hs, int Ws,
-                                                         int P, int D, int vec, int rts, int cts) {
-  extern __shared__ unsigned int tri_dist[];                   // [2][TRI_CH + 2 * 2^D][TRI_CW / 4]: sized by the launch, for occupancy at small D
-  constexpr int WPR = TRI_CW / 4;
-  const int ct = blockIdx.x % cts, rt = (blockIdx.x / cts) % rts, b = blockIdx.x / (cts * rts);
-  const int halo = 1 << D, cap = halo + 1, nrmax = TRI_CH + 2 * halo;
-  const int v0 = rt * TRI_CH, th = min(TRI_CH, Hs - v0), nr = th + 2 * halo;
-  const int wl = threadIdx.x % WPR, rl = threadIdx.x / WPR;      // this thread's word of a row, and its first row
-  const int u0 = ct * TRI_CW + 4 * wl;
-  auto dist = [&](int buf, int r) -> unsigned int& { return tri_dist[(buf * nrmax + r) * WPR + wl]; };
-  const bool live = u0 < P;
-  const unsigned char* ib = inter + (long)b * Hs * P;
-  bool seen = false;
-#pragma unroll 4
-  for (int r = rl; r < nr; r += 256 / WPR) {
-    const int v = v0 - halo + r;
-    unsigned int wd = (unsigned int)cap * 0x01010101u;           // outside the image: no seed
-    if (live && v >= 0 && v < Hs) wd = *reinterpret_cast<const unsigned int*>(ib + (long)v * P + u0);
-    dist(0, r) = wd;
-    seen |= live && wd != (unsigned int)cap * 0x01010101u;
-  }
-  unsigned char* bb = band + (long)b * Hs * Ws;
-  auto store = [&](int v, unsigned int o) {
-    if (vec) {
-      *reinterpret_cast<unsigned int*>(bb + (long)v * Ws + u0) = o;
-    } else {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        if (u0 + q < Ws) bb[(long)v * Ws + u0 + q] = (unsigned char)(o >> (8 * q));
-    }
-  };
-  if (!__syncthreads_or(seen)) {                                 // no seed within 2^D of any row this tile read: in no band
-    if (live)
-      for (int r = halo + rl; r < halo + th; r += 256 / WPR) store(v0 - halo + r, 0xFFFFFFFFu);
-    return;
-  }
-  int cur = 0;
-  for (int s = 1; s <= halo; s <<= 1) {
-    for (int r = rl; r < nr; r += 256 / WPR) {
-      const unsigned int a = dist(cur, r);
-      const unsigned int up = r >= s ? dist(cur, r - s) : 0xFFFFFFFFu, dn = r + s < nr ? dist(cur, r + s) : 0xFFFFFFFFu;
-      unsigned int wd = 0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int m = min(min((int)((a >> (8 * q)) & 255u), cap), min((int)((up >> (8 * q)) & 255u), (int)((dn >> (8 * q)) & 255u)) + s);
-        wd |= (unsigned int)m << (8 * q);
-      }
-      dist(cur ^ 1, r) = wd;
-    }
-    __syncthreads();
-    cur ^= 1;
-  }
-  if (!live) return;
-  for (int r = halo + rl; r < halo + th; r += 256 / WPR) {
-    const unsigned int wd = dist(cur, r);
-    unsigned int o = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int d = (int)((wd >> (8 * q)) & 255u);
-      const unsigned int i = d > halo ? 255u : d <= 1 ? 0u : (unsigned int)(32 - __clz(d - 1));
-      o |= i << (8 * q);
-    }
-    store(v0 - halo + r, o);
   }
 }
 
@@ -1816,239 +1057,6 @@ int fs_grid_sample_bwd_input(const float* gout, const float* grid, float* dx, in
   hipError_t e = hipMemsetAsync(dx, 0, sizeof(float) * (size_t)B * C * H * W, stream);
   if (e != hipSuccess) return (int)e;
   hipLaunchKernelGGL(grid_sample_bwd_input_kernel, dim3(cdiv((long)B * h * w, 256)), dim3(256), 0, stream, gout, grid, dx, B, C, H, W, h, w, nhwc);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
-int fs_inverse_grid(const float* grid, int* owner, float* grid_inv, int B, int h, int w, int Hs, int Ws, hipStream_t stream) {
-  FS_REQUIRE(grid && owner && grid_inv && B > 0 && h > 0 && w > 0 && Hs > 0 && Ws > 0 && (long)h * w < 2147483647L);
-  const long n = (long)B * Hs * Ws;
-  hipError_t e = hipMemsetAsync(owner, 0xFF, sizeof(int) * (size_t)n, stream);      // -1
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(inverse_owner_kernel, dim3(cdiv((long)B * h * w, 256)), dim3(256), 0, stream, grid, owner, B, h * w, Hs, Ws);
-  FS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(inverse_grid_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, owner, grid_inv, n, h, w);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
-int fs_fill_nearest(float* vals, const int* owner, int* scratch, int B, int C, int Hs, int Ws, hipStream_t stream) {
-  FS_REQUIRE(vals && owner && scratch && B > 0 && C > 0 && Hs > 0 && Ws > 0 && (long)Hs * Ws < 2147483647L);
-  const long per = (long)Hs * Ws, n = (long)B * per;
-  int* rowx = scratch;          // [B*Hs*Ws]
-  int* src = scratch + n;       // [B*Hs*Ws]
-  FS_REQUIRE(Ws <= 16384);     // one row of column indices in LDS
-  hipLaunchKernelGGL(fill_row_nearest_kernel, dim3((unsigned)((long)B * Hs)), dim3(256), (size_t)Ws * sizeof(int), stream, owner, rowx, Ws);
-  FS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(fill_col_nearest_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, rowx, src, n, Hs, Ws);
-  FS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(fill_copy_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, vals, owner, src, C, per, n);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
-long fs_unwarp_labels_scratch_ints(int B, int h, int w, int Hs, int Ws) {
-  return (B > 0 && h > 0 && w > 0 && Hs > 0 && Ws > 0) ? 2L * B * Hs * Ws + (long)B * ((long)h * w + 1) : 0;
-}
-
-int fs_unwarp_labels(const float* cls, const float* m, const float* grid, long long* labels, unsigned char* hole, int* scratch, int B, int K,
-                     int h, int w, int Hs, int Ws, hipStream_t stream) {
-  FS_REQUIRE(cls && m && grid && labels && scratch && B > 0 && K >= 2 && K <= UNWARP_MAX_K && h > 0 && w > 0 && Hs > 0 && Ws > 0);
-  FS_REQUIRE(Ws <= 16384 && (long)h * w < 2147483647L && (long)Hs * Ws < 2147483647L);      // one row in LDS; int pixel / point indices
-  const long per = (long)Hs * Ws, n = (long)B * per;
-  const long bpi = ((long)h * w + 1 + 255) / 256;
-  const long threads_max = 4294967295L - 255;          // every launch below: fewer than 2^32 work-items
-  FS_REQUIRE(n <= threads_max && (long)B * Hs * 256 <= threads_max && (long)B * bpi * 256 <= threads_max);
-  int* owner = scratch;         // [B*Hs*Ws]
-  int* rowx = scratch + n;      // [B*Hs*Ws]
-  int* dec = scratch + 2 * n;   // [B*(h*w+1)]
-  hipLaunchKernelGGL(unwarp_decide_kernel, dim3((unsigned)(B * bpi)), dim3(256), 0, stream, cls, m, dec, K, h, w, (int)bpi);
-  FS_LAUNCH_CHECK();
-  hipError_t e = hipMemsetAsync(owner, 0xFF, sizeof(int) * (size_t)n, stream);      // -1
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(inverse_owner_kernel, dim3(cdiv((long)B * h * w, 256)), dim3(256), 0, stream, grid, owner, B, h * w, Hs, Ws);
-  FS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(fill_row_nearest_kernel, dim3((unsigned)((long)B * Hs)), dim3(256), (size_t)Ws * sizeof(int), stream, owner, rowx, Ws);
-  FS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(unwarp_label_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, owner, rowx, dec, labels, hole, n, Hs, Ws, h * w);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
-// scratch of fs_unwarp_accuracy: fs_unwarp_labels' three maps, then (16-byte aligned) one record per workgroup of the count pass
-static long unwarp_accuracy_rec_offset(int B, int h, int w, int Hs, int Ws) {
-  return (2L * B * Hs * Ws + (long)B * ((long)h * w + 1) + 3) & ~3L;
-}
-long fs_unwarp_accuracy_scratch_ints(int B, int h, int w, int Hs, int Ws) {
-  if (!(B > 0 && h > 0 && w > 0 && Hs > 0 && Ws > 0)) return 0;
-  const long bpi = ((long)Hs * Ws + UACC_CHUNK - 1) / UACC_CHUNK;
-  return unwarp_accuracy_rec_offset(B, h, w, Hs, Ws) + (long)B * bpi * UACC_REC;
-}
-
-// fs_unwarp_accuracy's launches; with band / trec / trim (all or none) the count pass is the bucketing one and trim is summed after it;
-// with areas / arec / atab (all or none) it is the AREA one: class_area_sampled_kernel tags dec and writes areas[:,2] before it, atab
-// is zeroed for it and unwarp_area_finalize_kernel writes areas[:,0:2] after it
-extern "C++" {
-template <bool AREA>
-static void unwarp_count_launch(bool vec, long wgs, hipStream_t stream, const int* owner, const int* rowx, const int* dec, const float* y,
-                                const long long* cls_label, long long* labels, int* rec, int Hs, int Ws, int hw, int K, int cpi,
-                                const unsigned char* band, int* trec, int* arec, int* atab) {
-  if (band == nullptr) {
-    if (vec)
-      hipLaunchKernelGGL((unwarp_count_kernel<true, false, AREA>), dim3((unsigned)wgs), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
-                         rec, Hs, Ws, hw, K, cpi, nullptr, nullptr, arec, atab);
-    else
-      hipLaunchKernelGGL((unwarp_count_kernel<false, false, AREA>), dim3((unsigned)wgs), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
-                         rec, Hs, Ws, hw, K, cpi, nullptr, nullptr, arec, atab);
-  } else if (vec && ((uintptr_t)band & 3) == 0) {
-    hipLaunchKernelGGL((unwarp_count_kernel<true, true, AREA>), dim3((unsigned)wgs), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
-                       rec, Hs, Ws, hw, K, cpi, band, trec, arec, atab);
-  } else {
-    hipLaunchKernelGGL((unwarp_count_kernel<false, true, AREA>), dim3((unsigned)wgs), dim3(256), 0, stream, owner, rowx, dec, y, cls_label, labels,
-                       rec, Hs, Ws, hw, K, cpi, band, trec, arec, atab);
-  }
-}
-}  // extern "C++"
-static int unwarp_accuracy_launch(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label,
-                                  long long* counts, float* acc, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws,
-                                  const unsigned char* band, int* trec, long long* trim, int D, long long* areas, int* arec, int* atab,
-                                  hipStream_t stream) {
-  FS_REQUIRE(cls && m && grid && y && cls_label && counts && acc && scratch && B > 0 && K >= 2 && K <= UNWARP_MAX_K && h > 0 && w > 0 &&
-             Hs > 0 && Ws > 0);
-  // one row in LDS; int pixel / point indices, the count pass's included (a workgroup's last trip may start up to a chunk past the end)
-  FS_REQUIRE(Ws <= 16384 && (long)h * w < 2147483647L && (long)Hs * Ws < 2147483647L - UACC_CHUNK);
-  const long per = (long)Hs * Ws, n = (long)B * per;
-  const long bpi = ((long)h * w + 1 + 255) / 256;
-  const long cpi = (per + UACC_CHUNK - 1) / UACC_CHUNK;                 // count-pass workgroups (= records) per image
-  const long threads_max = 4294967295L - 255;          // every launch below: fewer than 2^32 work-items
-  FS_REQUIRE(n <= threads_max && (long)B * Hs * 256 <= threads_max && (long)B * bpi * 256 <= threads_max && (long)B * cpi * 256 <= threads_max);
-  int* owner = scratch;         // [B*Hs*Ws]
-  int* rowx = scratch + n;      // [B*Hs*Ws]
-  int* dec = scratch + 2 * n;   // [B*(h*w+1)]
-  int* rec = scratch + unwarp_accuracy_rec_offset(B, h, w, Hs, Ws);     // [B*cpi][UACC_REC]
-  FS_REQUIRE(((uintptr_t)scratch & 15) == 0);          // the records are stored and read 16 bytes at a time
-  hipLaunchKernelGGL(unwarp_decide_kernel, dim3((unsigned)(B * bpi)), dim3(256), 0, stream, cls, m, dec, K, h, w, (int)bpi);
-  FS_LAUNCH_CHECK();
-  if (areas != nullptr) {
-    hipLaunchKernelGGL(class_area_sampled_kernel, dim3((unsigned)B), dim3(256), 0, stream, cls, m, grid, y, cls_label, dec, areas, K, h * w, Hs, Ws);
-    FS_LAUNCH_CHECK();
-    const hipError_t ea = hipMemsetAsync(atab, 0, sizeof(int) * (size_t)B * K, stream);
-    if (ea != hipSuccess) return (int)ea;
-  }
-  hipError_t e = hipMemsetAsync(owner, 0xFF, sizeof(int) * (size_t)n, stream);      // -1
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(inverse_owner_kernel, dim3(cdiv((long)B * h * w, 256)), dim3(256), 0, stream, grid, owner, B, h * w, Hs, Ws);
-  FS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(fill_row_nearest_kernel, dim3((unsigned)((long)B * Hs)), dim3(256), (size_t)Ws * sizeof(int), stream, owner, rowx, Ws);
-  FS_LAUNCH_CHECK();
-  const bool vec = Ws % 4 == 0 && ((uintptr_t)y & 15) == 0 && ((uintptr_t)labels & 15) == 0;
-  if (areas == nullptr)
-    unwarp_count_launch<false>(vec, B * cpi, stream, owner, rowx, dec, y, cls_label, labels, rec, Hs, Ws, h * w, K, (int)cpi, band, trec, nullptr, nullptr);
-  else
-    unwarp_count_launch<true>(vec, B * cpi, stream, owner, rowx, dec, y, cls_label, labels, rec, Hs, Ws, h * w, K, (int)cpi, band, trec, arec, atab);
-  FS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(unwarp_count_finalize_kernel, dim3((unsigned)B), dim3(256), 0, stream, rec, counts, (int)cpi);
-  FS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(unwarp_accuracy_kernel, dim3(1), dim3(256), 0, stream, counts, acc, B);
-  FS_LAUNCH_CHECK();
-  if (band != nullptr) {
-    hipLaunchKernelGGL(unwarp_trim_finalize_kernel, dim3((unsigned)B), dim3(256), 0, stream, trec, trim, (int)cpi, D);
-    FS_LAUNCH_CHECK();
-  }
-  if (areas != nullptr) {
-    hipLaunchKernelGGL(unwarp_area_finalize_kernel, dim3((unsigned)B), dim3(256), 0, stream, arec, atab, cls_label, areas, K, (int)cpi, (long long)per);
-    FS_LAUNCH_CHECK();
-  }
-  return FS_OK;
-}
-
-int fs_unwarp_accuracy(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
-                       float* acc, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws, hipStream_t stream) {
-  return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                                nullptr, stream);
-}
-
-// include/fovealseg.h: ints of scratch fs_trimap_bands needs (the row pass's byte map, its rows pitched to four bytes)
-static long trimap_pitch(int Ws) { return ((long)Ws + 3) & ~3L; }
-long fs_trimap_bands_scratch_ints(int B, int Hs, int Ws) { return (B > 0 && Hs > 0 && Ws > 0) ? (long)B * Hs * trimap_pitch(Ws) / 4 : 0; }
-
-int fs_trimap_bands(const float* y, unsigned char* band, int* scratch, int B, int Hs, int Ws, int D, int frame, hipStream_t stream) {
-  FS_REQUIRE(y && band && scratch && B > 0 && Hs > 0 && Ws > 0 && D >= 0 && D <= TRI_MAX_D && (frame == 0 || frame == 1));
-  const long P = trimap_pitch(Ws);
-  const long rgs = cdiv(Hs, TRI_RG), segs = cdiv(Ws, TRI_SEG), rts = cdiv(Hs, TRI_CH), cts = cdiv(P, TRI_CW);
-  FS_REQUIRE(P < 2147483647L && (long)B * rgs * segs <= 16777215L && (long)B * rts * cts <= 16777215L);      // fewer than 2^32 work-items
-  unsigned char* inter = reinterpret_cast<unsigned char*>(scratch);
-  hipLaunchKernelGGL(trimap_row_kernel, dim3((unsigned)(B * rgs * segs)), dim3(256), 0, stream, y, inter, Hs, Ws, (int)P, D, frame, (int)rgs,
-                     (int)segs);
-  FS_LAUNCH_CHECK();
-  const int vec = Ws % 4 == 0 && ((uintptr_t)band & 3) == 0;
-  hipLaunchKernelGGL(trimap_col_kernel, dim3((unsigned)(B * rts * cts)), dim3(256), 2 * (TRI_CH + (2 << D)) * TRI_CW, stream, inter, band, Hs, Ws, (int)P, D, vec, (int)rts,
-                     (int)cts);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
-// scratch of fs_unwarp_trimap (ints): fs_unwarp_accuracy's, then the bucket records of the count pass, the band bytes, fs_trimap_bands' own
-static long unwarp_trimap_trec_offset(int B, int h, int w, int Hs, int Ws) { return (fs_unwarp_accuracy_scratch_ints(B, h, w, Hs, Ws) + 3) & ~3L; }
-static long unwarp_trimap_band_offset(int B, int h, int w, int Hs, int Ws) {
-  const long cpi = ((long)Hs * Ws + UACC_CHUNK - 1) / UACC_CHUNK;
-  return unwarp_trimap_trec_offset(B, h, w, Hs, Ws) + (long)B * cpi * TRIM_REC;
-}
-static long unwarp_trimap_inter_offset(int B, int h, int w, int Hs, int Ws) {
-  return unwarp_trimap_band_offset(B, h, w, Hs, Ws) + ((((long)B * Hs * Ws + 3) / 4 + 3) & ~3L);
-}
-long fs_unwarp_trimap_scratch_ints(int B, int h, int w, int Hs, int Ws) {
-  if (!(B > 0 && h > 0 && w > 0 && Hs > 0 && Ws > 0)) return 0;
-  return unwarp_trimap_inter_offset(B, h, w, Hs, Ws) + fs_trimap_bands_scratch_ints(B, Hs, Ws);
-}
-
-int fs_unwarp_trimap(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
-                     float* acc, long long* trim, long long* labels, int* scratch, int B, int K, int h, int w, int Hs, int Ws, int D, int frame,
-                     hipStream_t stream) {
-  FS_REQUIRE(cls && m && grid && y && cls_label && counts && acc && trim && scratch && B > 0 && K >= 2 && K <= UNWARP_MAX_K && h > 0 && w > 0 &&
-             Hs > 0 && Ws > 0 && D >= 0 && D <= TRI_MAX_D && (frame == 0 || frame == 1));
-  FS_REQUIRE(Ws <= 16384 && (long)h * w < 2147483647L && (long)Hs * Ws < 2147483647L - UACC_CHUNK && ((uintptr_t)scratch & 15) == 0);
-  unsigned char* band = reinterpret_cast<unsigned char*>(scratch + unwarp_trimap_band_offset(B, h, w, Hs, Ws));
-  const int r = fs_trimap_bands(y, band, scratch + unwarp_trimap_inter_offset(B, h, w, Hs, Ws), B, Hs, Ws, D, frame, stream);
-  if (r != FS_OK) return r;
-  return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, band,
-                                scratch + unwarp_trimap_trec_offset(B, h, w, Hs, Ws), trim, D, nullptr, nullptr, nullptr, stream);
-}
-
-// scratch of fs_unwarp_class_areas (ints): fs_unwarp_trimap's (trim or not), then (16-byte aligned) the hot-class records of the count
-// pass, one per workgroup, then atab (B, K): the SUMS over each image's workgroups of the other predicted classes' pixels
-static long unwarp_areas_arec_offset(int B, int h, int w, int Hs, int Ws) { return (fs_unwarp_trimap_scratch_ints(B, h, w, Hs, Ws) + 3) & ~3L; }
-static long unwarp_areas_atab_offset(int B, int h, int w, int Hs, int Ws) {
-  const long cpi = ((long)Hs * Ws + UACC_CHUNK - 1) / UACC_CHUNK;
-  return unwarp_areas_arec_offset(B, h, w, Hs, Ws) + (long)B * cpi * AREA_REC;
-}
-long fs_unwarp_class_areas_scratch_ints(int B, int K, int h, int w, int Hs, int Ws) {
-  if (!(B > 0 && K > 0 && h > 0 && w > 0 && Hs > 0 && Ws > 0)) return 0;
-  return unwarp_areas_atab_offset(B, h, w, Hs, Ws) + (long)B * K;
-}
-
-int fs_unwarp_class_areas(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
-                          float* acc, long long* areas, long long* trim, long long* labels, int* scratch, int B, int K, int h, int w, int Hs,
-                          int Ws, int D, int frame, hipStream_t stream) {
-  FS_REQUIRE(cls && m && grid && y && cls_label && counts && acc && areas && scratch && B > 0 && K >= 2 && K <= UNWARP_MAX_K && h > 0 && w > 0 &&
-             Hs > 0 && Ws > 0);
-  FS_REQUIRE(Ws <= 16384 && (long)h * w < 2147483647L && (long)Hs * Ws < 2147483647L - UACC_CHUNK && ((uintptr_t)scratch & 15) == 0);
-  int* arec = scratch + unwarp_areas_arec_offset(B, h, w, Hs, Ws);
-  int* atab = scratch + unwarp_areas_atab_offset(B, h, w, Hs, Ws);
-  if (trim == nullptr)
-    return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, nullptr, nullptr, nullptr, 0, areas,
-                                  arec, atab, stream);
-  FS_REQUIRE(D >= 0 && D <= TRI_MAX_D && (frame == 0 || frame == 1));
-  unsigned char* band = reinterpret_cast<unsigned char*>(scratch + unwarp_trimap_band_offset(B, h, w, Hs, Ws));
-  const int r = fs_trimap_bands(y, band, scratch + unwarp_trimap_inter_offset(B, h, w, Hs, Ws), B, Hs, Ws, D, frame, stream);
-  if (r != FS_OK) return r;
-  return unwarp_accuracy_launch(cls, m, grid, y, cls_label, counts, acc, labels, scratch, B, K, h, w, Hs, Ws, band,
-                                scratch + unwarp_trimap_trec_offset(B, h, w, Hs, Ws), trim, D, areas, arec, atab, stream);
-}
-
-int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, hipStream_t stream) {
-  FS_REQUIRE(grid && u && v && n > 0 && H > 0 && W > 0);
-  hipLaunchKernelGGL(inverse_index_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, grid, u, v, n, H, W);
   FS_LAUNCH_CHECK();
   return FS_OK;
 }

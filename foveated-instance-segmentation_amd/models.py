@@ -277,19 +277,9 @@ class DeformSegmentationModule(nn.Module):
         if seg_label.shape[0] != img.shape[0] or cls_label.shape[0] != img.shape[0]:
             raise ValueError(f"seg_label {tuple(seg_label.shape)} and cls_label {tuple(cls_label.shape)} must have img's batch size {img.shape[0]}")
         cls, m, grid, _ = self._head_parts(img, focus, label_size, "evaluate")
-        if class_areas:
-            out = ops.unwarp_class_areas(cls, m, grid, seg_label, cls_label, dia_factor=trimap, frame=trimap_frame, return_labels=return_labels)
-            counts, acc = out[0], out[1]
-            return (acc[0], acc[1], acc[2], acc[3], counts) + tuple(reversed(out[3:])) + (out[2],)
-        if trimap is None:
-            out = ops.unwarp_accuracy(cls, m, grid, seg_label, cls_label, return_labels=return_labels)
-            counts, acc = out[0], out[1]
-            res = (acc[0], acc[1], acc[2], acc[3], counts)
-            return res + (out[2],) if return_labels else res
-        out = ops.unwarp_trimap(cls, m, grid, seg_label, cls_label, dia_factor=trimap, frame=trimap_frame, return_labels=return_labels)
-        counts, acc = out[0], out[1]
-        res = (acc[0], acc[1], acc[2], acc[3], counts)
-        return res + (out[3], out[2]) if return_labels else res + (out[2],)
+        counts, acc, areas, trim, labels = ops.unwarp_count(cls, m, grid, seg_label, cls_label, dia_factor=trimap, frame=trimap_frame,
+                                                            areas=class_areas, return_labels=return_labels)
+        return (acc[0], acc[1], acc[2], acc[3], counts) + tuple(t for t in (labels, trim, areas) if t is not None)
 
     def forward(self, feed_dict, *, writer=None, segSize=None, F_Xlr_acc_map=False, count=None, epoch=None,
                 feed_dict_info=None, feed_batch_count=None, cur_iter=None, is_inference=False, rank=None):

@@ -1484,13 +1484,13 @@ def unwarp_labels(cls, m, grid, Hs, Ws):
     return labels, hole
 
 
-def unwarp_accuracy(cls, m, grid, y, cls_label, return_labels=False):
-    """The four full-resolution accuracies of MODEL.upsample for the C1 head (no autograd), without the (B,K,Hs,Ws) prediction, a class
-    map or a ground-truth tensor: the predicted class of a pixel is `unwarp_labels`'s, its ground truth `t = y.long()`,
-    `t * cls_label + (1 - t) * (K - 1)`, and the gather pass counts instead of storing (fs_unwarp_accuracy).  cls (B,K), m (B,h,w),
-    grid (B,h,w,2) as for unwarp_labels; y (B,Hs,Ws) or (B,1,Hs,Ws) the label mask at the output size; cls_label (B,) or (B,1).
-    Returns (counts (B,6) int64 = cls_fg, bin_fg, union_fg, cls_bg, bin_bg, union_bg per image, acc (4,) fp32 = acc, acc_bin_fg,
-    acc_cls_fbg, acc_bin_fbg as SegLoss's out[3:7]) and, with return_labels, the (B,Hs,Ws) int64 class map of unwarp_labels."""
+def unwarp_count(cls, m, grid, y, cls_label, dia_factor=None, frame=True, areas=False, return_labels=False):
+    """The checks, allocations and call that unwarp_accuracy, unwarp_trimap and unwarp_class_areas share; models.py's evaluate() calls
+    it directly.  Internal to the package: the documented ops are those three.  dia_factor=None: no trimap.  The entry point is the
+    smallest that counts what is asked for: fs_unwarp_class_areas with areas, else fs_unwarp_trimap with a trimap, else
+    fs_unwarp_accuracy.  Returns the five-tuple (counts, acc, areas, trim, labels) in this order, None where not asked for."""
+    with_trim = dia_factor is not None
+    D, fr = _trimap_args(dia_factor, frame) if with_trim else (0, 0)
     B, K = cls.shape
     _, h, w, _ = grid.shape
     if tuple(m.shape) != (B, h, w):
@@ -1504,13 +1504,34 @@ def unwarp_accuracy(cls, m, grid, y, cls_label, return_labels=False):
         cls_label = cls_label[:, 0]
     if tuple(cls_label.shape) != (B,):
         raise ValueError(f"cls_label {tuple(cls_label.shape)} must be (B,) or (B, 1) with B = {B}")
-    counts = torch.empty(B, 6, device=cls.device, dtype=torch.int64)
-    acc = torch.empty(4, device=cls.device, dtype=torch.float32)
-    labels = torch.empty(B, Hs, Ws, device=cls.device, dtype=torch.int64) if return_labels else None
-    scratch = torch.empty(hip.query("fs_unwarp_accuracy_scratch_ints", B, h, w, Hs, Ws), device=cls.device, dtype=torch.int32)
-    hip.call("fs_unwarp_accuracy", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()),
-             hip.ptr(y.float().contiguous()), hip.ptr(cls_label.long().contiguous()), hip.ptr(counts), hip.ptr(acc), hip.ptr(labels),
-             hip.ptr(scratch), B, K, h, w, Hs, Ws)
+    dev = cls.device
+    counts = torch.empty(B, 6, device=dev, dtype=torch.int64)
+    acc = torch.empty(4, device=dev, dtype=torch.float32)
+    area = torch.empty(B, 3, K, 3, device=dev, dtype=torch.int64) if areas else None
+    trim = torch.empty(B, D + 1, 3, device=dev, dtype=torch.int64) if with_trim else None
+    labels = torch.empty(B, Hs, Ws, device=dev, dtype=torch.int64) if return_labels else None
+    # (entry point, the dimensions its scratch query takes, its outputs after acc, its arguments after the dimensions)
+    if areas:
+        name, qdims, outs, tail = "fs_unwarp_class_areas", (B, K, h, w, Hs, Ws), (area, trim, labels), (D, fr)
+    elif with_trim:
+        name, qdims, outs, tail = "fs_unwarp_trimap", (B, h, w, Hs, Ws), (trim, labels), (D, fr)
+    else:
+        name, qdims, outs, tail = "fs_unwarp_accuracy", (B, h, w, Hs, Ws), (labels,), ()
+    scratch = torch.empty(hip.query(name + "_scratch_ints", *qdims), device=dev, dtype=torch.int32)
+    hip.call(name, hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(y.float().contiguous()),
+             hip.ptr(cls_label.long().contiguous()), hip.ptr(counts), hip.ptr(acc), *(hip.ptr(t) for t in outs), hip.ptr(scratch),
+             B, K, h, w, Hs, Ws, *tail)
+    return counts, acc, area, trim, labels
+
+
+def unwarp_accuracy(cls, m, grid, y, cls_label, return_labels=False):
+    """The four full-resolution accuracies of MODEL.upsample for the C1 head (no autograd), without the (B,K,Hs,Ws) prediction, a class
+    map or a ground-truth tensor: the predicted class of a pixel is `unwarp_labels`'s, its ground truth `t = y.long()`,
+    `t * cls_label + (1 - t) * (K - 1)`, and the gather pass counts instead of storing (fs_unwarp_accuracy).  cls (B,K), m (B,h,w),
+    grid (B,h,w,2) as for unwarp_labels; y (B,Hs,Ws) or (B,1,Hs,Ws) the label mask at the output size; cls_label (B,) or (B,1).
+    Returns (counts (B,6) int64 = cls_fg, bin_fg, union_fg, cls_bg, bin_bg, union_bg per image, acc (4,) fp32 = acc, acc_bin_fg,
+    acc_cls_fbg, acc_bin_fbg as SegLoss's out[3:7]) and, with return_labels, the (B,Hs,Ws) int64 class map of unwarp_labels."""
+    counts, acc, _, _, labels = unwarp_count(cls, m, grid, y, cls_label, return_labels=return_labels)
     return (counts, acc, labels) if return_labels else (counts, acc)
 
 
@@ -1547,28 +1568,9 @@ def unwarp_trimap(cls, m, grid, y, cls_label, dia_factor=5, frame=True, return_l
     pixels in the band, of those whose predicted class equals the ground truth (the reference's acc_sum) and of those that agree with
     it on foreground versus background.  An image without a boundary seed (a constant label with frame=False, an all-foreground one
     with frame=True) has all-zero rows: the reference divides 0 by 0 there, trimap_from_counts and train.TrimapMeter leave it out."""
-    D, fr = _trimap_args(dia_factor, frame)
-    B, K = cls.shape
-    _, h, w, _ = grid.shape
-    if tuple(m.shape) != (B, h, w):
-        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
-    if y.dim() == 4 and y.shape[1] == 1:
-        y = y[:, 0]
-    if y.dim() != 3 or y.shape[0] != B:
-        raise ValueError(f"y {tuple(y.shape)} must be (B, Hs, Ws) or (B, 1, Hs, Ws) with B = {B}")
-    Hs, Ws = int(y.shape[1]), int(y.shape[2])
-    if cls_label.dim() == 2 and cls_label.shape[1] == 1:
-        cls_label = cls_label[:, 0]
-    if tuple(cls_label.shape) != (B,):
-        raise ValueError(f"cls_label {tuple(cls_label.shape)} must be (B,) or (B, 1) with B = {B}")
-    counts = torch.empty(B, 6, device=cls.device, dtype=torch.int64)
-    acc = torch.empty(4, device=cls.device, dtype=torch.float32)
-    trim = torch.empty(B, D + 1, 3, device=cls.device, dtype=torch.int64)
-    labels = torch.empty(B, Hs, Ws, device=cls.device, dtype=torch.int64) if return_labels else None
-    scratch = torch.empty(hip.query("fs_unwarp_trimap_scratch_ints", B, h, w, Hs, Ws), device=cls.device, dtype=torch.int32)
-    hip.call("fs_unwarp_trimap", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()),
-             hip.ptr(y.float().contiguous()), hip.ptr(cls_label.long().contiguous()), hip.ptr(counts), hip.ptr(acc), hip.ptr(trim),
-             hip.ptr(labels), hip.ptr(scratch), B, K, h, w, Hs, Ws, D, fr)
+    if dia_factor is None:
+        raise TypeError("unwarp_trimap needs dia_factor (0 .. 7); unwarp_accuracy is the op without a trimap")
+    counts, acc, _, trim, labels = unwarp_count(cls, m, grid, y, cls_label, dia_factor, frame, return_labels=return_labels)
     return (counts, acc, trim, labels) if return_labels else (counts, acc, trim)
 
 
@@ -1591,31 +1593,8 @@ def unwarp_class_areas(cls, m, grid, y, cls_label, dia_factor=None, frame=True, 
     ceiling -- the label after the sampler and the nearest un-warp against itself (VAL.y_sampled_reverse, models/models_instance.py:909-918):
     every pixel takes grid_sample_label's value of the grid point that feeds it -- and space 2 the prediction in the sampled space
     (PredAssemble(cls, m).argmax(1) against the sampled ground truth).  A cls_label outside 0 .. K-1 has no lab / inter row."""
-    with_trim = dia_factor is not None
-    D, fr = _trimap_args(dia_factor, frame) if with_trim else (0, 0)
-    B, K = cls.shape
-    _, h, w, _ = grid.shape
-    if tuple(m.shape) != (B, h, w):
-        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
-    if y.dim() == 4 and y.shape[1] == 1:
-        y = y[:, 0]
-    if y.dim() != 3 or y.shape[0] != B:
-        raise ValueError(f"y {tuple(y.shape)} must be (B, Hs, Ws) or (B, 1, Hs, Ws) with B = {B}")
-    Hs, Ws = int(y.shape[1]), int(y.shape[2])
-    if cls_label.dim() == 2 and cls_label.shape[1] == 1:
-        cls_label = cls_label[:, 0]
-    if tuple(cls_label.shape) != (B,):
-        raise ValueError(f"cls_label {tuple(cls_label.shape)} must be (B,) or (B, 1) with B = {B}")
-    counts = torch.empty(B, 6, device=cls.device, dtype=torch.int64)
-    acc = torch.empty(4, device=cls.device, dtype=torch.float32)
-    areas = torch.empty(B, 3, K, 3, device=cls.device, dtype=torch.int64)
-    trim = torch.empty(B, D + 1, 3, device=cls.device, dtype=torch.int64) if with_trim else None
-    labels = torch.empty(B, Hs, Ws, device=cls.device, dtype=torch.int64) if return_labels else None
-    scratch = torch.empty(hip.query("fs_unwarp_class_areas_scratch_ints", B, K, h, w, Hs, Ws), device=cls.device, dtype=torch.int32)
-    hip.call("fs_unwarp_class_areas", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()),
-             hip.ptr(y.float().contiguous()), hip.ptr(cls_label.long().contiguous()), hip.ptr(counts), hip.ptr(acc), hip.ptr(areas),
-             hip.ptr(trim), hip.ptr(labels), hip.ptr(scratch), B, K, h, w, Hs, Ws, D, fr)
-    return (counts, acc, areas) + ((trim,) if with_trim else ()) + ((labels,) if return_labels else ())
+    counts, acc, areas, trim, labels = unwarp_count(cls, m, grid, y, cls_label, dia_factor, frame, areas=True, return_labels=return_labels)
+    return (counts, acc, areas) + ((trim,) if trim is not None else ()) + ((labels,) if return_labels else ())
 
 
 def class_scores_from_areas(areas):

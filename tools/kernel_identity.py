@@ -1,0 +1,155 @@
+"""Are the gfx950 kernels of two builds the same device code, kernel by kernel?  For refactors that move kernels between
+translation units, where the whole-.text comparison of profiles/r13/README.md (a) no longer applies.
+
+    python tools/kernel_identity.py --before DIR_OF_PARENT_OBJECTS --after DIR_OF_THIS_TREES_OBJECTS [--only frontend,unwarp] [--md]
+
+Every `*.o` of each directory is unbundled (llvm-objcopy --dump-section .hip_fatbin, clang-offload-bundler --unbundle of the
+hipv4-amdgcn-amd-amdhsa--gfx950 entry).  For every kernel symbol of `--before` (an STT_FUNC with a `<name>.kd` descriptor) the tool
+finds the symbol in `--after` -- exactly once, in whichever object -- and compares the symbol's bytes (st_value, st_size), its 64-byte
+kernel descriptor with the code offset left out (it is the distance from the descriptor to the code, which moves with the file's
+layout), and its entry of the `.note` metadata (llvm-readelf --notes: arguments, LDS, registers).  Objects whose kernel set is the same
+before and after are also compared as whole .text sections.  Exit status 1 if anything differs."""
+import argparse
+import glob
+import os
+import re
+import struct
+import subprocess
+import sys
+import tempfile
+
+LLVM = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/llvm/bin")
+TARGET = "hipv4-amdgcn-amd-amdhsa--gfx950"
+
+
+def tool(name):
+    return os.path.join(LLVM, name)
+
+
+def code_object(obj, tmp):
+    fat = os.path.join(tmp, os.path.basename(obj) + ".fatbin")
+    co = os.path.join(tmp, os.path.basename(obj) + ".co")
+    subprocess.run([tool("llvm-objcopy"), "--dump-section", f".hip_fatbin={fat}", obj, os.devnull], check=True)
+    subprocess.run([tool("clang-offload-bundler"), "--unbundle", "--type=o", f"--targets={TARGET}", f"--input={fat}", f"--output={co}"], check=True)
+    return co
+
+
+class Elf:
+    """The little of ELF64 this needs: sections by name, symbols with their bytes."""
+
+    def __init__(self, path):
+        self.path = path
+        d = self.data = open(path, "rb").read()
+        assert d[:4] == b"\x7fELF" and d[4] == 2 and d[5] == 1, path
+        shoff, = struct.unpack_from("<Q", d, 0x28)
+        shentsize, shnum, shstrndx = struct.unpack_from("<HHH", d, 0x3A)
+        raw = [struct.unpack_from("<IIQQQQIIQQ", d, shoff + i * shentsize) for i in range(shnum)]
+        stroff = raw[shstrndx][4]
+        self.sections = []
+        for s in raw:
+            name = d[stroff + s[0]:d.index(b"\0", stroff + s[0])].decode()
+            self.sections.append({"name": name, "type": s[1], "addr": s[3], "off": s[4], "size": s[5], "link": s[6], "entsize": s[9]})
+        self.symbols = {}
+        for s in self.sections:
+            if s["type"] != 2:                       # SHT_SYMTAB
+                continue
+            strs = self.sections[s["link"]]
+            for i in range(s["size"] // s["entsize"]):
+                nm, info, _other, shndx, value, size = struct.unpack_from("<IBBHQQ", d, s["off"] + i * s["entsize"])
+                name = d[strs["off"] + nm:d.index(b"\0", strs["off"] + nm)].decode()
+                if name and 0 < shndx < len(self.sections):
+                    self.symbols[name] = (info & 15, shndx, value, size)
+
+    def section(self, name):
+        s = next(s for s in self.sections if s["name"] == name)
+        return self.data[s["off"]:s["off"] + s["size"]]
+
+    def bytes_of(self, name):
+        _t, shndx, value, size = self.symbols[name]
+        s = self.sections[shndx]
+        o = s["off"] + value - s["addr"]
+        return self.data[o:o + size]
+
+    def kernels(self):
+        return sorted(n for n, v in self.symbols.items() if v[0] == 2 and n + ".kd" in self.symbols)
+
+    def metadata(self):
+        """kernel name -> the text of its amdhsa.kernels entry."""
+        out = subprocess.run([tool("llvm-readelf"), "--notes", self.path], check=True, capture_output=True, text=True).stdout
+        body = out.split("amdhsa.kernels:", 1)[1].split("amdhsa.target:", 1)[0]
+        res = {}
+        for entry in re.split(r"\n  - ", body)[1:]:
+            res[re.search(r"^    \.name:\s+(\S+)\s*$", entry, re.M).group(1)] = entry.strip()      # arguments' .name lines are indented further
+        return res
+
+
+def descriptor(elf, k):
+    kd = elf.bytes_of(k + ".kd")
+    assert len(kd) == 64, (k, len(kd))
+    return kd[:16] + kd[24:]                         # bytes 16..23: kernel_code_entry_byte_offset
+
+
+def load(directory, only, tmp):
+    objs = {}
+    for o in sorted(glob.glob(os.path.join(directory, "*.o"))):
+        stem = os.path.basename(o)[:-2]
+        if only and stem not in only:
+            continue
+        sub = os.path.join(tmp, str(len(os.listdir(tmp))))
+        os.makedirs(sub)
+        objs[stem] = Elf(code_object(o, sub))
+    return objs
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--before", required=True)
+    ap.add_argument("--after", required=True)
+    ap.add_argument("--only", default="", help="comma-separated object stems (default: all)")
+    ap.add_argument("--md", action="store_true", help="print the per-kernel table as markdown")
+    args = ap.parse_args()
+    only = set(filter(None, args.only.split(",")))
+    bad = 0
+    with tempfile.TemporaryDirectory() as tmp:
+        before, after = load(args.before, only, tmp), load(args.after, only, tmp)
+        where = {}
+        for stem, e in after.items():
+            for k in e.kernels():
+                where.setdefault(k, []).append(stem)
+        meta_after = {stem: e.metadata() for stem, e in after.items()}
+        rows = []
+        for stem, e in before.items():
+            meta = e.metadata()
+            for k in e.kernels():
+                homes = where.get(k, [])
+                if len(homes) != 1:
+                    rows.append((k, stem, "-", 0, f"found {len(homes)} times"))
+                    bad += 1
+                    continue
+                a = after[homes[0]]
+                same = [e.bytes_of(k) == a.bytes_of(k), descriptor(e, k) == descriptor(a, k), meta[k] == meta_after[homes[0]][k]]
+                verdict = "identical" if all(same) else "DIFFERS in " + ", ".join(n for n, s in zip(("code", "descriptor", "metadata"), same) if not s)
+                bad += not all(same)
+                rows.append((k, stem, homes[0], len(e.bytes_of(k)), verdict))
+        extra = sorted(set(where) - {r[0] for r in rows})
+        for k in extra:
+            rows.append((k, "-", where[k][0], 0, "only in --after"))
+            bad += 1
+        demangle = subprocess.run(["c++filt"] + [r[0] for r in rows], capture_output=True, text=True).stdout.split("\n") if rows else []
+        if args.md:
+            print("| kernel | object before | object after | bytes | |\n|---|---|---|---|---|")
+        for r, name in zip(rows, demangle):
+            name = re.sub(r"\(anonymous namespace\)::", "", name)
+            name = re.sub(r"^void ", "", re.sub(r"\(.*$", "", name))
+            print(f"| `{name}` | `{r[1]}.o` | `{r[2]}.o` | {r[3]} | {r[4]} |" if args.md else f"{r[4]:12s} {r[3]:8d}  {r[1]:>16s} -> {r[2]:16s} {name}")
+        for stem in sorted(set(before) & set(after)):
+            if before[stem].kernels() == after[stem].kernels():
+                t = before[stem].section(".text") == after[stem].section(".text")
+                print(f"whole .text of {stem}.o: {len(before[stem].section('.text'))} bytes, {'byte-identical' if t else 'DIFFERS'}")
+                bad += not t
+        print(f"{len(rows)} kernels, {bad} difference(s)")
+    return 1 if bad else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
