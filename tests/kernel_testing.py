@@ -55,6 +55,18 @@ class Out:
         left = torch.isnan(body) if isinstance(self.fill, float) and math.isnan(self.fill) else body == self.fill
         return bool(left.all())
 
+    def rows_left(self, row):
+        """For scratch too large to bring to the host (the slab scratch of the bwd-weight kernels): the guards are compared on
+        the device, and the body, taken as rows of `row` elements, gives per row how many elements still hold the fill value
+        (0 = written completely, row = untouched).  Returns that count per row as a host tensor."""
+        torch.cuda.synchronize()
+        s = _SENT[self.dtype]
+        assert bool((self.base[:self.g] == s).all()) and bool((self.base[self.g + self.n:] == s).all()), "a guard was written"
+        assert self.n % row == 0
+        body = self.t.reshape(-1, row)
+        left = torch.isnan(body) if isinstance(self.fill, float) and math.isnan(self.fill) else body == self.fill
+        return left.sum(dim=1).cpu()
+
 
 def dev(t, dtype=torch.float32):
     return None if t is None else t.to(dtype).contiguous().to(DEV)
