@@ -86,6 +86,7 @@ __global__ __launch_bounds__(1024) void compress_softmax_fwd_kernel(const float*
 // an image forms the image's softmax dot product itself (6 400 products: cheaper than a launch), then owns a contiguous slice of the pixels;
 // the slice is walked as float4 channel quads (768 threads = a multiple of the C/4 quads of a pixel, so a thread keeps its channel quad
 // and four dw accumulators).  Each workgroup leaves one record of C + 1 partial sums; fs_slab_reduce adds the records in index order.
+constexpr int CS_FWD_MAX_HW = 16384;      // compress_softmax_fwd_kernel keeps one float per pixel in dynamic LDS
 constexpr int CS_SLICES = 8;
 constexpr int CS_THREADS = 768;
 __global__ __launch_bounds__(CS_THREADS) void compress_softmax_bwd_kernel(const float* __restrict__ g, const float* __restrict__ xs,
@@ -891,7 +892,11 @@ int fs_compress_bwd(const float* g, const float* s, const float* w, float* ds, f
 
 int fs_compress_softmax_fwd(const float* s, const float* w, const float* bias, float* xs, int B, int HW, int C,
                             hipStream_t stream) {
-  FS_REQUIRE(s && w && bias && xs && B > 0 && HW > 0 && HW <= 16384 && C > 0 && C <= 32);
+  FS_REQUIRE(s && w && bias && xs && B > 0 && HW > 0 && HW <= CS_FWD_MAX_HW && C > 0 && C <= 32);
+  // the largest map is 64 KiB of dynamic LDS on top of the kernel's static red[16]: past the 64 KiB a launch gets without asking
+  static unsigned long long done = 0ull;
+  const int r = fs_lds_opt_in((const void*)compress_softmax_fwd_kernel, CS_FWD_MAX_HW * (int)sizeof(float), done);
+  if (r != FS_OK) return r;
   hipLaunchKernelGGL(compress_softmax_fwd_kernel, dim3(B), dim3(1024), HW * sizeof(float), stream, s, w, bias, xs, HW, C);
   FS_LAUNCH_CHECK();
   return FS_OK;

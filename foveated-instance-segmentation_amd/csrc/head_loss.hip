@@ -315,7 +315,7 @@ int fs_pred_assemble_bwd(const float* dpred, const float* cls, const float* m, f
   return FS_OK;
 }
 
-// accum: (3K + 1 + 6B) doubles of scratch; out: 7 floats; coef: 2K floats kept for the backward
+// accum: B * ceil(HW / 1024) * (3K + 7) doubles of scratch (one record per workgroup); out: 7 floats; coef: 2K floats kept for the backward
 int fs_seg_loss_fwd(const float* pred, const long long* gt, int B, int K, int HW, float gamma, float eps, double* accum,
                     float* out, float* coef, hipStream_t stream) {
   FS_REQUIRE(pred && gt && accum && out && coef && B > 0 && K > 1 && K <= KMAX && HW > 0);

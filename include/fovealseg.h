@@ -42,7 +42,8 @@ int fs_compress_fwd(const float* s, const float* w, const float* bias, float* ou
  * cross-workgroup sum of this library is two launches, partials then an ordered sum: no result depends on workgroup timing). */
 int fs_compress_bwd(const float* g, const float* s, const float* w, float* ds, float* dw, float* db, int B, int HW, int C,
                     float* scratch, fs_stream_t stream);
-/* s (B,HW,C) -> xs (B,HW) = softmax_HW(w . relu(s) + bias).  models/models.py:369-372,715-723. */
+/* s (B,HW,C) -> xs (B,HW) = softmax_HW(w . relu(s) + bias), HW <= 16384 (one workgroup keeps an image's logits in LDS; the launcher
+ * asks for the 64 KiB of dynamic LDS the largest map needs), C <= 32.  models/models.py:369-372,715-723. */
 int fs_compress_softmax_fwd(const float* s, const float* w, const float* bias, float* xs, int B, int HW, int C, fs_stream_t stream);
 /* backward: C a multiple of 4; scratch = fs_compress_softmax_bwd_scratch_floats(B, C) floats (round 5: eight workgroups per image, one
  * record of C + 1 partial sums each). */

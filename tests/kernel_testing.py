@@ -11,8 +11,8 @@ DEV = "cuda"
 GUARD = 256                 # floats (1 KiB) of sentinel on both sides of every output
 U = 2.0 ** -24              # unit roundoff of fp32
 
-_FILL = {torch.float32: float("nan"), torch.float64: float("nan"), torch.uint8: 0xFF, torch.int32: -9999}
-_SENT = {torch.float32: 777.25, torch.float64: 777.25, torch.uint8: 0xA5, torch.int32: -7777}
+_FILL = {torch.float32: float("nan"), torch.float64: float("nan"), torch.uint8: 0xFF, torch.int32: -9999, torch.int64: -9999}
+_SENT = {torch.float32: 777.25, torch.float64: 777.25, torch.uint8: 0xA5, torch.int32: -7777, torch.int64: -7777}
 
 
 class Out:
