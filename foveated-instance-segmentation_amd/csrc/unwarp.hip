@@ -8,7 +8,9 @@
 //                MODEL.upsample (models/models.py:378-474,968), the trimap buckets (eval.py:41-67), the per-class areas of the three
 //                spaces (eval.py:197,218-257,313-322; models/models_instance.py:909-918; utils.py:289-317)
 //   trimap bands which band of width 1, 2, 4 .. 2^D around the label's boundary a pixel lies in     (eval.py:41-67)
-// Host side: fs_unwarp_labels / _accuracy / _trimap / _class_areas are one launch sequence with optional parts.  unwarp_plan() derives
+//   surface      the q-th percentile of the distances between two masks' borders (HD95), as two integer order statistics of d^2
+//                                                                                            (VAL.hd95; utils.py:25-101, in 2-D)
+// Host side: fs_unwarp_labels / _accuracy / _trimap / _class_areas / _hd are one launch sequence with optional parts.  unwarp_plan() derives
 // every size, scratch offset and limit from the shape and the feature set, UnwarpJob carries the caller's pointers, unwarp_run()
 // checks both and launches.  A refused call launches nothing: every check, fs_trimap_bands' included, comes before the first launch.
 #include "common.h"
@@ -740,6 +742,276 @@ __global__ __launch_bounds__(256) void trimap_col_kernel(const unsigned char* __
   }
 }
 
+// ---- surface distance between two masks: the Hausdorff percentile (HD95) of evaluate(hausdorff=...) ----------------------------------
+// The published definition utils.py:25-101 was copied from, in 2-D (the reference's own function flattens both masks before it erodes
+// them and is called by nothing): the border of a mask is its foreground with a background 4-neighbour, everything
+// outside the image being background; every border pixel of one mask takes the Euclidean distance to the nearest border pixel of the
+// other, in both directions; the two sets are pooled; np.percentile(., q) interpolates between two order statistics.  Squared
+// distances between pixels are integers, so everything up to the caller's two square roots is integer work, and exact:
+//   fg       one byte per pixel, bit 0 = predicted foreground, bit 1 = label foreground (unwarp_fg_kernel, or the caller's)
+//   column   per mask the border bit, and g = the vertical distance to the nearest border pixel of the pixel's column (two sweeps)
+//   row      a border pixel at (y, x) of one mask: d^2 = min over x' of (x - x')^2 + g_other(y, x')^2, the row of g in LDS; the scan
+//            walks outwards and stops once dx^2 alone reaches the best value so far, which no later column can beat; beyond the
+//            first few columns the wave scans together for one pixel at a time
+//   select   a two-level radix select over the pooled d^2 of an image: the row pass runs twice, first counting d^2 >> 15 into a
+//            histogram, whose prefix sums give the bucket of either rank, then counting the low 15 bits of the values in those buckets.
+//            No list of distances exists at any size; integer atomics only, the same bits in any order.
+// HD_SENT is g in a column without a border pixel.  With Hs, Ws <= 16384 a true d^2 is at most 2 * 16383^2 < 2^29, HD_SENT^2 = 2^30
+// lies above every one of them, and dx^2 + HD_SENT^2 <= 16383^2 + 2^30 < 2^31 stays an int.
+constexpr int HD_SENT = 32768;
+constexpr int HD_MAX_SIDE = 16384;
+constexpr int HD_L1_SHIFT = 15;                        // level 1: d^2 >> 15, at most 2^14 buckets
+constexpr int HD_L2_BINS = 1 << HD_L1_SHIFT;           // level 2: the low 15 bits
+constexpr int HD_CACHE = 1024;                         // row pass: the first bins of a histogram are counted in LDS, then flushed
+constexpr int HD_NEAR = 8;                             // row pass: columns on either side a lane scans alone before the wave joins in
+
+// fg[b,v,u]: unwarp_label_kernel's gather (bit 0: the class is not K-1) and the label mask's truncation (bit 1).  dec may carry
+// class_area_sampled_kernel's bit.  VEC: Ws % 4 == 0, y 16-byte aligned: four neighbours of one row, one word stored.
+template <bool VEC>
+__global__ __launch_bounds__(256) void unwarp_fg_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
+                                                        const float* __restrict__ yl, unsigned char* __restrict__ fg, int Hs, int Ws, int hw,
+                                                        int K, int blocks_per_image) {
+  const int b = blockIdx.x / blocks_per_image, chunk = blockIdx.x - b * blocks_per_image;
+  const int per = Hs * Ws;
+  const long base = (long)b * per;
+  const int* ob = owner + base;
+  const int* rx = rowx + base;
+  const int* db = dec + (long)b * (hw + 1);
+  const float* yb = yl + base;
+  const int bg = K - 1;
+  const int p0 = chunk * UACC_CHUNK;
+  if (VEC) {
+    const int p = p0 + (int)threadIdx.x * 4;
+    if (p >= per) return;
+    const int4 o4 = *reinterpret_cast<const int4*>(ob + p);
+    const float4 y4 = *reinterpret_cast<const float4*>(yb + p);
+    const int y = p / Ws, x = p - y * Ws;
+    int q[4] = {o4.x, o4.y, o4.z, o4.w};
+    const int holes = (o4.x < 0) | (o4.y < 0) << 1 | (o4.z < 0) << 2 | (o4.w < 0) << 3;
+    if (holes) {
+      int src[4];
+      nearest_claimed4(rx, y, x, Hs, Ws, holes, src);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
+    }
+    const float ys[4] = {y4.x, y4.y, y4.z, y4.w};
+    unsigned int wd = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const unsigned int pf = (db[q[k]] & DEC_CLASS_MASK) != bg, lf = (long long)ys[k] != 0;
+      wd |= (pf | lf << 1) << (8 * k);
+    }
+    *reinterpret_cast<unsigned int*>(fg + base + p) = wd;
+  } else {
+#pragma unroll 1
+    for (int j = 0; j < UACC_PIX; ++j) {
+      const int p = p0 + j * 256 + (int)threadIdx.x;
+      if (p >= per) break;
+      const int y = p / Ws, x = p - y * Ws;
+      const int a = unwarp_class_at(ob, rx, db, ob[p], y, x, Hs, Ws, hw) & DEC_CLASS_MASK;
+      fg[base + p] = (unsigned char)((a != bg) | ((long long)yb[p] != 0) << 1);
+    }
+  }
+}
+
+// column pass: a thread per column (coalesced across x).  Downwards: the border bits of both masks from the byte and its four
+// neighbours, g = rows since the last border pixel (HD_SENT before the first), both masks' g in one word (low half: bit 0's mask);
+// upwards: the minimum with the rows until the next one.  cnt[b][2] += the border pixels of either mask.
+__global__ __launch_bounds__(256) void hd_column_kernel(const unsigned char* __restrict__ fg, unsigned int* __restrict__ g, int* __restrict__ cnt,
+                                                        int Hs, int Ws, int xblocks) {
+  const int b = blockIdx.x / xblocks, x = (blockIdx.x - b * xblocks) * 256 + (int)threadIdx.x;
+  int n0 = 0, n1 = 0;
+  if (x < Ws) {
+    const unsigned char* f = fg + (long)b * Hs * Ws + x;
+    unsigned int* gb = g + (long)b * Hs * Ws + x;
+    const bool hasl = x > 0, hasr = x + 1 < Ws;
+    unsigned int up = 0u, c = f[0];
+    int d0 = HD_SENT, d1 = HD_SENT;
+    for (int y = 0; y < Hs; ++y) {
+      const long o = (long)y * Ws;
+      const unsigned int dn = y + 1 < Hs ? f[o + Ws] : 0u;
+      const unsigned int l = hasl ? f[o - 1] : 0u, r = hasr ? f[o + 1] : 0u;
+      const unsigned int bd = c & ~(up & dn & l & r) & 3u;
+      d0 = (bd & 1u) ? 0 : (d0 == HD_SENT ? HD_SENT : d0 + 1);
+      d1 = (bd & 2u) ? 0 : (d1 == HD_SENT ? HD_SENT : d1 + 1);
+      n0 += (int)(bd & 1u); n1 += (int)(bd >> 1);
+      gb[o] = (unsigned int)d0 | (unsigned int)d1 << 16;
+      up = c; c = dn;
+    }
+    d0 = HD_SENT, d1 = HD_SENT;
+    for (int y = Hs - 1; y >= 0; --y) {
+      const long o = (long)y * Ws;
+      const unsigned int v = gb[o];
+      const int a0 = (int)(v & 0xFFFFu), a1 = (int)(v >> 16);
+      d0 = a0 == 0 ? 0 : (d0 == HD_SENT ? HD_SENT : d0 + 1);
+      d1 = a1 == 0 ? 0 : (d1 == HD_SENT ? HD_SENT : d1 + 1);
+      const unsigned int wd = (unsigned int)min(a0, d0) | (unsigned int)min(a1, d1) << 16;
+      if (wd != v) gb[o] = wd;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) { n0 += __shfl_xor(n0, o, 64); n1 += __shfl_xor(n1, o, 64); }
+  if ((threadIdx.x & 63) == 0) {
+    if (n0) atomicAdd(cnt + 2 * b, n0);
+    if (n1) atomicAdd(cnt + 2 * b + 1, n1);
+  }
+}
+
+// row pass: one workgroup per image row, the row of g in LDS.  LEVEL 1: hist[b][d^2 >> 15] += 1 for every border pixel of either
+// mask; LEVEL 2: hist[b][0 / 1][d^2 & 32767] += 1 for those whose d^2 >> 15 is the bucket of the lower / upper rank (sel[b][0], [2]).
+// nb = bins of one histogram.  An image with an empty border has no distances: its rows return at once.
+template <int LEVEL>
+__global__ __launch_bounds__(256) void hd_row_kernel(const unsigned int* __restrict__ g, const int* __restrict__ cnt, const int* __restrict__ sel,
+                                                     int* __restrict__ hist, int Hs, int Ws, int nb) {
+  extern __shared__ unsigned int hd_row[];             // [Ws]
+  __shared__ int cache[LEVEL][HD_CACHE];
+  const int b = blockIdx.x / Hs;
+  if (cnt[2 * b] == 0 || cnt[2 * b + 1] == 0) return;
+  const unsigned int* gr = g + (long)blockIdx.x * Ws;
+  int any = 0;
+  for (int x = threadIdx.x; x < Ws; x += 256) {
+    const unsigned int v = gr[x];
+    hd_row[x] = v;
+    any |= (v & 0xFFFFu) == 0u || (v >> 16) == 0u;
+  }
+  for (int i = threadIdx.x; i < LEVEL * HD_CACHE; i += 256) (&cache[0][0])[i] = 0;
+  if (!__syncthreads_or(any)) return;                  // no border pixel in this row
+  int b0 = 0, b1 = 0;
+  if (LEVEL == 2) b0 = sel[4 * b], b1 = sel[4 * b + 2];
+  int* h = hist + (long)b * LEVEL * nb;
+  auto emit = [&](int best) {
+    if (LEVEL == 1) {
+      const int bin = best >> HD_L1_SHIFT;
+      if (bin < HD_CACHE) atomicAdd(&cache[0][bin], 1);
+      else if (bin < nb) atomicAdd(h + bin, 1);
+    } else {
+      const int hi = best >> HD_L1_SHIFT, bin = best & (HD_L2_BINS - 1);
+      if (bin < nb) {
+        if (hi == b0) { if (bin < HD_CACHE) atomicAdd(&cache[0][bin], 1); else atomicAdd(h + bin, 1); }
+        if (hi == b1) { if (bin < HD_CACHE) atomicAdd(&cache[LEVEL - 1][bin], 1); else atomicAdd(h + nb + bin, 1); }
+      }
+    }
+  };
+  // A wave takes 64 neighbouring pixels at a time.  Every lane first scans the HD_NEAR columns on either side of its own pixel, which
+  // settles nearly every pixel of a prediction near its label.  A pixel whose best value is still beyond HD_NEAR^2 is then scanned by the
+  // whole wave, 256 columns on either side a trip (a lane takes four of them), until the nearest unseen column alone reaches the best
+  // value: two border pixels in a row of 1024 cost sixteen trips, not a thousand steps of one lane.
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int c = wave; c * 64 < Ws; c += 4) {
+    const int x = c * 64 + lane;
+    const unsigned int v = x < Ws ? hd_row[x] : 0xFFFFFFFFu;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const bool isb = ((v >> (16 * k)) & 0xFFFFu) == 0u;   // a border pixel of mask k
+      const int sh = 16 * (1 - k);                      // the other mask's half
+      int best = 0x7FFFFFFF;
+      if (isb) {
+        const int g0 = (int)((v >> sh) & 0xFFFFu);
+        best = g0 * g0;
+        for (int dx = 1; dx <= HD_NEAR; ++dx) {
+          const int dx2 = dx * dx;
+          if (dx2 >= best) break;
+          if (x - dx >= 0) { const int gg = (int)((hd_row[x - dx] >> sh) & 0xFFFFu); best = min(best, dx2 + gg * gg); }
+          if (x + dx < Ws) { const int gg = (int)((hd_row[x + dx] >> sh) & 0xFFFFu); best = min(best, dx2 + gg * gg); }
+        }
+      }
+      const bool more = isb && (HD_NEAR + 1) * (HD_NEAR + 1) < best && (x - (HD_NEAR + 1) >= 0 || x + (HD_NEAR + 1) < Ws);
+      if (isb && !more) emit(best);
+      unsigned long long pending = __ballot(more);
+      while (pending != 0ull) {                         // uniform across the wave
+        const int src = __builtin_ctzll(pending);
+        pending &= pending - 1ull;
+        const int xs = c * 64 + src;
+        int bs = __shfl(best, src, 64);
+        for (int base = HD_NEAR + 1; base < Ws; base += 256) {
+          if (base * base >= bs || (xs - base < 0 && xs + base >= Ws)) break;
+          int mine = bs;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int dx = base + 64 * j + lane, dx2 = dx * dx;
+            if (dx2 < mine) {
+              if (xs - dx >= 0) { const int gg = (int)((hd_row[xs - dx] >> sh) & 0xFFFFu); mine = min(mine, dx2 + gg * gg); }
+              if (xs + dx < Ws) { const int gg = (int)((hd_row[xs + dx] >> sh) & 0xFFFFu); mine = min(mine, dx2 + gg * gg); }
+            }
+          }
+#pragma unroll
+          for (int o = 32; o > 0; o >>= 1) mine = min(mine, __shfl_xor(mine, o, 64));
+          bs = mine;
+        }
+        if (lane == src) emit(bs);
+      }
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < LEVEL * HD_CACHE; i += 256) {
+    const int which = i / HD_CACHE, bin = i - which * HD_CACHE;
+    const int c = cache[which][bin];
+    if (c != 0 && bin < nb) atomicAdd(h + (long)which * nb + bin, c);
+  }
+}
+
+// the bin of h[0 .. nb) that holds the element of rank r (0-based, ascending; r < the histogram's total) -> out[0], and r's rank
+// inside that bin -> out[1].  Block-wide, 256 threads; part = 256 ints of LDS.
+__device__ __forceinline__ void hd_find_rank(const int* __restrict__ h, int nb, int r, int* out, int* part) {
+  const int tid = threadIdx.x;
+  const int seg = (nb + 255) / 256;
+  const int x0 = min(tid * seg, nb), x1 = min(x0 + seg, nb);
+  int s = 0;
+  for (int i = x0; i < x1; ++i) s += h[i];
+  __syncthreads();
+  part[tid] = s;
+  __syncthreads();
+  if (tid == 0) {
+    int c = 0;
+    for (int t = 0; t < 256; ++t) { const int v = part[t]; part[t] = c; c += v; }
+  }
+  __syncthreads();
+  int c = part[tid];
+  if (r >= c && r < c + s) {
+    for (int i = x0; i < x1; ++i) {
+      const int v = h[i];
+      if (r < c + v) { out[0] = i; out[1] = r - c; break; }
+      c += v;
+    }
+  }
+}
+// n = n_pred + n_label pooled distances; np.percentile's two order statistics: ranks lo = q (n-1) div 100 and hi = lo + (a remainder).
+// sel[b] = (bucket of lo, lo's rank in it, bucket of hi, hi's rank in it).  An empty border: hd[b] = (n_pred, n_label, -1, -1), final.
+__global__ __launch_bounds__(256) void hd_select1_kernel(const int* __restrict__ cnt, const int* __restrict__ hist1, int* __restrict__ sel,
+                                                         long long* __restrict__ hd, int nb1, int q) {
+  __shared__ int part[256];
+  const int b = blockIdx.x;
+  const int n0 = cnt[2 * b], n1 = cnt[2 * b + 1];
+  if (n0 == 0 || n1 == 0) {
+    if (threadIdx.x == 0) { hd[4 * b] = n0; hd[4 * b + 1] = n1; hd[4 * b + 2] = -1; hd[4 * b + 3] = -1; }
+    return;
+  }
+  const long long t = (long long)q * ((long long)n0 + n1 - 1);
+  const int lo = (int)(t / 100), hi = lo + (t % 100 != 0);
+  const int* h = hist1 + (long)b * nb1;
+  hd_find_rank(h, nb1, lo, sel + 4 * b, part);
+  hd_find_rank(h, nb1, hi, sel + 4 * b + 2, part);
+}
+// hd[b] = (n_pred, n_label, d2_lo, d2_hi): the bucket's high bits and the bin of the rank inside the bucket's histogram
+__global__ __launch_bounds__(256) void hd_select2_kernel(const int* __restrict__ cnt, const int* __restrict__ hist2, const int* __restrict__ sel,
+                                                         long long* __restrict__ hd, int nb2) {
+  __shared__ int part[256];
+  __shared__ int res[4];
+  const int b = blockIdx.x;
+  const int n0 = cnt[2 * b], n1 = cnt[2 * b + 1];
+  if (n0 == 0 || n1 == 0) return;
+  const int* h = hist2 + (long)b * 2 * nb2;
+  hd_find_rank(h, nb2, sel[4 * b + 1], res, part);
+  hd_find_rank(h + nb2, nb2, sel[4 * b + 3], res + 2, part);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    hd[4 * b] = n0; hd[4 * b + 1] = n1;
+    hd[4 * b + 2] = ((long long)sel[4 * b] << HD_L1_SHIFT) | res[0];
+    hd[4 * b + 3] = ((long long)sel[4 * b + 2] << HD_L1_SHIFT) | res[2];
+  }
+}
+
 // ---- host: one plan, one job, one launcher -------------------------------------------------------------------------------------------
 constexpr long INT_LIMIT = 2147483647L;                // pixel / point indices are ints
 constexpr long THREADS_MAX = 4294967295L - 255;        // every launch: fewer than 2^32 work-items
@@ -763,10 +1035,31 @@ TrimapPlan trimap_plan(int B, int Hs, int Ws) {
   return t;
 }
 
+// fs_surface_hd's sizes.  Scratch, in ints: g [n] (both masks' column distances, two 16-bit halves a pixel), then the region zeroed
+// before every call: cnt [B][2], sel [B][4], the level-1 histograms [B][nb1], the level-2 histograms [B][2][nb2].  The histograms are
+// no longer than the image's largest d^2 = (Hs-1)^2 + (Ws-1)^2 needs.
+struct SurfacePlan {
+  long n, nb1, nb2;
+  long g, cnt, sel, h1, h2, total;
+  bool ok;                                             // launchable
+};
+SurfacePlan surface_plan(int B, int Hs, int Ws) {
+  SurfacePlan s = {};
+  if (!(B > 0 && Hs > 0 && Ws > 0)) return s;
+  s.n = (long)B * Hs * Ws;
+  const long maxd2 = (long)(Hs - 1) * (Hs - 1) + (long)(Ws - 1) * (Ws - 1);
+  s.nb1 = (maxd2 >> HD_L1_SHIFT) + 1, s.nb2 = maxd2 + 1 < HD_L2_BINS ? maxd2 + 1 : HD_L2_BINS;
+  s.g = 0, s.cnt = align4(s.n), s.sel = s.cnt + 2L * B, s.h1 = s.sel + 4L * B, s.h2 = s.h1 + (long)B * s.nb1;
+  s.total = s.h2 + 2L * B * s.nb2;
+  s.ok = Hs <= HD_MAX_SIDE && Ws <= HD_MAX_SIDE && (long)B * Hs * 256 <= THREADS_MAX && (long)B * cdiv(Ws, 256) * 256 <= THREADS_MAX;
+  return s;
+}
+
 // What a call computes on top of the class-map gather.  UW_COUNT: the gather counts (fs_unwarp_accuracy); UW_TRIM / UW_AREA: it also
-// buckets by trimap band / sums class areas.  Each feature appends its regions to the scratch of the one before; UW_AREA's layout keeps
-// UW_TRIM's regions whether or not the call has a trimap.
-enum : unsigned { UW_LABELS = 0, UW_COUNT = 1, UW_TRIM = 2, UW_AREA = 4 };
+// buckets by trimap band / sums class areas; UW_HD: a foreground byte map and the surface distances behind the count pass.  Each
+// feature appends its regions to the scratch of the one before; UW_AREA's layout keeps UW_TRIM's regions whether or not the call has a
+// trimap, and UW_HD's come after whatever the other features of the call take.
+enum : unsigned { UW_LABELS = 0, UW_COUNT = 1, UW_TRIM = 2, UW_AREA = 4, UW_HD = 8 };
 
 struct UnwarpPlan {
   int B, K, h, w, Hs, Ws;
@@ -778,8 +1071,10 @@ struct UnwarpPlan {
   long rec;                                            // UW_COUNT: [B*cpi][UACC_REC]
   long trec, band, inter;                              // UW_TRIM: [B*cpi][TRIM_REC], n band bytes, TrimapPlan::ints
   long arec, atab;                                     // UW_AREA: [B*cpi][AREA_REC], [B][K] sums of the other predicted classes' pixels
+  long fg, hds;                                        // UW_HD: n foreground bytes, SurfacePlan::total
   long total;
   TrimapPlan tri;
+  SurfacePlan sp;
   bool ok;                                             // launchable: sizes and limits (pointers are the job's)
 };
 UnwarpPlan unwarp_plan(int B, int K, int h, int w, int Hs, int Ws, unsigned features) {
@@ -798,11 +1093,16 @@ UnwarpPlan unwarp_plan(int B, int K, int h, int w, int Hs, int Ws, unsigned feat
     p.total = p.inter + p.tri.ints;
   }
   if (features & UW_AREA) p.arec = align4(p.total), p.atab = p.arec + (long)B * p.cpi * AREA_REC, p.total = p.atab + (long)B * K;
+  if (features & UW_HD) {
+    p.sp = surface_plan(B, Hs, Ws);
+    p.fg = align4(p.total), p.hds = p.fg + align4((p.n + 3) / 4), p.total = p.hds + p.sp.total;
+  }
   // a workgroup's last trip of the count pass may start up to a chunk past the end
   const long per_max = INT_LIMIT - (features & UW_COUNT ? UACC_CHUNK : 0);
   p.ok = K >= 2 && K <= UNWARP_MAX_K && row_fits_lds(Ws) && (long)h * w < INT_LIMIT && p.per < per_max && p.n <= THREADS_MAX &&
          (long)B * Hs * 256 <= THREADS_MAX && (long)B * p.bpi * 256 <= THREADS_MAX &&
-         (!(features & UW_COUNT) || (long)B * p.cpi * 256 <= THREADS_MAX) && (!(features & UW_TRIM) || p.tri.ok);
+         (!(features & UW_COUNT) || (long)B * p.cpi * 256 <= THREADS_MAX) && (!(features & UW_TRIM) || p.tri.ok) &&
+         (!(features & UW_HD) || ((features & UW_COUNT) && p.sp.ok));
   return p;
 }
 
@@ -814,6 +1114,7 @@ struct UnwarpJob {
   struct { const float* y; const long long* cls_label; long long* counts; float* acc; } count;  // UW_COUNT
   struct { long long* out; int D, frame; } trim;                                                // UW_TRIM
   struct { long long* out; } areas;                                                             // UW_AREA
+  struct { long long* out; int q; } hd;                                                         // UW_HD
 };
 
 bool trimap_args_ok(int D, int frame) { return D >= 0 && D <= TRI_MAX_D && (frame == 0 || frame == 1); }
@@ -826,6 +1127,35 @@ int trimap_launch(const TrimapPlan& t, const float* y, unsigned char* band, unsi
   const int vec = Ws % 4 == 0 && ((uintptr_t)band & 3) == 0;
   hipLaunchKernelGGL(trimap_col_kernel, dim3((unsigned)(B * t.rts * t.cts)), dim3(256), 2 * (TRI_CH + (2 << D)) * TRI_CW, stream, inter, band,
                      Hs, Ws, (int)t.P, D, vec, (int)t.rts, (int)t.cts);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+bool hd_args_ok(int q) { return q >= 1 && q <= 100; }
+
+// zeroed counters and histograms, the column pass, then twice the row pass with a selection behind it
+int surface_launch(const SurfacePlan& sp, const unsigned char* fg, long long* hd, int* s, int B, int Hs, int Ws, int q, hipStream_t stream) {
+  const hipError_t e = hipMemsetAsync(s + sp.cnt, 0, sizeof(int) * (size_t)(sp.total - sp.cnt), stream);
+  if (e != hipSuccess) return (int)e;
+  unsigned int* g = reinterpret_cast<unsigned int*>(s + sp.g);
+  const int xblocks = cdiv(Ws, 256);
+  hipLaunchKernelGGL(hd_column_kernel, dim3((unsigned)(B * xblocks)), dim3(256), 0, stream, fg, g, s + sp.cnt, Hs, Ws, xblocks);
+  FS_LAUNCH_CHECK();
+  const int lds = Ws * (int)sizeof(unsigned int);
+  if (lds > 48 * 1024) {                               // with the static histograms beside it the row is beyond the default
+    static unsigned long long done1 = 0ull, done2 = 0ull;
+    FS_TRY(fs_lds_opt_in(reinterpret_cast<const void*>(&hd_row_kernel<1>), lds, done1));
+    FS_TRY(fs_lds_opt_in(reinterpret_cast<const void*>(&hd_row_kernel<2>), lds, done2));
+  }
+  hipLaunchKernelGGL(hd_row_kernel<1>, dim3((unsigned)((long)B * Hs)), dim3(256), (size_t)lds, stream, g, s + sp.cnt, s + sp.sel, s + sp.h1, Hs, Ws,
+                     (int)sp.nb1);
+  FS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(hd_select1_kernel, dim3((unsigned)B), dim3(256), 0, stream, s + sp.cnt, s + sp.h1, s + sp.sel, hd, (int)sp.nb1, q);
+  FS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(hd_row_kernel<2>, dim3((unsigned)((long)B * Hs)), dim3(256), (size_t)lds, stream, g, s + sp.cnt, s + sp.sel, s + sp.h2, Hs, Ws,
+                     (int)sp.nb2);
+  FS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(hd_select2_kernel, dim3((unsigned)B), dim3(256), 0, stream, s + sp.cnt, s + sp.h2, s + sp.sel, hd, (int)sp.nb2);
   FS_LAUNCH_CHECK();
   return FS_OK;
 }
@@ -868,14 +1198,15 @@ const CountKernel COUNT_KERNELS[8] = {
     unwarp_count_kernel<true, true, false>,   unwarp_count_kernel<false, false, true>, unwarp_count_kernel<true, false, true>,
     unwarp_count_kernel<false, true, true>,   unwarp_count_kernel<true, true, true>};
 
-// The launches of the four entry points: [trimap bands,] prelude, then either the class map or the count pass and its finalizers
-// (the trimap's and the areas' after the accuracies').
+// The launches of the five entry points: [trimap bands,] prelude, then either the class map or the count pass and its finalizers
+// (the trimap's and the areas' after the accuracies'), then with UW_HD the foreground bytes and the surface distances.
 int unwarp_run(const UnwarpPlan& p, const UnwarpJob& j, hipStream_t stream) {
-  const bool count = p.features & UW_COUNT, trim = p.features & UW_TRIM, area = p.features & UW_AREA;
+  const bool count = p.features & UW_COUNT, trim = p.features & UW_TRIM, area = p.features & UW_AREA, hdq = p.features & UW_HD;
   FS_REQUIRE(p.ok && j.cls && j.m && j.grid && j.scratch && (count || j.labels.map));
   // the records are stored and read 16 bytes at a time
   FS_REQUIRE(!count || (j.count.y && j.count.cls_label && j.count.counts && j.count.acc && ((uintptr_t)j.scratch & 15) == 0));
   FS_REQUIRE((!trim || (j.trim.out && trimap_args_ok(j.trim.D, j.trim.frame))) && (!area || j.areas.out));
+  FS_REQUIRE(!hdq || (j.hd.out && hd_args_ok(j.hd.q)));
   int* s = j.scratch;
   unsigned char* band = trim ? reinterpret_cast<unsigned char*>(s + p.band) : nullptr;
   if (trim) FS_TRY(trimap_launch(p.tri, j.count.y, band, reinterpret_cast<unsigned char*>(s + p.inter), p.B, p.Hs, p.Ws, j.trim.D, j.trim.frame, stream));
@@ -905,6 +1236,14 @@ int unwarp_run(const UnwarpPlan& p, const UnwarpJob& j, hipStream_t stream) {
     hipLaunchKernelGGL(unwarp_area_finalize_kernel, dim3((unsigned)p.B), dim3(256), 0, stream, arec, atab, j.count.cls_label, j.areas.out, p.K,
                        (int)p.cpi, (long long)p.per);
     FS_LAUNCH_CHECK();
+  }
+  if (hdq) {
+    unsigned char* fg = reinterpret_cast<unsigned char*>(s + p.fg);
+    const bool vec4 = p.Ws % 4 == 0 && ((uintptr_t)j.count.y & 15) == 0;
+    hipLaunchKernelGGL(vec4 ? unwarp_fg_kernel<true> : unwarp_fg_kernel<false>, dim3((unsigned)(p.B * p.cpi)), dim3(256), 0, stream, s + p.owner,
+                       s + p.rowx, s + p.dec, j.count.y, fg, p.Hs, p.Ws, p.h * p.w, p.K, (int)p.cpi);
+    FS_LAUNCH_CHECK();
+    FS_TRY(surface_launch(p.sp, fg, j.hd.out, s + p.hds, p.B, p.Hs, p.Ws, j.hd.q, stream));
   }
   return FS_OK;
 }
@@ -950,6 +1289,11 @@ long fs_unwarp_class_areas_scratch_ints(int B, int K, int h, int w, int Hs, int 
   return unwarp_plan(B, K, h, w, Hs, Ws, UW_COUNT | UW_AREA).total;
 }
 long fs_trimap_bands_scratch_ints(int B, int Hs, int Ws) { return trimap_plan(B, Hs, Ws).ints; }
+// the layout with every other feature's regions: a call without areas or trimap needs less
+long fs_unwarp_hd_scratch_ints(int B, int K, int h, int w, int Hs, int Ws) {
+  return unwarp_plan(B, K, h, w, Hs, Ws, UW_COUNT | UW_AREA | UW_HD).total;
+}
+long fs_surface_hd_scratch_ints(int B, int Hs, int Ws) { return surface_plan(B, Hs, Ws).total; }
 
 int fs_unwarp_labels(const float* cls, const float* m, const float* grid, long long* labels, unsigned char* hole, int* scratch, int B, int K,
                      int h, int w, int Hs, int Ws, hipStream_t stream) {
@@ -980,6 +1324,20 @@ int fs_unwarp_class_areas(const float* cls, const float* m, const float* grid, c
                           int Ws, int D, int frame, hipStream_t stream) {
   return unwarp_run(unwarp_plan(B, K, h, w, Hs, Ws, UW_COUNT | UW_AREA | (trim ? UW_TRIM : 0)),
                     {cls, m, grid, scratch, {labels}, {y, cls_label, counts, acc}, {trim, D, frame}, {areas}}, stream);
+}
+
+// areas == nullptr: no class areas; trim == nullptr: no trimap, D and frame are not read
+int fs_unwarp_hd(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts, float* acc,
+                 long long* areas, long long* trim, long long* labels, long long* hd, int* scratch, int B, int K, int h, int w, int Hs, int Ws,
+                 int D, int frame, int q, hipStream_t stream) {
+  return unwarp_run(unwarp_plan(B, K, h, w, Hs, Ws, UW_COUNT | UW_HD | (areas ? UW_AREA : 0) | (trim ? UW_TRIM : 0)),
+                    {cls, m, grid, scratch, {labels}, {y, cls_label, counts, acc}, {trim, D, frame}, {areas}, {hd, q}}, stream);
+}
+
+int fs_surface_hd(const unsigned char* fg, long long* hd, int* scratch, int B, int Hs, int Ws, int q, hipStream_t stream) {
+  const SurfacePlan sp = surface_plan(B, Hs, Ws);
+  FS_REQUIRE(fg && hd && scratch && ((uintptr_t)scratch & 15) == 0 && sp.ok && hd_args_ok(q));
+  return surface_launch(sp, fg, hd, scratch, B, Hs, Ws, q, stream);
 }
 
 }  // extern "C"

@@ -44,6 +44,8 @@ SIGNATURES = {
     "fs_trimap_bands": "ppp" + "iiiii",
     "fs_unwarp_trimap": "pppppppppp" + "iiiiiiii",
     "fs_unwarp_class_areas": "ppppppppppp" + "iiiiiiii",
+    "fs_unwarp_hd": "pppppppppppp" + "iiiiiiiii",
+    "fs_surface_hd": "ppp" + "iiii",
     "fs_conv2d_fwd": "ppppiiiiiiiiiiiifuplp",
     "fs_conv2d_fwd_residual": "ppppp" + "iiiiiiiiiiii" + "fufu" + "l" + "plp",
     "fs_conv2d_fwd_stats": "pppppiiiiiiiiiiiifuplp",
@@ -117,7 +119,8 @@ HOST_ONLY = ("fs_set_conv_precision", "fs_get_conv_precision", "fs_conv2d_worksp
              "fs_conv2d_pack_persistent", "fs_conv2d_ws_mode",
              "fs_edge_loss_stats_floats", "fs_compress_softmax_bwd_scratch_floats", "fs_gauss_grid_bwd_scratch_floats",
              "fs_unwarp_labels_scratch_ints", "fs_unwarp_accuracy_scratch_ints",
-             "fs_trimap_bands_scratch_ints", "fs_unwarp_trimap_scratch_ints", "fs_unwarp_class_areas_scratch_ints")
+             "fs_trimap_bands_scratch_ints", "fs_unwarp_trimap_scratch_ints", "fs_unwarp_class_areas_scratch_ints",
+             "fs_unwarp_hd_scratch_ints", "fs_surface_hd_scratch_ints")
 
 
 class HipLibraryError(RuntimeError):
@@ -174,6 +177,10 @@ def load():
     lib.fs_unwarp_trimap_scratch_ints.argtypes = [_I] * 5
     lib.fs_unwarp_class_areas_scratch_ints.restype = _L
     lib.fs_unwarp_class_areas_scratch_ints.argtypes = [_I] * 6
+    lib.fs_unwarp_hd_scratch_ints.restype = _L
+    lib.fs_unwarp_hd_scratch_ints.argtypes = [_I] * 6
+    lib.fs_surface_hd_scratch_ints.restype = _L
+    lib.fs_surface_hd_scratch_ints.argtypes = [_I] * 3
     lib.fs_stream_wait.restype = _I
     lib.fs_stream_wait.argtypes = [_P, _P]
     lib.fs_set_deterministic.restype = _I

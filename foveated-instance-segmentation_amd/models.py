@@ -240,7 +240,7 @@ class DeformSegmentationModule(nn.Module):
         return labels
 
     @torch.no_grad()
-    def evaluate(self, img, focus, seg_label, cls_label, seg_size=None, return_labels=False, class_areas=False, trimap=None, trimap_frame=True):
+    def evaluate(self, img, focus, seg_label, cls_label, seg_size=None, return_labels=False, class_areas=False, hausdorff=None, trimap=None, trimap_frame=True):
         """Full-resolution scoring without the loss: predict's stages, then the four accuracies of forward's MODEL.upsample branch
         (models/models.py:378-474,869-873,1074-1083) taken against the label in the pass that would have written the class map
         (ops.unwarp_accuracy / fs_unwarp_accuracy): no (B,K,H,W) prediction, no class map and no ground-truth tensor exist.
@@ -268,7 +268,14 @@ class DeformSegmentationModule(nn.Module):
         ceiling (VAL.y_sampled_reverse, IoU(Y', Y): every pixel takes the sampled label of the grid point that feeds it -- what a
         perfect network behind this sampler would score), space 2 the prediction in the sampled space (Mean IoU_deformed); the lab
         rows of spaces 0 and 2 are the label distribution before and after sampling.  ops.class_scores_from_areas makes IoU and Dice,
-        train.ClassIoUMeter the dataset-level summary.  With the default the call, its result and its launches are unchanged."""
+        train.ClassIoUMeter the dataset-level summary.  With the default the call, its result and its launches are unchanged.
+
+        hausdorff (None, or the percentile: an int 1 .. 100, 95 for VAL.hd95) adds the surface-distance statistics of ops.surface_hd
+        for the predicted foreground (class != num_class - 1) against the label's (seg_label.long() != 0): the LAST element of the
+        result, after labels, trim and areas where those are present, is then hd (B,4) int64 = (n_pred, n_label, d2_lo, d2_hi) -- the
+        two borders' sizes and the two pooled squared distances np.percentile interpolates between, -1 where a border is empty.
+        ops.hd_from_stats makes the distance in pixels, train.HausdorffMeter the dataset mean.  It is the published 2-D definition,
+        not what the reference's uncalled utils.hd95 returns.  With the default the call is unchanged."""
         if seg_label.dim() not in (3, 4) or (seg_label.dim() == 4 and seg_label.shape[1] != 1):
             raise ValueError(f"seg_label must be (B,H,W) or (B,1,H,W), got {tuple(seg_label.shape)}")
         label_size = (int(seg_label.shape[-2]), int(seg_label.shape[-1]))
@@ -277,9 +284,9 @@ class DeformSegmentationModule(nn.Module):
         if seg_label.shape[0] != img.shape[0] or cls_label.shape[0] != img.shape[0]:
             raise ValueError(f"seg_label {tuple(seg_label.shape)} and cls_label {tuple(cls_label.shape)} must have img's batch size {img.shape[0]}")
         cls, m, grid, _ = self._head_parts(img, focus, label_size, "evaluate")
-        counts, acc, areas, trim, labels = ops.unwarp_count(cls, m, grid, seg_label, cls_label, dia_factor=trimap, frame=trimap_frame,
-                                                            areas=class_areas, return_labels=return_labels)
-        return (acc[0], acc[1], acc[2], acc[3], counts) + tuple(t for t in (labels, trim, areas) if t is not None)
+        counts, acc, areas, trim, labels, hd = ops.unwarp_count(cls, m, grid, seg_label, cls_label, dia_factor=trimap, frame=trimap_frame,
+                                                                areas=class_areas, return_labels=return_labels, hd_q=hausdorff)
+        return (acc[0], acc[1], acc[2], acc[3], counts) + tuple(t for t in (labels, trim, areas, hd) if t is not None)
 
     def forward(self, feed_dict, *, writer=None, segSize=None, F_Xlr_acc_map=False, count=None, epoch=None,
                 feed_dict_info=None, feed_batch_count=None, cur_iter=None, is_inference=False, rank=None):

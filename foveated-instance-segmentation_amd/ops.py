@@ -1484,13 +1484,22 @@ def unwarp_labels(cls, m, grid, Hs, Ws):
     return labels, hole
 
 
-def unwarp_count(cls, m, grid, y, cls_label, dia_factor=None, frame=True, areas=False, return_labels=False):
+def _hd_q(q):
+    if isinstance(q, bool) or int(q) != q or not 1 <= int(q) <= 100:
+        raise ValueError(f"the Hausdorff percentile must be an integer 1 .. 100, got {q!r}")
+    return int(q)
+
+
+def unwarp_count(cls, m, grid, y, cls_label, dia_factor=None, frame=True, areas=False, return_labels=False, hd_q=None):
     """The checks, allocations and call that unwarp_accuracy, unwarp_trimap and unwarp_class_areas share; models.py's evaluate() calls
-    it directly.  Internal to the package: the documented ops are those three.  dia_factor=None: no trimap.  The entry point is the
-    smallest that counts what is asked for: fs_unwarp_class_areas with areas, else fs_unwarp_trimap with a trimap, else
-    fs_unwarp_accuracy.  Returns the five-tuple (counts, acc, areas, trim, labels) in this order, None where not asked for."""
+    it directly.  Internal to the package: the documented ops are those three.  dia_factor=None: no trimap.  hd_q (None, or 1 .. 100):
+    the surface-distance statistics of surface_hd, prediction foreground (class != K-1) against label foreground.  The entry point is
+    the smallest that counts what is asked for: fs_unwarp_hd with hd_q, else fs_unwarp_class_areas with areas, else fs_unwarp_trimap
+    with a trimap, else fs_unwarp_accuracy.  Returns the six-tuple (counts, acc, areas, trim, labels, hd) in this order, None where not
+    asked for."""
     with_trim = dia_factor is not None
     D, fr = _trimap_args(dia_factor, frame) if with_trim else (0, 0)
+    q = _hd_q(hd_q) if hd_q is not None else None
     B, K = cls.shape
     _, h, w, _ = grid.shape
     if tuple(m.shape) != (B, h, w):
@@ -1510,8 +1519,11 @@ def unwarp_count(cls, m, grid, y, cls_label, dia_factor=None, frame=True, areas=
     area = torch.empty(B, 3, K, 3, device=dev, dtype=torch.int64) if areas else None
     trim = torch.empty(B, D + 1, 3, device=dev, dtype=torch.int64) if with_trim else None
     labels = torch.empty(B, Hs, Ws, device=dev, dtype=torch.int64) if return_labels else None
+    hd = torch.empty(B, 4, device=dev, dtype=torch.int64) if q is not None else None
     # (entry point, the dimensions its scratch query takes, its outputs after acc, its arguments after the dimensions)
-    if areas:
+    if q is not None:
+        name, qdims, outs, tail = "fs_unwarp_hd", (B, K, h, w, Hs, Ws), (area, trim, labels, hd), (D, fr, q)
+    elif areas:
         name, qdims, outs, tail = "fs_unwarp_class_areas", (B, K, h, w, Hs, Ws), (area, trim, labels), (D, fr)
     elif with_trim:
         name, qdims, outs, tail = "fs_unwarp_trimap", (B, h, w, Hs, Ws), (trim, labels), (D, fr)
@@ -1521,7 +1533,7 @@ def unwarp_count(cls, m, grid, y, cls_label, dia_factor=None, frame=True, areas=
     hip.call(name, hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(y.float().contiguous()),
              hip.ptr(cls_label.long().contiguous()), hip.ptr(counts), hip.ptr(acc), *(hip.ptr(t) for t in outs), hip.ptr(scratch),
              B, K, h, w, Hs, Ws, *tail)
-    return counts, acc, area, trim, labels
+    return counts, acc, area, trim, labels, hd
 
 
 def unwarp_accuracy(cls, m, grid, y, cls_label, return_labels=False):
@@ -1531,7 +1543,7 @@ def unwarp_accuracy(cls, m, grid, y, cls_label, return_labels=False):
     grid (B,h,w,2) as for unwarp_labels; y (B,Hs,Ws) or (B,1,Hs,Ws) the label mask at the output size; cls_label (B,) or (B,1).
     Returns (counts (B,6) int64 = cls_fg, bin_fg, union_fg, cls_bg, bin_bg, union_bg per image, acc (4,) fp32 = acc, acc_bin_fg,
     acc_cls_fbg, acc_bin_fbg as SegLoss's out[3:7]) and, with return_labels, the (B,Hs,Ws) int64 class map of unwarp_labels."""
-    counts, acc, _, _, labels = unwarp_count(cls, m, grid, y, cls_label, return_labels=return_labels)
+    counts, acc, _, _, labels, _ = unwarp_count(cls, m, grid, y, cls_label, return_labels=return_labels)
     return (counts, acc, labels) if return_labels else (counts, acc)
 
 
@@ -1570,7 +1582,7 @@ def unwarp_trimap(cls, m, grid, y, cls_label, dia_factor=5, frame=True, return_l
     with frame=True) has all-zero rows: the reference divides 0 by 0 there, trimap_from_counts and train.TrimapMeter leave it out."""
     if dia_factor is None:
         raise TypeError("unwarp_trimap needs dia_factor (0 .. 7); unwarp_accuracy is the op without a trimap")
-    counts, acc, _, trim, labels = unwarp_count(cls, m, grid, y, cls_label, dia_factor, frame, return_labels=return_labels)
+    counts, acc, _, trim, labels, _ = unwarp_count(cls, m, grid, y, cls_label, dia_factor, frame, return_labels=return_labels)
     return (counts, acc, trim, labels) if return_labels else (counts, acc, trim)
 
 
@@ -1593,7 +1605,7 @@ def unwarp_class_areas(cls, m, grid, y, cls_label, dia_factor=None, frame=True, 
     ceiling -- the label after the sampler and the nearest un-warp against itself (VAL.y_sampled_reverse, models/models_instance.py:909-918):
     every pixel takes grid_sample_label's value of the grid point that feeds it -- and space 2 the prediction in the sampled space
     (PredAssemble(cls, m).argmax(1) against the sampled ground truth).  A cls_label outside 0 .. K-1 has no lab / inter row."""
-    counts, acc, areas, trim, labels = unwarp_count(cls, m, grid, y, cls_label, dia_factor, frame, areas=True, return_labels=return_labels)
+    counts, acc, areas, trim, labels, _ = unwarp_count(cls, m, grid, y, cls_label, dia_factor, frame, areas=True, return_labels=return_labels)
     return (counts, acc, areas) + ((trim,) if trim is not None else ()) + ((labels,) if return_labels else ())
 
 
@@ -1606,6 +1618,45 @@ def class_scores_from_areas(areas):
     a = areas.to(torch.float64)
     inter, union = a[..., 0], a[..., 1] + a[..., 2] - a[..., 0]
     return inter / (union + 1e-10), 2 * inter / (union + inter + 1e-10)
+
+
+def surface_hd(a, b, q=95):
+    """The q-th percentile of the Hausdorff distances between the borders of two masks (HD95 at q = 95; VAL.hd95), as the integers it is
+    made of (fs_surface_hd; no autograd).  a, b (B,H,W) or (H,W), bool or uint8 (non-zero = foreground), on the device; H, W <= 16384.
+    The border of a mask is its foreground with a background 4-neighbour, outside the image counting as background; every border pixel
+    of either mask takes the squared distance to the nearest border pixel of the other, and the two sets are pooled.  Returns hd (B,4)
+    int64 = (n_a, n_b, d2_lo, d2_hi): the border sizes and the pooled squared distances at the two ranks np.percentile interpolates
+    between; d2 = -1 where a border is empty.  hd_from_stats makes the distance.  This is the published 2-D definition; the
+    reference's utils.hd95 flattens both masks before it erodes them and returns something else."""
+    q = _hd_q(q)
+    if a.dim() == 2 and b.dim() == 2:
+        a, b = a[None], b[None]
+    if a.dim() != 3 or a.shape != b.shape or a.numel() == 0:
+        raise ValueError(f"a {tuple(a.shape)} and b {tuple(b.shape)} must be two non-empty (B, H, W) masks of one shape")
+    if a.dtype not in (torch.bool, torch.uint8) or b.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"masks must be bool or uint8, got {a.dtype} and {b.dtype}")
+    B, Hs, Ws = (int(v) for v in a.shape)
+    fg = ((a != 0).to(torch.uint8) | ((b != 0).to(torch.uint8) << 1)).contiguous()
+    hd = torch.empty(B, 4, device=a.device, dtype=torch.int64)
+    scratch = torch.empty(hip.query("fs_surface_hd_scratch_ints", B, Hs, Ws), device=a.device, dtype=torch.int32)
+    hip.call("fs_surface_hd", hip.ptr(fg), hip.ptr(hd), hip.ptr(scratch), B, Hs, Ws, q)
+    return hd
+
+
+def hd_from_stats(hd, q=95):
+    """(B,4) surface statistics (surface_hd's / evaluate(hausdorff=q)'s, on any device) -> (B,) fp64: np.percentile(distances, q) =
+    sqrt(d2_lo) + (sqrt(d2_hi) - sqrt(d2_lo)) * frac with frac = (q (n-1) mod 100) / 100, n = n_a + n_b; NaN where a border is empty
+    (the reference raises there).  q must be the q the statistics were made with.  Plain torch."""
+    q = _hd_q(q)
+    if hd.dim() != 2 or hd.shape[1] != 4:
+        raise ValueError(f"hd must be (B, 4), got {tuple(hd.shape)}")
+    hd = hd.to(torch.int64)
+    n = hd[:, 0] + hd[:, 1]
+    frac = ((q * (n - 1)) % 100).to(torch.float64) / 100.0
+    empty = (hd[:, 0] <= 0) | (hd[:, 1] <= 0) | (hd[:, 2] < 0)
+    lo, hi = hd[:, 2].clamp(min=0).to(torch.float64).sqrt(), hd[:, 3].clamp(min=0).to(torch.float64).sqrt()
+    out = lo + (hi - lo) * frac
+    return torch.where(empty, torch.full_like(out, float("nan")), out)
 
 
 def image_accuracies_from_counts(counts):

@@ -362,8 +362,17 @@ def evaluate_step(module, batch, meter=None, trimap_meter=None, class_meter=None
     takes the counts (no host read).  With a TrimapMeter as `trimap_meter` the call is evaluate(trimap=trimap_meter.dia_factor,
     trimap_frame=trimap_meter.frame): the result ends with the trim counters, which that meter takes.  With a ClassIoUMeter as
     `class_meter` the call has class_areas=True as well: the class areas come last in the result and go to that meter."""
+    return evaluate_step_hd(module, batch, meter, trimap_meter, class_meter)
+
+
+@torch.no_grad()
+def evaluate_step_hd(module, batch, meter=None, trimap_meter=None, class_meter=None, hd_meter=None):
+    """evaluate_step with one more meter: with a HausdorffMeter as `hd_meter` the call has hausdorff=hd_meter.q as well, the surface
+    statistics come last in the result (after the class areas) and go to that meter.  Without it, evaluate_step itself."""
     X, Fp, Y, cls = batch
     extra = {} if class_meter is None else {"class_areas": True}
+    if hd_meter is not None:
+        extra["hausdorff"] = hd_meter.q
     if trimap_meter is None:
         out = module.evaluate(X[:, :3], Fp, Y, cls, **extra)
     else:
@@ -374,7 +383,9 @@ def evaluate_step(module, batch, meter=None, trimap_meter=None, class_meter=None
     if trimap_meter is not None:
         trimap_meter.update(out[5])
     if class_meter is not None:
-        class_meter.update(out[-1])
+        class_meter.update(out[-2 if hd_meter is not None else -1])
+    if hd_meter is not None:
+        hd_meter.update(out[-1])
     return out
 
 
@@ -583,6 +594,40 @@ class ClassIoUMeter:
         res["label_share_shift"] = [b - a for a, b in zip(full, samp)]
         res["images"] = int(n)
         return res
+
+
+class HausdorffMeter:
+    """Dataset-level Hausdorff percentile (HD95 at q = 95; VAL.hd95) from the surface statistics of module.evaluate(hausdorff=q) /
+    ops.surface_hd.  `update(hd)` adds a batch's (B,4) int64 statistics into device-resident sums -- the per-image distances
+    (ops.hd_from_stats, fp64) of the images where both borders exist, their number, and the numbers of images left out -- without a
+    host read; `result(reduce=True)` makes ONE all-reduce over the ranks and ONE host read.  It returns `hd`, the mean distance in
+    pixels over the images where both borders exist (nan without one), `images`, their number, and `skipped_empty_pred` /
+    `skipped_empty_label`, the images whose predicted / label mask has no border (an image with neither counts in both).  The
+    reference's function raises RuntimeError on an empty mask; here such an image is left out and counted, as the trimap's
+    empty-band images are."""
+
+    def __init__(self, device, q=95):
+        from . import ops
+        self.q = ops._hd_q(q)
+        self.sums = torch.zeros(4, device=device, dtype=torch.float64)           # distance sum, images, empty pred, empty label
+
+    def update(self, hd):
+        from . import ops
+        if hd.dim() != 2 or hd.shape[1] != 4:
+            raise ValueError(f"hd must be (B, 4), got {tuple(hd.shape)}")
+        hd = hd.to(device=self.sums.device, dtype=torch.int64)
+        d = ops.hd_from_stats(hd, self.q)
+        ok = ~torch.isnan(d)
+        self.sums.add_(torch.stack([torch.where(ok, d, torch.zeros_like(d)).sum(), ok.double().sum(),
+                                    (hd[:, 0] <= 0).double().sum(), (hd[:, 1] <= 0).double().sum()]))
+
+    def result(self, reduce=True):
+        tot = self.sums.clone()
+        if reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            dist.all_reduce(tot, op=dist.ReduceOp.SUM)
+        tot = tot.cpu().tolist()
+        return {"hd": tot[0] / tot[1] if tot[1] > 0 else float("nan"), "images": int(tot[1]), "skipped_empty_pred": int(tot[2]),
+                "skipped_empty_label": int(tot[3]), "q": self.q}
 
 
 # ----------------------------------------------------------------------------------------------

@@ -163,6 +163,30 @@ long fs_unwarp_class_areas_scratch_ints(int B, int K, int h, int w, int Hs, int 
 int fs_unwarp_class_areas(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label,
                           long long* counts, float* acc, long long* areas, long long* trim, long long* labels, int* scratch,
                           int B, int K, int h, int w, int Hs, int Ws, int D, int frame, fs_stream_t stream);
+/* Surface distance between two masks: the q-th percentile of the Hausdorff distances (HD95 at q = 95; VAL.hd95, utils.py:25-101), as
+ * the integers it is made of.  fg (B,Hs,Ws) bytes, any alignment: bit 0 = foreground of the first mask (the prediction), bit 1 = of
+ * the second (the label).  The border of a mask is its foreground with a background 4-neighbour, everything outside the image
+ * counting as background (foreground XOR binary_erosion by the cross); every border pixel of one mask takes the squared Euclidean
+ * distance d^2 to the nearest border pixel of the other, in both directions, and the two sets are pooled: n = n_pred + n_label
+ * integers.  hd (B,4) int64 = (n_pred, n_label, d2_lo, d2_hi): the pooled values of ranks lo = q (n-1) div 100 and hi = lo + (q (n-1)
+ * mod 100 != 0) in ascending order -- np.percentile(., q) is sqrt(d2_lo) + (sqrt(d2_hi) - sqrt(d2_lo)) * (q (n-1) mod 100) / 100 --
+ * and d2_lo = d2_hi = -1 where either border is empty.  This is the published 2-D definition, NOT what utils.hd95 returns: that
+ * function flattens both masks to 1-D before it erodes them, and nothing in the reference calls it.  Exact: a column pass (vertical
+ * distance to the nearest border pixel), a row pass (the exact minimum over the row, pruned once dx^2 alone reaches the best value), a
+ * two-level radix select over integer histograms with the row pass run once per level; no list of distances, integer atomics only,
+ * bit-reproducible.  q = 1 .. 100.  scratch = fs_surface_hd_scratch_ints(B, Hs, Ws) ints, 16-byte aligned.  FS_ERR_ARG, with nothing
+ * launched, for a null pointer, a misaligned scratch, q outside 1 .. 100, non-positive sizes, Hs > 16384 or Ws > 16384. */
+long fs_surface_hd_scratch_ints(int B, int Hs, int Ws);
+int fs_surface_hd(const unsigned char* fg, long long* hd, int* scratch, int B, int Hs, int Ws, int q, fs_stream_t stream);
+/* fs_unwarp_class_areas with fs_surface_hd of the prediction against the label behind the count pass: hd (B,4) int64 as there, the
+ * first mask being "fs_unwarp_labels' class is not K-1" and the second t = (long)y != 0, gathered into a byte map in scratch (no
+ * (B,Hs,Ws) class map exists).  areas, trim and labels are nullable: given, each is fs_unwarp_class_areas' bit for bit; counts and acc
+ * are fs_unwarp_accuracy's.  scratch = fs_unwarp_hd_scratch_ints(B, K, h, w, Hs, Ws) ints, 16-byte aligned (>= the class areas').
+ * FS_ERR_ARG as fs_unwarp_class_areas for what is given, as fs_surface_hd, and for a null hd. */
+long fs_unwarp_hd_scratch_ints(int B, int K, int h, int w, int Hs, int Ws);
+int fs_unwarp_hd(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
+                 float* acc, long long* areas, long long* trim, long long* labels, long long* hd, int* scratch, int B, int K, int h, int w,
+                 int Hs, int Ws, int D, int frame, int q, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 

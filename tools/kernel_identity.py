@@ -1,14 +1,15 @@
 """Are the gfx950 kernels of two builds the same device code, kernel by kernel?  For refactors that move kernels between
 translation units, where the whole-.text comparison of profiles/r13/README.md (a) no longer applies.
 
-    python tools/kernel_identity.py --before DIR_OF_PARENT_OBJECTS --after DIR_OF_THIS_TREES_OBJECTS [--only frontend,unwarp] [--md]
+    python tools/kernel_identity.py --before DIR_OF_PARENT_OBJECTS --after DIR_OF_THIS_TREES_OBJECTS [--only frontend,unwarp] [--md] [--allow-new]
 
 Every `*.o` of each directory is unbundled (llvm-objcopy --dump-section .hip_fatbin, clang-offload-bundler --unbundle of the
 hipv4-amdgcn-amd-amdhsa--gfx950 entry).  For every kernel symbol of `--before` (an STT_FUNC with a `<name>.kd` descriptor) the tool
 finds the symbol in `--after` -- exactly once, in whichever object -- and compares the symbol's bytes (st_value, st_size), its 64-byte
 kernel descriptor with the code offset left out (it is the distance from the descriptor to the code, which moves with the file's
 layout), and its entry of the `.note` metadata (llvm-readelf --notes: arguments, LDS, registers).  Objects whose kernel set is the same
-before and after are also compared as whole .text sections.  Exit status 1 if anything differs."""
+before and after are also compared as whole .text sections.  Exit status 1 if anything differs; a kernel that only `--after` has is a
+difference unless --allow-new is given (a change that adds kernels and must leave the existing ones alone)."""
 import argparse
 import glob
 import os
@@ -107,6 +108,7 @@ def main():
     ap.add_argument("--after", required=True)
     ap.add_argument("--only", default="", help="comma-separated object stems (default: all)")
     ap.add_argument("--md", action="store_true", help="print the per-kernel table as markdown")
+    ap.add_argument("--allow-new", action="store_true", help="kernels only --after has are listed, not counted as differences")
     args = ap.parse_args()
     only = set(filter(None, args.only.split(",")))
     bad = 0
@@ -134,7 +136,7 @@ def main():
         extra = sorted(set(where) - {r[0] for r in rows})
         for k in extra:
             rows.append((k, "-", where[k][0], 0, "only in --after"))
-            bad += 1
+            bad += not args.allow_new
         demangle = subprocess.run(["c++filt"] + [r[0] for r in rows], capture_output=True, text=True).stdout.split("\n") if rows else []
         if args.md:
             print("| kernel | object before | object after | bytes | |\n|---|---|---|---|---|")
