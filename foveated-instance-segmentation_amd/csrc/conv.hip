@@ -247,7 +247,9 @@ static int g_conv_precision = [] {
 }();
 
 // Deterministic mode (fs_set_deterministic; FS_DETERMINISTIC=1 read once at load): every reduction whose order depends on workgroup
-// arrival -- the split-K atomics of the bwd-weight kernels -- is replaced by per-split partial tiles summed in index order.
+// arrival is replaced by one with a fixed order.  There are three: the split-K atomics of the bwd-weight kernels (per-split partial
+// tiles summed in index order), the dbias atomics of fs_linear_bwd_weight_bias (bpart slabs, conv_wgrad.hip) and the query-range split
+// of the fp32 attention dK / dV (nsplit = 1, transformer.hip: fs_deterministic()).
 static int g_deterministic = [] { const char* e = getenv("FS_DETERMINISTIC"); return (e && e[0] == '1') ? 1 : 0; }();
 
 template <int MT>

@@ -252,8 +252,10 @@ def set_conv_precision(mode: str) -> None:
 
 
 def set_deterministic(on: bool) -> None:
-    """Bit-reproducible training steps (the reference's cudnn.deterministic = True): bwd-weight sums its split-K partial tiles in index
-    order instead of by fp32 atomics (include/fovealseg.h fs_set_deterministic)."""
+    """Bit-reproducible training steps (the reference's cudnn.deterministic = True).  The library's three arrival-order reductions take a
+    fixed order: bwd-weight sums its split-K partial tiles in index order instead of by fp32 atomics, the linear layer's bias gradient
+    (fs_linear_bwd_weight_bias) sums per-split slabs instead of atomics, and the fp32 attention backward does not split the query range
+    of dK / dV (include/fovealseg.h fs_set_deterministic).  tests/test_step_invariance.py holds whole training steps to it."""
     if load().fs_set_deterministic(1 if on else 0) != 0:
         raise HipLibraryError("fs_set_deterministic failed")
     _ws_cache.clear()

@@ -570,7 +570,16 @@ def pad_in_channels(x, w):
     if not PAD_ODD_CHANNELS or cin % 4 == 0 or w.shape[2] * w.shape[3] > 32 or hip.get_conv_precision() == "f32":
         return x, w          # aligned already, or a filter beyond the aligned kernels' 32 taps (7x7 ResNet stem): generic kernels
     cp = padded_in_channels(cin)
-    return torch.nn.functional.pad(x, (0, cp - cin)), PadWeightChannels.apply(w, cp)
+    xp = torch.nn.functional.pad(x, (0, cp - cin))
+    # the padded tensor stands for x in the layer: it keeps x's producer / fan-out records, so ConvBnAct registers itself as the fan-out's
+    # conv consumer (FAN_GEOM, FAN_DONE) as it does without padding.  Every reader of these records compares shapes before a kernel takes
+    # a tensor of the unpadded width (conv2d_bwd_data: src_bn; StashGrad / ConvBnAct.backward: the addend), so a padded layer keeps its
+    # own reduction pass and the fan-out adds the other alias's gradient
+    for tag in ("_fs_fan", "_fs_after_fan", "_fs_bn"):
+        v = getattr(x, tag, None)
+        if v is not None:
+            setattr(xp, tag, v)
+    return xp, PadWeightChannels.apply(w, cp)
 
 
 FANOUT = os.environ.get("FS_FANOUT", "1") != "0"
@@ -749,7 +758,9 @@ class StashGrad(Function):
     convolution's bwd-data adds it in its epilogue (one read) instead of FanOut.backward adding two 1.57 GB tensors in a pass of its own
     (806 us per configs[1] step).  The branch behind this node must run its backward BEFORE the convolution's: put the node in the forward
     AFTER the convolution branch (the engine runs ready nodes in reverse order of creation); if the convolution's backward came first anyway
-    (FAN_DONE), the gradient is returned as usual and the fan-out adds it."""
+    (FAN_DONE), the gradient is returned as usual and the fan-out adds it.  Likewise when no convolution registered itself as the fan-out's
+    conv consumer (FAN_GEOM), or when that convolution reads a zero-padded copy of the tensor (pad_in_channels: another channel count than
+    this gradient's): a stash nobody pops would be a gradient that is never added."""
 
     @staticmethod
     def forward(ctx, x, fan_id):
@@ -759,6 +770,9 @@ class StashGrad(Function):
     @staticmethod
     def backward(ctx, g):
         if g is None or ctx.fan_id in FAN_DONE or ctx.fan_id in PENDING_RES or not (FUSE_BN_BWD_SUMS and FANOUT):
+            return g, None
+        geom = FAN_GEOM.get(ctx.fan_id)
+        if geom is None or tuple(geom[0]) != tuple(g.shape):
             return g, None
         PENDING_RES[ctx.fan_id] = (g if g.is_contiguous() else g.contiguous(), None)
         return None, None

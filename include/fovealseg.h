@@ -208,10 +208,16 @@ int fs_get_conv_precision(void);
  * engine's stream guards).  Used to run a small layer's weight gradient beside the bwd-data chain. */
 int fs_stream_wait(fs_stream_t waiter, fs_stream_t signaller);
 /* Deterministic mode -- the reference asks for it with torch.backends.cudnn.deterministic = True (train_deform_semantic.py:680-681).
- * By default the bwd-weight kernels add their split-K partial tiles with fp32 atomics, whose order is the workgroups' arrival order:
- * two runs of the same step differ in the last bits of the weight gradients.  on = 1 (or FS_DETERMINISTIC=1 in the environment at
- * load time): every split writes its partial tile to its own slab of a caller-provided scratch and the slabs are summed in index
- * order; every other reduction of the library is order-fixed in both modes.  Two runs of a training step are then bit-identical.
+ * By default three reductions add with fp32 atomics, whose order is the workgroups' arrival order, so two runs of the same step differ
+ * in the last bits of the gradients:
+ *   (1) the split-K partial tiles of the bwd-weight kernels (fs_conv2d_bwd_weight, fs_linear_bwd_weight_bias: dW);
+ *   (2) the bias gradient of fs_linear_bwd_weight_bias (dbias: one column sum per split and wave);
+ *   (3) dK / dV of the fp32 attention backward (fs_attention_bwd), when the query range is split to fill the chip.
+ * on = 1 (or FS_DETERMINISTIC=1 in the environment at load time): (1) every split writes its partial tile to its own slab of a
+ * caller-provided scratch and the slabs are summed in index order; (2) likewise for the column sums (slabs in the same scratch,
+ * fs_linear_bwd_weight_bias_ws_bytes); (3) the query range is not split (one workgroup per key chunk, plain stores).  Every other
+ * reduction of the library is order-fixed in both modes.  Two runs of a training step are then bit-identical, whatever stream a
+ * gradient was produced on (tests/test_step_invariance.py holds the three encoders' steps to that).
  * Process-global host-side word like the precision mode (same rules); costs one memset + one reduce launch per bwd-weight call. */
 int fs_set_deterministic(int on);
 int fs_get_deterministic(void);

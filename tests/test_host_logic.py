@@ -543,7 +543,9 @@ def test_stash_grad_hands_the_second_reader_gradient_to_the_conv_consumer():
     """ops.StashGrad (C1: `feat` read by the mask branch's conv and by the classification branch) on CPU tensors, with a stand-in for the conv
     consumer that does what ConvBnAct.backward does with the fan-out's records: (a) stash node created AFTER the conv branch in the forward ->
     the engine runs it first, the conv consumer finds the gradient in PENDING_RES and the fan-out adds nothing; (b) created BEFORE it -> the
-    conv consumer runs first (FAN_DONE), the gradient is returned as usual and the fan-out adds it.  Same result both ways."""
+    conv consumer runs first (FAN_DONE), the gradient is returned as usual and the fan-out adds it.  Same result both ways.  (c) NO conv
+    consumer registered itself for the fan-out (FAN_GEOM has no entry: C1's 3x3 conv reading a zero-padded copy that lost the fan tag), or
+    the registered one reads another shape than the gradient's -> the gradient is returned, nothing is stashed, the fan-out adds it."""
     import fovealseg  # noqa: F401
     from fovealseg import ops
 
@@ -554,6 +556,7 @@ def test_stash_grad_hands_the_second_reader_gradient_to_the_conv_consumer():
         def forward(ctx, x, k):
             ctx.fan = getattr(x, "_fs_fan", None)
             ctx.k = k
+            ops.FAN_GEOM[ctx.fan[0]] = (tuple(x.shape), (1, 1, 1, 1), 1, 0, 1)      # as ConvBnAct.forward registers the conv consumer
             return x * k
 
         @staticmethod
@@ -588,3 +591,23 @@ def test_stash_grad_hands_the_second_reader_gradient_to_the_conv_consumer():
     assert log == ["conv"], log
     assert torch.equal(ga, want) and torch.equal(gb, want)
     ops.reset_step_state()
+
+    # (c) the other alias is read by something that never looks at PENDING_RES
+    def run_without_conv_consumer(geom):
+        ops.reset_step_state()
+        x = torch.arange(8, dtype=torch.float32).view(2, 4).requires_grad_(True)
+        h = x * 1.0
+        fa, fb = ops.fan_out(h, 2)
+        fan = fa._fs_fan
+        if geom is not None:
+            ops.FAN_GEOM[fan[0]] = geom
+        y1 = fa * 3.0                                  # a plain consumer: pops nothing
+        fb = ops.StashGrad.apply(fb, fan[0])
+        y2 = (fb * fb).sum()
+        (y1.sum() + y2).backward()
+        assert not ops.PENDING_RES, "a gradient was stashed for a conv consumer that does not exist"
+        ops.reset_step_state()                         # ... so the next forward has nothing to complain about
+        return x.grad.clone()
+
+    assert torch.equal(run_without_conv_consumer(None), want)
+    assert torch.equal(run_without_conv_consumer(((2, 8), (1, 1, 1, 1), 1, 0, 1)), want)      # a consumer of a padded copy: other shape
