@@ -10,7 +10,9 @@
 //   trimap bands which band of width 1, 2, 4 .. 2^D around the label's boundary a pixel lies in     (eval.py:41-67)
 //   surface      the q-th percentile of the distances between two masks' borders (HD95), as two integer order statistics of d^2
 //                                                                                            (VAL.hd95; utils.py:25-101, in 2-D)
-// Host side: fs_unwarp_labels / _accuracy / _trimap / _class_areas / _hd are one launch sequence with optional parts.  unwarp_plan() derives
+//   instance     the mask "class is not K-1" gathered into bit words, its area, box and uncompressed COCO run-length code, and the head's
+//                class: the label-free output as a record (no counterpart in the reference; the code's format is the published one)
+// Host side: fs_unwarp_labels / _accuracy / _trimap / _class_areas / _hd / _instances are one launch sequence with optional parts.  unwarp_plan() derives
 // every size, scratch offset and limit from the shape and the feature set, UnwarpJob carries the caller's pointers, unwarp_run()
 // checks both and launches.  A refused call launches nothing: every check, fs_trimap_bands' included, comes before the first launch.
 #include "common.h"
@@ -1012,6 +1014,209 @@ __global__ __launch_bounds__(256) void hd_select2_kernel(const int* __restrict__
   }
 }
 
+// ---- the gazed instance as a record: bit mask, class, area, box and COCO run-length code (fs_unwarp_instances) ------------------------
+// The label-free output without a class map.  The mask "class is not K-1" is gathered straight into bit words, 32 columns a word, rows
+// pitched to P = ceil(Ws / 32) words with the bits past Ws clear; the statistics and the run-length code are made from the words, and
+// the class is the head's own decision.  The uncompressed COCO code reads the mask column-major (p = x * Hs + y) and lists the
+// distances between the boundaries T = {p : v[p] != v[p-1]}, v[-1] = 0 (format restated from its published definition; unpinned).
+//   bits     unwarp_fg_kernel's gather; a thread's four predicates are a nibble, eight lanes' nibbles a word (unwarp_bits_kernel), or
+//            the same words from a byte mask (mask_bits_kernel)
+//   count    one thread per (column, RLE_SEG-row segment): the boundaries in it, the position of its last one, its set pixels and
+//            their row range (rle_walk_kernel<false>)
+//   scan     one workgroup per image over its items in column-major order, which is the order of the runs: the exclusive sum of the
+//            boundary counts = where an item's first count goes, the running maximum of the last positions = the boundary before it;
+//            the same sweep sums the area, takes the box, and writes stats and the closing count (rle_scan_kernel)
+//   store    the walk again, storing counts[offset + i] = boundary - the one before, below cap (rle_walk_kernel<true>)
+// Plain stores only: the same bits in any order.  counts is zeroed by the launcher, so everything past the code reads 0.
+constexpr int RLE_SEG = 64;                            // rows per item: 16 items a column at 1024 rows
+
+// bits[b,y,i]: VEC (Ws % 4 == 0, 16-byte aligned owner / rowx): eight lanes a word, lane l the columns 32 i + 4 l .. + 3 of row y; a
+// quad is inside the row or past its end as a whole.  Otherwise one lane a column and a ballot, two words a wave.  No thread leaves
+// before the shuffles / the ballot.  words = B * Hs * P.
+template <bool VEC>
+__global__ __launch_bounds__(256) void unwarp_bits_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
+                                                          unsigned int* __restrict__ bits, int Hs, int Ws, int P, int hw, int K, long words) {
+  const int bg = K - 1;
+  const int per = Hs * Ws;
+  if (VEC) {
+    const long g = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
+    const int l = threadIdx.x & 7;
+    unsigned int nib = 0u;
+    if (g < words) {
+      const long row = g / P;                          // b * Hs + y
+      const int x = 32 * (int)(g - row * P) + 4 * l;
+      if (x < Ws) {
+        const long b = row / Hs;
+        const int y = (int)(row - b * Hs);
+        const int* ob = owner + b * per;
+        const int* db = dec + b * (hw + 1);
+        const int4 o4 = *reinterpret_cast<const int4*>(ob + y * Ws + x);
+        int q[4] = {o4.x, o4.y, o4.z, o4.w};
+        const int holes = (o4.x < 0) | (o4.y < 0) << 1 | (o4.z < 0) << 2 | (o4.w < 0) << 3;
+        if (holes) {
+          int src[4];
+          nearest_claimed4(rowx + b * per, y, x, Hs, Ws, holes, src);
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) nib |= (unsigned int)(db[q[k]] != bg) << k;
+      }
+    }
+    unsigned int wd = nib << (4 * l);
+    wd |= __shfl_xor(wd, 1, 64); wd |= __shfl_xor(wd, 2, 64); wd |= __shfl_xor(wd, 4, 64);
+    if (l == 0 && g < words) bits[g] = wd;
+  } else {
+    const long g = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
+    bool f = false;
+    if (g < words) {
+      const long row = g / P;
+      const int x = 32 * (int)(g - row * P) + (int)(threadIdx.x & 31);
+      if (x < Ws) {
+        const long b = row / Hs;
+        const int y = (int)(row - b * Hs);
+        const int* ob = owner + b * per;
+        f = unwarp_class_at(ob, rowx + b * per, dec + b * (hw + 1), ob[y * Ws + x], y, x, Hs, Ws, hw) != bg;
+      }
+    }
+    const unsigned long long bal = __ballot(f);
+    if ((threadIdx.x & 31) == 0 && g < words) bits[g] = (unsigned int)(bal >> (threadIdx.x & 32));
+  }
+}
+// the same words from a byte mask (non-zero = set), any alignment: one lane a column and a ballot
+__global__ __launch_bounds__(256) void mask_bits_kernel(const unsigned char* __restrict__ mask, unsigned int* __restrict__ bits, int Ws, int P,
+                                                        long words) {
+  const long g = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
+  bool f = false;
+  if (g < words) {
+    const long row = g / P;
+    const int x = 32 * (int)(g - row * P) + (int)(threadIdx.x & 31);
+    if (x < Ws) f = mask[row * Ws + x] != 0;
+  }
+  const unsigned long long bal = __ballot(f);
+  if ((threadIdx.x & 31) == 0 && g < words) bits[g] = (unsigned int)(bal >> (threadIdx.x & 32));
+}
+// cat[b] = the first maximal k < K-1 of cls[b,k], NaN maximal: unwarp_decide_kernel's comparison on the planes themselves
+__global__ __launch_bounds__(256) void instance_cat_kernel(const float* __restrict__ cls, long long* __restrict__ cat, int B, int K) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const float* c = cls + (long)b * K;
+  float best = 0.f;
+  int arg = 0;
+  for (int k = 0; k < K - 1; ++k) {
+    const float v = c[k];
+    if (k == 0 || v > best || (v != v && best == best)) { best = v; arg = k; }
+  }
+  cat[b] = arg;
+}
+// Item (x, s) = rows s * RLE_SEG .. of column x, item index x * S + s: column-major.  Lanes take neighbouring columns of one segment, so a
+// wave reads two words a row.  The pixel above the top of column x > 0 is the bottom of column x - 1; above pixel (0,0) it is 0.
+// STORE = false: cnt[item] = boundaries in the item, last[item] = position of its last one (0 without: no boundary lies before
+// position 0, and positions only grow along the items), st[item] = set pixels | (first set row in the segment) << 8 | (last) << 16.
+// STORE = true: cnt / last hold the scan's results (see rle_scan_kernel), and the item's i-th boundary at position p stores
+// counts[cnt + i] = p - the boundary before it, where cnt + i < cap.
+template <bool STORE>
+__global__ __launch_bounds__(256) void rle_walk_kernel(const unsigned int* __restrict__ bits, int* __restrict__ cnt, int* __restrict__ last,
+                                                       int* __restrict__ st, int* __restrict__ counts, int Hs, int Ws, int P, int S,
+                                                       int blocks_per_image, int cap) {
+  const int b = blockIdx.x / blocks_per_image;
+  const int g = (blockIdx.x - b * blocks_per_image) * 256 + (int)threadIdx.x;
+  const int M = Ws * S;
+  if (g >= M) return;
+  const int s = g / Ws, x = g - s * Ws;
+  const long item = (long)b * M + (long)x * S + s;
+  const unsigned int* ib = bits + (long)b * Hs * P;
+  const unsigned int* col = ib + (x >> 5);
+  const int sh = x & 31;
+  const int y0 = s * RLE_SEG, y1 = min(y0 + RLE_SEG, Hs);
+  unsigned int prev = 0u;
+  if (s > 0) prev = (col[(long)(y0 - 1) * P] >> sh) & 1u;
+  else if (x > 0) prev = (ib[(long)(Hs - 1) * P + ((x - 1) >> 5)] >> ((x - 1) & 31)) & 1u;
+  int n = 0, pos = 0, area = 0, ylo = 0, yhi = 0;
+  int* out = nullptr;
+  if (STORE) { n = cnt[item]; pos = last[item]; out = counts + (long)b * cap; }
+  const int p0 = x * Hs;
+  for (int y = y0; y < y1; ++y) {
+    const unsigned int v = (col[(long)y * P] >> sh) & 1u;
+    if (v != prev) {
+      if (STORE) {
+        if (n < cap) out[n] = p0 + y - pos;
+      }
+      pos = p0 + y;
+      ++n;
+    }
+    if (!STORE && v) {
+      if (area == 0) ylo = y - y0;
+      yhi = y - y0;
+      ++area;
+    }
+    prev = v;
+  }
+  if (!STORE) { cnt[item] = n; last[item] = pos; st[item] = area | ylo << 8 | yhi << 16; }
+}
+// One workgroup per image; thread t owns the items [t * chunk, (t+1) * chunk) of its M = Ws * S.  cnt[item] <- the boundaries before the
+// item, last[item] <- the position of the last boundary before it (0 = none: the code's first count is T[0] - 0).  stats[b] = (area,
+// x0, y0, bw, bh, n_runs) and counts[b, n_runs - 1] = N - the last boundary, where it lies below cap.
+__global__ __launch_bounds__(256) void rle_scan_kernel(int* __restrict__ cnt, int* __restrict__ last, const int* __restrict__ st,
+                                                       long long* __restrict__ stats, int* __restrict__ counts, int Hs, int Ws, int S, int cap) {
+  __shared__ int psum[256], pmax[256];
+  __shared__ long long red[16];
+  __shared__ int box[4];                               // max of: Ws - x, x + 1, Hs - y, y + 1 over the set pixels; 0 = none
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int M = Ws * S;
+  int* c = cnt + (long)b * M;
+  int* l = last + (long)b * M;
+  const int* sp = st + (long)b * M;
+  const int chunk = (M + 255) / 256;
+  const int i0 = min(tid * chunk, M), i1 = min(i0 + chunk, M);
+  if (tid < 4) box[tid] = 0;
+  int sum = 0, mx = 0, bx[4] = {0, 0, 0, 0};
+  long long area = 0;
+  for (int i = i0; i < i1; ++i) {
+    sum += c[i];
+    mx = max(mx, l[i]);
+    const int w = sp[i], a = w & 255;
+    if (a) {
+      const int x = i / S, yb = (i - x * S) * RLE_SEG;
+      area += a;
+      bx[0] = max(bx[0], Ws - x); bx[1] = max(bx[1], x + 1);
+      bx[2] = max(bx[2], Hs - (yb + ((w >> 8) & 255))); bx[3] = max(bx[3], yb + ((w >> 16) & 255) + 1);
+    }
+  }
+  psum[tid] = sum; pmax[tid] = mx;
+  __syncthreads();
+  if (area) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) atomicMax(&box[q], bx[q]);
+  }
+  if (tid == 0) {                                      // exclusive sum and exclusive running maximum over the 256 chunks
+    int cs = 0, cm = 0;
+    for (int t = 0; t < 256; ++t) {
+      const int vs = psum[t], vm = pmax[t];
+      psum[t] = cs; pmax[t] = cm;
+      cs += vs; cm = max(cm, vm);
+    }
+  }
+  __syncthreads();
+  int run = psum[tid], pm = pmax[tid];
+  for (int i = i0; i < i1; ++i) {
+    const int n = c[i], p = l[i];
+    c[i] = run; l[i] = pm;
+    run += n; pm = max(pm, p);
+  }
+  area = block_sum<long long>(area, red);
+  if (tid == 255) {                                    // its run / pm have passed every item: |T| and T[last]
+    long long* o = stats + (long)b * 6;
+    const bool any = area != 0;
+    o[0] = area;
+    o[1] = any ? Ws - box[0] : 0; o[2] = any ? Hs - box[2] : 0;
+    o[3] = any ? box[1] - (Ws - box[0]) : 0; o[4] = any ? box[3] - (Hs - box[2]) : 0;
+    o[5] = (long long)run + 1;
+    if (run < cap) counts[(long)b * cap + run] = Hs * Ws - pm;
+  }
+}
+
 // ---- host: one plan, one job, one launcher -------------------------------------------------------------------------------------------
 constexpr long INT_LIMIT = 2147483647L;                // pixel / point indices are ints
 constexpr long THREADS_MAX = 4294967295L - 255;        // every launch: fewer than 2^32 work-items
@@ -1055,11 +1260,31 @@ SurfacePlan surface_plan(int B, int Hs, int Ws) {
   return s;
 }
 
+// fs_mask_bits' / fs_mask_rle's sizes.  Scratch of the run-length passes, in ints: cnt, last, st, each [B][M], M = Ws * S items an image.
+struct RlePlan {
+  long P, words;                                       // words per row, of the batch
+  long S, M, bpi;                                      // segments per column, items and walk workgroups per image
+  long cnt, last, st, total;
+  bool bits_ok, ok;                                    // launchable: the bit packing, the run-length passes
+};
+RlePlan rle_plan(int B, int Hs, int Ws) {
+  RlePlan r = {};
+  if (!(B > 0 && Hs > 0 && Ws > 0)) return r;
+  r.P = cdiv(Ws, 32), r.words = (long)B * Hs * r.P;
+  r.S = cdiv(Hs, RLE_SEG), r.M = (long)Ws * r.S, r.bpi = cdiv(r.M, 256);
+  r.cnt = 0, r.last = (long)B * r.M, r.st = 2 * r.last, r.total = 3 * r.last;
+  r.bits_ok = r.words * 32 <= THREADS_MAX;             // one lane a bit slot in the ballot kernels
+  // positions and counts are ints: N < 2^31 (so M is one too)
+  r.ok = (long)Hs * Ws <= INT_LIMIT && (long)B * r.bpi * 256 <= THREADS_MAX;
+  return r;
+}
+
 // What a call computes on top of the class-map gather.  UW_COUNT: the gather counts (fs_unwarp_accuracy); UW_TRIM / UW_AREA: it also
 // buckets by trimap band / sums class areas; UW_HD: a foreground byte map and the surface distances behind the count pass.  Each
 // feature appends its regions to the scratch of the one before; UW_AREA's layout keeps UW_TRIM's regions whether or not the call has a
-// trimap, and UW_HD's come after whatever the other features of the call take.
-enum : unsigned { UW_LABELS = 0, UW_COUNT = 1, UW_TRIM = 2, UW_AREA = 4, UW_HD = 8 };
+// trimap, and UW_HD's come after whatever the other features of the call take.  UW_BITS (fs_unwarp_instances): the gather stores bit
+// words instead of classes, and the run-length passes follow; its regions come last of all, and it goes with no counting feature.
+enum : unsigned { UW_LABELS = 0, UW_COUNT = 1, UW_TRIM = 2, UW_AREA = 4, UW_HD = 8, UW_BITS = 16 };
 
 struct UnwarpPlan {
   int B, K, h, w, Hs, Ws;
@@ -1072,9 +1297,11 @@ struct UnwarpPlan {
   long trec, band, inter;                              // UW_TRIM: [B*cpi][TRIM_REC], n band bytes, TrimapPlan::ints
   long arec, atab;                                     // UW_AREA: [B*cpi][AREA_REC], [B][K] sums of the other predicted classes' pixels
   long fg, hds;                                        // UW_HD: n foreground bytes, SurfacePlan::total
+  long bitw, rles;                                     // UW_BITS: RlePlan::words bit words (used when the caller keeps none), RlePlan::total
   long total;
   TrimapPlan tri;
   SurfacePlan sp;
+  RlePlan rle;
   bool ok;                                             // launchable: sizes and limits (pointers are the job's)
 };
 UnwarpPlan unwarp_plan(int B, int K, int h, int w, int Hs, int Ws, unsigned features) {
@@ -1097,12 +1324,17 @@ UnwarpPlan unwarp_plan(int B, int K, int h, int w, int Hs, int Ws, unsigned feat
     p.sp = surface_plan(B, Hs, Ws);
     p.fg = align4(p.total), p.hds = p.fg + align4((p.n + 3) / 4), p.total = p.hds + p.sp.total;
   }
+  if (features & UW_BITS) {
+    p.rle = rle_plan(B, Hs, Ws);
+    p.bitw = align4(p.total), p.rles = p.bitw + align4(p.rle.words), p.total = p.rles + p.rle.total;
+  }
   // a workgroup's last trip of the count pass may start up to a chunk past the end
   const long per_max = INT_LIMIT - (features & UW_COUNT ? UACC_CHUNK : 0);
   p.ok = K >= 2 && K <= UNWARP_MAX_K && row_fits_lds(Ws) && (long)h * w < INT_LIMIT && p.per < per_max && p.n <= THREADS_MAX &&
          (long)B * Hs * 256 <= THREADS_MAX && (long)B * p.bpi * 256 <= THREADS_MAX &&
          (!(features & UW_COUNT) || (long)B * p.cpi * 256 <= THREADS_MAX) && (!(features & UW_TRIM) || p.tri.ok) &&
-         (!(features & UW_HD) || ((features & UW_COUNT) && p.sp.ok));
+         (!(features & UW_HD) || ((features & UW_COUNT) && p.sp.ok)) &&
+         (!(features & UW_BITS) || (features == UW_BITS && p.rle.bits_ok && p.rle.ok));
   return p;
 }
 
@@ -1115,6 +1347,7 @@ struct UnwarpJob {
   struct { long long* out; int D, frame; } trim;                                                // UW_TRIM
   struct { long long* out; } areas;                                                             // UW_AREA
   struct { long long* out; int q; } hd;                                                         // UW_HD
+  struct { long long *cat, *stats; int* counts; unsigned int* bits; int cap; } inst;            // UW_BITS; bits optional
 };
 
 bool trimap_args_ok(int D, int frame) { return D >= 0 && D <= TRI_MAX_D && (frame == 0 || frame == 1); }
@@ -1160,6 +1393,30 @@ int surface_launch(const SurfacePlan& sp, const unsigned char* fg, long long* hd
   return FS_OK;
 }
 
+int mask_bits_launch(const RlePlan& r, const unsigned char* mask, unsigned int* bits, int Ws, hipStream_t stream) {
+  hipLaunchKernelGGL(mask_bits_kernel, dim3(cdiv(r.words, 8)), dim3(256), 0, stream, mask, bits, Ws, (int)r.P, r.words);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+// zeroed counts, then count, scan, store
+int rle_launch(const RlePlan& r, const unsigned int* bits, long long* stats, int* counts, int* s, int B, int Hs, int Ws, int cap,
+               hipStream_t stream) {
+  const hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)B * cap, stream);
+  if (e != hipSuccess) return (int)e;
+  const dim3 grid((unsigned)(B * r.bpi));
+  hipLaunchKernelGGL(rle_walk_kernel<false>, grid, dim3(256), 0, stream, bits, s + r.cnt, s + r.last, s + r.st, counts, Hs, Ws, (int)r.P,
+                     (int)r.S, (int)r.bpi, cap);
+  FS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rle_scan_kernel, dim3((unsigned)B), dim3(256), 0, stream, s + r.cnt, s + r.last, s + r.st, stats, counts, Hs, Ws, (int)r.S,
+                     cap);
+  FS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rle_walk_kernel<true>, grid, dim3(256), 0, stream, bits, s + r.cnt, s + r.last, s + r.st, counts, Hs, Ws, (int)r.P,
+                     (int)r.S, (int)r.bpi, cap);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
 // owner = -1, then every grid point's claim
 int claim_owners(const float* grid, int* owner, int B, int h, int w, int Hs, int Ws, hipStream_t stream) {
   const hipError_t e = hipMemsetAsync(owner, 0xFF, sizeof(int) * (size_t)B * Hs * Ws, stream);
@@ -1198,11 +1455,14 @@ const CountKernel COUNT_KERNELS[8] = {
     unwarp_count_kernel<true, true, false>,   unwarp_count_kernel<false, false, true>, unwarp_count_kernel<true, false, true>,
     unwarp_count_kernel<false, true, true>,   unwarp_count_kernel<true, true, true>};
 
-// The launches of the five entry points: [trimap bands,] prelude, then either the class map or the count pass and its finalizers
-// (the trimap's and the areas' after the accuracies'), then with UW_HD the foreground bytes and the surface distances.
+// The launches of the six entry points: [trimap bands,] prelude, then either the class map, or with UW_BITS the bit words, the class
+// and the run-length passes, or the count pass and its finalizers (the trimap's and the areas' after the accuracies'), then with UW_HD
+// the foreground bytes and the surface distances.
 int unwarp_run(const UnwarpPlan& p, const UnwarpJob& j, hipStream_t stream) {
   const bool count = p.features & UW_COUNT, trim = p.features & UW_TRIM, area = p.features & UW_AREA, hdq = p.features & UW_HD;
-  FS_REQUIRE(p.ok && j.cls && j.m && j.grid && j.scratch && (count || j.labels.map));
+  const bool inst = p.features & UW_BITS;
+  FS_REQUIRE(p.ok && j.cls && j.m && j.grid && j.scratch && (count || inst || j.labels.map));
+  FS_REQUIRE(!inst || (j.inst.cat && j.inst.stats && j.inst.counts && j.inst.cap >= 1));
   // the records are stored and read 16 bytes at a time
   FS_REQUIRE(!count || (j.count.y && j.count.cls_label && j.count.counts && j.count.acc && ((uintptr_t)j.scratch & 15) == 0));
   FS_REQUIRE((!trim || (j.trim.out && trimap_args_ok(j.trim.D, j.trim.frame))) && (!area || j.areas.out));
@@ -1211,6 +1471,17 @@ int unwarp_run(const UnwarpPlan& p, const UnwarpJob& j, hipStream_t stream) {
   unsigned char* band = trim ? reinterpret_cast<unsigned char*>(s + p.band) : nullptr;
   if (trim) FS_TRY(trimap_launch(p.tri, j.count.y, band, reinterpret_cast<unsigned char*>(s + p.inter), p.B, p.Hs, p.Ws, j.trim.D, j.trim.frame, stream));
   FS_TRY(unwarp_prelude(p, j, stream));
+  if (inst) {
+    unsigned int* bits = j.inst.bits ? j.inst.bits : reinterpret_cast<unsigned int*>(s + p.bitw);
+    // four pixels a thread need whole 16-byte rows of owner and rowx
+    const bool vec4 = p.Ws % 4 == 0 && ((uintptr_t)s & 15) == 0;
+    hipLaunchKernelGGL(vec4 ? unwarp_bits_kernel<true> : unwarp_bits_kernel<false>, dim3(cdiv(p.rle.words, vec4 ? 32 : 8)), dim3(256), 0, stream,
+                       s + p.owner, s + p.rowx, s + p.dec, bits, p.Hs, p.Ws, (int)p.rle.P, p.h * p.w, p.K, p.rle.words);
+    FS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(instance_cat_kernel, dim3(cdiv(p.B, 256)), dim3(256), 0, stream, j.cls, j.inst.cat, p.B, p.K);
+    FS_LAUNCH_CHECK();
+    return rle_launch(p.rle, bits, j.inst.stats, j.inst.counts, s + p.rles, p.B, p.Hs, p.Ws, j.inst.cap, stream);
+  }
   if (!count) {
     hipLaunchKernelGGL(unwarp_label_kernel, dim3(cdiv(p.n, 256)), dim3(256), 0, stream, s + p.owner, s + p.rowx, s + p.dec, j.labels.map,
                        j.labels.hole, p.n, p.Hs, p.Ws, p.h * p.w);
@@ -1332,6 +1603,25 @@ int fs_unwarp_hd(const float* cls, const float* m, const float* grid, const floa
                  int D, int frame, int q, hipStream_t stream) {
   return unwarp_run(unwarp_plan(B, K, h, w, Hs, Ws, UW_COUNT | UW_HD | (areas ? UW_AREA : 0) | (trim ? UW_TRIM : 0)),
                     {cls, m, grid, scratch, {labels}, {y, cls_label, counts, acc}, {trim, D, frame}, {areas}, {hd, q}}, stream);
+}
+
+int fs_mask_bits(const unsigned char* mask, unsigned int* bits, int B, int Hs, int Ws, hipStream_t stream) {
+  const RlePlan r = rle_plan(B, Hs, Ws);
+  FS_REQUIRE(mask && bits && r.bits_ok);
+  return mask_bits_launch(r, mask, bits, Ws, stream);
+}
+
+long fs_mask_rle_scratch_ints(int B, int Hs, int Ws) { return rle_plan(B, Hs, Ws).total; }
+int fs_mask_rle(const unsigned int* bits, long long* stats, int* counts, int* scratch, int B, int Hs, int Ws, int cap, hipStream_t stream) {
+  const RlePlan r = rle_plan(B, Hs, Ws);
+  FS_REQUIRE(bits && stats && counts && scratch && r.ok && cap >= 1);
+  return rle_launch(r, bits, stats, counts, scratch, B, Hs, Ws, cap, stream);
+}
+
+long fs_unwarp_instances_scratch_ints(int B, int h, int w, int Hs, int Ws) { return unwarp_plan(B, 2, h, w, Hs, Ws, UW_BITS).total; }
+int fs_unwarp_instances(const float* cls, const float* m, const float* grid, long long* cat, long long* stats, int* counts, unsigned int* bits,
+                        int* scratch, int B, int K, int h, int w, int Hs, int Ws, int cap, hipStream_t stream) {
+  return unwarp_run(unwarp_plan(B, K, h, w, Hs, Ws, UW_BITS), {cls, m, grid, scratch, {}, {}, {}, {}, {}, {cat, stats, counts, bits, cap}}, stream);
 }
 
 int fs_surface_hd(const unsigned char* fg, long long* hd, int* scratch, int B, int Hs, int Ws, int q, hipStream_t stream) {

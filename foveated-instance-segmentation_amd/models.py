@@ -240,6 +240,25 @@ class DeformSegmentationModule(nn.Module):
         return labels
 
     @torch.no_grad()
+    def predict_instances(self, img, focus, seg_size=None, max_runs=None, return_bits=False):
+        """Label-free inference as an instance record: the gazed instance's class, area, box and mask, without the class map.
+
+        img, focus and seg_size as predict's; the stages are predict's up to the gather, which stores the mask `predict(...) !=
+        num_class - 1` as bit words (ops.unwarp_instances / fs_unwarp_instances) so that nothing of (B, *seg_size) wider than a bit
+        per pixel exists.  Returns (cat, stats, counts[, bits]): cat (B,) int64 the head's classification among the classes below
+        num_class - 1 (torch.argmax of their logits); stats (B,6) int64 = (area, x0, y0, bw, bh, n_runs) with [x0, y0, bw, bh] the
+        COCO box, all 0 for an empty mask; counts (B,max_runs) int32 the uncompressed COCO run-length code (column-major), zero past
+        its n_runs entries; with return_bits the mask itself, (B,H,ceil(W/32)) int32, bit j of word i = pixel x = 32 i + j.  All of it
+        equals what `predict` gives bit for bit, except that cat is the head's decision and not a pixel's label: a foreground pixel's
+        label differs from it only where the bilinear sample of the constant class planes ties two classes by rounding or has no
+        in-bounds weight.  max_runs (any int >= 1) defaults to 8 * W + 1, room for a mask whose every column crosses its outline at
+        most eight times; stats[:, 5] > max_runs tells a cut code.  ops.instances_to_coco turns the result into COCO / LVIS records.
+
+        Eval mode only, no label read, no argument written to, and a NaN saliency map is reported as in predict."""
+        cls, m, grid, seg_size = self._head_parts(img, focus, seg_size, "predict_instances")
+        return ops.unwarp_instances(cls, m, grid, *seg_size, max_runs=max_runs, return_bits=return_bits)
+
+    @torch.no_grad()
     def evaluate(self, img, focus, seg_label, cls_label, seg_size=None, return_labels=False, class_areas=False, hausdorff=None, trimap=None, trimap_frame=True):
         """Full-resolution scoring without the loss: predict's stages, then the four accuracies of forward's MODEL.upsample branch
         (models/models.py:378-474,869-873,1074-1083) taken against the label in the pass that would have written the class map

@@ -1498,6 +1498,111 @@ def unwarp_labels(cls, m, grid, Hs, Ws):
     return labels, hole
 
 
+def _max_runs(max_runs, Ws):
+    """The capacity of a run-length code: any int >= 1; None = 8 * Ws + 1, which holds every mask whose columns each cross its outline
+    at most eight times (a blob entered and left four times by a column) -- 32 KB of int32 per 1024-wide image."""
+    if max_runs is None:
+        return 8 * int(Ws) + 1
+    if isinstance(max_runs, bool) or int(max_runs) != max_runs or int(max_runs) < 1:
+        raise ValueError(f"max_runs must be an integer >= 1, got {max_runs!r}")
+    return int(max_runs)
+
+
+def mask_bits(mask):
+    """A mask as bit words (fs_mask_bits; no autograd): mask (B,Hs,Ws) or (Hs,Ws), bool or uint8 (non-zero = set), on the device.
+    Returns bits (B,Hs,P) int32, P = ceil(Ws / 32): bit j of word i of row y is pixel x = 32 i + j, the bits at x >= Ws are 0."""
+    if mask.dim() == 2:
+        mask = mask[None]
+    if mask.dim() != 3 or mask.numel() == 0:
+        raise ValueError(f"mask {tuple(mask.shape)} must be a non-empty (B, Hs, Ws)")
+    if mask.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f"the mask must be bool or uint8, got {mask.dtype}")
+    B, Hs, Ws = (int(v) for v in mask.shape)
+    bits = torch.empty(B, Hs, (Ws + 31) // 32, device=mask.device, dtype=torch.int32)
+    hip.call("fs_mask_bits", hip.ptr(mask.contiguous()), hip.ptr(bits), B, Hs, Ws)
+    return bits
+
+
+def mask_rle(mask_or_bits, Ws=None, max_runs=None):
+    """Area, box and uncompressed COCO run-length code of any mask, exact and on the device (fs_mask_rle; no autograd).  The argument
+    is a bool / uint8 mask (B,Hs,Ws) or (Hs,Ws), or int32 bit words (B,Hs,ceil(Ws/32)) as mask_bits returns them together with Ws.
+    Returns (stats (B,6) int64 = area, x0, y0, bw, bh, n_runs; counts (B,max_runs) int32).  [x0, y0, bw, bh] is the COCO box of the set
+    pixels, all 0 for an empty mask.  counts is the code of the mask read column-major (p = x * Hs + y): the run of zeros before the
+    first set pixel (0 when pixel (0,0) is set), then alternating run lengths, runs continuing from the bottom of a column into the
+    top of the next; an empty mask is [Hs * Ws], a full one [0, Hs * Ws].  n_runs is always the true length of the code; the first
+    min(n_runs, max_runs) entries of counts are its, the rest is 0, and n_runs > max_runs tells that the code was cut.  max_runs
+    defaults to 8 * Ws + 1 (see _max_runs).  The format is restated from its published definition (pycocotools' uncompressed RLE)."""
+    if mask_or_bits.dtype == torch.int32:
+        bits = mask_or_bits
+        if bits.dim() != 3 or bits.numel() == 0 or Ws is None or int(Ws) < 1 or bits.shape[2] != (int(Ws) + 31) // 32:
+            raise ValueError(f"bit words {tuple(bits.shape)} must be a non-empty (B, Hs, ceil(Ws / 32)) with Ws given, got Ws = {Ws!r}")
+        Ws = int(Ws)
+    else:
+        if Ws is not None and int(Ws) != mask_or_bits.shape[-1]:
+            raise ValueError(f"Ws = {Ws!r} differs from the mask's width {mask_or_bits.shape[-1]}")
+        bits = mask_bits(mask_or_bits)
+        Ws = int(mask_or_bits.shape[-1])
+    B, Hs = int(bits.shape[0]), int(bits.shape[1])
+    cap = _max_runs(max_runs, Ws)
+    stats = torch.empty(B, 6, device=bits.device, dtype=torch.int64)
+    counts = torch.empty(B, cap, device=bits.device, dtype=torch.int32)
+    scratch = torch.empty(hip.query("fs_mask_rle_scratch_ints", B, Hs, Ws), device=bits.device, dtype=torch.int32)
+    hip.call("fs_mask_rle", hip.ptr(bits.contiguous()), hip.ptr(stats), hip.ptr(counts), hip.ptr(scratch), B, Hs, Ws, cap)
+    return stats, counts
+
+
+def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False):
+    """The gazed instance of the C1 head as a record instead of a class map (fs_unwarp_instances; no autograd).  Arguments and checks
+    are unwarp_labels'.  The mask is `unwarp_labels(cls, m, grid, Hs, Ws)[0] != K - 1` bit for bit; no (B,Hs,Ws) tensor wider than its
+    bit words is allocated.  Returns (cat, stats, counts[, bits]): cat (B,) int64 = torch.argmax(cls[:, :K-1], 1), the head's
+    classification (first maximum, NaN maximal); stats (B,6) int64 and counts (B,max_runs) int32 are mask_rle's of the mask; bits
+    (B,Hs,ceil(Ws/32)) int32 are mask_bits' of it.  cat is the label of every set pixel except where the bilinear sample of the constant
+    class planes ties two classes by rounding or has no in-bounds weight (a grid point on the outer border).  max_runs: any int >= 1,
+    default 8 * Ws + 1 -- room for a mask every column of which crosses its outline at most eight times, 32 KB per 1024-wide image;
+    n_runs = stats[:, 5] > max_runs tells a cut code.  instances_to_coco makes the result records."""
+    B, K = cls.shape
+    _, h, w, _ = grid.shape
+    if tuple(m.shape) != (B, h, w):
+        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
+    Hs, Ws = int(Hs), int(Ws)
+    cap = _max_runs(max_runs, Ws)
+    dev = cls.device
+    cat = torch.empty(B, device=dev, dtype=torch.int64)
+    stats = torch.empty(B, 6, device=dev, dtype=torch.int64)
+    counts = torch.empty(B, cap, device=dev, dtype=torch.int32)
+    bits = torch.empty(B, Hs, (Ws + 31) // 32, device=dev, dtype=torch.int32) if return_bits else None
+    scratch = torch.empty(hip.query("fs_unwarp_instances_scratch_ints", B, h, w, Hs, Ws), device=dev, dtype=torch.int32)
+    hip.call("fs_unwarp_instances", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(cat),
+             hip.ptr(stats), hip.ptr(counts), hip.ptr(bits), hip.ptr(scratch), B, K, h, w, Hs, Ws, cap)
+    return (cat, stats, counts, bits) if return_bits else (cat, stats, counts)
+
+
+def instances_to_coco(cat, stats, counts, seg_size, image_ids=None):
+    """unwarp_instances' / predict_instances' tensors (on any device) as a list of COCO / LVIS result records, one per image:
+    {"image_id", "category_id", "bbox": [x, y, w, h], "area", "segmentation": {"size": [H, W], "counts": [...]}} with the uncompressed
+    run-length code pycocotools.mask.frPyObjects takes.  One device-to-host copy.  category_id is the class index cat[b]; image_id is
+    image_ids[b], or b.  No score is made up: the caller has the head's logits.  OverflowError, naming the image and the max_runs it
+    needs, where a code was cut (n_runs > counts.shape[1])."""
+    B, cap = int(counts.shape[0]), int(counts.shape[1])
+    if tuple(cat.shape) != (B,) or tuple(stats.shape) != (B, 6) or counts.dim() != 2:
+        raise ValueError(f"cat {tuple(cat.shape)}, stats {tuple(stats.shape)}, counts {tuple(counts.shape)} must be (B,), (B, 6), (B, max_runs)")
+    H, W = int(seg_size[0]), int(seg_size[1])
+    ids = list(range(B)) if image_ids is None else list(image_ids)
+    if len(ids) != B:
+        raise ValueError(f"{len(ids)} image ids for {B} images")
+    head = torch.cat([cat.to(torch.int64).reshape(B, 1), stats.to(torch.int64)], 1).contiguous()
+    host = torch.cat([head.view(torch.int32), counts.to(torch.int32)], 1).cpu()       # the int64 columns as pairs of words
+    head, code = host[:, :14].contiguous().view(torch.int64).tolist(), host[:, 14:]
+    out = []
+    for b in range(B):
+        c, area, x0, y0, bw, bh, n = head[b]
+        if n > cap:
+            raise OverflowError(f"image {ids[b]}: the run-length code has {n} counts and was cut at max_runs = {cap}; it needs max_runs >= {n}")
+        out.append({"image_id": ids[b], "category_id": c, "bbox": [x0, y0, bw, bh], "area": area,
+                    "segmentation": {"size": [H, W], "counts": code[b, :n].tolist()}})
+    return out
+
+
 def _hd_q(q):
     if isinstance(q, bool) or int(q) != q or not 1 <= int(q) <= 100:
         raise ValueError(f"the Hausdorff percentile must be an integer 1 .. 100, got {q!r}")

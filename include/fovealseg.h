@@ -187,6 +187,33 @@ long fs_unwarp_hd_scratch_ints(int B, int K, int h, int w, int Hs, int Ws);
 int fs_unwarp_hd(const float* cls, const float* m, const float* grid, const float* y, const long long* cls_label, long long* counts,
                  float* acc, long long* areas, long long* trim, long long* labels, long long* hd, int* scratch, int B, int K, int h, int w,
                  int Hs, int Ws, int D, int frame, int q, fs_stream_t stream);
+/* A byte mask as bit words.  mask (B,Hs,Ws) bytes, any alignment, non-zero = foreground; bits (B,Hs,P) 32-bit words, P =
+ * ceil(Ws / 32): bit j of word i of row y is pixel x = 32 i + j, bits at x >= Ws are 0.  FS_ERR_ARG for a null pointer, non-positive
+ * sizes or more than 2^32 - 256 bit slots (B * Hs * P * 32). */
+int fs_mask_bits(const unsigned char* mask, unsigned int* bits, int B, int Hs, int Ws, fs_stream_t stream);
+/* Area, box and uncompressed COCO run-length code of a bit mask, exact and on the device (the format is restated from its published
+ * definition; the reference has no RLE code).  bits (B,Hs,P) as fs_mask_bits makes them.  The mask is flattened column-major, v[p],
+ * p = x * Hs + y, N = Hs * Ws, v[-1] = 0; the boundaries are T = {p : v[p] != v[p-1]} ascending, and the code is T[0], T[i] - T[i-1],
+ * N - T[last]: the first count is the leading run of zeros (0 when pixel (0,0) is set), runs continue from the bottom of a column into
+ * the top of the next, an empty mask gives [N], a full one [0, N].  stats (B,6) int64 = (area, x0, y0, bw, bh, n_runs): the set
+ * pixels, their box [x0, y0, bw, bh] (all 0 for an empty mask) and n_runs = |T| + 1, always the true number.  counts (B,cap) int32:
+ * the first min(n_runs, cap) entries are the code's, every later entry is 0; n_runs > cap tells a truncated code, nothing is written
+ * past cap.  Three passes over (column, 64-row segment) items in column-major order -- count the boundaries of an item, scan the
+ * counts per image, walk again and store -- plain stores only, no atomics, no host read: the same bits in every mode.  scratch =
+ * fs_mask_rle_scratch_ints(B, Hs, Ws) ints.  FS_ERR_ARG, with nothing launched, for a null pointer, cap < 1, non-positive sizes or
+ * Hs * Ws >= 2^31. */
+long fs_mask_rle_scratch_ints(int B, int Hs, int Ws);
+int fs_mask_rle(const unsigned int* bits, long long* stats, int* counts, int* scratch, int B, int Hs, int Ws, int cap, fs_stream_t stream);
+/* The gazed instance of the C1 head as a record, without a class map: the mask is "fs_unwarp_labels' class is not K-1" bit for bit
+ * (same kernels up to the gather, which stores bit words instead of classes), stats and counts are fs_mask_rle's of it.  cat (B)
+ * int64 = the first maximal k < K-1 of cls[b,k], NaN maximal (torch.argmax(cls[:, :K-1], 1)): the head's classification, and the
+ * class of every set pixel except where the bilinear sample of that constant plane ties two classes by rounding or has no in-bounds
+ * weight.  bits (B,Hs,P) as fs_mask_bits', nullable: null keeps the words in scratch.  scratch =
+ * fs_unwarp_instances_scratch_ints(B, h, w, Hs, Ws) ints; 16-byte aligned, four pixels a thread are gathered where Ws % 4 == 0.
+ * FS_ERR_ARG as fs_unwarp_labels and fs_mask_rle, and for a null cat. */
+long fs_unwarp_instances_scratch_ints(int B, int h, int w, int Hs, int Ws);
+int fs_unwarp_instances(const float* cls, const float* m, const float* grid, long long* cat, long long* stats, int* counts,
+                        unsigned int* bits, int* scratch, int B, int K, int h, int w, int Hs, int Ws, int cap, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
