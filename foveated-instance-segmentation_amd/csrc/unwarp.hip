@@ -12,7 +12,9 @@
 //                                                                                            (VAL.hd95; utils.py:25-101, in 2-D)
 //   instance     the mask "class is not K-1" gathered into bit words, its area, box and uncompressed COCO run-length code, and the head's
 //                class: the label-free output as a record (no counterpart in the reference; the code's format is the published one)
-// Host side: fs_unwarp_labels / _accuracy / _trimap / _class_areas / _hd / _instances are one launch sequence with optional parts.  unwarp_plan() derives
+//   score        the record's confidence: the foreground softmax mass per grid point as a 24-bit integer table, summed over the set pixels
+//                in the instance gather, times the head's class probability (no counterpart in the reference; unpinned)
+// Host side: fs_unwarp_labels / _accuracy / _trimap / _class_areas / _hd / _instances / _instances_scored are one launch sequence with optional parts.  unwarp_plan() derives
 // every size, scratch offset and limit from the shape and the feature set, UnwarpJob carries the caller's pointers, unwarp_run()
 // checks both and launches.  A refused call launches nothing: every check, fs_trimap_bands' included, comes before the first launch.
 #include "common.h"
@@ -1217,6 +1219,196 @@ __global__ __launch_bounds__(256) void rle_scan_kernel(int* __restrict__ cnt, in
   }
 }
 
+// ---- the instance's confidence score (fs_head_fg_q, fs_unwarp_instances_scored; no counterpart in the reference: unpinned) -------------
+// A pixel's foreground probability is the softmax mass of the classes below K-1 among the K values v[k] that unwarp_nearest(pred)
+// holds there -- the values unwarp_decide_kernel takes the argmax of, so one number per feeding point: qt[b,p] = rint(2^24 * P),
+// P = sum_{k<K-1} exp(v[k] - max v) / sum_{k<K} exp(v[k] - max v) in fp64 from the fp32 v; a NaN P (a NaN or +inf among the v, or all
+// of them -inf) gives 0.  The v are unwarp_decide_kernel's float operations (same taps, same sample4); they are formed twice, for the
+// maximum and for the sums, instead of being kept.  dec (nullable) = unwarp_decide_kernel's table: given, "class is not K-1" rides in
+// bit SCORE_FG_BIT of the word, so that the scored gather reads one word per pixel as the unscored one reads dec.
+constexpr int SCORE_FG_BIT = 31;
+constexpr int SCORE_Q_MASK = 0x7fffffff;
+constexpr double SCORE_ONE = 16777216.0;               // 2^24
+__global__ __launch_bounds__(256) void head_fg_q_kernel(const float* __restrict__ cls, const float* __restrict__ m, const int* __restrict__ dec,
+                                                        int* __restrict__ qt, int K, int h, int w, int blocks_per_image) {
+  __shared__ float cs[UNWARP_MAX_K];
+  const int b = blockIdx.x / blocks_per_image;
+  const int hw = h * w;
+  for (int k = threadIdx.x; k < K; k += 256) cs[k] = cls[(long)b * K + k];
+  __syncthreads();
+  const int p = (blockIdx.x - b * blocks_per_image) * 256 + threadIdx.x;
+  if (p > hw) return;
+  float gx = 0.f, gy = 0.f;
+  if (p < hw) {
+    const int yi = p / w, xi = p - yi * w;
+    gx = __fsub_rn(__fmul_rn(__fdiv_rn((float)xi, (float)w), 2.f), 1.f);
+    gy = __fsub_rn(__fmul_rn(__fdiv_rn((float)yi, (float)h), 2.f), 1.f);
+  }
+  const Taps t = make_taps(gx, gy, h, w);
+  const bool inw = t.oky0 & t.okx0, ine = t.oky0 & t.okx1, isw = t.oky1 & t.okx0, ise = t.oky1 & t.okx1;
+  auto sample4 = [&](float vnw, float vne, float vsw, float vse) {
+    float acc = __fmul_rn(vnw, t.nw);
+    acc = __fmaf_rn(vne, t.ne, acc);
+    acc = __fmaf_rn(vsw, t.sw, acc);
+    return __fmaf_rn(vse, t.se, acc);
+  };
+  auto plane = [&](float c) { return sample4(inw ? c : 0.f, ine ? c : 0.f, isw ? c : 0.f, ise ? c : 0.f); };
+  const float c = cs[K - 1];
+  const float* mp = m + (long)b * hw;
+  const float vb = sample4(inw ? __fmul_rn(c, mp[t.y0 * w + t.x0]) : 0.f, ine ? __fmul_rn(c, mp[t.y0 * w + t.x0 + 1]) : 0.f,
+                           isw ? __fmul_rn(c, mp[(t.y0 + 1) * w + t.x0]) : 0.f, ise ? __fmul_rn(c, mp[(t.y0 + 1) * w + t.x0 + 1]) : 0.f);
+  float mx = vb;
+  bool nan = vb != vb;
+  for (int k = 0; k < K - 1; ++k) {
+    const float v = plane(cs[k]);
+    nan |= v != v;
+    if (v > mx) mx = v;
+  }
+  double fg = 0.0;
+  for (int k = 0; k < K - 1; ++k) fg += exp((double)plane(cs[k]) - (double)mx);
+  const double P = fg / (fg + exp((double)vb - (double)mx));
+  unsigned int word = (!nan && P == P) ? (unsigned int)(int)rint(P * SCORE_ONE) : 0u;
+  const long i = (long)b * (hw + 1) + p;
+  if (dec != nullptr) word |= (unsigned int)(dec[i] != K - 1) << SCORE_FG_BIT;
+  qt[i] = (int)word;
+}
+// unwarp_bits_kernel's gather from head_fg_q_kernel's packed table, with the q of every set pixel summed per image.  A thread's sum is
+// one image's (a quad and a column lie in one row).  A wave's words are consecutive -- WPW = 8 with VEC, 2 without -- so its images are
+// those of its first to its last word: one, or two where it straddles an image's end, or more where an image has fewer words than a
+// wave; bits past a row's end add nothing.  Per image the wave reduces by shuffles (a thread's sum is below 2^27, so 32 lanes fit 32
+// bits and the last step is taken in 64; a wave without a set pixel of the image, the usual case of a small mask, skips them).  The
+// sum of the wave's FIRST image goes to the wave's record by plain stores, written whatever its value -- rec[wave] as two 32-bit
+// halves with VEC (256 pixels: up to 2^32), one int without (64 pixels: up to 2^30) -- and instance_conf_kernel sums an image's
+// records in a fixed pass.  Only the sums of a wave's further images -- a straddling wave -- are added into qsum[b] (zeroed by the
+// launcher) by 64-bit integer atomics, where non-zero; and every sum is where rec is null (the launcher: a scratch too misaligned
+// for VEC at a width whose records were sized for it).  One atomic per wave or workgroup and
+// image instead was measured: adds to 64 hot addresses serialise, 0.17 ms for a 7 150-pixel mask and 1.1 ms for a full one at B = 64
+// (profiles/r21).  The waves are not joined: no barrier.  Integer sums: the same bits in any order.
+template <bool VEC>
+__global__ __launch_bounds__(256) void unwarp_bits_score_kernel(const int* __restrict__ owner, const int* __restrict__ rowx,
+                                                                const int* __restrict__ qf, unsigned int* __restrict__ bits,
+                                                                unsigned long long* __restrict__ qsum, int* __restrict__ rec, int Hs, int Ws,
+                                                                int P, int hw, long words) {
+  constexpr unsigned int WPW = VEC ? 8 : 2;            // words per wave: no more images than that
+  const int per = Hs * Ws;
+  unsigned int s = 0u;
+  long tb = -1;                                        // this thread's image
+  if (VEC) {
+    const long g = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
+    const int l = threadIdx.x & 7;
+    unsigned int nib = 0u;
+    if (g < words) {
+      const long row = g / P;
+      const int x = 32 * (int)(g - row * P) + 4 * l;
+      if (x < Ws) {
+        const long b = row / Hs;
+        const int y = (int)(row - b * Hs);
+        const int* ob = owner + b * per;
+        const int* db = qf + b * (hw + 1);
+        const int4 o4 = *reinterpret_cast<const int4*>(ob + y * Ws + x);
+        int q[4] = {o4.x, o4.y, o4.z, o4.w};
+        const int holes = (o4.x < 0) | (o4.y < 0) << 1 | (o4.z < 0) << 2 | (o4.w < 0) << 3;
+        if (holes) {
+          int src[4];
+          nearest_claimed4(rowx + b * per, y, x, Hs, Ws, holes, src);
+#pragma unroll
+          for (int k = 0; k < 4; ++k)
+            if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int wd = db[q[k]];
+          nib |= (unsigned int)(wd < 0) << k;
+          s += wd < 0 ? (unsigned int)(wd & SCORE_Q_MASK) : 0u;
+        }
+        tb = b;
+      }
+    }
+    unsigned int wd = nib << (4 * l);
+    wd |= __shfl_xor(wd, 1, 64); wd |= __shfl_xor(wd, 2, 64); wd |= __shfl_xor(wd, 4, 64);
+    if (l == 0 && g < words) bits[g] = wd;
+  } else {
+    const long g = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
+    bool f = false;
+    if (g < words) {
+      const long row = g / P;
+      const int x = 32 * (int)(g - row * P) + (int)(threadIdx.x & 31);
+      if (x < Ws) {
+        const long b = row / Hs;
+        const int y = (int)(row - b * Hs);
+        const int* ob = owner + b * per;
+        const int wd = unwarp_class_at(ob, rowx + b * per, qf + b * (hw + 1), ob[y * Ws + x], y, x, Hs, Ws, hw);
+        f = wd < 0;
+        s = f ? (unsigned int)(wd & SCORE_Q_MASK) : 0u;
+        tb = b;
+      }
+    }
+    const unsigned long long bal = __ballot(f);
+    if ((threadIdx.x & 31) == 0 && g < words) bits[g] = (unsigned int)(bal >> (threadIdx.x & 32));
+  }
+  // words < 2^27 (one lane a bit slot) and Hs * P < 2^31: 32-bit divisions
+  const unsigned int wpi = (unsigned int)Hs * (unsigned int)P, nw = (unsigned int)words;
+  const unsigned int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
+  const unsigned int g0 = wave * WPW;
+  unsigned long long first = 0ull;
+  if (g0 < nw) {
+    const unsigned int g1 = (g0 + WPW < nw ? g0 + WPW : nw) - 1;
+    const unsigned int b_lo = g0 / wpi, nimg = g1 / wpi - b_lo + 1;
+    for (unsigned int i = 0; i < nimg; ++i) {
+      unsigned int v = tb == (long)(b_lo + i) ? s : 0u;
+      if (__ballot(v != 0u) == 0ull) continue;         // wave-uniform
+#pragma unroll
+      for (int o = 16; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+      const unsigned long long t = (unsigned long long)v + (unsigned long long)__shfl_xor(v, 32, 64);
+      if (i == 0 && rec != nullptr) first = t;
+      else if ((threadIdx.x & 63) == 0) atomicAdd(qsum + b_lo + i, t);
+    }
+  }
+  if ((threadIdx.x & 63) == 0 && rec != nullptr) {
+    if (VEC) { rec[2 * (long)wave] = (int)(unsigned int)first; rec[2 * (long)wave + 1] = (int)(unsigned int)(first >> 32); }
+    else rec[wave] = (int)(unsigned int)first;
+  }
+}
+// qsum[b] += the records of the waves whose first image is b -- wave v's first word is v * wpw, so they are the waves ceil(b * wpi / wpw)
+// .. ceil((b+1) * wpi / wpw) - 1 -- summed by one workgroup per image in a fixed order; then
+// conf[b] = (score, cls_prob, mask_prob): cls_prob = the fp64 softmax over cls[b, :K-1] at cat[b] (NaN where the row holds one),
+// mask_prob = qsum / (area * 2^24) in fp64 (0 for an empty mask), score = their fp64 product; each rounded to fp32 once.  area =
+// stats[b,0], rle_scan_kernel's.
+__global__ __launch_bounds__(256) void instance_conf_kernel(const float* __restrict__ cls, const long long* __restrict__ cat,
+                                                            const long long* __restrict__ stats, const int* __restrict__ rec,
+                                                            long long* __restrict__ qsum, float* __restrict__ conf, int K, long wpi, int wpw,
+                                                            long nwaves) {                   // wpw = 8: records of two ints, 2: of one
+  __shared__ long long red[16];
+  const int b = blockIdx.x;
+  const long w0 = (b * wpi + wpw - 1) / wpw, w1e = ((b + 1) * wpi + wpw - 1) / wpw;
+  const long w1 = w1e < nwaves ? w1e : nwaves;
+  long long part = 0;
+  if (rec != nullptr) {
+    for (long v = w0 + threadIdx.x; v < w1; v += 256)
+      part += wpw == 8 ? (long long)((unsigned long long)(unsigned int)rec[2 * v] | (unsigned long long)(unsigned int)rec[2 * v + 1] << 32)
+                       : (long long)rec[v];
+  }
+  part = block_sum<long long>(part, red);
+  if (threadIdx.x != 0) return;
+  const long long q = qsum[b] + part;                  // the straddling waves' atomics are in already
+  qsum[b] = q;
+  const float* c = cls + (long)b * K;
+  const int a = (int)cat[b];
+  float mx = c[0];
+  for (int k = 1; k < K - 1; ++k)
+    if (c[k] > mx) mx = c[k];
+  double sum = 0.0, ea = 0.0;
+  for (int k = 0; k < K - 1; ++k) {
+    const double e = exp((double)c[k] - (double)mx);
+    sum += e;
+    if (k == a) ea = e;
+  }
+  const double cp = ea / sum;
+  const long long area = stats[(long)b * 6];
+  const double mp = area > 0 ? (double)q / ((double)area * SCORE_ONE) : 0.0;
+  conf[3 * b] = (float)(cp * mp); conf[3 * b + 1] = (float)cp; conf[3 * b + 2] = (float)mp;
+}
+
 // ---- host: one plan, one job, one launcher -------------------------------------------------------------------------------------------
 constexpr long INT_LIMIT = 2147483647L;                // pixel / point indices are ints
 constexpr long THREADS_MAX = 4294967295L - 255;        // every launch: fewer than 2^32 work-items
@@ -1284,7 +1476,9 @@ RlePlan rle_plan(int B, int Hs, int Ws) {
 // feature appends its regions to the scratch of the one before; UW_AREA's layout keeps UW_TRIM's regions whether or not the call has a
 // trimap, and UW_HD's come after whatever the other features of the call take.  UW_BITS (fs_unwarp_instances): the gather stores bit
 // words instead of classes, and the run-length passes follow; its regions come last of all, and it goes with no counting feature.
-enum : unsigned { UW_LABELS = 0, UW_COUNT = 1, UW_TRIM = 2, UW_AREA = 4, UW_HD = 8, UW_BITS = 16 };
+// UW_SCORE (fs_unwarp_instances_scored): UW_BITS with the gather also summing the feeding points' foreground probabilities; its one
+// regions, the packed table and the gather's per-wave records, come behind UW_BITS', whose layout stays what it is without it.
+enum : unsigned { UW_LABELS = 0, UW_COUNT = 1, UW_TRIM = 2, UW_AREA = 4, UW_HD = 8, UW_BITS = 16, UW_SCORE = 32 };
 
 struct UnwarpPlan {
   int B, K, h, w, Hs, Ws;
@@ -1298,6 +1492,7 @@ struct UnwarpPlan {
   long arec, atab;                                     // UW_AREA: [B*cpi][AREA_REC], [B][K] sums of the other predicted classes' pixels
   long fg, hds;                                        // UW_HD: n foreground bytes, SurfacePlan::total
   long bitw, rles;                                     // UW_BITS: RlePlan::words bit words (used when the caller keeps none), RlePlan::total
+  long qtab, srec;                                     // UW_SCORE: [B*(h*w+1)] head_fg_q_kernel's packed words; two ints per wave of the gather
   long total;
   TrimapPlan tri;
   SurfacePlan sp;
@@ -1328,13 +1523,18 @@ UnwarpPlan unwarp_plan(int B, int K, int h, int w, int Hs, int Ws, unsigned feat
     p.rle = rle_plan(B, Hs, Ws);
     p.bitw = align4(p.total), p.rles = p.bitw + align4(p.rle.words), p.total = p.rles + p.rle.total;
   }
+  // the gather's waves: four to a workgroup of 32 words and two ints each where Ws % 4 == 0, else four to one of 8 words and one int
+  if (features & UW_SCORE)
+    p.qtab = align4(p.total), p.srec = align4(p.qtab + (long)B * ((long)h * w + 1)),
+    p.total = p.srec + (Ws % 4 == 0 ? 8 * ((p.rle.words + 31) / 32) : 4 * ((p.rle.words + 7) / 8));
   // a workgroup's last trip of the count pass may start up to a chunk past the end
   const long per_max = INT_LIMIT - (features & UW_COUNT ? UACC_CHUNK : 0);
   p.ok = K >= 2 && K <= UNWARP_MAX_K && row_fits_lds(Ws) && (long)h * w < INT_LIMIT && p.per < per_max && p.n <= THREADS_MAX &&
          (long)B * Hs * 256 <= THREADS_MAX && (long)B * p.bpi * 256 <= THREADS_MAX &&
          (!(features & UW_COUNT) || (long)B * p.cpi * 256 <= THREADS_MAX) && (!(features & UW_TRIM) || p.tri.ok) &&
          (!(features & UW_HD) || ((features & UW_COUNT) && p.sp.ok)) &&
-         (!(features & UW_BITS) || (features == UW_BITS && p.rle.bits_ok && p.rle.ok));
+         (!(features & UW_BITS) || ((features & ~UW_SCORE) == UW_BITS && p.rle.bits_ok && p.rle.ok)) &&
+         (!(features & UW_SCORE) || (features & UW_BITS));
   return p;
 }
 
@@ -1347,7 +1547,7 @@ struct UnwarpJob {
   struct { long long* out; int D, frame; } trim;                                                // UW_TRIM
   struct { long long* out; } areas;                                                             // UW_AREA
   struct { long long* out; int q; } hd;                                                         // UW_HD
-  struct { long long *cat, *stats; int* counts; unsigned int* bits; int cap; } inst;            // UW_BITS; bits optional
+  struct { long long *cat, *stats; int* counts; unsigned int* bits; int cap; float* conf; long long* qsum; } inst;   // UW_BITS; bits optional; conf, qsum: UW_SCORE
 };
 
 bool trimap_args_ok(int D, int frame) { return D >= 0 && D <= TRI_MAX_D && (frame == 0 || frame == 1); }
@@ -1455,14 +1655,15 @@ const CountKernel COUNT_KERNELS[8] = {
     unwarp_count_kernel<true, true, false>,   unwarp_count_kernel<false, false, true>, unwarp_count_kernel<true, false, true>,
     unwarp_count_kernel<false, true, true>,   unwarp_count_kernel<true, true, true>};
 
-// The launches of the six entry points: [trimap bands,] prelude, then either the class map, or with UW_BITS the bit words, the class
-// and the run-length passes, or the count pass and its finalizers (the trimap's and the areas' after the accuracies'), then with UW_HD
+// The launches of the seven entry points: [trimap bands,] prelude, then either the class map, or with UW_BITS the bit words, the class
+// and the run-length passes (with UW_SCORE the packed table before the gather, the confidences behind the run-length passes), or the count pass and its finalizers (the trimap's and the areas' after the accuracies'), then with UW_HD
 // the foreground bytes and the surface distances.
 int unwarp_run(const UnwarpPlan& p, const UnwarpJob& j, hipStream_t stream) {
   const bool count = p.features & UW_COUNT, trim = p.features & UW_TRIM, area = p.features & UW_AREA, hdq = p.features & UW_HD;
-  const bool inst = p.features & UW_BITS;
+  const bool inst = p.features & UW_BITS, score = p.features & UW_SCORE;
   FS_REQUIRE(p.ok && j.cls && j.m && j.grid && j.scratch && (count || inst || j.labels.map));
   FS_REQUIRE(!inst || (j.inst.cat && j.inst.stats && j.inst.counts && j.inst.cap >= 1));
+  FS_REQUIRE(!score || (j.inst.conf && j.inst.qsum));
   // the records are stored and read 16 bytes at a time
   FS_REQUIRE(!count || (j.count.y && j.count.cls_label && j.count.counts && j.count.acc && ((uintptr_t)j.scratch & 15) == 0));
   FS_REQUIRE((!trim || (j.trim.out && trimap_args_ok(j.trim.D, j.trim.frame))) && (!area || j.areas.out));
@@ -1475,12 +1676,32 @@ int unwarp_run(const UnwarpPlan& p, const UnwarpJob& j, hipStream_t stream) {
     unsigned int* bits = j.inst.bits ? j.inst.bits : reinterpret_cast<unsigned int*>(s + p.bitw);
     // four pixels a thread need whole 16-byte rows of owner and rowx
     const bool vec4 = p.Ws % 4 == 0 && ((uintptr_t)s & 15) == 0;
-    hipLaunchKernelGGL(vec4 ? unwarp_bits_kernel<true> : unwarp_bits_kernel<false>, dim3(cdiv(p.rle.words, vec4 ? 32 : 8)), dim3(256), 0, stream,
-                       s + p.owner, s + p.rowx, s + p.dec, bits, p.Hs, p.Ws, (int)p.rle.P, p.h * p.w, p.K, p.rle.words);
+    int* srec = nullptr;
+    if (score) {
+      unsigned long long* qsum = reinterpret_cast<unsigned long long*>(j.inst.qsum);
+      srec = (p.Ws % 4 == 0) == vec4 ? s + p.srec : nullptr;     // the records were sized for the gather the width allows
+      hipLaunchKernelGGL(head_fg_q_kernel, dim3((unsigned)(p.B * p.bpi)), dim3(256), 0, stream, j.cls, j.m, s + p.dec, s + p.qtab, p.K, p.h, p.w,
+                         (int)p.bpi);
+      FS_LAUNCH_CHECK();
+      const hipError_t e = hipMemsetAsync(qsum, 0, sizeof(long long) * (size_t)p.B, stream);
+      if (e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(vec4 ? unwarp_bits_score_kernel<true> : unwarp_bits_score_kernel<false>, dim3(cdiv(p.rle.words, vec4 ? 32 : 8)), dim3(256),
+                         0, stream, s + p.owner, s + p.rowx, s + p.qtab, bits, qsum, srec, p.Hs, p.Ws, (int)p.rle.P, p.h * p.w, p.rle.words);
+    } else {
+      hipLaunchKernelGGL(vec4 ? unwarp_bits_kernel<true> : unwarp_bits_kernel<false>, dim3(cdiv(p.rle.words, vec4 ? 32 : 8)), dim3(256), 0, stream,
+                         s + p.owner, s + p.rowx, s + p.dec, bits, p.Hs, p.Ws, (int)p.rle.P, p.h * p.w, p.K, p.rle.words);
+    }
     FS_LAUNCH_CHECK();
     hipLaunchKernelGGL(instance_cat_kernel, dim3(cdiv(p.B, 256)), dim3(256), 0, stream, j.cls, j.inst.cat, p.B, p.K);
     FS_LAUNCH_CHECK();
-    return rle_launch(p.rle, bits, j.inst.stats, j.inst.counts, s + p.rles, p.B, p.Hs, p.Ws, j.inst.cap, stream);
+    FS_TRY(rle_launch(p.rle, bits, j.inst.stats, j.inst.counts, s + p.rles, p.B, p.Hs, p.Ws, j.inst.cap, stream));
+    if (score) {
+      const int wpw = vec4 ? 8 : 2;
+      hipLaunchKernelGGL(instance_conf_kernel, dim3((unsigned)p.B), dim3(256), 0, stream, j.cls, j.inst.cat, j.inst.stats, srec, j.inst.qsum,
+                         j.inst.conf, p.K, (long)p.Hs * p.rle.P, wpw, 4L * cdiv(p.rle.words, 4 * wpw));
+      FS_LAUNCH_CHECK();
+    }
+    return FS_OK;
   }
   if (!count) {
     hipLaunchKernelGGL(unwarp_label_kernel, dim3(cdiv(p.n, 256)), dim3(256), 0, stream, s + p.owner, s + p.rowx, s + p.dec, j.labels.map,
@@ -1622,6 +1843,26 @@ long fs_unwarp_instances_scratch_ints(int B, int h, int w, int Hs, int Ws) { ret
 int fs_unwarp_instances(const float* cls, const float* m, const float* grid, long long* cat, long long* stats, int* counts, unsigned int* bits,
                         int* scratch, int B, int K, int h, int w, int Hs, int Ws, int cap, hipStream_t stream) {
   return unwarp_run(unwarp_plan(B, K, h, w, Hs, Ws, UW_BITS), {cls, m, grid, scratch, {}, {}, {}, {}, {}, {cat, stats, counts, bits, cap}}, stream);
+}
+
+// the per-grid-point foreground probabilities alone: the table without the flag
+int fs_head_fg_q(const float* cls, const float* m, int* q, int B, int K, int h, int w, hipStream_t stream) {
+  FS_REQUIRE(cls && m && q && B > 0 && h > 0 && w > 0 && K >= 2 && K <= UNWARP_MAX_K && (long)h * w < INT_LIMIT);
+  const long bpi = ((long)h * w + 1 + 255) / 256;
+  FS_REQUIRE((long)B * bpi * 256 <= THREADS_MAX);
+  hipLaunchKernelGGL(head_fg_q_kernel, dim3((unsigned)(B * bpi)), dim3(256), 0, stream, cls, m, (const int*)nullptr, q, K, h, w, (int)bpi);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+long fs_unwarp_instances_scored_scratch_ints(int B, int h, int w, int Hs, int Ws) {
+  return unwarp_plan(B, 2, h, w, Hs, Ws, UW_BITS | UW_SCORE).total;
+}
+int fs_unwarp_instances_scored(const float* cls, const float* m, const float* grid, long long* cat, long long* stats, int* counts,
+                               unsigned int* bits, float* conf, long long* qsum, int* scratch, int B, int K, int h, int w, int Hs, int Ws,
+                               int cap, hipStream_t stream) {
+  return unwarp_run(unwarp_plan(B, K, h, w, Hs, Ws, UW_BITS | UW_SCORE),
+                    {cls, m, grid, scratch, {}, {}, {}, {}, {}, {cat, stats, counts, bits, cap, conf, qsum}}, stream);
 }
 
 int fs_surface_hd(const unsigned char* fg, long long* hd, int* scratch, int B, int Hs, int Ws, int q, hipStream_t stream) {

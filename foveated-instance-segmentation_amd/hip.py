@@ -49,6 +49,8 @@ SIGNATURES = {
     "fs_mask_bits": "pp" + "iii",
     "fs_mask_rle": "pppp" + "iiii",
     "fs_unwarp_instances": "pppppppp" + "iiiiiii",
+    "fs_head_fg_q": "ppp" + "iiii",
+    "fs_unwarp_instances_scored": "pppppppppp" + "iiiiiii",
     "fs_conv2d_fwd": "ppppiiiiiiiiiiiifuplp",
     "fs_conv2d_fwd_residual": "ppppp" + "iiiiiiiiiiii" + "fufu" + "l" + "plp",
     "fs_conv2d_fwd_stats": "pppppiiiiiiiiiiiifuplp",
@@ -123,7 +125,8 @@ HOST_ONLY = ("fs_set_conv_precision", "fs_get_conv_precision", "fs_conv2d_worksp
              "fs_edge_loss_stats_floats", "fs_compress_softmax_bwd_scratch_floats", "fs_gauss_grid_bwd_scratch_floats",
              "fs_unwarp_labels_scratch_ints", "fs_unwarp_accuracy_scratch_ints",
              "fs_trimap_bands_scratch_ints", "fs_unwarp_trimap_scratch_ints", "fs_unwarp_class_areas_scratch_ints",
-             "fs_unwarp_hd_scratch_ints", "fs_surface_hd_scratch_ints", "fs_mask_rle_scratch_ints", "fs_unwarp_instances_scratch_ints")
+             "fs_unwarp_hd_scratch_ints", "fs_surface_hd_scratch_ints", "fs_mask_rle_scratch_ints", "fs_unwarp_instances_scratch_ints",
+             "fs_unwarp_instances_scored_scratch_ints")
 
 
 class HipLibraryError(RuntimeError):
@@ -188,6 +191,8 @@ def load():
     lib.fs_mask_rle_scratch_ints.argtypes = [_I] * 3
     lib.fs_unwarp_instances_scratch_ints.restype = _L
     lib.fs_unwarp_instances_scratch_ints.argtypes = [_I] * 5
+    lib.fs_unwarp_instances_scored_scratch_ints.restype = _L
+    lib.fs_unwarp_instances_scored_scratch_ints.argtypes = [_I] * 5
     lib.fs_stream_wait.restype = _I
     lib.fs_stream_wait.argtypes = [_P, _P]
     lib.fs_set_deterministic.restype = _I

@@ -240,7 +240,7 @@ class DeformSegmentationModule(nn.Module):
         return labels
 
     @torch.no_grad()
-    def predict_instances(self, img, focus, seg_size=None, max_runs=None, return_bits=False):
+    def predict_instances(self, img, focus, seg_size=None, max_runs=None, return_bits=False, return_score=False):
         """Label-free inference as an instance record: the gazed instance's class, area, box and mask, without the class map.
 
         img, focus and seg_size as predict's; the stages are predict's up to the gather, which stores the mask `predict(...) !=
@@ -254,8 +254,17 @@ class DeformSegmentationModule(nn.Module):
         in-bounds weight.  max_runs (any int >= 1) defaults to 8 * W + 1, room for a mask whose every column crosses its outline at
         most eight times; stats[:, 5] > max_runs tells a cut code.  ops.instances_to_coco turns the result into COCO / LVIS records.
 
+        return_score=True appends conf (B,3) fp32 = (score, cls_prob, mask_prob) as the last element (ops.unwarp_instances(score=True);
+        unpinned, the reference has no score): cls_prob the softmax probability of cat among the classes below num_class - 1, mask_prob
+        the mean over the mask's pixels of the softmax mass of those classes against background, score their product -- the mean
+        probability of class cat over the mask, what COCOeval / the LVIS evaluator rank records by (instances_to_coco(..., conf=conf)).
+        mask_prob and score are 0 for an empty mask, cls_prob and score NaN where the class logits hold a NaN.  The other results are
+        the unscored call's bit for bit; the call allocates a few bytes per grid point more and no full-resolution tensor.
+
         Eval mode only, no label read, no argument written to, and a NaN saliency map is reported as in predict."""
         cls, m, grid, seg_size = self._head_parts(img, focus, seg_size, "predict_instances")
+        if return_score:
+            return ops.unwarp_instances(cls, m, grid, *seg_size, max_runs=max_runs, return_bits=return_bits, score=True)[:-1]
         return ops.unwarp_instances(cls, m, grid, *seg_size, max_runs=max_runs, return_bits=return_bits)
 
     @torch.no_grad()

@@ -1551,7 +1551,21 @@ def mask_rle(mask_or_bits, Ws=None, max_runs=None):
     return stats, counts
 
 
-def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False):
+def head_fg_q(cls, m):
+    """The C1 head's foreground probability per grid point as an integer table (fs_head_fg_q; no autograd; unpinned: the reference
+    has no counterpart).  cls (B,K), m (B,h,w).  Returns q (B, h*w+1) int32 = rint(P * 2^24): P is the softmax mass of the classes
+    below K-1 among the K fp32 values `unwarp_nearest(PredAssemble(cls, m), ...)` carries from grid point p (entry h*w: from the sample at
+    (0,0), which feeds an image without a claimed pixel), evaluated in fp64 with the maximum subtracted; 0 where P is NaN."""
+    B, K = cls.shape
+    if m.dim() != 3 or m.shape[0] != B:
+        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) with B = {B}")
+    h, w = int(m.shape[1]), int(m.shape[2])
+    q = torch.empty(B, h * w + 1, device=cls.device, dtype=torch.int32)
+    hip.call("fs_head_fg_q", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(q), B, K, h, w)
+    return q
+
+
+def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False, score=False):
     """The gazed instance of the C1 head as a record instead of a class map (fs_unwarp_instances; no autograd).  Arguments and checks
     are unwarp_labels'.  The mask is `unwarp_labels(cls, m, grid, Hs, Ws)[0] != K - 1` bit for bit; no (B,Hs,Ws) tensor wider than its
     bit words is allocated.  Returns (cat, stats, counts[, bits]): cat (B,) int64 = torch.argmax(cls[:, :K-1], 1), the head's
@@ -1559,7 +1573,12 @@ def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False):
     (B,Hs,ceil(Ws/32)) int32 are mask_bits' of it.  cat is the label of every set pixel except where the bilinear sample of the constant
     class planes ties two classes by rounding or has no in-bounds weight (a grid point on the outer border).  max_runs: any int >= 1,
     default 8 * Ws + 1 -- room for a mask every column of which crosses its outline at most eight times, 32 KB per 1024-wide image;
-    n_runs = stats[:, 5] > max_runs tells a cut code.  instances_to_coco makes the result records."""
+    n_runs = stats[:, 5] > max_runs tells a cut code.  instances_to_coco makes the result records.
+
+    score=True (fs_unwarp_instances_scored; unpinned) appends conf (B,3) fp32 = (score, cls_prob, mask_prob) and qsum (B,) int64 behind
+    everything else: qsum is the sum of head_fg_q(cls, m)[b, feeding point] over the set pixels, added in the same gather; mask_prob =
+    qsum / (area * 2^24), 0 for an empty mask; cls_prob = softmax(cls[b, :K-1])[cat[b]] in fp64, NaN where that row holds a NaN; score
+    = their product, the mean probability of class cat over the mask.  The other results are the unscored call's bit for bit."""
     B, K = cls.shape
     _, h, w, _ = grid.shape
     if tuple(m.shape) != (B, h, w):
@@ -1571,18 +1590,27 @@ def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False):
     stats = torch.empty(B, 6, device=dev, dtype=torch.int64)
     counts = torch.empty(B, cap, device=dev, dtype=torch.int32)
     bits = torch.empty(B, Hs, (Ws + 31) // 32, device=dev, dtype=torch.int32) if return_bits else None
+    if score:
+        conf = torch.empty(B, 3, device=dev, dtype=torch.float32)
+        qsum = torch.empty(B, device=dev, dtype=torch.int64)
+        scratch = torch.empty(hip.query("fs_unwarp_instances_scored_scratch_ints", B, h, w, Hs, Ws), device=dev, dtype=torch.int32)
+        hip.call("fs_unwarp_instances_scored", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(cat),
+                 hip.ptr(stats), hip.ptr(counts), hip.ptr(bits), hip.ptr(conf), hip.ptr(qsum), hip.ptr(scratch), B, K, h, w, Hs, Ws, cap)
+        return (cat, stats, counts, bits, conf, qsum) if return_bits else (cat, stats, counts, conf, qsum)
     scratch = torch.empty(hip.query("fs_unwarp_instances_scratch_ints", B, h, w, Hs, Ws), device=dev, dtype=torch.int32)
     hip.call("fs_unwarp_instances", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(cat),
              hip.ptr(stats), hip.ptr(counts), hip.ptr(bits), hip.ptr(scratch), B, K, h, w, Hs, Ws, cap)
     return (cat, stats, counts, bits) if return_bits else (cat, stats, counts)
 
 
-def instances_to_coco(cat, stats, counts, seg_size, image_ids=None):
+def instances_to_coco(cat, stats, counts, seg_size, image_ids=None, conf=None):
     """unwarp_instances' / predict_instances' tensors (on any device) as a list of COCO / LVIS result records, one per image:
     {"image_id", "category_id", "bbox": [x, y, w, h], "area", "segmentation": {"size": [H, W], "counts": [...]}} with the uncompressed
     run-length code pycocotools.mask.frPyObjects takes.  One device-to-host copy.  category_id is the class index cat[b]; image_id is
-    image_ids[b], or b.  No score is made up: the caller has the head's logits.  OverflowError, naming the image and the max_runs it
-    needs, where a code was cut (n_runs > counts.shape[1])."""
+    image_ids[b], or b.  With conf (B,3) -- unwarp_instances(score=True)'s / predict_instances(return_score=True)'s -- every record
+    also has "score": conf[b, 0] as a Python float, the key COCOeval and the LVIS evaluator rank by; without it no score is made up.
+    OverflowError, naming the image and the max_runs it needs, where a code was cut (n_runs > counts.shape[1]); ValueError, naming the
+    image, where a score is NaN."""
     B, cap = int(counts.shape[0]), int(counts.shape[1])
     if tuple(cat.shape) != (B,) or tuple(stats.shape) != (B, 6) or counts.dim() != 2:
         raise ValueError(f"cat {tuple(cat.shape)}, stats {tuple(stats.shape)}, counts {tuple(counts.shape)} must be (B,), (B, 6), (B, max_runs)")
@@ -1590,16 +1618,28 @@ def instances_to_coco(cat, stats, counts, seg_size, image_ids=None):
     ids = list(range(B)) if image_ids is None else list(image_ids)
     if len(ids) != B:
         raise ValueError(f"{len(ids)} image ids for {B} images")
+    if conf is not None and (conf.dim() != 2 or conf.shape[0] != B or conf.shape[1] < 1):
+        raise ValueError(f"conf {tuple(conf.shape)} must be (B, 3) = ({B}, 3): (score, cls_prob, mask_prob) per image")
     head = torch.cat([cat.to(torch.int64).reshape(B, 1), stats.to(torch.int64)], 1).contiguous()
-    host = torch.cat([head.view(torch.int32), counts.to(torch.int32)], 1).cpu()       # the int64 columns as pairs of words
-    head, code = host[:, :14].contiguous().view(torch.int64).tolist(), host[:, 14:]
+    parts = [head.view(torch.int32)]                                                   # the int64 columns as pairs of words
+    if conf is not None:
+        parts.append(conf[:, :1].to(torch.float32).contiguous().view(torch.int32))     # the score's fp32 word
+    n0 = sum(int(t.shape[1]) for t in parts)
+    host = torch.cat(parts + [counts.to(torch.int32)], 1).cpu()
+    head, code = host[:, :14].contiguous().view(torch.int64).tolist(), host[:, n0:]
+    scores = host[:, 14:15].contiguous().view(torch.float32).reshape(B).tolist() if conf is not None else None
     out = []
     for b in range(B):
         c, area, x0, y0, bw, bh, n = head[b]
         if n > cap:
             raise OverflowError(f"image {ids[b]}: the run-length code has {n} counts and was cut at max_runs = {cap}; it needs max_runs >= {n}")
-        out.append({"image_id": ids[b], "category_id": c, "bbox": [x0, y0, bw, bh], "area": area,
-                    "segmentation": {"size": [H, W], "counts": code[b, :n].tolist()}})
+        rec = {"image_id": ids[b], "category_id": c, "bbox": [x0, y0, bw, bh], "area": area,
+               "segmentation": {"size": [H, W], "counts": code[b, :n].tolist()}}
+        if scores is not None:
+            if scores[b] != scores[b]:
+                raise ValueError(f"image {ids[b]}: the score is NaN (a NaN among the head's class logits)")
+            rec["score"] = scores[b]
+        out.append(rec)
     return out
 
 

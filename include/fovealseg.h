@@ -214,6 +214,28 @@ int fs_mask_rle(const unsigned int* bits, long long* stats, int* counts, int* sc
 long fs_unwarp_instances_scratch_ints(int B, int h, int w, int Hs, int Ws);
 int fs_unwarp_instances(const float* cls, const float* m, const float* grid, long long* cat, long long* stats, int* counts,
                         unsigned int* bits, int* scratch, int B, int K, int h, int w, int Hs, int Ws, int cap, fs_stream_t stream);
+/* The foreground probability of the C1 head per grid point, as an integer (no counterpart in the reference: UNPINNED, a definition of
+ * this library's).  v[b,:,p] = the K fp32 values that the bilinear sample of the prediction (fs_pred_assemble_fwd's) holds at grid point
+ * p's inverse coordinate, p < h*w, and at (0,0) for p = h*w -- the values fs_unwarp_labels takes the argmax of, formed by the same
+ * float operations.  P = sum_{k<K-1} exp(v_k - max v) / sum_{k<K} exp(v_k - max v), evaluated in fp64 from the fp32 v: the softmax mass
+ * of the classes below K-1.  q (B, h*w+1) int32 = rint(P * 2^24), 0 .. 2^24; 0 where P is NaN (a NaN or +inf among the v, or every v
+ * -inf).  FS_ERR_ARG for a null pointer, non-positive sizes, K < 2 or K > 1024. */
+int fs_head_fg_q(const float* cls, const float* m, int* q, int B, int K, int h, int w, fs_stream_t stream);
+/* fs_unwarp_instances with a confidence for the record (UNPINNED, as the run-length code): cat, stats, counts and bits are
+ * fs_unwarp_instances' bit for bit.  qsum (B) int64 = the sum of fs_head_fg_q's q[b, feeding point] over the set pixels of the mask,
+ * added in the gather that stores the bit words; below 2^55, and an integer sum: the same bits in every order and precision mode.
+ * conf (B,3) fp32 = (score, cls_prob, mask_prob): mask_prob = qsum / (area * 2^24) formed in fp64, 0 for an empty mask; cls_prob =
+ * the fp64 softmax over cls[b, :K-1] at cat[b], NaN where that row holds a NaN; score = the fp64 product of the two; each rounded to
+ * fp32 once.  Where no tap of a set pixel's sample lies out of bounds, P * cls_prob is the K-way softmax probability of class cat
+ * there: score is the mean probability of the predicted class over the predicted mask.  Every wave of the gather stores the sum of
+ * its first image as a record, summed per image in a fixed pass; only a wave that straddles two images adds the second one's part
+ * with a 64-bit integer atomic.  scratch = fs_unwarp_instances_scored_scratch_ints(B, h, w, Hs, Ws) ints >= the unscored query, by the
+ * table's B * (h*w+1) ints, the records (a quarter of an int per bit word where Ws % 4 == 0, half of one otherwise) and alignment: less than a bit a pixel.  FS_ERR_ARG, with nothing launched, as fs_unwarp_instances, and for a null conf or
+ * qsum. */
+long fs_unwarp_instances_scored_scratch_ints(int B, int h, int w, int Hs, int Ws);
+int fs_unwarp_instances_scored(const float* cls, const float* m, const float* grid, long long* cat, long long* stats, int* counts,
+                               unsigned int* bits, float* conf, long long* qsum, int* scratch, int B, int K, int h, int w, int Hs,
+                               int Ws, int cap, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
