@@ -1,0 +1,372 @@
+// The gaze gate: does the record a viewer already holds still answer "which instance is looked at" for a new frame and gaze?
+// (no counterpart in the reference: UNPINNED, a definition of this library's).  All of it is integer work.  Passes:
+//   tiles    the hot pass: the new frame against the 8-bit key frame the record was made from, one sum of absolute differences per
+//            T x T tile.  15 bytes read per pixel, one int written per tile; every entry is one workgroup's and is stored plainly.
+//   decide   a workgroup per viewer sums the tiles (changed tiles, changed tiles of the region of interest, total), one lane applies
+//            the decision table.  Pure: it writes the gate record only.
+//   commit   for the viewers that ran the network: the frame becomes the key frame, the gaze the key gaze, the new record's rows move to
+//            the viewer's slots; every viewer's previous gaze and age advance.
+// The pixel code q and the gaze in 1/16-pixel units are one function each, used by every pass that needs them: a frame against the
+// key that commit made from it differs nowhere, NaN pixels included.
+#include "common.h"
+
+namespace {
+
+constexpr long GATE_INT_LIMIT = 2147483647L;           // pixel and tile indices are ints
+constexpr long GATE_WGS_MAX = 16777215L;               // workgroups of 256 threads: fewer than 2^32 work-items a launch
+constexpr int GATE_MAX_SIDE = 1 << 26;                 // decide / commit: the gaze in 1/16 pixels stays below 2^30, its squared distances below 2^62
+constexpr int GATE_THREADS = 256;
+
+// q(v) = (int) rintf(fminf(fmaxf(v, 0), 1) * 255.0f): one fp32 multiply, round to nearest even; NaN -> 0.  The clamps are written as
+// comparisons so that a NaN takes the first branch's 0 whatever the min / max instructions make of it.
+__device__ __forceinline__ int gate_q(float v) {
+  v = v > 0.f ? v : 0.f;
+  v = v < 1.f ? v : 1.f;
+  return (int)rintf(__fmul_rn(v, 255.0f));
+}
+
+// the gaze coordinate in 1/16-pixel units: clamp(rint((double)f * ((side - 1) * 16)), 0, (side - 1) * 16), NaN -> 0
+__device__ __forceinline__ long long gate_gaze(float f, int side) {
+  const double top = (double)(((long long)side - 1) * 16);
+  double v = rint(__dmul_rn((double)f, top));
+  v = v > 0.0 ? v : 0.0;
+  v = v < top ? v : top;
+  return (long long)v;
+}
+
+__device__ __forceinline__ long long gate_d2(long long ay, long long ax, long long by, long long bx) {
+  const long long dy = ay - by, dx = ax - bx;
+  return dy * dy + dx * dx;
+}
+
+__device__ __forceinline__ int gate_wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+__device__ __forceinline__ long long gate_wave_sum(long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__device__ __forceinline__ int gate_absdiff(float v, unsigned int k) {
+  const int d = gate_q(v) - (int)k;
+  return d < 0 ? -d : d;
+}
+
+constexpr int GATE_SEG = 256;                          // the four-pixel form: columns a workgroup covers, four a lane
+
+// The four-pixel form (W % 4 == 0, img 16-byte and key 4-byte aligned): one workgroup per (viewer, tile row, 256-column segment).  A
+// lane takes four pixels of a row -- a 16-byte load of img and a 4-byte load of key per channel -- so a wave reads 1 KB of one row at
+// a time and the four waves take every fourth row of the band.  The T / 4 lanes of a tile are neighbours: their sums meet by
+// shuffles, the four waves' through LDS, and one lane per tile stores the entry.
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_band_kernel(const float* __restrict__ img, const unsigned char* __restrict__ key,
+                                                                       int* __restrict__ sad, int H, int W, int T, int th, int tw, int nseg) {
+  __shared__ int red[GATE_THREADS / 64][GATE_SEG / 8];
+  const unsigned int blk = blockIdx.x;
+  const int seg = (int)(blk % (unsigned)nseg);
+  const int ty = (int)((blk / (unsigned)nseg) % (unsigned)th);
+  const size_t b = blk / (unsigned)nseg / (unsigned)th;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int y0 = ty * T, rows = min(T, H - y0);
+  const int x = seg * GATE_SEG + lane * 4;
+  const size_t plane = (size_t)H * W;
+  int s = 0;
+  if (x < W) {
+    const size_t base = b * 3 * plane + (size_t)y0 * W + x;
+#pragma unroll 2
+    for (int r = wave; r < rows; r += GATE_THREADS / 64) {
+      const size_t at = base + (size_t)r * W;
+      f32x4 v[3];
+      unsigned int k[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        v[c] = *reinterpret_cast<const f32x4*>(img + at + c * plane);
+        k[c] = *reinterpret_cast<const unsigned int*>(key + at + c * plane);
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        s += gate_absdiff(v[c].x, k[c] & 255u) + gate_absdiff(v[c].y, (k[c] >> 8) & 255u) + gate_absdiff(v[c].z, (k[c] >> 16) & 255u) +
+             gate_absdiff(v[c].w, k[c] >> 24);
+    }
+  }
+  const int lanes = T >> 2;                            // lanes a tile: 2, 4, 8 or 16
+  for (int o = lanes >> 1; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((lane & (lanes - 1)) == 0) red[wave][lane / lanes] = s;
+  __syncthreads();
+  const int per_seg = GATE_SEG / T, tx = seg * per_seg + (int)threadIdx.x;
+  if ((int)threadIdx.x < per_seg && tx < tw)
+    sad[(b * th + ty) * tw + tx] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// The one-pixel form, for any width and alignment: one workgroup per (viewer, tile row, tile column), a lane takes a pixel of the tile
+// and reads its three channels.
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_kernel(const float* __restrict__ img, const unsigned char* __restrict__ key,
+                                                                  int* __restrict__ sad, int H, int W, int T, int th, int tw) {
+  __shared__ int red[GATE_THREADS / 64];
+  const unsigned int blk = blockIdx.x;
+  const int tx = (int)(blk % (unsigned)tw);
+  const int ty = (int)((blk / (unsigned)tw) % (unsigned)th);
+  const size_t b = blk / (unsigned)tw / (unsigned)th;
+  const int y0 = ty * T, x0 = tx * T;
+  const int rows = min(T, H - y0), cols = min(T, W - x0);
+  const size_t plane = (size_t)H * W;
+  const size_t base = b * 3 * plane + (size_t)y0 * W + x0;
+  int s = 0;
+  const int per = rows * cols;
+  for (int j = threadIdx.x; j < per; j += GATE_THREADS) {
+    const int r = j / cols, x = j - r * cols;
+    const size_t at = base + (size_t)r * W + x;
+    float v[3];
+    unsigned int k[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      v[c] = img[at + c * plane];
+      k[c] = key[at + c * plane];
+    }
+    s += gate_absdiff(v[0], k[0]) + gate_absdiff(v[1], k[1]) + gate_absdiff(v[2], k[2]);
+  }
+  s = gate_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) sad[blk] = red[0] + red[1] + red[2] + red[3];
+}
+
+struct GateRule {
+  int H, W, T, th, tw, P;
+  int level, scene_tiles, roi_tiles, margin, max_age, inside_on;
+  long long saccade2, fixation2;
+};
+
+// gstate (B,6) = (valid, gy_key, gx_key, gy_prev, gx_prev, age); stats (B,6) = fs_mask_rle's (area, x0, y0, bw, bh, n_runs);
+// gate (B,8) = (code, n_changed, n_roi_changed, sad_total, d2_key, d2_prev, inside_bit, age + 1)
+__global__ __launch_bounds__(GATE_THREADS) void gate_decide_kernel(const int* __restrict__ sad, const long long* __restrict__ gstate,
+                                                                   const float* __restrict__ focus, const long long* __restrict__ stats,
+                                                                   const unsigned int* __restrict__ bits, const int* __restrict__ force,
+                                                                   long long* __restrict__ gate, GateRule p) {
+  __shared__ int red_c[GATE_THREADS / 64], red_r[GATE_THREADS / 64];
+  __shared__ long long red_t[GATE_THREADS / 64];
+  const size_t b = blockIdx.x;
+  const long long gy = gate_gaze(focus[2 * b], p.H), gx = gate_gaze(focus[2 * b + 1], p.W);
+  const int py = (int)((gy + 8) >> 4), px = (int)((gx + 8) >> 4);
+  const int gty = py / p.T, gtx = px / p.T;
+  // the record's box grown by the margin and clipped, as a range of tiles; empty for an empty mask
+  const long long* st = stats + b * 6;
+  int tx0 = 1, tx1 = 0, ty0 = 1, ty1 = 0;
+  if (st[0] != 0) {
+    const long long bx0 = max(st[1] - p.margin, 0LL), bx1 = min(st[1] + st[3] + p.margin, (long long)p.W);
+    const long long by0 = max(st[2] - p.margin, 0LL), by1 = min(st[2] + st[4] + p.margin, (long long)p.H);
+    if (bx0 < bx1 && by0 < by1) {
+      tx0 = (int)(bx0 / p.T), tx1 = (int)((bx1 - 1) / p.T);
+      ty0 = (int)(by0 / p.T), ty1 = (int)((by1 - 1) / p.T);
+    }
+  }
+  const int tiles = p.th * p.tw;
+  const int* sb = sad + b * tiles;
+  int nc = 0, nr = 0;
+  long long tot = 0;
+  for (int i = threadIdx.x; i < tiles; i += GATE_THREADS) {
+    const int ty = i / p.tw, tx = i - ty * p.tw;
+    const int n_el = 3 * min(p.T, p.H - ty * p.T) * min(p.T, p.W - tx * p.T);
+    const int s = sb[i];
+    const bool changed = s > p.level * n_el;
+    const bool roi = (tx >= tx0 && tx <= tx1 && ty >= ty0 && ty <= ty1) || (tx == gtx && ty == gty);
+    nc += changed ? 1 : 0;
+    nr += (changed && roi) ? 1 : 0;
+    tot += s;
+  }
+  nc = gate_wave_sum(nc);
+  nr = gate_wave_sum(nr);
+  tot = gate_wave_sum(tot);
+  if ((threadIdx.x & 63) == 0) {
+    red_c[threadIdx.x >> 6] = nc;
+    red_r[threadIdx.x >> 6] = nr;
+    red_t[threadIdx.x >> 6] = tot;
+  }
+  __syncthreads();
+  if (threadIdx.x != 0) return;
+  nc = red_c[0] + red_c[1] + red_c[2] + red_c[3];
+  nr = red_r[0] + red_r[1] + red_r[2] + red_r[3];
+  tot = red_t[0] + red_t[1] + red_t[2] + red_t[3];
+  const long long* g = gstate + b * 6;
+  const long long valid = g[0], age1 = g[5] + 1;
+  const long long d2_key = gate_d2(gy, gx, g[1], g[2]), d2_prev = gate_d2(gy, gx, g[3], g[4]);
+  const int inside = (int)((bits[(b * p.H + py) * p.P + (px >> 5)] >> (px & 31)) & 1u);
+  int code = 0;
+  if (force != nullptr && force[b] != 0) code = 7;
+  else if (valid == 0) code = 1;
+  else if (d2_prev > p.saccade2) code = 2;
+  else if (nc > p.scene_tiles) code = 3;
+  else if (nr > p.roi_tiles) code = 4;
+  else if (!(p.inside_on != 0 && inside != 0) && d2_key > p.fixation2) code = 5;
+  else if (p.max_age > 0 && age1 > p.max_age) code = 6;
+  long long* o = gate + b * 8;
+  o[0] = code;
+  o[1] = nc;
+  o[2] = nr;
+  o[3] = tot;
+  o[4] = d2_key;
+  o[5] = d2_prev;
+  o[6] = inside;
+  o[7] = age1;
+}
+
+// is viewer b among idx[0 .. n), ascending?
+__device__ __forceinline__ bool gate_ran(const int* __restrict__ idx, int n, int b) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (idx[mid] < b) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && idx[lo] == b;
+}
+
+// one lane per viewer: g_prev <- g for all; a viewer that ran gets g_key <- g, age <- 0, valid <- 1, any other age <- age + 1
+__global__ void gate_commit_state_kernel(const int* __restrict__ idx, int n, long long* __restrict__ gstate, const float* __restrict__ focus,
+                                         int B, int H, int W) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const long long gy = gate_gaze(focus[2 * (size_t)b], H), gx = gate_gaze(focus[2 * (size_t)b + 1], W);
+  long long* g = gstate + (size_t)b * 6;
+  if (n > 0 && gate_ran(idx, n, b)) {
+    g[0] = 1;
+    g[1] = gy;
+    g[2] = gx;
+    g[5] = 0;
+  } else {
+    g[5] = g[5] + 1;
+  }
+  g[3] = gy;
+  g[4] = gx;
+}
+
+// key[idx[j]] <- q(img[idx[j]]): bpi workgroups a viewer; VEC as in the tile pass, four pixels a lane and one 4-byte store
+template <bool VEC>
+__global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_kernel(const float* __restrict__ img, const int* __restrict__ idx,
+                                                                         unsigned char* __restrict__ key, int B, size_t per, unsigned int bpi) {
+  const unsigned int j = blockIdx.x / bpi;
+  const int b = idx[j];
+  if (b < 0 || b >= B) return;                         // an index outside the batch writes nothing
+  const size_t e = ((size_t)(blockIdx.x - j * bpi) * GATE_THREADS + threadIdx.x) * (VEC ? 4 : 1);
+  if (e >= per) return;
+  const size_t at = (size_t)b * per + e;
+  if (VEC) {
+    const f32x4 v = *reinterpret_cast<const f32x4*>(img + at);
+    const unsigned int k = (unsigned int)gate_q(v.x) | ((unsigned int)gate_q(v.y) << 8) | ((unsigned int)gate_q(v.z) << 16) |
+                           ((unsigned int)gate_q(v.w) << 24);
+    *reinterpret_cast<unsigned int*>(key + at) = k;
+  } else {
+    key[at] = (unsigned char)gate_q(img[at]);
+  }
+}
+
+// The record tensors as rows of 32-bit words (an int64 is two): cat 2, stats 12, counts cap, bits H * P, conf 3.  src == dst (or a
+// null pair, conf) is a part of no words.
+struct GateRows {
+  const unsigned int* src[5];
+  unsigned int* dst[5];
+  unsigned int words[5];
+  unsigned int total;
+};
+
+// row j of every part -> row idx[j]; bpr workgroups a row
+__global__ __launch_bounds__(GATE_THREADS) void gate_commit_rows_kernel(const int* __restrict__ idx, int B, GateRows r, unsigned int bpr) {
+  const unsigned int j = blockIdx.x / bpr;
+  const int b = idx[j];
+  if (b < 0 || b >= B) return;
+  unsigned int w = (blockIdx.x - j * bpr) * GATE_THREADS + threadIdx.x;
+  if (w >= r.total) return;
+#pragma unroll
+  for (int k = 0; k < 5; ++k) {
+    if (w < r.words[k]) {
+      r.dst[k][(size_t)b * r.words[k] + w] = r.src[k][(size_t)j * r.words[k] + w];
+      return;
+    }
+    w -= r.words[k];
+  }
+}
+
+bool gate_tile_ok(int T) { return T == 8 || T == 16 || T == 32 || T == 64; }
+bool gate_vec_ok(const float* img, const unsigned char* key, int W) {
+  return W % 4 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)key & 3) == 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fs_gate_tiles(const float* img, const unsigned char* key, int* sad, int B, int H, int W, int T, hipStream_t stream) {
+  FS_REQUIRE(img && key && sad && B > 0 && H > 0 && W > 0 && gate_tile_ok(T) && (long)H * W < GATE_INT_LIMIT);
+  const int th = cdiv(H, T), tw = cdiv(W, T);
+  const bool vec = gate_vec_ok(img, key, W);
+  const int nseg = cdiv(W, GATE_SEG);
+  const long wgs = (long)B * th * (vec ? nseg : tw);
+  FS_REQUIRE((long)B * th * tw <= GATE_WGS_MAX);
+  if (vec)
+    hipLaunchKernelGGL(gate_tiles_band_kernel, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, key, sad, H, W, T, th, tw, nseg);
+  else
+    hipLaunchKernelGGL(gate_tiles_kernel, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, key, sad, H, W, T, th, tw);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+int fs_gate_decide(const int* sad, const long long* gstate, const float* focus, const long long* stats, const unsigned int* bits,
+                   const int* force, long long* gate, int B, int H, int W, int T, int level, int scene_tiles, int roi_tiles, int margin,
+                   long saccade2, long fixation2, int max_age, int inside_on, hipStream_t stream) {
+  FS_REQUIRE(sad && gstate && focus && stats && bits && gate && B > 0 && H > 0 && W > 0 && gate_tile_ok(T) && (long)H * W < GATE_INT_LIMIT);
+  FS_REQUIRE(level >= 0 && level <= 254 && margin >= 0 && H <= GATE_MAX_SIDE && W <= GATE_MAX_SIDE && B <= GATE_WGS_MAX);
+  GateRule p;
+  p.H = H, p.W = W, p.T = T, p.th = cdiv(H, T), p.tw = cdiv(W, T), p.P = (W + 31) / 32;
+  p.level = level, p.scene_tiles = scene_tiles, p.roi_tiles = roi_tiles, p.margin = margin, p.max_age = max_age, p.inside_on = inside_on;
+  p.saccade2 = saccade2, p.fixation2 = fixation2;
+  hipLaunchKernelGGL(gate_decide_kernel, dim3((unsigned)B), dim3(GATE_THREADS), 0, stream, sad, gstate, focus, stats, bits, force, gate, p);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+int fs_gate_commit(const float* img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus,
+                   const long long* src_cat, const long long* src_stats, const int* src_counts, const unsigned int* src_bits,
+                   const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts, unsigned int* dst_bits, float* dst_conf,
+                   int B, int H, int W, int cap, hipStream_t stream) {
+  FS_REQUIRE(img && key && gstate && focus && B > 0 && H > 0 && W > 0 && (long)H * W < GATE_INT_LIMIT && n >= 0 && n <= B);
+  FS_REQUIRE(H <= GATE_MAX_SIDE && W <= GATE_MAX_SIDE && cap >= 1);
+  FS_REQUIRE(src_cat && src_stats && src_counts && src_bits && dst_cat && dst_stats && dst_counts && dst_bits);
+  FS_REQUIRE((src_conf == nullptr) == (dst_conf == nullptr) && (n == 0 || idx != nullptr));
+  const size_t per = (size_t)3 * H * W;
+  const bool vec = gate_vec_ok(img, key, W);
+  const long bpi = (long)((per / (vec ? 4 : 1) + GATE_THREADS - 1) / GATE_THREADS);
+  GateRows r;
+  const long nbits = (long)H * ((W + 31) / 32);
+  const void* src[5] = {src_cat, src_stats, src_counts, src_bits, src_conf};
+  void* dst[5] = {dst_cat, dst_stats, dst_counts, dst_bits, dst_conf};
+  const long words[5] = {2, 12, cap, nbits, 3};
+  long total = 0;
+  for (int k = 0; k < 5; ++k) {
+    const bool moves = src[k] != nullptr && src[k] != dst[k];
+    r.src[k] = static_cast<const unsigned int*>(src[k]);
+    r.dst[k] = static_cast<unsigned int*>(dst[k]);
+    r.words[k] = moves ? (unsigned int)words[k] : 0u;
+    total += moves ? words[k] : 0;
+  }
+  FS_REQUIRE(total < GATE_INT_LIMIT);
+  r.total = (unsigned int)total;
+  const long bpr = (total + GATE_THREADS - 1) / GATE_THREADS;
+  FS_REQUIRE((long)n * bpi <= GATE_WGS_MAX && (long)n * bpr <= GATE_WGS_MAX);
+  hipLaunchKernelGGL(gate_commit_state_kernel, dim3((unsigned)cdiv(B, GATE_THREADS)), dim3(GATE_THREADS), 0, stream, idx, n, gstate, focus, B, H, W);
+  FS_LAUNCH_CHECK();
+  if (n == 0) return FS_OK;
+  if (vec)
+    hipLaunchKernelGGL(gate_commit_frame_kernel<true>, dim3((unsigned)(n * bpi)), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
+  else
+    hipLaunchKernelGGL(gate_commit_frame_kernel<false>, dim3((unsigned)(n * bpi)), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
+  FS_LAUNCH_CHECK();
+  if (total > 0) {
+    hipLaunchKernelGGL(gate_commit_rows_kernel, dim3((unsigned)(n * bpr)), dim3(GATE_THREADS), 0, stream, idx, B, r, (unsigned)bpr);
+    FS_LAUNCH_CHECK();
+  }
+  return FS_OK;
+}
+
+}  // extern "C"

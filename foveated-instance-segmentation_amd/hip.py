@@ -51,6 +51,9 @@ SIGNATURES = {
     "fs_unwarp_instances": "pppppppp" + "iiiiiii",
     "fs_head_fg_q": "ppp" + "iiii",
     "fs_unwarp_instances_scored": "pppppppppp" + "iiiiiii",
+    "fs_gate_tiles": "ppp" + "iiii",
+    "fs_gate_decide": "ppppppp" + "iiiiiiii" + "ll" + "ii",
+    "fs_gate_commit": "pp" + "i" + "p" * 13 + "iiii",
     "fs_conv2d_fwd": "ppppiiiiiiiiiiiifuplp",
     "fs_conv2d_fwd_residual": "ppppp" + "iiiiiiiiiiii" + "fufu" + "l" + "plp",
     "fs_conv2d_fwd_stats": "pppppiiiiiiiiiiiifuplp",

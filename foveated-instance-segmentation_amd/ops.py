@@ -1643,6 +1643,101 @@ def instances_to_coco(cat, stats, counts, seg_size, image_ids=None, conf=None):
     return out
 
 
+GATE_TILES = (8, 16, 32, 64)
+GATE_CODES = {0: "REUSE", 1: "RUN_INIT", 2: "HOLD_SACCADE", 3: "RUN_SCENE", 4: "RUN_ROI", 5: "RUN_GAZE", 6: "RUN_AGE", 7: "RUN_FORCED"}
+GATE_RUNS = (1, 3, 4, 5, 6, 7)                      # the codes after which the network runs
+
+
+def _gate_tile(T):
+    if isinstance(T, bool) or int(T) != T or int(T) not in GATE_TILES:
+        raise ValueError(f"the tile side must be one of {GATE_TILES}, got {T!r}")
+    return int(T)
+
+
+def gate_tiles(img, key, tile=32, out=None):
+    """How much every tile of new frames differs from the 8-bit key frames (fs_gate_tiles; no autograd; unpinned: the reference has
+    no counterpart).  img (B,3,H,W) fp32, key (B,3,H,W) uint8 = q of the frames the records were made from, q(v) = rint(clamp(v, 0, 1) *
+    255) in fp32, NaN -> 0.  Returns sad (B,th,tw) int32, th = ceil(H / tile), tw = ceil(W / tile): the sum of |q(img) - key| over the
+    three channels and the tile's pixels (the last tiles are ragged).  out: a (B,th,tw) int32 tensor to write into."""
+    T = _gate_tile(tile)
+    if img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != torch.float32:
+        raise ValueError(f"img must be a non-empty fp32 (B,3,H,W), got {img.dtype} {tuple(img.shape)}")
+    if key.dtype != torch.uint8 or key.shape != img.shape:
+        raise ValueError(f"key must be uint8 {tuple(img.shape)}, got {key.dtype} {tuple(key.shape)}")
+    B, _, H, W = (int(v) for v in img.shape)
+    shape = (B, (H + T - 1) // T, (W + T - 1) // T)
+    if out is None:
+        out = torch.empty(shape, device=img.device, dtype=torch.int32)
+    elif out.dtype != torch.int32 or tuple(out.shape) != shape:
+        raise ValueError(f"out must be int32 {shape}, got {out.dtype} {tuple(out.shape)}")
+    hip.call("fs_gate_tiles", hip.ptr(img), hip.ptr(key), hip.ptr(out), B, H, W, T)
+    return out
+
+
+def gate_decide(sad, gstate, focus, stats, bits, frame_size, tile=32, level=8, scene_tiles=0, roi_tiles=0, margin=16,
+                saccade2=2 ** 62, fixation2=0, max_age=0, inside_on=True, force=None, out=None):
+    """The gate's decision per viewer (fs_gate_decide; no autograd; unpinned).  sad (B,th,tw) int32 as gate_tiles returns it; gstate
+    (B,6) int64 = (valid, gy_key, gx_key, gy_prev, gx_prev, age), gazes in 1/16-pixel units; focus (B,2) fp32 normalised (row, col);
+    stats (B,6) int64 and bits (B,H,ceil(W/32)) int32 the records' (mask_rle, mask_bits); force (B,) int32 or None; frame_size = (H, W).
+    saccade2 and fixation2 are squared distances in 1/16-pixel units, floor((px * 16) ** 2).  Returns gate (B,8) int64 = (code,
+    n_changed, n_roi_changed, sad_total, d2_key, d2_prev, inside_bit, age + 1); the codes are GATE_CODES, the first rule that holds in
+    the order 7, 1, 2, 3, 4, 5, 6, 0 (include/fovealseg.h).  Nothing but gate is written."""
+    T = _gate_tile(tile)
+    H, W = int(frame_size[0]), int(frame_size[1])
+    B = int(sad.shape[0])
+    if sad.dtype != torch.int32 or tuple(sad.shape) != (B, (H + T - 1) // T, (W + T - 1) // T):
+        raise ValueError(f"sad must be int32 (B, ceil(H/T), ceil(W/T)) for H, W, T = {H}, {W}, {T}, got {sad.dtype} {tuple(sad.shape)}")
+    if gstate.dtype != torch.int64 or tuple(gstate.shape) != (B, 6) or stats.dtype != torch.int64 or tuple(stats.shape) != (B, 6):
+        raise ValueError(f"gstate and stats must be int64 ({B}, 6), got {tuple(gstate.shape)} and {tuple(stats.shape)}")
+    if focus.dtype != torch.float32 or tuple(focus.shape) != (B, 2):
+        raise ValueError(f"focus must be fp32 ({B}, 2), got {focus.dtype} {tuple(focus.shape)}")
+    if bits.dtype != torch.int32 or tuple(bits.shape) != (B, H, (W + 31) // 32):
+        raise ValueError(f"bits must be int32 {(B, H, (W + 31) // 32)}, got {bits.dtype} {tuple(bits.shape)}")
+    if force is not None and (force.dtype != torch.int32 or tuple(force.shape) != (B,)):
+        raise ValueError(f"force must be int32 ({B},), got {force.dtype} {tuple(force.shape)}")
+    if isinstance(level, bool) or int(level) != level or not 0 <= int(level) <= 254:
+        raise ValueError(f"level must be an integer 0 .. 254, got {level!r}")
+    if int(margin) < 0:
+        raise ValueError(f"margin must be >= 0, got {margin!r}")
+    if out is None:
+        out = torch.empty(B, 8, device=sad.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (B, 8):
+        raise ValueError(f"out must be int64 ({B}, 8), got {out.dtype} {tuple(out.shape)}")
+    hip.call("fs_gate_decide", hip.ptr(sad), hip.ptr(gstate), hip.ptr(focus), hip.ptr(stats), hip.ptr(bits), hip.ptr(force), hip.ptr(out),
+             B, H, W, T, int(level), int(scene_tiles), int(roi_tiles), int(margin), int(saccade2), int(fixation2), int(max_age),
+             1 if inside_on else 0)
+    return out
+
+
+def gate_commit(img, idx, key, gstate, focus, src, dst):
+    """What a step leaves behind (fs_gate_commit; no autograd; unpinned), in place.  idx (n,) int32 ascending, or None for n = 0: the
+    viewers whose record was made anew from img (B,3,H,W) fp32.  src = (cat, stats, counts, bits[, conf]) with n rows, dst the same
+    with B rows: row j moves to row idx[j]; a pair that is one tensor is already in place.  For the viewers of idx key (B,3,H,W) uint8
+    <- q(img), g_key <- g, age <- 0, valid <- 1 in gstate (B,6) int64; for every viewer g_prev <- g; any other viewer's age grows by
+    one.  With n = 0 src is not read (pass dst)."""
+    B, _, H, W = (int(v) for v in img.shape)
+    n = 0 if idx is None else int(idx.shape[0])
+    if img.dim() != 4 or img.shape[1] != 3 or img.dtype != torch.float32 or key.dtype != torch.uint8 or key.shape != img.shape:
+        raise ValueError(f"img must be fp32 (B,3,H,W) and key uint8 of its shape, got {tuple(img.shape)} and {tuple(key.shape)}")
+    if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 1 or n > B):
+        raise ValueError(f"idx must be int32 (n,) with n <= {B}, got {idx.dtype} {tuple(idx.shape)}")
+    if gstate.dtype != torch.int64 or tuple(gstate.shape) != (B, 6) or focus.dtype != torch.float32 or tuple(focus.shape) != (B, 2):
+        raise ValueError(f"gstate must be int64 ({B}, 6) and focus fp32 ({B}, 2), got {tuple(gstate.shape)} and {tuple(focus.shape)}")
+    if len(src) != len(dst) or len(dst) not in (4, 5):
+        raise ValueError("src and dst must both be (cat, stats, counts, bits) or (cat, stats, counts, bits, conf)")
+    cap = int(dst[2].shape[1])
+    tails = ((), (6,), (cap,), (H, (W + 31) // 32), (3,))
+    dtypes = (torch.int64, torch.int64, torch.int32, torch.int32, torch.float32)
+    for s, d, tail, dt in zip(src, dst, tails, dtypes):
+        if d.dtype != dt or tuple(d.shape) != (B,) + tail:
+            raise ValueError(f"a dst record tensor must be {dt} {(B,) + tail}, got {d.dtype} {tuple(d.shape)}")
+        if s is not d and n > 0 and (s.dtype != dt or tuple(s.shape) != (n,) + tail):
+            raise ValueError(f"a src record tensor must be {dt} {(n,) + tail}, got {s.dtype} {tuple(s.shape)}")
+    sp = [hip.ptr(s) for s in src] + [None] * (5 - len(src))
+    dp = [hip.ptr(d) for d in dst] + [None] * (5 - len(dst))
+    hip.call("fs_gate_commit", hip.ptr(img), hip.ptr(idx), n, hip.ptr(key), hip.ptr(gstate), hip.ptr(focus), *sp, *dp, B, H, W, cap)
+
+
 def _hd_q(q):
     if isinstance(q, bool) or int(q) != q or not 1 <= int(q) <= 100:
         raise ValueError(f"the Hausdorff percentile must be an integer 1 .. 100, got {q!r}")

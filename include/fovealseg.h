@@ -236,6 +236,42 @@ long fs_unwarp_instances_scored_scratch_ints(int B, int h, int w, int Hs, int Ws
 int fs_unwarp_instances_scored(const float* cls, const float* m, const float* grid, long long* cat, long long* stats, int* counts,
                                unsigned int* bits, float* conf, long long* qsum, int* scratch, int B, int K, int h, int w, int Hs,
                                int Ws, int cap, fs_stream_t stream);
+/* The gaze gate (no counterpart in the reference: UNPINNED, a definition of this library's): does the record a viewer
+ * holds still answer for a new frame and gaze?  All integers.  Pixel code q(v) = (int) rintf(fminf(fmaxf(v, 0), 1) * 255.0f): one fp32
+ * multiply, round to nearest even, NaN -> 0, k/255 -> k.  fs_gate_tiles, the hot pass: img (B,3,H,W) fp32 NCHW, the new frames; key
+ * (B,3,H,W) bytes, q of the frame each viewer's record was made from; T in {8, 16, 32, 64}, th = ceil(H/T), tw = ceil(W/T), the last
+ * tiles ragged.  sad (B,th,tw) int32 = the sum over the 3 channels and the tile's pixels of |q(img) - key|.  15 bytes read per pixel;
+ * every entry is one workgroup's, written with a plain store: no atomics, nothing to zero.  Four pixels a lane (a 16-byte load of img, a
+ * 4-byte load of key) where W % 4 == 0, img is 16-byte and key 4-byte aligned; one pixel a lane otherwise.  FS_ERR_ARG, with nothing
+ * launched, for a null pointer, non-positive sizes, T outside the set, H * W >= 2^31 or more than 2^24 - 1 tiles. */
+int fs_gate_tiles(const float* img, const unsigned char* key, int* sad, int B, int H, int W, int T, fs_stream_t stream);
+/* The decision per viewer (UNPINNED).  sad as fs_gate_tiles makes it; gstate (B,6) int64 = (valid, gy_key, gx_key, gy_prev, gx_prev,
+ * age); focus (B,2) fp32 = normalised (row, col); stats (B,6) int64 and bits (B,H,P) the record's, as fs_mask_rle / fs_mask_bits make
+ * them; force (B) int32, nullable.  The gaze in 1/16-pixel units: gy = clamp(rint((double)f_row * ((H-1)*16)), 0, (H-1)*16), gx likewise
+ * with W, NaN -> 0; the gaze pixel (py, px) = ((gy+8)>>4, (gx+8)>>4); d2 = the squared distance of two such points.  A tile is changed
+ * iff sad > level * n_el, n_el = 3 * its true pixel count.  The region of interest is every tile that meets the box [x0, y0, bw, bh]
+ * grown by margin pixels and clipped (nothing when area = 0), plus the tile of the gaze pixel.  The first rule that holds decides:
+ *   7 RUN_FORCED force[b] != 0;  1 RUN_INIT valid == 0;  2 HOLD_SACCADE d2(g, g_prev) > saccade2;  3 RUN_SCENE n_changed > scene_tiles;
+ *   4 RUN_ROI n_roi_changed > roi_tiles;  5 RUN_GAZE not (inside_on and the mask's bit at (py, px)) and d2(g, g_key) > fixation2;
+ *   6 RUN_AGE max_age > 0 and age + 1 > max_age;  0 REUSE.
+ * gate (B,8) int64 = (code, n_changed, n_roi_changed, sad_total, d2_key, d2_prev, inside_bit, age + 1), every column written for every
+ * viewer.  One workgroup a viewer sums its tiles, one lane decides; nothing but gate is written.  The thresholds come squared, in
+ * 1/16-pixel units: floor((px * 16)^2).  FS_ERR_ARG, with nothing launched, for a null pointer other than force, non-positive sizes, T
+ * outside the set, level outside 0 .. 254, margin < 0, H * W >= 2^31, or a side above 2^26 (d2 stays below 2^62). */
+int fs_gate_decide(const int* sad, const long long* gstate, const float* focus, const long long* stats, const unsigned int* bits,
+                   const int* force, long long* gate, int B, int H, int W, int T, int level, int scene_tiles, int roi_tiles, int margin,
+                   long saccade2, long fixation2, int max_age, int inside_on, fs_stream_t stream);
+/* What a step leaves behind (UNPINNED).  idx (n) int32 ascending = the viewers whose record was made anew; row j of the src tensors
+ * (cat (n), stats (n,6) int64, counts (n,cap) int32, bits (n,H,P), conf (n,3) fp32) belongs to viewer idx[j].  For those viewers key <-
+ * q(img[idx[j]]) (img is the whole (B,3,H,W) batch), g_key <- g, age <- 0, valid <- 1, and the rows are copied j -> idx[j] into the dst
+ * tensors of B rows.  For every viewer g_prev <- g; one that is not in idx gets age <- age + 1.  A pair with src == dst is already in
+ * place and is not touched; conf is nullable, as a pair.  n == 0: the state pass alone is launched, idx may be null.  An idx entry
+ * outside 0 .. B-1 writes nothing.  FS_ERR_ARG, with nothing launched, for a null pointer, non-positive sizes, cap < 1, n outside 0 ..
+ * B, H * W >= 2^31 or a side above 2^26. */
+int fs_gate_commit(const float* img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus,
+                   const long long* src_cat, const long long* src_stats, const int* src_counts, const unsigned int* src_bits,
+                   const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts, unsigned int* dst_bits,
+                   float* dst_conf, int B, int H, int W, int cap, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
