@@ -1408,6 +1408,46 @@ __global__ __launch_bounds__(256) void instance_conf_kernel(const float* __restr
   const double mp = area > 0 ? (double)q / ((double)area * SCORE_ONE) : 0.0;
   conf[3 * b] = (float)(cp * mp); conf[3 * b + 1] = (float)cp; conf[3 * b + 2] = (float)mp;
 }
+// unwarp_bits_score_kernel's sums over the set bits of given words instead of the gathered ones (fs_unwarp_instances_component: the
+// words are the component's, qf is head_fg_q_kernel's table).  One lane a word -- most words around one component are 0 and their
+// lanes leave after one read; a lane with set bits walks them, and for each does the gather's owner / nearest_claimed look-up and
+// table read.  A lane's sum is one image's and below 2^29.  The records are that kernel's with VEC: eight consecutive words (eight
+// neighbouring lanes) make record g / 8, two ints, = the sum over those of the eight whose image is the first word's, by plain
+// stores; a lane of a further image -- a group that straddles an image's end -- adds its sum into qsum (zeroed by the launcher) by a
+// 64-bit integer atomic.  instance_conf_kernel sums the records with wpw = 8.  Integer sums: the same bits in any order.
+__global__ __launch_bounds__(256) void component_qsum_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ qf,
+                                                             const unsigned int* __restrict__ cbits, unsigned long long* __restrict__ qsum,
+                                                             int* __restrict__ rec, int Hs, int Ws, int P, int hw, long words) {
+  const int per = Hs * Ws;
+  const long g = (long)blockIdx.x * 256 + threadIdx.x;
+  const long wpi = (long)Hs * P;
+  unsigned long long s = 0ull;
+  long tb = -1;
+  if (g < words) {
+    const long row = g / P;
+    const int c = (int)(g - row * P);
+    unsigned int wd = cbits[g];
+    if (c == P - 1 && (Ws & 31)) wd &= (1u << (Ws & 31)) - 1u;
+    tb = row / Hs;
+    if (wd != 0u) {
+      const int y = (int)(row - tb * Hs);
+      const int* ob = owner + tb * per;
+      const int* rx = rowx + tb * per;
+      const int* db = qf + tb * (hw + 1);
+      while (wd != 0u) {
+        const int x = 32 * c + __ffs((int)wd) - 1;
+        wd &= wd - 1u;
+        s += (unsigned int)(unwarp_class_at(ob, rx, db, ob[y * Ws + x], y, x, Hs, Ws, hw) & SCORE_Q_MASK);
+      }
+    }
+  }
+  const long g0 = g & ~7L;                              // the group's first word; the eight lanes are neighbours in one wave
+  const long b0 = g0 < words ? g0 / wpi : -1;
+  unsigned long long first = tb == b0 ? s : 0ull;
+  first += __shfl_xor(first, 1, 64); first += __shfl_xor(first, 2, 64); first += __shfl_xor(first, 4, 64);
+  if (tb != b0 && s != 0ull) atomicAdd(qsum + tb, s);
+  if (g == g0 && g < words) { rec[2 * (g >> 3)] = (int)(unsigned int)first; rec[2 * (g >> 3) + 1] = (int)(unsigned int)(first >> 32); }
+}
 
 // ---- host: one plan, one job, one launcher -------------------------------------------------------------------------------------------
 constexpr long INT_LIMIT = 2147483647L;                // pixel / point indices are ints
@@ -1478,7 +1518,10 @@ RlePlan rle_plan(int B, int Hs, int Ws) {
 // words instead of classes, and the run-length passes follow; its regions come last of all, and it goes with no counting feature.
 // UW_SCORE (fs_unwarp_instances_scored): UW_BITS with the gather also summing the feeding points' foreground probabilities; its one
 // regions, the packed table and the gather's per-wave records, come behind UW_BITS', whose layout stays what it is without it.
-enum : unsigned { UW_LABELS = 0, UW_COUNT = 1, UW_TRIM = 2, UW_AREA = 4, UW_HD = 8, UW_BITS = 16, UW_SCORE = 32 };
+// UW_COMP (fs_unwarp_instances_component): UW_BITS with the connected component under the gaze taken from the gathered words before
+// the run-length passes; with UW_SCORE the q sum is taken over the component's bits by a pass of its own (component_qsum_kernel) and the
+// gather is the unscored one.  Its regions come behind everything else.
+enum : unsigned { UW_LABELS = 0, UW_COUNT = 1, UW_TRIM = 2, UW_AREA = 4, UW_HD = 8, UW_BITS = 16, UW_SCORE = 32, UW_COMP = 64 };
 
 struct UnwarpPlan {
   int B, K, h, w, Hs, Ws;
@@ -1492,6 +1535,8 @@ struct UnwarpPlan {
   long arec, atab;                                     // UW_AREA: [B*cpi][AREA_REC], [B][K] sums of the other predicted classes' pixels
   long fg, hds;                                        // UW_HD: n foreground bytes, SurfacePlan::total
   long bitw, rles;                                     // UW_BITS: RlePlan::words bit words (used when the caller keeps none), RlePlan::total
+  long raww, cmps, crec;                               // UW_COMP: the gathered bit words, ComponentPlan::scratch, two ints per eight words: component_qsum_kernel's records
+  ComponentPlan cmp;
   long qtab, srec;                                     // UW_SCORE: [B*(h*w+1)] head_fg_q_kernel's packed words; two ints per wave of the gather
   long total;
   TrimapPlan tri;
@@ -1527,14 +1572,19 @@ UnwarpPlan unwarp_plan(int B, int K, int h, int w, int Hs, int Ws, unsigned feat
   if (features & UW_SCORE)
     p.qtab = align4(p.total), p.srec = align4(p.qtab + (long)B * ((long)h * w + 1)),
     p.total = p.srec + (Ws % 4 == 0 ? 8 * ((p.rle.words + 31) / 32) : 4 * ((p.rle.words + 7) / 8));
+  if (features & UW_COMP) {
+    p.cmp = component_plan(B, Hs, Ws);
+    p.raww = align4(p.total), p.cmps = p.raww + align4(p.rle.words), p.crec = p.cmps + align4(p.cmp.scratch);
+    p.total = p.crec + 2 * ((p.rle.words + 7) / 8);
+  }
   // a workgroup's last trip of the count pass may start up to a chunk past the end
   const long per_max = INT_LIMIT - (features & UW_COUNT ? UACC_CHUNK : 0);
   p.ok = K >= 2 && K <= UNWARP_MAX_K && row_fits_lds(Ws) && (long)h * w < INT_LIMIT && p.per < per_max && p.n <= THREADS_MAX &&
          (long)B * Hs * 256 <= THREADS_MAX && (long)B * p.bpi * 256 <= THREADS_MAX &&
          (!(features & UW_COUNT) || (long)B * p.cpi * 256 <= THREADS_MAX) && (!(features & UW_TRIM) || p.tri.ok) &&
          (!(features & UW_HD) || ((features & UW_COUNT) && p.sp.ok)) &&
-         (!(features & UW_BITS) || ((features & ~UW_SCORE) == UW_BITS && p.rle.bits_ok && p.rle.ok)) &&
-         (!(features & UW_SCORE) || (features & UW_BITS));
+         (!(features & UW_BITS) || ((features & ~(UW_SCORE | UW_COMP)) == UW_BITS && p.rle.bits_ok && p.rle.ok)) &&
+         (!(features & UW_SCORE) || (features & UW_BITS)) && (!(features & UW_COMP) || ((features & UW_BITS) && p.cmp.ok));
   return p;
 }
 
@@ -1548,6 +1598,7 @@ struct UnwarpJob {
   struct { long long* out; } areas;                                                             // UW_AREA
   struct { long long* out; int q; } hd;                                                         // UW_HD
   struct { long long *cat, *stats; int* counts; unsigned int* bits; int cap; float* conf; long long* qsum; } inst;   // UW_BITS; bits optional; conf, qsum: UW_SCORE
+  struct { const float* focus; long long* out; int conn; long snap2; } comp;                    // UW_COMP
 };
 
 bool trimap_args_ok(int D, int frame) { return D >= 0 && D <= TRI_MAX_D && (frame == 0 || frame == 1); }
@@ -1660,10 +1711,11 @@ const CountKernel COUNT_KERNELS[8] = {
 // the foreground bytes and the surface distances.
 int unwarp_run(const UnwarpPlan& p, const UnwarpJob& j, hipStream_t stream) {
   const bool count = p.features & UW_COUNT, trim = p.features & UW_TRIM, area = p.features & UW_AREA, hdq = p.features & UW_HD;
-  const bool inst = p.features & UW_BITS, score = p.features & UW_SCORE;
+  const bool inst = p.features & UW_BITS, score = p.features & UW_SCORE, comp = p.features & UW_COMP;
   FS_REQUIRE(p.ok && j.cls && j.m && j.grid && j.scratch && (count || inst || j.labels.map));
   FS_REQUIRE(!inst || (j.inst.cat && j.inst.stats && j.inst.counts && j.inst.cap >= 1));
   FS_REQUIRE(!score || (j.inst.conf && j.inst.qsum));
+  FS_REQUIRE(!comp || (j.comp.focus && j.comp.out && (j.comp.conn == 4 || j.comp.conn == 8) && j.comp.snap2 >= 0));
   // the records are stored and read 16 bytes at a time
   FS_REQUIRE(!count || (j.count.y && j.count.cls_label && j.count.counts && j.count.acc && ((uintptr_t)j.scratch & 15) == 0));
   FS_REQUIRE((!trim || (j.trim.out && trimap_args_ok(j.trim.D, j.trim.frame))) && (!area || j.areas.out));
@@ -1677,6 +1729,33 @@ int unwarp_run(const UnwarpPlan& p, const UnwarpJob& j, hipStream_t stream) {
     // four pixels a thread need whole 16-byte rows of owner and rowx
     const bool vec4 = p.Ws % 4 == 0 && ((uintptr_t)s & 15) == 0;
     int* srec = nullptr;
+    if (comp) {
+      // the gather's words stay in scratch, the component's become the record's: bits, the run-length code and the q sum are taken from them
+      unsigned int* raw = reinterpret_cast<unsigned int*>(s + p.raww);
+      if (score) {
+        hipLaunchKernelGGL(head_fg_q_kernel, dim3((unsigned)(p.B * p.bpi)), dim3(256), 0, stream, j.cls, j.m, s + p.dec, s + p.qtab, p.K, p.h, p.w,
+                           (int)p.bpi);
+        FS_LAUNCH_CHECK();
+      }
+      hipLaunchKernelGGL(vec4 ? unwarp_bits_kernel<true> : unwarp_bits_kernel<false>, dim3(cdiv(p.rle.words, vec4 ? 32 : 8)), dim3(256), 0, stream,
+                         s + p.owner, s + p.rowx, s + p.dec, raw, p.Hs, p.Ws, (int)p.rle.P, p.h * p.w, p.K, p.rle.words);
+      FS_LAUNCH_CHECK();
+      hipLaunchKernelGGL(instance_cat_kernel, dim3(cdiv(p.B, 256)), dim3(256), 0, stream, j.cls, j.inst.cat, p.B, p.K);
+      FS_LAUNCH_CHECK();
+      FS_TRY(component_launch(p.cmp, raw, j.comp.focus, bits, j.comp.out, s + p.cmps, p.B, p.Hs, p.Ws, j.comp.conn, j.comp.snap2, stream));
+      FS_TRY(rle_launch(p.rle, bits, j.inst.stats, j.inst.counts, s + p.rles, p.B, p.Hs, p.Ws, j.inst.cap, stream));
+      if (score) {
+        const hipError_t e = hipMemsetAsync(j.inst.qsum, 0, sizeof(long long) * (size_t)p.B, stream);
+        if (e != hipSuccess) return (int)e;
+        hipLaunchKernelGGL(component_qsum_kernel, dim3(cdiv(p.rle.words, 256)), dim3(256), 0, stream, s + p.owner, s + p.rowx, s + p.qtab, bits,
+                           reinterpret_cast<unsigned long long*>(j.inst.qsum), s + p.crec, p.Hs, p.Ws, (int)p.rle.P, p.h * p.w, p.rle.words);
+        FS_LAUNCH_CHECK();
+        hipLaunchKernelGGL(instance_conf_kernel, dim3((unsigned)p.B), dim3(256), 0, stream, j.cls, j.inst.cat, j.inst.stats, s + p.crec, j.inst.qsum,
+                           j.inst.conf, p.K, (long)p.Hs * p.rle.P, 8, (long)cdiv(p.rle.words, 8));
+        FS_LAUNCH_CHECK();
+      }
+      return FS_OK;
+    }
     if (score) {
       unsigned long long* qsum = reinterpret_cast<unsigned long long*>(j.inst.qsum);
       srec = (p.Ws % 4 == 0) == vec4 ? s + p.srec : nullptr;     // the records were sized for the gather the width allows
@@ -1863,6 +1942,18 @@ int fs_unwarp_instances_scored(const float* cls, const float* m, const float* gr
                                int cap, hipStream_t stream) {
   return unwarp_run(unwarp_plan(B, K, h, w, Hs, Ws, UW_BITS | UW_SCORE),
                     {cls, m, grid, scratch, {}, {}, {}, {}, {}, {cat, stats, counts, bits, cap, conf, qsum}}, stream);
+}
+
+// the scratch of the scored call, which holds the unscored one's; conf == nullptr (with qsum): no score
+long fs_unwarp_instances_component_scratch_ints(int B, int h, int w, int Hs, int Ws) {
+  return unwarp_plan(B, 2, h, w, Hs, Ws, UW_BITS | UW_SCORE | UW_COMP).total;
+}
+int fs_unwarp_instances_component(const float* cls, const float* m, const float* grid, const float* focus, long long* cat, long long* stats,
+                                  int* counts, unsigned int* bits, long long* comp, float* conf, long long* qsum, int* scratch, int B, int K,
+                                  int h, int w, int Hs, int Ws, int cap, int conn, long snap2, hipStream_t stream) {
+  FS_REQUIRE((conf == nullptr) == (qsum == nullptr));
+  return unwarp_run(unwarp_plan(B, K, h, w, Hs, Ws, UW_BITS | UW_COMP | (conf ? UW_SCORE : 0u)),
+                    {cls, m, grid, scratch, {}, {}, {}, {}, {}, {cat, stats, counts, bits, cap, conf, qsum}, {focus, comp, conn, snap2}}, stream);
 }
 
 int fs_surface_hd(const unsigned char* fg, long long* hd, int* scratch, int B, int Hs, int Ws, int q, hipStream_t stream) {

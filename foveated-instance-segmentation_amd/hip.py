@@ -51,6 +51,8 @@ SIGNATURES = {
     "fs_unwarp_instances": "pppppppp" + "iiiiiii",
     "fs_head_fg_q": "ppp" + "iiii",
     "fs_unwarp_instances_scored": "pppppppppp" + "iiiiiii",
+    "fs_mask_component": "ppppp" + "iiii" + "l",
+    "fs_unwarp_instances_component": "p" * 12 + "iiiiiiii" + "l",
     "fs_gate_tiles": "ppp" + "iiii",
     "fs_gate_decide": "ppppppp" + "iiiiiiii" + "ll" + "ii",
     "fs_gate_commit": "pp" + "i" + "p" * 13 + "iiii",
@@ -129,7 +131,8 @@ HOST_ONLY = ("fs_set_conv_precision", "fs_get_conv_precision", "fs_conv2d_worksp
              "fs_unwarp_labels_scratch_ints", "fs_unwarp_accuracy_scratch_ints",
              "fs_trimap_bands_scratch_ints", "fs_unwarp_trimap_scratch_ints", "fs_unwarp_class_areas_scratch_ints",
              "fs_unwarp_hd_scratch_ints", "fs_surface_hd_scratch_ints", "fs_mask_rle_scratch_ints", "fs_unwarp_instances_scratch_ints",
-             "fs_unwarp_instances_scored_scratch_ints")
+             "fs_unwarp_instances_scored_scratch_ints", "fs_mask_component_scratch_ints", "fs_mask_component_route",
+             "fs_unwarp_instances_component_scratch_ints")
 
 
 class HipLibraryError(RuntimeError):
@@ -196,6 +199,12 @@ def load():
     lib.fs_unwarp_instances_scratch_ints.argtypes = [_I] * 5
     lib.fs_unwarp_instances_scored_scratch_ints.restype = _L
     lib.fs_unwarp_instances_scored_scratch_ints.argtypes = [_I] * 5
+    lib.fs_mask_component_scratch_ints.restype = _L
+    lib.fs_mask_component_scratch_ints.argtypes = [_I] * 3
+    lib.fs_mask_component_route.restype = _I
+    lib.fs_mask_component_route.argtypes = [_I] * 3
+    lib.fs_unwarp_instances_component_scratch_ints.restype = _L
+    lib.fs_unwarp_instances_component_scratch_ints.argtypes = [_I] * 5
     lib.fs_stream_wait.restype = _I
     lib.fs_stream_wait.argtypes = [_P, _P]
     lib.fs_set_deterministic.restype = _I

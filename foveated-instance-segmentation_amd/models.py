@@ -240,7 +240,7 @@ class DeformSegmentationModule(nn.Module):
         return labels
 
     @torch.no_grad()
-    def predict_instances(self, img, focus, seg_size=None, max_runs=None, return_bits=False, return_score=False):
+    def predict_instances(self, img, focus, seg_size=None, max_runs=None, return_bits=False, return_score=False, component=None, snap_px=None):
         """Label-free inference as an instance record: the gazed instance's class, area, box and mask, without the class map.
 
         img, focus and seg_size as predict's; the stages are predict's up to the gather, which stores the mask `predict(...) !=
@@ -261,8 +261,24 @@ class DeformSegmentationModule(nn.Module):
         mask_prob and score are 0 for an empty mask, cls_prob and score NaN where the class logits hold a NaN.  The other results are
         the unscored call's bit for bit; the call allocates a few bytes per grid point more and no full-resolution tensor.
 
+        component = 4 or 8 (ops.unwarp_instances(component=...); unpinned) keeps only the connected component of the mask under the
+        gaze -- the set pixel at the gaze point `focus`, or the nearest one within snap_px pixels (None: any distance) -- with 4- or
+        8-connectivity, taken on the device from the bit words: stats, counts, bits, mask_prob and score then describe that one blob,
+        not a second object or specks the head also marked, and are the empty mask's where there is none; cat and cls_prob are
+        unchanged.  comp (B,4) int64 = (seed_y, seed_x, d2, area_all) is appended as the last element, behind conf.  ValueError for
+        any other component, or for snap_px without component.  With component=None the call is what it was.
+
         Eval mode only, no label read, no argument written to, and a NaN saliency map is reported as in predict."""
+        if component is None:
+            if snap_px is not None:
+                raise ValueError("snap_px goes with component = 4 or 8")
+        else:
+            ops._component_args(component, snap_px)
         cls, m, grid, seg_size = self._head_parts(img, focus, seg_size, "predict_instances")
+        if component is not None:
+            out = ops.unwarp_instances(cls, m, grid, *seg_size, max_runs=max_runs, return_bits=return_bits, score=return_score,
+                                       component=component, focus=focus, snap_px=snap_px)
+            return out[:-2] + out[-1:] if return_score else out              # qsum stays inside
         if return_score:
             return ops.unwarp_instances(cls, m, grid, *seg_size, max_runs=max_runs, return_bits=return_bits, score=True)[:-1]
         return ops.unwarp_instances(cls, m, grid, *seg_size, max_runs=max_runs, return_bits=return_bits)

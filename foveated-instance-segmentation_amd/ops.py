@@ -5,6 +5,7 @@ reference's logical (Cout,Cin,R,S) shape with RSCK strides, so `w.permute(2,3,1,
 [R][S][Cin][Cout] array the kernels read (DESIGN.md "Data layout").
 """
 import ctypes
+import math
 import os
 import weakref
 import zlib
@@ -1551,6 +1552,56 @@ def mask_rle(mask_or_bits, Ws=None, max_runs=None):
     return stats, counts
 
 
+COMPONENT_OFF2 = 2 ** 62                            # a squared distance no pixel reaches: snap_px = None
+
+
+def _component_args(component, snap_px):
+    """(conn, snap2) of mask_component / unwarp_instances(component=...): connectivity 4 or 8; snap_px None (no limit) or a finite number
+    of pixels >= 0, snap2 = floor(snap_px ** 2)."""
+    if isinstance(component, bool) or component not in (4, 8):
+        raise ValueError(f"the connectivity must be 4 or 8, got {component!r}")
+    if snap_px is None:
+        return int(component), COMPONENT_OFF2
+    px = float(snap_px)
+    if not (px >= 0.0) or math.isinf(px):
+        raise ValueError(f"snap_px must be a finite number of pixels >= 0, got {snap_px!r}")
+    return int(component), COMPONENT_OFF2 if px >= 2.0 ** 31 else int(math.floor(px * px))     # 2^31 squared is 2^62: no overflow in px * px
+
+
+def _focus_arg(focus, B, dev):
+    if not isinstance(focus, torch.Tensor) or tuple(focus.shape) != (B, 2):
+        raise ValueError(f"focus must be (B, 2) = ({B}, 2), got {tuple(getattr(focus, 'shape', ()))}")
+    return focus.to(device=dev, dtype=torch.float32).contiguous()
+
+
+def mask_component(mask_or_bits, focus, Ws=None, connectivity=8, snap_px=None):
+    """The connected component of a mask under the gaze, on the device and on bit words (fs_mask_component; no autograd; unpinned:
+    the reference has no counterpart).  The mask as mask_rle takes it: bool / uint8 (B,Hs,Ws) or (Hs,Ws), or int32 bit words
+    (B,Hs,ceil(Ws/32)) together with Ws.  focus (B,2) normalised (row, col), turned into a gaze pixel as gate_decide does.  The seed is
+    the gaze pixel where it is set, else the nearest set pixel (ties: the smaller row-major index), unless it lies more than snap_px
+    pixels away (None: any distance; snap2 = floor(snap_px ** 2) against the squared distance).  connectivity 4 or 8.  Returns
+    (bits_c (B,Hs,ceil(Ws/32)) int32, the component's words, all 0 where there is none; comp (B,4) int64 = (seed_y, seed_x, d2, area_all),
+    (-1, -1, -1, area_all) where there is none; area_all counts the input's set pixels).  mask_rle(bits_c, Ws) gives its record."""
+    conn, snap2 = _component_args(connectivity, snap_px)
+    if mask_or_bits.dtype == torch.int32:
+        bits = mask_or_bits
+        if bits.dim() != 3 or bits.numel() == 0 or Ws is None or int(Ws) < 1 or bits.shape[2] != (int(Ws) + 31) // 32:
+            raise ValueError(f"bit words {tuple(bits.shape)} must be a non-empty (B, Hs, ceil(Ws / 32)) with Ws given, got Ws = {Ws!r}")
+        Ws = int(Ws)
+    else:
+        if Ws is not None and int(Ws) != mask_or_bits.shape[-1]:
+            raise ValueError(f"Ws = {Ws!r} differs from the mask's width {mask_or_bits.shape[-1]}")
+        bits = mask_bits(mask_or_bits)
+        Ws = int(mask_or_bits.shape[-1])
+    B, Hs = int(bits.shape[0]), int(bits.shape[1])
+    f = _focus_arg(focus, B, bits.device)
+    out = torch.empty_like(bits, memory_format=torch.contiguous_format)
+    comp = torch.empty(B, 4, device=bits.device, dtype=torch.int64)
+    scratch = torch.empty(hip.query("fs_mask_component_scratch_ints", B, Hs, Ws), device=bits.device, dtype=torch.int32)
+    hip.call("fs_mask_component", hip.ptr(bits.contiguous()), hip.ptr(f), hip.ptr(out), hip.ptr(comp), hip.ptr(scratch), B, Hs, Ws, conn, snap2)
+    return out, comp
+
+
 def head_fg_q(cls, m):
     """The C1 head's foreground probability per grid point as an integer table (fs_head_fg_q; no autograd; unpinned: the reference
     has no counterpart).  cls (B,K), m (B,h,w).  Returns q (B, h*w+1) int32 = rint(P * 2^24): P is the softmax mass of the classes
@@ -1565,7 +1616,7 @@ def head_fg_q(cls, m):
     return q
 
 
-def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False, score=False):
+def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False, score=False, component=None, focus=None, snap_px=None):
     """The gazed instance of the C1 head as a record instead of a class map (fs_unwarp_instances; no autograd).  Arguments and checks
     are unwarp_labels'.  The mask is `unwarp_labels(cls, m, grid, Hs, Ws)[0] != K - 1` bit for bit; no (B,Hs,Ws) tensor wider than its
     bit words is allocated.  Returns (cat, stats, counts[, bits]): cat (B,) int64 = torch.argmax(cls[:, :K-1], 1), the head's
@@ -1578,18 +1629,40 @@ def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False, sco
     score=True (fs_unwarp_instances_scored; unpinned) appends conf (B,3) fp32 = (score, cls_prob, mask_prob) and qsum (B,) int64 behind
     everything else: qsum is the sum of head_fg_q(cls, m)[b, feeding point] over the set pixels, added in the same gather; mask_prob =
     qsum / (area * 2^24), 0 for an empty mask; cls_prob = softmax(cls[b, :K-1])[cat[b]] in fp64, NaN where that row holds a NaN; score
-    = their product, the mean probability of class cat over the mask.  The other results are the unscored call's bit for bit."""
+    = their product, the mean probability of class cat over the mask.  The other results are the unscored call's bit for bit.
+
+    component = 4 or 8 (fs_unwarp_instances_component; unpinned) keeps only the connected component of that mask under the gaze: focus
+    (B,2) normalised (row, col) and snap_px as mask_component's.  stats, counts, bits, qsum, mask_prob and score then describe the
+    component (the empty mask's record where there is none); cat and cls_prob are unchanged.  comp (B,4) int64 = (seed_y, seed_x, d2,
+    area_all) is appended as the last element, behind conf / qsum where present.  Nothing is read on the host in between."""
     B, K = cls.shape
     _, h, w, _ = grid.shape
     if tuple(m.shape) != (B, h, w):
         raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
+    if component is None and (focus is not None or snap_px is not None):
+        raise ValueError("focus and snap_px go with component = 4 or 8")
     Hs, Ws = int(Hs), int(Ws)
     cap = _max_runs(max_runs, Ws)
     dev = cls.device
+    if component is not None:
+        conn, snap2 = _component_args(component, snap_px)
+        if focus is None:
+            raise ValueError("component needs focus (B, 2): the gaze that picks it")
+        f = _focus_arg(focus, B, dev)
     cat = torch.empty(B, device=dev, dtype=torch.int64)
     stats = torch.empty(B, 6, device=dev, dtype=torch.int64)
     counts = torch.empty(B, cap, device=dev, dtype=torch.int32)
     bits = torch.empty(B, Hs, (Ws + 31) // 32, device=dev, dtype=torch.int32) if return_bits else None
+    if component is not None:
+        comp = torch.empty(B, 4, device=dev, dtype=torch.int64)
+        conf = torch.empty(B, 3, device=dev, dtype=torch.float32) if score else None
+        qsum = torch.empty(B, device=dev, dtype=torch.int64) if score else None
+        scratch = torch.empty(hip.query("fs_unwarp_instances_component_scratch_ints", B, h, w, Hs, Ws), device=dev, dtype=torch.int32)
+        hip.call("fs_unwarp_instances_component", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(f),
+                 hip.ptr(cat), hip.ptr(stats), hip.ptr(counts), hip.ptr(bits), hip.ptr(comp), hip.ptr(conf), hip.ptr(qsum), hip.ptr(scratch),
+                 B, K, h, w, Hs, Ws, cap, conn, snap2)
+        out = (cat, stats, counts) + ((bits,) if return_bits else ()) + ((conf, qsum) if score else ())
+        return out + (comp,)
     if score:
         conf = torch.empty(B, 3, device=dev, dtype=torch.float32)
         qsum = torch.empty(B, device=dev, dtype=torch.int64)

@@ -44,7 +44,10 @@ class GazeSession:
     around the gaze the record was made for.  saccade_px (0.10 * min(H, W)): a jump this long since the last step counts as a saccade
     in flight: the old record is kept and nothing runs; None switches the rule off.  max_age (0): steps after which a record is
     re-made whatever else holds; 0 = never.  reuse_inside_mask (True): a gaze that still lies on the record's mask keeps the record
-    however far it has drifted.  max_runs (None): as predict_instances.  score (False): also keep conf.
+    however far it has drifted.  max_runs (None): as predict_instances.  score (False): also keep conf.  component (None, 4 or 8)
+    and snap_px (None): as predict_instances -- the record is the connected component under the gaze.  The gate needs no change for
+    it: its box, the region of interest grown from it and the inside bit are read from the record's stats and bits, so they follow the
+    component; a gaze that lands on another blob the head also marked is then outside the record's mask and re-makes it (RUN_GAZE).
 
     These defaults are this library's choices.  They have not been validated on real gaze data: tune them on recordings of the
     headset and scenes you serve.
@@ -53,7 +56,7 @@ class GazeSession:
     code -> number of viewer-steps so far (ops.GATE_CODES names the codes)."""
 
     def __init__(self, module, batch, frame_size, *, tile=32, level=8, scene_frac=0.25, roi_tiles=0, roi_margin=16, fixation_px=None,
-                 saccade_px=_DEFAULT, max_age=0, reuse_inside_mask=True, max_runs=None, score=False):
+                 saccade_px=_DEFAULT, max_age=0, reuse_inside_mask=True, max_runs=None, score=False, component=None, snap_px=None):
         self.module = module
         self.batch = _int_ge("batch", batch, 1)
         if len(frame_size) != 2:
@@ -83,6 +86,12 @@ class GazeSession:
         self.cap = ops._max_runs(max_runs, self.W)
         self.max_runs = max_runs
         self.score = bool(score)
+        if component is None:
+            if snap_px is not None:
+                raise ValueError("snap_px goes with component = 4 or 8")
+        else:
+            ops._component_args(component, snap_px)
+        self.component, self.snap_px = component, snap_px
         self.counts = {code: 0 for code in sorted(ops.GATE_CODES)}
         self._dev = None
 
@@ -169,7 +178,11 @@ class GazeSession:
             else:
                 sel = idx.long()
                 xi, fi = x.index_select(0, sel), focus.index_select(0, sel)
-            new = list(self.module.predict_instances(xi, fi, max_runs=self.max_runs, return_bits=True, return_score=self.score))
+            if self.component is None:
+                new = list(self.module.predict_instances(xi, fi, max_runs=self.max_runs, return_bits=True, return_score=self.score))
+            else:                                                          # comp, the last element, is not part of the record
+                new = list(self.module.predict_instances(xi, fi, max_runs=self.max_runs, return_bits=True, return_score=self.score,
+                                                         component=self.component, snap_px=self.snap_px))[:-1]
             if len(run) == B:
                 # every record is new: the tensors predict_instances made become the session's, nothing is copied
                 self._rec = new

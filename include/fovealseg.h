@@ -236,6 +236,44 @@ long fs_unwarp_instances_scored_scratch_ints(int B, int h, int w, int Hs, int Ws
 int fs_unwarp_instances_scored(const float* cls, const float* m, const float* grid, long long* cat, long long* stats, int* counts,
                                unsigned int* bits, float* conf, long long* qsum, int* scratch, int B, int K, int h, int w, int Hs,
                                int Ws, int cap, fs_stream_t stream);
+/* The connected component of a mask under the gaze (no counterpart in the reference: UNPINNED, a definition of this library's;
+ * DESIGN.md §1 f-3).  All integers, on bit words.  bits (B,Hs,P), P = ceil(Ws/32), as fs_mask_bits lays them out (the bits at x >= Ws
+ * are not read as pixels); focus (B,2) fp32 = normalised (row, col); conn = 4 (edge neighbours) or 8 (edge and corner neighbours);
+ * snap2 = a squared distance in whole pixels.  The gaze pixel is fs_gate_decide's: gy = clamp(rint((double)f_row * ((Hs-1) * 16)), 0,
+ * (Hs-1) * 16), NaN -> 0, py = (gy + 8) >> 4, px likewise with Ws.  The seed is (py, px) where that bit is set (d2 = 0), else the set
+ * pixel (y, x) that minimises key = d2 * 2^31 + (y * Ws + x), d2 = (y-py)^2 + (x-px)^2: the nearest set pixel, ties to the smaller
+ * row-major index.  There is no component for an empty mask or where d2 > snap2.  The component is every set pixel joined to the seed
+ * by a path of set pixels with steps of the chosen neighbourhood; outside the image is background.  out (B,Hs,P) = its bit words, all 0
+ * where there is none, the bits at x >= Ws always 0; out may not be bits.  comp (B,4) int64 = (seed_y, seed_x, d2, area_all), area_all
+ * the popcount of the input within x < Ws; (-1, -1, -1, area_all) where there is no component.  A set function of the input: the same
+ * bits in every order of execution.  One workgroup per image grows the reached set until a sweep adds nothing; the set lives in LDS
+ * where Hs * (P | 1) words fit 156 KiB (fs_mask_component_route = 1), in out itself otherwise (= 2; 0 for sizes that are refused).
+ * scratch = fs_mask_component_scratch_ints(B, Hs, Ws) ints, any 4-byte alignment; its contents after the call are unspecified.  FS_ERR_ARG, with nothing launched, for a null
+ * pointer, out == bits, conn outside {4, 8}, snap2 < 0, non-positive sizes, a side above 16384 or Hs * Ws >= 2^31. */
+long fs_mask_component_scratch_ints(int B, int Hs, int Ws);
+int fs_mask_component_route(int B, int Hs, int Ws);
+int fs_mask_component(const unsigned int* bits, const float* focus, unsigned int* out, long long* comp, int* scratch, int B, int Hs,
+                      int Ws, int conn, long snap2, fs_stream_t stream);
+/* fs_unwarp_instances / fs_unwarp_instances_scored with the record describing the component under the gaze instead of every foreground
+ * pixel (no counterpart in the reference: UNPINNED).  The decide / owner / fill passes and the bit gather are fs_unwarp_instances';
+ * with conf the gather is still the unscored one -- the words are the same, and the scored gather's sums over the whole mask would be
+ * discarded -- and fs_head_fg_q's table is made beside it.  fs_mask_component's passes take the component of the gathered words
+ * (focus, conn, snap2 and comp as there); fs_mask_rle's passes
+ * run once, on the component's words.  stats, counts and bits (nullable) are the component's; cat is unchanged.  conf and qsum are
+ * given or null together: qsum (B) = the sum of fs_head_fg_q's q over the set bits of the component only (the same owner / nearest
+ * look-up and table read per bit as the scored gather; integer sums: one record per eight consecutive bit words by plain stores,
+ * summed per image in a fixed pass, and only a group of eight that straddles an image's end adds the further image's part into qsum
+ * with a 64-bit integer atomic, as the scored gather's straddling waves do), conf (B,3) as
+ * fs_unwarp_instances_scored's with that qsum and the component's area: cls_prob is unchanged, mask_prob and score describe the
+ * component.  With no component the record is the empty mask's: stats all 0 but n_runs = 1, the code [Hs * Ws], mask_prob = score =
+ * 0.  No host read between the steps.  scratch = fs_unwarp_instances_component_scratch_ints(B, h, w, Hs, Ws) ints (the scored call's,
+ * two bit planes' worth less one where bits is kept, and the component's).  FS_ERR_ARG, with nothing launched, as
+ * fs_unwarp_instances_scored and fs_mask_component, and for conf and qsum not both given or both null. */
+long fs_unwarp_instances_component_scratch_ints(int B, int h, int w, int Hs, int Ws);
+int fs_unwarp_instances_component(const float* cls, const float* m, const float* grid, const float* focus, long long* cat,
+                                  long long* stats, int* counts, unsigned int* bits, long long* comp, float* conf, long long* qsum,
+                                  int* scratch, int B, int K, int h, int w, int Hs, int Ws, int cap, int conn, long snap2,
+                                  fs_stream_t stream);
 /* The gaze gate (no counterpart in the reference: UNPINNED, a definition of this library's): does the record a viewer
  * holds still answer for a new frame and gaze?  All integers.  Pixel code q(v) = (int) rintf(fminf(fmaxf(v, 0), 1) * 255.0f): one fp32
  * multiply, round to nearest even, NaN -> 0, k/255 -> k.  fs_gate_tiles, the hot pass: img (B,3,H,W) fp32 NCHW, the new frames; key
