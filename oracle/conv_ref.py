@@ -99,6 +99,16 @@ def conv2d_bwd_weight(x, dy, R_, S_, stride=1, pad=0, dil=1, dw0=None):
     return dw if dw0 is None else dw0 + dw
 
 
+def linear_wgrad_ref(x, dy):
+    """fs_linear_bwd_weight_bias: x (rows, Cin), dy (rows, Cout) -> dw (Cin, Cout) = x^T dy, dbias (Cout) = column sums of dy"""
+    return torch.einsum("rc,rk->ck", x, dy), dy.sum(0)
+
+
+def linear_wgrad_terms(x, dy):
+    """sum|terms| of every element of the pair above: |x|^T |dy| and the column sums of |dy|"""
+    return linear_wgrad_ref(x.abs(), dy.abs())
+
+
 # ------------------------------------------------------------------------------------------------
 # the fused entry points
 # ------------------------------------------------------------------------------------------------

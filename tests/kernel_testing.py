@@ -1,5 +1,5 @@
-"""Helpers shared by the C-ABI kernel tests (tests/test_elementwise_kernels.py, tests/test_transformer_kernels.py): guarded,
-pre-filled output buffers and the bound / bit-equality checks.  Not a test module and not a conftest."""
+"""Helpers shared by the C-ABI kernel tests (tests/test_*_kernels.py): guarded, pre-filled output buffers, the bound /
+bit-equality checks, the precision-mode switch and the bound of an MFMA contraction.  Not a test module and not a conftest."""
 import math
 
 import torch
@@ -100,6 +100,45 @@ def exact(family, what, got, ref):
     got, ref = got.reshape(ref.shape), ref.to(got.dtype)
     bad = got != ref
     assert not bool(bad.any()), f"{family} {what}: {int(bad.sum())} of {ref.numel()} elements differ (bit-equal required)"
+
+
+# ---- the MFMA GEMM kernels: chain constants and the bound of one contraction (derived in the header of tests/test_conv_kernels.py) ----
+MODES = ["f32", "bf16x3", "f16x2"]
+P_STEPS = {0: 1, 1: 6, 2: 3}              # accumulator additions per product
+S_SPLIT = {0: 0, 1: 3, 2: 12}             # the split's own error, in u |x y| per product
+F16_FLOOR = 2.0 ** -37                    # the floor of a two-plane fp16 operand per product, times max|x| max|w|
+
+
+def direct_bound(a, count, terms, amax, bmax, extra):
+    """(P n + S + extra) u sum|terms| [+ n * F16_FLOOR max|x| max|w| in f16x2] per element; a = 0 fp32, 1 bf16x3, 2 f16x2"""
+    b = (P_STEPS[a] * count + S_SPLIT[a] + extra) * U * terms
+    return b + (count * F16_FLOOR * amax * bmax if a == 2 else 0.0)
+
+
+class precision:
+    """the library's precision (and deterministic) mode for the duration of a with-block"""
+
+    def __init__(self, mode, det=False):
+        self.mode, self.det = mode, det
+
+    def __enter__(self):
+        hip.set_conv_precision(self.mode)
+        hip.set_deterministic(self.det)
+
+    def __exit__(self, *exc):
+        hip.set_deterministic(False)
+        hip.set_conv_precision(hip.default_conv_precision())
+
+
+def wide(t):
+    """fp32 values with the last mantissa bit set: full 24-bit significands"""
+    b = t.float().contiguous().view(torch.int32) | 1
+    return b.view(torch.float32).double()
+
+
+def pow2(gen, *shape):
+    """+- 2^j, j in -2 .. 2"""
+    return (2.0 ** torch.randint(-2, 3, shape, generator=gen).double()) * (torch.randint(0, 2, shape, generator=gen).double() * 2 - 1)
 
 
 def randint(gen, lo, hi, *shape):

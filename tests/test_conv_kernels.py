@@ -65,16 +65,15 @@ import conv_ref as C  # noqa: E402
 import elementwise_ref as E  # noqa: E402
 import fovealseg_oracle as O  # noqa: E402
 import transformer_ref as R  # noqa: E402
-from kernel_testing import U, Out, check, dev, exact, f32, report  # noqa: E402
+from kernel_testing import (F16_FLOOR, MODES, P_STEPS, S_SPLIT, U, Out, check, dev, direct_bound, exact, f32, pow2, precision,  # noqa: E402,F401
+                            report, wide)
 
 hip = fovealseg.hip
 HipError = fovealseg.hip.HipLibraryError
 gpu = pytest.mark.gpu
-MODES = ["f32", "bf16x3", "f16x2"]
-P_STEPS = {0: 1, 1: 6, 2: 3}              # accumulator additions per product
-S_SPLIT = {0: 0, 1: 3, 2: 12}             # the split's own error, in u |x y| per product
+# MODES, P_STEPS, S_SPLIT, F16_FLOOR, direct_bound, precision, wide and pow2 live in tests/kernel_testing.py (shared with
+# tests/test_linear_wgrad_kernels.py)
 F16_WIDTH = 2.0 ** -22                    # relative error of a two-plane fp16 operand
-F16_FLOOR = 2.0 ** -37                    # ... and its floor per product, times max|x| max|w|
 WINO_ROUND = 14                           # roundings of the row transforms (T, U, output), see the header
 
 ROUTES = ["GENERIC", "PLAIN", "HALO", "WINO_F23", "WINO_F43", "TAPSET_FWD", "TAPSET_BWD1", "POINTWISE", "GATHER", "SCATTER", "S2FWD",
@@ -146,21 +145,6 @@ case_id = lambda c: c.id
 # ================================================================================================
 def lib():
     return hip.load()
-
-
-class precision:
-    """the library's precision (and deterministic) mode for the duration of a with-block"""
-
-    def __init__(self, mode, det=False):
-        self.mode, self.det = mode, det
-
-    def __enter__(self):
-        hip.set_conv_precision(self.mode)
-        hip.set_deterministic(self.det)
-
-    def __exit__(self, *exc):
-        hip.set_deterministic(False)
-        hip.set_conv_precision(hip.default_conv_precision())
 
 
 def ws_bytes(c, transposed):
@@ -292,17 +276,6 @@ def gen_for(c, salt):
     return torch.Generator().manual_seed(sum(c.args) * 131 + salt)
 
 
-def wide(t):
-    """fp32 values with the last mantissa bit set: full 24-bit significands"""
-    b = t.float().contiguous().view(torch.int32) | 1
-    return b.view(torch.float32).double()
-
-
-def pow2(gen, *shape):
-    """+- 2^j, j in -2 .. 2"""
-    return (2.0 ** torch.randint(-2, 3, shape, generator=gen).double()) * (torch.randint(0, 2, shape, generator=gen).double() * 2 - 1)
-
-
 def lattice(gen, B, H, W, Ch, step):
     """one non-zero (a power of two, in one channel) per step x step block of pixels: any window of `step` pixels a side
     holds at most one"""
@@ -416,12 +389,6 @@ def wgrad_data(ci, kind):
 def arith(mode, fam):
     """the arithmetic a path runs in: the generic kernel is fp32 in every mode"""
     return 0 if (mode == "f32" or fam == 0) else MODES.index(mode)
-
-
-def direct_bound(a, count, terms, amax, bmax, extra):
-    """(P n + S + extra) u sum|terms| [+ n * F16_FLOOR max|x| max|w| in f16x2] per element (header)"""
-    b = (P_STEPS[a] * count + S_SPLIT[a] + extra) * U * terms
-    return b + (count * F16_FLOOR * amax * bmax if a == 2 else 0.0)
 
 
 def wino_bound(a, m, Cs, wterms, amax, bmax, extra, kind="float"):

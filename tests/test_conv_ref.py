@@ -106,6 +106,34 @@ def test_bound_helpers(case):
     assert torch.equal(C.bwd_weight_count(x, dy, k, k, st, pad, dil), dw_1)
 
 
+@pytest.mark.parametrize("kind", ["int", "float"])
+@pytest.mark.parametrize("rows,Ci,Co", [(1, 3, 2), (17, 16, 16), (75, 20, 37), (300, 5, 132)])
+def test_linear_wgrad_matches_torch_autograd(rows, Ci, Co, kind):
+    """linear_wgrad_ref / linear_wgrad_terms against the fp64 autograd of F.linear: dW = (w.grad)^T in the [Cin][Cout] layout
+    of the C ABI, dbias = bias.grad; the terms are the same pair on absolute values"""
+    gen = torch.Generator().manual_seed(rows * 31 + Ci + Co)
+    if kind == "int":
+        mk = lambda *s: torch.randint(-3, 4, s, generator=gen).double()      # noqa: E731
+    else:
+        mk = lambda *s: torch.randn(*s, generator=gen, dtype=torch.float64)      # noqa: E731
+    x, dy = mk(rows, Ci), mk(rows, Co)
+
+    def torch_pair(a, g):
+        w, b = torch.zeros(Co, Ci, dtype=torch.float64, requires_grad=True), torch.zeros(Co, dtype=torch.float64, requires_grad=True)
+        F.linear(a, w, b).backward(g)
+        return w.grad.t().contiguous(), b.grad
+
+    for (dw, db), (dw_t, db_t) in ((C.linear_wgrad_ref(x, dy), torch_pair(x, dy)), (C.linear_wgrad_terms(x, dy), torch_pair(x.abs(), dy.abs()))):
+        assert dw.shape == (Ci, Co) and db.shape == (Co,) and dw.dtype == torch.float64
+        if kind == "int":
+            assert torch.equal(dw, dw_t) and torch.equal(db, db_t)
+        else:
+            close(dw, dw_t), close(db, db_t)
+    tw, tb = C.linear_wgrad_terms(x, dy)
+    dw, db = C.linear_wgrad_ref(x, dy)
+    assert bool((tw >= dw.abs() - 1e-12 * tw).all()) and bool((tb >= db.abs() - 1e-12 * tb).all())
+
+
 def test_flip_transpose_is_the_stride_1_bwd_data():
     for case in [c for c in CASES if c[6] == 1]:
         B, H, W, Ci, Co, k, st, pad, dil = case
