@@ -119,20 +119,53 @@ SIGNATURES = {
 _CT = {"p": _P, "i": _I, "l": _L, "f": _F, "u": _U}
 
 _lib = None
-# declared in the header, host-side only (no stream argument)
-HOST_ONLY = ("fs_set_conv_precision", "fs_get_conv_precision", "fs_conv2d_workspace_bytes", "fs_conv2d_stats_slabs", "fs_conv2d_kernel_choice",
-             "fs_bn_bwd_slabs", "fs_dwconv3_wgrad_lanes", "fs_conv2d_bwd_data_bnsum_slabs",
-             "fs_conv2d_fwd_affine_act_ok", "fs_conv2d_fwd_residual_ok", "fs_linear_bwd_weight_bias_ok", "fs_attention_split_ws_bytes", "fs_attention_bwd_split_ws_bytes", "fs_attention_mask_words", "fs_attention_bwd_split_parts_offset",
-             "fs_stream_wait", "fs_set_deterministic", "fs_get_deterministic", "fs_conv2d_bwd_weight_ws_bytes", "fs_linear_bwd_weight_bias_ws_bytes",
-             "fs_conv2d_bwd_weight_plan",
-             "fs_colsum_scratch_floats", "fs_bn_stats_scratch_doubles", "fs_mask_head_bwd_scratch_floats", "fs_layernorm_bwd_scratch_floats",
-             "fs_conv2d_pack_persistent", "fs_conv2d_ws_mode",
-             "fs_edge_loss_stats_floats", "fs_compress_softmax_bwd_scratch_floats", "fs_gauss_grid_bwd_scratch_floats",
-             "fs_unwarp_labels_scratch_ints", "fs_unwarp_accuracy_scratch_ints",
-             "fs_trimap_bands_scratch_ints", "fs_unwarp_trimap_scratch_ints", "fs_unwarp_class_areas_scratch_ints",
-             "fs_unwarp_hd_scratch_ints", "fs_surface_hd_scratch_ints", "fs_mask_rle_scratch_ints", "fs_unwarp_instances_scratch_ints",
-             "fs_unwarp_instances_scored_scratch_ints", "fs_mask_component_scratch_ints", "fs_mask_component_route",
-             "fs_unwarp_instances_component_scratch_ints")
+# declared in the header, host-side only (no stream argument): name -> (result type, argument type string), in the letters of
+# SIGNATURES.  fs_conv2d_bwd_weight_plan's `int* out` is a plain p: a c_void_p parameter takes the ctypes int arrays its callers pass.
+HOST_ONLY = {
+    "fs_set_conv_precision": ("i", "i"),
+    "fs_get_conv_precision": ("i", ""),
+    "fs_conv2d_workspace_bytes": ("l", "iiiiiiiiiiii"),
+    "fs_conv2d_stats_slabs": ("i", "iiiiiiiiiiii" + "l"),
+    "fs_conv2d_kernel_choice": ("i", "iiiiiiiiiiii" + "il"),
+    "fs_bn_bwd_slabs": ("i", "li"),
+    "fs_dwconv3_wgrad_lanes": ("i", "iiii"),
+    "fs_conv2d_bwd_data_bnsum_slabs": ("i", "iiiiiiiiiiii" + "l"),
+    "fs_conv2d_fwd_affine_act_ok": ("i", "iiiiiiiiiiii" + "l"),
+    "fs_conv2d_fwd_residual_ok": ("i", "iiiiiiiiiiii" + "ll"),
+    "fs_linear_bwd_weight_bias_ok": ("i", "lii"),
+    "fs_attention_split_ws_bytes": ("l", "iii"),
+    "fs_attention_bwd_split_ws_bytes": ("l", "iii"),
+    "fs_attention_mask_words": ("l", "iiii"),
+    "fs_attention_bwd_split_parts_offset": ("l", "iii"),
+    "fs_stream_wait": ("i", "pp"),
+    "fs_set_deterministic": ("i", "i"),
+    "fs_get_deterministic": ("i", ""),
+    "fs_conv2d_bwd_weight_ws_bytes": ("l", "iiiiiii"),
+    "fs_linear_bwd_weight_bias_ws_bytes": ("l", "ii"),
+    "fs_conv2d_bwd_weight_plan": ("i", "iiiiiiiiiiii" + "lp"),
+    "fs_colsum_scratch_floats": ("l", "li"),
+    "fs_bn_stats_scratch_doubles": ("l", "li"),
+    "fs_mask_head_bwd_scratch_floats": ("l", "li"),
+    "fs_layernorm_bwd_scratch_floats": ("l", "li"),
+    "fs_conv2d_pack_persistent": ("i", "iiiiiiiiiiii" + "il"),
+    "fs_conv2d_ws_mode": ("i", "i"),
+    "fs_edge_loss_stats_floats": ("l", "l"),
+    "fs_compress_softmax_bwd_scratch_floats": ("l", "ii"),
+    "fs_gauss_grid_bwd_scratch_floats": ("l", "iii"),
+    "fs_unwarp_labels_scratch_ints": ("l", "iiiii"),
+    "fs_unwarp_accuracy_scratch_ints": ("l", "iiiii"),
+    "fs_trimap_bands_scratch_ints": ("l", "iii"),
+    "fs_unwarp_trimap_scratch_ints": ("l", "iiiii"),
+    "fs_unwarp_class_areas_scratch_ints": ("l", "iiiiii"),
+    "fs_unwarp_hd_scratch_ints": ("l", "iiiiii"),
+    "fs_surface_hd_scratch_ints": ("l", "iii"),
+    "fs_mask_rle_scratch_ints": ("l", "iii"),
+    "fs_unwarp_instances_scratch_ints": ("l", "iiiii"),
+    "fs_unwarp_instances_scored_scratch_ints": ("l", "iiiii"),
+    "fs_mask_component_scratch_ints": ("l", "iii"),
+    "fs_mask_component_route": ("i", "iii"),
+    "fs_unwarp_instances_component_scratch_ints": ("l", "iiiii"),
+}
 
 
 class HipLibraryError(RuntimeError):
@@ -161,92 +194,10 @@ def load():
         fn = getattr(lib, name)          # AttributeError here = header/library mismatch
         fn.restype = _I
         fn.argtypes = [_CT[c] for c in sig] + [_P]
-    lib.fs_set_conv_precision.restype = _I
-    lib.fs_set_conv_precision.argtypes = [_I]
-    lib.fs_get_conv_precision.restype = _I
-    lib.fs_get_conv_precision.argtypes = []
-    lib.fs_colsum_scratch_floats.restype = _L
-    lib.fs_colsum_scratch_floats.argtypes = [_L, _I]
-    lib.fs_bn_stats_scratch_doubles.restype = _L
-    lib.fs_bn_stats_scratch_doubles.argtypes = [_L, _I]
-    lib.fs_mask_head_bwd_scratch_floats.restype = _L
-    lib.fs_mask_head_bwd_scratch_floats.argtypes = [_L, _I]
-    lib.fs_layernorm_bwd_scratch_floats.restype = _L
-    lib.fs_layernorm_bwd_scratch_floats.argtypes = [_L, _I]
-    lib.fs_edge_loss_stats_floats.restype = _L
-    lib.fs_edge_loss_stats_floats.argtypes = [_L]
-    lib.fs_compress_softmax_bwd_scratch_floats.restype = _L
-    lib.fs_compress_softmax_bwd_scratch_floats.argtypes = [_I, _I]
-    lib.fs_gauss_grid_bwd_scratch_floats.restype = _L
-    lib.fs_gauss_grid_bwd_scratch_floats.argtypes = [_I, _I, _I]
-    lib.fs_unwarp_labels_scratch_ints.restype = _L
-    lib.fs_unwarp_labels_scratch_ints.argtypes = [_I] * 5
-    lib.fs_unwarp_accuracy_scratch_ints.restype = _L
-    lib.fs_unwarp_accuracy_scratch_ints.argtypes = [_I] * 5
-    lib.fs_trimap_bands_scratch_ints.restype = _L
-    lib.fs_trimap_bands_scratch_ints.argtypes = [_I] * 3
-    lib.fs_unwarp_trimap_scratch_ints.restype = _L
-    lib.fs_unwarp_trimap_scratch_ints.argtypes = [_I] * 5
-    lib.fs_unwarp_class_areas_scratch_ints.restype = _L
-    lib.fs_unwarp_class_areas_scratch_ints.argtypes = [_I] * 6
-    lib.fs_unwarp_hd_scratch_ints.restype = _L
-    lib.fs_unwarp_hd_scratch_ints.argtypes = [_I] * 6
-    lib.fs_surface_hd_scratch_ints.restype = _L
-    lib.fs_surface_hd_scratch_ints.argtypes = [_I] * 3
-    lib.fs_mask_rle_scratch_ints.restype = _L
-    lib.fs_mask_rle_scratch_ints.argtypes = [_I] * 3
-    lib.fs_unwarp_instances_scratch_ints.restype = _L
-    lib.fs_unwarp_instances_scratch_ints.argtypes = [_I] * 5
-    lib.fs_unwarp_instances_scored_scratch_ints.restype = _L
-    lib.fs_unwarp_instances_scored_scratch_ints.argtypes = [_I] * 5
-    lib.fs_mask_component_scratch_ints.restype = _L
-    lib.fs_mask_component_scratch_ints.argtypes = [_I] * 3
-    lib.fs_mask_component_route.restype = _I
-    lib.fs_mask_component_route.argtypes = [_I] * 3
-    lib.fs_unwarp_instances_component_scratch_ints.restype = _L
-    lib.fs_unwarp_instances_component_scratch_ints.argtypes = [_I] * 5
-    lib.fs_stream_wait.restype = _I
-    lib.fs_stream_wait.argtypes = [_P, _P]
-    lib.fs_set_deterministic.restype = _I
-    lib.fs_set_deterministic.argtypes = [_I]
-    lib.fs_get_deterministic.restype = _I
-    lib.fs_get_deterministic.argtypes = []
-    lib.fs_conv2d_bwd_weight_ws_bytes.restype = _L
-    lib.fs_conv2d_bwd_weight_ws_bytes.argtypes = [_I] * 7
-    lib.fs_conv2d_bwd_weight_plan.restype = _I
-    lib.fs_conv2d_bwd_weight_plan.argtypes = [_I] * 12 + [_L, ctypes.POINTER(_I)]
-    lib.fs_linear_bwd_weight_bias_ws_bytes.restype = _L
-    lib.fs_linear_bwd_weight_bias_ws_bytes.argtypes = [_I] * 2
-    lib.fs_conv2d_workspace_bytes.restype = _L
-    lib.fs_conv2d_workspace_bytes.argtypes = [_I] * 12
-    lib.fs_conv2d_stats_slabs.restype = _I
-    lib.fs_conv2d_stats_slabs.argtypes = [_I] * 12 + [_L]
-    lib.fs_conv2d_kernel_choice.restype = _I
-    lib.fs_conv2d_kernel_choice.argtypes = [_I] * 13 + [_L]
-    lib.fs_conv2d_pack_persistent.restype = _I
-    lib.fs_conv2d_pack_persistent.argtypes = [_I] * 13 + [_L]
-    lib.fs_conv2d_ws_mode.restype = _I
-    lib.fs_conv2d_ws_mode.argtypes = [_I]
-    lib.fs_bn_bwd_slabs.restype = _I
-    lib.fs_bn_bwd_slabs.argtypes = [_L, _I]
-    lib.fs_dwconv3_wgrad_lanes.restype = _I
-    lib.fs_dwconv3_wgrad_lanes.argtypes = [_I] * 4
-    lib.fs_conv2d_bwd_data_bnsum_slabs.restype = _I
-    lib.fs_conv2d_bwd_data_bnsum_slabs.argtypes = [_I] * 12 + [_L]
-    lib.fs_conv2d_fwd_affine_act_ok.restype = _I
-    lib.fs_conv2d_fwd_affine_act_ok.argtypes = [_I] * 12 + [_L]
-    lib.fs_conv2d_fwd_residual_ok.restype = _I
-    lib.fs_conv2d_fwd_residual_ok.argtypes = [_I] * 12 + [_L, _L]
-    lib.fs_linear_bwd_weight_bias_ok.restype = _I
-    lib.fs_linear_bwd_weight_bias_ok.argtypes = [_L, _I, _I]
-    lib.fs_attention_split_ws_bytes.restype = _L
-    lib.fs_attention_split_ws_bytes.argtypes = [_I] * 3
-    lib.fs_attention_bwd_split_ws_bytes.restype = _L
-    lib.fs_attention_bwd_split_ws_bytes.argtypes = [_I] * 3
-    lib.fs_attention_bwd_split_parts_offset.restype = _L
-    lib.fs_attention_bwd_split_parts_offset.argtypes = [_I] * 3
-    lib.fs_attention_mask_words.restype = _L
-    lib.fs_attention_mask_words.argtypes = [_I] * 4
+    for name, (res, sig) in HOST_ONLY.items():
+        fn = getattr(lib, name)
+        fn.restype = _CT[res]
+        fn.argtypes = [_CT[c] for c in sig]
     _lib = lib
     global _default_mode
     _default_mode = ("f32", "bf16x3", "f16x2")[lib.fs_get_conv_precision()]
@@ -302,21 +253,9 @@ def query(name, *args):
     return v
 
 
-def wgrad_workspace(device, Cin, Cout, R, S, stride, pad, dil):
-    """(scratch tensor | None, bytes) for fs_conv2d_bwd_weight: per-split partial tiles (deterministic mode; strided 3x3 layers in every mode)."""
-    n = query("fs_conv2d_bwd_weight_ws_bytes", Cin, Cout, R, S, stride, pad, dil)
-    if n == 0:
-        return None, 0
-    return torch.empty(n, device=device, dtype=torch.uint8), n
-
-
 def conv_workspace_bytes(H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed):
     """Scratch bytes the conv entry points can use for this shape under the current precision mode (cached)."""
     return query("fs_conv2d_workspace_bytes", H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed)
-
-
-def conv_stats_slabs(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes):
-    return query("fs_conv2d_stats_slabs", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes)
 
 
 def attention_split_ws_bytes(B, Nk, heads, backward=False):
@@ -332,11 +271,6 @@ def linear_bwd_weight_bias_ok(rows, Cin, Cout):
 def fwd_affine_act_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes):
     """True where fs_conv2d_fwd_affine_act serves this shape under the current precision mode (cached)."""
     return query("fs_conv2d_fwd_affine_act_ok", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes) == 1
-
-
-def fwd_residual_ok(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, rows_per_sample, ws_bytes):
-    """True where fs_conv2d_fwd_residual serves this shape under the current precision mode (cached)."""
-    return query("fs_conv2d_fwd_residual_ok", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, rows_per_sample, ws_bytes) == 1
 
 
 def bwd_data_bnsum_slabs(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes):

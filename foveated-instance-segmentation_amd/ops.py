@@ -9,6 +9,7 @@ import math
 import os
 import weakref
 import zlib
+from typing import NamedTuple
 
 import torch
 from torch.autograd import Function
@@ -138,13 +139,96 @@ def _launch(kind, flops, name, *args):
         TIMER.launch(kind, flops, lambda: hip.call(name, *args), tag=(name,) + tuple(a for a in args if type(a) is int and a < (1 << 20)))
 
 
-def _conv_kind(Cs, Cd, R, S, stride, pad, dil):
-    """Timer bucket = the kernel csrc/conv.hip selects: the halo-tiled 3x3 stride-1 kernel, the other aligned kernels, or the generic one."""
-    if Cs % 4 or Cd % 4:
-        return "conv_generic"
-    if R == 3 and S == 3 and stride == 1 and pad == 1 and dil == 1 and Cs >= 32 and hip.get_conv_precision() != "f32":
-        return "conv3x3"
-    return "conv_affine"
+class ConvProblem(NamedTuple):
+    """One convolution as the C ABI spells it (csrc/conv_kernels.h FsConvProblem): x (B,H,W,Cin) -> y (B,Ho,Wo,Cout) under an R x S filter.
+    The field order IS the argument block of every conv entry point and host query, so `*p` passes it and nothing else in this module
+    spells that order out.  The queries go through hip.query: cached per argument tuple, dropped when a library mode changes."""
+    B: int
+    H: int
+    W: int
+    Cin: int
+    Ho: int
+    Wo: int
+    Cout: int
+    R: int
+    S: int
+    stride: int
+    pad: int
+    dil: int
+
+    @classmethod
+    def of(cls, x_shape, w_shape, stride, pad, dil=1):
+        """The problem of a (B,H,W,Cin) input under a logical (Cout,Cin,R,S) weight."""
+        B, H, W, Cin = x_shape
+        Cout, Cin2, R, S = w_shape
+        assert Cin == Cin2, (tuple(x_shape), tuple(w_shape))
+        Ho, Wo = _out_hw(H, W, R, S, stride, pad, dil)
+        return cls(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil)
+
+    @classmethod
+    def linear(cls, rows, cin, cout):
+        """A linear layer over `rows` rows of `cin` features as the 1x1 convolution of an image one pixel wide and `rows` high."""
+        return cls(1, rows, 1, cin, rows, 1, cout, 1, 1, 1, 0, 1)
+
+    @property
+    def flops(self):
+        """Algorithmic work of any of the three convolutions of this problem (exact: every factor is an integer, the product < 2^53)."""
+        B, _, _, Cin, Ho, Wo, Cout, R, S, _, _, _ = self
+        return 2.0 * B * Ho * Wo * Cout * R * S * Cin
+
+    @property
+    def x_shape(self):
+        """Shape of the input and of its gradient, as a plain tuple (compares equal to tuple(t.shape))."""
+        return self[0:4]
+
+    @property
+    def y_shape(self):
+        return (self.B, self.Ho, self.Wo, self.Cout)
+
+    def at_batch(self, B):
+        """The same problem over B images (one batch range of it)."""
+        return self._replace(B=B)
+
+    def batch_ranges(self):
+        """_batch_ranges over this problem's input and output tensors."""
+        return _batch_ranges(self.B, self.H * self.W * self.Cin, self.Ho * self.Wo * self.Cout)
+
+    def kind(self, transposed):
+        """Timer bucket = the kernel csrc/conv.hip selects: the halo-tiled 3x3 stride-1 kernel, the other aligned kernels, or the generic one
+        (transposed = bwd-data: the kernel's source channels are Cout)."""
+        if self.Cin % 4 or self.Cout % 4:
+            return "conv_generic"
+        if self[7:] == (3, 3, 1, 1, 1) and (self.Cout if transposed else self.Cin) >= 32 and hip.get_conv_precision() != "f32":
+            return "conv3x3"
+        return "conv_affine"
+
+    def ws_bytes(self, transposed):
+        """Scratch bytes the conv entry points can use for this shape under the current precision mode."""
+        return hip.query("fs_conv2d_workspace_bytes", *self[1:], transposed)
+
+    def pack_persistent(self, transposed, ws):
+        """Non-zero where the kernel this problem runs on can keep its weight pack across calls (fs_conv2d_pack / fs_conv2d_ws_mode)."""
+        return hip.query("fs_conv2d_pack_persistent", *self, transposed, ws)
+
+    def stats_slabs(self, ws):
+        """Slab rows fs_conv2d_fwd_stats writes."""
+        return hip.query("fs_conv2d_stats_slabs", *self, ws)
+
+    def bnsum_slabs(self, ws):
+        """Slab rows of fs_conv2d_bwd_data_bnsum, 0 = this problem's kernel has no such epilogue."""
+        return hip.query("fs_conv2d_bwd_data_bnsum_slabs", *self, ws)
+
+    def affine_act_ok(self, ws):
+        """True where fs_conv2d_fwd_affine_act serves this problem."""
+        return hip.query("fs_conv2d_fwd_affine_act_ok", *self, ws) == 1
+
+    def residual_ok(self, rows_per_sample, ws):
+        """True where fs_conv2d_fwd_residual serves this problem."""
+        return hip.query("fs_conv2d_fwd_residual_ok", *self, rows_per_sample, ws) == 1
+
+    def wgrad_ws_bytes(self):
+        """Scratch bytes of fs_conv2d_bwd_weight: per-split partial tiles (deterministic mode; strided 3x3 layers in every mode)."""
+        return hip.query("fs_conv2d_bwd_weight_ws_bytes", self.Cin, self.Cout, *self[7:])
 
 
 def weight_amax(w):
@@ -183,19 +267,14 @@ def _batch_ranges(B, *per_image_elems):
 
 
 def conv2d_fwd(x, w, bias, stride, pad, drop_p=0.0, drop_key=0, dil=1, w_amax=None):
-    B, H, W, Cin = x.shape
-    Cout, Cin2, R, S = w.shape
-    assert Cin == Cin2, (x.shape, w.shape)
-    Ho, Wo = _out_hw(H, W, R, S, stride, pad, dil)
-    ranges = _batch_ranges(B, H * W * Cin, Ho * Wo * Cout) if drop_p == 0.0 else [(0, B)]
+    p = ConvProblem.of(x.shape, w.shape, stride, pad, dil)
+    ranges = p.batch_ranges() if drop_p == 0.0 else [(0, p.B)]
     if len(ranges) > 1:
         return torch.cat([conv2d_fwd(x[b0:b1], w, bias, stride, pad, 0.0, 0, dil, w_amax) for b0, b1 in ranges])
-    y = torch.empty(B, Ho, Wo, Cout, device=x.device, dtype=torch.float32)
-    kind = _conv_kind(Cin, Cout, R, S, stride, pad, dil)
-    ws, ws_bytes, packed = _pack_for(w, x.device, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0)
-    _launch_conv(packed, kind, 2.0 * B * Ho * Wo * Cout * R * S * Cin, "fs_conv2d_fwd", hip.ptr(x), hip.ptr(rsck(w)), hip.ptr(bias),
-            hip.ptr(y), B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, float(drop_p), int(drop_key), hip.ptr(ws), ws_bytes,
-            hip.ptr(w_amax))
+    y = torch.empty(p.y_shape, device=x.device, dtype=torch.float32)
+    ws, ws_bytes, packed = _pack_for(w, x.device, p, 0)
+    _launch_conv(packed, p.kind(0), p.flops, "fs_conv2d_fwd", hip.ptr(x), hip.ptr(rsck(w)), hip.ptr(bias),
+            hip.ptr(y), *p, float(drop_p), int(drop_key), hip.ptr(ws), ws_bytes, hip.ptr(w_amax))
     return y
 
 
@@ -228,19 +307,19 @@ class _Pack:
     __slots__ = ("w", "args", "transposed", "ws", "n", "mode", "cell", "epoch", "version", "used", "group", "stream", "ready", "__weakref__")
 
 
-def _pack_for(w, device, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed):
+def _pack_for(w, device, problem, transposed):
     """(scratch | None, bytes, already packed?) for a conv entry point on weight tensor `w`."""
-    n = hip.conv_workspace_bytes(H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed)
+    n = problem.ws_bytes(transposed)
     if n == 0:
         return None, 0, False
     cell = getattr(w, "_fs_epoch", None) if (PACK_PERSIST or getattr(w, "_fs_static", False)) else None
-    if cell is None or not hip.query("fs_conv2d_pack_persistent", B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, transposed, n):
+    if cell is None or not problem.pack_persistent(transposed, n):
         return torch.empty(n, device=device, dtype=torch.uint8), n, False
     packs = w.__dict__.get("_fs_packs")
     if packs is None:
         packs = w.__dict__["_fs_packs"] = {}
     mode = hip.get_conv_precision()
-    key = (transposed, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, mode)
+    key = (transposed, *problem, mode)
     e = packs.get(key)
     if e is None:
         e = packs[key] = _Pack()
@@ -356,21 +435,17 @@ FUSE_BN_BWD_SUMS = os.environ.get("FS_FUSE_BN_BWD", "1") != "0"
 
 def conv2d_fwd_stats(x, w, bias, stride, pad, drop_p=0.0, drop_key=0, dil=1, w_amax=None):
     """Forward conv + per-workgroup BatchNorm partial sums (slab [nwg][Cout][2])."""
-    B, H, W, Cin = x.shape
-    Cout, Cin2, R, S = w.shape
-    assert Cin == Cin2, (x.shape, w.shape)
-    Ho, Wo = _out_hw(H, W, R, S, stride, pad, dil)
-    ranges = _batch_ranges(B, H * W * Cin, Ho * Wo * Cout) if drop_p == 0.0 else [(0, B)]
+    p = ConvProblem.of(x.shape, w.shape, stride, pad, dil)
+    ranges = p.batch_ranges() if drop_p == 0.0 else [(0, p.B)]
     if len(ranges) > 1:          # slab rows of the ranges concatenate: the finalize pass sums over all of them
         parts = [conv2d_fwd_stats(x[b0:b1], w, bias, stride, pad, 0.0, 0, dil, w_amax) for b0, b1 in ranges]
-        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), sum(p[2] for p in parts)
-    y = torch.empty(B, Ho, Wo, Cout, device=x.device, dtype=torch.float32)
-    ws, ws_bytes, packed = _pack_for(w, x.device, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 0)
-    nwg = hip.conv_stats_slabs(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes)
-    slab = torch.empty(nwg * Cout * 2, device=x.device, dtype=torch.float32)
-    _launch_conv(packed, _conv_kind(Cin, Cout, R, S, stride, pad, dil), 2.0 * B * Ho * Wo * Cout * R * S * Cin, "fs_conv2d_fwd_stats", hip.ptr(x), hip.ptr(rsck(w)),
-            hip.ptr(bias), hip.ptr(y), hip.ptr(slab), B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, float(drop_p), int(drop_key),
-            hip.ptr(ws), ws_bytes, hip.ptr(w_amax))
+        return torch.cat([q[0] for q in parts]), torch.cat([q[1] for q in parts]), sum(q[2] for q in parts)
+    y = torch.empty(p.y_shape, device=x.device, dtype=torch.float32)
+    ws, ws_bytes, packed = _pack_for(w, x.device, p, 0)
+    nwg = p.stats_slabs(ws_bytes)
+    slab = torch.empty(nwg * p.Cout * 2, device=x.device, dtype=torch.float32)
+    _launch_conv(packed, p.kind(0), p.flops, "fs_conv2d_fwd_stats", hip.ptr(x), hip.ptr(rsck(w)), hip.ptr(bias), hip.ptr(y), hip.ptr(slab),
+            *p, float(drop_p), int(drop_key), hip.ptr(ws), ws_bytes, hip.ptr(w_amax))
     return y, slab, nwg
 
 
@@ -387,36 +462,33 @@ def conv2d_bwd_data(dy, w, x_shape, stride, pad, dil=1, w_amax=None, src_bn=None
     the lookup misses and the layer runs its own reduction pass).  addend = (dz, mask bytes | None): a second gradient of x -- the
     residual branch's -- added in the same epilogue (ConvBnAct.backward stashes it in PENDING_RES only after asking the library that
     this shape's kernel takes it)."""
-    B, H, W, Cin = x_shape
-    Cout, _, R, S = w.shape
-    _, Ho, Wo, _ = dy.shape
-    ranges = _batch_ranges(B, H * W * Cin, Ho * Wo * Cout)
+    p = ConvProblem.of(x_shape, w.shape, stride, pad, dil)
+    assert tuple(dy.shape) == p.y_shape, (tuple(dy.shape), p)
+    ranges = p.batch_ranges()
     if len(ranges) > 1:          # without the fused extras; the addend joins afterwards
-        dx = torch.cat([conv2d_bwd_data(dy[b0:b1], w, (b1 - b0, H, W, Cin), stride, pad, dil, w_amax) for b0, b1 in ranges])
+        dx = torch.cat([conv2d_bwd_data(dy[b0:b1], w, p.at_batch(b1 - b0).x_shape, stride, pad, dil, w_amax) for b0, b1 in ranges])
         if addend is not None:
             a_src, a_mask = addend
             dx += a_src if a_mask is None else a_src * _unmask_bits(a_mask, a_src)
         return dx
-    dx = torch.empty(B, H, W, Cin, device=dy.device, dtype=torch.float32)
-    kind = _conv_kind(Cout, Cin, R, S, stride, pad, dil)
-    ws, ws_bytes, packed = _pack_for(w, dy.device, B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 1)
-    flops = 2.0 * B * Ho * Wo * Cout * R * S * Cin
-    if src_bn is not None and not (FUSE_BN_BWD_SUMS and FANOUT and tuple(src_bn[0].shape) == (B, H, W, Cin)):
+    dx = torch.empty(p.x_shape, device=dy.device, dtype=torch.float32)
+    kind = p.kind(1)
+    ws, ws_bytes, packed = _pack_for(w, dy.device, p, 1)
+    if src_bn is not None and not (FUSE_BN_BWD_SUMS and FANOUT and tuple(src_bn[0].shape) == p.x_shape):
         src_bn = None
     if src_bn is not None or addend is not None:
-        rows = hip.bwd_data_bnsum_slabs(B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, ws_bytes)
+        rows = p.bnsum_slabs(ws_bytes)
         if rows > 0:
             y, amask, mean, invstd = src_bn[:4] if src_bn is not None else (None, None, None, None)
-            slab = torch.empty(rows * Cin * 2, device=dy.device, dtype=torch.float32) if src_bn is not None else None
+            slab = torch.empty(rows * p.Cin * 2, device=dy.device, dtype=torch.float32) if src_bn is not None else None
             a_src, a_mask = addend if addend is not None else (None, None)
-            _launch_conv(packed, kind, flops, "fs_conv2d_bwd_data_bnsum", hip.ptr(dy), hip.ptr(rsck(w)), hip.ptr(dx), B, H, W, Cin, Ho, Wo, Cout, R, S,
-                    stride, pad, dil, hip.ptr(ws), ws_bytes, hip.ptr(w_amax), hip.ptr(y), hip.ptr(amask), hip.ptr(mean), hip.ptr(invstd),
+            _launch_conv(packed, kind, p.flops, "fs_conv2d_bwd_data_bnsum", hip.ptr(dy), hip.ptr(rsck(w)), hip.ptr(dx), *p,
+                    hip.ptr(ws), ws_bytes, hip.ptr(w_amax), hip.ptr(y), hip.ptr(amask), hip.ptr(mean), hip.ptr(invstd),
                     hip.ptr(slab), hip.ptr(a_src), hip.ptr(a_mask))
             if slab is not None:
                 BN_SLABS[(dx.data_ptr(), y.data_ptr())] = (slab, rows, dx)
             return dx
-    _launch_conv(packed, kind, flops, "fs_conv2d_bwd_data", hip.ptr(dy), hip.ptr(rsck(w)), hip.ptr(dx),
-            B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, hip.ptr(ws), ws_bytes, hip.ptr(w_amax))
+    _launch_conv(packed, kind, p.flops, "fs_conv2d_bwd_data", hip.ptr(dy), hip.ptr(rsck(w)), hip.ptr(dx), *p, hip.ptr(ws), ws_bytes, hip.ptr(w_amax))
     if addend is not None:          # the library no longer takes the addend for this shape (precision mode changed since the stash): add here
         a_src, a_mask = addend
         dx = dx + (a_src if a_mask is None else a_src * _unmask_bits(a_mask, a_src))
@@ -480,23 +552,22 @@ def _direct_grad_target(p):
 def conv2d_bwd_weight(x, dy, w_shape, stride, pad, out=None, dil=1, accumulate=False, keep=None):
     """dW of conv2d.  out = a gradient buffer in the weight's layout; accumulate=True adds into it (the DIRECT_GRAD arena
     is zeroed once per step by zero_grad, so the per-layer memset is skipped and repeated backwards accumulate like .grad)."""
-    B, H, W, Cin = x.shape
-    Cout, _, R, S = w_shape
-    _, Ho, Wo, _ = dy.shape
-    ranges = _batch_ranges(B, H * W * Cin, Ho * Wo * Cout)
+    p = ConvProblem.of(x.shape, w_shape, stride, pad, dil)
+    assert tuple(dy.shape) == p.y_shape, (tuple(dy.shape), p)
+    ranges = p.batch_ranges()
     if len(ranges) > 1:          # the ranges' gradients accumulate in one buffer
-        buf = out if out is not None else new_rsck_weight(Cout, Cin, R, S, device=x.device)
+        buf = out if out is not None else new_rsck_weight(p.Cout, p.Cin, p.R, p.S, device=x.device)
         for i, (b0, b1) in enumerate(ranges):
             conv2d_bwd_weight(x[b0:b1], dy[b0:b1], w_shape, stride, pad, out=buf, dil=dil, accumulate=accumulate or i > 0)
         return buf
-    dw = rsck(out) if out is not None else torch.empty(R, S, Cin, Cout, device=x.device, dtype=torch.float32)
-    k3 = R == 3 and S == 3 and stride == 1 and pad == 1 and dil == 1 and Cin % 4 == 0 and Cout % 4 == 0 and Cin >= 16 and Cout >= 16
-    dws, dws_bytes = hip.wgrad_workspace(x.device, Cin, Cout, R, S, stride, pad, dil)      # deterministic mode; strided 3x3 layers
+    dw = rsck(out) if out is not None else torch.empty(p.R, p.S, p.Cin, p.Cout, device=x.device, dtype=torch.float32)
+    k3 = p[7:] == (3, 3, 1, 1, 1) and p.Cin % 4 == 0 and p.Cout % 4 == 0 and p.Cin >= 16 and p.Cout >= 16
+    dws_bytes = p.wgrad_ws_bytes()          # deterministic mode; strided 3x3 layers
+    dws = torch.empty(dws_bytes, device=x.device, dtype=torch.uint8) if dws_bytes else None
     if keep is not None and dws is not None:
         keep.append(dws)          # the launch runs on a side stream: the scratch must outlive this call (join_wgrad_streams)
-    _launch("wgrad3x3" if (k3 and hip.get_conv_precision() != "f32") else "conv_wgrad", 2.0 * B * Ho * Wo * Cout * R * S * Cin,
-            "fs_conv2d_bwd_weight", hip.ptr(x), hip.ptr(dy), hip.ptr(dw),
-            B, H, W, Cin, Ho, Wo, Cout, R, S, stride, pad, dil, 1 if accumulate else 0, hip.ptr(dws), dws_bytes)
+    _launch("wgrad3x3" if (k3 and hip.get_conv_precision() != "f32") else "conv_wgrad", p.flops,
+            "fs_conv2d_bwd_weight", hip.ptr(x), hip.ptr(dy), hip.ptr(dw), *p, 1 if accumulate else 0, hip.ptr(dws), dws_bytes)
     return out if out is not None else dw.permute(3, 2, 0, 1)
 
 
@@ -666,6 +737,34 @@ def _queue_wgrad_join():
         pass
 
 
+def _wgrad_side_or_inline(x, dy, w_shape, stride, pad, dil, tgt):
+    """The weight gradient of ConvBnAct.backward: on the side stream where the kernel adds straight into the gradient arena (tgt) and the
+    layer is below WGRAD_SIDE_FLOPS, else on the current stream.  Returns what autograd gets: None where the arena took the gradient."""
+    # (not under stream capture: forking the side stream into a capture once per layer and joining it once at the end ends in a host
+    #  segmentation fault inside hipStreamEndCapture on ROCm 7.2 -- tools/probes/graph_probe.py, profiles/r05/graph_probe.txt)
+    if (tgt is not None and ConvProblem.of(x.shape, w_shape, stride, pad, dil).flops < WGRAD_SIDE_FLOPS and TIMER is None
+            and not torch.cuda.is_current_stream_capturing()):
+        side = _wgrad_side_stream(dy.device)
+        _queue_wgrad_join()                       # backward() returns with its stream ordered behind the side stream
+        hip.stream_wait(side, hip._stream())      # dy (and x) were produced on the current stream
+        keep = _WGRAD_SIDE_BUSY.setdefault(side, [])
+        if len(keep) >= _WGRAD_ROTATE and not torch.cuda.is_current_stream_capturing():
+            # a long backward (configs[4]: every layer is small) does not hold on to all of its activations and gradients: lists
+            # retire under an event and go when it has completed
+            _wgrad_retire(side, keep)
+            keep = _WGRAD_SIDE_BUSY[side] = []
+            _wgrad_reap()
+        keep.append((x, dy))
+        hip.set_stream_override(side)
+        try:
+            conv2d_bwd_weight(x, dy, w_shape, stride, pad, out=tgt, dil=dil, accumulate=True, keep=keep)
+        finally:
+            hip.set_stream_override(None)
+        return None
+    dw = conv2d_bwd_weight(x, dy, w_shape, stride, pad, out=tgt, dil=dil, accumulate=tgt is not None)
+    return None if tgt is not None else dw
+
+
 # BatchNorm-backward column sums that the PRODUCER of a gradient tensor already formed (FanOut.backward below, the bwd-data epilogue of the
 # consumer conv, HrFuse.backward): (dz.data_ptr(), y.data_ptr()) -> (slab, nslab, dz), y = the conv output of the layer the sums are for
 # (one fuse gradient is the output gradient of up to three layers).  The entry keeps dz alive, so its address cannot be reused while the
@@ -719,7 +818,7 @@ class FanOut(Function):
 
 _FAN_IDS = [0]
 # A two-way fan-out whose consumers are a convolution and a residual input (BasicBlock, models/hrnetv2_nodownsp.py:46-62): the conv
-# consumer's forward leaves its geometry in FAN_GEOM under the fan id, the residual consumer's backward (it always runs first) asks the
+# consumer's forward leaves its ConvProblem in FAN_GEOM under the fan id, the residual consumer's backward (it always runs first) asks the
 # library whether that convolution's bwd-data epilogue takes an addend and, if so, leaves (dz, mask bytes) in PENDING_RES instead of
 # materialising the residual gradient; the conv consumer's backward passes it on (conv2d_bwd_data) -- no n-ary add, no dres tensor.
 FAN_GEOM = {}
@@ -773,7 +872,7 @@ class StashGrad(Function):
         if g is None or ctx.fan_id in FAN_DONE or ctx.fan_id in PENDING_RES or not (FUSE_BN_BWD_SUMS and FANOUT):
             return g, None
         geom = FAN_GEOM.get(ctx.fan_id)
-        if geom is None or tuple(geom[0]) != tuple(g.shape):
+        if geom is None or geom.x_shape != tuple(g.shape):
             return g, None
         PENDING_RES[ctx.fan_id] = (g if g.is_contiguous() else g.contiguous(), None)
         return None, None
@@ -829,20 +928,15 @@ class ConvBnAct(Function):
         #  the call site, which modules.conv_bn_act records in meta before Function.apply switches it off)
         if not training and FUSE_EVAL_BN and not meta.get("grad_enabled", True) and Cin % 4 == 0 and Cout % 4 == 0:
             # inference: eval-mode BatchNorm, residual and activation in the conv epilogue where this shape's kernel has one
-            B_, H_, W_, _ = x.shape
-            R_, S_ = w.shape[2], w.shape[3]
-            Ho_, Wo_ = _out_hw(H_, W_, R_, S_, meta["stride"], meta["pad"], dil)
-            ws_bytes = hip.conv_workspace_bytes(H_, W_, Cin, Ho_, Wo_, Cout, R_, S_, meta["stride"], meta["pad"], dil, 0)
-            if hip.fwd_affine_act_ok(B_, H_, W_, Cin, Ho_, Wo_, Cout, R_, S_, meta["stride"], meta["pad"], dil, ws_bytes):
+            p = ConvProblem.of(x.shape, w.shape, meta["stride"], meta["pad"], dil)
+            if p.affine_act_ok(p.ws_bytes(0)):
                 coef = torch.empty(2, Cout, device=x.device, dtype=torch.float32)
                 hip.call("fs_bn_eval_affine", hip.ptr(meta["running_mean"]), hip.ptr(meta["running_var"]), hip.ptr(gamma), hip.ptr(beta), Cout,
                          BN_EPS, hip.ptr(coef[0]), hip.ptr(coef[1]))
-                z = torch.empty(B_, Ho_, Wo_, Cout, device=x.device, dtype=torch.float32)
-                ws, ws_bytes, packed = _pack_for(w, x.device, B_, H_, W_, Cin, Ho_, Wo_, Cout, R_, S_, meta["stride"], meta["pad"], dil, 0)
-                _launch_conv(packed, _conv_kind(Cin, Cout, R_, S_, meta["stride"], meta["pad"], dil), 2.0 * B_ * Ho_ * Wo_ * Cout * R_ * S_ * Cin,
-                        "fs_conv2d_fwd_affine_act", hip.ptr(x), hip.ptr(rsck(w)), hip.ptr(bias), hip.ptr(coef[0]), hip.ptr(coef[1]), hip.ptr(res),
-                        hip.ptr(z), B_, H_, W_, Cin, Ho_, Wo_, Cout, R_, S_, meta["stride"], meta["pad"], dil, meta["act"], hip.ptr(ws), ws_bytes,
-                        hip.ptr(wa))
+                z = torch.empty(p.y_shape, device=x.device, dtype=torch.float32)
+                ws, ws_bytes, packed = _pack_for(w, x.device, p, 0)
+                _launch_conv(packed, p.kind(0), p.flops, "fs_conv2d_fwd_affine_act", hip.ptr(x), hip.ptr(rsck(w)), hip.ptr(bias), hip.ptr(coef[0]),
+                        hip.ptr(coef[1]), hip.ptr(res), hip.ptr(z), *p, meta["act"], hip.ptr(ws), ws_bytes, hip.ptr(wa))
                 return z
         if fused_stats:
             y, slab, nwg = conv2d_fwd_stats(x, w, bias, meta["stride"], meta["pad"], drop_p, meta["drop_key"], dil, w_amax=wa)
@@ -879,8 +973,7 @@ class ConvBnAct(Function):
         ctx.src_bn = getattr(x, "_fs_bn", None)       # x is the output of another conv + BatchNorm layer: its record, for the bwd-data epilogue
         ctx.fan = getattr(x, "_fs_fan", None)         # x is one of the two aliases of a fan-out: this conv may absorb the other alias's gradient
         if ctx.fan is not None:
-            FAN_GEOM[ctx.fan[0]] = (tuple(x.shape), tuple(w.shape), meta["stride"], meta["pad"], dil)
-        if ctx.fan is not None:
+            FAN_GEOM[ctx.fan[0]] = ConvProblem.of(x.shape, w.shape, meta["stride"], meta["pad"], dil)
             z._fs_after_fan = ctx.fan[0]              # z is computed FROM the fan-out's conv alias: a layer reading z runs its backward before this one
         rfan = getattr(res, "_fs_fan", None) if res is not None else None
         # The residual gradient may only be left for the fan-out's conv consumer when that consumer's backward is certain to run AFTER this
@@ -906,14 +999,9 @@ class ConvBnAct(Function):
         absorb = None
         if (m["has_res"] and ctx.res_fan is not None and ctx.res_fan[1] is not None and FUSE_BN_BWD_SUMS and FANOUT
                 and (m["act"] == ACT_NONE or amask is not None)):
-            xs, wsh, st, pd, dl = ctx.res_fan[1]
-            if xs == tuple(y.shape):
-                fB, fH, fW, fCin = xs
-                fCout, _, fR, fS = wsh
-                fHo, fWo = _out_hw(fH, fW, fR, fS, st, pd, dl)
-                wsb = hip.conv_workspace_bytes(fH, fW, fCin, fHo, fWo, fCout, fR, fS, st, pd, dl, 1)
-                if hip.bwd_data_bnsum_slabs(fB, fH, fW, fCin, fHo, fWo, fCout, fR, fS, st, pd, dl, wsb) > 0 and ctx.res_fan[0] not in FAN_DONE:
-                    absorb = ctx.res_fan[0]
+            fp = ctx.res_fan[1]          # the problem of the fan-out's conv consumer
+            if fp.x_shape == tuple(y.shape) and fp.bnsum_slabs(fp.ws_bytes(1)) > 0 and ctx.res_fan[0] not in FAN_DONE:
+                absorb = ctx.res_fan[0]
         dres = torch.empty_like(y) if (m["has_res"] and absorb is None) else None
         tg, tb = _direct_grad_target(gamma), _direct_grad_target(ctx.beta_ref)
         direct_affine = tg is not None and tb is not None
@@ -947,31 +1035,7 @@ class ConvBnAct(Function):
         src_bn = ctx.src_bn if ctx.fan is None else (ctx.fan[1] if pend is not None else None)
         if not WGRAD_FIRST:
             dx = conv2d_bwd_data(dy, w, x.shape, m["stride"], m["pad"], m["dil"], w_amax=ctx.w_amax, src_bn=src_bn, addend=pend) if ctx.needs_input_grad[0] else None
-        # (not under stream capture: forking the side stream into a capture once per layer and joining it once at the end ends in a host
-        #  segmentation fault inside hipStreamEndCapture on ROCm 7.2 -- tools/probes/graph_probe.py, profiles/r05/graph_probe.txt)
-        if (tgt is not None and 2.0 * M * C * w.shape[1] * w.shape[2] * w.shape[3] < WGRAD_SIDE_FLOPS and TIMER is None
-                and not torch.cuda.is_current_stream_capturing()):
-            side = _wgrad_side_stream(dy.device)
-            _queue_wgrad_join()                       # backward() returns with its stream ordered behind the side stream
-            hip.stream_wait(side, hip._stream())      # dy (and x) were produced on the current stream
-            keep = _WGRAD_SIDE_BUSY.setdefault(side, [])
-            if len(keep) >= _WGRAD_ROTATE and not torch.cuda.is_current_stream_capturing():
-                # a long backward (configs[4]: every layer is small) does not hold on to all of its activations and gradients: lists
-                # retire under an event and go when it has completed
-                _wgrad_retire(side, keep)
-                keep = _WGRAD_SIDE_BUSY[side] = []
-                _wgrad_reap()
-            keep.append((x, dy))
-            hip.set_stream_override(side)
-            try:
-                conv2d_bwd_weight(x, dy, w.shape, m["stride"], m["pad"], out=tgt, dil=m["dil"], accumulate=True, keep=keep)
-            finally:
-                hip.set_stream_override(None)
-            dw = None
-        else:
-            dw = conv2d_bwd_weight(x, dy, w.shape, m["stride"], m["pad"], out=tgt, dil=m["dil"], accumulate=tgt is not None)
-        if tgt is not None:
-            dw = None
+        dw = _wgrad_side_or_inline(x, dy, w.shape, m["stride"], m["pad"], m["dil"], tgt)
         if WGRAD_FIRST:     # dx is what the next backward node reads: produce it last so it is the freshest tensor in the cache
             dx = conv2d_bwd_data(dy, w, x.shape, m["stride"], m["pad"], m["dil"], w_amax=ctx.w_amax, src_bn=src_bn, addend=pend) if ctx.needs_input_grad[0] else None
         dbias = colsum(dy, C) if m["has_bias"] else None
@@ -1005,19 +1069,12 @@ class ConvBias(Function):
         dx = conv2d_bwd_data(dy, w, x.shape, stride, pad) if ctx.needs_input_grad[0] else None
         if ctx.w_via is not None and getattr(w, "_fs_grad_via", None) is None:
             w._fs_grad_via = ctx.w_via
-        tgt = _direct_grad_target(w)
         cout, cin, r, s = w.shape
-        rows = dy.numel() // cout
-        if has_bias and r == 1 and s == 1 and stride == 1 and pad == 0 and hip.linear_bwd_weight_bias_ok(rows, cin, cout):
+        if has_bias and r == 1 and s == 1 and stride == 1 and pad == 0 and hip.linear_bwd_weight_bias_ok(dy.numel() // cout, cin, cout):
             # a linear layer: the bias gradient (column sums of dy) rides in the weight-gradient launch, which reads dy anyway
-            btgt = _direct_grad_target(ctx.bias_ref)
-            dw = rsck(tgt) if tgt is not None else torch.empty(1, 1, cin, cout, device=x.device, dtype=torch.float32)
-            db = btgt if btgt is not None else torch.empty(cout, device=x.device, dtype=torch.float32)
-            lws_bytes = hip.query("fs_linear_bwd_weight_bias_ws_bytes", cin, cout)      # deterministic mode only
-            lws = torch.empty(lws_bytes, device=x.device, dtype=torch.uint8) if lws_bytes else None
-            _launch("conv_wgrad", 2.0 * rows * cout * cin, "fs_linear_bwd_weight_bias", hip.ptr(x), hip.ptr(dy), hip.ptr(dw), hip.ptr(db),
-                    rows, cin, cout, 1 if tgt is not None else 0, 1 if btgt is not None else 0, hip.ptr(lws), lws_bytes)
-            return (dx, None if tgt is not None else dw.permute(3, 2, 0, 1), None if btgt is not None else db, None, None, None, None)
+            dw, db = _linear_param_grads(x, dy, w, ctx.bias_ref)
+            return dx, dw, db, None, None, None, None
+        tgt = _direct_grad_target(w)
         dw = conv2d_bwd_weight(x, dy, w.shape, stride, pad, out=tgt, accumulate=tgt is not None)
         if tgt is not None:
             dw = None
@@ -2223,13 +2280,13 @@ class LinearResidual(Function):
     def forward(ctx, x, w, bias, res, drop_p, drop_key, dp_p, dp_key):
         cout, cin = w.shape[0], w.shape[1]
         rows = x.numel() // cin
-        x4 = x.reshape(1, rows, 1, cin)
+        p = ConvProblem.linear(rows, cin, cout)
+        x4 = x.reshape(p.x_shape)
         rps = rows // res.shape[0]
-        ws, ws_bytes, packed = _pack_for(w, x.device, 1, rows, 1, cin, rows, 1, cout, 1, 1, 1, 0, 1, 0)
+        ws, ws_bytes, packed = _pack_for(w, x.device, p, 0)
         out = torch.empty_like(res)
-        _launch_conv(packed, "conv_affine", 2.0 * rows * cout * cin, "fs_conv2d_fwd_residual", hip.ptr(x4), hip.ptr(rsck(w)), hip.ptr(bias),
-                     hip.ptr(res), hip.ptr(out), 1, rows, 1, cin, rows, 1, cout, 1, 1, 1, 0, 1, float(drop_p), int(drop_key), float(dp_p), int(dp_key),
-                     rps, hip.ptr(ws), ws_bytes, None)
+        _launch_conv(packed, "conv_affine", p.flops, "fs_conv2d_fwd_residual", hip.ptr(x4), hip.ptr(rsck(w)), hip.ptr(bias),
+                     hip.ptr(res), hip.ptr(out), *p, float(drop_p), int(drop_key), float(dp_p), int(dp_key), rps, hip.ptr(ws), ws_bytes, None)
         ctx.save_for_backward(x4, w)
         ctx.cfg = (float(drop_p), int(drop_key), float(dp_p), int(dp_key), rps, bias is not None, tuple(x.shape))
         ctx.bias_ref = bias
@@ -2284,8 +2341,8 @@ def linear_residual(x, w, bias, res, drop_p, drop_key, dp_p, dp_key):
     rows = x.numel() // cin
     if rows % res.shape[0] or rows * max(cin, cout) * 4 >= MAX_TENSOR_BYTES:
         return None
-    wsb = hip.conv_workspace_bytes(rows, 1, cin, rows, 1, cout, 1, 1, 1, 0, 1, 0)
-    if not hip.fwd_residual_ok(1, rows, 1, cin, rows, 1, cout, 1, 1, 1, 0, 1, rows // res.shape[0], wsb):
+    p = ConvProblem.linear(rows, cin, cout)
+    if not p.residual_ok(rows // res.shape[0], p.ws_bytes(0)):
         return None
     return LinearResidual.apply(x, w, bias, res.contiguous(), drop_p, drop_key, dp_p, dp_key)
 

@@ -269,6 +269,33 @@ def test_case_table_reaches_every_path():
                        for c in ragged), mode
 
 
+def test_conv_problem_record_is_the_abi_argument_block():
+    """ops.ConvProblem, the one place the Python side spells the twelve integers of the conv ABI: built from tensor shapes it IS the
+    argument block of the case (c.args is written out independently above), and in every precision mode, for both directions, each of
+    its host queries answers what the direct library call with *c.args answers at the scratch fs_conv2d_workspace_bytes asks for."""
+    P = fovealseg.ops.ConvProblem
+    for mode in MODES:
+        with precision(mode):
+            for c in CASES:
+                p = P.of((c.B, c.H, c.W, c.Cin), (c.Cout, c.Cin, c.k, c.k), c.stride, c.pad, c.dil)
+                assert tuple(p) == c.args and len(c.args) == 12, (c.id, p)
+                assert p.x_shape == (c.B, c.H, c.W, c.Cin) and p.y_shape == (c.B, c.Ho, c.Wo, c.Cout)
+                assert p.flops == 2.0 * c.B * c.Ho * c.Wo * c.Cout * c.k * c.k * c.Cin
+                assert tuple(p.at_batch(c.B + 3)) == (c.B + 3,) + c.args[1:]
+                assert p.wgrad_ws_bytes() == wgrad_ws_bytes(c), (c.id, mode)
+                for tr in (0, 1):
+                    ws = ws_bytes(c, tr)
+                    assert p.ws_bytes(tr) == ws, (c.id, mode, tr)
+                    assert p.pack_persistent(tr, ws) == persistent(c, tr, ws), (c.id, mode, tr)
+                    assert p.stats_slabs(ws) == int(lib().fs_conv2d_stats_slabs(*c.args, ws)), (c.id, mode, tr)
+                    assert p.bnsum_slabs(ws) == int(lib().fs_conv2d_bwd_data_bnsum_slabs(*c.args, ws)), (c.id, mode, tr)
+                    assert p.affine_act_ok(ws) == (int(lib().fs_conv2d_fwd_affine_act_ok(*c.args, ws)) == 1), (c.id, mode, tr)
+                    for rows in residual_rows(c):
+                        assert p.residual_ok(rows, ws) == (int(lib().fs_conv2d_fwd_residual_ok(*c.args, rows, ws)) == 1), (c.id, mode, tr, rows)
+    assert tuple(P.linear(396, 64, 96)) == (1, 396, 1, 64, 396, 1, 96, 1, 1, 1, 0, 1)
+    assert P.linear(396, 64, 96).flops == 2.0 * 396 * 96 * 64
+
+
 # ================================================================================================
 # data and references: made once per (case, kind), shared by the three modes, never modified
 # ================================================================================================

@@ -31,6 +31,46 @@ def test_library_exports_every_declared_symbol():
     assert exported == declared
 
 
+def _header_signatures():
+    """{name: (result letter, argument letters)} of every `int|long fs_*( ... );` declaration of the header, in hip.SIGNATURES' letters."""
+    src = open(os.path.join(ROOT, "include", "fovealseg.h")).read()
+    src = re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", src, flags=re.S))
+    letters = {"int": "i", "long": "l", "float": "f", "uint32_t": "u", "unsigned": "u", "fs_stream_t": "p"}
+    out = {}
+    for res, name, params in re.findall(r"\b(int|long)\s+(fs_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src):
+        params = [q.strip() for q in params.split(",")]
+        if params in (["void"], [""]):
+            params = []
+        sig = ""
+        for q in params:
+            words = [t for t in q.replace("*", " * ").split() if t != "const"]
+            assert len(words) >= 2, (name, q)                 # a type and a parameter name
+            sig += "p" if "*" in words else letters[" ".join(words[:-1])]
+        assert name not in out, name
+        out[name] = (letters[res], sig)
+    return out
+
+
+def test_ctypes_tables_state_the_headers_parameter_types():
+    """Every parameter TYPE of both binding tables against include/fovealseg.h (test_library_exports_every_declared_symbol compares names
+    only): a `long` bound as `i` would truncate a scratch size, a float bound as `i` would pass garbage, and either still loads and runs."""
+    header = _header_signatures()
+    assert sorted(header) == _header_symbols()                 # the parser saw every declaration
+    assert len(hip.SIGNATURES) >= 98 and len(hip.HOST_ONLY) >= 43
+    for name, sig in hip.SIGNATURES.items():
+        assert header[name] == ("i", sig + "p"), (name, header[name], sig)      # hip.load() appends the trailing stream
+    for name, entry in hip.HOST_ONLY.items():
+        assert header[name] == tuple(entry), (name, header[name], entry)
+    # ... and load() binds what the tables say
+    lib = hip.load()
+    for name, (res, sig) in hip.HOST_ONLY.items():
+        fn = getattr(lib, name)
+        assert fn.restype is hip._CT[res] and list(fn.argtypes) == [hip._CT[c] for c in sig], name
+    for name, sig in hip.SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is hip._I and list(fn.argtypes) == [hip._CT[c] for c in sig] + [hip._P], name
+
+
 def test_stale_library_refuses_to_load(monkeypatch):
     """the library is stamped with a content hash of the sources it was built from, and hip.load() refuses a library whose
     stamp differs from the csrc/ beside it (a shipped .so can never silently be older than its sources)."""
@@ -556,7 +596,7 @@ def test_stash_grad_hands_the_second_reader_gradient_to_the_conv_consumer():
         def forward(ctx, x, k):
             ctx.fan = getattr(x, "_fs_fan", None)
             ctx.k = k
-            ops.FAN_GEOM[ctx.fan[0]] = (tuple(x.shape), (1, 1, 1, 1), 1, 0, 1)      # as ConvBnAct.forward registers the conv consumer
+            ops.FAN_GEOM[ctx.fan[0]] = ops.ConvProblem.of(x.shape, (1, 1, 1, 1), 1, 0)      # as ConvBnAct.forward registers the conv consumer
             return x * k
 
         @staticmethod
@@ -570,7 +610,7 @@ def test_stash_grad_hands_the_second_reader_gradient_to_the_conv_consumer():
     def run(stash_after_conv):
         ops.reset_step_state()
         log.clear()
-        x = torch.arange(8, dtype=torch.float32).view(2, 4).requires_grad_(True)
+        x = torch.arange(8, dtype=torch.float32).view(2, 2, 2, 1).requires_grad_(True)
         h = x * 1.0                                    # a non-leaf, like the encoder's output
         fa, fb = ops.fan_out(h, 2)
         fan = fa._fs_fan
@@ -584,7 +624,7 @@ def test_stash_grad_hands_the_second_reader_gradient_to_the_conv_consumer():
         assert not ops.PENDING_RES
         return x.grad.clone()
 
-    want = 3.0 + 2.0 * torch.arange(8, dtype=torch.float32).view(2, 4)
+    want = 3.0 + 2.0 * torch.arange(8, dtype=torch.float32).view(2, 2, 2, 1)
     ga = run(True)
     assert log == ["conv+addend"], log
     gb = run(False)
@@ -595,7 +635,7 @@ def test_stash_grad_hands_the_second_reader_gradient_to_the_conv_consumer():
     # (c) the other alias is read by something that never looks at PENDING_RES
     def run_without_conv_consumer(geom):
         ops.reset_step_state()
-        x = torch.arange(8, dtype=torch.float32).view(2, 4).requires_grad_(True)
+        x = torch.arange(8, dtype=torch.float32).view(2, 2, 2, 1).requires_grad_(True)
         h = x * 1.0
         fa, fb = ops.fan_out(h, 2)
         fan = fa._fs_fan
@@ -610,4 +650,5 @@ def test_stash_grad_hands_the_second_reader_gradient_to_the_conv_consumer():
         return x.grad.clone()
 
     assert torch.equal(run_without_conv_consumer(None), want)
-    assert torch.equal(run_without_conv_consumer(((2, 8), (1, 1, 1, 1), 1, 0, 1)), want)      # a consumer of a padded copy: other shape
+    padded = ops.ConvProblem.of((2, 2, 2, 16), (1, 16, 1, 1), 1, 0)
+    assert torch.equal(run_without_conv_consumer(padded), want)      # a consumer of a padded copy: other shape
