@@ -53,6 +53,8 @@ SIGNATURES = {
     "fs_unwarp_instances_scored": "pppppppppp" + "iiiiiii",
     "fs_mask_component": "ppppp" + "iiii" + "l",
     "fs_unwarp_instances_component": "p" * 12 + "iiiiiiii" + "l",
+    "fs_mask_erode": "ppp" + "iiii",
+    "fs_mask_pair_counts": "pppp" + "iiii",
     "fs_gate_tiles": "ppp" + "iiii",
     "fs_gate_decide": "ppppppp" + "iiiiiiii" + "ll" + "ii",
     "fs_gate_commit": "pp" + "i" + "p" * 13 + "iiii",
@@ -165,6 +167,8 @@ HOST_ONLY = {
     "fs_mask_component_scratch_ints": ("l", "iii"),
     "fs_mask_component_route": ("i", "iii"),
     "fs_unwarp_instances_component_scratch_ints": ("l", "iiiii"),
+    "fs_mask_erode_scratch_ints": ("l", "iiii"),
+    "fs_mask_pair_scratch_ints": ("l", "iiii"),
 }
 
 

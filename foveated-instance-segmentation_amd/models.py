@@ -5,6 +5,7 @@ with the same constructor/forward signatures, attribute names, return tuples, st
 `feed_dict['seg_label']` side effect (:951), under the effective LVIS-50 configuration
 (SURVEY.md Appendix A).  Branches the default run never takes raise NotImplementedError.
 """
+import math
 import os
 
 import numpy as np
@@ -282,6 +283,46 @@ class DeformSegmentationModule(nn.Module):
         if return_score:
             return ops.unwarp_instances(cls, m, grid, *seg_size, max_runs=max_runs, return_bits=return_bits, score=True)[:-1]
         return ops.unwarp_instances(cls, m, grid, *seg_size, max_runs=max_runs, return_bits=return_bits)
+
+    @torch.no_grad()
+    def evaluate_instances(self, img, focus, seg_label, cls_label, seg_size=None, max_runs=None, component=None, snap_px=None, boundary=0.02):
+        """The instance record scored against the label: predict_instances(..., return_bits=True, return_score=True, component=...),
+        then the counters of mask IoU and Boundary IoU (Cheng et al., CVPR 2021, restated: unpinned) of the record's mask against the
+        label's foreground `seg_label.long() != 0` (evaluate's hausdorff rule), taken on bit words (ops.mask_bits, ops.mask_pair_counts).
+
+        img, focus, max_runs, component and snap_px as predict_instances'; seg_label (B,H,W) or (B,1,H,W) and cls_label (B,) or (B,1)
+        as evaluate's, seg_size defaulting to the label's size and not differing from it.  boundary is the dilation ratio, a finite
+        float > 0: d = ops.boundary_dilation(H, W, boundary), 0.02 of the diagonal.  Returns (cat, stats, counts, conf[, comp], pair):
+        every element but the last is predict_instances' for the same arguments bit for bit (comp exactly when component is given);
+        pair (B,6) int64 = (|p & g|, |p|, |g|, |band(p) & band(g)|, |band(p)|, |band(g)|) of the record's mask p -- the component,
+        with component -- and the label g.  ops.pair_scores makes IoU and Boundary IoU, train.InstanceAPMeter AP and Boundary AP over
+        a dataset (cls_label is that meter's; here only its batch size is checked).  Nothing of (B,H,W) wider than a bit a pixel is
+        allocated beyond the label's bool mask.  Eval mode only, no host read, no argument written to, nothing in the module changes."""
+        if isinstance(boundary, bool) or not isinstance(boundary, float) or not (boundary > 0.0) or math.isinf(boundary):
+            raise ValueError(f"boundary must be a finite float > 0, got {boundary!r}")
+        if component is None:
+            if snap_px is not None:
+                raise ValueError("snap_px goes with component = 4 or 8")
+        else:
+            ops._component_args(component, snap_px)
+        if seg_label.dim() not in (3, 4) or (seg_label.dim() == 4 and seg_label.shape[1] != 1):
+            raise ValueError(f"seg_label must be (B,H,W) or (B,1,H,W), got {tuple(seg_label.shape)}")
+        label_size = (int(seg_label.shape[-2]), int(seg_label.shape[-1]))
+        if seg_size is not None and (len(seg_size) != 2 or (int(seg_size[0]), int(seg_size[1])) != label_size):
+            raise ValueError(f"seg_size {tuple(seg_size)} differs from the label's size {label_size}: the counters are taken pixel against pixel")
+        if seg_label.shape[0] != img.shape[0] or cls_label.shape[0] != img.shape[0]:
+            raise ValueError(f"seg_label {tuple(seg_label.shape)} and cls_label {tuple(cls_label.shape)} must have img's batch size {img.shape[0]}")
+        d = ops.boundary_dilation(*label_size, boundary)
+        if d > ops.MORPH_MAX_D:
+            raise ValueError(f"boundary {boundary!r} gives a dilation of {d} pixels at {label_size}, above ops.MORPH_MAX_D = {ops.MORPH_MAX_D}")
+        out = self.predict_instances(img, focus, label_size, max_runs=max_runs, return_bits=True, return_score=True, component=component,
+                                     snap_px=snap_px)
+        bits = out[3]
+        y = seg_label.reshape(seg_label.shape[0], *label_size)
+        # seg_label.long() != 0 without the int64 copy: truncation towards 0 keeps what is at least 1 in magnitude (NaN: unset)
+        label = ops.mask_bits((y >= 1) | (y <= -1) if y.is_floating_point() else y != 0)
+        pair = ops.mask_pair_counts(bits, label, d, Ws=label_size[1])
+        return out[:3] + out[4:] + (pair,)
 
     @torch.no_grad()
     def evaluate(self, img, focus, seg_label, cls_label, seg_size=None, return_labels=False, class_areas=False, hausdorff=None, trimap=None, trimap_frame=True):

@@ -1659,6 +1659,109 @@ def mask_component(mask_or_bits, focus, Ws=None, connectivity=8, snap_px=None):
     return out, comp
 
 
+def boundary_dilation(Hs, Ws, ratio=0.02):
+    """The dilation of Boundary IoU in pixels (Cheng et al., CVPR 2021, restated: unpinned): d = max(1, int(round(ratio *
+    math.sqrt(Hs * Hs + Ws * Ws)))) in Python floats, ratio a finite float > 0 -- 0.02 of the image diagonal, 29 at 1024 x 1024."""
+    if isinstance(Hs, bool) or isinstance(Ws, bool) or int(Hs) != Hs or int(Ws) != Ws or int(Hs) < 1 or int(Ws) < 1:
+        raise ValueError(f"the size must be two integers >= 1, got {(Hs, Ws)!r}")
+    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not (float(ratio) > 0.0) or math.isinf(float(ratio)):
+        raise ValueError(f"the boundary ratio must be a finite number > 0, got {ratio!r}")
+    Hs, Ws = int(Hs), int(Ws)
+    return max(1, int(round(float(ratio) * math.sqrt(Hs * Hs + Ws * Ws))))
+
+
+MORPH_MAX_D = 2047                                  # fs_mask_erode's cap: a diagonal of 100 000 pixels at the default ratio
+
+
+def _morph_d(d):
+    if isinstance(d, bool) or not isinstance(d, int) or d < 1 or d > MORPH_MAX_D:
+        raise ValueError(f"d must be an int 1 .. {MORPH_MAX_D}, got {d!r}")
+    return d
+
+
+def _bits_arg(mask_or_bits, Ws):
+    """(bits (B,Hs,P) int32, Ws) of a mask argument as mask_rle / mask_component take it."""
+    if not isinstance(mask_or_bits, torch.Tensor):
+        raise ValueError("the mask must be a tensor: bool / uint8 (B,Hs,Ws) or (Hs,Ws), or int32 bit words with Ws")
+    if mask_or_bits.dtype == torch.int32:
+        bits = mask_or_bits
+        if bits.dim() != 3 or bits.numel() == 0 or Ws is None or int(Ws) < 1 or bits.shape[2] != (int(Ws) + 31) // 32:
+            raise ValueError(f"bit words {tuple(bits.shape)} must be a non-empty (B, Hs, ceil(Ws / 32)) with Ws given, got Ws = {Ws!r}")
+        return bits, int(Ws)
+    if mask_or_bits.dtype not in (torch.bool, torch.uint8) or mask_or_bits.dim() not in (2, 3) or mask_or_bits.numel() == 0:
+        raise ValueError(f"the mask must be a non-empty bool / uint8 (B,Hs,Ws) or (Hs,Ws), got {mask_or_bits.dtype} {tuple(mask_or_bits.shape)}")
+    if Ws is not None and int(Ws) != mask_or_bits.shape[-1]:
+        raise ValueError(f"Ws = {Ws!r} differs from the mask's width {mask_or_bits.shape[-1]}")
+    return None, int(mask_or_bits.shape[-1])
+
+
+def mask_erode(mask_or_bits, d, Ws=None):
+    """Erosion of a mask by a (2d+1) x (2d+1) square, on the device and on bit words (fs_mask_erode; no autograd; unpinned: restated
+    from the published definition of Boundary IoU).  The mask as mask_rle takes it: bool / uint8 (B,Hs,Ws) or (Hs,Ws), or int32 bit
+    words (B,Hs,ceil(Ws/32)) together with Ws; d an int >= 1 (and <= 2047), not a bool.  Returns bits (B,Hs,ceil(Ws/32)) int32: pixel
+    (y,x) is set iff every pixel of the square centred on it is set, every pixel outside the image counting as unset -- scipy's
+    binary_erosion(m, ones((3,3)), iterations=d, border_value=0); all 0 where 2d+1 exceeds a side."""
+    d = _morph_d(d)
+    bits, Ws = _bits_arg(mask_or_bits, Ws)
+    if bits is None:
+        bits = mask_bits(mask_or_bits)
+    B, Hs = int(bits.shape[0]), int(bits.shape[1])
+    out = torch.empty_like(bits, memory_format=torch.contiguous_format)
+    scratch = torch.empty(max(1, hip.query("fs_mask_erode_scratch_ints", B, Hs, Ws, d)), device=bits.device, dtype=torch.int32)
+    hip.call("fs_mask_erode", hip.ptr(bits.contiguous()), hip.ptr(out), hip.ptr(scratch), B, Hs, Ws, d)
+    return out
+
+
+def mask_boundary(mask_or_bits, d, Ws=None):
+    """The boundary band of Boundary IoU as bit words: m & ~mask_erode(m, d), the set pixels within d of an unset pixel or of the
+    image's outside (chessboard distance); the mask itself where 2d+1 exceeds a side.  Arguments as mask_erode's; the bits at
+    x >= Ws of the result are 0."""
+    d = _morph_d(d)
+    bits, Ws = _bits_arg(mask_or_bits, Ws)
+    if bits is None:
+        bits = mask_bits(mask_or_bits)
+    er = mask_erode(bits, d, Ws)
+    band = bits & ~er
+    if Ws & 31:
+        band[:, :, -1] &= (1 << (Ws & 31)) - 1                      # the input's padding bits are no pixels
+    return band
+
+
+def mask_pair_counts(a, b, d, Ws=None):
+    """The counters of mask IoU and Boundary IoU of a prediction a and a label b (fs_mask_pair_counts; no autograd; unpinned).  a and
+    b as mask_erode takes a mask, of one shape and kind; d as there.  Returns pair (B,6) int64 = (|a & b|, |a|, |b|, |band(a) &
+    band(b)|, |band(a)|, |band(b)|), band = mask_boundary's; both erosions and the counts are taken on the device without a host
+    read, on nothing wider than a bit a pixel.  pair_scores makes the two measures."""
+    d = _morph_d(d)
+    abits, Wa = _bits_arg(a, Ws)
+    bbits, Wb = _bits_arg(b, Ws)
+    if (abits is None) != (bbits is None) or tuple(a.shape[-2:]) != tuple(b.shape[-2:]) or Wa != Wb or a.device != b.device:
+        raise ValueError(f"the two masks must be of one kind, size and device, got {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}")
+    if abits is None:
+        if (a.dim() == 3 and b.dim() == 3 and a.shape[0] != b.shape[0]) or a.dim() != b.dim():
+            raise ValueError(f"the two masks must have one batch size, got {tuple(a.shape)} and {tuple(b.shape)}")
+        abits, bbits = mask_bits(a), mask_bits(b)
+    elif a.shape[0] != b.shape[0]:
+        raise ValueError(f"the two masks must have one batch size, got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, Hs = int(abits.shape[0]), int(abits.shape[1])
+    pair = torch.empty(B, 6, device=abits.device, dtype=torch.int64)
+    scratch = torch.empty(max(1, hip.query("fs_mask_pair_scratch_ints", B, Hs, Wa, d)), device=abits.device, dtype=torch.int32)
+    hip.call("fs_mask_pair_counts", hip.ptr(abits.contiguous()), hip.ptr(bbits.contiguous()), hip.ptr(pair), hip.ptr(scratch), B, Hs, Wa, d)
+    return pair
+
+
+def pair_scores(pair):
+    """(iou, biou), two fp64 tensors (B,), from mask_pair_counts' counters: n / (a + b - n) per triple, 0 where the union is 0."""
+    if pair.dim() != 2 or pair.shape[1] != 6:
+        raise ValueError(f"pair must be (B, 6), got {tuple(pair.shape)}")
+    p = pair.to(torch.int64)
+    out = []
+    for o in (0, 3):
+        n, u = p[:, o], p[:, o + 1] + p[:, o + 2] - p[:, o]
+        out.append(torch.where(u > 0, n.double() / u.clamp(min=1).double(), torch.zeros_like(n, dtype=torch.float64)))
+    return out[0], out[1]
+
+
 def head_fg_q(cls, m):
     """The C1 head's foreground probability per grid point as an integer table (fs_head_fg_q; no autograd; unpinned: the reference
     has no counterpart).  cls (B,K), m (B,h,w).  Returns q (B, h*w+1) int32 = rint(P * 2^24): P is the softmax mass of the classes

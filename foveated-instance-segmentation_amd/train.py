@@ -10,6 +10,7 @@ its parameters (params are views into it, conv weights keep RSCK strides), one f
 and flat Adam moments, so a step is one fused HIP kernel and the data-parallel exchange is one RCCL
 all-reduce per arena (4 per step, 522 MB total) instead of DDP's ~20 x 25 MB buckets.
 """
+import math
 import os
 
 import torch
@@ -628,6 +629,124 @@ class HausdorffMeter:
         tot = tot.cpu().tolist()
         return {"hd": tot[0] / tot[1] if tot[1] > 0 else float("nan"), "images": int(tot[1]), "skipped_empty_pred": int(tot[2]),
                 "skipped_empty_label": int(tot[3]), "q": self.q}
+
+
+class InstanceAPMeter:
+    """Dataset-level AP and Boundary AP of the instance records (module.evaluate_instances / ops.mask_pair_counts): what a COCO / LVIS
+    evaluator reports, restated from COCOeval's published algorithm for this task's shape -- one label instance and at most one record
+    an image (unpinned: the reference has no instance metric; Boundary AP is Cheng et al., CVPR 2021).  `update(cat, conf, stats, pair,
+    cls_label)` keeps one row an image ON the device -- ten int64: cat, cls_label, area, the six counters, and the bits of the fp32
+    score -- without a host read; `result(reduce=True)` exchanges the row counts over the ranks, runs ONE padded all_gather, puts the
+    ranks' rows one behind the other in rank order, makes ONE host read and computes in int64 / fp64 on the host:
+
+    a record exists iff its area > 0, a label instance iff |g| > 0 (its class is cls_label).  Per class k and threshold t = (50 + 5 j)
+    / 100, j = 0 .. 9: the records with cat == k in descending score (ties in insertion order, a NaN score last); a record is a TP iff
+    its image's label instance exists, has class k and the measure passes t -- in integers, 100 n >= (50 + 5 j) u with u = a + b - n > 0
+    -- else an FP; recall cumTP / nGT_k and precision cumTP / (cumTP + cumFP), precision made non-increasing from the right and sampled
+    at the 101 recalls q / 100 (the first rank with 100 cumTP >= q nGT_k; 0 past the end); AP_kj is the mean of the samples.  `AP`,
+    `AP50`, `AP75` average over the classes with nGT_k > 0 (AP also over j; nan without such a class), the measure being mask IoU;
+    `bAP`, `bAP50`, `bAP75` take min(mask IoU, Boundary IoU): both comparisons must hold.  Beside them `mIoU` and `mBIoU`, the means
+    of the two measures over the images whose label instance exists (a missing record counts 0), `cls_acc`, the share of images with
+    cat == cls_label, `n_images` and `n_records`."""
+
+    ROW = 10
+
+    def __init__(self, device, num_class):
+        self.num_class = int(num_class)
+        if self.num_class < 2:
+            raise ValueError(f"num_class must be at least 2, got {num_class}")
+        self.device = torch.device(device)
+        self.rows = []                                                           # one (B, ROW) int64 tensor a batch, on the device
+
+    def update(self, cat, conf, stats, pair, cls_label):
+        B = int(cat.shape[0])
+        if tuple(conf.shape) != (B, 3) or stats.dim() != 2 or stats.shape[0] != B or tuple(pair.shape) != (B, 6) or cls_label.shape[0] != B \
+                or cls_label.numel() != B:
+            raise ValueError(f"cat (B,), conf (B,3), stats (B,6), pair (B,6) and cls_label (B,) or (B,1) must share B, got {tuple(cat.shape)}, "
+                             f"{tuple(conf.shape)}, {tuple(stats.shape)}, {tuple(pair.shape)}, {tuple(cls_label.shape)}")
+        dev = self.device
+        score = conf[:, 0].to(device=dev, dtype=torch.float32).contiguous().view(torch.int32).to(torch.int64)
+        row = torch.cat([cat.to(device=dev, dtype=torch.int64).reshape(B, 1), cls_label.to(device=dev, dtype=torch.int64).reshape(B, 1),
+                         stats[:, :1].to(device=dev, dtype=torch.int64), pair.to(device=dev, dtype=torch.int64), score.reshape(B, 1)], 1)
+        self.rows.append(row)
+
+    def gathered(self, reduce=True):
+        """The rows of every rank, rank after rank, as a host int64 tensor (n, ROW)."""
+        mine = torch.cat(self.rows, 0) if self.rows else torch.zeros(0, self.ROW, device=self.device, dtype=torch.int64)
+        if reduce and dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            world = dist.get_world_size()
+            n = torch.tensor([mine.shape[0]], device=self.device, dtype=torch.int64)
+            counts = [torch.zeros_like(n) for _ in range(world)]
+            dist.all_gather(counts, n)
+            counts = [int(c) for c in torch.cat(counts).cpu().tolist()]
+            cap = max(max(counts), 1)
+            padded = torch.zeros(cap, self.ROW, device=self.device, dtype=torch.int64)
+            padded[:mine.shape[0]] = mine
+            parts = [torch.zeros_like(padded) for _ in range(world)]
+            dist.all_gather(parts, padded)
+            mine = torch.cat([p[:c] for p, c in zip(parts, counts)], 0)
+        return mine.cpu()
+
+    @staticmethod
+    def _passes(n, a, b, t100):
+        u = a + b - n
+        return (u > 0) & (100 * n >= t100 * u)
+
+    def result(self, reduce=True):
+        import numpy as np
+        rows = self.gathered(reduce).numpy()
+        cat, cls, area, pair = rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3:9]
+        score = rows[:, 9].astype(np.int32).view(np.float32).astype(np.float64)
+        key = np.where(np.isnan(score), -np.inf, score)
+        has_gt, has_rec = pair[:, 2] > 0, area > 0
+        nan = float("nan")
+        res = {}
+        aps = {(b, t): [] for b in (0, 1) for t in range(10)}
+        for k in range(self.num_class):
+            n_gt = int((has_gt & (cls == k)).sum())
+            if n_gt == 0:
+                continue
+            sel = np.nonzero(has_rec & (cat == k))[0]
+            sel = sel[np.argsort(-key[sel], kind="stable")]                      # descending score, ties in insertion order
+            p = pair[sel]
+            right = has_gt[sel] & (cls[sel] == k)
+            for j in range(10):
+                mask_ok = right & self._passes(p[:, 0], p[:, 1], p[:, 2], 50 + 5 * j)
+                for b, ok in ((0, mask_ok), (1, mask_ok & self._passes(p[:, 3], p[:, 4], p[:, 5], 50 + 5 * j))):
+                    tp = np.cumsum(ok.astype(np.int64))
+                    seen = np.arange(1, len(sel) + 1, dtype=np.int64)
+                    prec = tp / seen
+                    if len(prec):
+                        prec = np.maximum.accumulate(prec[::-1])[::-1]
+                    at = np.searchsorted(100 * tp, np.arange(101, dtype=np.int64) * n_gt, side="left")
+                    samples = [float(prec[i]) if i < len(prec) else 0.0 for i in at.tolist()]
+                    aps[(b, j)].append(math.fsum(samples) / 101)
+        for b, name in ((0, "AP"), (1, "bAP")):
+            every = [v for j in range(10) for v in aps[(b, j)]]
+            res[name] = math.fsum(every) / len(every) if every else nan
+            for j, tag in ((0, "50"), (5, "75")):
+                res[name + tag] = math.fsum(aps[(b, j)]) / len(aps[(b, j)]) if aps[(b, j)] else nan
+        g = pair[has_gt]
+        for name, o in (("mIoU", 0), ("mBIoU", 3)):
+            u = g[:, o + 1] + g[:, o + 2] - g[:, o]
+            vals = [int(n) / int(uu) if uu > 0 else 0.0 for n, uu in zip(g[:, o].tolist(), u.tolist())]
+            res[name] = math.fsum(vals) / len(vals) if vals else nan
+        res["n_images"], res["n_records"] = int(len(rows)), int(has_rec.sum())
+        res["cls_acc"] = int((cat == cls).sum()) / len(rows) if len(rows) else nan
+        return res
+
+
+@torch.no_grad()
+def evaluate_instances_step(module, batch, meter=None, **kw):
+    """evaluate_step's counterpart for the instance record: module.evaluate_instances on (X, Fp, Y, cls) with **kw (component, snap_px,
+    boundary, max_runs, seg_size) (module.eval() by caller).  Returns its (cat, stats, counts, conf[, comp], pair); an InstanceAPMeter
+    given as `meter` takes (cat, conf, stats, pair, cls) -- no host read."""
+    X, Fp, Y, cls = batch
+    out = module.evaluate_instances(X[:, :3], Fp, Y, cls, **kw)
+    module.check_nan()
+    if meter is not None:
+        meter.update(out[0], out[3], out[1], out[-1], cls)
+    return out
 
 
 # ----------------------------------------------------------------------------------------------

@@ -254,6 +254,28 @@ long fs_mask_component_scratch_ints(int B, int Hs, int Ws);
 int fs_mask_component_route(int B, int Hs, int Ws);
 int fs_mask_component(const unsigned int* bits, const float* focus, unsigned int* out, long long* comp, int* scratch, int B, int Hs,
                       int Ws, int conn, long snap2, fs_stream_t stream);
+/* Erosion of a bit mask by a (2d+1) x (2d+1) square (no counterpart in the reference: UNPINNED, restated from the published definition
+ * of Boundary IoU, Cheng et al., CVPR 2021: copyMakeBorder(0) + erode(3x3, iterations = d)).  All integers, on bit
+ * words.  bits (B,Hs,P), P = ceil(Ws/32), as fs_mask_bits lays them out (the bits at x >= Ws are not read as pixels).  out (B,Hs,P):
+ * bit (y,x) is set iff every pixel of the square centred on (y,x) is set, every pixel outside the image counting as unset; the bits at
+ * x >= Ws always 0; out may not be bits.  2d+1 above a side is legal and gives the empty erosion.  The boundary band of Boundary IoU is
+ * bits & ~out.  A rows pass then a columns pass, each an AND over 2d+1 neighbours built by doubling in LDS (O(log d) steps), the plane
+ * between them in scratch = fs_mask_erode_scratch_ints(B, Hs, Ws, d) ints (0 for sizes that are refused), any 4-byte alignment; its
+ * contents after the call are unspecified.  FS_ERR_ARG, with nothing launched, for a null pointer, out == bits, non-positive sizes, a
+ * side above 16384, Hs * Ws >= 2^31, d < 1 or d > 2047. */
+long fs_mask_erode_scratch_ints(int B, int Hs, int Ws, int d);
+int fs_mask_erode(const unsigned int* bits, unsigned int* out, int* scratch, int B, int Hs, int Ws, int d, fs_stream_t stream);
+/* The counters of mask IoU and Boundary IoU of two bit masks (UNPINNED, as fs_mask_erode).  a, b (B,Hs,P) as fs_mask_bits lays them out
+ * (the bits at x >= Ws are not read; a may be b).  With the band of a mask m, band(m) = m & ~E_d(m), E_d fs_mask_erode's, pair (B,6)
+ * int64 = (|a & b|, |a|, |b|, |band(a) & band(b)|, |band(a)|, |band(b)|); with 2d+1 above a side the bands are the masks.  Both
+ * erosions and the popcounts run with no host read in between; the popcounts are reduced by shuffles into one record a workgroup,
+ * added per image in index order (no atomics: the same numbers in every order of execution).  scratch =
+ * fs_mask_pair_scratch_ints(B, Hs, Ws, d) ints (four bit planes an image and the records; 0 for sizes that are refused), any 4-byte
+ * alignment; its contents after the call are unspecified.  FS_ERR_ARG, with nothing launched, for a null pointer and as fs_mask_erode
+ * for the sizes and d. */
+long fs_mask_pair_scratch_ints(int B, int Hs, int Ws, int d);
+int fs_mask_pair_counts(const unsigned int* a, const unsigned int* b, long long* pair, int* scratch, int B, int Hs, int Ws, int d,
+                        fs_stream_t stream);
 /* fs_unwarp_instances / fs_unwarp_instances_scored with the record describing the component under the gaze instead of every foreground
  * pixel (no counterpart in the reference: UNPINNED).  The decide / owner / fill passes and the bit gather are fs_unwarp_instances';
  * with conf the gather is still the unscored one -- the words are the same, and the scored gather's sums over the whole mask would be
