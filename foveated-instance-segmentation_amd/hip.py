@@ -58,6 +58,11 @@ SIGNATURES = {
     "fs_gate_tiles": "ppp" + "iiii",
     "fs_gate_decide": "ppppppp" + "iiiiiiii" + "ll" + "ii",
     "fs_gate_commit": "pp" + "i" + "p" * 13 + "iiii",
+    "fs_frame_profiles": "pp" + "iii",
+    "fs_key_profiles": "pp" + "iii",
+    "fs_profile_shift": "pppp" + "iiiii",
+    "fs_state_shift": "p" * 13 + "iiii",
+    "fs_motion_commit": "p" + "i" + "ppp" + "iii",
     "fs_conv2d_fwd": "ppppiiiiiiiiiiiifuplp",
     "fs_conv2d_fwd_residual": "ppppp" + "iiiiiiiiiiii" + "fufu" + "l" + "plp",
     "fs_conv2d_fwd_stats": "pppppiiiiiiiiiiiifuplp",
@@ -169,6 +174,7 @@ HOST_ONLY = {
     "fs_unwarp_instances_component_scratch_ints": ("l", "iiiii"),
     "fs_mask_erode_scratch_ints": ("l", "iiii"),
     "fs_mask_pair_scratch_ints": ("l", "iiii"),
+    "fs_state_shift_scratch_ints": ("l", "iiii"),
 }
 
 

@@ -6,6 +6,7 @@ reference's logical (Cout,Cin,R,S) shape with RSCK strides, so `w.permute(2,3,1,
 """
 import ctypes
 import math
+import operator
 import os
 import weakref
 import zlib
@@ -1969,6 +1970,160 @@ def gate_commit(img, idx, key, gstate, focus, src, dst):
     sp = [hip.ptr(s) for s in src] + [None] * (5 - len(src))
     dp = [hip.ptr(d) for d in dst] + [None] * (5 - len(dst))
     hip.call("fs_gate_commit", hip.ptr(img), hip.ptr(idx), n, hip.ptr(key), hip.ptr(gstate), hip.ptr(focus), *sp, *dp, B, H, W, cap)
+
+
+MOTION_MAX_PX = 255                                 # fs_profile_shift's largest search range
+
+
+def _index_or_none(v):
+    """v as an int where it is an integer of any integer type (no bool, no float), else None."""
+    if isinstance(v, bool):
+        return None
+    try:
+        return operator.index(v)
+    except TypeError:
+        return None
+
+
+def _motion_px(motion_px, H, W):
+    """The search range R of the motion estimate: an integer 1 .. 255 with 4 R < min(H, W)."""
+    R = _index_or_none(motion_px)
+    if R is None or not 1 <= R <= MOTION_MAX_PX or 4 * R >= min(int(H), int(W)):
+        raise ValueError(f"motion_px must be an integer 1 .. {MOTION_MAX_PX} with 4 * motion_px < min(H, W) = {min(int(H), int(W))}, got {motion_px!r}")
+    if 8 * max(int(H), int(W)) + 8 * (2 * R + 1) > 65536:
+        raise ValueError(f"a side of {max(int(H), int(W))} pixels with motion_px = {R} is beyond the estimate's 64 KiB of LDS")
+    return R
+
+
+def _motion_gain(gain):
+    g = _index_or_none(gain)
+    if g is None or not 0 <= g <= 8:
+        raise ValueError(f"motion_gain must be an integer 0 .. 8, got {gain!r}")
+    return g
+
+
+def _profile_sizes(B, H, W):
+    if 765 * max(H, W) >= 2 ** 31 or H * W >= 2 ** 31:
+        raise ValueError(f"a frame of {H} x {W} pixels is beyond int32 profiles")
+    return (B, H + W)
+
+
+def _profiles(name, src, dtype, out):
+    if not isinstance(src, torch.Tensor) or src.dim() != 4 or src.shape[1] != 3 or src.numel() == 0 or src.dtype != dtype:
+        raise ValueError(f"the frames must be a non-empty {dtype} (B,3,H,W), got {getattr(src, 'dtype', None)} {tuple(getattr(src, 'shape', ()))}")
+    B, _, H, W = (int(v) for v in src.shape)
+    shape = _profile_sizes(B, H, W)
+    if out is None:
+        out = torch.empty(shape, device=src.device, dtype=torch.int32)
+    elif out.dtype != torch.int32 or tuple(out.shape) != shape:
+        raise ValueError(f"out must be int32 {shape}, got {out.dtype} {tuple(out.shape)}")
+    hip.call(name, hip.ptr(src), hip.ptr(out), B, H, W)
+    return out
+
+
+def frame_profiles(img, out=None):
+    """The integral projections of frames (fs_frame_profiles; no autograd; unpinned: the reference has no counterpart).  img (B,3,H,W)
+    fp32.  Returns prof (B, H + W) int32: prof[b, :H] = the row sums and prof[b, H:] = the column sums of the luma code L = q_r + q_g +
+    q_b, q the gate's pixel code (gate_tiles).  out: a (B, H + W) int32 tensor to write into."""
+    return _profiles("fs_frame_profiles", img, torch.float32, out)
+
+
+def key_profiles(key, out=None):
+    """frame_profiles of 8-bit key frames (fs_key_profiles): key (B,3,H,W) uint8.  The profiles of a frame and of the key gate_commit
+    made from it are equal."""
+    return _profiles("fs_key_profiles", key, torch.uint8, out)
+
+
+def profile_shift(prof, prof_key, gstate, frame_size, motion_px, motion_gain=6, out=None):
+    """The integer translation of every viewer against its key frame (fs_profile_shift; no autograd; unpinned).  prof, prof_key (B, H +
+    W) int32 as frame_profiles / key_profiles make them; gstate (B,6) int64 the gate's; frame_size = (H, W); motion_px = R, the search
+    range.  Per axis cost(s) = sum_{i=R}^{n-1-R} |P[i] - K[i - s]|; the least cost wins, ties to the smaller |s|, then to the negative s,
+    and the shift is taken only if cost(s) * 8 <= cost(0) * motion_gain.  Returns shift (B,4) int64 = (dy, dx, cost_best, cost_zero),
+    all 0 for a viewer without a record."""
+    H, W = int(frame_size[0]), int(frame_size[1])
+    R, gain = _motion_px(motion_px, H, W), _motion_gain(motion_gain)
+    if not isinstance(prof, torch.Tensor) or prof.dim() != 2 or prof.dtype != torch.int32 or prof.shape[1] != H + W or prof.shape[0] < 1:
+        raise ValueError(f"prof must be int32 (B, H + W) = (B, {H + W}), got {getattr(prof, 'dtype', None)} {tuple(getattr(prof, 'shape', ()))}")
+    B = int(prof.shape[0])
+    _profile_sizes(B, H, W)
+    if prof_key.dtype != torch.int32 or prof_key.shape != prof.shape:
+        raise ValueError(f"prof_key must be int32 {tuple(prof.shape)}, got {prof_key.dtype} {tuple(prof_key.shape)}")
+    if gstate.dtype != torch.int64 or tuple(gstate.shape) != (B, 6):
+        raise ValueError(f"gstate must be int64 ({B}, 6), got {gstate.dtype} {tuple(gstate.shape)}")
+    if out is None:
+        out = torch.empty(B, 4, device=prof.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (B, 4):
+        raise ValueError(f"out must be int64 ({B}, 4), got {out.dtype} {tuple(out.shape)}")
+    hip.call("fs_profile_shift", hip.ptr(prof), hip.ptr(prof_key), hip.ptr(gstate), hip.ptr(out), B, H, W, R, gain)
+    return out
+
+
+def state_shift_scratch(B, H, W, cap, device):
+    """The scratch tensor state_shift wants for these sizes (fs_state_shift_scratch_ints ints)."""
+    return torch.empty(hip.query("fs_state_shift_scratch_ints", int(B), int(H), int(W), int(cap)), device=device, dtype=torch.int32)
+
+
+def state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion=None, scratch=None):
+    """Move the state of every viewer whose shift is not (0, 0), in place (fs_state_shift; no autograd; unpinned).  img (B,3,H,W) fp32
+    the new frames; shift (B,4) int64 as profile_shift returns it; key (B,3,H,W) uint8 and bits (B,H,ceil(W/32)) int32 are moved by (dy,
+    dx) -- the key's uncovered border is filled with q(img), the mask's with 0 -- through the spare buffers key2 and bits2 of the same
+    shapes, whose contents afterwards are unspecified; the four gaze coordinates of gstate (B,6) int64 move by 16 * d, clamped; stats
+    (B,6) int64 and counts (B,cap) int32 become mask_rle's of the moved bits; prof_key (B, H + W) int32 becomes key_profiles of the
+    moved key; mstate (B,4) int64 = (dy_total, dx_total, moves, path) grows.  A still viewer's rows are not written.  Returns motion
+    (B,6) int64 = (dy, dx, cost_best, cost_zero, dy_total, dx_total), written for every viewer.  scratch: state_shift_scratch(...)."""
+    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != torch.float32:
+        raise ValueError(f"img must be a non-empty fp32 (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
+    B, _, H, W = (int(v) for v in img.shape)
+    _profile_sizes(B, H, W)
+    P = (W + 31) // 32
+    for name, k in (("key", key), ("key2", key2)):
+        if k.dtype != torch.uint8 or k.shape != img.shape:
+            raise ValueError(f"{name} must be uint8 {tuple(img.shape)}, got {k.dtype} {tuple(k.shape)}")
+    for name, w in (("bits", bits), ("bits2", bits2)):
+        if w.dtype != torch.int32 or tuple(w.shape) != (B, H, P):
+            raise ValueError(f"{name} must be int32 {(B, H, P)}, got {w.dtype} {tuple(w.shape)}")
+    if key2.data_ptr() == key.data_ptr() or bits2.data_ptr() == bits.data_ptr():
+        raise ValueError("key2 and bits2 must be buffers of their own: the move does not read what it writes")
+    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[0] != B or counts.shape[1] < 1:
+        raise ValueError(f"counts must be int32 ({B}, cap), got {counts.dtype} {tuple(counts.shape)}")
+    cap = int(counts.shape[1])
+    for name, t, tail in (("shift", shift, (4,)), ("gstate", gstate, (6,)), ("stats", stats, (6,)), ("mstate", mstate, (4,))):
+        if t.dtype != torch.int64 or tuple(t.shape) != (B,) + tail:
+            raise ValueError(f"{name} must be int64 {(B,) + tail}, got {t.dtype} {tuple(t.shape)}")
+    if prof_key.dtype != torch.int32 or tuple(prof_key.shape) != (B, H + W):
+        raise ValueError(f"prof_key must be int32 {(B, H + W)}, got {prof_key.dtype} {tuple(prof_key.shape)}")
+    if motion is None:
+        motion = torch.empty(B, 6, device=img.device, dtype=torch.int64)
+    elif motion.dtype != torch.int64 or tuple(motion.shape) != (B, 6):
+        raise ValueError(f"motion must be int64 ({B}, 6), got {motion.dtype} {tuple(motion.shape)}")
+    need = hip.query("fs_state_shift_scratch_ints", B, H, W, cap)
+    if scratch is None:
+        scratch = torch.empty(need, device=img.device, dtype=torch.int32)
+    elif scratch.dtype != torch.int32 or scratch.dim() != 1 or scratch.numel() < need:
+        raise ValueError(f"scratch must be int32 with at least {need} entries, got {scratch.dtype} {tuple(scratch.shape)}")
+    hip.call("fs_state_shift", hip.ptr(img), hip.ptr(shift), hip.ptr(key), hip.ptr(key2), hip.ptr(bits), hip.ptr(bits2), hip.ptr(gstate),
+             hip.ptr(stats), hip.ptr(counts), hip.ptr(prof_key), hip.ptr(mstate), hip.ptr(motion), hip.ptr(scratch), B, H, W, cap)
+    return motion
+
+
+def motion_commit(idx, prof, prof_key, mstate, frame_size):
+    """What a step leaves behind for the motion estimate (fs_motion_commit; no autograd; unpinned), in place, after gate_commit: for the
+    viewers of idx (int32 (n,) ascending, or None) prof_key (B, H + W) int32 <- prof, this step's frame_profiles, and mstate (B,4) int64
+    <- 0.  frame_size = (H, W)."""
+    H, W = int(frame_size[0]), int(frame_size[1])
+    if not isinstance(prof, torch.Tensor) or prof.dim() != 2 or prof.dtype != torch.int32 or prof.shape[1] != H + W or prof.shape[0] < 1:
+        raise ValueError(f"prof must be int32 (B, H + W) = (B, {H + W}), got {getattr(prof, 'dtype', None)} {tuple(getattr(prof, 'shape', ()))}")
+    B = int(prof.shape[0])
+    _profile_sizes(B, H, W)
+    n = 0 if idx is None else int(idx.shape[0])
+    if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 1 or n > B):
+        raise ValueError(f"idx must be int32 (n,) with n <= {B}, got {idx.dtype} {tuple(idx.shape)}")
+    if prof_key.dtype != torch.int32 or prof_key.shape != prof.shape:
+        raise ValueError(f"prof_key must be int32 {tuple(prof.shape)}, got {prof_key.dtype} {tuple(prof_key.shape)}")
+    if mstate.dtype != torch.int64 or tuple(mstate.shape) != (B, 4):
+        raise ValueError(f"mstate must be int64 ({B}, 4), got {mstate.dtype} {tuple(mstate.shape)}")
+    if n:
+        hip.call("fs_motion_commit", hip.ptr(idx), n, hip.ptr(prof), hip.ptr(prof_key), hip.ptr(mstate), B, H, W)
 
 
 def _hd_q(q):

@@ -49,14 +49,24 @@ class GazeSession:
     it: its box, the region of interest grown from it and the inside bit are read from the record's stats and bits, so they follow the
     component; a gaze that lands on another blob the head also marked is then outside the record's mask and re-makes it (RUN_GAZE).
 
+    motion_px (None): an integer R >= 1 switches global motion compensation on, for a camera that translates (a head-mounted one):
+    before the gate looks, every step estimates an integer shift (dy, dx) in [-R, R]^2 per viewer from the integral projections of the
+    new frame against the key frame's (ops.frame_profiles, profile_shift) and moves the viewer's state by it -- key frame, mask, key
+    and previous gaze, stats / counts re-encoded (ops.state_shift).  The unchanged gate then verifies the move: a wrong estimate shows
+    as changed tiles and the record is re-made as before.  cat and conf are not touched: mask_prob keeps describing the pixels the
+    record was made from.  motion_gain (6), an integer 0 .. 8: a shift is taken only if its cost is at most motion_gain / 8 of the
+    cost of standing still.  Needs 4 * R < min(H, W), R <= 255, and a second key buffer: 3 * H * W bytes a viewer more (201 MB at B =
+    64, 1024 x 1024).  With motion_px the step returns one more element, motion.
+
     These defaults are this library's choices.  They have not been validated on real gaze data: tune them on recordings of the
     headset and scenes you serve.
 
-    step(img, focus, force=None) returns (cat, stats, counts, bits[, conf], gate).  `counts` (the attribute) is a dict, decision
-    code -> number of viewer-steps so far (ops.GATE_CODES names the codes)."""
+    step(img, focus, force=None) returns (cat, stats, counts, bits[, conf], gate[, motion]).  `counts` (the attribute) is a dict,
+    decision code -> number of viewer-steps so far (ops.GATE_CODES names the codes)."""
 
     def __init__(self, module, batch, frame_size, *, tile=32, level=8, scene_frac=0.25, roi_tiles=0, roi_margin=16, fixation_px=None,
-                 saccade_px=_DEFAULT, max_age=0, reuse_inside_mask=True, max_runs=None, score=False, component=None, snap_px=None):
+                 saccade_px=_DEFAULT, max_age=0, reuse_inside_mask=True, max_runs=None, score=False, component=None, snap_px=None,
+                 motion_px=None, motion_gain=6):
         self.module = module
         self.batch = _int_ge("batch", batch, 1)
         if len(frame_size) != 2:
@@ -92,6 +102,8 @@ class GazeSession:
         else:
             ops._component_args(component, snap_px)
         self.component, self.snap_px = component, snap_px
+        self.motion_gain = ops._motion_gain(motion_gain)
+        self.motion_px = None if motion_px is None else ops._motion_px(motion_px, self.H, self.W)
         self.counts = {code: 0 for code in sorted(ops.GATE_CODES)}
         self._dev = None
 
@@ -109,6 +121,16 @@ class GazeSession:
         if self.score:
             rec.append(torch.zeros(B, 3, device=dev, dtype=torch.float32))
         self._rec = rec
+        if self.motion_px is not None:
+            self._key2 = torch.zeros_like(self._key)
+            self._bits2 = torch.zeros_like(rec[3])
+            self._prof = torch.zeros(B, H + W, device=dev, dtype=torch.int32)
+            self._prof_key = torch.zeros(B, H + W, device=dev, dtype=torch.int32)       # the profiles of the all-zero key
+            self._shift = torch.zeros(B, 4, device=dev, dtype=torch.int64)
+            self._mstate = torch.zeros(B, 4, device=dev, dtype=torch.int64)
+            self._motion = torch.zeros(B, 6, device=dev, dtype=torch.int64)
+            self._motion_host = torch.zeros(B, 6, dtype=torch.int64).pin_memory()
+            self._scratch = ops.state_shift_scratch(B, H, W, self.cap, dev)
 
     def reset(self, viewers=None):
         """Forget the records of `viewers` (a sequence of viewer indices; None = all): their next step is RUN_INIT."""
@@ -136,12 +158,15 @@ class GazeSession:
         """One frame per viewer.  img (B,3,H,W) fp32 and focus (B,2) as predict_instances takes them, on the device; force: None, or B
         flags (any sequence or tensor), non-zero = re-make this viewer's record now.
 
-        Returns (cat, stats, counts, bits[, conf], gate): the record of every viewer as predict_instances(img, focus, return_bits=True)
+        Returns (cat, stats, counts, bits[, conf], gate[, motion]): the record of every viewer as predict_instances(img, focus, return_bits=True)
         makes it -- made now for the viewers that ran, the held one for the others -- and gate (B,8) int64 on the host = (code,
         n_changed, n_roi_changed, sad_total, d2_key, d2_prev, inside_bit, age + 1) per viewer (ops.gate_decide).  The record tensors are
         the session's own: the next step overwrites them.  The step reads gate once, 64 * B bytes, its only synchronisation; the
         network runs on the viewers with a RUN code alone (img itself when that is everyone, img[idx] otherwise).  img and focus are
-        never written.  RuntimeError in train mode, ValueError for other shapes than the constructor's."""
+        never written.  With motion_px the state is moved to the new frame first (the class docstring), and motion (B,6) int64 on the host =
+        (dy, dx, cost_best, cost_zero, dy_total, dx_total) per viewer comes last, read in the same synchronisation: the shift applied in
+        this step, the estimate's costs, and the shift summed since the record was made (0 for a viewer whose record this step made).
+        RuntimeError in train mode, ValueError for other shapes than the constructor's."""
         if self.module.training:
             raise RuntimeError("GazeSession.step() needs eval mode (module.eval()): in train mode the encoder would update its BatchNorm running statistics")
         B, H, W = self.batch, self.H, self.W
@@ -158,11 +183,19 @@ class GazeSession:
         fdev = self._force(force, img.device)
         x = img.contiguous()
         f = focus.float().contiguous()
+        moving = self.motion_px is not None
+        if moving:
+            ops.frame_profiles(x, out=self._prof)
+            ops.profile_shift(self._prof, self._prof_key, self._gstate, (H, W), self.motion_px, self.motion_gain, out=self._shift)
+            ops.state_shift(x, self._shift, self._key, self._key2, self._rec[3], self._bits2, self._gstate, self._rec[1], self._rec[2],
+                            self._prof_key, self._mstate, motion=self._motion, scratch=self._scratch)
         ops.gate_tiles(x, self._key, self.tile, out=self._sad)
         ops.gate_decide(self._sad, self._gstate, f, self._rec[1], self._rec[3], (H, W), tile=self.tile, level=self.level,
                         scene_tiles=self.scene_tiles, roi_tiles=self.roi_tiles, margin=self.roi_margin, saccade2=self.saccade2,
                         fixation2=self.fixation2, max_age=self.max_age, inside_on=self.inside_on, force=fdev, out=self._gate)
         self._gate_host.copy_(self._gate, non_blocking=True)
+        if moving:
+            self._motion_host.copy_(self._motion, non_blocking=True)
         torch.cuda.current_stream(img.device).synchronize()
         gate = self._gate_host.clone()
         codes = gate[:, 0].tolist()
@@ -187,4 +220,11 @@ class GazeSession:
                 # every record is new: the tensors predict_instances made become the session's, nothing is copied
                 self._rec = new
             ops.gate_commit(x, idx, self._key, self._gstate, f, new, self._rec)
+            if moving:
+                ops.motion_commit(idx, self._prof, self._prof_key, self._mstate, (H, W))
+        if moving:
+            motion = self._motion_host.clone()
+            if run:
+                motion[run, 4:] = 0                                        # motion_commit's totals, known without a second read
+            return (*self._rec, gate, motion)
         return (*self._rec, gate)

@@ -332,6 +332,49 @@ int fs_gate_commit(const float* img, const int* idx, int n, unsigned char* key, 
                    const long long* src_cat, const long long* src_stats, const int* src_counts, const unsigned int* src_bits,
                    const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts, unsigned int* dst_bits,
                    float* dst_conf, int B, int H, int W, int cap, fs_stream_t stream);
+/* Global motion compensation in front of the gate (no counterpart in the reference: UNPINNED, a definition of this library's; DESIGN.md
+ * §1 f-3; its defaults are not validated on real gaze data): a viewer's record is carried along a camera that translates by whole
+ * pixels, and the unchanged gate then verifies the move.  All integers.  The pixel code q is the gate's, NaN -> 0; the luma code is
+ * L(y,x) = q_r + q_g + q_b, 0 .. 765.  Profiles: prof (B, H + W) int32, row b = [prow (H) | pcol (W)], prow[y] = sum_x L, pcol[x] =
+ * sum_y L.  fs_frame_profiles takes img (B,3,H,W) fp32 NCHW, fs_key_profiles key (B,3,H,W) bytes: the profiles of a frame and of the key
+ * commit made from it are equal.  The hot pass, 12 bytes a pixel: four pixels a lane by 16-byte (4-byte: key) loads where W % 4 == 0
+ * and the pointer is so aligned, one pixel a lane otherwise; prof is zeroed, then row sums (shuffles) and column sums (lanes, LDS) are
+ * added with integer atomics, so every order gives the same integers.  FS_ERR_ARG, with nothing launched, for a null pointer,
+ * non-positive sizes, H * W >= 2^31 or 765 * max(H, W) >= 2^31. */
+int fs_frame_profiles(const float* img, int* prof, int B, int H, int W, fs_stream_t stream);
+int fs_key_profiles(const unsigned char* key, int* prof, int B, int H, int W, fs_stream_t stream);
+/* The integer translation of every viewer (UNPINNED).  prof the new frames' profiles, prof_key the key frames'; gstate (B,6) the gate's.
+ * Per axis, for a new profile P, a key profile K of length n and s in [-R, R]: cost(s) = sum_{i=R}^{n-1-R} |P[i] - K[i - s]| in int64
+ * (the content at i came from i - s).  The best s has the least cost, ties going to the smaller |s|, then to the negative s; it is
+ * taken only if cost(s) * 8 <= cost(0) * gain, gain 0 .. 8, and is 0 otherwise (sensor noise on a still camera must not walk the record
+ * a pixel at a time).  shift (B,4) int64 = (dy, dx, cost_best, cost_zero): dy from prow, dx from pcol, cost_best the sum over the two
+ * axes of the least cost (whether or not the gain rule took its shift), cost_zero of cost(0).  A viewer with valid == 0 gets (0, 0, 0,
+ * 0).  One workgroup a viewer, both profiles of an axis and the 2R+1 costs in LDS.  FS_ERR_ARG, with nothing launched, as
+ * fs_frame_profiles and unless 1 <= R <= 255, 4R < min(H, W), 0 <= gain <= 8 and 8 * max(H, W) + 8 * (2R+1) <= 65536 bytes of LDS. */
+int fs_profile_shift(const int* prof, const int* prof_key, const long long* gstate, long long* shift, int B, int H, int W, int R, int gain,
+                     fs_stream_t stream);
+/* Move the state of every viewer whose (dy, dx) = shift[b, 0:2] is not (0, 0) (UNPINNED); a still viewer's tensors are not written and
+ * cost no key traffic (every workgroup reads shift[b] and leaves).  img (B,3,H,W) fp32 the new frames.
+ *   key'[c,y,x] = key[c,y-dy,x-dx] where that lies in the frame, else q(img[c,y,x]): the uncovered border cannot be judged and counts
+ *     as unchanged.  bits'[y,x] = bits[y-dy,x-dx], else 0; the bits at x >= W are 0.
+ *   gstate: gy_key, gy_prev += 16 dy and gx_key, gx_prev += 16 dx, clamped to [0, (side-1) * 16]: the previous gaze moves too, so a
+ *     counter-rotating eye is not read as a saccade.  stats / counts become fs_mask_rle's of bits' (cap entries), through its passes.
+ *   prof_key becomes the profiles of key'.  mstate (B,4) int64 = (dy_total, dx_total, moves, path) grows by (dy, dx, 1, |dy| + |dx|).
+ * cat and conf are not touched: mask_prob keeps describing the pixels the record was made from.  For every viewer motion (B,6) int64 =
+ * (dy, dx, cost_best, cost_zero, dy_total, dx_total), the totals after this move.  The move does not read what it writes: the moved
+ * planes are written to key2 (B,3,H,W) and bits2 (B,H,P) and copied back (the bits by funnel shifts over the word borders, four key
+ * bytes a lane where W % 4 == 0 and key, key2 are 4-byte aligned); the contents of key2, bits2 and scratch after the call are
+ * unspecified.  scratch = fs_state_shift_scratch_ints(B, H, W, cap) ints, 8-byte aligned (0 for sizes that are refused).  FS_ERR_ARG,
+ * with nothing launched, for a null pointer, key2 == key, bits2 == bits, a misaligned scratch, cap < 1, as fs_frame_profiles and
+ * fs_mask_rle for the sizes, or a side above 2^26. */
+long fs_state_shift_scratch_ints(int B, int H, int W, int cap);
+int fs_state_shift(const float* img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits,
+                   unsigned int* bits2, long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate,
+                   long long* motion, int* scratch, int B, int H, int W, int cap, fs_stream_t stream);
+/* After fs_gate_commit (UNPINNED): for the viewers idx[0 .. n) whose record was made anew, prof_key <- prof (this step's frame
+ * profiles: the profiles of the key frame commit made) and mstate <- 0.  n == 0 launches nothing, idx may be null; an idx entry outside
+ * 0 .. B-1 writes nothing.  FS_ERR_ARG for a null pointer, n outside 0 .. B, and as fs_frame_profiles for the sizes. */
+int fs_motion_commit(const int* idx, int n, const int* prof, int* prof_key, long long* mstate, int B, int H, int W, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
