@@ -4,6 +4,8 @@
 //                                                                                            (models/models.py:639-655,931-932)
 //   fill         exact nearest claimed pixel for the holes: nearest column per row, then the best row   (models.py:159-286, 'nearest')
 //   decide       the C1 head's argmax once per grid point, gathered through owner + fill -> class map    (models/models.py:930-940; eval.py:195)
+//   gather       which grid point feeds a full-resolution pixel: feeding_point / feeding_points4, the one rule under every stage below;
+//                its bit-word output: bit_slot, store_word_nibbles / store_word_ballot, gather_bits
 //   count        the same gather, counting against the label instead of storing: the six counters and four accuracies of
 //                MODEL.upsample (models/models.py:378-474,968), the trimap buckets (eval.py:41-67), the per-class areas of the three
 //                spaces (eval.py:197,218-257,313-322; models/models_instance.py:909-918; utils.py:289-317)
@@ -14,7 +16,8 @@
 //                class: the label-free output as a record (no counterpart in the reference; the code's format is the published one)
 //   score        the record's confidence: the foreground softmax mass per grid point as a 24-bit integer table, summed over the set pixels
 //                in the instance gather, times the head's class probability (no counterpart in the reference; unpinned)
-// Host side: fs_unwarp_labels / _accuracy / _trimap / _class_areas / _hd / _instances / _instances_scored are one launch sequence with optional parts.  unwarp_plan() derives
+// Host side: fs_unwarp_labels / _accuracy / _trimap / _class_areas / _hd / _instances / _instances_scored / _instances_component are one
+// launch sequence with optional parts.  unwarp_plan() derives
 // every size, scratch offset and limit from the shape and the feature set, UnwarpJob carries the caller's pointers, unwarp_run()
 // checks both and launches.  A refused call launches nothing: every check, fs_trimap_bands' included, comes before the first launch.
 #include "common.h"
@@ -129,6 +132,60 @@ __device__ __forceinline__ int nearest_claimed(const int* __restrict__ rx, int y
   }
   return bsrc;
 }
+// nearest_claimed for the four pixels (y, x .. x+3) of one row at once (x % 4 == 0, Ws % 4 == 0): one 16-byte read of rx per row serves
+// all four.  Every pixel sees its candidates in nearest_claimed's order and under its comparison; the rows past the point where
+// nearest_claimed would have stopped for it cannot win (dd >= d*d > best), so each src[k] is nearest_claimed's.  A claimed pixel
+// (hole bit clear) takes no part.
+__device__ __forceinline__ void nearest_claimed4(const int* __restrict__ rx, int y, int x, int Hs, int Ws, int holes, int src[4]) {
+  long best[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { best[k] = (holes >> k) & 1 ? -1 : 0; src[k] = -1; }
+  for (int d = 0; d < Hs; ++d) {
+    const long d2 = (long)d * d;
+    bool done = true;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) done = done && best[k] >= 0 && d2 > best[k];
+    if (done) break;
+    for (int sgn = 0; sgn < 2; ++sgn) {
+      const int yy = sgn == 0 ? y - d : y + d;
+      if (yy < 0 || yy >= Hs || (d == 0 && sgn == 1)) continue;
+      const int4 r = *reinterpret_cast<const int4*>(rx + (long)yy * Ws + x);
+      const int xs[4] = {r.x, r.y, r.z, r.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int xx = xs[k];
+        if (xx < 0) continue;
+        const long dx = (long)(x + k - xx);
+        const long dd = d2 + dx * dx;
+        const int cand = yy * Ws + xx;
+        if (best[k] < 0 || dd < best[k] || (dd == best[k] && cand < src[k])) { best[k] = dd; src[k] = cand; }
+      }
+    }
+  }
+}
+// THE rule of every full-resolution result: the grid point that feeds pixel (y, x) of an image is the pixel's owner o; for a hole
+// (o < 0) the owner of the nearest claimed pixel; point hw = h*w, the sample at (0,0), in an image without any claim.  ob, rx = the
+// image's owner map and its rows of fill_row_nearest_kernel.  Every table read through the result has hw + 1 entries an image.
+__device__ __forceinline__ int feeding_point(const int* __restrict__ ob, const int* __restrict__ rx, int o, int y, int x, int Hs, int Ws,
+                                             int hw) {
+  if (o >= 0) return o;
+  const int src = nearest_claimed(rx, y, x, Hs, Ws);
+  return src >= 0 ? ob[src] : hw;
+}
+// the same for the four pixels (y, x .. x+3), x % 4 == 0, Ws % 4 == 0, ob and rx 16-byte aligned: one 16-byte read of their owners
+__device__ __forceinline__ void feeding_points4(const int* __restrict__ ob, const int* __restrict__ rx, int y, int x, int Hs, int Ws, int hw,
+                                                int q[4]) {
+  const int4 o4 = *reinterpret_cast<const int4*>(ob + y * Ws + x);
+  q[0] = o4.x; q[1] = o4.y; q[2] = o4.z; q[3] = o4.w;
+  const int holes = (o4.x < 0) | (o4.y < 0) << 1 | (o4.z < 0) << 2 | (o4.w < 0) << 3;
+  if (holes) {
+    int src[4];
+    nearest_claimed4(rx, y, x, Hs, Ws, holes, src);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
+  }
+}
 __global__ void fill_col_nearest_kernel(const int* __restrict__ rowx, int* __restrict__ src, long n, int Hs, int Ws) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -202,8 +259,7 @@ __global__ __launch_bounds__(256) void unwarp_decide_kernel(const float* __restr
   if (v > best || (v != v && best == best)) arg = K - 1;
   dec[(long)b * (hw + 1) + p] = arg;
 }
-// labels[b,v,u] = dec[b, point feeding the pixel]: its owner; a hole's nearest claimed pixel's owner (fill_col_nearest_kernel's search);
-// dec[b,h*w] in an image without any claim.  hole (nullable) = the pixel has no owner.
+// labels[b,v,u] = dec[b, feeding_point of the pixel]; hole (nullable) = the pixel has no owner.
 __global__ __launch_bounds__(256) void unwarp_label_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
                                                            long long* __restrict__ labels, unsigned char* __restrict__ hole, long n, int Hs, int Ws,
                                                            int hw) {
@@ -211,21 +267,16 @@ __global__ __launch_bounds__(256) void unwarp_label_kernel(const int* __restrict
   if (i >= n) return;
   const long per = (long)Hs * Ws;
   const long b = i / per;
+  const int rem = (int)(i - b * per);                  // per < 2^31
+  const int y = rem / Ws, x = rem - y * Ws;
   const int o = owner[i];
-  int q = o;
-  if (o < 0) {
-    const long rem = i - b * per;
-    const int y = (int)(rem / Ws), x = (int)(rem - (long)y * Ws);
-    const int src = nearest_claimed(rowx + b * per, y, x, Hs, Ws);
-    q = src >= 0 ? owner[b * per + src] : hw;
-  }
-  labels[i] = (long long)dec[b * (hw + 1) + q];
+  labels[i] = (long long)dec[b * (hw + 1) + feeding_point(owner + b * per, rowx + b * per, o, y, x, Hs, Ws, hw)];
   if (hole != nullptr) hole[i] = o < 0;
 }
 
 // ---- the four full-resolution accuracies without the class map ---------------------------------------------------------------------
-// unwarp_label_kernel's gather with the compare-and-count of seg_loss_fwd_kernel behind it: the predicted class of a pixel is
-// dec[point feeding it], its ground truth one read of the label mask (t = (long)y, gt = t*cls_label + (1-t)*(K-1), models.py:968),
+// The gather with the compare-and-count of seg_loss_fwd_kernel behind it: the predicted class of a pixel is dec[its feeding_point],
+// its ground truth one read of the label mask (t = (long)y, gt = t*cls_label + (1-t)*(K-1), models.py:968),
 // and the six counters of models/models.py:378-474 are summed where the class would have been stored.
 // pixels per thread: one trip of four neighbours.  8 and 16 (fewer records) measured slower: 614 / 616 against 519 us at B = 64, 1024^2,
 // and 24 / 34 against 14 us at B = 1, where 256 workgroups a trip longer leave the CUs short of waves (profiles/r07)
@@ -233,46 +284,6 @@ constexpr int UACC_PIX = 4;
 constexpr int UACC_CHUNK = 256 * UACC_PIX;             // pixels per workgroup, all of one image
 constexpr int UACC_REC = 8;                            // ints per workgroup record: the six counters + 2 of padding (two 16-byte stores)
 struct AccCount { int c[6]; };
-__device__ __forceinline__ int unwarp_class_at(const int* __restrict__ ob, const int* __restrict__ rx, const int* __restrict__ db, int o,
-                                               int y, int x, int Hs, int Ws, int hw) {
-  int q = o;
-  if (o < 0) {
-    const int src = nearest_claimed(rx, y, x, Hs, Ws);
-    q = src >= 0 ? ob[src] : hw;
-  }
-  return db[q];
-}
-// nearest_claimed for the four pixels (y, x .. x+3) of one row at once (x % 4 == 0, Ws % 4 == 0): one 16-byte read of rx per row serves
-// all four.  Every pixel sees its candidates in nearest_claimed's order and under its comparison; the rows past the point where
-// nearest_claimed would have stopped for it cannot win (dd >= d*d > best), so each src[k] is nearest_claimed's.  A claimed pixel
-// (hole bit clear) takes no part.
-__device__ __forceinline__ void nearest_claimed4(const int* __restrict__ rx, int y, int x, int Hs, int Ws, int holes, int src[4]) {
-  long best[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) { best[k] = (holes >> k) & 1 ? -1 : 0; src[k] = -1; }
-  for (int d = 0; d < Hs; ++d) {
-    const long d2 = (long)d * d;
-    bool done = true;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) done = done && best[k] >= 0 && d2 > best[k];
-    if (done) break;
-    for (int sgn = 0; sgn < 2; ++sgn) {
-      const int yy = sgn == 0 ? y - d : y + d;
-      if (yy < 0 || yy >= Hs || (d == 0 && sgn == 1)) continue;
-      const int4 r = *reinterpret_cast<const int4*>(rx + (long)yy * Ws + x);
-      const int xs[4] = {r.x, r.y, r.z, r.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int xx = xs[k];
-        if (xx < 0) continue;
-        const long dx = (long)(x + k - xx);
-        const long dd = d2 + dx * dx;
-        const int cand = yy * Ws + xx;
-        if (best[k] < 0 || dd < best[k] || (dd == best[k] && cand < src[k])) { best[k] = dd; src[k] = cand; }
-      }
-    }
-  }
-}
 // head_loss.hip's predicates (seg_loss_fwd_kernel) on one pixel: a = predicted class, yv = the label mask's value
 __device__ __forceinline__ void count_pixel(AccCount& n, int a, float yv, long long cl, int bg) {
   const long long t = (long long)yv;
@@ -362,18 +373,10 @@ __global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict
     for (int j = 0; j < UACC_PIX / 4; ++j) {
       const int p = p0 + (j * 256 + (int)threadIdx.x) * 4;
       if (p >= per) break;                             // per % 4 == 0: the four pixels are in or out together
-      const int4 o4 = *reinterpret_cast<const int4*>(ob + p);
       const float4 y4 = *reinterpret_cast<const float4*>(yb + p);
       const int y = p / Ws, x = p - y * Ws;            // Ws % 4 == 0: one row
-      int q[4] = {o4.x, o4.y, o4.z, o4.w};
-      const int holes = (o4.x < 0) | (o4.y < 0) << 1 | (o4.z < 0) << 2 | (o4.w < 0) << 3;
-      if (holes) {
-        int src[4];
-        nearest_claimed4(rx, y, x, Hs, Ws, holes, src);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-          if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
-      }
+      int q[4];
+      feeding_points4(ob, rx, y, x, Hs, Ws, hw, q);
       int a0 = db[q[0]], a1 = db[q[1]], a2 = db[q[2]], a3 = db[q[3]];
       if (AREA) {
         a0 = area_pixel(aw, hist, a0, y4.x, cl, bg); a1 = area_pixel(aw, hist, a1, y4.y, cl, bg);
@@ -397,7 +400,7 @@ __global__ __launch_bounds__(256) void unwarp_count_kernel(const int* __restrict
       const int p = p0 + j * 256 + (int)threadIdx.x;
       if (p >= per) break;
       const int y = p / Ws, x = p - y * Ws;
-      int a = unwarp_class_at(ob, rx, db, ob[p], y, x, Hs, Ws, hw);
+      int a = db[feeding_point(ob, rx, ob[p], y, x, Hs, Ws, hw)];
       if (AREA) a = area_pixel(aw, hist, a, yb[p], cl, bg);
       count_pixel(n, a, yb[p], cl, bg);
       if (TRIM) trim_pixel(tbw, band[base + p], a, yb[p], cl, bg);
@@ -769,7 +772,7 @@ constexpr int HD_L2_BINS = 1 << HD_L1_SHIFT;           // level 2: the low 15 bi
 constexpr int HD_CACHE = 1024;                         // row pass: the first bins of a histogram are counted in LDS, then flushed
 constexpr int HD_NEAR = 8;                             // row pass: columns on either side a lane scans alone before the wave joins in
 
-// fg[b,v,u]: unwarp_label_kernel's gather (bit 0: the class is not K-1) and the label mask's truncation (bit 1).  dec may carry
+// fg[b,v,u]: bit 0 = the class dec[feeding_point] is not K-1, bit 1 = the label mask's truncation is not 0.  dec may carry
 // class_area_sampled_kernel's bit.  VEC: Ws % 4 == 0, y 16-byte aligned: four neighbours of one row, one word stored.
 template <bool VEC>
 __global__ __launch_bounds__(256) void unwarp_fg_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
@@ -787,18 +790,10 @@ __global__ __launch_bounds__(256) void unwarp_fg_kernel(const int* __restrict__ 
   if (VEC) {
     const int p = p0 + (int)threadIdx.x * 4;
     if (p >= per) return;
-    const int4 o4 = *reinterpret_cast<const int4*>(ob + p);
     const float4 y4 = *reinterpret_cast<const float4*>(yb + p);
     const int y = p / Ws, x = p - y * Ws;
-    int q[4] = {o4.x, o4.y, o4.z, o4.w};
-    const int holes = (o4.x < 0) | (o4.y < 0) << 1 | (o4.z < 0) << 2 | (o4.w < 0) << 3;
-    if (holes) {
-      int src[4];
-      nearest_claimed4(rx, y, x, Hs, Ws, holes, src);
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
-    }
+    int q[4];
+    feeding_points4(ob, rx, y, x, Hs, Ws, hw, q);
     const float ys[4] = {y4.x, y4.y, y4.z, y4.w};
     unsigned int wd = 0;
 #pragma unroll
@@ -813,7 +808,7 @@ __global__ __launch_bounds__(256) void unwarp_fg_kernel(const int* __restrict__ 
       const int p = p0 + j * 256 + (int)threadIdx.x;
       if (p >= per) break;
       const int y = p / Ws, x = p - y * Ws;
-      const int a = unwarp_class_at(ob, rx, db, ob[p], y, x, Hs, Ws, hw) & DEC_CLASS_MASK;
+      const int a = db[feeding_point(ob, rx, ob[p], y, x, Hs, Ws, hw)] & DEC_CLASS_MASK;
       fg[base + p] = (unsigned char)((a != bg) | ((long long)yb[p] != 0) << 1);
     }
   }
@@ -1021,8 +1016,8 @@ __global__ __launch_bounds__(256) void hd_select2_kernel(const int* __restrict__
 // pitched to P = ceil(Ws / 32) words with the bits past Ws clear; the statistics and the run-length code are made from the words, and
 // the class is the head's own decision.  The uncompressed COCO code reads the mask column-major (p = x * Hs + y) and lists the
 // distances between the boundaries T = {p : v[p] != v[p-1]}, v[-1] = 0 (format restated from its published definition; unpinned).
-//   bits     unwarp_fg_kernel's gather; a thread's four predicates are a nibble, eight lanes' nibbles a word (unwarp_bits_kernel), or
-//            the same words from a byte mask (mask_bits_kernel)
+//   bits     the predicate of every pixel's feeding point, packed as it is gathered (gather_bits: unwarp_bits_kernel), or the same words
+//            from a byte mask (mask_bits_kernel)
 //   count    one thread per (column, RLE_SEG-row segment): the boundaries in it, the position of its last one, its set pixels and
 //            their row range (rle_walk_kernel<false>)
 //   scan     one workgroup per image over its items in column-major order, which is the order of the runs: the exclusive sum of the
@@ -1032,72 +1027,80 @@ __global__ __launch_bounds__(256) void hd_select2_kernel(const int* __restrict__
 // Plain stores only: the same bits in any order.  counts is zeroed by the launcher, so everything past the code reads 0.
 constexpr int RLE_SEG = 64;                            // rows per item: 16 items a column at 1024 rows
 
-// bits[b,y,i]: VEC (Ws % 4 == 0, 16-byte aligned owner / rowx): eight lanes a word, lane l the columns 32 i + 4 l .. + 3 of row y; a
-// quad is inside the row or past its end as a whole.  Otherwise one lane a column and a ballot, two words a wave.  No thread leaves
-// before the shuffles / the ballot.  words = B * Hs * P.
+// Word g of bits (words = B * Hs * P of them) is word i of row = b * Hs + y, the columns 32 i .. 32 i + 31.  LPW lanes make one word,
+// a workgroup 256 / LPW consecutive ones: LPW = 8, lane l of the eight holds the columns x .. x + 3 = 32 i + 4 l .. (Ws % 4 == 0: the
+// quad is inside the row or past its end as a whole); LPW = 32, one lane a column x.  live: the word exists and x < Ws.
+struct BitSlot { long g, row; int x; bool live; };
+template <int LPW>
+__device__ __forceinline__ BitSlot bit_slot(int Ws, int P, long words) {
+  BitSlot s;
+  s.g = (long)blockIdx.x * (256 / LPW) + threadIdx.x / LPW;
+  s.row = s.g / P;
+  s.x = 32 * (int)(s.g - s.row * P) + (32 / LPW) * (int)(threadIdx.x % LPW);
+  s.live = s.g < words && s.x < Ws;
+  return s;
+}
+// The two stores of word g; every thread of the wave calls them.  Eight lanes a word: nib = the flags of the lane's four columns, or-ed
+// over the eight by three shuffles.  One lane a bit: a ballot, two words a wave.  A lane that is not live passes no flag.
+__device__ __forceinline__ void store_word_nibbles(unsigned int* __restrict__ bits, long g, long words, unsigned int nib) {
+  const int l = threadIdx.x & 7;
+  unsigned int wd = nib << (4 * l);
+  wd |= __shfl_xor(wd, 1, 64); wd |= __shfl_xor(wd, 2, 64); wd |= __shfl_xor(wd, 4, 64);
+  if (l == 0 && g < words) bits[g] = wd;
+}
+__device__ __forceinline__ void store_word_ballot(unsigned int* __restrict__ bits, long g, long words, bool f) {
+  const unsigned long long bal = __ballot(f);
+  if ((threadIdx.x & 31) == 0 && g < words) bits[g] = (unsigned int)(bal >> (threadIdx.x & 32));
+}
+// head_fg_q_kernel's packed word of a grid point (the score section below): the foreground flag in the sign bit, q in the rest
+constexpr int SCORE_FG_BIT = 31;
+constexpr int SCORE_Q_MASK = 0x7fffffff;
+struct GatherSum { unsigned int s; long b; };          // SCORE: the q of this thread's set pixels, and their image (-1: not live)
+// The gather into bit words: bit (b, y, x) = the predicate of tab[b, feeding_point of the pixel], tab of hw + 1 words an image.
+// Without SCORE tab is unwarp_decide_kernel's and the predicate "the class is not bg"; with it tab is head_fg_q_kernel's packed table,
+// the predicate its sign bit, and the q of the set pixels is summed (a quad and a column lie in one row: one image a thread).
+// VEC (Ws % 4 == 0, 16-byte aligned owner / rowx): four pixels a thread, eight lanes a word; else one lane a column.  No thread
+// leaves before the store's shuffles / ballot.
+template <bool VEC, bool SCORE>
+__device__ __forceinline__ GatherSum gather_bits(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ tab,
+                                                 unsigned int* __restrict__ bits, int Hs, int Ws, int P, int hw, int bg, long words) {
+  constexpr int NPIX = VEC ? 4 : 1;
+  const BitSlot sl = bit_slot<32 / NPIX>(Ws, P, words);
+  GatherSum sum = {0u, -1};
+  unsigned int set = 0u;                               // flag k: column x + k
+  if (sl.live) {
+    const int per = Hs * Ws;
+    const long b = sl.row / Hs;
+    const int y = (int)(sl.row - b * Hs);
+    const int* ob = owner + b * per;
+    const int* rx = rowx + b * per;
+    const int* tb = tab + b * (hw + 1);
+    int q[4];
+    if (VEC) feeding_points4(ob, rx, y, sl.x, Hs, Ws, hw, q);
+    else q[0] = feeding_point(ob, rx, ob[y * Ws + sl.x], y, sl.x, Hs, Ws, hw);
+#pragma unroll
+    for (int k = 0; k < NPIX; ++k) {
+      const int wd = tb[q[k]];
+      const bool f = SCORE ? wd < 0 : wd != bg;
+      set |= (unsigned int)f << k;
+      if (SCORE) sum.s += f ? (unsigned int)(wd & SCORE_Q_MASK) : 0u;
+    }
+    sum.b = b;
+  }
+  if (VEC) store_word_nibbles(bits, sl.g, words, set);
+  else store_word_ballot(bits, sl.g, words, set != 0u);
+  return sum;
+}
 template <bool VEC>
 __global__ __launch_bounds__(256) void unwarp_bits_kernel(const int* __restrict__ owner, const int* __restrict__ rowx, const int* __restrict__ dec,
                                                           unsigned int* __restrict__ bits, int Hs, int Ws, int P, int hw, int K, long words) {
-  const int bg = K - 1;
-  const int per = Hs * Ws;
-  if (VEC) {
-    const long g = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
-    const int l = threadIdx.x & 7;
-    unsigned int nib = 0u;
-    if (g < words) {
-      const long row = g / P;                          // b * Hs + y
-      const int x = 32 * (int)(g - row * P) + 4 * l;
-      if (x < Ws) {
-        const long b = row / Hs;
-        const int y = (int)(row - b * Hs);
-        const int* ob = owner + b * per;
-        const int* db = dec + b * (hw + 1);
-        const int4 o4 = *reinterpret_cast<const int4*>(ob + y * Ws + x);
-        int q[4] = {o4.x, o4.y, o4.z, o4.w};
-        const int holes = (o4.x < 0) | (o4.y < 0) << 1 | (o4.z < 0) << 2 | (o4.w < 0) << 3;
-        if (holes) {
-          int src[4];
-          nearest_claimed4(rowx + b * per, y, x, Hs, Ws, holes, src);
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) nib |= (unsigned int)(db[q[k]] != bg) << k;
-      }
-    }
-    unsigned int wd = nib << (4 * l);
-    wd |= __shfl_xor(wd, 1, 64); wd |= __shfl_xor(wd, 2, 64); wd |= __shfl_xor(wd, 4, 64);
-    if (l == 0 && g < words) bits[g] = wd;
-  } else {
-    const long g = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
-    bool f = false;
-    if (g < words) {
-      const long row = g / P;
-      const int x = 32 * (int)(g - row * P) + (int)(threadIdx.x & 31);
-      if (x < Ws) {
-        const long b = row / Hs;
-        const int y = (int)(row - b * Hs);
-        const int* ob = owner + b * per;
-        f = unwarp_class_at(ob, rowx + b * per, dec + b * (hw + 1), ob[y * Ws + x], y, x, Hs, Ws, hw) != bg;
-      }
-    }
-    const unsigned long long bal = __ballot(f);
-    if ((threadIdx.x & 31) == 0 && g < words) bits[g] = (unsigned int)(bal >> (threadIdx.x & 32));
-  }
+  gather_bits<VEC, false>(owner, rowx, dec, bits, Hs, Ws, P, hw, K - 1, words);
 }
-// the same words from a byte mask (non-zero = set), any alignment: one lane a column and a ballot
+// the same words from a byte mask (non-zero = set), any alignment
 __global__ __launch_bounds__(256) void mask_bits_kernel(const unsigned char* __restrict__ mask, unsigned int* __restrict__ bits, int Ws, int P,
                                                         long words) {
-  const long g = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
-  bool f = false;
-  if (g < words) {
-    const long row = g / P;
-    const int x = 32 * (int)(g - row * P) + (int)(threadIdx.x & 31);
-    if (x < Ws) f = mask[row * Ws + x] != 0;
-  }
-  const unsigned long long bal = __ballot(f);
-  if ((threadIdx.x & 31) == 0 && g < words) bits[g] = (unsigned int)(bal >> (threadIdx.x & 32));
+  const BitSlot sl = bit_slot<32>(Ws, P, words);
+  store_word_ballot(bits, sl.g, words, sl.live && mask[sl.row * Ws + sl.x] != 0);
 }
 // cat[b] = the first maximal k < K-1 of cls[b,k], NaN maximal: unwarp_decide_kernel's comparison on the planes themselves
 __global__ __launch_bounds__(256) void instance_cat_kernel(const float* __restrict__ cls, long long* __restrict__ cat, int B, int K) {
@@ -1226,8 +1229,6 @@ __global__ __launch_bounds__(256) void rle_scan_kernel(int* __restrict__ cnt, in
 // of them -inf) gives 0.  The v are unwarp_decide_kernel's float operations (same taps, same sample4); they are formed twice, for the
 // maximum and for the sums, instead of being kept.  dec (nullable) = unwarp_decide_kernel's table: given, "class is not K-1" rides in
 // bit SCORE_FG_BIT of the word, so that the scored gather reads one word per pixel as the unscored one reads dec.
-constexpr int SCORE_FG_BIT = 31;
-constexpr int SCORE_Q_MASK = 0x7fffffff;
 constexpr double SCORE_ONE = 16777216.0;               // 2^24
 __global__ __launch_bounds__(256) void head_fg_q_kernel(const float* __restrict__ cls, const float* __restrict__ m, const int* __restrict__ dec,
                                                         int* __restrict__ qt, int K, int h, int w, int blocks_per_image) {
@@ -1272,8 +1273,8 @@ __global__ __launch_bounds__(256) void head_fg_q_kernel(const float* __restrict_
   if (dec != nullptr) word |= (unsigned int)(dec[i] != K - 1) << SCORE_FG_BIT;
   qt[i] = (int)word;
 }
-// unwarp_bits_kernel's gather from head_fg_q_kernel's packed table, with the q of every set pixel summed per image.  A thread's sum is
-// one image's (a quad and a column lie in one row).  A wave's words are consecutive -- WPW = 8 with VEC, 2 without -- so its images are
+// gather_bits from head_fg_q_kernel's packed table, and behind it the q of every set pixel summed per image.  A thread's sum is one
+// image's.  A wave's words are consecutive -- WPW = 8 with VEC, 2 without -- so its images are
 // those of its first to its last word: one, or two where it straddles an image's end, or more where an image has fewer words than a
 // wave; bits past a row's end add nothing.  Per image the wave reduces by shuffles (a thread's sum is below 2^27, so 32 lanes fit 32
 // bits and the last step is taken in 64; a wave without a set pixel of the image, the usual case of a small mask, skips them).  The
@@ -1290,62 +1291,9 @@ __global__ __launch_bounds__(256) void unwarp_bits_score_kernel(const int* __res
                                                                 unsigned long long* __restrict__ qsum, int* __restrict__ rec, int Hs, int Ws,
                                                                 int P, int hw, long words) {
   constexpr unsigned int WPW = VEC ? 8 : 2;            // words per wave: no more images than that
-  const int per = Hs * Ws;
-  unsigned int s = 0u;
-  long tb = -1;                                        // this thread's image
-  if (VEC) {
-    const long g = (long)blockIdx.x * 32 + (threadIdx.x >> 3);
-    const int l = threadIdx.x & 7;
-    unsigned int nib = 0u;
-    if (g < words) {
-      const long row = g / P;
-      const int x = 32 * (int)(g - row * P) + 4 * l;
-      if (x < Ws) {
-        const long b = row / Hs;
-        const int y = (int)(row - b * Hs);
-        const int* ob = owner + b * per;
-        const int* db = qf + b * (hw + 1);
-        const int4 o4 = *reinterpret_cast<const int4*>(ob + y * Ws + x);
-        int q[4] = {o4.x, o4.y, o4.z, o4.w};
-        const int holes = (o4.x < 0) | (o4.y < 0) << 1 | (o4.z < 0) << 2 | (o4.w < 0) << 3;
-        if (holes) {
-          int src[4];
-          nearest_claimed4(rowx + b * per, y, x, Hs, Ws, holes, src);
-#pragma unroll
-          for (int k = 0; k < 4; ++k)
-            if ((holes >> k) & 1) q[k] = src[k] >= 0 ? ob[src[k]] : hw;
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const int wd = db[q[k]];
-          nib |= (unsigned int)(wd < 0) << k;
-          s += wd < 0 ? (unsigned int)(wd & SCORE_Q_MASK) : 0u;
-        }
-        tb = b;
-      }
-    }
-    unsigned int wd = nib << (4 * l);
-    wd |= __shfl_xor(wd, 1, 64); wd |= __shfl_xor(wd, 2, 64); wd |= __shfl_xor(wd, 4, 64);
-    if (l == 0 && g < words) bits[g] = wd;
-  } else {
-    const long g = (long)blockIdx.x * 8 + (threadIdx.x >> 5);
-    bool f = false;
-    if (g < words) {
-      const long row = g / P;
-      const int x = 32 * (int)(g - row * P) + (int)(threadIdx.x & 31);
-      if (x < Ws) {
-        const long b = row / Hs;
-        const int y = (int)(row - b * Hs);
-        const int* ob = owner + b * per;
-        const int wd = unwarp_class_at(ob, rowx + b * per, qf + b * (hw + 1), ob[y * Ws + x], y, x, Hs, Ws, hw);
-        f = wd < 0;
-        s = f ? (unsigned int)(wd & SCORE_Q_MASK) : 0u;
-        tb = b;
-      }
-    }
-    const unsigned long long bal = __ballot(f);
-    if ((threadIdx.x & 31) == 0 && g < words) bits[g] = (unsigned int)(bal >> (threadIdx.x & 32));
-  }
+  const GatherSum mine = gather_bits<VEC, true>(owner, rowx, qf, bits, Hs, Ws, P, hw, 0, words);
+  const unsigned int s = mine.s;
+  const long tb = mine.b;                              // this thread's image
   // words < 2^27 (one lane a bit slot) and Hs * P < 2^31: 32-bit divisions
   const unsigned int wpi = (unsigned int)Hs * (unsigned int)P, nw = (unsigned int)words;
   const unsigned int wave = blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -1410,8 +1358,7 @@ __global__ __launch_bounds__(256) void instance_conf_kernel(const float* __restr
 }
 // unwarp_bits_score_kernel's sums over the set bits of given words instead of the gathered ones (fs_unwarp_instances_component: the
 // words are the component's, qf is head_fg_q_kernel's table).  One lane a word -- most words around one component are 0 and their
-// lanes leave after one read; a lane with set bits walks them, and for each does the gather's owner / nearest_claimed look-up and
-// table read.  A lane's sum is one image's and below 2^29.  The records are that kernel's with VEC: eight consecutive words (eight
+// lanes leave after one read; a lane with set bits walks them, and for each reads the table at the pixel's feeding_point.  A lane's sum is one image's and below 2^29.  The records are that kernel's with VEC: eight consecutive words (eight
 // neighbouring lanes) make record g / 8, two ints, = the sum over those of the eight whose image is the first word's, by plain
 // stores; a lane of a further image -- a group that straddles an image's end -- adds its sum into qsum (zeroed by the launcher) by a
 // 64-bit integer atomic.  instance_conf_kernel sums the records with wpw = 8.  Integer sums: the same bits in any order.
@@ -1437,7 +1384,7 @@ __global__ __launch_bounds__(256) void component_qsum_kernel(const int* __restri
       while (wd != 0u) {
         const int x = 32 * c + __ffs((int)wd) - 1;
         wd &= wd - 1u;
-        s += (unsigned int)(unwarp_class_at(ob, rx, db, ob[y * Ws + x], y, x, Hs, Ws, hw) & SCORE_Q_MASK);
+        s += (unsigned int)(db[feeding_point(ob, rx, ob[y * Ws + x], y, x, Hs, Ws, hw)] & SCORE_Q_MASK);
       }
     }
   }
@@ -1706,9 +1653,9 @@ const CountKernel COUNT_KERNELS[8] = {
     unwarp_count_kernel<true, true, false>,   unwarp_count_kernel<false, false, true>, unwarp_count_kernel<true, false, true>,
     unwarp_count_kernel<false, true, true>,   unwarp_count_kernel<true, true, true>};
 
-// The launches of the seven entry points: [trimap bands,] prelude, then either the class map, or with UW_BITS the bit words, the class
-// and the run-length passes (with UW_SCORE the packed table before the gather, the confidences behind the run-length passes), or the count pass and its finalizers (the trimap's and the areas' after the accuracies'), then with UW_HD
-// the foreground bytes and the surface distances.
+// The launches of the eight entry points: [trimap bands,] prelude, then either the class map, or with UW_BITS the instance sequence
+// below, or the count pass and its finalizers (the trimap's and the areas' after the accuracies'), then with UW_HD the foreground
+// bytes and the surface distances.
 int unwarp_run(const UnwarpPlan& p, const UnwarpJob& j, hipStream_t stream) {
   const bool count = p.features & UW_COUNT, trim = p.features & UW_TRIM, area = p.features & UW_AREA, hdq = p.features & UW_HD;
   const bool inst = p.features & UW_BITS, score = p.features & UW_SCORE, comp = p.features & UW_COMP;
@@ -1725,59 +1672,51 @@ int unwarp_run(const UnwarpPlan& p, const UnwarpJob& j, hipStream_t stream) {
   if (trim) FS_TRY(trimap_launch(p.tri, j.count.y, band, reinterpret_cast<unsigned char*>(s + p.inter), p.B, p.Hs, p.Ws, j.trim.D, j.trim.frame, stream));
   FS_TRY(unwarp_prelude(p, j, stream));
   if (inst) {
+    // The record -- words, run-length code, q sum -- is made from `bits`, the caller's words or scratch.  Without a component the gather
+    // writes them, and a scored gather sums q as it goes.  With one the gather is the unscored one and its words stay in scratch; the
+    // component's become `bits`, and the q sum is a pass of its own over them (component_qsum_kernel).
     unsigned int* bits = j.inst.bits ? j.inst.bits : reinterpret_cast<unsigned int*>(s + p.bitw);
+    unsigned int* gathered = comp ? reinterpret_cast<unsigned int*>(s + p.raww) : bits;
+    unsigned long long* qsum = reinterpret_cast<unsigned long long*>(j.inst.qsum);
+    const bool fused = score && !comp;
     // four pixels a thread need whole 16-byte rows of owner and rowx
     const bool vec4 = p.Ws % 4 == 0 && ((uintptr_t)s & 15) == 0;
-    int* srec = nullptr;
-    if (comp) {
-      // the gather's words stay in scratch, the component's become the record's: bits, the run-length code and the q sum are taken from them
-      unsigned int* raw = reinterpret_cast<unsigned int*>(s + p.raww);
-      if (score) {
-        hipLaunchKernelGGL(head_fg_q_kernel, dim3((unsigned)(p.B * p.bpi)), dim3(256), 0, stream, j.cls, j.m, s + p.dec, s + p.qtab, p.K, p.h, p.w,
-                           (int)p.bpi);
-        FS_LAUNCH_CHECK();
-      }
-      hipLaunchKernelGGL(vec4 ? unwarp_bits_kernel<true> : unwarp_bits_kernel<false>, dim3(cdiv(p.rle.words, vec4 ? 32 : 8)), dim3(256), 0, stream,
-                         s + p.owner, s + p.rowx, s + p.dec, raw, p.Hs, p.Ws, (int)p.rle.P, p.h * p.w, p.K, p.rle.words);
-      FS_LAUNCH_CHECK();
-      hipLaunchKernelGGL(instance_cat_kernel, dim3(cdiv(p.B, 256)), dim3(256), 0, stream, j.cls, j.inst.cat, p.B, p.K);
-      FS_LAUNCH_CHECK();
-      FS_TRY(component_launch(p.cmp, raw, j.comp.focus, bits, j.comp.out, s + p.cmps, p.B, p.Hs, p.Ws, j.comp.conn, j.comp.snap2, stream));
-      FS_TRY(rle_launch(p.rle, bits, j.inst.stats, j.inst.counts, s + p.rles, p.B, p.Hs, p.Ws, j.inst.cap, stream));
-      if (score) {
-        const hipError_t e = hipMemsetAsync(j.inst.qsum, 0, sizeof(long long) * (size_t)p.B, stream);
-        if (e != hipSuccess) return (int)e;
-        hipLaunchKernelGGL(component_qsum_kernel, dim3(cdiv(p.rle.words, 256)), dim3(256), 0, stream, s + p.owner, s + p.rowx, s + p.qtab, bits,
-                           reinterpret_cast<unsigned long long*>(j.inst.qsum), s + p.crec, p.Hs, p.Ws, (int)p.rle.P, p.h * p.w, p.rle.words);
-        FS_LAUNCH_CHECK();
-        hipLaunchKernelGGL(instance_conf_kernel, dim3((unsigned)p.B), dim3(256), 0, stream, j.cls, j.inst.cat, j.inst.stats, s + p.crec, j.inst.qsum,
-                           j.inst.conf, p.K, (long)p.Hs * p.rle.P, 8, (long)cdiv(p.rle.words, 8));
-        FS_LAUNCH_CHECK();
-      }
-      return FS_OK;
-    }
+    const dim3 ggrid(cdiv(p.rle.words, vec4 ? 32 : 8));
+    const int hw = p.h * p.w, P = (int)p.rle.P;
+    // the route's q records for instance_conf_kernel: the component pass's, two ints per eight words; or the scored gather's, one per
+    // wave of wpw words -- null where they were sized for the gather the width allows and the scratch's alignment forbids it
+    int* qrec = comp ? s + p.crec : (p.Ws % 4 == 0) == vec4 ? s + p.srec : nullptr;
+    const int wpw = comp || vec4 ? 8 : 2;
+    const long nwaves = comp ? (long)cdiv(p.rle.words, 8) : 4L * cdiv(p.rle.words, 4 * wpw);
     if (score) {
-      unsigned long long* qsum = reinterpret_cast<unsigned long long*>(j.inst.qsum);
-      srec = (p.Ws % 4 == 0) == vec4 ? s + p.srec : nullptr;     // the records were sized for the gather the width allows
       hipLaunchKernelGGL(head_fg_q_kernel, dim3((unsigned)(p.B * p.bpi)), dim3(256), 0, stream, j.cls, j.m, s + p.dec, s + p.qtab, p.K, p.h, p.w,
                          (int)p.bpi);
       FS_LAUNCH_CHECK();
+    }
+    if (fused) {
       const hipError_t e = hipMemsetAsync(qsum, 0, sizeof(long long) * (size_t)p.B, stream);
       if (e != hipSuccess) return (int)e;
-      hipLaunchKernelGGL(vec4 ? unwarp_bits_score_kernel<true> : unwarp_bits_score_kernel<false>, dim3(cdiv(p.rle.words, vec4 ? 32 : 8)), dim3(256),
-                         0, stream, s + p.owner, s + p.rowx, s + p.qtab, bits, qsum, srec, p.Hs, p.Ws, (int)p.rle.P, p.h * p.w, p.rle.words);
+      hipLaunchKernelGGL(vec4 ? unwarp_bits_score_kernel<true> : unwarp_bits_score_kernel<false>, ggrid, dim3(256), 0, stream, s + p.owner,
+                         s + p.rowx, s + p.qtab, gathered, qsum, qrec, p.Hs, p.Ws, P, hw, p.rle.words);
     } else {
-      hipLaunchKernelGGL(vec4 ? unwarp_bits_kernel<true> : unwarp_bits_kernel<false>, dim3(cdiv(p.rle.words, vec4 ? 32 : 8)), dim3(256), 0, stream,
-                         s + p.owner, s + p.rowx, s + p.dec, bits, p.Hs, p.Ws, (int)p.rle.P, p.h * p.w, p.K, p.rle.words);
+      hipLaunchKernelGGL(vec4 ? unwarp_bits_kernel<true> : unwarp_bits_kernel<false>, ggrid, dim3(256), 0, stream, s + p.owner, s + p.rowx,
+                         s + p.dec, gathered, p.Hs, p.Ws, P, hw, p.K, p.rle.words);
     }
     FS_LAUNCH_CHECK();
     hipLaunchKernelGGL(instance_cat_kernel, dim3(cdiv(p.B, 256)), dim3(256), 0, stream, j.cls, j.inst.cat, p.B, p.K);
     FS_LAUNCH_CHECK();
+    if (comp) FS_TRY(component_launch(p.cmp, gathered, j.comp.focus, bits, j.comp.out, s + p.cmps, p.B, p.Hs, p.Ws, j.comp.conn, j.comp.snap2, stream));
     FS_TRY(rle_launch(p.rle, bits, j.inst.stats, j.inst.counts, s + p.rles, p.B, p.Hs, p.Ws, j.inst.cap, stream));
+    if (score && comp) {
+      const hipError_t e = hipMemsetAsync(qsum, 0, sizeof(long long) * (size_t)p.B, stream);
+      if (e != hipSuccess) return (int)e;
+      hipLaunchKernelGGL(component_qsum_kernel, dim3(cdiv(p.rle.words, 256)), dim3(256), 0, stream, s + p.owner, s + p.rowx, s + p.qtab, bits, qsum,
+                         qrec, p.Hs, p.Ws, P, hw, p.rle.words);
+      FS_LAUNCH_CHECK();
+    }
     if (score) {
-      const int wpw = vec4 ? 8 : 2;
-      hipLaunchKernelGGL(instance_conf_kernel, dim3((unsigned)p.B), dim3(256), 0, stream, j.cls, j.inst.cat, j.inst.stats, srec, j.inst.qsum,
-                         j.inst.conf, p.K, (long)p.Hs * p.rle.P, wpw, 4L * cdiv(p.rle.words, 4 * wpw));
+      hipLaunchKernelGGL(instance_conf_kernel, dim3((unsigned)p.B), dim3(256), 0, stream, j.cls, j.inst.cat, j.inst.stats, qrec, j.inst.qsum,
+                         j.inst.conf, p.K, (long)p.Hs * P, wpw, nwaves);
       FS_LAUNCH_CHECK();
     }
     return FS_OK;

@@ -1582,6 +1582,28 @@ def mask_bits(mask):
     return bits
 
 
+def _bits_arg(mask_or_bits, Ws):
+    """(bits (B,Hs,P) int32, Ws) of a mask argument as mask_rle / mask_component take it; bits is None for a mask still to be packed."""
+    if not isinstance(mask_or_bits, torch.Tensor):
+        raise ValueError("the mask must be a tensor: bool / uint8 (B,Hs,Ws) or (Hs,Ws), or int32 bit words with Ws")
+    if mask_or_bits.dtype == torch.int32:
+        bits = mask_or_bits
+        if bits.dim() != 3 or bits.numel() == 0 or Ws is None or int(Ws) < 1 or bits.shape[2] != (int(Ws) + 31) // 32:
+            raise ValueError(f"bit words {tuple(bits.shape)} must be a non-empty (B, Hs, ceil(Ws / 32)) with Ws given, got Ws = {Ws!r}")
+        return bits, int(Ws)
+    if mask_or_bits.dtype not in (torch.bool, torch.uint8) or mask_or_bits.dim() not in (2, 3) or mask_or_bits.numel() == 0:
+        raise ValueError(f"the mask must be a non-empty bool / uint8 (B,Hs,Ws) or (Hs,Ws), got {mask_or_bits.dtype} {tuple(mask_or_bits.shape)}")
+    if Ws is not None and int(Ws) != mask_or_bits.shape[-1]:
+        raise ValueError(f"Ws = {Ws!r} differs from the mask's width {mask_or_bits.shape[-1]}")
+    return None, int(mask_or_bits.shape[-1])
+
+
+def _mask_words(mask_or_bits, Ws):
+    """_bits_arg with the mask packed: (bits (B,Hs,P) int32, Ws)."""
+    bits, Ws = _bits_arg(mask_or_bits, Ws)
+    return (mask_bits(mask_or_bits) if bits is None else bits), Ws
+
+
 def mask_rle(mask_or_bits, Ws=None, max_runs=None):
     """Area, box and uncompressed COCO run-length code of any mask, exact and on the device (fs_mask_rle; no autograd).  The argument
     is a bool / uint8 mask (B,Hs,Ws) or (Hs,Ws), or int32 bit words (B,Hs,ceil(Ws/32)) as mask_bits returns them together with Ws.
@@ -1591,16 +1613,7 @@ def mask_rle(mask_or_bits, Ws=None, max_runs=None):
     top of the next; an empty mask is [Hs * Ws], a full one [0, Hs * Ws].  n_runs is always the true length of the code; the first
     min(n_runs, max_runs) entries of counts are its, the rest is 0, and n_runs > max_runs tells that the code was cut.  max_runs
     defaults to 8 * Ws + 1 (see _max_runs).  The format is restated from its published definition (pycocotools' uncompressed RLE)."""
-    if mask_or_bits.dtype == torch.int32:
-        bits = mask_or_bits
-        if bits.dim() != 3 or bits.numel() == 0 or Ws is None or int(Ws) < 1 or bits.shape[2] != (int(Ws) + 31) // 32:
-            raise ValueError(f"bit words {tuple(bits.shape)} must be a non-empty (B, Hs, ceil(Ws / 32)) with Ws given, got Ws = {Ws!r}")
-        Ws = int(Ws)
-    else:
-        if Ws is not None and int(Ws) != mask_or_bits.shape[-1]:
-            raise ValueError(f"Ws = {Ws!r} differs from the mask's width {mask_or_bits.shape[-1]}")
-        bits = mask_bits(mask_or_bits)
-        Ws = int(mask_or_bits.shape[-1])
+    bits, Ws = _mask_words(mask_or_bits, Ws)
     B, Hs = int(bits.shape[0]), int(bits.shape[1])
     cap = _max_runs(max_runs, Ws)
     stats = torch.empty(B, 6, device=bits.device, dtype=torch.int64)
@@ -1641,16 +1654,7 @@ def mask_component(mask_or_bits, focus, Ws=None, connectivity=8, snap_px=None):
     (bits_c (B,Hs,ceil(Ws/32)) int32, the component's words, all 0 where there is none; comp (B,4) int64 = (seed_y, seed_x, d2, area_all),
     (-1, -1, -1, area_all) where there is none; area_all counts the input's set pixels).  mask_rle(bits_c, Ws) gives its record."""
     conn, snap2 = _component_args(connectivity, snap_px)
-    if mask_or_bits.dtype == torch.int32:
-        bits = mask_or_bits
-        if bits.dim() != 3 or bits.numel() == 0 or Ws is None or int(Ws) < 1 or bits.shape[2] != (int(Ws) + 31) // 32:
-            raise ValueError(f"bit words {tuple(bits.shape)} must be a non-empty (B, Hs, ceil(Ws / 32)) with Ws given, got Ws = {Ws!r}")
-        Ws = int(Ws)
-    else:
-        if Ws is not None and int(Ws) != mask_or_bits.shape[-1]:
-            raise ValueError(f"Ws = {Ws!r} differs from the mask's width {mask_or_bits.shape[-1]}")
-        bits = mask_bits(mask_or_bits)
-        Ws = int(mask_or_bits.shape[-1])
+    bits, Ws = _mask_words(mask_or_bits, Ws)
     B, Hs = int(bits.shape[0]), int(bits.shape[1])
     f = _focus_arg(focus, B, bits.device)
     out = torch.empty_like(bits, memory_format=torch.contiguous_format)
@@ -1680,22 +1684,6 @@ def _morph_d(d):
     return d
 
 
-def _bits_arg(mask_or_bits, Ws):
-    """(bits (B,Hs,P) int32, Ws) of a mask argument as mask_rle / mask_component take it."""
-    if not isinstance(mask_or_bits, torch.Tensor):
-        raise ValueError("the mask must be a tensor: bool / uint8 (B,Hs,Ws) or (Hs,Ws), or int32 bit words with Ws")
-    if mask_or_bits.dtype == torch.int32:
-        bits = mask_or_bits
-        if bits.dim() != 3 or bits.numel() == 0 or Ws is None or int(Ws) < 1 or bits.shape[2] != (int(Ws) + 31) // 32:
-            raise ValueError(f"bit words {tuple(bits.shape)} must be a non-empty (B, Hs, ceil(Ws / 32)) with Ws given, got Ws = {Ws!r}")
-        return bits, int(Ws)
-    if mask_or_bits.dtype not in (torch.bool, torch.uint8) or mask_or_bits.dim() not in (2, 3) or mask_or_bits.numel() == 0:
-        raise ValueError(f"the mask must be a non-empty bool / uint8 (B,Hs,Ws) or (Hs,Ws), got {mask_or_bits.dtype} {tuple(mask_or_bits.shape)}")
-    if Ws is not None and int(Ws) != mask_or_bits.shape[-1]:
-        raise ValueError(f"Ws = {Ws!r} differs from the mask's width {mask_or_bits.shape[-1]}")
-    return None, int(mask_or_bits.shape[-1])
-
-
 def mask_erode(mask_or_bits, d, Ws=None):
     """Erosion of a mask by a (2d+1) x (2d+1) square, on the device and on bit words (fs_mask_erode; no autograd; unpinned: restated
     from the published definition of Boundary IoU).  The mask as mask_rle takes it: bool / uint8 (B,Hs,Ws) or (Hs,Ws), or int32 bit
@@ -1703,9 +1691,7 @@ def mask_erode(mask_or_bits, d, Ws=None):
     (y,x) is set iff every pixel of the square centred on it is set, every pixel outside the image counting as unset -- scipy's
     binary_erosion(m, ones((3,3)), iterations=d, border_value=0); all 0 where 2d+1 exceeds a side."""
     d = _morph_d(d)
-    bits, Ws = _bits_arg(mask_or_bits, Ws)
-    if bits is None:
-        bits = mask_bits(mask_or_bits)
+    bits, Ws = _mask_words(mask_or_bits, Ws)
     B, Hs = int(bits.shape[0]), int(bits.shape[1])
     out = torch.empty_like(bits, memory_format=torch.contiguous_format)
     scratch = torch.empty(max(1, hip.query("fs_mask_erode_scratch_ints", B, Hs, Ws, d)), device=bits.device, dtype=torch.int32)
@@ -1718,9 +1704,7 @@ def mask_boundary(mask_or_bits, d, Ws=None):
     image's outside (chessboard distance); the mask itself where 2d+1 exceeds a side.  Arguments as mask_erode's; the bits at
     x >= Ws of the result are 0."""
     d = _morph_d(d)
-    bits, Ws = _bits_arg(mask_or_bits, Ws)
-    if bits is None:
-        bits = mask_bits(mask_or_bits)
+    bits, Ws = _mask_words(mask_or_bits, Ws)
     er = mask_erode(bits, d, Ws)
     band = bits & ~er
     if Ws & 31:
@@ -1805,7 +1789,8 @@ def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False, sco
     Hs, Ws = int(Hs), int(Ws)
     cap = _max_runs(max_runs, Ws)
     dev = cls.device
-    if component is not None:
+    comp = component is not None
+    if comp:
         conn, snap2 = _component_args(component, snap_px)
         if focus is None:
             raise ValueError("component needs focus (B, 2): the gaze that picks it")
@@ -1814,27 +1799,16 @@ def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False, sco
     stats = torch.empty(B, 6, device=dev, dtype=torch.int64)
     counts = torch.empty(B, cap, device=dev, dtype=torch.int32)
     bits = torch.empty(B, Hs, (Ws + 31) // 32, device=dev, dtype=torch.int32) if return_bits else None
-    if component is not None:
-        comp = torch.empty(B, 4, device=dev, dtype=torch.int64)
-        conf = torch.empty(B, 3, device=dev, dtype=torch.float32) if score else None
-        qsum = torch.empty(B, device=dev, dtype=torch.int64) if score else None
-        scratch = torch.empty(hip.query("fs_unwarp_instances_component_scratch_ints", B, h, w, Hs, Ws), device=dev, dtype=torch.int32)
-        hip.call("fs_unwarp_instances_component", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(f),
-                 hip.ptr(cat), hip.ptr(stats), hip.ptr(counts), hip.ptr(bits), hip.ptr(comp), hip.ptr(conf), hip.ptr(qsum), hip.ptr(scratch),
-                 B, K, h, w, Hs, Ws, cap, conn, snap2)
-        out = (cat, stats, counts) + ((bits,) if return_bits else ()) + ((conf, qsum) if score else ())
-        return out + (comp,)
-    if score:
-        conf = torch.empty(B, 3, device=dev, dtype=torch.float32)
-        qsum = torch.empty(B, device=dev, dtype=torch.int64)
-        scratch = torch.empty(hip.query("fs_unwarp_instances_scored_scratch_ints", B, h, w, Hs, Ws), device=dev, dtype=torch.int32)
-        hip.call("fs_unwarp_instances_scored", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(cat),
-                 hip.ptr(stats), hip.ptr(counts), hip.ptr(bits), hip.ptr(conf), hip.ptr(qsum), hip.ptr(scratch), B, K, h, w, Hs, Ws, cap)
-        return (cat, stats, counts, bits, conf, qsum) if return_bits else (cat, stats, counts, conf, qsum)
-    scratch = torch.empty(hip.query("fs_unwarp_instances_scratch_ints", B, h, w, Hs, Ws), device=dev, dtype=torch.int32)
-    hip.call("fs_unwarp_instances", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(cat),
-             hip.ptr(stats), hip.ptr(counts), hip.ptr(bits), hip.ptr(scratch), B, K, h, w, Hs, Ws, cap)
-    return (cat, stats, counts, bits) if return_bits else (cat, stats, counts)
+    conf = torch.empty(B, 3, device=dev, dtype=torch.float32) if score else None
+    qsum = torch.empty(B, device=dev, dtype=torch.int64) if score else None
+    cout = torch.empty(B, 4, device=dev, dtype=torch.int64) if comp else None
+    # the smallest entry point for what is asked; the component's takes conf and qsum null for no score
+    name = "fs_unwarp_instances_component" if comp else "fs_unwarp_instances_scored" if score else "fs_unwarp_instances"
+    scratch = torch.empty(hip.query(name + "_scratch_ints", B, h, w, Hs, Ws), device=dev, dtype=torch.int32)
+    tensors = ([cls.contiguous(), m.contiguous(), grid.contiguous()] + ([f] if comp else []) + [cat, stats, counts, bits] +
+               ([cout] if comp else []) + ([conf, qsum] if comp or score else []) + [scratch])
+    hip.call(name, *[hip.ptr(t) for t in tensors], B, K, h, w, Hs, Ws, cap, *((conn, snap2) if comp else ()))
+    return (cat, stats, counts) + ((bits,) if return_bits else ()) + ((conf, qsum) if score else ()) + ((cout,) if comp else ())
 
 
 def instances_to_coco(cat, stats, counts, seg_size, image_ids=None, conf=None):

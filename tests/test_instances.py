@@ -400,6 +400,27 @@ def test_new_entry_points_stay_inside_their_scratch(Hs, Ws):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("Hs,Ws,K", [(8, 8, 4), (37, 300, 6), (9, 7, 4)])
+def test_instances_scratch_off_16_bytes(Hs, Ws, K):
+    """A scratch that is only 4-byte aligned takes the one-pixel gather at every width, also where Ws % 4 == 0 and an aligned one takes
+    four pixels a thread (test_instance_score.py has the scored entry point's case).  The results are the aligned call's."""
+    import kernel_testing as KT
+    cls, m, grid = _tp()._inputs(2, K, 9, 11, Hs * 1000 + Ws)
+    B, cap, P = 2, 8 * Ws + 1, (Ws + 31) // 32
+    want = ops.unwarp_instances(cls, m, grid, Hs, Ws, return_bits=True)
+    ints = hip.query("fs_unwarp_instances_scratch_ints", B, 9, 11, Hs, Ws)
+    scr = KT.Out(ints + 4, torch.int32)
+    assert scr.ptr % 16 == 0
+    o = [KT.Out(B, torch.int64), KT.Out(B * 6, torch.int64), KT.Out(B * cap, torch.int32), KT.Out(B * Hs * P, torch.int32, fill=0x3C3C3C3D)]
+    hip.call("fs_unwarp_instances", cls.data_ptr(), m.data_ptr(), grid.data_ptr(), *[t.ptr for t in o], scr.ptr + 4, B, K, 9, 11, Hs, Ws, cap)
+    body = scr.get(complete=False)
+    assert int(body[0]) == -9999 and bool((body[ints + 1:] == -9999).all())             # the ints before and behind the shifted scratch
+    assert len(want) == 4
+    for t, w in zip(o, want):
+        assert torch.equal(t.get().view(w.shape), w.cpu())
+
+
+@pytest.mark.gpu
 def test_new_entry_points_reject_bad_arguments():
     B, K, h, w, Hs, Ws, cap = 1, 4, 4, 4, 8, 8, 20
     cls, m, grid = _tp()._inputs(B, K, h, w, 0)
