@@ -8,7 +8,11 @@
 //            the viewer's slots; every viewer's previous gaze and age advance.
 // The pixel code q and the gaze in 1/16-pixel units are one function each, used by every pass that needs them: a frame against the
 // key that commit made from it differs nowhere, NaN pixels included.
+// A frame may also come as bytes (pixel value byte / 255, whose code q is the byte): fs_gate_tiles_u8 and fs_gate_commit_u8 are the tile
+// pass on 6 bytes a pixel and the key copy; decide, and commit's state and row passes, are the same kernels for both.
 #include "common.h"
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -126,6 +130,102 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_tiles_kernel(const float* _
       k[c] = key[at + c * plane];
     }
     s += gate_absdiff(v[0], k[0]) + gate_absdiff(v[1], k[1]) + gate_absdiff(v[2], k[2]);
+  }
+  s = gate_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) sad[blk] = red[0] + red[1] + red[2] + red[3];
+}
+
+constexpr int GATE_SEG_U8 = 1024;                      // the byte form: the most columns a workgroup covers, sixteen a lane
+
+// The byte form of the tile pass (fs_gate_tiles_u8): the frame is bytes as the key is, the pixel code is the byte itself, 6 bytes read
+// per pixel.  The 16-pixel form (W % 16 == 0, img and key 16-byte aligned) keeps the band cut above: one workgroup per (viewer, tile
+// row, segment), a lane takes sixteen pixels of a row -- one 16-byte load of img and one of key per channel, four v_sad_u8 each -- and
+// a lane's sixteen pixels are one tile's for T >= 16, two tiles' for T = 8 (s0 the first eight, s1 the last).  A row takes 1 << lg lanes, the least power
+// of two that covers min(W, 1024) columns and is no less than a tile's lanes; the 64 >> lg rows of a wave are neighbours, the four
+// waves take the row groups in turn.  A tile's lanes meet by shuffles inside a row, then across the rows of the wave, the waves through LDS.
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_u8_band_kernel(const unsigned char* __restrict__ img,
+                                                                          const unsigned char* __restrict__ key, int* __restrict__ sad, int H,
+                                                                          int W, int T, int th, int tw, int nseg, int lg) {
+  __shared__ int red[GATE_THREADS / 64][GATE_SEG_U8 / 8];
+  const unsigned int blk = blockIdx.x;
+  const int seg = (int)(blk % (unsigned)nseg);
+  const int ty = (int)((blk / (unsigned)nseg) % (unsigned)th);
+  const size_t b = blk / (unsigned)nseg / (unsigned)th;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lpr = 1 << lg, sub = 64 >> lg;              // lanes a row, rows a wave
+  const int cl = lane & (lpr - 1), rs = lane >> lg;
+  const int y0 = ty * T, rows = min(T, H - y0);
+  const int x = (seg << (lg + 4)) + cl * 16;
+  const size_t plane = (size_t)H * W;
+  unsigned int s0 = 0, s1 = 0;
+  if (x < W) {
+    const size_t base = b * 3 * plane + (size_t)y0 * W + x;
+#pragma unroll 2
+    for (int r = wave * sub + rs; r < rows; r += (GATE_THREADS / 64) * sub) {
+      const size_t at = base + (size_t)r * W;
+      u32x4 v[3], k[3];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        v[c] = *reinterpret_cast<const u32x4*>(img + at + c * plane);
+        k[c] = *reinterpret_cast<const u32x4*>(key + at + c * plane);
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        s0 = __builtin_amdgcn_sad_u8(v[c].x, k[c].x, s0);
+        s0 = __builtin_amdgcn_sad_u8(v[c].y, k[c].y, s0);
+        s1 = __builtin_amdgcn_sad_u8(v[c].z, k[c].z, s1);
+        s1 = __builtin_amdgcn_sad_u8(v[c].w, k[c].w, s1);
+      }
+    }
+  }
+  int a0 = (int)s0, a1 = (int)s1;
+  if (T >= 16) {
+    a0 += a1;
+    for (int o = (T >> 4) >> 1; o > 0; o >>= 1) a0 += __shfl_xor(a0, o, 64);      // the T / 16 lanes of a tile
+  }
+  for (int o = lpr; o < 64; o <<= 1) {                  // the rows of the wave
+    a0 += __shfl_xor(a0, o, 64);
+    a1 += __shfl_xor(a1, o, 64);
+  }
+  if (rs == 0) {
+    if (T == 8) {
+      red[wave][2 * cl] = a0;
+      red[wave][2 * cl + 1] = a1;
+    } else if ((cl & ((T >> 4) - 1)) == 0) {
+      red[wave][cl / (T >> 4)] = a0;
+    }
+  }
+  __syncthreads();
+  const int per_seg = (lpr * 16) / T;                   // at most 128 entries a segment, one a lane
+  const int tx = seg * per_seg + (int)threadIdx.x;
+  if ((int)threadIdx.x < per_seg && tx < tw)
+    sad[(b * th + ty) * tw + tx] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// The one-pixel byte form, for any width and alignment: gate_tiles_kernel's cut, a workgroup a tile.
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_u8_kernel(const unsigned char* __restrict__ img, const unsigned char* __restrict__ key,
+                                                                     int* __restrict__ sad, int H, int W, int T, int th, int tw) {
+  __shared__ int red[GATE_THREADS / 64];
+  const unsigned int blk = blockIdx.x;
+  const int tx = (int)(blk % (unsigned)tw);
+  const int ty = (int)((blk / (unsigned)tw) % (unsigned)th);
+  const size_t b = blk / (unsigned)tw / (unsigned)th;
+  const int y0 = ty * T, x0 = tx * T;
+  const int rows = min(T, H - y0), cols = min(T, W - x0);
+  const size_t plane = (size_t)H * W;
+  const size_t base = b * 3 * plane + (size_t)y0 * W + x0;
+  int s = 0;
+  const int per = rows * cols;
+  for (int j = threadIdx.x; j < per; j += GATE_THREADS) {
+    const int r = j / cols, x = j - r * cols;
+    const size_t at = base + (size_t)r * W + x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int d = (int)img[at + c * plane] - (int)key[at + c * plane];
+      s += d < 0 ? -d : d;
+    }
   }
   s = gate_wave_sum(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -262,6 +362,21 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_kernel(const f
   }
 }
 
+// key[idx[j]] <- img[idx[j]] for a frame of bytes (fs_gate_commit_u8): the pixel code is the byte, so this is a copy.  VEC (the viewer's
+// 3 * H * W bytes a multiple of 16, img and key 16-byte aligned): sixteen bytes a lane; one byte a lane otherwise.
+template <bool VEC>
+__global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_u8_kernel(const unsigned char* __restrict__ img, const int* __restrict__ idx,
+                                                                            unsigned char* __restrict__ key, int B, size_t per, unsigned int bpi) {
+  const unsigned int j = blockIdx.x / bpi;
+  const int b = idx[j];
+  if (b < 0 || b >= B) return;                         // an index outside the batch writes nothing
+  const size_t e = ((size_t)(blockIdx.x - j * bpi) * GATE_THREADS + threadIdx.x) * (VEC ? 16 : 1);
+  if (e >= per) return;
+  const size_t at = (size_t)b * per + e;
+  if (VEC) *reinterpret_cast<u32x4*>(key + at) = *reinterpret_cast<const u32x4*>(img + at);
+  else key[at] = img[at];
+}
+
 // The record tensors as rows of 32-bit words (an int64 is two): cat 2, stats 12, counts cap, bits H * P, conf 3.  src == dst (or a
 // null pair, conf) is a part of no words.
 struct GateRows {
@@ -293,6 +408,74 @@ bool gate_vec_ok(const float* img, const unsigned char* key, int W) {
   return W % 4 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)key & 3) == 0;
 }
 
+bool gate_vec_u8_ok(const unsigned char* img, const unsigned char* key, int W) {
+  return W % 16 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)key & 15) == 0;
+}
+
+// the frame pass of commit by the frame's type: lanes take 4 floats / 16 bytes where vec
+bool gate_frame_vec(const float* img, const unsigned char* key, int W, size_t) { return gate_vec_ok(img, key, W); }
+bool gate_frame_vec(const unsigned char* img, const unsigned char* key, int, size_t per) {
+  return per % 16 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)key & 15) == 0;
+}
+int gate_frame_lane(const float*) { return 4; }
+int gate_frame_lane(const unsigned char*) { return 16; }
+void gate_commit_frame(const float* img, const int* idx, unsigned char* key, int B, size_t per, bool vec, long wgs, long bpi, hipStream_t stream) {
+  if (vec)
+    hipLaunchKernelGGL(gate_commit_frame_kernel<true>, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
+  else
+    hipLaunchKernelGGL(gate_commit_frame_kernel<false>, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
+}
+void gate_commit_frame(const unsigned char* img, const int* idx, unsigned char* key, int B, size_t per, bool vec, long wgs, long bpi,
+                       hipStream_t stream) {
+  if (vec)
+    hipLaunchKernelGGL(gate_commit_frame_u8_kernel<true>, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
+  else
+    hipLaunchKernelGGL(gate_commit_frame_u8_kernel<false>, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
+}
+
+// fs_gate_commit / fs_gate_commit_u8: the checks, the state pass, the frame pass of the frame's type, the row pass
+template <typename T>
+int gate_commit_run(const T* img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus, const long long* src_cat,
+                    const long long* src_stats, const int* src_counts, const unsigned int* src_bits, const float* src_conf, long long* dst_cat,
+                    long long* dst_stats, int* dst_counts, unsigned int* dst_bits, float* dst_conf, int B, int H, int W, int cap,
+                    hipStream_t stream) {
+  FS_REQUIRE(img && key && gstate && focus && B > 0 && H > 0 && W > 0 && (long)H * W < GATE_INT_LIMIT && n >= 0 && n <= B);
+  FS_REQUIRE(H <= GATE_MAX_SIDE && W <= GATE_MAX_SIDE && cap >= 1);
+  FS_REQUIRE(src_cat && src_stats && src_counts && src_bits && dst_cat && dst_stats && dst_counts && dst_bits);
+  FS_REQUIRE((src_conf == nullptr) == (dst_conf == nullptr) && (n == 0 || idx != nullptr));
+  const size_t per = (size_t)3 * H * W;
+  const bool vec = gate_frame_vec(img, key, W, per);
+  const long bpi = (long)((per / (vec ? gate_frame_lane(img) : 1) + GATE_THREADS - 1) / GATE_THREADS);
+  GateRows r;
+  const long nbits = (long)H * ((W + 31) / 32);
+  const void* src[5] = {src_cat, src_stats, src_counts, src_bits, src_conf};
+  void* dst[5] = {dst_cat, dst_stats, dst_counts, dst_bits, dst_conf};
+  const long words[5] = {2, 12, cap, nbits, 3};
+  long total = 0;
+  for (int k = 0; k < 5; ++k) {
+    const bool moves = src[k] != nullptr && src[k] != dst[k];
+    r.src[k] = static_cast<const unsigned int*>(src[k]);
+    r.dst[k] = static_cast<unsigned int*>(dst[k]);
+    r.words[k] = moves ? (unsigned int)words[k] : 0u;
+    total += moves ? words[k] : 0;
+  }
+  FS_REQUIRE(total < GATE_INT_LIMIT);
+  r.total = (unsigned int)total;
+  const long bpr = (total + GATE_THREADS - 1) / GATE_THREADS;
+  FS_REQUIRE((long)n * bpi <= GATE_WGS_MAX && (long)n * bpr <= GATE_WGS_MAX);
+  hipLaunchKernelGGL(gate_commit_state_kernel, dim3((unsigned)cdiv(B, GATE_THREADS)), dim3(GATE_THREADS), 0, stream, idx, n, gstate, focus, B, H, W);
+  FS_LAUNCH_CHECK();
+  if (n == 0) return FS_OK;
+  gate_commit_frame(img, idx, key, B, per, vec, n * bpi, bpi, stream);
+  FS_LAUNCH_CHECK();
+  if (total > 0) {
+    hipLaunchKernelGGL(gate_commit_rows_kernel, dim3((unsigned)(n * bpr)), dim3(GATE_THREADS), 0, stream, idx, B, r, (unsigned)bpr);
+    FS_LAUNCH_CHECK();
+  }
+  return FS_OK;
+}
+
+
 }  // namespace
 
 extern "C" {
@@ -308,6 +491,24 @@ int fs_gate_tiles(const float* img, const unsigned char* key, int* sad, int B, i
     hipLaunchKernelGGL(gate_tiles_band_kernel, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, key, sad, H, W, T, th, tw, nseg);
   else
     hipLaunchKernelGGL(gate_tiles_kernel, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, key, sad, H, W, T, th, tw);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+int fs_gate_tiles_u8(const unsigned char* img, const unsigned char* key, int* sad, int B, int H, int W, int T, hipStream_t stream) {
+  FS_REQUIRE(img && key && sad && B > 0 && H > 0 && W > 0 && gate_tile_ok(T) && (long)H * W < GATE_INT_LIMIT);
+  const int th = cdiv(H, T), tw = cdiv(W, T);
+  FS_REQUIRE((long)B * th * tw <= GATE_WGS_MAX);
+  if (gate_vec_u8_ok(img, key, W)) {
+    int lg = 0;                                         // lanes a row: covers min(W, 1024) columns, and a tile's T / 16 lanes
+    while (lg < 6 && (16 << lg) < W) ++lg;
+    while ((16 << lg) < T) ++lg;
+    const int nseg = cdiv(W, 16 << lg);
+    hipLaunchKernelGGL(gate_tiles_u8_band_kernel, dim3((unsigned)((long)B * th * nseg)), dim3(GATE_THREADS), 0, stream, img, key, sad, H, W, T,
+                       th, tw, nseg, lg);
+  } else {
+    hipLaunchKernelGGL(gate_tiles_u8_kernel, dim3((unsigned)((long)B * th * tw)), dim3(GATE_THREADS), 0, stream, img, key, sad, H, W, T, th, tw);
+  }
   FS_LAUNCH_CHECK();
   return FS_OK;
 }
@@ -330,43 +531,16 @@ int fs_gate_commit(const float* img, const int* idx, int n, unsigned char* key, 
                    const long long* src_cat, const long long* src_stats, const int* src_counts, const unsigned int* src_bits,
                    const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts, unsigned int* dst_bits, float* dst_conf,
                    int B, int H, int W, int cap, hipStream_t stream) {
-  FS_REQUIRE(img && key && gstate && focus && B > 0 && H > 0 && W > 0 && (long)H * W < GATE_INT_LIMIT && n >= 0 && n <= B);
-  FS_REQUIRE(H <= GATE_MAX_SIDE && W <= GATE_MAX_SIDE && cap >= 1);
-  FS_REQUIRE(src_cat && src_stats && src_counts && src_bits && dst_cat && dst_stats && dst_counts && dst_bits);
-  FS_REQUIRE((src_conf == nullptr) == (dst_conf == nullptr) && (n == 0 || idx != nullptr));
-  const size_t per = (size_t)3 * H * W;
-  const bool vec = gate_vec_ok(img, key, W);
-  const long bpi = (long)((per / (vec ? 4 : 1) + GATE_THREADS - 1) / GATE_THREADS);
-  GateRows r;
-  const long nbits = (long)H * ((W + 31) / 32);
-  const void* src[5] = {src_cat, src_stats, src_counts, src_bits, src_conf};
-  void* dst[5] = {dst_cat, dst_stats, dst_counts, dst_bits, dst_conf};
-  const long words[5] = {2, 12, cap, nbits, 3};
-  long total = 0;
-  for (int k = 0; k < 5; ++k) {
-    const bool moves = src[k] != nullptr && src[k] != dst[k];
-    r.src[k] = static_cast<const unsigned int*>(src[k]);
-    r.dst[k] = static_cast<unsigned int*>(dst[k]);
-    r.words[k] = moves ? (unsigned int)words[k] : 0u;
-    total += moves ? words[k] : 0;
-  }
-  FS_REQUIRE(total < GATE_INT_LIMIT);
-  r.total = (unsigned int)total;
-  const long bpr = (total + GATE_THREADS - 1) / GATE_THREADS;
-  FS_REQUIRE((long)n * bpi <= GATE_WGS_MAX && (long)n * bpr <= GATE_WGS_MAX);
-  hipLaunchKernelGGL(gate_commit_state_kernel, dim3((unsigned)cdiv(B, GATE_THREADS)), dim3(GATE_THREADS), 0, stream, idx, n, gstate, focus, B, H, W);
-  FS_LAUNCH_CHECK();
-  if (n == 0) return FS_OK;
-  if (vec)
-    hipLaunchKernelGGL(gate_commit_frame_kernel<true>, dim3((unsigned)(n * bpi)), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
-  else
-    hipLaunchKernelGGL(gate_commit_frame_kernel<false>, dim3((unsigned)(n * bpi)), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
-  FS_LAUNCH_CHECK();
-  if (total > 0) {
-    hipLaunchKernelGGL(gate_commit_rows_kernel, dim3((unsigned)(n * bpr)), dim3(GATE_THREADS), 0, stream, idx, B, r, (unsigned)bpr);
-    FS_LAUNCH_CHECK();
-  }
-  return FS_OK;
+  return gate_commit_run(img, idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat, dst_stats, dst_counts, dst_bits,
+                         dst_conf, B, H, W, cap, stream);
+}
+
+int fs_gate_commit_u8(const unsigned char* img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus,
+                      const long long* src_cat, const long long* src_stats, const int* src_counts, const unsigned int* src_bits,
+                      const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts, unsigned int* dst_bits, float* dst_conf,
+                      int B, int H, int W, int cap, hipStream_t stream) {
+  return gate_commit_run(img, idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat, dst_stats, dst_counts, dst_bits,
+                         dst_conf, B, H, W, cap, stream);
 }
 
 }  // extern "C"

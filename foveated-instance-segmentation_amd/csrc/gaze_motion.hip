@@ -12,7 +12,8 @@
 //            back; one lane a viewer moves the gazes and the totals and writes the motion row; fs_mask_rle's passes re-encode the moved
 //            words into scratch rows that reach stats / counts for the moving viewers alone; the key profiles are taken again.
 //   commit   for the viewers whose record was made anew: the frame's profiles become the key's, the totals 0.
-// The pixel code q is the gate's (gaze_gate.hip), restated here operation for operation.
+// The pixel code q is the gate's (gaze_gate.hip), restated here operation for operation.  For a frame of bytes (pixel value byte / 255,
+// q the byte) the profiles are fs_key_profiles of the frame, and fs_state_shift_u8 fills the key's border with the frame's bytes.
 #include "common.h"
 
 extern "C" {
@@ -255,6 +256,52 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_move_kernel(const float
   }
 }
 
+// motion_move_kernel for a frame of bytes (fs_state_shift_u8): the uncovered border is filled with the frame's byte, the pixel code of
+// such a frame.  Everything else as above.
+template <int V>
+__global__ __launch_bounds__(MOTION_THREADS) void motion_move_u8_kernel(const unsigned char* __restrict__ img, const long long* __restrict__ shift,
+                                                                        const unsigned char* __restrict__ key, unsigned char* __restrict__ key2,
+                                                                        const unsigned int* __restrict__ bits, unsigned int* __restrict__ bits2,
+                                                                        int H, int W, int P, unsigned int nk, unsigned int nb) {
+  const size_t b = blockIdx.x / (nk + nb);
+  const unsigned int r = blockIdx.x - (unsigned int)b * (nk + nb);
+  if (motion_still(shift, b)) return;
+  const int dy = (int)shift[4 * b], dx = (int)shift[4 * b + 1];
+  if (r < nk) {
+    const size_t plane = (size_t)H * W, per = 3 * plane;
+    const unsigned char* ib = img + b * per;
+    const unsigned char* kb = key + b * per;
+    unsigned char* ob = key2 + b * per;
+    for (int it = 0; it < MOTION_ITER; ++it) {
+      const size_t e = (((size_t)r * MOTION_ITER + it) * MOTION_THREADS + threadIdx.x) * V;
+      if (e >= per) return;
+      const int c = (int)(e / plane);
+      const int rem = (int)(e - c * plane);
+      const int y = rem / W, x = rem - y * W;
+      const int sy = y - dy;
+      const bool row_in = sy >= 0 && sy < H;
+      const size_t srow = c * plane + (size_t)(row_in ? sy : 0) * W;
+      unsigned int out = 0;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {                    // V == 4: W % 4 == 0, the four pixels lie in one row
+        const int sx = x + j - dx;
+        const unsigned int k = (row_in && sx >= 0 && sx < W) ? (unsigned int)kb[srow + sx] : (unsigned int)ib[e + j];
+        out |= k << (8 * j);
+      }
+      if (V == 4) *reinterpret_cast<unsigned int*>(ob + e) = out;
+      else ob[e] = (unsigned char)out;
+    }
+  } else {
+    const unsigned int w = (r - nk) * MOTION_THREADS + threadIdx.x;
+    if (w >= (unsigned int)(H * P)) return;
+    const int y = (int)(w / (unsigned)P), c = (int)(w - (unsigned)y * P);
+    const int sy = y - dy;
+    unsigned int out = 0;
+    if (sy >= 0 && sy < H) out = motion_get(bits + (b * H + sy) * P, P, W, 32 * c - dx) & motion_tail(c, P, W);
+    bits2[b * H * P + w] = out;
+  }
+}
+
 // key <- key2 and bits <- bits2 for the moving viewers; lane 0 of a viewer's first workgroup moves its gazes and totals and writes its
 // motion row (every viewer).  gstate (B,6) as the gate's; mstate (B,4) = (dy_total, dx_total, moves, path); motion (B,6) = (dy, dx,
 // cost_best, cost_zero, dy_total, dx_total).
@@ -362,6 +409,68 @@ int motion_profiles(const T* src, const long long* shift, int* prof, int B, int 
 
 long motion_pad2(long v) { return (v + 1) & ~1L; }
 
+// the move pass by the frame's type
+template <int V>
+void motion_move(const float* img, const long long* shift, const unsigned char* key, unsigned char* key2, const unsigned int* bits,
+                 unsigned int* bits2, int H, int W, int P, long nk, long nb, dim3 grid, hipStream_t stream) {
+  hipLaunchKernelGGL(motion_move_kernel<V>, grid, dim3(MOTION_THREADS), 0, stream, img, shift, key, key2, bits, bits2, H, W, P, (unsigned)nk,
+                     (unsigned)nb);
+}
+template <int V>
+void motion_move(const unsigned char* img, const long long* shift, const unsigned char* key, unsigned char* key2, const unsigned int* bits,
+                 unsigned int* bits2, int H, int W, int P, long nk, long nb, dim3 grid, hipStream_t stream) {
+  hipLaunchKernelGGL(motion_move_u8_kernel<V>, grid, dim3(MOTION_THREADS), 0, stream, img, shift, key, key2, bits, bits2, H, W, P, (unsigned)nk,
+                     (unsigned)nb);
+}
+
+// fs_state_shift / fs_state_shift_u8: the checks and every pass, the move pass of the frame's type
+template <typename T>
+int motion_state_shift(const T* img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
+                       long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch, int B,
+                       int H, int W, int cap, hipStream_t stream) {
+  FS_REQUIRE(img && shift && key && key2 && bits && bits2 && gstate && stats && counts && prof_key && mstate && motion && scratch);
+  FS_REQUIRE(motion_sizes_ok(B, H, W) && cap >= 1 && H <= MOTION_MAX_SIDE && W <= MOTION_MAX_SIDE && key != key2 && bits != bits2);
+  FS_REQUIRE(((uintptr_t)scratch & 7) == 0 && fs_mask_rle_scratch_ints(B, H, W) > 0);
+  const int P = (W + 31) / 32, n = H + W;
+  const size_t per = (size_t)3 * H * W;
+  const bool vec = W % 4 == 0 && ((uintptr_t)key & 3) == 0 && ((uintptr_t)key2 & 3) == 0;
+  const long chunk = (long)MOTION_THREADS * MOTION_ITER * (vec ? 4 : 1);
+  const long nk = (long)((per + chunk - 1) / chunk), nb = cdiv((long)H * P, MOTION_THREADS);
+  const long bpv = cdiv(12L + cap + n, MOTION_THREADS);
+  FS_REQUIRE((long)B * (nk + nb) <= MOTION_WGS_MAX && (long)B * bpv <= MOTION_WGS_MAX && 12L + cap + n < MOTION_INT_LIMIT);
+  FS_REQUIRE((long)B * cdiv(n, MOTION_THREADS) <= MOTION_WGS_MAX && (long)B * cdiv(W, MOTION_SEG) * cdiv(H, MOTION_BAND) <= MOTION_WGS_MAX);
+  long long* stats2 = reinterpret_cast<long long*>(scratch);
+  int* counts2 = scratch + 12L * B;
+  int* rle = counts2 + motion_pad2((long)B * cap);
+  const dim3 grid((unsigned)(B * (nk + nb))), block(MOTION_THREADS);
+  if (vec) {
+    motion_move<4>(img, shift, key, key2, bits, bits2, H, W, P, nk, nb, grid, stream);
+    FS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(motion_back_kernel<4>, grid, block, 0, stream, shift, key2, key, bits2, bits, gstate, mstate, motion, H, W, P, (unsigned)nk,
+                       (unsigned)nb);
+  } else {
+    motion_move<1>(img, shift, key, key2, bits, bits2, H, W, P, nk, nb, grid, stream);
+    FS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(motion_back_kernel<1>, grid, block, 0, stream, shift, key2, key, bits2, bits, gstate, mstate, motion, H, W, P, (unsigned)nk,
+                       (unsigned)nb);
+  }
+  FS_LAUNCH_CHECK();
+  FS_TRY(fs_mask_rle(bits, stats2, counts2, rle, B, H, W, cap, stream));
+  hipLaunchKernelGGL(motion_finish_kernel, dim3((unsigned)(B * bpv)), block, 0, stream, shift, reinterpret_cast<const unsigned int*>(stats2),
+                     reinterpret_cast<const unsigned int*>(counts2), reinterpret_cast<unsigned int*>(stats), reinterpret_cast<unsigned int*>(counts),
+                     prof_key, cap, n, (unsigned)bpv);
+  FS_LAUNCH_CHECK();
+  const dim3 pgrid((unsigned)(B * cdiv(W, MOTION_SEG) * cdiv(H, MOTION_BAND)));
+  const int nseg = cdiv(W, MOTION_SEG), nband = cdiv(H, MOTION_BAND);
+  if (vec)
+    hipLaunchKernelGGL((motion_profile_kernel<unsigned char, true>), pgrid, block, 0, stream, key, shift, prof_key, H, W, nseg, nband);
+  else
+    hipLaunchKernelGGL((motion_profile_kernel<unsigned char, false>), pgrid, block, 0, stream, key, shift, prof_key, H, W, nseg, nband);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+
 }  // namespace
 
 extern "C" {
@@ -396,46 +505,13 @@ long fs_state_shift_scratch_ints(int B, int H, int W, int cap) {
 int fs_state_shift(const float* img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
                    long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch, int B,
                    int H, int W, int cap, hipStream_t stream) {
-  FS_REQUIRE(img && shift && key && key2 && bits && bits2 && gstate && stats && counts && prof_key && mstate && motion && scratch);
-  FS_REQUIRE(motion_sizes_ok(B, H, W) && cap >= 1 && H <= MOTION_MAX_SIDE && W <= MOTION_MAX_SIDE && key != key2 && bits != bits2);
-  FS_REQUIRE(((uintptr_t)scratch & 7) == 0 && fs_mask_rle_scratch_ints(B, H, W) > 0);
-  const int P = (W + 31) / 32, n = H + W;
-  const size_t per = (size_t)3 * H * W;
-  const bool vec = W % 4 == 0 && ((uintptr_t)key & 3) == 0 && ((uintptr_t)key2 & 3) == 0;
-  const long chunk = (long)MOTION_THREADS * MOTION_ITER * (vec ? 4 : 1);
-  const long nk = (long)((per + chunk - 1) / chunk), nb = cdiv((long)H * P, MOTION_THREADS);
-  const long bpv = cdiv(12L + cap + n, MOTION_THREADS);
-  FS_REQUIRE((long)B * (nk + nb) <= MOTION_WGS_MAX && (long)B * bpv <= MOTION_WGS_MAX && 12L + cap + n < MOTION_INT_LIMIT);
-  FS_REQUIRE((long)B * cdiv(n, MOTION_THREADS) <= MOTION_WGS_MAX && (long)B * cdiv(W, MOTION_SEG) * cdiv(H, MOTION_BAND) <= MOTION_WGS_MAX);
-  long long* stats2 = reinterpret_cast<long long*>(scratch);
-  int* counts2 = scratch + 12L * B;
-  int* rle = counts2 + motion_pad2((long)B * cap);
-  const dim3 grid((unsigned)(B * (nk + nb))), block(MOTION_THREADS);
-  if (vec) {
-    hipLaunchKernelGGL(motion_move_kernel<4>, grid, block, 0, stream, img, shift, key, key2, bits, bits2, H, W, P, (unsigned)nk, (unsigned)nb);
-    FS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(motion_back_kernel<4>, grid, block, 0, stream, shift, key2, key, bits2, bits, gstate, mstate, motion, H, W, P, (unsigned)nk,
-                       (unsigned)nb);
-  } else {
-    hipLaunchKernelGGL(motion_move_kernel<1>, grid, block, 0, stream, img, shift, key, key2, bits, bits2, H, W, P, (unsigned)nk, (unsigned)nb);
-    FS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(motion_back_kernel<1>, grid, block, 0, stream, shift, key2, key, bits2, bits, gstate, mstate, motion, H, W, P, (unsigned)nk,
-                       (unsigned)nb);
-  }
-  FS_LAUNCH_CHECK();
-  FS_TRY(fs_mask_rle(bits, stats2, counts2, rle, B, H, W, cap, stream));
-  hipLaunchKernelGGL(motion_finish_kernel, dim3((unsigned)(B * bpv)), block, 0, stream, shift, reinterpret_cast<const unsigned int*>(stats2),
-                     reinterpret_cast<const unsigned int*>(counts2), reinterpret_cast<unsigned int*>(stats), reinterpret_cast<unsigned int*>(counts),
-                     prof_key, cap, n, (unsigned)bpv);
-  FS_LAUNCH_CHECK();
-  const dim3 pgrid((unsigned)(B * cdiv(W, MOTION_SEG) * cdiv(H, MOTION_BAND)));
-  const int nseg = cdiv(W, MOTION_SEG), nband = cdiv(H, MOTION_BAND);
-  if (vec)
-    hipLaunchKernelGGL((motion_profile_kernel<unsigned char, true>), pgrid, block, 0, stream, key, shift, prof_key, H, W, nseg, nband);
-  else
-    hipLaunchKernelGGL((motion_profile_kernel<unsigned char, false>), pgrid, block, 0, stream, key, shift, prof_key, H, W, nseg, nband);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
+  return motion_state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch, B, H, W, cap, stream);
+}
+
+int fs_state_shift_u8(const unsigned char* img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
+                      long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch, int B,
+                      int H, int W, int cap, hipStream_t stream) {
+  return motion_state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch, B, H, W, cap, stream);
 }
 
 int fs_motion_commit(const int* idx, int n, const int* prof, int* prof_key, long long* mstate, int B, int H, int W, hipStream_t stream) {

@@ -63,6 +63,11 @@ SIGNATURES = {
     "fs_profile_shift": "pppp" + "iiiii",
     "fs_state_shift": "p" * 13 + "iiii",
     "fs_motion_commit": "p" + "i" + "ppp" + "iii",
+    "fs_gaze_lowres_u8_fwd": "pppiiiii",
+    "fs_grid_sample_u8_fwd": "pppiiiiiii",
+    "fs_gate_tiles_u8": "ppp" + "iiii",
+    "fs_gate_commit_u8": "pp" + "i" + "p" * 13 + "iiii",
+    "fs_state_shift_u8": "p" * 13 + "iiii",
     "fs_conv2d_fwd": "ppppiiiiiiiiiiiifuplp",
     "fs_conv2d_fwd_residual": "ppppp" + "iiiiiiiiiiii" + "fufu" + "l" + "plp",
     "fs_conv2d_fwd_stats": "pppppiiiiiiiiiiiifuplp",

@@ -198,7 +198,9 @@ class DeformSegmentationModule(nn.Module):
 
     def _head_parts(self, img, focus, seg_size, who):
         """predict's / evaluate's shared front: argument checks, then forward's stages up to the C1 head's two factors.
-        Returns (cls (B,K), m (B,h,w), grid (B,h,w,2), seg_size as two ints)."""
+        Returns (cls (B,K), m (B,h,w), grid (B,h,w,2), seg_size as two ints).  img is fp32, or a planar torch.uint8 frame whose pixel
+        value is byte / 255 correctly rounded: the results equal those of the fp32 frame of that quotient bit for bit, and the frame is
+        read as bytes by the two gathers of the front (ops.gaze_lowres, ops.grid_sample_u8)."""
         if self.training:
             raise RuntimeError(f"{who}() needs eval mode (module.eval()): in train mode the encoder would update its BatchNorm running statistics")
         if img.dim() != 4 or img.shape[1] != 3:
@@ -218,7 +220,9 @@ class DeformSegmentationModule(nn.Module):
         if self.cfg.MODEL.uniform_sample != "":
             xs = xs * 0 + 1.0 / (self.grid_size_x * self.grid_size_y)       # as forward, models/models.py:816-818
         grid = self.create_grid(xs)
-        feat = self.encoder.forward_nhwc(ops.GridSample.apply(x, grid))
+        # a frame of bytes (pixel value byte / 255) is read by the two gathers of the front alone: no fp32 frame is made
+        sampled = ops.grid_sample_u8(x, grid) if x.dtype == torch.uint8 else ops.GridSample.apply(x, grid)
+        feat = self.encoder.forward_nhwc(sampled)
         cls, m = self.decoder.forward_parts_nhwc(feat)
         return cls, m, grid, (int(seg_size[0]), int(seg_size[1]))
 
@@ -226,7 +230,8 @@ class DeformSegmentationModule(nn.Module):
     def predict(self, img, focus, seg_size=None):
         """Label-free inference: which class every full-resolution pixel of `img` belongs to, given the gaze point `focus`.
 
-        img (B,3,H,W) as forward's img_data, focus (B,2) as its focus_point; returns the int64 class map (B, *seg_size), seg_size
+        img (B,3,H,W) as forward's img_data -- or the same frame as torch.uint8, pixel value byte / 255, which gives the same result bit
+        for bit without an fp32 frame (predict_instances, evaluate and evaluate_instances likewise) --, focus (B,2) as its focus_point; returns the int64 class map (B, *seg_size), seg_size
         defaulting to (H, W).  The stages are forward's -- saliency, the sampling grid (uniform_sample and the task-size up-sampling
         included), GridSample, encoder, C1 head -- then the inverse warp with nearest hole filling and the argmax over classes
         (models/models.py:639-655,930-940; eval.py:195), fused in ops.unwarp_labels so that no (B,K,*seg_size) prediction exists.

@@ -1337,6 +1337,9 @@ def gaze_lowres(x, focus, hs, ws):
     B, C, H, W = x.shape
     assert C == 3
     out = torch.empty(B, hs, ws, 5, device=x.device, dtype=torch.float32)
+    if x.dtype == torch.uint8:                          # a frame of bytes: four one-byte taps a channel, 12 bytes read and 20 written a point
+        _launch("fe_gaze_lowres_u8", 1.0 * B * hs * ws * (12 + 20), "fs_gaze_lowres_u8_fwd", hip.ptr(x), hip.ptr(focus), hip.ptr(out), B, H, W, hs, ws)
+        return out
     _launch("fe_gaze_lowres", 4.0 * B * hs * ws * (4 * 3 + 5), "fs_gaze_lowres_fwd", hip.ptr(x), hip.ptr(focus), hip.ptr(out), B, H, W, hs, ws)
     return out
 
@@ -1498,6 +1501,20 @@ class GridSample(Function):
             dx = torch.empty_like(x)
             hip.call("fs_grid_sample_bwd_input", hip.ptr(gout), hip.ptr(grid), hip.ptr(dx), B, C, H, W, h, w, 1)
         return dx, dgrid
+
+
+def grid_sample_u8(x, grid):
+    """GridSample's forward on a frame of bytes (fs_grid_sample_u8_fwd; no autograd): x (B,C,H,W) uint8 with the pixel value byte / 255,
+    grid (B,h,w,2) fp32 -> (B,h,w,C) fp32 NHWC, equal to GridSample.apply(x.float() / 255, grid) bit for bit."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.numel() == 0 or x.dtype != torch.uint8:
+        raise ValueError(f"x must be a non-empty uint8 (B,C,H,W), got {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))}")
+    B, C, H, W = (int(v) for v in x.shape)
+    if grid.dim() != 4 or grid.shape[0] != B or grid.shape[3] != 2 or grid.numel() == 0 or grid.dtype != torch.float32:
+        raise ValueError(f"grid must be a non-empty fp32 ({B},h,w,2), got {grid.dtype} {tuple(grid.shape)}")
+    h, w = int(grid.shape[1]), int(grid.shape[2])
+    out = torch.empty(B, h, w, C, device=x.device, dtype=torch.float32)
+    _launch("fe_grid_sample_u8_fwd", 1.0 * B * h * w * (4 * C + 8 + 4 * C), "fs_grid_sample_u8_fwd", hip.ptr(x), hip.ptr(grid), hip.ptr(out), B, C, H, W, h, w, 1)
+    return out
 
 
 def grid_sample_label(y, grid, return_float=False):
@@ -1862,14 +1879,11 @@ def _gate_tile(T):
     return int(T)
 
 
-def gate_tiles(img, key, tile=32, out=None):
-    """How much every tile of new frames differs from the 8-bit key frames (fs_gate_tiles; no autograd; unpinned: the reference has
-    no counterpart).  img (B,3,H,W) fp32, key (B,3,H,W) uint8 = q of the frames the records were made from, q(v) = rint(clamp(v, 0, 1) *
-    255) in fp32, NaN -> 0.  Returns sad (B,th,tw) int32, th = ceil(H / tile), tw = ceil(W / tile): the sum of |q(img) - key| over the
-    three channels and the tile's pixels (the last tiles are ragged).  out: a (B,th,tw) int32 tensor to write into."""
+def _gate_tiles(name, dtype, img, key, tile, out):
     T = _gate_tile(tile)
-    if img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != torch.float32:
-        raise ValueError(f"img must be a non-empty fp32 (B,3,H,W), got {img.dtype} {tuple(img.shape)}")
+    what = "fp32" if dtype == torch.float32 else "uint8"
+    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
+        raise ValueError(f"img must be a non-empty {what} (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
     if key.dtype != torch.uint8 or key.shape != img.shape:
         raise ValueError(f"key must be uint8 {tuple(img.shape)}, got {key.dtype} {tuple(key.shape)}")
     B, _, H, W = (int(v) for v in img.shape)
@@ -1878,8 +1892,22 @@ def gate_tiles(img, key, tile=32, out=None):
         out = torch.empty(shape, device=img.device, dtype=torch.int32)
     elif out.dtype != torch.int32 or tuple(out.shape) != shape:
         raise ValueError(f"out must be int32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    hip.call("fs_gate_tiles", hip.ptr(img), hip.ptr(key), hip.ptr(out), B, H, W, T)
+    hip.call(name, hip.ptr(img), hip.ptr(key), hip.ptr(out), B, H, W, T)
     return out
+
+
+def gate_tiles(img, key, tile=32, out=None):
+    """How much every tile of new frames differs from the 8-bit key frames (fs_gate_tiles; no autograd; unpinned: the reference has
+    no counterpart).  img (B,3,H,W) fp32, key (B,3,H,W) uint8 = q of the frames the records were made from, q(v) = rint(clamp(v, 0, 1) *
+    255) in fp32, NaN -> 0.  Returns sad (B,th,tw) int32, th = ceil(H / tile), tw = ceil(W / tile): the sum of |q(img) - key| over the
+    three channels and the tile's pixels (the last tiles are ragged).  out: a (B,th,tw) int32 tensor to write into."""
+    return _gate_tiles("fs_gate_tiles", torch.float32, img, key, tile, out)
+
+
+def gate_tiles_u8(img, key, tile=32, out=None):
+    """gate_tiles for frames of bytes (fs_gate_tiles_u8): img (B,3,H,W) uint8, the pixel value byte / 255, whose code q is the byte.  sad
+    is the sum of |img - key|, equal to gate_tiles(img.float() / 255, key, tile); 6 bytes read a pixel instead of 15."""
+    return _gate_tiles("fs_gate_tiles_u8", torch.uint8, img, key, tile, out)
 
 
 def gate_decide(sad, gstate, focus, stats, bits, frame_size, tile=32, level=8, scene_tiles=0, roi_tiles=0, margin=16,
@@ -1917,16 +1945,14 @@ def gate_decide(sad, gstate, focus, stats, bits, frame_size, tile=32, level=8, s
     return out
 
 
-def gate_commit(img, idx, key, gstate, focus, src, dst):
-    """What a step leaves behind (fs_gate_commit; no autograd; unpinned), in place.  idx (n,) int32 ascending, or None for n = 0: the
-    viewers whose record was made anew from img (B,3,H,W) fp32.  src = (cat, stats, counts, bits[, conf]) with n rows, dst the same
-    with B rows: row j moves to row idx[j]; a pair that is one tensor is already in place.  For the viewers of idx key (B,3,H,W) uint8
-    <- q(img), g_key <- g, age <- 0, valid <- 1 in gstate (B,6) int64; for every viewer g_prev <- g; any other viewer's age grows by
-    one.  With n = 0 src is not read (pass dst)."""
+def _gate_commit(name, dtype, img, idx, key, gstate, focus, src, dst):
+    what = "fp32" if dtype == torch.float32 else "uint8"
+    if (not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype
+            or key.dtype != torch.uint8 or key.shape != img.shape):
+        raise ValueError(f"img must be a non-empty {what} (B,3,H,W) and key uint8 of its shape, got {getattr(img, 'dtype', None)} "
+                         f"{tuple(getattr(img, 'shape', ()))} and {tuple(key.shape)}")
     B, _, H, W = (int(v) for v in img.shape)
     n = 0 if idx is None else int(idx.shape[0])
-    if img.dim() != 4 or img.shape[1] != 3 or img.dtype != torch.float32 or key.dtype != torch.uint8 or key.shape != img.shape:
-        raise ValueError(f"img must be fp32 (B,3,H,W) and key uint8 of its shape, got {tuple(img.shape)} and {tuple(key.shape)}")
     if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 1 or n > B):
         raise ValueError(f"idx must be int32 (n,) with n <= {B}, got {idx.dtype} {tuple(idx.shape)}")
     if gstate.dtype != torch.int64 or tuple(gstate.shape) != (B, 6) or focus.dtype != torch.float32 or tuple(focus.shape) != (B, 2):
@@ -1943,7 +1969,22 @@ def gate_commit(img, idx, key, gstate, focus, src, dst):
             raise ValueError(f"a src record tensor must be {dt} {(n,) + tail}, got {s.dtype} {tuple(s.shape)}")
     sp = [hip.ptr(s) for s in src] + [None] * (5 - len(src))
     dp = [hip.ptr(d) for d in dst] + [None] * (5 - len(dst))
-    hip.call("fs_gate_commit", hip.ptr(img), hip.ptr(idx), n, hip.ptr(key), hip.ptr(gstate), hip.ptr(focus), *sp, *dp, B, H, W, cap)
+    hip.call(name, hip.ptr(img), hip.ptr(idx), n, hip.ptr(key), hip.ptr(gstate), hip.ptr(focus), *sp, *dp, B, H, W, cap)
+
+
+def gate_commit(img, idx, key, gstate, focus, src, dst):
+    """What a step leaves behind (fs_gate_commit; no autograd; unpinned), in place.  idx (n,) int32 ascending, or None for n = 0: the
+    viewers whose record was made anew from img (B,3,H,W) fp32.  src = (cat, stats, counts, bits[, conf]) with n rows, dst the same
+    with B rows: row j moves to row idx[j]; a pair that is one tensor is already in place.  For the viewers of idx key (B,3,H,W) uint8
+    <- q(img), g_key <- g, age <- 0, valid <- 1 in gstate (B,6) int64; for every viewer g_prev <- g; any other viewer's age grows by
+    one.  With n = 0 src is not read (pass dst)."""
+    _gate_commit("fs_gate_commit", torch.float32, img, idx, key, gstate, focus, src, dst)
+
+
+def gate_commit_u8(img, idx, key, gstate, focus, src, dst):
+    """gate_commit for frames of bytes (fs_gate_commit_u8): img (B,3,H,W) uint8; for the viewers of idx key <- img, a copy.  Everything
+    else as gate_commit, and equal to it on img.float() / 255."""
+    _gate_commit("fs_gate_commit_u8", torch.uint8, img, idx, key, gstate, focus, src, dst)
 
 
 MOTION_MAX_PX = 255                                 # fs_profile_shift's largest search range
@@ -2037,16 +2078,9 @@ def state_shift_scratch(B, H, W, cap, device):
     return torch.empty(hip.query("fs_state_shift_scratch_ints", int(B), int(H), int(W), int(cap)), device=device, dtype=torch.int32)
 
 
-def state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion=None, scratch=None):
-    """Move the state of every viewer whose shift is not (0, 0), in place (fs_state_shift; no autograd; unpinned).  img (B,3,H,W) fp32
-    the new frames; shift (B,4) int64 as profile_shift returns it; key (B,3,H,W) uint8 and bits (B,H,ceil(W/32)) int32 are moved by (dy,
-    dx) -- the key's uncovered border is filled with q(img), the mask's with 0 -- through the spare buffers key2 and bits2 of the same
-    shapes, whose contents afterwards are unspecified; the four gaze coordinates of gstate (B,6) int64 move by 16 * d, clamped; stats
-    (B,6) int64 and counts (B,cap) int32 become mask_rle's of the moved bits; prof_key (B, H + W) int32 becomes key_profiles of the
-    moved key; mstate (B,4) int64 = (dy_total, dx_total, moves, path) grows.  A still viewer's rows are not written.  Returns motion
-    (B,6) int64 = (dy, dx, cost_best, cost_zero, dy_total, dx_total), written for every viewer.  scratch: state_shift_scratch(...)."""
-    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != torch.float32:
-        raise ValueError(f"img must be a non-empty fp32 (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
+def _state_shift(entry, dtype, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch):
+    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
+        raise ValueError(f"img must be a non-empty {'fp32' if dtype == torch.float32 else 'uint8'} (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
     B, _, H, W = (int(v) for v in img.shape)
     _profile_sizes(B, H, W)
     P = (W + 31) // 32
@@ -2075,9 +2109,26 @@ def state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_
         scratch = torch.empty(need, device=img.device, dtype=torch.int32)
     elif scratch.dtype != torch.int32 or scratch.dim() != 1 or scratch.numel() < need:
         raise ValueError(f"scratch must be int32 with at least {need} entries, got {scratch.dtype} {tuple(scratch.shape)}")
-    hip.call("fs_state_shift", hip.ptr(img), hip.ptr(shift), hip.ptr(key), hip.ptr(key2), hip.ptr(bits), hip.ptr(bits2), hip.ptr(gstate),
+    hip.call(entry, hip.ptr(img), hip.ptr(shift), hip.ptr(key), hip.ptr(key2), hip.ptr(bits), hip.ptr(bits2), hip.ptr(gstate),
              hip.ptr(stats), hip.ptr(counts), hip.ptr(prof_key), hip.ptr(mstate), hip.ptr(motion), hip.ptr(scratch), B, H, W, cap)
     return motion
+
+
+def state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion=None, scratch=None):
+    """Move the state of every viewer whose shift is not (0, 0), in place (fs_state_shift; no autograd; unpinned).  img (B,3,H,W) fp32
+    the new frames; shift (B,4) int64 as profile_shift returns it; key (B,3,H,W) uint8 and bits (B,H,ceil(W/32)) int32 are moved by (dy,
+    dx) -- the key's uncovered border is filled with q(img), the mask's with 0 -- through the spare buffers key2 and bits2 of the same
+    shapes, whose contents afterwards are unspecified; the four gaze coordinates of gstate (B,6) int64 move by 16 * d, clamped; stats
+    (B,6) int64 and counts (B,cap) int32 become mask_rle's of the moved bits; prof_key (B, H + W) int32 becomes key_profiles of the
+    moved key; mstate (B,4) int64 = (dy_total, dx_total, moves, path) grows.  A still viewer's rows are not written.  Returns motion
+    (B,6) int64 = (dy, dx, cost_best, cost_zero, dy_total, dx_total), written for every viewer.  scratch: state_shift_scratch(...)."""
+    return _state_shift("fs_state_shift", torch.float32, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch)
+
+
+def state_shift_u8(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion=None, scratch=None):
+    """state_shift for frames of bytes (fs_state_shift_u8): img (B,3,H,W) uint8; the key's uncovered border is filled with the frame's
+    byte.  Everything else as state_shift, and equal to it on img.float() / 255; the scratch is the same."""
+    return _state_shift("fs_state_shift_u8", torch.uint8, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch)
 
 
 def motion_commit(idx, prof, prof_key, mstate, frame_size):

@@ -155,8 +155,10 @@ class GazeSession:
 
     @torch.no_grad()
     def step(self, img, focus, force=None):
-        """One frame per viewer.  img (B,3,H,W) fp32 and focus (B,2) as predict_instances takes them, on the device; force: None, or B
-        flags (any sequence or tensor), non-zero = re-make this viewer's record now.
+        """One frame per viewer.  img (B,3,H,W) fp32, or uint8 with the pixel value byte / 255, and focus (B,2) as predict_instances takes
+        them, on the device; force: None, or B flags (any sequence or tensor), non-zero = re-make this viewer's record now.  A uint8 frame
+        gives what img.float() / 255 gives bit for bit and is never converted: gate, commit, motion, the selection of the viewers that run
+        and the network's front all read the bytes.  The state is the same tensors either way, so the dtype may change from step to step.
 
         Returns (cat, stats, counts, bits[, conf], gate[, motion]): the record of every viewer as predict_instances(img, focus, return_bits=True)
         makes it -- made now for the viewers that ran, the held one for the others -- and gate (B,8) int64 on the host = (code,
@@ -170,8 +172,8 @@ class GazeSession:
         if self.module.training:
             raise RuntimeError("GazeSession.step() needs eval mode (module.eval()): in train mode the encoder would update its BatchNorm running statistics")
         B, H, W = self.batch, self.H, self.W
-        if not isinstance(img, torch.Tensor) or tuple(img.shape) != (B, 3, H, W) or img.dtype != torch.float32:
-            raise ValueError(f"img must be fp32 {(B, 3, H, W)}, got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
+        if not isinstance(img, torch.Tensor) or tuple(img.shape) != (B, 3, H, W) or img.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"img must be fp32 or uint8 {(B, 3, H, W)}, got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
         if not isinstance(focus, torch.Tensor) or tuple(focus.shape) != (B, 2):
             raise ValueError(f"focus must be ({B}, 2), got {tuple(getattr(focus, 'shape', ()))}")
         if not img.is_cuda or focus.device != img.device:
@@ -184,12 +186,17 @@ class GazeSession:
         x = img.contiguous()
         f = focus.float().contiguous()
         moving = self.motion_px is not None
+        # a frame of bytes stays bytes: its pixel code is the byte, so its profiles are key_profiles of it and the gate compares bytes
+        if x.dtype == torch.uint8:
+            profiles, state_shift, gate_tiles, gate_commit = ops.key_profiles, ops.state_shift_u8, ops.gate_tiles_u8, ops.gate_commit_u8
+        else:
+            profiles, state_shift, gate_tiles, gate_commit = ops.frame_profiles, ops.state_shift, ops.gate_tiles, ops.gate_commit
         if moving:
-            ops.frame_profiles(x, out=self._prof)
+            profiles(x, out=self._prof)
             ops.profile_shift(self._prof, self._prof_key, self._gstate, (H, W), self.motion_px, self.motion_gain, out=self._shift)
-            ops.state_shift(x, self._shift, self._key, self._key2, self._rec[3], self._bits2, self._gstate, self._rec[1], self._rec[2],
-                            self._prof_key, self._mstate, motion=self._motion, scratch=self._scratch)
-        ops.gate_tiles(x, self._key, self.tile, out=self._sad)
+            state_shift(x, self._shift, self._key, self._key2, self._rec[3], self._bits2, self._gstate, self._rec[1], self._rec[2],
+                        self._prof_key, self._mstate, motion=self._motion, scratch=self._scratch)
+        gate_tiles(x, self._key, self.tile, out=self._sad)
         ops.gate_decide(self._sad, self._gstate, f, self._rec[1], self._rec[3], (H, W), tile=self.tile, level=self.level,
                         scene_tiles=self.scene_tiles, roi_tiles=self.roi_tiles, margin=self.roi_margin, saccade2=self.saccade2,
                         fixation2=self.fixation2, max_age=self.max_age, inside_on=self.inside_on, force=fdev, out=self._gate)
@@ -203,7 +210,7 @@ class GazeSession:
             self.counts[c] += 1
         run = [b for b, c in enumerate(codes) if c in ops.GATE_RUNS]
         if not run:
-            ops.gate_commit(x, None, self._key, self._gstate, f, self._rec, self._rec)
+            gate_commit(x, None, self._key, self._gstate, f, self._rec, self._rec)
         else:
             idx = torch.tensor(run, dtype=torch.int32, device=img.device)
             if len(run) == B:
@@ -219,7 +226,7 @@ class GazeSession:
             if len(run) == B:
                 # every record is new: the tensors predict_instances made become the session's, nothing is copied
                 self._rec = new
-            ops.gate_commit(x, idx, self._key, self._gstate, f, new, self._rec)
+            gate_commit(x, idx, self._key, self._gstate, f, new, self._rec)
             if moving:
                 ops.motion_commit(idx, self._prof, self._prof_key, self._mstate, (H, W))
         if moving:

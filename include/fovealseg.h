@@ -375,6 +375,32 @@ int fs_state_shift(const float* img, const long long* shift, unsigned char* key,
  * profiles: the profiles of the key frame commit made) and mstate <- 0.  n == 0 launches nothing, idx may be null; an idx entry outside
  * 0 .. B-1 writes nothing.  FS_ERR_ARG for a null pointer, n outside 0 .. B, and as fs_frame_profiles for the sizes. */
 int fs_motion_commit(const int* idx, int n, const int* prof, int* prof_key, long long* mstate, int B, int H, int W, fs_stream_t stream);
+/* Frames as bytes (no counterpart in the reference: UNPINNED).  A uint8 frame is planar (B,3,H,W) bytes, contiguous; its
+ * pixel value is v = (float)byte / 255.0f, correctly rounded (fs_ingest_sample's expression), and its pixel code q(v) is the byte itself.
+ * Each entry point below equals its fp32 twin fed byte / 255 bit for bit, and returns FS_ERR_ARG, with nothing launched, under the twin's
+ * conditions.  The profiles of such a frame are fs_key_profiles of it.
+ * fs_gaze_lowres_u8_fwd: fs_gaze_lowres_fwd with the four taps of every low-resolution point converted as they are read. */
+int fs_gaze_lowres_u8_fwd(const unsigned char* x, const float* focus, float* out, int B, int H, int W, int hs, int ws, fs_stream_t stream);
+/* fs_grid_sample_fwd on bytes, forward only: x (B,C,H,W) bytes, out fp32 (B,h,w,C) [nhwc_out=1] or (B,C,h,w) [nhwc_out=0]; the taps of
+ * fs_grid_sample_fwd, an out-of-bounds tap 0.f, the same multiply and three fused multiply-adds. */
+int fs_grid_sample_u8_fwd(const unsigned char* x, const float* grid, float* out, int B, int C, int H, int W, int h, int w, int nhwc_out,
+                          fs_stream_t stream);
+/* fs_gate_tiles on bytes, the hot pass: sad (B,th,tw) int32 = the sum over the 3 channels and the tile's pixels of |img - key|, 6 bytes read
+ * per pixel, plain stores, no atomics.  Sixteen pixels a lane (one 16-byte load of img and of key per channel, four v_sad_u8 each) where
+ * W % 16 == 0 and both pointers are 16-byte aligned: a row takes the least power of two of lanes that covers min(W, 1024) columns and a
+ * tile, so a wave of a narrow frame takes several rows at once; one pixel a lane otherwise. */
+int fs_gate_tiles_u8(const unsigned char* img, const unsigned char* key, int* sad, int B, int H, int W, int T, fs_stream_t stream);
+/* fs_gate_commit on bytes: key[idx[j]] <- img[idx[j]], a copy (sixteen bytes a lane where 3 * H * W % 16 == 0 and both pointers are 16-byte
+ * aligned); the state and row passes are fs_gate_commit's. */
+int fs_gate_commit_u8(const unsigned char* img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus,
+                      const long long* src_cat, const long long* src_stats, const int* src_counts, const unsigned int* src_bits,
+                      const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts, unsigned int* dst_bits,
+                      float* dst_conf, int B, int H, int W, int cap, fs_stream_t stream);
+/* fs_state_shift on bytes: the key's uncovered border is filled with the frame's byte; every other pass is fs_state_shift's, with the
+ * same scratch (fs_state_shift_scratch_ints). */
+int fs_state_shift_u8(const unsigned char* img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits,
+                      unsigned int* bits2, long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate,
+                      long long* motion, int* scratch, int B, int H, int W, int cap, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
