@@ -10,7 +10,10 @@
 // key that commit made from it differs nowhere, NaN pixels included.
 // A frame may also come as bytes (pixel value byte / 255, whose code q is the byte): fs_gate_tiles_u8 and fs_gate_commit_u8 are the tile
 // pass on 6 bytes a pixel and the key copy; decide, and commit's state and row passes, are the same kernels for both.
+// A frame of interleaved bytes (frame_view.h) is read where it lies: fs_gate_tiles_hwc and fs_gate_commit_hwc de-interleave sixteen pixels a
+// lane in registers (v_perm_b32), so that v_sad_u8 meets matching bytes and the key stays planar; decide and the shared passes do not change.
 #include "common.h"
+#include "frame_view.h"
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
@@ -233,6 +236,101 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_tiles_u8_kernel(const unsig
   if (threadIdx.x == 0) sad[blk] = red[0] + red[1] + red[2] + red[3];
 }
 
+// The tile pass on an interleaved frame (fs_gate_tiles_hwc), vector form (fs_byte_frame_route = 1, key 16-byte aligned):
+// gate_tiles_u8_band_kernel's cut and sums, lane for lane.  A lane owns the 48 (SX = 3) or 64 (SX = 4) bytes of its sixteen pixels --
+// three or four 16-byte loads, whose lines the wave's neighbours finish -- and splits them into a channel a register quad; the key takes
+// one 16-byte load a channel as there.  The fourth byte of an RGBA pixel is selected by no perm and reaches no sum.
+template <int SX>
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_hwc_band_kernel(const unsigned char* __restrict__ img, long sb, long sy,
+                                                                           const unsigned char* __restrict__ key, int* __restrict__ sad, int H,
+                                                                           int W, int T, int th, int tw, int nseg, int lg) {
+  __shared__ int red[GATE_THREADS / 64][GATE_SEG_U8 / 8];
+  const unsigned int blk = blockIdx.x;
+  const int seg = (int)(blk % (unsigned)nseg);
+  const int ty = (int)((blk / (unsigned)nseg) % (unsigned)th);
+  const size_t b = blk / (unsigned)nseg / (unsigned)th;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lpr = 1 << lg, sub = 64 >> lg;              // lanes a row, rows a wave
+  const int cl = lane & (lpr - 1), rs = lane >> lg;
+  const int y0 = ty * T, rows = min(T, H - y0);
+  const int x = (seg << (lg + 4)) + cl * 16;
+  const size_t plane = (size_t)H * W;
+  unsigned int s0 = 0, s1 = 0;
+  if (x < W) {
+    const size_t base = b * 3 * plane + (size_t)y0 * W + x;
+    const unsigned char* fbase = img + (size_t)b * sb + (size_t)y0 * sy + (size_t)x * SX;
+#pragma unroll 2
+    for (int r = wave * sub + rs; r < rows; r += (GATE_THREADS / 64) * sub) {
+      const size_t at = base + (size_t)r * W;
+      u32x4 v[3], k[3];
+      hwc_load16<SX>(fbase + (size_t)r * sy, v);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) k[c] = *reinterpret_cast<const u32x4*>(key + at + c * plane);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        s0 = __builtin_amdgcn_sad_u8(v[c].x, k[c].x, s0);
+        s0 = __builtin_amdgcn_sad_u8(v[c].y, k[c].y, s0);
+        s1 = __builtin_amdgcn_sad_u8(v[c].z, k[c].z, s1);
+        s1 = __builtin_amdgcn_sad_u8(v[c].w, k[c].w, s1);
+      }
+    }
+  }
+  int a0 = (int)s0, a1 = (int)s1;
+  if (T >= 16) {
+    a0 += a1;
+    for (int o = (T >> 4) >> 1; o > 0; o >>= 1) a0 += __shfl_xor(a0, o, 64);      // the T / 16 lanes of a tile
+  }
+  for (int o = lpr; o < 64; o <<= 1) {                  // the rows of the wave
+    a0 += __shfl_xor(a0, o, 64);
+    a1 += __shfl_xor(a1, o, 64);
+  }
+  if (rs == 0) {
+    if (T == 8) {
+      red[wave][2 * cl] = a0;
+      red[wave][2 * cl + 1] = a1;
+    } else if ((cl & ((T >> 4) - 1)) == 0) {
+      red[wave][cl / (T >> 4)] = a0;
+    }
+  }
+  __syncthreads();
+  const int per_seg = (lpr * 16) / T;                   // at most 128 entries a segment, one a lane
+  const int tx = seg * per_seg + (int)threadIdx.x;
+  if ((int)threadIdx.x < per_seg && tx < tw)
+    sad[(b * th + ty) * tw + tx] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+}
+
+// The one-pixel form on an interleaved frame, for any width, pitch and alignment: gate_tiles_u8_kernel's cut, a workgroup a tile.
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_hwc_kernel(const unsigned char* __restrict__ img, long sb, long sy, int sx,
+                                                                      const unsigned char* __restrict__ key, int* __restrict__ sad, int H, int W,
+                                                                      int T, int th, int tw) {
+  __shared__ int red[GATE_THREADS / 64];
+  const unsigned int blk = blockIdx.x;
+  const int tx = (int)(blk % (unsigned)tw);
+  const int ty = (int)((blk / (unsigned)tw) % (unsigned)th);
+  const size_t b = blk / (unsigned)tw / (unsigned)th;
+  const int y0 = ty * T, x0 = tx * T;
+  const int rows = min(T, H - y0), cols = min(T, W - x0);
+  const size_t plane = (size_t)H * W;
+  const size_t base = b * 3 * plane + (size_t)y0 * W + x0;
+  const unsigned char* fbase = img + (size_t)b * sb + (size_t)y0 * sy + (size_t)x0 * sx;
+  int s = 0;
+  const int per = rows * cols;
+  for (int j = threadIdx.x; j < per; j += GATE_THREADS) {
+    const int r = j / cols, x = j - r * cols;
+    const size_t at = base + (size_t)r * W + x;
+    const unsigned char* f = fbase + (size_t)r * sy + (size_t)x * sx;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int d = (int)f[c] - (int)key[at + c * plane];
+      s += d < 0 ? -d : d;
+    }
+  }
+  s = gate_wave_sum(s);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) sad[blk] = red[0] + red[1] + red[2] + red[3];
+}
+
 struct GateRule {
   int H, W, T, th, tw, P;
   int level, scene_tiles, roi_tiles, margin, max_age, inside_on;
@@ -377,6 +475,34 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_u8_kernel(cons
   else key[at] = img[at];
 }
 
+// key[idx[j]] <- the de-interleaved frame of viewer idx[j] (fs_gate_commit_hwc); the key stays planar.  SX > 0, the vector form (the tile
+// pass's conditions): a lane takes sixteen pixels of a row, splits them as the tile pass does and stores sixteen bytes a channel; per =
+// H * W / 16 such pieces a viewer.  SX = 0, the one-byte form: per = 3 * H * W bytes a viewer, a lane one of them.
+template <int SX>
+__global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_hwc_kernel(const unsigned char* __restrict__ img, long sb, long sy, int sx,
+                                                                             const int* __restrict__ idx, unsigned char* __restrict__ key, int B,
+                                                                             int H, int W, size_t per, unsigned int bpi) {
+  const unsigned int j = blockIdx.x / bpi;
+  const int b = idx[j];
+  if (b < 0 || b >= B) return;                         // an index outside the batch writes nothing
+  const size_t e = (size_t)(blockIdx.x - j * bpi) * GATE_THREADS + threadIdx.x;
+  if (e >= per) return;
+  const size_t plane = (size_t)H * W;
+  if (SX > 0) {
+    const int w16 = W >> 4;
+    const int y = (int)(e / (unsigned)w16), x = (int)(e - (size_t)y * w16) * 16;
+    u32x4 v[3];
+    hwc_load16<(SX > 0 ? SX : 3)>(img + (size_t)b * sb + (size_t)y * sy + (size_t)x * SX, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<u32x4*>(key + ((size_t)b * 3 + c) * plane + (size_t)y * W + x) = v[c];
+  } else {
+    const int c = (int)(e / plane);
+    const size_t rem = e - c * plane;
+    const int y = (int)(rem / (unsigned)W), x = (int)(rem - (size_t)y * W);
+    key[(size_t)b * 3 * plane + e] = img[(size_t)b * sb + (size_t)y * sy + (size_t)x * sx + c];
+  }
+}
+
 // The record tensors as rows of 32-bit words (an int64 is two): cat 2, stats 12, counts cap, bits H * P, conf 3.  src == dst (or a
 // null pair, conf) is a part of no words.
 struct GateRows {
@@ -433,14 +559,37 @@ void gate_commit_frame(const unsigned char* img, const int* idx, unsigned char* 
     hipLaunchKernelGGL(gate_commit_frame_u8_kernel<false>, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
 }
 
-// fs_gate_commit / fs_gate_commit_u8: the checks, the state pass, the frame pass of the frame's type, the row pass
+// an interleaved frame: the vector form takes H * W / 16 pieces a viewer, the one-byte form 3 * H * W bytes
+bool gate_frame_vec(const HwcView& img, const unsigned char* key, int W, size_t) { return hwc_vec_ok(img, W) && ((uintptr_t)key & 15) == 0; }
+int gate_frame_lane(const HwcView&) { return 48; }
+void gate_commit_frame(const HwcView& img, const int* idx, unsigned char* key, int B, size_t per, bool vec, long wgs, long bpi, hipStream_t stream,
+                       int H, int W) {
+  const dim3 grid((unsigned)wgs), block(GATE_THREADS);
+  const size_t units = vec ? per / 48 : per;
+  if (vec && img.sx == 3)
+    hipLaunchKernelGGL(gate_commit_frame_hwc_kernel<3>, grid, block, 0, stream, img.p, img.sb, img.sy, img.sx, idx, key, B, H, W, units, (unsigned)bpi);
+  else if (vec)
+    hipLaunchKernelGGL(gate_commit_frame_hwc_kernel<4>, grid, block, 0, stream, img.p, img.sb, img.sy, img.sx, idx, key, B, H, W, units, (unsigned)bpi);
+  else
+    hipLaunchKernelGGL(gate_commit_frame_hwc_kernel<0>, grid, block, 0, stream, img.p, img.sb, img.sy, img.sx, idx, key, B, H, W, units, (unsigned)bpi);
+}
 template <typename T>
-int gate_commit_run(const T* img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus, const long long* src_cat,
+void gate_commit_frame(const T* img, const int* idx, unsigned char* key, int B, size_t per, bool vec, long wgs, long bpi, hipStream_t stream, int,
+                       int) {
+  gate_commit_frame(img, idx, key, B, per, vec, wgs, bpi, stream);
+}
+inline bool gate_frame_ok(const float*, int, int, int) { return true; }
+inline bool gate_frame_ok(const unsigned char*, int, int, int) { return true; }
+inline bool gate_frame_ok(const HwcView& v, int B, int H, int W) { return hwc_view_ok(v, B, H, W); }
+
+// fs_gate_commit / fs_gate_commit_u8 / fs_gate_commit_hwc: the checks, the state pass, the frame pass of the frame's type, the row pass
+template <typename F>
+int gate_commit_run(F img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus, const long long* src_cat,
                     const long long* src_stats, const int* src_counts, const unsigned int* src_bits, const float* src_conf, long long* dst_cat,
                     long long* dst_stats, int* dst_counts, unsigned int* dst_bits, float* dst_conf, int B, int H, int W, int cap,
                     hipStream_t stream) {
   FS_REQUIRE(img && key && gstate && focus && B > 0 && H > 0 && W > 0 && (long)H * W < GATE_INT_LIMIT && n >= 0 && n <= B);
-  FS_REQUIRE(H <= GATE_MAX_SIDE && W <= GATE_MAX_SIDE && cap >= 1);
+  FS_REQUIRE(H <= GATE_MAX_SIDE && W <= GATE_MAX_SIDE && cap >= 1 && gate_frame_ok(img, B, H, W));
   FS_REQUIRE(src_cat && src_stats && src_counts && src_bits && dst_cat && dst_stats && dst_counts && dst_bits);
   FS_REQUIRE((src_conf == nullptr) == (dst_conf == nullptr) && (n == 0 || idx != nullptr));
   const size_t per = (size_t)3 * H * W;
@@ -466,7 +615,7 @@ int gate_commit_run(const T* img, const int* idx, int n, unsigned char* key, lon
   hipLaunchKernelGGL(gate_commit_state_kernel, dim3((unsigned)cdiv(B, GATE_THREADS)), dim3(GATE_THREADS), 0, stream, idx, n, gstate, focus, B, H, W);
   FS_LAUNCH_CHECK();
   if (n == 0) return FS_OK;
-  gate_commit_frame(img, idx, key, B, per, vec, n * bpi, bpi, stream);
+  gate_commit_frame(img, idx, key, B, per, vec, n * bpi, bpi, stream, H, W);
   FS_LAUNCH_CHECK();
   if (total > 0) {
     hipLaunchKernelGGL(gate_commit_rows_kernel, dim3((unsigned)(n * bpr)), dim3(GATE_THREADS), 0, stream, idx, B, r, (unsigned)bpr);
@@ -541,6 +690,37 @@ int fs_gate_commit_u8(const unsigned char* img, const int* idx, int n, unsigned 
                       int B, int H, int W, int cap, hipStream_t stream) {
   return gate_commit_run(img, idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat, dst_stats, dst_counts, dst_bits,
                          dst_conf, B, H, W, cap, stream);
+}
+
+int fs_gate_tiles_hwc(const unsigned char* img, long sb, long sy, int sx, const unsigned char* key, int* sad, int B, int H, int W, int T,
+                      hipStream_t stream) {
+  FS_REQUIRE(img && key && sad && B > 0 && H > 0 && W > 0 && gate_tile_ok(T) && (long)H * W < GATE_INT_LIMIT);
+  const HwcView v{img, sb, sy, sx};
+  FS_REQUIRE(hwc_view_ok(v, B, H, W));
+  const int th = cdiv(H, T), tw = cdiv(W, T);
+  FS_REQUIRE((long)B * th * tw <= GATE_WGS_MAX);
+  const dim3 block(GATE_THREADS);
+  if (hwc_vec_ok(v, W) && ((uintptr_t)key & 15) == 0) {
+    int lg = 0;                                         // lanes a row, as fs_gate_tiles_u8 chooses them
+    while (lg < 6 && (16 << lg) < W) ++lg;
+    while ((16 << lg) < T) ++lg;
+    const int nseg = cdiv(W, 16 << lg);
+    const dim3 grid((unsigned)((long)B * th * nseg));
+    if (sx == 3) hipLaunchKernelGGL(gate_tiles_hwc_band_kernel<3>, grid, block, 0, stream, img, sb, sy, key, sad, H, W, T, th, tw, nseg, lg);
+    else hipLaunchKernelGGL(gate_tiles_hwc_band_kernel<4>, grid, block, 0, stream, img, sb, sy, key, sad, H, W, T, th, tw, nseg, lg);
+  } else {
+    hipLaunchKernelGGL(gate_tiles_hwc_kernel, dim3((unsigned)((long)B * th * tw)), block, 0, stream, img, sb, sy, sx, key, sad, H, W, T, th, tw);
+  }
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+int fs_gate_commit_hwc(const unsigned char* img, long sb, long sy, int sx, const int* idx, int n, unsigned char* key, long long* gstate,
+                       const float* focus, const long long* src_cat, const long long* src_stats, const int* src_counts,
+                       const unsigned int* src_bits, const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts,
+                       unsigned int* dst_bits, float* dst_conf, int B, int H, int W, int cap, hipStream_t stream) {
+  return gate_commit_run(HwcView{img, sb, sy, sx}, idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat, dst_stats,
+                         dst_counts, dst_bits, dst_conf, B, H, W, cap, stream);
 }
 
 }  // extern "C"

@@ -14,7 +14,10 @@
 //   commit   for the viewers whose record was made anew: the frame's profiles become the key's, the totals 0.
 // The pixel code q is the gate's (gaze_gate.hip), restated here operation for operation.  For a frame of bytes (pixel value byte / 255,
 // q the byte) the profiles are fs_key_profiles of the frame, and fs_state_shift_u8 fills the key's border with the frame's bytes.
+// An interleaved frame of bytes (frame_view.h) is read where it lies: fs_frame_profiles_hwc is the profile pass on it, fs_state_shift_hwc
+// fills the border from it; every other pass is shared.
 #include "common.h"
+#include "frame_view.h"
 
 extern "C" {
 long fs_mask_rle_scratch_ints(int B, int Hs, int Ws);
@@ -123,6 +126,77 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_profile_kernel(const T*
       if (x < W) {
         const size_t at = base + (size_t)r * W;
         l = motion_code(src + at) + motion_code(src + at + plane) + motion_code(src + at + 2 * plane);
+      }
+      acc += l;
+      const int rs = motion_wave_sum(l);
+      if (lane == 0) rsum[wave][r] = rs;
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < rows)
+      atomicAdd(prow + threadIdx.x, rsum[0][threadIdx.x] + rsum[1][threadIdx.x] + rsum[2][threadIdx.x] + rsum[3][threadIdx.x]);
+    if (x < W) atomicAdd(pcol + x, acc);
+  }
+}
+
+// motion_profile_kernel on an interleaved frame of bytes (fs_frame_profiles_hwc): the same cut, sums and atomics.  VEC (fs_byte_frame_route
+// = 1): a lane's four pixels are 12 bytes in three 4-byte loads (SX = 3) or one 16-byte load (SX = 4); a pixel's luma is the sum of its
+// three bytes (v_sad_u8 against 0), the fourth byte of an RGBA pixel masked off.  Otherwise a lane takes one column of the band.
+template <int SX, bool VEC>
+__global__ __launch_bounds__(MOTION_THREADS) void motion_profile_hwc_kernel(const unsigned char* __restrict__ src, long sb, long sy,
+                                                                            int* __restrict__ prof, int H, int W, int nseg, int nband) {
+  __shared__ int red[MOTION_THREADS / 64][MOTION_SEG];
+  __shared__ int rsum[MOTION_THREADS / 64][MOTION_BAND];
+  const unsigned int blk = blockIdx.x;
+  const int seg = (int)(blk % (unsigned)nseg);
+  const int band = (int)((blk / (unsigned)nseg) % (unsigned)nband);
+  const size_t b = blk / (unsigned)nseg / (unsigned)nband;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int y0 = band * MOTION_BAND, rows = min(MOTION_BAND, H - y0);
+  int* prow = prof + b * ((size_t)H + W) + y0;
+  int* pcol = prof + b * ((size_t)H + W) + H;
+  if (VEC) {
+    const int x = seg * MOTION_SEG + lane * 4;
+    const unsigned char* base = src + b * (size_t)sb + (size_t)y0 * sy + (size_t)x * SX;
+    int acc[4] = {0, 0, 0, 0};
+    for (int r = wave; r < rows; r += MOTION_THREADS / 64) {
+      int l[4] = {0, 0, 0, 0};
+      if (x < W) {
+        const unsigned char* at = base + (size_t)r * sy;
+        if (SX == 3) {
+          const unsigned int w0 = *reinterpret_cast<const unsigned int*>(at), w1 = *reinterpret_cast<const unsigned int*>(at + 4),
+                             w2 = *reinterpret_cast<const unsigned int*>(at + 8);
+          l[0] = (int)__builtin_amdgcn_sad_u8(w0 & 0x00ffffffu, 0u, 0u);
+          l[1] = (int)__builtin_amdgcn_sad_u8(w0 >> 24, 0u, __builtin_amdgcn_sad_u8(w1 & 0x0000ffffu, 0u, 0u));
+          l[2] = (int)__builtin_amdgcn_sad_u8(w1 >> 16, 0u, __builtin_amdgcn_sad_u8(w2 & 0x000000ffu, 0u, 0u));
+          l[3] = (int)__builtin_amdgcn_sad_u8(w2 >> 8, 0u, 0u);
+        } else {
+          const hwc_u32x4 v = *reinterpret_cast<const hwc_u32x4*>(at);
+          l[0] = (int)__builtin_amdgcn_sad_u8(v.x & 0x00ffffffu, 0u, 0u);
+          l[1] = (int)__builtin_amdgcn_sad_u8(v.y & 0x00ffffffu, 0u, 0u);
+          l[2] = (int)__builtin_amdgcn_sad_u8(v.z & 0x00ffffffu, 0u, 0u);
+          l[3] = (int)__builtin_amdgcn_sad_u8(v.w & 0x00ffffffu, 0u, 0u);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j) acc[j] += l[j];
+      const int rs = motion_wave_sum(l[0] + l[1] + l[2] + l[3]);
+      if (lane == 0) rsum[0][r] = rs;                   // a row is one wave's
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) red[wave][lane * 4 + j] = acc[j];
+    __syncthreads();
+    if ((int)threadIdx.x < rows) atomicAdd(prow + threadIdx.x, rsum[0][threadIdx.x]);
+    const int xc = seg * MOTION_SEG + (int)threadIdx.x;
+    if (xc < W) atomicAdd(pcol + xc, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
+  } else {
+    const int x = seg * MOTION_SEG + (int)threadIdx.x;
+    const unsigned char* base = src + b * (size_t)sb + (size_t)y0 * sy + (size_t)x * SX;
+    int acc = 0;
+    for (int r = 0; r < rows; ++r) {
+      int l = 0;
+      if (x < W) {
+        const unsigned char* at = base + (size_t)r * sy;
+        l = (int)at[0] + (int)at[1] + (int)at[2];
       }
       acc += l;
       const int rs = motion_wave_sum(l);
@@ -302,6 +376,54 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_move_u8_kernel(const un
   }
 }
 
+// motion_move_u8_kernel for an interleaved frame of bytes (fs_state_shift_hwc): the uncovered border is filled with the frame's byte of
+// that channel, read where it lies.  Everything else as above.
+template <int V>
+__global__ __launch_bounds__(MOTION_THREADS) void motion_move_hwc_kernel(const unsigned char* __restrict__ img, long sb, long sy, int sx,
+                                                                         const long long* __restrict__ shift, const unsigned char* __restrict__ key,
+                                                                         unsigned char* __restrict__ key2, const unsigned int* __restrict__ bits,
+                                                                         unsigned int* __restrict__ bits2, int H, int W, int P, unsigned int nk,
+                                                                         unsigned int nb) {
+  const size_t b = blockIdx.x / (nk + nb);
+  const unsigned int r = blockIdx.x - (unsigned int)b * (nk + nb);
+  if (motion_still(shift, b)) return;
+  const int dy = (int)shift[4 * b], dx = (int)shift[4 * b + 1];
+  if (r < nk) {
+    const size_t plane = (size_t)H * W, per = 3 * plane;
+    const unsigned char* ib = img + b * (size_t)sb;
+    const unsigned char* kb = key + b * per;
+    unsigned char* ob = key2 + b * per;
+    for (int it = 0; it < MOTION_ITER; ++it) {
+      const size_t e = (((size_t)r * MOTION_ITER + it) * MOTION_THREADS + threadIdx.x) * V;
+      if (e >= per) return;
+      const int c = (int)(e / plane);
+      const int rem = (int)(e - c * plane);
+      const int y = rem / W, x = rem - y * W;
+      const int sy0 = y - dy;
+      const bool row_in = sy0 >= 0 && sy0 < H;
+      const size_t srow = c * plane + (size_t)(row_in ? sy0 : 0) * W;
+      const unsigned char* frow = ib + (size_t)y * sy + c;
+      unsigned int out = 0;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {                    // V == 4: W % 4 == 0, the four pixels lie in one row
+        const int sx0 = x + j - dx;
+        const unsigned int k = (row_in && sx0 >= 0 && sx0 < W) ? (unsigned int)kb[srow + sx0] : (unsigned int)frow[(size_t)(x + j) * sx];
+        out |= k << (8 * j);
+      }
+      if (V == 4) *reinterpret_cast<unsigned int*>(ob + e) = out;
+      else ob[e] = (unsigned char)out;
+    }
+  } else {
+    const unsigned int w = (r - nk) * MOTION_THREADS + threadIdx.x;
+    if (w >= (unsigned int)(H * P)) return;
+    const int y = (int)(w / (unsigned)P), c = (int)(w - (unsigned)y * P);
+    const int sy0 = y - dy;
+    unsigned int out = 0;
+    if (sy0 >= 0 && sy0 < H) out = motion_get(bits + (b * H + sy0) * P, P, W, 32 * c - dx) & motion_tail(c, P, W);
+    bits2[b * H * P + w] = out;
+  }
+}
+
 // key <- key2 and bits <- bits2 for the moving viewers; lane 0 of a viewer's first workgroup moves its gazes and totals and writes its
 // motion row (every viewer).  gstate (B,6) as the gate's; mstate (B,4) = (dy_total, dx_total, moves, path); motion (B,6) = (dy, dx,
 // cost_best, cost_zero, dy_total, dx_total).
@@ -423,14 +545,24 @@ void motion_move(const unsigned char* img, const long long* shift, const unsigne
                      (unsigned)nb);
 }
 
-// fs_state_shift / fs_state_shift_u8: the checks and every pass, the move pass of the frame's type
-template <typename T>
-int motion_state_shift(const T* img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
+template <int V>
+void motion_move(const HwcView& img, const long long* shift, const unsigned char* key, unsigned char* key2, const unsigned int* bits,
+                 unsigned int* bits2, int H, int W, int P, long nk, long nb, dim3 grid, hipStream_t stream) {
+  hipLaunchKernelGGL(motion_move_hwc_kernel<V>, grid, dim3(MOTION_THREADS), 0, stream, img.p, img.sb, img.sy, img.sx, shift, key, key2, bits, bits2,
+                     H, W, P, (unsigned)nk, (unsigned)nb);
+}
+inline bool motion_frame_ok(const float*, int, int, int) { return true; }
+inline bool motion_frame_ok(const unsigned char*, int, int, int) { return true; }
+inline bool motion_frame_ok(const HwcView& v, int B, int H, int W) { return hwc_view_ok(v, B, H, W); }
+
+// fs_state_shift / fs_state_shift_u8 / fs_state_shift_hwc: the checks and every pass, the move pass of the frame's type
+template <typename F>
+int motion_state_shift(F img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
                        long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch, int B,
                        int H, int W, int cap, hipStream_t stream) {
   FS_REQUIRE(img && shift && key && key2 && bits && bits2 && gstate && stats && counts && prof_key && mstate && motion && scratch);
   FS_REQUIRE(motion_sizes_ok(B, H, W) && cap >= 1 && H <= MOTION_MAX_SIDE && W <= MOTION_MAX_SIDE && key != key2 && bits != bits2);
-  FS_REQUIRE(((uintptr_t)scratch & 7) == 0 && fs_mask_rle_scratch_ints(B, H, W) > 0);
+  FS_REQUIRE(((uintptr_t)scratch & 7) == 0 && fs_mask_rle_scratch_ints(B, H, W) > 0 && motion_frame_ok(img, B, H, W));
   const int P = (W + 31) / 32, n = H + W;
   const size_t per = (size_t)3 * H * W;
   const bool vec = W % 4 == 0 && ((uintptr_t)key & 3) == 0 && ((uintptr_t)key2 & 3) == 0;
@@ -512,6 +644,33 @@ int fs_state_shift_u8(const unsigned char* img, const long long* shift, unsigned
                       long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch, int B,
                       int H, int W, int cap, hipStream_t stream) {
   return motion_state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch, B, H, W, cap, stream);
+}
+
+int fs_frame_profiles_hwc(const unsigned char* img, long sb, long sy, int sx, int* prof, int B, int H, int W, hipStream_t stream) {
+  FS_REQUIRE(img && prof && motion_sizes_ok(B, H, W));
+  const HwcView v{img, sb, sy, sx};
+  FS_REQUIRE(hwc_view_ok(v, B, H, W));
+  const int n = H + W;
+  const int bpv = cdiv(n, MOTION_THREADS), nseg = cdiv(W, MOTION_SEG), nband = cdiv(H, MOTION_BAND);
+  FS_REQUIRE((long)B * bpv <= MOTION_WGS_MAX && (long)B * nseg * nband <= MOTION_WGS_MAX);
+  hipLaunchKernelGGL(motion_zero_kernel, dim3((unsigned)(B * bpv)), dim3(MOTION_THREADS), 0, stream, prof, (const long long*)nullptr, n,
+                     (unsigned)bpv);
+  FS_LAUNCH_CHECK();
+  const dim3 grid((unsigned)(B * nseg * nband)), block(MOTION_THREADS);
+  const bool vec = hwc_vec_ok(v, W);
+  if (sx == 3 && vec) hipLaunchKernelGGL((motion_profile_hwc_kernel<3, true>), grid, block, 0, stream, img, sb, sy, prof, H, W, nseg, nband);
+  else if (sx == 3) hipLaunchKernelGGL((motion_profile_hwc_kernel<3, false>), grid, block, 0, stream, img, sb, sy, prof, H, W, nseg, nband);
+  else if (vec) hipLaunchKernelGGL((motion_profile_hwc_kernel<4, true>), grid, block, 0, stream, img, sb, sy, prof, H, W, nseg, nband);
+  else hipLaunchKernelGGL((motion_profile_hwc_kernel<4, false>), grid, block, 0, stream, img, sb, sy, prof, H, W, nseg, nband);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+int fs_state_shift_hwc(const unsigned char* img, long sb, long sy, int sx, const long long* shift, unsigned char* key, unsigned char* key2,
+                       unsigned int* bits, unsigned int* bits2, long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate,
+                       long long* motion, int* scratch, int B, int H, int W, int cap, hipStream_t stream) {
+  return motion_state_shift(HwcView{img, sb, sy, sx}, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch, B, H, W,
+                            cap, stream);
 }
 
 int fs_motion_commit(const int* idx, int n, const int* prof, int* prof_key, long long* mstate, int B, int H, int W, hipStream_t stream) {

@@ -68,6 +68,12 @@ SIGNATURES = {
     "fs_gate_tiles_u8": "ppp" + "iiii",
     "fs_gate_commit_u8": "pp" + "i" + "p" * 13 + "iiii",
     "fs_state_shift_u8": "p" * 13 + "iiii",
+    "fs_gaze_lowres_hwc_fwd": "plli" + "pp" + "iiiii",
+    "fs_grid_sample_hwc_fwd": "plli" + "pp" + "iiiiii",
+    "fs_gate_tiles_hwc": "plli" + "pp" + "iiii",
+    "fs_gate_commit_hwc": "plli" + "p" + "i" + "p" * 13 + "iiii",
+    "fs_frame_profiles_hwc": "plli" + "p" + "iii",
+    "fs_state_shift_hwc": "plli" + "p" * 12 + "iiii",
     "fs_conv2d_fwd": "ppppiiiiiiiiiiiifuplp",
     "fs_conv2d_fwd_residual": "ppppp" + "iiiiiiiiiiii" + "fufu" + "l" + "plp",
     "fs_conv2d_fwd_stats": "pppppiiiiiiiiiiiifuplp",
@@ -180,6 +186,7 @@ HOST_ONLY = {
     "fs_mask_erode_scratch_ints": ("l", "iiii"),
     "fs_mask_pair_scratch_ints": ("l", "iiii"),
     "fs_state_shift_scratch_ints": ("l", "iiii"),
+    "fs_byte_frame_route": ("l", "plli" + "i"),
 }
 
 

@@ -200,7 +200,9 @@ class DeformSegmentationModule(nn.Module):
         """predict's / evaluate's shared front: argument checks, then forward's stages up to the C1 head's two factors.
         Returns (cls (B,K), m (B,h,w), grid (B,h,w,2), seg_size as two ints).  img is fp32, or a planar torch.uint8 frame whose pixel
         value is byte / 255 correctly rounded: the results equal those of the fp32 frame of that quotient bit for bit, and the frame is
-        read as bytes by the two gathers of the front (ops.gaze_lowres, ops.grid_sample_u8)."""
+        read as bytes by the two gathers of the front (ops.gaze_lowres, ops.grid_sample_u8).  A uint8 frame may also be a view of
+        interleaved bytes (hwc.permute(0, 3, 1, 2), rgba.permute(0, 3, 1, 2)[:, :3], padded rows, a crop: ops.byte_frame_layout): the
+        gathers read it where it lies, nothing is copied, and the results equal those of its planar copy bit for bit."""
         if self.training:
             raise RuntimeError(f"{who}() needs eval mode (module.eval()): in train mode the encoder would update its BatchNorm running statistics")
         if img.dim() != 4 or img.shape[1] != 3:
@@ -214,7 +216,9 @@ class DeformSegmentationModule(nn.Module):
             raise ValueError(f"seg_size must be (H, W) with positive sides, got {tuple(seg_size)}")
         self.check_nan()
         ops.reset_step_state()
-        x = img.contiguous()
+        # a uint8 view of interleaved bytes (ops.byte_frame_layout: a permuted HWC / RGBA buffer) is read where it lies
+        hwc = img.dtype == torch.uint8 and not img.is_contiguous() and ops.byte_frame_layout(img) is not None
+        x = img if hwc else img.contiguous()
         xs, _ = self.saliency(x, focus.float().contiguous())
         self._note_nan(xs)
         if self.cfg.MODEL.uniform_sample != "":

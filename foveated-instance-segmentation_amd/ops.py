@@ -1333,10 +1333,95 @@ class SegLoss(Function):
 # ----------------------------------------------------------------------------------------------
 # foveation front-end
 # ----------------------------------------------------------------------------------------------
+def byte_frame_strides(shape, strides):
+    """byte_frame_layout's rule as a pure function of a (B,3,H,W) shape and its element strides (sb, sc, sy, sx); strides of dimensions
+    of size 1 are ignored.  ("planar",) for a contiguous tensor; ("hwc", sb, sy, sx) for interleaved bytes -- sc == 1, sx in {3, 4}, sy
+    >= W * sx, and sb == 0 (every viewer sees the one frame), sb >= H * sy or B == 1; None for anything else.  In the hwc tuple the
+    ignored strides are normalised: sb = 0 for B == 1, sy = W * sx for H == 1, sx = 3 for W == 1."""
+    B, C, H, W = (int(v) for v in shape)
+    sb, sc, sy, sx = (int(v) for v in strides)
+    if C != 3 or min(B, H, W) < 1:
+        return None
+    if (W == 1 or sx == 1) and (H == 1 or sy == W) and (sc == H * W) and (B == 1 or sb == 3 * H * W):
+        return ("planar",)
+    if sc != 1:
+        return None
+    if W == 1:
+        sx = 3
+    if sx not in (3, 4):
+        return None
+    if H == 1:
+        sy = W * sx
+    if sy < W * sx:
+        return None
+    if B == 1:
+        sb = 0
+    if sb != 0 and sb < H * sy:
+        return None
+    return ("hwc", sb, sy, sx)
+
+
+def byte_frame_layout(img):
+    """How a uint8 frame (B,3,H,W) lies in memory, from its strides alone: ("planar",) when it is contiguous (the fs_*_u8 route);
+    ("hwc", sb, sy, sx) when it is a view of interleaved bytes, the byte of channel c at (b, y, x) being byte b * sb + y * sy + x * sx + c
+    from img.data_ptr() (the fs_*_hwc route: nothing is copied); None for anything else.  An hwc view is what a camera's or a decoder's
+    (B,H,W,3) or (B,H,W,4) buffer is after permute(0, 3, 1, 2) (and [:, :3] for RGBA / RGBX, whose fourth byte is never used): tight or
+    with padded rows, a crop of a larger buffer, x.contiguous(memory_format=torch.channels_last), or one frame expanded over the batch
+    (sb == 0).  The channel order is the tensor's own.  The kernels read whole pixels, so the W * sx bytes of the last row must lie inside
+    the tensor's storage (an RGBA view's last alpha byte: true of every view of a real (B,H,W,4) buffer); a view that ends short is None."""
+    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.dtype != torch.uint8 or img.shape[1] != 3 or img.numel() == 0:
+        return None
+    if img.is_contiguous():
+        return ("planar",)
+    layout = byte_frame_strides(img.shape, img.stride())
+    if layout is not None and layout[0] == "hwc":
+        _, sb, sy, sx = layout
+        if img.storage_offset() + (img.shape[0] - 1) * sb + (img.shape[2] - 1) * sy + img.shape[3] * sx > img.untyped_storage().nbytes():
+            return None
+    return layout
+
+
+def _hwc_args(img, layout):
+    """The (pointer, sb, sy, sx) of an hwc view (byte_frame_layout) for the fs_*_hwc entry points."""
+    _, sb, sy, sx = layout
+    if not img.is_cuda:
+        raise hip.HipLibraryError("fovealseg kernels need device tensors (got a CPU tensor); there is no CPU path")
+    return img.data_ptr(), sb, sy, sx
+
+
+def _byte_frame(img, what="img"):
+    """("planar",) or ("hwc", ...) of a uint8 frame the *_u8 functions take; ValueError for any other layout, before any launch."""
+    layout = byte_frame_layout(img)
+    if layout is None:
+        raise ValueError(f"{what} must be a contiguous uint8 (B,3,H,W) or a view of interleaved (B,H,W,3) / (B,H,W,4) bytes "
+                         f"(ops.byte_frame_layout), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))} with strides "
+                         f"{tuple(img.stride()) if isinstance(img, torch.Tensor) else None}; call .contiguous() on it")
+    return layout
+
+
+def byte_frame_select(img, sel):
+    """img.index_select(0, sel) for an hwc view that stays one: the rows of the chosen frames are gathered from the underlying bytes (3 * H *
+    W or 4 * H * W bytes a frame, never a planar copy) and viewed as (n,3,H,W) again.  With sb == 0 the n frames are the one frame."""
+    layout = byte_frame_layout(img)
+    if layout is None or layout[0] != "hwc":
+        return img.index_select(0, sel)
+    _, sb, sy, sx = layout
+    B, _, H, W = (int(v) for v in img.shape)
+    n = int(sel.shape[0])
+    if sb == 0:
+        return img[:1].expand(n, 3, H, W)
+    rows = img.as_strided((B, H, W * sx), (sb, sy, 1)).index_select(0, sel)
+    return rows.view(n, H, W, sx).permute(0, 3, 1, 2)[:, :3]
+
+
 def gaze_lowres(x, focus, hs, ws):
     B, C, H, W = x.shape
     assert C == 3
     out = torch.empty(B, hs, ws, 5, device=x.device, dtype=torch.float32)
+    if x.dtype == torch.uint8 and not x.is_contiguous():    # an interleaved frame of bytes, read where it lies
+        _launch("fe_gaze_lowres_hwc", 1.0 * B * hs * ws * (12 + 20), "fs_gaze_lowres_hwc_fwd", *_hwc_args(x, _byte_frame(x, "x")),
+                hip.ptr(focus), hip.ptr(out), B, H, W, hs, ws)
+        return out
     if x.dtype == torch.uint8:                          # a frame of bytes: four one-byte taps a channel, 12 bytes read and 20 written a point
         _launch("fe_gaze_lowres_u8", 1.0 * B * hs * ws * (12 + 20), "fs_gaze_lowres_u8_fwd", hip.ptr(x), hip.ptr(focus), hip.ptr(out), B, H, W, hs, ws)
         return out
@@ -1512,6 +1597,12 @@ def grid_sample_u8(x, grid):
     if grid.dim() != 4 or grid.shape[0] != B or grid.shape[3] != 2 or grid.numel() == 0 or grid.dtype != torch.float32:
         raise ValueError(f"grid must be a non-empty fp32 ({B},h,w,2), got {grid.dtype} {tuple(grid.shape)}")
     h, w = int(grid.shape[1]), int(grid.shape[2])
+    if not x.is_contiguous():                           # an interleaved frame (three channels), read where it lies: one address a tap
+        layout = _byte_frame(x, "x")
+        out = torch.empty(B, h, w, C, device=x.device, dtype=torch.float32)
+        _launch("fe_grid_sample_hwc_fwd", 1.0 * B * h * w * (4 * C + 8 + 4 * C), "fs_grid_sample_hwc_fwd", *_hwc_args(x, layout), hip.ptr(grid),
+                hip.ptr(out), B, H, W, h, w, 1)
+        return out
     out = torch.empty(B, h, w, C, device=x.device, dtype=torch.float32)
     _launch("fe_grid_sample_u8_fwd", 1.0 * B * h * w * (4 * C + 8 + 4 * C), "fs_grid_sample_u8_fwd", hip.ptr(x), hip.ptr(grid), hip.ptr(out), B, C, H, W, h, w, 1)
     return out
@@ -1887,12 +1978,17 @@ def _gate_tiles(name, dtype, img, key, tile, out):
     if key.dtype != torch.uint8 or key.shape != img.shape:
         raise ValueError(f"key must be uint8 {tuple(img.shape)}, got {key.dtype} {tuple(key.shape)}")
     B, _, H, W = (int(v) for v in img.shape)
+    if dtype == torch.uint8 and not img.is_contiguous():
+        hwc = _hwc_args(img, _byte_frame(img))
     shape = (B, (H + T - 1) // T, (W + T - 1) // T)
     if out is None:
         out = torch.empty(shape, device=img.device, dtype=torch.int32)
     elif out.dtype != torch.int32 or tuple(out.shape) != shape:
         raise ValueError(f"out must be int32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    hip.call(name, hip.ptr(img), hip.ptr(key), hip.ptr(out), B, H, W, T)
+    if dtype == torch.uint8 and not img.is_contiguous():
+        hip.call("fs_gate_tiles_hwc", *hwc, hip.ptr(key), hip.ptr(out), B, H, W, T)
+    else:
+        hip.call(name, hip.ptr(img), hip.ptr(key), hip.ptr(out), B, H, W, T)
     return out
 
 
@@ -1906,7 +2002,8 @@ def gate_tiles(img, key, tile=32, out=None):
 
 def gate_tiles_u8(img, key, tile=32, out=None):
     """gate_tiles for frames of bytes (fs_gate_tiles_u8): img (B,3,H,W) uint8, the pixel value byte / 255, whose code q is the byte.  sad
-    is the sum of |img - key|, equal to gate_tiles(img.float() / 255, key, tile); 6 bytes read a pixel instead of 15."""
+    is the sum of |img - key|, equal to gate_tiles(img.float() / 255, key, tile); 6 bytes read a pixel instead of 15.  img is contiguous,
+    or an hwc view of interleaved bytes (byte_frame_layout; fs_gate_tiles_hwc), read where it lies; ValueError for any other layout."""
     return _gate_tiles("fs_gate_tiles_u8", torch.uint8, img, key, tile, out)
 
 
@@ -1952,6 +2049,7 @@ def _gate_commit(name, dtype, img, idx, key, gstate, focus, src, dst):
         raise ValueError(f"img must be a non-empty {what} (B,3,H,W) and key uint8 of its shape, got {getattr(img, 'dtype', None)} "
                          f"{tuple(getattr(img, 'shape', ()))} and {tuple(key.shape)}")
     B, _, H, W = (int(v) for v in img.shape)
+    hwc = _hwc_args(img, _byte_frame(img)) if dtype == torch.uint8 and not img.is_contiguous() else None
     n = 0 if idx is None else int(idx.shape[0])
     if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 1 or n > B):
         raise ValueError(f"idx must be int32 (n,) with n <= {B}, got {idx.dtype} {tuple(idx.shape)}")
@@ -1969,6 +2067,9 @@ def _gate_commit(name, dtype, img, idx, key, gstate, focus, src, dst):
             raise ValueError(f"a src record tensor must be {dt} {(n,) + tail}, got {s.dtype} {tuple(s.shape)}")
     sp = [hip.ptr(s) for s in src] + [None] * (5 - len(src))
     dp = [hip.ptr(d) for d in dst] + [None] * (5 - len(dst))
+    if hwc is not None:
+        hip.call("fs_gate_commit_hwc", *hwc, hip.ptr(idx), n, hip.ptr(key), hip.ptr(gstate), hip.ptr(focus), *sp, *dp, B, H, W, cap)
+        return
     hip.call(name, hip.ptr(img), hip.ptr(idx), n, hip.ptr(key), hip.ptr(gstate), hip.ptr(focus), *sp, *dp, B, H, W, cap)
 
 
@@ -1983,7 +2084,8 @@ def gate_commit(img, idx, key, gstate, focus, src, dst):
 
 def gate_commit_u8(img, idx, key, gstate, focus, src, dst):
     """gate_commit for frames of bytes (fs_gate_commit_u8): img (B,3,H,W) uint8; for the viewers of idx key <- img, a copy.  Everything
-    else as gate_commit, and equal to it on img.float() / 255."""
+    else as gate_commit, and equal to it on img.float() / 255.  img is contiguous, or an hwc view of interleaved bytes (byte_frame_layout;
+    fs_gate_commit_hwc: the key takes the de-interleaved frame and stays planar); ValueError for any other layout."""
     _gate_commit("fs_gate_commit_u8", torch.uint8, img, idx, key, gstate, focus, src, dst)
 
 
@@ -2027,12 +2129,16 @@ def _profiles(name, src, dtype, out):
     if not isinstance(src, torch.Tensor) or src.dim() != 4 or src.shape[1] != 3 or src.numel() == 0 or src.dtype != dtype:
         raise ValueError(f"the frames must be a non-empty {dtype} (B,3,H,W), got {getattr(src, 'dtype', None)} {tuple(getattr(src, 'shape', ()))}")
     B, _, H, W = (int(v) for v in src.shape)
+    hwc = _hwc_args(src, _byte_frame(src, "the frames")) if dtype == torch.uint8 and not src.is_contiguous() else None
     shape = _profile_sizes(B, H, W)
     if out is None:
         out = torch.empty(shape, device=src.device, dtype=torch.int32)
     elif out.dtype != torch.int32 or tuple(out.shape) != shape:
         raise ValueError(f"out must be int32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    hip.call(name, hip.ptr(src), hip.ptr(out), B, H, W)
+    if hwc is not None:
+        hip.call("fs_frame_profiles_hwc", *hwc, hip.ptr(out), B, H, W)
+    else:
+        hip.call(name, hip.ptr(src), hip.ptr(out), B, H, W)
     return out
 
 
@@ -2045,7 +2151,8 @@ def frame_profiles(img, out=None):
 
 def key_profiles(key, out=None):
     """frame_profiles of 8-bit key frames (fs_key_profiles): key (B,3,H,W) uint8.  The profiles of a frame and of the key gate_commit
-    made from it are equal."""
+    made from it are equal.  A frame of bytes may also be an hwc view of interleaved bytes (byte_frame_layout; fs_frame_profiles_hwc), read
+    where it lies; ValueError for any other non-contiguous layout."""
     return _profiles("fs_key_profiles", key, torch.uint8, out)
 
 
@@ -2082,6 +2189,7 @@ def _state_shift(entry, dtype, img, shift, key, key2, bits, bits2, gstate, stats
     if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
         raise ValueError(f"img must be a non-empty {'fp32' if dtype == torch.float32 else 'uint8'} (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
     B, _, H, W = (int(v) for v in img.shape)
+    hwc = _hwc_args(img, _byte_frame(img)) if dtype == torch.uint8 and not img.is_contiguous() else None
     _profile_sizes(B, H, W)
     P = (W + 31) // 32
     for name, k in (("key", key), ("key2", key2)):
@@ -2109,7 +2217,11 @@ def _state_shift(entry, dtype, img, shift, key, key2, bits, bits2, gstate, stats
         scratch = torch.empty(need, device=img.device, dtype=torch.int32)
     elif scratch.dtype != torch.int32 or scratch.dim() != 1 or scratch.numel() < need:
         raise ValueError(f"scratch must be int32 with at least {need} entries, got {scratch.dtype} {tuple(scratch.shape)}")
-    hip.call(entry, hip.ptr(img), hip.ptr(shift), hip.ptr(key), hip.ptr(key2), hip.ptr(bits), hip.ptr(bits2), hip.ptr(gstate),
+    if hwc is not None:
+        entry, frame = "fs_state_shift_hwc", hwc
+    else:
+        frame = (hip.ptr(img),)
+    hip.call(entry, *frame, hip.ptr(shift), hip.ptr(key), hip.ptr(key2), hip.ptr(bits), hip.ptr(bits2), hip.ptr(gstate),
              hip.ptr(stats), hip.ptr(counts), hip.ptr(prof_key), hip.ptr(mstate), hip.ptr(motion), hip.ptr(scratch), B, H, W, cap)
     return motion
 
@@ -2127,7 +2239,8 @@ def state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_
 
 def state_shift_u8(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion=None, scratch=None):
     """state_shift for frames of bytes (fs_state_shift_u8): img (B,3,H,W) uint8; the key's uncovered border is filled with the frame's
-    byte.  Everything else as state_shift, and equal to it on img.float() / 255; the scratch is the same."""
+    byte.  Everything else as state_shift, and equal to it on img.float() / 255; the scratch is the same.  img is contiguous, or an hwc
+    view of interleaved bytes (byte_frame_layout; fs_state_shift_hwc); ValueError for any other layout."""
     return _state_shift("fs_state_shift_u8", torch.uint8, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch)
 
 

@@ -159,6 +159,10 @@ class GazeSession:
         them, on the device; force: None, or B flags (any sequence or tensor), non-zero = re-make this viewer's record now.  A uint8 frame
         gives what img.float() / 255 gives bit for bit and is never converted: gate, commit, motion, the selection of the viewers that run
         and the network's front all read the bytes.  The state is the same tensors either way, so the dtype may change from step to step.
+        A uint8 frame may also be a view of interleaved bytes, as a camera or a decoder makes them -- hwc.permute(0, 3, 1, 2) of a (B,H,W,3)
+        buffer, rgba.permute(0, 3, 1, 2)[:, :3] of a (B,H,W,4) one, with padded rows, as a crop, or one frame expanded over the viewers
+        (ops.byte_frame_layout) --: it is read where it lies, gives what its planar copy gives bit for bit, and a step in which nobody
+        runs allocates nothing.  Any other non-contiguous frame is copied, as before.
 
         Returns (cat, stats, counts, bits[, conf], gate[, motion]): the record of every viewer as predict_instances(img, focus, return_bits=True)
         makes it -- made now for the viewers that ran, the held one for the others -- and gate (B,8) int64 on the host = (code,
@@ -183,7 +187,9 @@ class GazeSession:
         elif img.device != self._dev:
             raise ValueError(f"the session lives on {self._dev}, img is on {img.device}")
         fdev = self._force(force, img.device)
-        x = img.contiguous()
+        # a view of interleaved bytes (ops.byte_frame_layout: a camera's HWC / RGBA buffer, permuted) is read where it lies
+        hwc = img.dtype == torch.uint8 and not img.is_contiguous() and ops.byte_frame_layout(img) is not None
+        x = img if hwc else img.contiguous()
         f = focus.float().contiguous()
         moving = self.motion_px is not None
         # a frame of bytes stays bytes: its pixel code is the byte, so its profiles are key_profiles of it and the gate compares bytes
@@ -217,7 +223,8 @@ class GazeSession:
                 xi, fi = x, focus
             else:
                 sel = idx.long()
-                xi, fi = x.index_select(0, sel), focus.index_select(0, sel)
+                # the running viewers of an interleaved frame stay interleaved: their bytes are gathered as they lie, no planar copy
+                xi, fi = (ops.byte_frame_select(x, sel) if hwc else x.index_select(0, sel)), focus.index_select(0, sel)
             if self.component is None:
                 new = list(self.module.predict_instances(xi, fi, max_runs=self.max_runs, return_bits=True, return_score=self.score))
             else:                                                          # comp, the last element, is not part of the record

@@ -401,6 +401,44 @@ int fs_gate_commit_u8(const unsigned char* img, const int* idx, int n, unsigned 
 int fs_state_shift_u8(const unsigned char* img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits,
                       unsigned int* bits2, long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate,
                       long long* motion, int* scratch, int B, int H, int W, int cap, fs_stream_t stream);
+/* Frames as interleaved bytes, read where they lie (UNPINNED): what cameras, decoders, OpenCV, PIL and numpy make.  The
+ * frame is described by (img, sb, sy, sx): the byte of channel c at (b, y, x) is img[b * sb + y * sy + x * sx + c], c = 0 .. 2; sx = 3
+ * (RGB) or 4 (RGBA / RGBX: the fourth byte reaches no result); a row spans W * sx bytes of a pitch sy >= W * sx; images lie sb >= H * sy
+ * apart, or sb = 0: every viewer sees the one image.  Each entry point below equals its planar twin fed the de-interleaved frame bit for
+ * bit, never writes the frame, and returns FS_ERR_ARG, with nothing launched, under the twin's conditions and for sx outside {3, 4}, sy <
+ * W * sx, sb < 0, or 0 < sb < H * sy with B > 1.  The session's state stays planar.
+ * fs_byte_frame_route (host only): which forms the passes take for such a frame of width W: 1 the vector forms (W % 16 == 0 and img, sy, sb
+ * multiples of 16, so that every sixteen pixels of every row start at a 16-byte boundary), 0 the one-pixel forms (any width, pitch and
+ * alignment), -1 a description that is refused (null img, sx, sy < W * sx, sb < 0, W < 1). */
+long fs_byte_frame_route(const unsigned char* img, long sb, long sy, int sx, int W);
+/* fs_gaze_lowres_u8_fwd on an interleaved frame: the same four taps and the same operations, a tap's three bytes from one address. */
+int fs_gaze_lowres_hwc_fwd(const unsigned char* img, long sb, long sy, int sx, const float* focus, float* out, int B, int H, int W, int hs,
+                           int ws, fs_stream_t stream);
+/* fs_grid_sample_u8_fwd with C = 3 on an interleaved frame: out fp32 (B,h,w,3) [nhwc_out=1] or (B,3,h,w) [nhwc_out=0]; one address a tap
+ * instead of three planes. */
+int fs_grid_sample_hwc_fwd(const unsigned char* img, long sb, long sy, int sx, const float* grid, float* out, int B, int H, int W, int h, int w,
+                           int nhwc_out, fs_stream_t stream);
+/* fs_gate_tiles_u8 on an interleaved frame, the hot pass: 6 (sx = 3) or 7 (sx = 4) bytes read per pixel, plain stores, no atomics.  Vector
+ * form (route 1 and key 16-byte aligned): fs_gate_tiles_u8's cut; a lane owns the 48 or 64 frame bytes of its sixteen pixels (three or
+ * four 16-byte loads), splits them into a register quad a channel with v_perm_b32 (6 perms four RGB pixels, 7 four RGBA pixels) and meets
+ * the key's 16-byte load per channel with v_sad_u8.  One pixel a lane otherwise. */
+int fs_gate_tiles_hwc(const unsigned char* img, long sb, long sy, int sx, const unsigned char* key, int* sad, int B, int H, int W, int T,
+                      fs_stream_t stream);
+/* fs_gate_commit_u8 on an interleaved frame: key[idx[j]] <- the de-interleaved frame of viewer idx[j]; the key stays planar.  Sixteen
+ * pixels a lane (split as in the tile pass, three 16-byte stores) under the tile pass's conditions, one byte a lane otherwise.  The state
+ * and row passes are fs_gate_commit's. */
+int fs_gate_commit_hwc(const unsigned char* img, long sb, long sy, int sx, const int* idx, int n, unsigned char* key, long long* gstate,
+                       const float* focus, const long long* src_cat, const long long* src_stats, const int* src_counts,
+                       const unsigned int* src_bits, const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts,
+                       unsigned int* dst_bits, float* dst_conf, int B, int H, int W, int cap, fs_stream_t stream);
+/* fs_key_profiles of an interleaved frame: prof (B, H + W) int32, the row and column sums of r + g + b per pixel.  Four pixels a lane (12
+ * bytes in three 4-byte loads, or one 16-byte load) on route 1, one pixel a lane otherwise; the same zeroing and integer atomics. */
+int fs_frame_profiles_hwc(const unsigned char* img, long sb, long sy, int sx, int* prof, int B, int H, int W, fs_stream_t stream);
+/* fs_state_shift_u8 on an interleaved frame: only the move pass reads the frame (the key's uncovered border takes the frame's byte of
+ * that channel); every other pass and the scratch are fs_state_shift's. */
+int fs_state_shift_hwc(const unsigned char* img, long sb, long sy, int sx, const long long* shift, unsigned char* key, unsigned char* key2,
+                       unsigned int* bits, unsigned int* bits2, long long* gstate, long long* stats, int* counts, int* prof_key,
+                       long long* mstate, long long* motion, int* scratch, int B, int H, int W, int cap, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
