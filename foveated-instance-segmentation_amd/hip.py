@@ -48,6 +48,7 @@ SIGNATURES = {
     "fs_surface_hd": "ppp" + "iiii",
     "fs_mask_bits": "pp" + "iii",
     "fs_mask_rle": "pppp" + "iiii",
+    "fs_rle_bits": "pp" + "i" + "ppp" + "iiii",
     "fs_unwarp_instances": "pppppppp" + "iiiiiii",
     "fs_head_fg_q": "ppp" + "iiii",
     "fs_unwarp_instances_scored": "pppppppppp" + "iiiiiii",
@@ -178,6 +179,7 @@ HOST_ONLY = {
     "fs_unwarp_hd_scratch_ints": ("l", "iiiiii"),
     "fs_surface_hd_scratch_ints": ("l", "iii"),
     "fs_mask_rle_scratch_ints": ("l", "iii"),
+    "fs_rle_bits_scratch_ints": ("l", "ii"),
     "fs_unwarp_instances_scratch_ints": ("l", "iiiii"),
     "fs_unwarp_instances_scored_scratch_ints": ("l", "iiiii"),
     "fs_mask_component_scratch_ints": ("l", "iii"),

@@ -306,7 +306,13 @@ class DeformSegmentationModule(nn.Module):
         pair (B,6) int64 = (|p & g|, |p|, |g|, |band(p) & band(g)|, |band(p)|, |band(g)|) of the record's mask p -- the component,
         with component -- and the label g.  ops.pair_scores makes IoU and Boundary IoU, train.InstanceAPMeter AP and Boundary AP over
         a dataset (cls_label is that meter's; here only its batch size is checked).  Nothing of (B,H,W) wider than a bit a pixel is
-        allocated beyond the label's bool mask.  Eval mode only, no host read, no argument written to, nothing in the module changes."""
+        allocated beyond the label's bool mask.  Eval mode only, no host read, no argument written to, nothing in the module changes.
+
+        seg_label may also be a tuple (counts, n_runs): the label's uncompressed run-length code as ops.rle_bits takes it -- counts
+        (B,cap) int32, n_runs int64 (B,) or a stats (B,6) tensor --, at seg_size, which is then required (ops.coco_to_instances makes
+        both from COCO / LVIS annotations).  The label's bit words then come from ops.rle_bits instead of ops.mask_bits and no dense
+        label exists at all.  An image whose code is not valid (cut, a negative count, a wrong sum) scores as an empty label, |g| = 0:
+        the call still reads nothing on the host; ops.rle_bits(counts, n_runs, seg_size, check=True) tells such a code beforehand."""
         if isinstance(boundary, bool) or not isinstance(boundary, float) or not (boundary > 0.0) or math.isinf(boundary):
             raise ValueError(f"boundary must be a finite float > 0, got {boundary!r}")
         if component is None:
@@ -314,6 +320,25 @@ class DeformSegmentationModule(nn.Module):
                 raise ValueError("snap_px goes with component = 4 or 8")
         else:
             ops._component_args(component, snap_px)
+        if isinstance(seg_label, (tuple, list)):
+            if len(seg_label) != 2:
+                raise ValueError(f"a run-length label is a tuple (counts, n_runs), got {len(seg_label)} elements")
+            if seg_size is None or len(seg_size) != 2:
+                raise ValueError("a run-length label needs seg_size = (H, W): the code does not carry its size")
+            counts, n_runs = seg_label
+            label_size = (int(seg_size[0]), int(seg_size[1]))
+            if not isinstance(counts, torch.Tensor) or counts.dim() != 2 or counts.shape[0] != img.shape[0] or cls_label.shape[0] != img.shape[0]:
+                raise ValueError(f"counts {tuple(getattr(counts, 'shape', ()))} and cls_label {tuple(cls_label.shape)} must have img's batch size "
+                                 f"{img.shape[0]}")
+            d = ops.boundary_dilation(*label_size, boundary)
+            if d > ops.MORPH_MAX_D:
+                raise ValueError(f"boundary {boundary!r} gives a dilation of {d} pixels at {label_size}, above ops.MORPH_MAX_D = {ops.MORPH_MAX_D}")
+            ops._rle_args(counts, n_runs, label_size)                               # other dtypes and shapes raise before the network runs
+            out = self.predict_instances(img, focus, label_size, max_runs=max_runs, return_bits=True, return_score=True, component=component,
+                                         snap_px=snap_px)
+            label, _info = ops.rle_bits(counts, n_runs, label_size)                 # behind the network's peak, where mask_bits stands
+            pair = ops.mask_pair_counts(out[3], label, d, Ws=label_size[1])
+            return out[:3] + out[4:] + (pair,)
         if seg_label.dim() not in (3, 4) or (seg_label.dim() == 4 and seg_label.shape[1] != 1):
             raise ValueError(f"seg_label must be (B,H,W) or (B,1,H,W), got {tuple(seg_label.shape)}")
         label_size = (int(seg_label.shape[-2]), int(seg_label.shape[-1]))

@@ -1919,14 +1919,117 @@ def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False, sco
     return (cat, stats, counts) + ((bits,) if return_bits else ()) + ((conf, qsum) if score else ()) + ((cout,) if comp else ())
 
 
-def instances_to_coco(cat, stats, counts, seg_size, image_ids=None, conf=None):
+RLE_STATUS = {0: "valid", 1: "the code was cut: n_runs exceeds the capacity of counts", 2: "n_runs is below 1 or a count is negative",
+              3: "the counts do not sum to Hs * Ws"}
+
+
+def rle_bits(counts, n_runs, size, check=False):
+    """mask_rle's inverse: the uncompressed run-length code back into bit words, on the device (fs_rle_bits; no autograd; unpinned, as
+    the code itself).  counts (B,cap) int32 on the device, as mask_rle / unwarp_instances / coco_to_instances make them; n_runs the
+    codes' lengths, int64 (B,) -- or a stats (B,6) int64 tensor, whose column 5 is read where it lies, without a copy; size = (Hs, Ws).
+    Entries of counts at or past n_runs are never read.  Every well-formed code decodes, canonical or not (zero-length runs anywhere).
+    Returns (bits (B,Hs,ceil(Ws/32)) int32 in mask_bits' layout, the bits at x >= Ws 0; info (B,4) int64 = (status, area, n_read,
+    total)): status 0 valid, 1 cut (n_runs > cap), 2 bad (n_runs < 1 or a negative count), 3 the counts do not sum to Hs * Ws (the
+    first that applies); area the set pixels of a valid code, else 0; an image whose status is not 0 gets all-zero words.  No host
+    read -- unless check=True, which reads info once and raises ValueError naming the first such image and its status in words."""
+    B, cap, Hs, Ws = _rle_args(counts, n_runs, size)
+    n_runs = n_runs.contiguous()
+    n_ptr, n_stride = (hip.ptr(n_runs) + 5 * 8, 6) if n_runs.dim() == 2 else (hip.ptr(n_runs), 1)
+    dev = counts.device
+    bits = torch.empty(B, Hs, (Ws + 31) // 32, device=dev, dtype=torch.int32)
+    info = torch.empty(B, 4, device=dev, dtype=torch.int64)
+    scratch = torch.empty(hip.query("fs_rle_bits_scratch_ints", B, cap), device=dev, dtype=torch.int32)
+    hip.call("fs_rle_bits", hip.ptr(counts.contiguous()), n_ptr, n_stride, hip.ptr(bits), hip.ptr(info), hip.ptr(scratch), B, Hs, Ws, cap)
+    if check:
+        for b, st in enumerate(info[:, 0].cpu().tolist()):
+            if st != 0:
+                raise ValueError(f"image {b}: {RLE_STATUS[st]} (status {st}; size {(Hs, Ws)}, capacity {cap})")
+    return bits, info
+
+
+def _rle_args(counts, n_runs, size):
+    """(B, cap, Hs, Ws) of rle_bits' arguments, or ValueError: the checks of the host, nothing launched."""
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.dim() != 2 or counts.numel() == 0:
+        raise ValueError(f"counts must be a non-empty int32 (B, cap) tensor, got {getattr(counts, 'dtype', None)} {tuple(getattr(counts, 'shape', ()))}")
+    B, cap = int(counts.shape[0]), int(counts.shape[1])
+    if not isinstance(n_runs, torch.Tensor) or n_runs.dtype != torch.int64 or tuple(n_runs.shape) not in ((B,), (B, 6)) \
+            or n_runs.device != counts.device:
+        raise ValueError(f"n_runs must be an int64 (B,) = ({B},) tensor or a stats ({B}, 6) tensor on counts' device, got "
+                         f"{getattr(n_runs, 'dtype', None)} {tuple(getattr(n_runs, 'shape', ()))}")
+    if len(size) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 1 for v in size):
+        raise ValueError(f"size must be two integers >= 1 (Hs, Ws), got {size!r}")
+    return B, cap, int(size[0]), int(size[1])
+
+
+def rle_to_string(counts):
+    """The compressed string form of a run-length code, the one COCO / LVIS files carry (host; unpinned: restated from the published
+    definition, pycocotools' rleToString).  counts: a list of Python ints.  Count i is written as x = counts[i], less counts[i - 2]
+    for i > 2, in 5-bit groups, low group first: c = x & 31, x >>= 5 (arithmetic); another group follows iff x != -1 where c & 16 is
+    set, iff x != 0 otherwise; a group that is followed has bit 32 set; the character is chr(c + 48).  [0, 5] -> "05",
+    [10, 20, 30, 5] -> ":d0n0A"."""
+    out = []
+    counts = list(counts)
+    for i, v in enumerate(counts):
+        if isinstance(v, bool) or not isinstance(v, int):
+            raise ValueError(f"count {i} must be a Python int, got {v!r}")
+        x = v - counts[i - 2] if i > 2 else v
+        while True:
+            c = x & 31
+            x >>= 5
+            more = x != -1 if c & 16 else x != 0
+            out.append(chr((c | 32 if more else c) + 48))
+            if not more:
+                break
+    return "".join(out)
+
+
+RLE_STRING_GROUPS = 13                              # 65 bits: more than any int64 count or difference needs
+
+
+def rle_from_string(s):
+    """rle_to_string's inverse (host; unpinned: pycocotools' rleFrString restated): s a str or ASCII bytes -> the list of counts.  Per
+    count, (c & 31) << 5 k is accumulated over the groups k = 0, 1, ... while bit 32 of c = ord(ch) - 48 is set, the value is
+    sign-extended from bit 16 of the last group, and counts[i - 2] is added for i > 2.  ValueError, naming the position, for a character
+    outside chr(48) .. chr(111), a string that ends inside a count, or a count of more than 13 groups; an empty string is []."""
+    if isinstance(s, (bytes, bytearray)):
+        try:
+            s = bytes(s).decode("ascii")
+        except UnicodeDecodeError:
+            raise ValueError("the compressed code holds a byte outside ASCII") from None
+    if not isinstance(s, str):
+        raise ValueError(f"the compressed code must be a str or bytes, got {type(s).__name__}")
+    counts, p, n = [], 0, len(s)
+    while p < n:
+        x, k = 0, 0
+        while True:
+            if p >= n:
+                raise ValueError(f"the compressed code ends inside count {len(counts)} (position {p})")
+            c = ord(s[p]) - 48
+            if c < 0 or c > 63:
+                raise ValueError(f"character {s[p]!r} at position {p} is outside chr(48) .. chr(111)")
+            if k >= RLE_STRING_GROUPS:
+                raise ValueError(f"count {len(counts)} has more than {RLE_STRING_GROUPS} groups (position {p})")
+            x |= (c & 31) << (5 * k)
+            p, k = p + 1, k + 1
+            if not c & 32:
+                if c & 16:
+                    x -= 1 << (5 * k)
+                break
+        if len(counts) > 2:
+            x += counts[-2]
+        counts.append(x)
+    return counts
+
+
+def instances_to_coco(cat, stats, counts, seg_size, image_ids=None, conf=None, compressed=False):
     """unwarp_instances' / predict_instances' tensors (on any device) as a list of COCO / LVIS result records, one per image:
     {"image_id", "category_id", "bbox": [x, y, w, h], "area", "segmentation": {"size": [H, W], "counts": [...]}} with the uncompressed
-    run-length code pycocotools.mask.frPyObjects takes.  One device-to-host copy.  category_id is the class index cat[b]; image_id is
+    run-length code pycocotools.mask.frPyObjects takes -- or, with compressed=True, "counts" as the compressed string result files carry
+    (rle_to_string; about a fifth of the list's size in JSON).  One device-to-host copy.  category_id is the class index cat[b]; image_id is
     image_ids[b], or b.  With conf (B,3) -- unwarp_instances(score=True)'s / predict_instances(return_score=True)'s -- every record
     also has "score": conf[b, 0] as a Python float, the key COCOeval and the LVIS evaluator rank by; without it no score is made up.
     OverflowError, naming the image and the max_runs it needs, where a code was cut (n_runs > counts.shape[1]); ValueError, naming the
-    image, where a score is NaN."""
+    image, where a score is NaN.  coco_to_instances is the inverse."""
     B, cap = int(counts.shape[0]), int(counts.shape[1])
     if tuple(cat.shape) != (B,) or tuple(stats.shape) != (B, 6) or counts.dim() != 2:
         raise ValueError(f"cat {tuple(cat.shape)}, stats {tuple(stats.shape)}, counts {tuple(counts.shape)} must be (B,), (B, 6), (B, max_runs)")
@@ -1949,14 +2052,79 @@ def instances_to_coco(cat, stats, counts, seg_size, image_ids=None, conf=None):
         c, area, x0, y0, bw, bh, n = head[b]
         if n > cap:
             raise OverflowError(f"image {ids[b]}: the run-length code has {n} counts and was cut at max_runs = {cap}; it needs max_runs >= {n}")
+        runs = code[b, :n].tolist()
         rec = {"image_id": ids[b], "category_id": c, "bbox": [x0, y0, bw, bh], "area": area,
-               "segmentation": {"size": [H, W], "counts": code[b, :n].tolist()}}
+               "segmentation": {"size": [H, W], "counts": rle_to_string(runs) if compressed else runs}}
         if scores is not None:
             if scores[b] != scores[b]:
                 raise ValueError(f"image {ids[b]}: the score is NaN (a NaN among the head's class logits)")
             rec["score"] = scores[b]
         out.append(rec)
     return out
+
+
+INT32_MAX = 2 ** 31 - 1
+
+
+def coco_to_instances(records, device, max_runs=None):
+    """instances_to_coco's inverse: a list of COCO / LVIS result records, or of annotation records, as the tensors the library's own
+    operations take.  Every record has "image_id", "category_id" and "segmentation" = {"size": [H, W], "counts": ...}, counts a list of
+    ints (the uncompressed code) or the compressed string (rle_from_string); "score" in every record or in none.  Returns (image_ids, a
+    list; cat (n,) int64; n_runs (n,) int64; counts (n,cap) int32, zero behind each code; sizes (n,2) int64 = (H, W); scores (n,)
+    fp32, or None where no record has one), the tensors on `device`, made by ONE host-to-device copy.  cap defaults to the longest code;
+    with max_runs (an int >= 1) a longer code is stored cut while n_runs stays its true length, which rle_bits reports as status 1.
+    rle_bits(counts[sel], n_runs[sel], (H, W)) decodes the records of one size.  ValueError, naming the record, for a polygon
+    segmentation (rasterising polygons is not built), a missing key, a count outside int32, a malformed string, or scores in only some."""
+    records = list(records)
+    if not records:
+        raise ValueError("no records")
+    rows, ids, longest = [], [], 1
+    with_score = [isinstance(r, dict) and "score" in r for r in records]
+    if any(with_score) and not all(with_score):
+        raise ValueError(f"record {with_score.index(False)} has no score while others have: scores go with every record or with none")
+    for i, r in enumerate(records):
+        if not isinstance(r, dict):
+            raise ValueError(f"record {i} is no dict")
+        for key in ("image_id", "category_id", "segmentation"):
+            if key not in r:
+                raise ValueError(f"record {i}: the key {key!r} is missing")
+        seg = r["segmentation"]
+        if not isinstance(seg, dict):
+            raise ValueError(f"record {i} (image {r['image_id']!r}): the segmentation is a polygon list, not an RLE dict; polygons are not rasterised here")
+        for key in ("size", "counts"):
+            if key not in seg:
+                raise ValueError(f"record {i} (image {r['image_id']!r}): the segmentation's key {key!r} is missing")
+        size, code = seg["size"], seg["counts"]
+        if len(size) != 2 or any(isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > INT32_MAX for v in size):
+            raise ValueError(f"record {i} (image {r['image_id']!r}): the size must be two integers >= 1, got {size!r}")
+        if isinstance(code, (str, bytes, bytearray)):
+            try:
+                code = rle_from_string(code)
+            except ValueError as e:
+                raise ValueError(f"record {i} (image {r['image_id']!r}): {e}") from None
+        code = list(code)
+        for j, v in enumerate(code):
+            if isinstance(v, bool) or not isinstance(v, int) or v < -INT32_MAX - 1 or v > INT32_MAX:
+                raise ValueError(f"record {i} (image {r['image_id']!r}): count {j} = {v!r} is no integer within int32")
+        c = r["category_id"]
+        if isinstance(c, bool) or not isinstance(c, int):
+            raise ValueError(f"record {i} (image {r['image_id']!r}): category_id must be an integer, got {c!r}")
+        ids.append(r["image_id"])
+        rows.append((c, len(code), int(size[0]), int(size[1]), code))
+        longest = max(longest, len(code))
+    cap = longest if max_runs is None else _max_runs(max_runs, 1)
+    n = len(rows)
+    head = torch.tensor([row[:4] for row in rows], dtype=torch.int64).reshape(n, 4)
+    score = torch.tensor([float(r["score"]) for r in records] if all(with_score) else [0.0] * n, dtype=torch.float32).reshape(n, 1)
+    code = torch.zeros(n, cap, dtype=torch.int32)
+    for i, row in enumerate(rows):
+        m = min(row[1], cap)
+        if m:
+            code[i, :m] = torch.tensor(row[4][:m], dtype=torch.int32)
+    dev = torch.cat([head.view(torch.int32), score.view(torch.int32), code], 1).to(device)            # the one copy
+    head = dev[:, :8].reshape(-1).view(torch.int64).reshape(n, 4)                                     # flat first: a row's stride is odd
+    scores = dev[:, 8].contiguous().view(torch.float32) if all(with_score) else None
+    return ids, head[:, 0].contiguous(), head[:, 1].contiguous(), dev[:, 9:].contiguous(), head[:, 2:4].contiguous(), scores
 
 
 GATE_TILES = (8, 16, 32, 64)

@@ -749,6 +749,73 @@ def evaluate_instances_step(module, batch, meter=None, **kw):
     return out
 
 
+@torch.no_grad()
+def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64):
+    """Score stored records: dt a COCO / LVIS results list (ops.instances_to_coco's records, with "score"), gt an annotation list,
+    both with RLE segmentations (list or compressed string counts; ops.coco_to_instances), into an InstanceAPMeter -- what
+    evaluate_instances_step feeds it, from files instead of a network.  The lists are paired by "image_id": one ground-truth instance
+    an image, as everywhere in this library, and at most one result; an image with ground truth but no result enters as an empty
+    record (area 0, score 0, class -1).  The images are taken in gt's order, grouped by mask size and cut into chunks of `chunk`; per
+    chunk ONE host-to-device copy carries both sides, ops.rle_bits decodes them, ops.mask_pair_counts (d = ops.boundary_dilation(H, W,
+    boundary)) counts, and meter.update(cat, conf, stats, pair, cls) takes stats[:, 0] = the decoded area, conf[:, 0] = the record's
+    score and cls = the annotation's category_id.  No host read beyond the parse: a code that is not valid scores as an empty mask
+    (ops.rle_bits(check=True) tells one).  Returns the number of images.  ValueError for two records of one image on either side, a
+    result without ground truth, without a score or of another size than its ground truth, and as ops.coco_to_instances."""
+    from . import ops
+    if isinstance(boundary, bool) or not isinstance(boundary, float) or not (boundary > 0.0) or math.isinf(boundary):
+        raise ValueError(f"boundary must be a finite float > 0, got {boundary!r}")
+    if isinstance(chunk, bool) or int(chunk) != chunk or int(chunk) < 1:
+        raise ValueError(f"chunk must be an integer >= 1, got {chunk!r}")
+    device = meter.device if device is None else torch.device(device)
+
+    def by_image(records, what):
+        out = {}
+        for i, r in enumerate(records):
+            if not isinstance(r, dict) or "image_id" not in r:
+                raise ValueError(f"{what} record {i}: the key 'image_id' is missing")
+            if r["image_id"] in out:
+                raise ValueError(f"{what}: image {r['image_id']!r} has more than one record; one instance an image is scored")
+            out[r["image_id"]] = r
+        return out
+
+    def size_of(r, what):
+        seg = r.get("segmentation")
+        if not isinstance(seg, dict) or "size" not in seg or len(seg["size"]) != 2:
+            raise ValueError(f"{what} of image {r['image_id']!r}: the segmentation must be an RLE dict with a size (polygons are not rasterised here)")
+        return int(seg["size"][0]), int(seg["size"][1])
+
+    gts, dts = by_image(gt, "ground truth"), by_image(dt, "results")
+    groups = {}
+    for image_id, g in gts.items():
+        groups.setdefault(size_of(g, "the ground truth"), []).append(image_id)
+    for image_id, r in dts.items():
+        if image_id not in gts:
+            raise ValueError(f"results: image {image_id!r} has no ground truth")
+        if "score" not in r:
+            raise ValueError(f"results: the record of image {image_id!r} has no score")
+        if size_of(r, "the result") != size_of(gts[image_id], "the ground truth"):
+            raise ValueError(f"image {image_id!r}: the result's size {size_of(r, 'the result')} differs from the ground truth's "
+                             f"{size_of(gts[image_id], 'the ground truth')}")
+    for (H, W), ids in groups.items():
+        d = ops.boundary_dilation(H, W, boundary)
+        if d > ops.MORPH_MAX_D:
+            raise ValueError(f"boundary {boundary!r} gives a dilation of {d} pixels at {(H, W)}, above ops.MORPH_MAX_D = {ops.MORPH_MAX_D}")
+        for at in range(0, len(ids), int(chunk)):
+            part = ids[at:at + int(chunk)]
+            n = len(part)
+            missing = {"category_id": -1, "score": 0.0, "segmentation": {"size": [H, W], "counts": [H * W]}}
+            both = [dict(dts.get(i, missing), image_id=i) for i in part] + [dict(gts[i], score=0.0) for i in part]
+            _ids, cat, n_runs, counts, _sizes, scores = ops.coco_to_instances(both, device)
+            bits, info = ops.rle_bits(counts, n_runs, (H, W))
+            pair = ops.mask_pair_counts(bits[:n], bits[n:], d, Ws=W)
+            stats = torch.zeros(n, 6, device=device, dtype=torch.int64)
+            stats[:, 0] = info[:n, 1]
+            conf = torch.zeros(n, 3, device=device, dtype=torch.float32)
+            conf[:, 0] = scores[:n]
+            meter.update(cat[:n], conf, stats, pair, cat[n:])
+    return len(gts)
+
+
 # ----------------------------------------------------------------------------------------------
 # checkpoint / resume (SURVEY.md §8(f)-4)
 # ----------------------------------------------------------------------------------------------

@@ -204,6 +204,25 @@ int fs_mask_bits(const unsigned char* mask, unsigned int* bits, int B, int Hs, i
  * Hs * Ws >= 2^31. */
 long fs_mask_rle_scratch_ints(int B, int Hs, int Ws);
 int fs_mask_rle(const unsigned int* bits, long long* stats, int* counts, int* scratch, int B, int Hs, int Ws, int cap, fs_stream_t stream);
+/* fs_mask_rle's inverse: the uncompressed run-length code back into bit words, exact and on the device (UNPINNED, as the code itself).
+ * counts (B,cap) int32 as fs_mask_rle defines them: runs of 0, 1, 0, ... over the mask flattened column-major, p = x * Hs + y, the run
+ * of zeros first.  n_runs[b * n_stride] int64 = the length of image b's code: a (B) vector has n_stride = 1, a stats (B,6) tensor is
+ * passed as it lies (pointer to its column 5, n_stride = 6).  Entries of counts at or past n_runs are never read.  Every well-formed
+ * code is accepted, canonical or not: zero-length runs may stand anywhere, [N] is the empty mask and [0, N] the full one, N = Hs * Ws.
+ * With end[r] the sum of the first r + 1 counts, pixel p takes (the first r with end[r] > p) & 1.  bits (B,Hs,P), P = ceil(Ws/32), in
+ * fs_mask_bits' layout, the bits at x >= Ws always 0; every word is written by a plain store: nothing to zero beforehand, no atomics,
+ * no host read, the same bits in every mode.  info (B,4) int64 = (status, area, n_read, total): n_read = min(max(n_runs, 0), cap);
+ * total = the int64 sum of the n_read counts; status = the first that applies of 1 CUT (n_runs > cap), 2 BAD (n_runs < 1, or a count
+ * read is negative), 3 SUM (total != N), else 0; area = the sum of the odd-indexed counts where status is 0, else 0.  An image whose
+ * status is not 0 gets all-zero words; no code makes the kernels read or write outside their tensors (every address comes from B, Hs,
+ * Ws, cap and n_read alone).  Two passes: one workgroup an image scans the counts into clamped int ends in scratch and writes info; a
+ * wave per 64 columns x 64 rows bisects for the run of each column's first pixel, walks down the columns and ballots a row's two
+ * words.  scratch = fs_rle_bits_scratch_ints(B, cap) ints (B * cap + 2 B; 0 for B < 1 or cap < 1), any 4-byte alignment; its contents
+ * after the call are unspecified.  FS_ERR_ARG, with nothing launched, for a null pointer, n_stride < 1, cap < 1, non-positive sizes,
+ * Hs * Ws >= 2^31 or more than 2^32 - 256 bit slots (B * Hs * P * 32). */
+long fs_rle_bits_scratch_ints(int B, int cap);
+int fs_rle_bits(const int* counts, const long long* n_runs, int n_stride, unsigned int* bits, long long* info, int* scratch, int B, int Hs,
+                int Ws, int cap, fs_stream_t stream);
 /* The gazed instance of the C1 head as a record, without a class map: the mask is "fs_unwarp_labels' class is not K-1" bit for bit
  * (same kernels up to the gather, which stores bit words instead of classes), stats and counts are fs_mask_rle's of it.  cat (B)
  * int64 = the first maximal k < K-1 of cls[b,k], NaN maximal (torch.argmax(cls[:, :K-1], 1)): the head's classification, and the
