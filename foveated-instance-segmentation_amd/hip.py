@@ -49,6 +49,7 @@ SIGNATURES = {
     "fs_mask_bits": "pp" + "iii",
     "fs_mask_rle": "pppp" + "iiii",
     "fs_rle_bits": "pp" + "i" + "ppp" + "iiii",
+    "fs_poly_bits": "pppppp" + "iiiii",
     "fs_unwarp_instances": "pppppppp" + "iiiiiii",
     "fs_head_fg_q": "ppp" + "iiii",
     "fs_unwarp_instances_scored": "pppppppppp" + "iiiiiii",
@@ -180,6 +181,8 @@ HOST_ONLY = {
     "fs_surface_hd_scratch_ints": ("l", "iii"),
     "fs_mask_rle_scratch_ints": ("l", "iii"),
     "fs_rle_bits_scratch_ints": ("l", "ii"),
+    "fs_poly_bits_scratch_ints": ("l", "iii"),
+    "fs_poly_bits_band_rows": ("i", "ii"),
     "fs_unwarp_instances_scratch_ints": ("l", "iiiii"),
     "fs_unwarp_instances_scored_scratch_ints": ("l", "iiiii"),
     "fs_mask_component_scratch_ints": ("l", "iii"),

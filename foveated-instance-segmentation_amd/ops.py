@@ -2127,6 +2127,139 @@ def coco_to_instances(records, device, max_runs=None):
     return ids, head[:, 0].contiguous(), head[:, 1].contiguous(), dev[:, 9:].contiguous(), head[:, 2:4].contiguous(), scores
 
 
+POLY_SIDE_MAX = 16384                               # fs_poly_bits' cap on a side: coordinate products stay inside int32
+POLY_STATUS = {0: "valid", 1: "the image's ring or vertex offsets are out of range or decreasing"}
+
+
+def polygon_rings(polys):
+    """COCO / LVIS polygon lists as the three tables fs_poly_bits takes (host).  polys: a list with one entry per image, each entry a
+    polygon list [[x0, y0, x1, y1, ...], ...] as an annotation's "segmentation" carries it; an empty polygon list is allowed and is
+    the empty mask.  Returns CPU tensors (verts (V,2) int32 = (y, x); ring_off (R+1,) int32: ring r owns verts[ring_off[r] :
+    ring_off[r+1]]; img_ring (B+1,) int32: image b owns the rings img_ring[b] : img_ring[b+1]).  The coordinates are rounded half to
+    even on float64 (np.round, as the reference's b2_preprocess_lvis.py:282-297 does) and NOT clipped: poly_bits clamps them onto
+    the frame.  ValueError, naming the image and the ring, for an entry that is not a list of lists, a ring of odd or zero length, a
+    coordinate that is no number or not finite, and a rounded value outside int32."""
+    import numpy as np
+    if not isinstance(polys, (list, tuple)):
+        raise ValueError(f"polys must be a list with one polygon list per image, got {type(polys).__name__}")
+    rows, ring_off, img_ring = [], [0], [0]
+    for b, entry in enumerate(polys):
+        if not isinstance(entry, (list, tuple)) or any(not isinstance(ring, (list, tuple)) for ring in entry):
+            raise ValueError(f"image {b}: the segmentation must be a polygon list, a list of lists [x0, y0, x1, y1, ...]")
+        for j, ring in enumerate(entry):
+            if len(ring) == 0 or len(ring) % 2:
+                raise ValueError(f"image {b}, ring {j}: a ring is x, y pairs; it has {len(ring)} numbers")
+            for k, v in enumerate(ring):
+                if isinstance(v, bool) or not isinstance(v, (int, float)):
+                    raise ValueError(f"image {b}, ring {j}: coordinate {k} = {v!r} is no number")
+            try:
+                xy = np.round(np.array([float(v) for v in ring], dtype=np.float64))
+            except OverflowError:
+                raise ValueError(f"image {b}, ring {j}: a coordinate is outside float64") from None
+            if not np.isfinite(xy).all():
+                raise ValueError(f"image {b}, ring {j}: coordinate {int(np.flatnonzero(~np.isfinite(xy))[0])} is not finite")
+            if (xy < -INT32_MAX - 1).any() or (xy > INT32_MAX).any():
+                raise ValueError(f"image {b}, ring {j}: a rounded coordinate is outside int32")
+            rows.append(xy.reshape(-1, 2)[:, ::-1].astype(np.int32))                  # (x, y) pairs -> (y, x)
+            ring_off.append(ring_off[-1] + len(ring) // 2)
+        img_ring.append(len(ring_off) - 1)
+    if ring_off[-1] > INT32_MAX:
+        raise ValueError(f"{ring_off[-1]} vertices are more than int32 offsets hold")
+    verts = np.concatenate(rows, 0) if rows else np.zeros((0, 2), dtype=np.int32)
+    return (torch.from_numpy(np.ascontiguousarray(verts)), torch.tensor(ring_off, dtype=torch.int32), torch.tensor(img_ring, dtype=torch.int32))
+
+
+def _poly_args(verts, ring_off, img_ring, size):
+    """(B, R, V, Hs, Ws) of poly_bits' arguments, or ValueError: the checks of the host, nothing launched."""
+    for name, t, ok in (("verts", verts, lambda t: t.dim() == 2 and t.shape[1] == 2), ("ring_off", ring_off, lambda t: t.dim() == 1 and t.numel() >= 1),
+                        ("img_ring", img_ring, lambda t: t.dim() == 1 and t.numel() >= 2)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not ok(t):
+            raise ValueError(f"{name} must be an int32 tensor -- verts (V, 2), ring_off (R + 1,), img_ring (B + 1,), B >= 1 -- got "
+                             f"{getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))}")
+    if not (verts.device == ring_off.device == img_ring.device):
+        raise ValueError("verts, ring_off and img_ring must be on one device")
+    if len(size) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 1 or int(v) > POLY_SIDE_MAX for v in size):
+        raise ValueError(f"size must be two integers 1 .. {POLY_SIDE_MAX} (Hs, Ws), got {size!r}")
+    return int(img_ring.numel()) - 1, int(ring_off.numel()) - 1, int(verts.shape[0]), int(size[0]), int(size[1])
+
+
+def poly_bits(verts, ring_off, img_ring, size, device=None, check=False):
+    """Polygon lists as bit words, on the device (fs_poly_bits; no autograd).  verts, ring_off, img_ring as polygon_rings makes them
+    (int32; (y, x) vertices rounded but not clipped), size = (Hs, Ws), each side at most 16384.  Tables on the host go to `device`
+    (default "cuda") in ONE host-to-device copy; tables already on a device are used where they lie.  UNPINNED -- the reference makes
+    its labels with np.round, a clip onto the frame and skimage.draw.polygon (b2_preprocess_lvis.py:282-297), which is not at hand, so
+    the rule is this library's restatement of what that is understood to give for integer vertices, not verified against it: a vertex
+    is clamped to the frame; a ring is the closed chain of a polygon's vertices; it sets pixel (y, x) iff the pixel lies on one of its
+    edges (end points included) or the even-odd crossing number is odd (edges oriented so that y0 < y1, y0 <= y < y1, counted where
+    (x - x0)(y1 - y0) < (y - y0)(x1 - x0)); an image's mask is the OR of its rings, so overlapping polygons do not cancel while a
+    self-intersecting ring follows even-odd.  It is not pycocotools' frPoly, which traces a 5x upsampled outline and differs along the
+    rim.  Returns (bits (B,Hs,ceil(Ws/32)) int32 in mask_bits' layout, the bits at x >= Ws 0; info (B,4) int64 = (status, area,
+    n_rings, n_vertices)): status 0 valid, 1 the image's offsets are out of range or decreasing (all-zero words, area 0); an image
+    without rings is the empty mask.  No host read -- unless check=True, which reads info once and raises ValueError naming the first
+    image whose status is not 0.  mask_rle(bits, Ws) gives the label evaluate_instances(seg_label=(counts, stats)) takes."""
+    B, R, V, Hs, Ws = _poly_args(verts, ring_off, img_ring, size)
+    if verts.device.type == "cpu":
+        dev = torch.device("cuda" if device is None else device)
+        keep = torch.cat([img_ring, ring_off, verts.reshape(-1)]).to(dev)              # the one copy
+        p_img = hip.ptr(keep)
+        p_ring, p_verts = p_img + 4 * (B + 1), p_img + 4 * (B + 1 + R + 1)             # the buffer's end where V = 0: never read
+    else:
+        dev = verts.device
+        if device is not None and torch.device(device) != dev:
+            raise ValueError(f"the tables are on {dev}, not on {device}")
+        keep = (verts.contiguous(), ring_off.contiguous(), img_ring.contiguous())
+        p_ring, p_img = hip.ptr(keep[1]), hip.ptr(keep[2])
+        p_verts = hip.ptr(keep[0]) if V else p_ring
+    bits = torch.empty(B, Hs, (Ws + 31) // 32, device=dev, dtype=torch.int32)
+    info = torch.empty(B, 4, device=dev, dtype=torch.int64)
+    scratch = torch.empty(max(1, hip.query("fs_poly_bits_scratch_ints", B, Hs, Ws)), device=dev, dtype=torch.int32)
+    hip.call("fs_poly_bits", p_verts, p_ring, p_img, hip.ptr(bits), hip.ptr(info), hip.ptr(scratch), B, R, V, Hs, Ws)
+    del keep                                                                           # the tables, held until the launch is queued
+    if check:
+        for b, st in enumerate(info[:, 0].cpu().tolist()):
+            if st != 0:
+                raise ValueError(f"image {b}: {POLY_STATUS[st]} (status {st}; {R} rings, {V} vertices)")
+    return bits, info
+
+
+def coco_masks(records, size, device):
+    """COCO / LVIS records of ONE size as bit words, whichever way each carries its mask: "segmentation" an RLE dict (counts a list or
+    the compressed string) or a polygon list.  size = (H, W); records as coco_to_instances takes them ("image_id", "category_id",
+    "segmentation"; "score" in every record or in none).  Returns (image_ids, a list; cat (n,) int64; bits (n,H,ceil(W/32)) int32;
+    info (n,2) int64 = (status, area); scores (n,) fp32 or None), the rows in record order.  RLE rows go through coco_to_instances and
+    rle_bits, polygon rows through polygon_rings and poly_bits (unpinned rules both; see there): each kind is handed all n rows, the
+    other kind's rows as empty masks, and the two results are ORed, so the order needs no index on the device.  At most two
+    host-to-device copies (one a kind) and no host read: a code or offsets that are not valid give an empty mask and a status that is
+    not 0 (rle_bits' for an RLE row, poly_bits' for a polygon row).  ValueError as coco_to_instances and polygon_rings raise it (the
+    latter's "image i" is record i), and for an RLE record whose size is not `size`."""
+    records = list(records)
+    if len(size) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 1 for v in size):
+        raise ValueError(f"size must be two integers >= 1 (H, W), got {size!r}")
+    H, W = int(size[0]), int(size[1])
+    empty = {"size": [H, W], "counts": [H * W]}
+    as_rle, polys, n_poly = [], [], 0
+    for i, r in enumerate(records):
+        seg = r.get("segmentation") if isinstance(r, dict) else None
+        if isinstance(seg, (list, tuple)):
+            as_rle.append(dict(r, segmentation=empty))
+            polys.append(seg)
+            n_poly += 1
+        else:
+            if isinstance(seg, dict) and "size" in seg and list(seg["size"]) != [H, W]:
+                raise ValueError(f"record {i} (image {r.get('image_id')!r}): the code's size {seg['size']!r} is not {[H, W]}")
+            as_rle.append(r)
+            polys.append([])
+    ids, cat, n_runs, counts, _sizes, scores = coco_to_instances(as_rle, device)
+    bits = info = None
+    if n_poly < len(records):
+        bits, info4 = rle_bits(counts, n_runs, (H, W))
+        info = info4[:, :2]
+    if n_poly:
+        pbits, pinfo = poly_bits(*polygon_rings(polys), (H, W), device=device)
+        bits, info = (pbits, pinfo[:, :2]) if bits is None else (bits | pbits, info + pinfo[:, :2])
+    return ids, cat, bits, info.contiguous(), scores
+
+
 GATE_TILES = (8, 16, 32, 64)
 GATE_CODES = {0: "REUSE", 1: "RUN_INIT", 2: "HOLD_SACCADE", 3: "RUN_SCENE", 4: "RUN_ROI", 5: "RUN_GAZE", 6: "RUN_AGE", 7: "RUN_FORCED"}
 GATE_RUNS = (1, 3, 4, 5, 6, 7)                      # the codes after which the network runs

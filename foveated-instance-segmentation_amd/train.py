@@ -750,7 +750,7 @@ def evaluate_instances_step(module, batch, meter=None, **kw):
 
 
 @torch.no_grad()
-def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64):
+def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64, images=None):
     """Score stored records: dt a COCO / LVIS results list (ops.instances_to_coco's records, with "score"), gt an annotation list,
     both with RLE segmentations (list or compressed string counts; ops.coco_to_instances), into an InstanceAPMeter -- what
     evaluate_instances_step feeds it, from files instead of a network.  The lists are paired by "image_id": one ground-truth instance
@@ -760,7 +760,13 @@ def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64):
     boundary)) counts, and meter.update(cat, conf, stats, pair, cls) takes stats[:, 0] = the decoded area, conf[:, 0] = the record's
     score and cls = the annotation's category_id.  No host read beyond the parse: a code that is not valid scores as an empty mask
     (ops.rle_bits(check=True) tells one).  Returns the number of images.  ValueError for two records of one image on either side, a
-    result without ground truth, without a score or of another size than its ground truth, and as ops.coco_to_instances."""
+    result without ground truth, without a score or of another size than its ground truth, and as ops.coco_to_instances.
+
+    images: the annotation file's "images" list (dicts with "id", "height", "width") or a dict image_id -> (H, W).  With it a
+    segmentation may on either side be a polygon list, as LVIS v1 and COCO's non-crowd annotations carry it: its size comes from
+    `images` (ValueError for an image that is not there), and a chunk's masks come from ops.coco_masks -- RLE rows through
+    ops.rle_bits, polygon rows through ops.poly_bits (the reference's rasterisation restated, unpinned: see there), at most two copies
+    a chunk.  With images=None every call, result and error is what it was without the argument."""
     from . import ops
     if isinstance(boundary, bool) or not isinstance(boundary, float) or not (boundary > 0.0) or math.isinf(boundary):
         raise ValueError(f"boundary must be a finite float > 0, got {boundary!r}")
@@ -778,8 +784,20 @@ def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64):
             out[r["image_id"]] = r
         return out
 
+    sizes = None
+    if images is not None:
+        try:
+            sizes = {k: (int(v[0]), int(v[1])) for k, v in images.items()} if isinstance(images, dict) else \
+                {im["id"]: (int(im["height"]), int(im["width"])) for im in images}
+        except (KeyError, TypeError, IndexError, ValueError):
+            raise ValueError('images must be a list of dicts with "id", "height" and "width", or a dict image_id -> (H, W)') from None
+
     def size_of(r, what):
         seg = r.get("segmentation")
+        if sizes is not None and isinstance(seg, (list, tuple)):
+            if r["image_id"] not in sizes:
+                raise ValueError(f"{what} of image {r['image_id']!r} is a polygon list and the image is missing from `images`")
+            return sizes[r["image_id"]]
         if not isinstance(seg, dict) or "size" not in seg or len(seg["size"]) != 2:
             raise ValueError(f"{what} of image {r['image_id']!r}: the segmentation must be an RLE dict with a size (polygons are not rasterised here)")
         return int(seg["size"][0]), int(seg["size"][1])
@@ -805,8 +823,11 @@ def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64):
             n = len(part)
             missing = {"category_id": -1, "score": 0.0, "segmentation": {"size": [H, W], "counts": [H * W]}}
             both = [dict(dts.get(i, missing), image_id=i) for i in part] + [dict(gts[i], score=0.0) for i in part]
-            _ids, cat, n_runs, counts, _sizes, scores = ops.coco_to_instances(both, device)
-            bits, info = ops.rle_bits(counts, n_runs, (H, W))
+            if sizes is None:
+                _ids, cat, n_runs, counts, _sizes, scores = ops.coco_to_instances(both, device)
+                bits, info = ops.rle_bits(counts, n_runs, (H, W))
+            else:
+                _ids, cat, bits, info, scores = ops.coco_masks(both, (H, W), device)
             pair = ops.mask_pair_counts(bits[:n], bits[n:], d, Ws=W)
             stats = torch.zeros(n, 6, device=device, dtype=torch.int64)
             stats[:, 0] = info[:n, 1]

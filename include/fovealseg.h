@@ -223,6 +223,39 @@ int fs_mask_rle(const unsigned int* bits, long long* stats, int* counts, int* sc
 long fs_rle_bits_scratch_ints(int B, int cap);
 int fs_rle_bits(const int* counts, const long long* n_runs, int n_stride, unsigned int* bits, long long* info, int* scratch, int B, int Hs,
                 int Ws, int cap, fs_stream_t stream);
+/* COCO / LVIS polygon lists into bit words, exact and on the device.  The reference makes its labels this way in its dataset
+ * preparation (DynamicFocus/e_preprocess_scripts/b2_preprocess_lvis.py:282-297): per polygon np.round, a clip of x to [0, W-1] and of y
+ * to [0, H-1], skimage.draw.polygon, and the union of the polygons as the label.  UNPINNED: skimage is not at hand, so the definition
+ * is this library's, restated from that call site -- what skimage.draw.polygon is understood to produce for integer vertices (the
+ * interior plus the edge and vertex points), not verified against it.  It is NOT pycocotools' frPoly, which traces a 5x upsampled
+ * outline and differs along the rim.
+ *   vertex  (vy, vx) = (clamp(y, 0, Hs-1), clamp(x, 0, Ws-1)); the caller rounds (round half to even on the file's double), the
+ *           kernel clamps: any int32 is defined and no vertex value ever forms an address.
+ *   ring    the closed chain of a polygon's n >= 1 vertices, edges (v_i, v_(i+1) mod n).
+ *   pixel   the integer point (y, x) is set by a ring iff (a) it lies on an edge, end points included (cross product 0 and inside the
+ *           edge's box; a one-vertex ring is its point, a two-vertex ring its segment's lattice points), or (b) the crossing number is
+ *           odd: of the edges oriented so that y0 < y1 with y0 <= y < y1, those with (x - x0)(y1 - y0) < (y - y0)(x1 - x0) are
+ *           counted; horizontal edges do not count.
+ *   mask    the OR of the image's rings: overlapping polygons do not cancel, a self-intersecting ring follows even-odd.
+ * verts (V,2) int32 = (y, x), rounded, not clipped; ring_off (R+1) int32: ring r owns verts[ring_off[r] : ring_off[r+1]]; img_ring
+ * (B+1) int32: image b owns the rings img_ring[b] : img_ring[b+1]; vertices no ring of the call's images owns are never read.  bits
+ * (B,Hs,P), P = ceil(Ws/32), in fs_mask_bits' layout, the bits at x >= Ws always 0; every word is written by a plain store: nothing to
+ * zero beforehand, no atomics on global memory, no host read.  info (B,4) int64 = (status, area, n_rings, n_vertices): status 1 where
+ * img_ring[b], img_ring[b+1] are not 0 <= . <= . <= R or, over the image's rings, ring_off[r], ring_off[r+1] are not 0 <= . <= . <= V
+ * -- such an image gets all-zero words and (1, 0, 0, 0); else 0, area = the set pixels, n_rings and n_vertices as the offsets say.  An
+ * image without rings, or with empty rings only, is the empty mask with status 0.  One workgroup per image and band of
+ * fs_poly_bits_band_rows(Hs, Ws) = min(Hs, 64, 4096 / P) rows keeps a toggle buffer and the mask in LDS (32 KiB at the most) and takes
+ * ring after ring: every non-horizontal edge flips, for each of its rows y0 <= y < y1 in the band, the bit at column x0 + ceil((y -
+ * y0)(x1 - x0) / (y1 - y0)) (exact, by an incremental division) and ORs in its lattice points, horizontal edges OR their span; a
+ * prefix-XOR along each toggled row is the even-odd interior.  XOR and OR in LDS do not depend on order: the same bits in every mode
+ * and every run.  scratch = fs_poly_bits_scratch_ints(B, Hs, Ws) ints (one popcount per image and band, summed into info by a second
+ * kernel; 0 for sizes that are refused), any 4-byte alignment, as verts and bits.  FS_ERR_ARG, with nothing launched, for a null
+ * pointer, non-positive B, Hs or Ws, negative R or V, a side above 16384 (every product of two coordinate differences stays inside
+ * int32), Hs * Ws >= 2^31 or more than 2^32 - 256 bit slots (B * Hs * P * 32). */
+long fs_poly_bits_scratch_ints(int B, int Hs, int Ws);
+int fs_poly_bits_band_rows(int Hs, int Ws);
+int fs_poly_bits(const int* verts, const int* ring_off, const int* img_ring, unsigned int* bits, long long* info, int* scratch, int B, int R,
+                 int V, int Hs, int Ws, fs_stream_t stream);
 /* The gazed instance of the C1 head as a record, without a class map: the mask is "fs_unwarp_labels' class is not K-1" bit for bit
  * (same kernels up to the gather, which stores bit words instead of classes), stats and counts are fs_mask_rle's of it.  cat (B)
  * int64 = the first maximal k < K-1 of cls[b,k], NaN maximal (torch.argmax(cls[:, :K-1], 1)): the head's classification, and the
