@@ -57,6 +57,7 @@ SIGNATURES = {
     "fs_unwarp_instances_component": "p" * 12 + "iiiiiiii" + "l",
     "fs_mask_erode": "ppp" + "iiii",
     "fs_mask_pair_counts": "pppp" + "iiii",
+    "fs_mask_candidates": "p" * 9 + "iiii" + "l",
     "fs_gate_tiles": "ppp" + "iiii",
     "fs_gate_decide": "ppppppp" + "iiiiiiii" + "ll" + "ii",
     "fs_gate_commit": "pp" + "i" + "p" * 13 + "iiii",
@@ -190,6 +191,7 @@ HOST_ONLY = {
     "fs_unwarp_instances_component_scratch_ints": ("l", "iiiii"),
     "fs_mask_erode_scratch_ints": ("l", "iiii"),
     "fs_mask_pair_scratch_ints": ("l", "iiii"),
+    "fs_mask_candidates_scratch_ints": ("l", "iiii"),
     "fs_state_shift_scratch_ints": ("l", "iiii"),
     "fs_byte_frame_route": ("l", "plli" + "i"),
 }

@@ -294,7 +294,8 @@ class DeformSegmentationModule(nn.Module):
         return ops.unwarp_instances(cls, m, grid, *seg_size, max_runs=max_runs, return_bits=return_bits)
 
     @torch.no_grad()
-    def evaluate_instances(self, img, focus, seg_label, cls_label, seg_size=None, max_runs=None, component=None, snap_px=None, boundary=0.02):
+    def evaluate_instances(self, img, focus, seg_label=None, cls_label=None, seg_size=None, max_runs=None, component=None, snap_px=None, boundary=0.02,
+                           candidates=None, cand_snap_px=None):
         """The instance record scored against the label: predict_instances(..., return_bits=True, return_score=True, component=...),
         then the counters of mask IoU and Boundary IoU (Cheng et al., CVPR 2021, restated: unpinned) of the record's mask against the
         label's foreground `seg_label.long() != 0` (evaluate's hausdorff rule), taken on bit words (ops.mask_bits, ops.mask_pair_counts).
@@ -312,7 +313,22 @@ class DeformSegmentationModule(nn.Module):
         (B,cap) int32, n_runs int64 (B,) or a stats (B,6) tensor --, at seg_size, which is then required (ops.coco_to_instances makes
         both from COCO / LVIS annotations).  The label's bit words then come from ops.rle_bits instead of ops.mask_bits and no dense
         label exists at all.  An image whose code is not valid (cut, a negative count, a wrong sum) scores as an empty label, |g| = 0:
-        the call still reads nothing on the host; ops.rle_bits(counts, n_runs, seg_size, check=True) tells such a code beforehand."""
+        the call still reads nothing on the host; ops.rle_bits(counts, n_runs, seg_size, check=True) tells such a code beforehand.
+
+        candidates = (cbits, cand_off, cand_cat) gives the images' annotated instances instead of one label (ops.coco_candidates makes
+        the three from an annotation file's records): cbits (N,H,ceil(W/32)) int32 bit words at seg_size, which is then required,
+        cand_off (B+1,) int32, cand_cat (N,) int64 or None.  seg_label and cls_label must then be None.  The label is the candidate
+        selected by the call's own focus (ops.mask_candidates, unpinned: of the instances that contain the gaze pixel the smallest,
+        else the nearest within cand_snap_px pixels, None meaning any distance): after predict_instances one
+        ops.mask_candidates(..., pred=the record's bits) and one ops.mask_pair_counts(the record's bits, the selected words, d)
+        follow, without a host read.  Returns (cat, stats, counts, conf[, comp], pair, sel): sel (B,8) int64 as ops.mask_candidates'
+        -- sel[:, 1] is the class train.InstanceAPMeter needs, sel[:, 0] the selected row, sel[:, 6] the row that overlaps the
+        record best; an image whose gaze selects nothing has |g| = 0.  Without the keyword every call and result is what it was."""
+        if candidates is None:
+            if cand_snap_px is not None:
+                raise ValueError("cand_snap_px goes with candidates")
+            if seg_label is None or cls_label is None:
+                raise TypeError("evaluate_instances() needs seg_label and cls_label, or candidates=(cbits, cand_off, cand_cat)")
         if isinstance(boundary, bool) or not isinstance(boundary, float) or not (boundary > 0.0) or math.isinf(boundary):
             raise ValueError(f"boundary must be a finite float > 0, got {boundary!r}")
         if component is None:
@@ -320,6 +336,27 @@ class DeformSegmentationModule(nn.Module):
                 raise ValueError("snap_px goes with component = 4 or 8")
         else:
             ops._component_args(component, snap_px)
+        if candidates is not None:
+            if seg_label is not None or cls_label is not None:
+                raise ValueError("with candidates the label is the selected candidate: seg_label and cls_label must be None")
+            if not isinstance(candidates, (tuple, list)) or len(candidates) != 3:
+                raise ValueError("candidates is a tuple (cbits, cand_off, cand_cat)")
+            if seg_size is None or len(seg_size) != 2:
+                raise ValueError("candidates need seg_size = (H, W): bit words do not carry their width")
+            cbits, cand_off, cand_cat = candidates
+            label_size = (int(seg_size[0]), int(seg_size[1]))
+            ops._component_args(8, cand_snap_px)
+            _N, Hc, _P, Bc = ops._candidate_args(cbits, cand_off, label_size[1], cand_cat)          # before the network runs
+            if Hc != label_size[0] or Bc != img.shape[0]:
+                raise ValueError(f"candidates of height {Hc} for {Bc} images do not go with seg_size {label_size} and img's batch size {img.shape[0]}")
+            d = ops.boundary_dilation(*label_size, boundary)
+            if d > ops.MORPH_MAX_D:
+                raise ValueError(f"boundary {boundary!r} gives a dilation of {d} pixels at {label_size}, above ops.MORPH_MAX_D = {ops.MORPH_MAX_D}")
+            out = self.predict_instances(img, focus, label_size, max_runs=max_runs, return_bits=True, return_score=True, component=component,
+                                         snap_px=snap_px)
+            gbits, sel, _cand = ops.mask_candidates(cbits, cand_off, focus, label_size[1], pred=out[3], cand_cat=cand_cat, snap_px=cand_snap_px)
+            pair = ops.mask_pair_counts(out[3], gbits, d, Ws=label_size[1])
+            return out[:3] + out[4:] + (pair, sel)
         if isinstance(seg_label, (tuple, list)):
             if len(seg_label) != 2:
                 raise ValueError(f"a run-length label is a tuple (counts, n_runs), got {len(seg_label)} elements")

@@ -2260,6 +2260,102 @@ def coco_masks(records, size, device):
     return ids, cat, bits, info.contiguous(), scores
 
 
+def _candidate_args(cbits, cand_off, Ws, cand_cat):
+    """(N, Hs, P, B) of mask_candidates' tables, or ValueError: the checks of the host, nothing launched."""
+    if not isinstance(cbits, torch.Tensor) or cbits.dtype != torch.int32 or cbits.dim() != 3 or Ws is None or isinstance(Ws, bool) \
+            or int(Ws) != Ws or int(Ws) < 1 or cbits.shape[2] != (int(Ws) + 31) // 32 or cbits.shape[1] < 1:
+        raise ValueError(f"cbits must be int32 bit words (N, Hs, ceil(Ws / 32)) with Hs >= 1 and Ws given, got "
+                         f"{getattr(cbits, 'dtype', None)} {tuple(getattr(cbits, 'shape', ()))} and Ws = {Ws!r}")
+    N, Hs, P = (int(v) for v in cbits.shape)
+    if not isinstance(cand_off, torch.Tensor) or cand_off.dtype != torch.int32 or cand_off.dim() != 1 or cand_off.numel() < 2:
+        raise ValueError(f"cand_off must be an int32 tensor (B + 1,), B >= 1, got {getattr(cand_off, 'dtype', None)} "
+                         f"{tuple(getattr(cand_off, 'shape', ()))}")
+    if cand_cat is not None and (not isinstance(cand_cat, torch.Tensor) or cand_cat.dtype != torch.int64 or tuple(cand_cat.shape) != (N,)):
+        raise ValueError(f"cand_cat must be int64 ({N},), got {getattr(cand_cat, 'dtype', None)} {tuple(getattr(cand_cat, 'shape', ()))}")
+    for name, t in (("cand_off", cand_off), ("cand_cat", cand_cat)):
+        if t is not None and t.device != cbits.device:
+            raise ValueError(f"{name} is on {t.device}, cbits on {cbits.device}")
+    if Hs > POLY_SIDE_MAX or int(Ws) > POLY_SIDE_MAX:
+        raise ValueError(f"a side of {(Hs, int(Ws))} is above {POLY_SIDE_MAX}")
+    return N, Hs, P, int(cand_off.numel()) - 1
+
+
+def mask_candidates(cbits, cand_off, focus, Ws, pred=None, cand_cat=None, snap_px=None):
+    """Of every image's annotated instances, the one under the gaze, on the device and on bit words (fs_mask_candidates; no autograd).
+    UNPINNED: the reference builds its labels by choosing an annotation and putting the gaze inside it
+    (b2_preprocess_lvis.py:258-333); this is the inverse of that step and a definition of this library's.  cbits (N,Hs,ceil(Ws/32))
+    int32, the candidates' masks in mask_bits' layout (N = 0 allowed; the bits at x >= Ws are not read); cand_off (B+1,) int32: image
+    b owns the rows cand_off[b] : cand_off[b+1]; focus (B,2) normalised (row, col), turned into a gaze pixel as mask_component does;
+    pred (B,Hs,ceil(Ws/32)) int32 or None, a prediction's bit words per image; cand_cat (N,) int64 or None; snap_px None (any
+    distance) or a finite number of pixels >= 0, snap2 = floor(snap_px ** 2) (as mask_component).  Returns (gbits, sel, cand):
+
+    cand (N,6) int64 = (b, area, inter, d2, near_y, near_x): the row's image, its set pixels, |c & pred[b]| (0 without pred), and its
+    set pixel nearest to the gaze pixel with the squared distance (ties to the smaller row-major index; -1, -1, -1 for an empty row).
+    sel (B,8) int64 = (index, cls, d2, area, inter, n_hit, best, status).  index: the SELECTED row -- among the image's rows with area >
+    0 and d2 <= snap2 the least (d2, area, row): of several instances that contain the gaze pixel the smallest (a cup on a table gives
+    the cup), of none the nearest within the snap distance, ties to the smaller area, then row -- or -1; cls = cand_cat[index] (-1
+    for none or without cand_cat); d2, area, inter the selected row's (-1, 0, 0); n_hit how many of the image's rows contain the gaze
+    pixel; best: among rows with inter > 0 the one of the greatest IoU with pred[b], compared exactly in integers, ties to the smaller
+    area, then row, or -1.  gbits (B,Hs,ceil(Ws/32)) int32 = the selected row's words with the bits at x >= Ws cleared, all 0 where
+    none is selected.  status 1 in every image where cand_off is not 0 = cand_off[0] <= ... <= cand_off[B] = N: then nothing is
+    selected anywhere and every cand row is (-1, area, 0, -1, -1, -1).  No host read; the same bits in every run."""
+    _conn, snap2 = _component_args(8, snap_px)
+    N, Hs, P, B = _candidate_args(cbits, cand_off, Ws, cand_cat)
+    Ws, dev = int(Ws), cbits.device
+    f = _focus_arg(focus, B, dev)
+    if pred is not None and (not isinstance(pred, torch.Tensor) or pred.dtype != torch.int32 or tuple(pred.shape) != (B, Hs, P) or pred.device != dev):
+        raise ValueError(f"pred must be int32 bit words {(B, Hs, P)} on {dev}, got {getattr(pred, 'dtype', None)} {tuple(getattr(pred, 'shape', ()))}")
+    gbits = torch.empty(B, Hs, P, device=dev, dtype=torch.int32)
+    sel = torch.empty(B, 8, device=dev, dtype=torch.int64)
+    cand = torch.empty(N, 6, device=dev, dtype=torch.int64)
+    scratch = torch.empty(max(1, hip.query("fs_mask_candidates_scratch_ints", B, N, Hs, Ws)), device=dev, dtype=torch.int32)
+    hip.call("fs_mask_candidates", hip.ptr(cbits.contiguous()) if N else None, hip.ptr(cand_off.contiguous()),
+             None if cand_cat is None or N == 0 else hip.ptr(cand_cat.contiguous()), hip.ptr(f),
+             None if pred is None else hip.ptr(pred.contiguous()), hip.ptr(cand) if N else None, hip.ptr(sel), hip.ptr(gbits),
+             hip.ptr(scratch), B, N, Hs, Ws, snap2)
+    return gbits, sel, cand
+
+
+def coco_candidates(records, size, device, image_ids):
+    """COCO / LVIS annotation records of ONE size, several an image, as mask_candidates' arguments.  records as coco_masks takes them
+    (RLE dicts or polygon lists, mixed); size = (H, W); image_ids the images in the order the batch has them.  The records are grouped
+    stably by "image_id" in the order of image_ids -- an id without records gets an empty range -- and rasterised through coco_masks
+    with its copies (at most two) plus one for the offsets.  Returns (cbits (N,H,ceil(W/32)) int32; cand_off (B+1,) int32; cand_cat
+    (N,) int64; info (N,2) int64 = coco_masks' (status, area); rows, a list: rows[i] is the index into `records` of candidate row i,
+    which maps mask_candidates' sel[:, 0] back to an annotation: records[rows[index]]["id"]).  "iscrowd" is not interpreted: a
+    crowd record is a candidate like any other.  ValueError for a record whose image is not in image_ids, an id named twice, and as
+    coco_masks."""
+    records, image_ids = list(records), list(image_ids)
+    if not image_ids:
+        raise ValueError("no image_ids")
+    place = {}
+    for b, image_id in enumerate(image_ids):
+        if image_id in place:
+            raise ValueError(f"image_ids names {image_id!r} twice")
+        place[image_id] = b
+    per = [[] for _ in image_ids]
+    for i, r in enumerate(records):
+        if not isinstance(r, dict) or "image_id" not in r:
+            raise ValueError(f"record {i}: the key 'image_id' is missing")
+        if r["image_id"] not in place:
+            raise ValueError(f"record {i}: image {r['image_id']!r} is not among image_ids")
+        per[place[r["image_id"]]].append(i)
+    rows = [i for group in per for i in group]
+    off = [0]
+    for group in per:
+        off.append(off[-1] + len(group))
+    if len(size) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 1 for v in size):
+        raise ValueError(f"size must be two integers >= 1 (H, W), got {size!r}")
+    dev = torch.device(device)
+    H, W = int(size[0]), int(size[1])
+    cand_off = torch.tensor(off, dtype=torch.int32).to(dev)
+    if not rows:
+        return (torch.empty(0, H, (W + 31) // 32, device=dev, dtype=torch.int32), cand_off, torch.empty(0, device=dev, dtype=torch.int64),
+                torch.empty(0, 2, device=dev, dtype=torch.int64), rows)
+    _ids, cat, cbits, info, _scores = coco_masks([{k: v for k, v in records[i].items() if k != "score"} for i in rows], size, dev)
+    return cbits, cand_off, cat, info, rows
+
+
 GATE_TILES = (8, 16, 32, 64)
 GATE_CODES = {0: "REUSE", 1: "RUN_INIT", 2: "HOLD_SACCADE", 3: "RUN_SCENE", 4: "RUN_ROI", 5: "RUN_GAZE", 6: "RUN_AGE", 7: "RUN_FORCED"}
 GATE_RUNS = (1, 3, 4, 5, 6, 7)                      # the codes after which the network runs

@@ -740,8 +740,16 @@ class InstanceAPMeter:
 def evaluate_instances_step(module, batch, meter=None, **kw):
     """evaluate_step's counterpart for the instance record: module.evaluate_instances on (X, Fp, Y, cls) with **kw (component, snap_px,
     boundary, max_runs, seg_size) (module.eval() by caller).  Returns its (cat, stats, counts, conf[, comp], pair); an InstanceAPMeter
-    given as `meter` takes (cat, conf, stats, pair, cls) -- no host read."""
+    given as `meter` takes (cat, conf, stats, pair, cls) -- no host read.  With candidates=(cbits, cand_off, cand_cat) in **kw (and
+    cand_snap_px, seg_size) the batch's Y and cls are not read: the label is the candidate under the gaze, the result ends in (pair,
+    sel), and the meter takes sel[:, 1], the selected candidate's class, as cls."""
     X, Fp, Y, cls = batch
+    if kw.get("candidates") is not None:
+        out = module.evaluate_instances(X[:, :3], Fp, **kw)
+        module.check_nan()
+        if meter is not None:
+            meter.update(out[0], out[3], out[1], out[-2], out[-1][:, 1])
+        return out
     out = module.evaluate_instances(X[:, :3], Fp, Y, cls, **kw)
     module.check_nan()
     if meter is not None:
@@ -750,7 +758,7 @@ def evaluate_instances_step(module, batch, meter=None, **kw):
 
 
 @torch.no_grad()
-def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64, images=None):
+def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64, images=None, gaze=None):
     """Score stored records: dt a COCO / LVIS results list (ops.instances_to_coco's records, with "score"), gt an annotation list,
     both with RLE segmentations (list or compressed string counts; ops.coco_to_instances), into an InstanceAPMeter -- what
     evaluate_instances_step feeds it, from files instead of a network.  The lists are paired by "image_id": one ground-truth instance
@@ -766,7 +774,18 @@ def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64, imag
     segmentation may on either side be a polygon list, as LVIS v1 and COCO's non-crowd annotations carry it: its size comes from
     `images` (ValueError for an image that is not there), and a chunk's masks come from ops.coco_masks -- RLE rows through
     ops.rle_bits, polygon rows through ops.poly_bits (the reference's rasterisation restated, unpinned: see there), at most two copies
-    a chunk.  With images=None every call, result and error is what it was without the argument."""
+    a chunk.  With images=None every call, result and error is what it was without the argument.
+
+    gaze: a dict image_id -> (row, col), normalised as focus is, for annotation files as they are downloaded: gt may then hold any
+    number of records an image (dt still at most one), `images` is required (sizes come from there for polygon files), and an
+    image's label is the annotation under its gaze (ops.mask_candidates, unpinned: of the instances that contain the gaze pixel the
+    smallest, else the nearest one at any distance).  Per chunk: ops.coco_candidates for the ground truth, ops.coco_masks for the
+    results, ONE ops.mask_candidates (pred = the results' words), ONE ops.mask_pair_counts against the selected words, then
+    meter.update(cat, conf, stats, pair, sel[:, 1]) -- the selected annotation's category_id as cls.  An image whose gaze selects
+    nothing (every annotation empty or not valid) enters with |g| = 0, i.e. without a label instance, by the meter's rule.
+    "iscrowd" is not interpreted: a crowd record is a candidate like any other.  No host read beyond the parse.  ValueError for
+    gaze without images, an image of gt without a gaze, a gaze that is not two numbers, and records of one image that differ in size.
+    With gaze=None every call, result and error is what it is without the argument, the "more than one record" error included."""
     from . import ops
     if isinstance(boundary, bool) or not isinstance(boundary, float) or not (boundary > 0.0) or math.isinf(boundary):
         raise ValueError(f"boundary must be a finite float > 0, got {boundary!r}")
@@ -802,6 +821,59 @@ def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64, imag
             raise ValueError(f"{what} of image {r['image_id']!r}: the segmentation must be an RLE dict with a size (polygons are not rasterised here)")
         return int(seg["size"][0]), int(seg["size"][1])
 
+    if gaze is not None:
+        if not isinstance(gaze, dict):
+            raise ValueError("gaze must be a dict image_id -> (row, col)")
+        if sizes is None:
+            raise ValueError("gaze needs `images`: the sizes of polygon annotations come from there")
+        many = {}
+        for i, r in enumerate(gt):
+            if not isinstance(r, dict) or "image_id" not in r:
+                raise ValueError(f"ground truth record {i}: the key 'image_id' is missing")
+            many.setdefault(r["image_id"], []).append(r)
+        dts, groups, focus_of = by_image(dt, "results"), {}, {}
+        for image_id, recs in many.items():
+            if image_id not in gaze:
+                raise ValueError(f"ground truth: image {image_id!r} has no gaze")
+            try:
+                row, col = gaze[image_id]
+                focus_of[image_id] = (float(row), float(col))
+            except (TypeError, ValueError):
+                raise ValueError(f"the gaze of image {image_id!r} must be two numbers (row, col), got {gaze[image_id]!r}") from None
+            size = size_of(recs[0], "the ground truth")
+            for r in recs[1:]:
+                if size_of(r, "the ground truth") != size:
+                    raise ValueError(f"image {image_id!r}: its annotations differ in size, {size} and {size_of(r, 'the ground truth')}")
+            groups.setdefault(size, []).append(image_id)
+        for image_id, r in dts.items():
+            if image_id not in many:
+                raise ValueError(f"results: image {image_id!r} has no ground truth")
+            if "score" not in r:
+                raise ValueError(f"results: the record of image {image_id!r} has no score")
+            if size_of(r, "the result") != size_of(many[image_id][0], "the ground truth"):
+                raise ValueError(f"image {image_id!r}: the result's size {size_of(r, 'the result')} differs from the ground truth's "
+                                 f"{size_of(many[image_id][0], 'the ground truth')}")
+        for (H, W), ids in groups.items():
+            d = ops.boundary_dilation(H, W, boundary)
+            if d > ops.MORPH_MAX_D:
+                raise ValueError(f"boundary {boundary!r} gives a dilation of {d} pixels at {(H, W)}, above ops.MORPH_MAX_D = {ops.MORPH_MAX_D}")
+        for (H, W), ids in groups.items():
+            d = ops.boundary_dilation(H, W, boundary)
+            for at in range(0, len(ids), int(chunk)):
+                part = ids[at:at + int(chunk)]
+                n = len(part)
+                missing = {"category_id": -1, "score": 0.0, "segmentation": {"size": [H, W], "counts": [H * W]}}
+                cbits, cand_off, cand_cat, _info, _rows = ops.coco_candidates([r for i in part for r in many[i]], (H, W), device, part)
+                _ids, cat, bits, info, scores = ops.coco_masks([dict(dts.get(i, missing), image_id=i) for i in part], (H, W), device)
+                focus = torch.tensor([focus_of[i] for i in part], dtype=torch.float32).reshape(n, 2).to(device)
+                gbits, sel, _cand = ops.mask_candidates(cbits, cand_off, focus, W, pred=bits, cand_cat=cand_cat)
+                pair = ops.mask_pair_counts(bits, gbits, d, Ws=W)
+                stats = torch.zeros(n, 6, device=device, dtype=torch.int64)
+                stats[:, 0] = info[:, 1]
+                conf = torch.zeros(n, 3, device=device, dtype=torch.float32)
+                conf[:, 0] = scores
+                meter.update(cat, conf, stats, pair, sel[:, 1])
+        return len(many)
     gts, dts = by_image(gt, "ground truth"), by_image(dt, "results")
     groups = {}
     for image_id, g in gts.items():

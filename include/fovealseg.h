@@ -328,6 +328,40 @@ int fs_mask_erode(const unsigned int* bits, unsigned int* out, int* scratch, int
 long fs_mask_pair_scratch_ints(int B, int Hs, int Ws, int d);
 int fs_mask_pair_counts(const unsigned int* a, const unsigned int* b, long long* pair, int* scratch, int B, int Hs, int Ws, int d,
                         fs_stream_t stream);
+/* Of an image's annotated instances, the one under the gaze.  The reference builds its labels by choosing one annotation and putting
+ * the gaze on a pixel inside it (DynamicFocus/e_preprocess_scripts/b2_preprocess_lvis.py:258-333: rasterise the annotation, ridx_rrcc =
+ * np.random.randint(len(rrs))); this is the inverse of that step -- the gaze and the annotations are given, the annotation looked at is
+ * asked for -- and has no counterpart there.  UNPINNED: the definition is this library's.  All integers, on bit
+ * words.  cbits (N,Hs,P), P = ceil(Ws/32), the candidates' masks as fs_mask_bits lays them out (the bits at x >= Ws are not read as
+ * pixels); cand_off (B+1) int32: image b owns the rows cand_off[b] .. cand_off[b+1]-1; cand_cat (N) int64 the rows' classes, nullable;
+ * focus (B,2) fp32 = normalised (row, col); pbits (B,Hs,P) one prediction an image (the record's mask), nullable; snap2 = a squared
+ * distance in whole pixels.  The gaze pixel (py, px) is fs_mask_component's: gy = clamp(rint((double)f_row * ((Hs-1) * 16)), 0, (Hs-1)
+ * * 16), NaN -> 0, py = (gy + 8) >> 4, px likewise with Ws.  Per candidate n of image b: area = its set pixels; inter = |c_n & p_b| (0
+ * without pbits); its nearest set pixel to the gaze = the minimum of key = d2 * 2^31 + (y * Ws + x), d2 = (y-py)^2 + (x-px)^2
+ * (fs_mask_component's seed rule, ties to the smaller row-major index); cand (N,6) int64 = (b, area, inter, d2, near_y, near_x), the
+ * last three -1 for an empty candidate.  The SELECTED instance of image b is, among its candidates with area > 0 and d2 <= snap2, the
+ * least (d2, area, n) in lexicographic order: where several contain the gaze pixel the smallest one (a cup on a table gives the cup),
+ * where none does the nearest one within the snap distance, ties to the smaller area, then the smaller row.  The BEST-OVERLAPPING
+ * instance is, among candidates with inter > 0, the one of the greatest inter / (area + |p_b| - inter), compared exactly by
+ * cross-multiplication in int64 (the products stay below 2^57), ties to the smaller area, then the smaller row.  sel (B,8) int64 =
+ * (index, cls, d2, area, inter, n_hit, best, status): index the selected global row or -1; cls = cand_cat[index], -1 for no selection
+ * or no cand_cat; d2, area, inter the selected row's (-1, 0, 0 for none); n_hit the number of the image's candidates that contain the
+ * gaze pixel; best the best-overlapping row or -1; status 0.  gbits (B,Hs,P) = the selected candidate's words, the bits at x >= Ws 0;
+ * all 0 where none is selected; every word is written by a plain store: nothing to zero beforehand.  cand_off is valid iff cand_off[0]
+ * == 0, it is non-decreasing and cand_off[B] == N; otherwise every image gets status 1, index = best = -1, cls = d2 = -1, area = inter
+ * = n_hit = 0 and zero gbits, and every cand row is (-1, area, 0, -1, -1, -1).  Validity is decided once, by a pass of its own, before
+ * anything depends on it; a candidate finds its image by bisecting cand_off, so no offset value and no cand_cat value ever forms an
+ * address (cand_cat is read at a selected row only).  N = 0 is valid: every image selects nothing (cbits and cand may then be null).
+ * A workgroup per (candidate, band of at most 256 rows and 8192 words) reads the candidate's words once and writes one record (area,
+ * inter, |p|, key) into scratch; a wave per image adds its candidates' records in index order and selects; a workgroup per (image,
+ * band) copies.  No atomics, no host read: the same bits in every run.  scratch = fs_mask_candidates_scratch_ints(B, N, Hs, Ws) ints
+ * (0 for sizes that are refused), any 4-byte alignment; its contents after the call are unspecified.  FS_ERR_ARG, with nothing
+ * launched, for a null pointer other than cand_cat and pbits (and cbits, cand with N = 0), gbits == cbits, B < 1, N < 0, a side below 1
+ * or above 16384, Hs * Ws >= 2^31, N or B times the bands an image beyond int range, snap2 < 0. */
+long fs_mask_candidates_scratch_ints(int B, int N, int Hs, int Ws);
+int fs_mask_candidates(const unsigned int* cbits, const int* cand_off, const long long* cand_cat, const float* focus,
+                       const unsigned int* pbits, long long* cand, long long* sel, unsigned int* gbits, int* scratch, int B, int N, int Hs,
+                       int Ws, long snap2, fs_stream_t stream);
 /* fs_unwarp_instances / fs_unwarp_instances_scored with the record describing the component under the gaze instead of every foreground
  * pixel (no counterpart in the reference: UNPINNED).  The decide / owner / fill passes and the bit gather are fs_unwarp_instances';
  * with conf the gather is still the unscored one -- the words are the same, and the scored gather's sums over the whole mask would be
