@@ -1,34 +1,32 @@
-// A frame of interleaved bytes read where it lies (fs_*_hwc; include/fovealseg.h "frames as interleaved bytes"): the byte of channel c at
-// (b, y, x) is p[b * sb + y * sy + x * sx + c], sx = 3 (RGB) or 4 (RGBA / RGBX, the fourth byte never read into a result), rows of any
-// pitch sy >= W * sx, images sb apart or all one image (sb = 0).  One description, one acceptance rule and one choice of route for
-// every pass that takes such a frame: frames_u8.hip (the network's front), gaze_gate.hip (tiles, commit), gaze_motion.hip (profiles, move).
+// A frame a pass can read.  A (B,3,H,W) frame comes in three layouts, and every pass that takes one (gaze_gate.hip: tiles, commit;
+// gaze_motion.hip: profiles, move; frames_u8.hip: the network's front) is written once, over a reader of the layout:
+//   PlanarFrame<float>           fp32, the value of channel c at (b, y, x) is p[(b * 3 + c) * H * W + y * W + x]; its code is q(value)
+//   PlanarFrame<unsigned char>   bytes in the same order; the pixel value is byte / 255, whose code is the byte
+//   HwcFrame<SX>                 interleaved bytes read where they lie (fs_*_hwc; include/fovealseg.h "frames as interleaved bytes"): the
+//                                byte of channel c at (b, y, x) is p[b * sb + y * sy + x * sx + c], sx = 3 (RGB) or 4 (RGBA / RGBX, the
+//                                fourth byte never read into a result), rows of any pitch sy >= W * sx, images sb apart or all one image
+//                                (sb = 0).  SX = 3 or 4 where the pass knows the step at compile time (the vector forms), 0 for the sx
+//                                given at run time (the one-pixel forms).
+// A reader is built inside the kernel from the kernel's own pointer and scalars, and on the host from an entry point's arguments.  On the
+// device it offers the few reads the passes use, all from a pixel's address px(b, y, x): the code of a channel, the luma codes of four
+// pixels from aligned loads, sixteen bytes a channel in planar order (bytes only), and a tap's value (float)byte / 255, correctly rounded
+// (bytes only).  On the host it carries what it accepts (ok), when its vector forms apply (wide, quad, wide_commit) and how many key
+// bytes a lane of commit's vector form writes (lane).
 #pragma once
 #include "common.h"
 
-typedef unsigned int hwc_u32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-struct HwcView {
-  const unsigned char* p;
-  long sb, sy;
-  int sx;
-  explicit operator bool() const { return p != nullptr; }
-};
-
-// what every fs_*_hwc entry point asks of the description beyond its twin's conditions
-inline bool hwc_view_ok(const HwcView& v, int B, int H, int W) {
-  if (v.p == nullptr || (v.sx != 3 && v.sx != 4) || W <= 0 || H <= 0 || v.sy < (long)W * v.sx || v.sb < 0) return false;
-  return !(B > 1 && v.sb > 0 && v.sb < (long)H * v.sy);      // images that overlap
+// The pixel code q(v) = (int) rintf(fminf(fmaxf(v, 0), 1) * 255.0f): one fp32 multiply, round to nearest even; NaN -> 0.  The clamps are
+// written as comparisons so that a NaN takes the first branch's 0 whatever the min / max instructions make of it.  One function for every
+// pass: a frame against the key that commit made from it differs nowhere, NaN pixels included.
+__device__ __forceinline__ int pixel_q(float v) {
+  v = v > 0.f ? v : 0.f;
+  v = v < 1.f ? v : 1.f;
+  return (int)rintf(__fmul_rn(v, 255.0f));
 }
+__device__ __forceinline__ int pixel_q(unsigned char v) { return (int)v; }
 
-// fs_byte_frame_route: -1 refused, 1 the vector forms (sixteen pixels a lane of the tile and commit passes, four of the profile pass:
-// every 16-pixel piece of every row starts at a multiple of 16 bytes), 0 the one-pixel forms
-inline long hwc_route(const unsigned char* p, long sb, long sy, int sx, int W) {
-  if (p == nullptr || (sx != 3 && sx != 4) || W <= 0 || sy < (long)W * sx || sb < 0) return -1;
-  return (W % 16 == 0 && ((uintptr_t)p & 15) == 0 && sy % 16 == 0 && sb % 16 == 0) ? 1 : 0;
-}
-inline bool hwc_vec_ok(const HwcView& v, int W) { return hwc_route(v.p, v.sb, v.sy, v.sx, W) == 1; }
-
-#if defined(__HIPCC__)
 namespace {
 
 constexpr unsigned int hwc_sel(unsigned int b0, unsigned int b1, unsigned int b2, unsigned int b3) {
@@ -55,28 +53,121 @@ __device__ __forceinline__ void hwc_split4(unsigned int d0, unsigned int d1, uns
   b = hwc_perm(v1, v0, hwc_sel(0, 1, 4, 5));
 }
 
-// Sixteen pixels of a row from their 48 (SX = 3) or 64 (SX = 4) bytes, 16-byte aligned: three or four 16-byte loads, then v[c] =
-// the sixteen bytes of channel c in planar order.
-template <int SX>
-__device__ __forceinline__ void hwc_load16(const unsigned char* __restrict__ p, hwc_u32x4* v) {
-  const hwc_u32x4* q = reinterpret_cast<const hwc_u32x4*>(p);
-  unsigned int o[3][4];
-  if (SX == 3) {
-    const hwc_u32x4 a = q[0], b = q[1], c = q[2];
-    hwc_split3(a.x, a.y, a.z, o[0][0], o[1][0], o[2][0]);
-    hwc_split3(a.w, b.x, b.y, o[0][1], o[1][1], o[2][1]);
-    hwc_split3(b.z, b.w, c.x, o[0][2], o[1][2], o[2][2]);
-    hwc_split3(c.y, c.z, c.w, o[0][3], o[1][3], o[2][3]);
-  } else {
-    const hwc_u32x4 a = q[0], b = q[1], c = q[2], d = q[3];
-    hwc_split4(a.x, a.y, a.z, a.w, o[0][0], o[1][0], o[2][0]);
-    hwc_split4(b.x, b.y, b.z, b.w, o[0][1], o[1][1], o[2][1]);
-    hwc_split4(c.x, c.y, c.z, c.w, o[0][2], o[1][2], o[2][2]);
-    hwc_split4(d.x, d.y, d.z, d.w, o[0][3], o[1][3], o[2][3]);
-  }
-#pragma unroll
-  for (int ch = 0; ch < 3; ++ch) v[ch] = hwc_u32x4{o[ch][0], o[ch][1], o[ch][2], o[ch][3]};
+// Four codes from one aligned load, added to l: 16 bytes of fp32, 4 of bytes.
+__device__ __forceinline__ void code4(const float* p, int* l) {
+  const f32x4 v = *reinterpret_cast<const f32x4*>(p);
+  l[0] += pixel_q(v.x), l[1] += pixel_q(v.y), l[2] += pixel_q(v.z), l[3] += pixel_q(v.w);
+}
+__device__ __forceinline__ void code4(const unsigned char* p, int* l) {
+  const unsigned int k = *reinterpret_cast<const unsigned int*>(p);
+  l[0] += (int)(k & 255u), l[1] += (int)((k >> 8) & 255u), l[2] += (int)((k >> 16) & 255u), l[3] += (int)(k >> 24);
 }
 
+template <typename T>
+struct PlanarFrame {
+  static constexpr int lane = sizeof(T) == 4 ? 4 : 16;           // commit's vector form: four codes of a 16-byte load, or sixteen bytes
+  const T* p;
+  size_t plane;
+  int W;
+  __host__ __device__ PlanarFrame(const T* p_, int H, int W_) : p(p_), plane((size_t)H * W_), W(W_) {}
+
+  __device__ __forceinline__ const T* px(size_t b, int y, int x) const { return p + b * 3 * plane + (size_t)y * W + x; }
+  __device__ __forceinline__ const T* down(const T* a, int rows) const { return a + (size_t)rows * W; }
+  __device__ __forceinline__ const T* right(const T* a, int cols) const { return a + cols; }
+  __device__ __forceinline__ int code(const T* a, int c) const { return pixel_q(a[c * plane]); }
+  // the code of element e = (c, y, x) of viewer b's frame in the key's order, which is this frame's own: e alone is used
+  __device__ __forceinline__ int code_of(size_t b, size_t e, int, int, int) const { return pixel_q(p[b * 3 * plane + e]); }
+  __device__ __forceinline__ void luma4(const T* a, int* l) const {      // l[j] += the three codes of pixel j, j < 4
+#pragma unroll
+    for (int c = 0; c < 3; ++c) code4(a + c * plane, l);
+  }
+  __device__ __forceinline__ void load16(const T* a, u32x4* v) const {   // bytes: v[c] = sixteen pixels of channel c
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = *reinterpret_cast<const u32x4*>(a + c * plane);
+  }
+  __device__ __forceinline__ float tap(const T* a, int c) const { return __fdiv_rn((float)a[c * plane], 255.0f); }
+
+  explicit operator bool() const { return p != nullptr; }
+  bool ok(int, int, int) const { return true; }
+  // every lane-pixel piece of every row is one aligned load (the tile pass, commit)
+  bool wide(int W_) const { return W_ % lane == 0 && ((uintptr_t)p & 15) == 0; }
+  // commit copies a planar frame of bytes as one run: whole 16-byte pieces a viewer, wherever the rows end
+  bool wide_commit(int W_, size_t per) const { return sizeof(T) == 4 ? wide(W_) : per % 16 == 0 && ((uintptr_t)p & 15) == 0; }
+  // every four-pixel piece of every row is one aligned load (the profile pass)
+  bool quad(int W_) const { return W_ % 4 == 0 && ((uintptr_t)p & (4 * sizeof(T) - 1)) == 0; }
+};
+
+template <int SX>
+struct HwcFrame {
+  static constexpr int lane = 48;                                 // commit's vector form: sixteen pixels, sixteen bytes a channel
+  const unsigned char* p;
+  long sb, sy;
+  int sx;
+  __host__ __device__ HwcFrame(const unsigned char* p_, long sb_, long sy_, int sx_) : p(p_), sb(sb_), sy(sy_), sx(sx_) {}
+
+  __device__ __forceinline__ int step() const { return SX > 0 ? SX : sx; }
+  __device__ __forceinline__ const unsigned char* px(size_t b, int y, int x) const {
+    return p + b * (size_t)sb + (size_t)y * sy + (size_t)x * step();
+  }
+  __device__ __forceinline__ const unsigned char* down(const unsigned char* a, int rows) const { return a + (size_t)rows * sy; }
+  __device__ __forceinline__ const unsigned char* right(const unsigned char* a, int cols) const { return a + (size_t)cols * step(); }
+  __device__ __forceinline__ int code(const unsigned char* a, int c) const { return (int)a[c]; }
+  __device__ __forceinline__ int code_of(size_t b, size_t, int c, int y, int x) const { return (int)px(b, y, x)[c]; }     // (c, y, x) are used
+  // Four pixels are 12 bytes in three 4-byte loads (SX = 3) or one 16-byte load (SX = 4); a pixel's luma is the sum of its three bytes
+  // (v_sad_u8 against 0), the fourth byte of an RGBA pixel masked off.  Added to l, as the planar frames' are.
+  __device__ __forceinline__ void luma4(const unsigned char* a, int* l) const {
+    if (SX == 3) {
+      const unsigned int w0 = *reinterpret_cast<const unsigned int*>(a), w1 = *reinterpret_cast<const unsigned int*>(a + 4),
+                         w2 = *reinterpret_cast<const unsigned int*>(a + 8);
+      l[0] += (int)__builtin_amdgcn_sad_u8(w0 & 0x00ffffffu, 0u, 0u);
+      l[1] += (int)__builtin_amdgcn_sad_u8(w0 >> 24, 0u, __builtin_amdgcn_sad_u8(w1 & 0x0000ffffu, 0u, 0u));
+      l[2] += (int)__builtin_amdgcn_sad_u8(w1 >> 16, 0u, __builtin_amdgcn_sad_u8(w2 & 0x000000ffu, 0u, 0u));
+      l[3] += (int)__builtin_amdgcn_sad_u8(w2 >> 8, 0u, 0u);
+    } else {
+      const u32x4 v = *reinterpret_cast<const u32x4*>(a);
+      l[0] += (int)__builtin_amdgcn_sad_u8(v.x & 0x00ffffffu, 0u, 0u);
+      l[1] += (int)__builtin_amdgcn_sad_u8(v.y & 0x00ffffffu, 0u, 0u);
+      l[2] += (int)__builtin_amdgcn_sad_u8(v.z & 0x00ffffffu, 0u, 0u);
+      l[3] += (int)__builtin_amdgcn_sad_u8(v.w & 0x00ffffffu, 0u, 0u);
+    }
+  }
+  // Sixteen pixels of a row from their 48 (SX = 3) or 64 (SX = 4) bytes, 16-byte aligned: three or four 16-byte loads, then v[c] = the
+  // sixteen bytes of channel c in planar order.
+  __device__ __forceinline__ void load16(const unsigned char* __restrict__ a, u32x4* v) const {
+    const u32x4* q = reinterpret_cast<const u32x4*>(a);
+    unsigned int o[3][4];
+    if (SX == 3) {
+      const u32x4 a0 = q[0], a1 = q[1], a2 = q[2];
+      hwc_split3(a0.x, a0.y, a0.z, o[0][0], o[1][0], o[2][0]);
+      hwc_split3(a0.w, a1.x, a1.y, o[0][1], o[1][1], o[2][1]);
+      hwc_split3(a1.z, a1.w, a2.x, o[0][2], o[1][2], o[2][2]);
+      hwc_split3(a2.y, a2.z, a2.w, o[0][3], o[1][3], o[2][3]);
+    } else {
+      const u32x4 a0 = q[0], a1 = q[1], a2 = q[2], a3 = q[3];
+      hwc_split4(a0.x, a0.y, a0.z, a0.w, o[0][0], o[1][0], o[2][0]);
+      hwc_split4(a1.x, a1.y, a1.z, a1.w, o[0][1], o[1][1], o[2][1]);
+      hwc_split4(a2.x, a2.y, a2.z, a2.w, o[0][2], o[1][2], o[2][2]);
+      hwc_split4(a3.x, a3.y, a3.z, a3.w, o[0][3], o[1][3], o[2][3]);
+    }
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) v[ch] = u32x4{o[ch][0], o[ch][1], o[ch][2], o[ch][3]};
+  }
+  __device__ __forceinline__ float tap(const unsigned char* a, int c) const { return __fdiv_rn((float)a[c], 255.0f); }
+
+  explicit operator bool() const { return p != nullptr; }
+  // a row of W pixels can be read: the pointer, the pixel step, the pitch and the image step
+  bool row_ok(int W) const { return p != nullptr && (sx == 3 || sx == 4) && W > 0 && sy >= (long)W * sx && sb >= 0; }
+  // what every fs_*_hwc entry point asks of the description beyond its twin's conditions: rows, and images that do not overlap
+  bool ok(int B, int H, int W) const { return row_ok(W) && H > 0 && !(B > 1 && sb > 0 && sb < (long)H * sy); }
+  // fs_byte_frame_route: -1 no readable row, 1 the vector forms (sixteen pixels a lane of the tile and commit passes, four of the profile
+  // pass: every 16-pixel piece of every row starts at a multiple of 16 bytes), 0 the one-pixel forms
+  long route(int W) const {
+    if (!row_ok(W)) return -1;
+    return (W % 16 == 0 && ((uintptr_t)p & 15) == 0 && sy % 16 == 0 && sb % 16 == 0) ? 1 : 0;
+  }
+  bool wide(int W) const { return route(W) == 1; }
+  bool wide_commit(int W, size_t) const { return wide(W); }
+  bool quad(int W) const { return wide(W); }
+};
+
 }  // namespace
-#endif

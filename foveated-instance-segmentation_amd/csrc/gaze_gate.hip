@@ -6,16 +6,16 @@
 //            the decision table.  Pure: it writes the gate record only.
 //   commit   for the viewers that ran the network: the frame becomes the key frame, the gaze the key gaze, the new record's rows move to
 //            the viewer's slots; every viewer's previous gaze and age advance.
-// The pixel code q and the gaze in 1/16-pixel units are one function each, used by every pass that needs them: a frame against the
-// key that commit made from it differs nowhere, NaN pixels included.
-// A frame may also come as bytes (pixel value byte / 255, whose code q is the byte): fs_gate_tiles_u8 and fs_gate_commit_u8 are the tile
-// pass on 6 bytes a pixel and the key copy; decide, and commit's state and row passes, are the same kernels for both.
-// A frame of interleaved bytes (frame_view.h) is read where it lies: fs_gate_tiles_hwc and fs_gate_commit_hwc de-interleave sixteen pixels a
-// lane in registers (v_perm_b32), so that v_sad_u8 meets matching bytes and the key stays planar; decide and the shared passes do not change.
+// The pixel code q (frame_view.h) and the gaze in 1/16-pixel units are one function each, used by every pass that needs them: a frame
+// against the key that commit made from it differs nowhere, NaN pixels included.
+// A frame comes in three layouts -- planar fp32, planar bytes (pixel value byte / 255, whose code q is the byte; 6 bytes a pixel read
+// instead of 15), interleaved bytes read where they lie -- and every pass that reads one is written once over the frame's reader
+// (frame_view.h): the one-pixel tile pass for all three, the 16-pixel band for the two byte layouts (an interleaved frame's sixteen pixels
+// are de-interleaved in registers, v_perm_b32, so that v_sad_u8 meets matching bytes and the key stays planar), commit's frame pass for
+// the planar two.  The fp32 four-pixel band has a cut of its own.  A kernel a layout remains where the layouts' arguments differ; it
+// builds its reader and calls the pass.  decide, and commit's state and row passes, read no frame.
 #include "common.h"
 #include "frame_view.h"
-
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
@@ -23,14 +23,6 @@ constexpr long GATE_INT_LIMIT = 2147483647L;           // pixel and tile indices
 constexpr long GATE_WGS_MAX = 16777215L;               // workgroups of 256 threads: fewer than 2^32 work-items a launch
 constexpr int GATE_MAX_SIDE = 1 << 26;                 // decide / commit: the gaze in 1/16 pixels stays below 2^30, its squared distances below 2^62
 constexpr int GATE_THREADS = 256;
-
-// q(v) = (int) rintf(fminf(fmaxf(v, 0), 1) * 255.0f): one fp32 multiply, round to nearest even; NaN -> 0.  The clamps are written as
-// comparisons so that a NaN takes the first branch's 0 whatever the min / max instructions make of it.
-__device__ __forceinline__ int gate_q(float v) {
-  v = v > 0.f ? v : 0.f;
-  v = v < 1.f ? v : 1.f;
-  return (int)rintf(__fmul_rn(v, 255.0f));
-}
 
 // the gaze coordinate in 1/16-pixel units: clamp(rint((double)f * ((side - 1) * 16)), 0, (side - 1) * 16), NaN -> 0
 __device__ __forceinline__ long long gate_gaze(float f, int side) {
@@ -46,19 +38,8 @@ __device__ __forceinline__ long long gate_d2(long long ay, long long ax, long lo
   return dy * dy + dx * dx;
 }
 
-__device__ __forceinline__ int gate_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ long long gate_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ int gate_absdiff(float v, unsigned int k) {
-  const int d = gate_q(v) - (int)k;
+  const int d = pixel_q(v) - (int)k;
   return d < 0 ? -d : d;
 }
 
@@ -107,10 +88,11 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_tiles_band_kernel(const flo
     sad[(b * th + ty) * tw + tx] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// The one-pixel form, for any width and alignment: one workgroup per (viewer, tile row, tile column), a lane takes a pixel of the tile
-// and reads its three channels.
-__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_kernel(const float* __restrict__ img, const unsigned char* __restrict__ key,
-                                                                  int* __restrict__ sad, int H, int W, int T, int th, int tw) {
+// The one-pixel form, for any layout, width and alignment: one workgroup per (viewer, tile row, tile column), a lane takes a pixel of the
+// tile and reads its three channels through the frame's reader.
+template <class F>
+__device__ __forceinline__ void gate_tiles_px(const F& f, const unsigned char* __restrict__ key, int* __restrict__ sad, int H, int W, int T,
+                                              int th, int tw) {
   __shared__ int red[GATE_THREADS / 64];
   const unsigned int blk = blockIdx.x;
   const int tx = (int)(blk % (unsigned)tw);
@@ -120,21 +102,20 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_tiles_kernel(const float* _
   const int rows = min(T, H - y0), cols = min(T, W - x0);
   const size_t plane = (size_t)H * W;
   const size_t base = b * 3 * plane + (size_t)y0 * W + x0;
+  const auto fbase = f.px(b, y0, x0);
   int s = 0;
   const int per = rows * cols;
   for (int j = threadIdx.x; j < per; j += GATE_THREADS) {
     const int r = j / cols, x = j - r * cols;
     const size_t at = base + (size_t)r * W + x;
-    float v[3];
-    unsigned int k[3];
+    const auto a = f.right(f.down(fbase, r), x);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      v[c] = img[at + c * plane];
-      k[c] = key[at + c * plane];
+      const int d = f.code(a, c) - (int)key[at + c * plane];
+      s += d < 0 ? -d : d;
     }
-    s += gate_absdiff(v[0], k[0]) + gate_absdiff(v[1], k[1]) + gate_absdiff(v[2], k[2]);
   }
-  s = gate_wave_sum(s);
+  s = wave_sum_i(s);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) sad[blk] = red[0] + red[1] + red[2] + red[3];
@@ -142,15 +123,16 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_tiles_kernel(const float* _
 
 constexpr int GATE_SEG_U8 = 1024;                      // the byte form: the most columns a workgroup covers, sixteen a lane
 
-// The byte form of the tile pass (fs_gate_tiles_u8): the frame is bytes as the key is, the pixel code is the byte itself, 6 bytes read
-// per pixel.  The 16-pixel form (W % 16 == 0, img and key 16-byte aligned) keeps the band cut above: one workgroup per (viewer, tile
-// row, segment), a lane takes sixteen pixels of a row -- one 16-byte load of img and one of key per channel, four v_sad_u8 each -- and
-// a lane's sixteen pixels are one tile's for T >= 16, two tiles' for T = 8 (s0 the first eight, s1 the last).  A row takes 1 << lg lanes, the least power
-// of two that covers min(W, 1024) columns and is no less than a tile's lanes; the 64 >> lg rows of a wave are neighbours, the four
-// waves take the row groups in turn.  A tile's lanes meet by shuffles inside a row, then across the rows of the wave, the waves through LDS.
-__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_u8_band_kernel(const unsigned char* __restrict__ img,
-                                                                          const unsigned char* __restrict__ key, int* __restrict__ sad, int H,
-                                                                          int W, int T, int th, int tw, int nseg, int lg) {
+// The 16-pixel form of the tile pass on a frame of bytes, planar or interleaved (the frame's vector form, key 16-byte aligned): the
+// frame is bytes as the key is, the pixel code is the byte itself.  It keeps the band cut above: one workgroup per (viewer, tile row,
+// segment), a lane takes sixteen pixels of a row -- the reader's sixteen bytes a channel in planar order and one 16-byte load of key per
+// channel, four v_sad_u8 each, so that v_sad_u8 meets matching bytes -- and a lane's sixteen pixels are one tile's for T >= 16, two
+// tiles' for T = 8 (s0 the first eight, s1 the last).  A row takes 1 << lg lanes, the least power of two that covers min(W, 1024)
+// columns and is no less than a tile's lanes; the 64 >> lg rows of a wave are neighbours, the four waves take the row groups in turn.  A
+// tile's lanes meet by shuffles inside a row, then across the rows of the wave, the waves through LDS.
+template <class F>
+__device__ __forceinline__ void gate_tiles_band(const F& f, const unsigned char* __restrict__ key, int* __restrict__ sad, int H, int W, int T,
+                                                int th, int tw, int nseg, int lg) {
   __shared__ int red[GATE_THREADS / 64][GATE_SEG_U8 / 8];
   const unsigned int blk = blockIdx.x;
   const int seg = (int)(blk % (unsigned)nseg);
@@ -165,105 +147,12 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_tiles_u8_band_kernel(const 
   unsigned int s0 = 0, s1 = 0;
   if (x < W) {
     const size_t base = b * 3 * plane + (size_t)y0 * W + x;
+    const unsigned char* fbase = f.px(b, y0, x);
 #pragma unroll 2
     for (int r = wave * sub + rs; r < rows; r += (GATE_THREADS / 64) * sub) {
       const size_t at = base + (size_t)r * W;
       u32x4 v[3], k[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        v[c] = *reinterpret_cast<const u32x4*>(img + at + c * plane);
-        k[c] = *reinterpret_cast<const u32x4*>(key + at + c * plane);
-      }
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        s0 = __builtin_amdgcn_sad_u8(v[c].x, k[c].x, s0);
-        s0 = __builtin_amdgcn_sad_u8(v[c].y, k[c].y, s0);
-        s1 = __builtin_amdgcn_sad_u8(v[c].z, k[c].z, s1);
-        s1 = __builtin_amdgcn_sad_u8(v[c].w, k[c].w, s1);
-      }
-    }
-  }
-  int a0 = (int)s0, a1 = (int)s1;
-  if (T >= 16) {
-    a0 += a1;
-    for (int o = (T >> 4) >> 1; o > 0; o >>= 1) a0 += __shfl_xor(a0, o, 64);      // the T / 16 lanes of a tile
-  }
-  for (int o = lpr; o < 64; o <<= 1) {                  // the rows of the wave
-    a0 += __shfl_xor(a0, o, 64);
-    a1 += __shfl_xor(a1, o, 64);
-  }
-  if (rs == 0) {
-    if (T == 8) {
-      red[wave][2 * cl] = a0;
-      red[wave][2 * cl + 1] = a1;
-    } else if ((cl & ((T >> 4) - 1)) == 0) {
-      red[wave][cl / (T >> 4)] = a0;
-    }
-  }
-  __syncthreads();
-  const int per_seg = (lpr * 16) / T;                   // at most 128 entries a segment, one a lane
-  const int tx = seg * per_seg + (int)threadIdx.x;
-  if ((int)threadIdx.x < per_seg && tx < tw)
-    sad[(b * th + ty) * tw + tx] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-}
-
-// The one-pixel byte form, for any width and alignment: gate_tiles_kernel's cut, a workgroup a tile.
-__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_u8_kernel(const unsigned char* __restrict__ img, const unsigned char* __restrict__ key,
-                                                                     int* __restrict__ sad, int H, int W, int T, int th, int tw) {
-  __shared__ int red[GATE_THREADS / 64];
-  const unsigned int blk = blockIdx.x;
-  const int tx = (int)(blk % (unsigned)tw);
-  const int ty = (int)((blk / (unsigned)tw) % (unsigned)th);
-  const size_t b = blk / (unsigned)tw / (unsigned)th;
-  const int y0 = ty * T, x0 = tx * T;
-  const int rows = min(T, H - y0), cols = min(T, W - x0);
-  const size_t plane = (size_t)H * W;
-  const size_t base = b * 3 * plane + (size_t)y0 * W + x0;
-  int s = 0;
-  const int per = rows * cols;
-  for (int j = threadIdx.x; j < per; j += GATE_THREADS) {
-    const int r = j / cols, x = j - r * cols;
-    const size_t at = base + (size_t)r * W + x;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int d = (int)img[at + c * plane] - (int)key[at + c * plane];
-      s += d < 0 ? -d : d;
-    }
-  }
-  s = gate_wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) sad[blk] = red[0] + red[1] + red[2] + red[3];
-}
-
-// The tile pass on an interleaved frame (fs_gate_tiles_hwc), vector form (fs_byte_frame_route = 1, key 16-byte aligned):
-// gate_tiles_u8_band_kernel's cut and sums, lane for lane.  A lane owns the 48 (SX = 3) or 64 (SX = 4) bytes of its sixteen pixels --
-// three or four 16-byte loads, whose lines the wave's neighbours finish -- and splits them into a channel a register quad; the key takes
-// one 16-byte load a channel as there.  The fourth byte of an RGBA pixel is selected by no perm and reaches no sum.
-template <int SX>
-__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_hwc_band_kernel(const unsigned char* __restrict__ img, long sb, long sy,
-                                                                           const unsigned char* __restrict__ key, int* __restrict__ sad, int H,
-                                                                           int W, int T, int th, int tw, int nseg, int lg) {
-  __shared__ int red[GATE_THREADS / 64][GATE_SEG_U8 / 8];
-  const unsigned int blk = blockIdx.x;
-  const int seg = (int)(blk % (unsigned)nseg);
-  const int ty = (int)((blk / (unsigned)nseg) % (unsigned)th);
-  const size_t b = blk / (unsigned)nseg / (unsigned)th;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int lpr = 1 << lg, sub = 64 >> lg;              // lanes a row, rows a wave
-  const int cl = lane & (lpr - 1), rs = lane >> lg;
-  const int y0 = ty * T, rows = min(T, H - y0);
-  const int x = (seg << (lg + 4)) + cl * 16;
-  const size_t plane = (size_t)H * W;
-  unsigned int s0 = 0, s1 = 0;
-  if (x < W) {
-    const size_t base = b * 3 * plane + (size_t)y0 * W + x;
-    const unsigned char* fbase = img + (size_t)b * sb + (size_t)y0 * sy + (size_t)x * SX;
-#pragma unroll 2
-    for (int r = wave * sub + rs; r < rows; r += (GATE_THREADS / 64) * sub) {
-      const size_t at = base + (size_t)r * W;
-      u32x4 v[3], k[3];
-      hwc_load16<SX>(fbase + (size_t)r * sy, v);
+      f.load16(f.down(fbase, r), v);
 #pragma unroll
       for (int c = 0; c < 3; ++c) k[c] = *reinterpret_cast<const u32x4*>(key + at + c * plane);
 #pragma unroll
@@ -299,36 +188,31 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_tiles_hwc_band_kernel(const
     sad[(b * th + ty) * tw + tx] = red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
 }
 
-// The one-pixel form on an interleaved frame, for any width, pitch and alignment: gate_tiles_u8_kernel's cut, a workgroup a tile.
+// The kernels of the two forms: each layout keeps the parameters of its entry point, raw pointers and scalars, and builds its reader from
+// them (profiles/r33/README.md: a reader passed by value changes the device code).
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_kernel(const float* __restrict__ img, const unsigned char* __restrict__ key,
+                                                                  int* __restrict__ sad, int H, int W, int T, int th, int tw) {
+  gate_tiles_px(PlanarFrame<float>(img, H, W), key, sad, H, W, T, th, tw);
+}
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_u8_kernel(const unsigned char* __restrict__ img, const unsigned char* __restrict__ key,
+                                                                     int* __restrict__ sad, int H, int W, int T, int th, int tw) {
+  gate_tiles_px(PlanarFrame<unsigned char>(img, H, W), key, sad, H, W, T, th, tw);
+}
 __global__ __launch_bounds__(GATE_THREADS) void gate_tiles_hwc_kernel(const unsigned char* __restrict__ img, long sb, long sy, int sx,
                                                                       const unsigned char* __restrict__ key, int* __restrict__ sad, int H, int W,
                                                                       int T, int th, int tw) {
-  __shared__ int red[GATE_THREADS / 64];
-  const unsigned int blk = blockIdx.x;
-  const int tx = (int)(blk % (unsigned)tw);
-  const int ty = (int)((blk / (unsigned)tw) % (unsigned)th);
-  const size_t b = blk / (unsigned)tw / (unsigned)th;
-  const int y0 = ty * T, x0 = tx * T;
-  const int rows = min(T, H - y0), cols = min(T, W - x0);
-  const size_t plane = (size_t)H * W;
-  const size_t base = b * 3 * plane + (size_t)y0 * W + x0;
-  const unsigned char* fbase = img + (size_t)b * sb + (size_t)y0 * sy + (size_t)x0 * sx;
-  int s = 0;
-  const int per = rows * cols;
-  for (int j = threadIdx.x; j < per; j += GATE_THREADS) {
-    const int r = j / cols, x = j - r * cols;
-    const size_t at = base + (size_t)r * W + x;
-    const unsigned char* f = fbase + (size_t)r * sy + (size_t)x * sx;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int d = (int)f[c] - (int)key[at + c * plane];
-      s += d < 0 ? -d : d;
-    }
-  }
-  s = gate_wave_sum(s);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  if (threadIdx.x == 0) sad[blk] = red[0] + red[1] + red[2] + red[3];
+  gate_tiles_px(HwcFrame<0>(img, sb, sy, sx), key, sad, H, W, T, th, tw);
+}
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_u8_band_kernel(const unsigned char* __restrict__ img,
+                                                                          const unsigned char* __restrict__ key, int* __restrict__ sad, int H,
+                                                                          int W, int T, int th, int tw, int nseg, int lg) {
+  gate_tiles_band(PlanarFrame<unsigned char>(img, H, W), key, sad, H, W, T, th, tw, nseg, lg);
+}
+template <int SX>
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_hwc_band_kernel(const unsigned char* __restrict__ img, long sb, long sy,
+                                                                           const unsigned char* __restrict__ key, int* __restrict__ sad, int H,
+                                                                           int W, int T, int th, int tw, int nseg, int lg) {
+  gate_tiles_band(HwcFrame<SX>(img, sb, sy, SX), key, sad, H, W, T, th, tw, nseg, lg);
 }
 
 struct GateRule {
@@ -374,9 +258,9 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_decide_kernel(const int* __
     nr += (changed && roi) ? 1 : 0;
     tot += s;
   }
-  nc = gate_wave_sum(nc);
-  nr = gate_wave_sum(nr);
-  tot = gate_wave_sum(tot);
+  nc = wave_sum_i(nc);
+  nr = wave_sum_i(nr);
+  tot = wave_sum_ll(tot);
   if ((threadIdx.x & 63) == 0) {
     red_c[threadIdx.x >> 6] = nc;
     red_r[threadIdx.x >> 6] = nr;
@@ -440,39 +324,27 @@ __global__ void gate_commit_state_kernel(const int* __restrict__ idx, int n, lon
   g[4] = gx;
 }
 
-// key[idx[j]] <- q(img[idx[j]]): bpi workgroups a viewer; VEC as in the tile pass, four pixels a lane and one 4-byte store
-template <bool VEC>
-__global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_kernel(const float* __restrict__ img, const int* __restrict__ idx,
+// key[idx[j]] <- the codes of img[idx[j]], a planar frame: it lies in the key's order, so a viewer is one run of per = 3 * H * W elements
+// and bpi workgroups take it.  VEC (the reader's wide_commit, key aligned to the store): a lane takes four floats and stores their codes
+// in 4 bytes, or copies sixteen bytes, whose codes they are; one element a lane otherwise.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_kernel(const T* __restrict__ img, const int* __restrict__ idx,
                                                                          unsigned char* __restrict__ key, int B, size_t per, unsigned int bpi) {
   const unsigned int j = blockIdx.x / bpi;
   const int b = idx[j];
   if (b < 0 || b >= B) return;                         // an index outside the batch writes nothing
-  const size_t e = ((size_t)(blockIdx.x - j * bpi) * GATE_THREADS + threadIdx.x) * (VEC ? 4 : 1);
+  const size_t e = ((size_t)(blockIdx.x - j * bpi) * GATE_THREADS + threadIdx.x) * (VEC ? PlanarFrame<T>::lane : 1);
   if (e >= per) return;
   const size_t at = (size_t)b * per + e;
-  if (VEC) {
-    const f32x4 v = *reinterpret_cast<const f32x4*>(img + at);
-    const unsigned int k = (unsigned int)gate_q(v.x) | ((unsigned int)gate_q(v.y) << 8) | ((unsigned int)gate_q(v.z) << 16) |
-                           ((unsigned int)gate_q(v.w) << 24);
-    *reinterpret_cast<unsigned int*>(key + at) = k;
+  if (!VEC) {
+    key[at] = (unsigned char)pixel_q(img[at]);
+  } else if (sizeof(T) == 4) {
+    int q[4] = {0, 0, 0, 0};
+    code4(img + at, q);
+    *reinterpret_cast<unsigned int*>(key + at) = (unsigned int)q[0] | ((unsigned int)q[1] << 8) | ((unsigned int)q[2] << 16) | ((unsigned int)q[3] << 24);
   } else {
-    key[at] = (unsigned char)gate_q(img[at]);
+    *reinterpret_cast<u32x4*>(key + at) = *reinterpret_cast<const u32x4*>(img + at);
   }
-}
-
-// key[idx[j]] <- img[idx[j]] for a frame of bytes (fs_gate_commit_u8): the pixel code is the byte, so this is a copy.  VEC (the viewer's
-// 3 * H * W bytes a multiple of 16, img and key 16-byte aligned): sixteen bytes a lane; one byte a lane otherwise.
-template <bool VEC>
-__global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_u8_kernel(const unsigned char* __restrict__ img, const int* __restrict__ idx,
-                                                                            unsigned char* __restrict__ key, int B, size_t per, unsigned int bpi) {
-  const unsigned int j = blockIdx.x / bpi;
-  const int b = idx[j];
-  if (b < 0 || b >= B) return;                         // an index outside the batch writes nothing
-  const size_t e = ((size_t)(blockIdx.x - j * bpi) * GATE_THREADS + threadIdx.x) * (VEC ? 16 : 1);
-  if (e >= per) return;
-  const size_t at = (size_t)b * per + e;
-  if (VEC) *reinterpret_cast<u32x4*>(key + at) = *reinterpret_cast<const u32x4*>(img + at);
-  else key[at] = img[at];
 }
 
 // key[idx[j]] <- the de-interleaved frame of viewer idx[j] (fs_gate_commit_hwc); the key stays planar.  SX > 0, the vector form (the tile
@@ -487,19 +359,20 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_hwc_kernel(con
   if (b < 0 || b >= B) return;                         // an index outside the batch writes nothing
   const size_t e = (size_t)(blockIdx.x - j * bpi) * GATE_THREADS + threadIdx.x;
   if (e >= per) return;
+  const HwcFrame<SX> f(img, sb, sy, sx);
   const size_t plane = (size_t)H * W;
   if (SX > 0) {
     const int w16 = W >> 4;
     const int y = (int)(e / (unsigned)w16), x = (int)(e - (size_t)y * w16) * 16;
     u32x4 v[3];
-    hwc_load16<(SX > 0 ? SX : 3)>(img + (size_t)b * sb + (size_t)y * sy + (size_t)x * SX, v);
+    f.load16(f.px(b, y, x), v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) *reinterpret_cast<u32x4*>(key + ((size_t)b * 3 + c) * plane + (size_t)y * W + x) = v[c];
   } else {
     const int c = (int)(e / plane);
     const size_t rem = e - c * plane;
     const int y = (int)(rem / (unsigned)W), x = (int)(rem - (size_t)y * W);
-    key[(size_t)b * 3 * plane + e] = img[(size_t)b * sb + (size_t)y * sy + (size_t)x * sx + c];
+    key[(size_t)b * 3 * plane + e] = (unsigned char)f.code(f.px(b, y, x), c);
   }
 }
 
@@ -530,71 +403,74 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_commit_rows_kernel(const in
 }
 
 bool gate_tile_ok(int T) { return T == 8 || T == 16 || T == 32 || T == 64; }
-bool gate_vec_ok(const float* img, const unsigned char* key, int W) {
-  return W % 4 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)key & 3) == 0;
+// a frame's vector form also asks the key to be aligned to what a lane takes of it: 4 bytes beside four floats, 16 beside sixteen bytes
+template <class F>
+bool gate_key_ok(const unsigned char* key) { return ((uintptr_t)key & (F::lane == 4 ? 3 : 15)) == 0; }
+
+// the tile pass's launch on a frame of bytes, by its layout; band = the 16-pixel form
+void gate_tiles_launch(const PlanarFrame<unsigned char>& f, bool band, dim3 grid, hipStream_t stream, const unsigned char* key, int* sad, int H, int W,
+                       int T, int th, int tw, int nseg, int lg) {
+  if (band) hipLaunchKernelGGL(gate_tiles_u8_band_kernel, grid, dim3(GATE_THREADS), 0, stream, f.p, key, sad, H, W, T, th, tw, nseg, lg);
+  else hipLaunchKernelGGL(gate_tiles_u8_kernel, grid, dim3(GATE_THREADS), 0, stream, f.p, key, sad, H, W, T, th, tw);
+}
+void gate_tiles_launch(const HwcFrame<0>& f, bool band, dim3 grid, hipStream_t stream, const unsigned char* key, int* sad, int H, int W, int T, int th,
+                       int tw, int nseg, int lg) {
+  const dim3 block(GATE_THREADS);
+  if (band && f.sx == 3) hipLaunchKernelGGL(gate_tiles_hwc_band_kernel<3>, grid, block, 0, stream, f.p, f.sb, f.sy, key, sad, H, W, T, th, tw, nseg, lg);
+  else if (band) hipLaunchKernelGGL(gate_tiles_hwc_band_kernel<4>, grid, block, 0, stream, f.p, f.sb, f.sy, key, sad, H, W, T, th, tw, nseg, lg);
+  else hipLaunchKernelGGL(gate_tiles_hwc_kernel, grid, block, 0, stream, f.p, f.sb, f.sy, f.sx, key, sad, H, W, T, th, tw);
 }
 
-bool gate_vec_u8_ok(const unsigned char* img, const unsigned char* key, int W) {
-  return W % 16 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)key & 15) == 0;
+// fs_gate_tiles_u8 / fs_gate_tiles_hwc: the checks, and the lanes a row and the segments of the 16-pixel form, chosen here alone
+template <class F>
+int gate_tiles_bytes(const F& f, const unsigned char* key, int* sad, int B, int H, int W, int T, hipStream_t stream) {
+  FS_REQUIRE(f && key && sad && B > 0 && H > 0 && W > 0 && gate_tile_ok(T) && (long)H * W < GATE_INT_LIMIT && f.ok(B, H, W));
+  const int th = cdiv(H, T), tw = cdiv(W, T);
+  FS_REQUIRE((long)B * th * tw <= GATE_WGS_MAX);
+  const bool band = f.wide(W) && gate_key_ok<F>(key);
+  int lg = 0;                                           // lanes a row: covers min(W, 1024) columns, and a tile's T / 16 lanes
+  while (lg < 6 && (16 << lg) < W) ++lg;
+  while ((16 << lg) < T) ++lg;
+  const int nseg = cdiv(W, 16 << lg);
+  gate_tiles_launch(f, band, dim3((unsigned)((long)B * th * (band ? nseg : tw))), stream, key, sad, H, W, T, th, tw, nseg, lg);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
 }
 
-// the frame pass of commit by the frame's type: lanes take 4 floats / 16 bytes where vec
-bool gate_frame_vec(const float* img, const unsigned char* key, int W, size_t) { return gate_vec_ok(img, key, W); }
-bool gate_frame_vec(const unsigned char* img, const unsigned char* key, int, size_t per) {
-  return per % 16 == 0 && ((uintptr_t)img & 15) == 0 && ((uintptr_t)key & 15) == 0;
-}
-int gate_frame_lane(const float*) { return 4; }
-int gate_frame_lane(const unsigned char*) { return 16; }
-void gate_commit_frame(const float* img, const int* idx, unsigned char* key, int B, size_t per, bool vec, long wgs, long bpi, hipStream_t stream) {
-  if (vec)
-    hipLaunchKernelGGL(gate_commit_frame_kernel<true>, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
-  else
-    hipLaunchKernelGGL(gate_commit_frame_kernel<false>, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
-}
-void gate_commit_frame(const unsigned char* img, const int* idx, unsigned char* key, int B, size_t per, bool vec, long wgs, long bpi,
+// the frame pass of commit by the frame's layout: a planar viewer is a run of per elements, an interleaved one H * W / 16 pieces (the
+// vector form) or per bytes
+template <typename T>
+void gate_commit_frame(const PlanarFrame<T>& f, const int* idx, unsigned char* key, int B, int, int, size_t per, bool vec, long wgs, long bpi,
                        hipStream_t stream) {
-  if (vec)
-    hipLaunchKernelGGL(gate_commit_frame_u8_kernel<true>, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
-  else
-    hipLaunchKernelGGL(gate_commit_frame_u8_kernel<false>, dim3((unsigned)wgs), dim3(GATE_THREADS), 0, stream, img, idx, key, B, per, (unsigned)bpi);
+  const dim3 grid((unsigned)wgs), block(GATE_THREADS);
+  if (vec) hipLaunchKernelGGL((gate_commit_frame_kernel<T, true>), grid, block, 0, stream, f.p, idx, key, B, per, (unsigned)bpi);
+  else hipLaunchKernelGGL((gate_commit_frame_kernel<T, false>), grid, block, 0, stream, f.p, idx, key, B, per, (unsigned)bpi);
 }
-
-// an interleaved frame: the vector form takes H * W / 16 pieces a viewer, the one-byte form 3 * H * W bytes
-bool gate_frame_vec(const HwcView& img, const unsigned char* key, int W, size_t) { return hwc_vec_ok(img, W) && ((uintptr_t)key & 15) == 0; }
-int gate_frame_lane(const HwcView&) { return 48; }
-void gate_commit_frame(const HwcView& img, const int* idx, unsigned char* key, int B, size_t per, bool vec, long wgs, long bpi, hipStream_t stream,
-                       int H, int W) {
+void gate_commit_frame(const HwcFrame<0>& f, const int* idx, unsigned char* key, int B, int H, int W, size_t per, bool vec, long wgs, long bpi,
+                       hipStream_t stream) {
   const dim3 grid((unsigned)wgs), block(GATE_THREADS);
   const size_t units = vec ? per / 48 : per;
-  if (vec && img.sx == 3)
-    hipLaunchKernelGGL(gate_commit_frame_hwc_kernel<3>, grid, block, 0, stream, img.p, img.sb, img.sy, img.sx, idx, key, B, H, W, units, (unsigned)bpi);
+  if (vec && f.sx == 3)
+    hipLaunchKernelGGL(gate_commit_frame_hwc_kernel<3>, grid, block, 0, stream, f.p, f.sb, f.sy, f.sx, idx, key, B, H, W, units, (unsigned)bpi);
   else if (vec)
-    hipLaunchKernelGGL(gate_commit_frame_hwc_kernel<4>, grid, block, 0, stream, img.p, img.sb, img.sy, img.sx, idx, key, B, H, W, units, (unsigned)bpi);
+    hipLaunchKernelGGL(gate_commit_frame_hwc_kernel<4>, grid, block, 0, stream, f.p, f.sb, f.sy, f.sx, idx, key, B, H, W, units, (unsigned)bpi);
   else
-    hipLaunchKernelGGL(gate_commit_frame_hwc_kernel<0>, grid, block, 0, stream, img.p, img.sb, img.sy, img.sx, idx, key, B, H, W, units, (unsigned)bpi);
+    hipLaunchKernelGGL(gate_commit_frame_hwc_kernel<0>, grid, block, 0, stream, f.p, f.sb, f.sy, f.sx, idx, key, B, H, W, units, (unsigned)bpi);
 }
-template <typename T>
-void gate_commit_frame(const T* img, const int* idx, unsigned char* key, int B, size_t per, bool vec, long wgs, long bpi, hipStream_t stream, int,
-                       int) {
-  gate_commit_frame(img, idx, key, B, per, vec, wgs, bpi, stream);
-}
-inline bool gate_frame_ok(const float*, int, int, int) { return true; }
-inline bool gate_frame_ok(const unsigned char*, int, int, int) { return true; }
-inline bool gate_frame_ok(const HwcView& v, int B, int H, int W) { return hwc_view_ok(v, B, H, W); }
 
-// fs_gate_commit / fs_gate_commit_u8 / fs_gate_commit_hwc: the checks, the state pass, the frame pass of the frame's type, the row pass
-template <typename F>
-int gate_commit_run(F img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus, const long long* src_cat,
+// fs_gate_commit / fs_gate_commit_u8 / fs_gate_commit_hwc: the checks, the state pass, the frame pass of the frame's layout, the row pass
+template <class F>
+int gate_commit_run(const F& img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus, const long long* src_cat,
                     const long long* src_stats, const int* src_counts, const unsigned int* src_bits, const float* src_conf, long long* dst_cat,
                     long long* dst_stats, int* dst_counts, unsigned int* dst_bits, float* dst_conf, int B, int H, int W, int cap,
                     hipStream_t stream) {
   FS_REQUIRE(img && key && gstate && focus && B > 0 && H > 0 && W > 0 && (long)H * W < GATE_INT_LIMIT && n >= 0 && n <= B);
-  FS_REQUIRE(H <= GATE_MAX_SIDE && W <= GATE_MAX_SIDE && cap >= 1 && gate_frame_ok(img, B, H, W));
+  FS_REQUIRE(H <= GATE_MAX_SIDE && W <= GATE_MAX_SIDE && cap >= 1 && img.ok(B, H, W));
   FS_REQUIRE(src_cat && src_stats && src_counts && src_bits && dst_cat && dst_stats && dst_counts && dst_bits);
   FS_REQUIRE((src_conf == nullptr) == (dst_conf == nullptr) && (n == 0 || idx != nullptr));
   const size_t per = (size_t)3 * H * W;
-  const bool vec = gate_frame_vec(img, key, W, per);
-  const long bpi = (long)((per / (vec ? gate_frame_lane(img) : 1) + GATE_THREADS - 1) / GATE_THREADS);
+  const bool vec = img.wide_commit(W, per) && gate_key_ok<F>(key);
+  const long bpi = (long)((per / (vec ? F::lane : 1) + GATE_THREADS - 1) / GATE_THREADS);
   GateRows r;
   const long nbits = (long)H * ((W + 31) / 32);
   const void* src[5] = {src_cat, src_stats, src_counts, src_bits, src_conf};
@@ -615,7 +491,7 @@ int gate_commit_run(F img, const int* idx, int n, unsigned char* key, long long*
   hipLaunchKernelGGL(gate_commit_state_kernel, dim3((unsigned)cdiv(B, GATE_THREADS)), dim3(GATE_THREADS), 0, stream, idx, n, gstate, focus, B, H, W);
   FS_LAUNCH_CHECK();
   if (n == 0) return FS_OK;
-  gate_commit_frame(img, idx, key, B, per, vec, n * bpi, bpi, stream, H, W);
+  gate_commit_frame(img, idx, key, B, H, W, per, vec, n * bpi, bpi, stream);
   FS_LAUNCH_CHECK();
   if (total > 0) {
     hipLaunchKernelGGL(gate_commit_rows_kernel, dim3((unsigned)(n * bpr)), dim3(GATE_THREADS), 0, stream, idx, B, r, (unsigned)bpr);
@@ -624,7 +500,6 @@ int gate_commit_run(F img, const int* idx, int n, unsigned char* key, long long*
   return FS_OK;
 }
 
-
 }  // namespace
 
 extern "C" {
@@ -632,7 +507,7 @@ extern "C" {
 int fs_gate_tiles(const float* img, const unsigned char* key, int* sad, int B, int H, int W, int T, hipStream_t stream) {
   FS_REQUIRE(img && key && sad && B > 0 && H > 0 && W > 0 && gate_tile_ok(T) && (long)H * W < GATE_INT_LIMIT);
   const int th = cdiv(H, T), tw = cdiv(W, T);
-  const bool vec = gate_vec_ok(img, key, W);
+  const bool vec = PlanarFrame<float>(img, H, W).wide(W) && gate_key_ok<PlanarFrame<float>>(key);
   const int nseg = cdiv(W, GATE_SEG);
   const long wgs = (long)B * th * (vec ? nseg : tw);
   FS_REQUIRE((long)B * th * tw <= GATE_WGS_MAX);
@@ -645,21 +520,7 @@ int fs_gate_tiles(const float* img, const unsigned char* key, int* sad, int B, i
 }
 
 int fs_gate_tiles_u8(const unsigned char* img, const unsigned char* key, int* sad, int B, int H, int W, int T, hipStream_t stream) {
-  FS_REQUIRE(img && key && sad && B > 0 && H > 0 && W > 0 && gate_tile_ok(T) && (long)H * W < GATE_INT_LIMIT);
-  const int th = cdiv(H, T), tw = cdiv(W, T);
-  FS_REQUIRE((long)B * th * tw <= GATE_WGS_MAX);
-  if (gate_vec_u8_ok(img, key, W)) {
-    int lg = 0;                                         // lanes a row: covers min(W, 1024) columns, and a tile's T / 16 lanes
-    while (lg < 6 && (16 << lg) < W) ++lg;
-    while ((16 << lg) < T) ++lg;
-    const int nseg = cdiv(W, 16 << lg);
-    hipLaunchKernelGGL(gate_tiles_u8_band_kernel, dim3((unsigned)((long)B * th * nseg)), dim3(GATE_THREADS), 0, stream, img, key, sad, H, W, T,
-                       th, tw, nseg, lg);
-  } else {
-    hipLaunchKernelGGL(gate_tiles_u8_kernel, dim3((unsigned)((long)B * th * tw)), dim3(GATE_THREADS), 0, stream, img, key, sad, H, W, T, th, tw);
-  }
-  FS_LAUNCH_CHECK();
-  return FS_OK;
+  return gate_tiles_bytes(PlanarFrame<unsigned char>(img, H, W), key, sad, B, H, W, T, stream);
 }
 
 int fs_gate_decide(const int* sad, const long long* gstate, const float* focus, const long long* stats, const unsigned int* bits,
@@ -680,46 +541,28 @@ int fs_gate_commit(const float* img, const int* idx, int n, unsigned char* key, 
                    const long long* src_cat, const long long* src_stats, const int* src_counts, const unsigned int* src_bits,
                    const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts, unsigned int* dst_bits, float* dst_conf,
                    int B, int H, int W, int cap, hipStream_t stream) {
-  return gate_commit_run(img, idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat, dst_stats, dst_counts, dst_bits,
-                         dst_conf, B, H, W, cap, stream);
+  return gate_commit_run(PlanarFrame<float>(img, H, W), idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat, dst_stats,
+                         dst_counts, dst_bits, dst_conf, B, H, W, cap, stream);
 }
 
 int fs_gate_commit_u8(const unsigned char* img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus,
                       const long long* src_cat, const long long* src_stats, const int* src_counts, const unsigned int* src_bits,
                       const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts, unsigned int* dst_bits, float* dst_conf,
                       int B, int H, int W, int cap, hipStream_t stream) {
-  return gate_commit_run(img, idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat, dst_stats, dst_counts, dst_bits,
-                         dst_conf, B, H, W, cap, stream);
+  return gate_commit_run(PlanarFrame<unsigned char>(img, H, W), idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat,
+                         dst_stats, dst_counts, dst_bits, dst_conf, B, H, W, cap, stream);
 }
 
 int fs_gate_tiles_hwc(const unsigned char* img, long sb, long sy, int sx, const unsigned char* key, int* sad, int B, int H, int W, int T,
                       hipStream_t stream) {
-  FS_REQUIRE(img && key && sad && B > 0 && H > 0 && W > 0 && gate_tile_ok(T) && (long)H * W < GATE_INT_LIMIT);
-  const HwcView v{img, sb, sy, sx};
-  FS_REQUIRE(hwc_view_ok(v, B, H, W));
-  const int th = cdiv(H, T), tw = cdiv(W, T);
-  FS_REQUIRE((long)B * th * tw <= GATE_WGS_MAX);
-  const dim3 block(GATE_THREADS);
-  if (hwc_vec_ok(v, W) && ((uintptr_t)key & 15) == 0) {
-    int lg = 0;                                         // lanes a row, as fs_gate_tiles_u8 chooses them
-    while (lg < 6 && (16 << lg) < W) ++lg;
-    while ((16 << lg) < T) ++lg;
-    const int nseg = cdiv(W, 16 << lg);
-    const dim3 grid((unsigned)((long)B * th * nseg));
-    if (sx == 3) hipLaunchKernelGGL(gate_tiles_hwc_band_kernel<3>, grid, block, 0, stream, img, sb, sy, key, sad, H, W, T, th, tw, nseg, lg);
-    else hipLaunchKernelGGL(gate_tiles_hwc_band_kernel<4>, grid, block, 0, stream, img, sb, sy, key, sad, H, W, T, th, tw, nseg, lg);
-  } else {
-    hipLaunchKernelGGL(gate_tiles_hwc_kernel, dim3((unsigned)((long)B * th * tw)), block, 0, stream, img, sb, sy, sx, key, sad, H, W, T, th, tw);
-  }
-  FS_LAUNCH_CHECK();
-  return FS_OK;
+  return gate_tiles_bytes(HwcFrame<0>(img, sb, sy, sx), key, sad, B, H, W, T, stream);
 }
 
 int fs_gate_commit_hwc(const unsigned char* img, long sb, long sy, int sx, const int* idx, int n, unsigned char* key, long long* gstate,
                        const float* focus, const long long* src_cat, const long long* src_stats, const int* src_counts,
                        const unsigned int* src_bits, const float* src_conf, long long* dst_cat, long long* dst_stats, int* dst_counts,
                        unsigned int* dst_bits, float* dst_conf, int B, int H, int W, int cap, hipStream_t stream) {
-  return gate_commit_run(HwcView{img, sb, sy, sx}, idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat, dst_stats,
+  return gate_commit_run(HwcFrame<0>(img, sb, sy, sx), idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat, dst_stats,
                          dst_counts, dst_bits, dst_conf, B, H, W, cap, stream);
 }
 

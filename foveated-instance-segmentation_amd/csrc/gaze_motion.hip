@@ -12,10 +12,10 @@
 //            back; one lane a viewer moves the gazes and the totals and writes the motion row; fs_mask_rle's passes re-encode the moved
 //            words into scratch rows that reach stats / counts for the moving viewers alone; the key profiles are taken again.
 //   commit   for the viewers whose record was made anew: the frame's profiles become the key's, the totals 0.
-// The pixel code q is the gate's (gaze_gate.hip), restated here operation for operation.  For a frame of bytes (pixel value byte / 255,
-// q the byte) the profiles are fs_key_profiles of the frame, and fs_state_shift_u8 fills the key's border with the frame's bytes.
-// An interleaved frame of bytes (frame_view.h) is read where it lies: fs_frame_profiles_hwc is the profile pass on it, fs_state_shift_hwc
-// fills the border from it; every other pass is shared.
+// The pixel code q is the gate's, one function (frame_view.h).  A frame comes as planar fp32, planar bytes (pixel value byte / 255, q the
+// byte: its profiles are fs_key_profiles of it) or interleaved bytes read where they lie; the profile pass and the move pass, which fills
+// the key's uncovered border with the frame's codes, are written once over the frame's reader (frame_view.h), a kernel a layout where
+// the layouts' arguments differ.  Every other pass reads no frame.
 #include "common.h"
 #include "frame_view.h"
 
@@ -36,37 +36,8 @@ constexpr int MOTION_MAX_R = 255;
 constexpr int MOTION_LDS_BYTES = 65536;                // the estimate: two profiles of an axis and the costs
 constexpr int MOTION_ITER = 16;                        // elements a lane of the move and copy passes takes, 256 lanes apart
 
-__device__ __forceinline__ int motion_q(float v) {
-  v = v > 0.f ? v : 0.f;
-  v = v < 1.f ? v : 1.f;
-  return (int)rintf(__fmul_rn(v, 255.0f));
-}
-
-__device__ __forceinline__ int motion_wave_sum(int v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ long long motion_wave_sum(long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 __device__ __forceinline__ bool motion_still(const long long* __restrict__ shift, size_t b) {
   return shift[4 * b] == 0 && shift[4 * b + 1] == 0;
-}
-
-// one pixel's code of a frame (fp32) or of a key (bytes), and four of them from one aligned load
-__device__ __forceinline__ int motion_code(const float* p) { return motion_q(*p); }
-__device__ __forceinline__ int motion_code(const unsigned char* p) { return (int)*p; }
-__device__ __forceinline__ void motion_code4(const float* p, int* l) {
-  const f32x4 v = *reinterpret_cast<const f32x4*>(p);
-  l[0] += motion_q(v.x), l[1] += motion_q(v.y), l[2] += motion_q(v.z), l[3] += motion_q(v.w);
-}
-__device__ __forceinline__ void motion_code4(const unsigned char* p, int* l) {
-  const unsigned int k = *reinterpret_cast<const unsigned int*>(p);
-  l[0] += (int)(k & 255u), l[1] += (int)((k >> 8) & 255u), l[2] += (int)((k >> 16) & 255u), l[3] += (int)(k >> 24);
 }
 
 // prof[b] <- 0 for every viewer (shift null) or for the moving ones
@@ -78,37 +49,31 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_zero_kernel(int* __rest
   if (i < (unsigned int)n) prof[b * n + i] = 0;
 }
 
-// prof[b] += the row and column sums of L over one band of one segment.  VEC (W % 4 == 0, src aligned for a four-pixel load): a wave
-// takes every fourth row, a lane four pixels of it.  Otherwise a lane takes one column of the band.
-template <typename T, bool VEC>
-__global__ __launch_bounds__(MOTION_THREADS) void motion_profile_kernel(const T* __restrict__ src, const long long* __restrict__ shift,
-                                                                        int* __restrict__ prof, int H, int W, int nseg, int nband) {
+// prof[b] += the row and column sums of L over one band of one segment, the frame read through its reader.  VEC (the reader's quad): a
+// wave takes every fourth row, a lane four pixels of it -- their luma codes from aligned loads.  Otherwise a lane takes one column of the
+// band.
+template <class F, bool VEC>
+__device__ __forceinline__ void motion_profile(const F& f, int* __restrict__ prof, int H, int W, int nseg, int nband) {
   __shared__ int red[MOTION_THREADS / 64][MOTION_SEG];
   __shared__ int rsum[MOTION_THREADS / 64][MOTION_BAND];   // row sums meet here, so that one wave adds the band's rows as contiguous words
   const unsigned int blk = blockIdx.x;
   const int seg = (int)(blk % (unsigned)nseg);
   const int band = (int)((blk / (unsigned)nseg) % (unsigned)nband);
   const size_t b = blk / (unsigned)nseg / (unsigned)nband;
-  if (shift != nullptr && motion_still(shift, b)) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int y0 = band * MOTION_BAND, rows = min(MOTION_BAND, H - y0);
-  const size_t plane = (size_t)H * W;
   int* prow = prof + b * ((size_t)H + W) + y0;
   int* pcol = prof + b * ((size_t)H + W) + H;
   if (VEC) {
     const int x = seg * MOTION_SEG + lane * 4;
-    const size_t base = b * 3 * plane + (size_t)y0 * W + x;
+    const auto base = f.px(b, y0, x);
     int acc[4] = {0, 0, 0, 0};
     for (int r = wave; r < rows; r += MOTION_THREADS / 64) {
       int l[4] = {0, 0, 0, 0};
-      if (x < W) {
-        const size_t at = base + (size_t)r * W;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) motion_code4(src + at + c * plane, l);
-      }
+      if (x < W) f.luma4(f.down(base, r), l);
 #pragma unroll
       for (int j = 0; j < 4; ++j) acc[j] += l[j];
-      const int rs = motion_wave_sum(l[0] + l[1] + l[2] + l[3]);
+      const int rs = wave_sum_i(l[0] + l[1] + l[2] + l[3]);
       if (lane == 0) rsum[0][r] = rs;                   // a row is one wave's
     }
 #pragma unroll
@@ -119,16 +84,16 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_profile_kernel(const T*
     if (xc < W) atomicAdd(pcol + xc, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
   } else {
     const int x = seg * MOTION_SEG + (int)threadIdx.x;
-    const size_t base = b * 3 * plane + (size_t)y0 * W + x;
+    const auto base = f.px(b, y0, x);
     int acc = 0;
     for (int r = 0; r < rows; ++r) {
       int l = 0;
       if (x < W) {
-        const size_t at = base + (size_t)r * W;
-        l = motion_code(src + at) + motion_code(src + at + plane) + motion_code(src + at + 2 * plane);
+        const auto at = f.down(base, r);
+        l = f.code(at, 0) + f.code(at, 1) + f.code(at, 2);
       }
       acc += l;
-      const int rs = motion_wave_sum(l);
+      const int rs = wave_sum_i(l);
       if (lane == 0) rsum[wave][r] = rs;
     }
     __syncthreads();
@@ -138,75 +103,18 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_profile_kernel(const T*
   }
 }
 
-// motion_profile_kernel on an interleaved frame of bytes (fs_frame_profiles_hwc): the same cut, sums and atomics.  VEC (fs_byte_frame_route
-// = 1): a lane's four pixels are 12 bytes in three 4-byte loads (SX = 3) or one 16-byte load (SX = 4); a pixel's luma is the sum of its
-// three bytes (v_sad_u8 against 0), the fourth byte of an RGBA pixel masked off.  Otherwise a lane takes one column of the band.
+// its kernels: each layout keeps the parameters of its entry point and builds its reader from them.  Only a planar frame can be a key,
+// whose profiles are taken again after a move: shift null, every viewer; else the moving ones, and a still viewer's workgroups leave here.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(MOTION_THREADS) void motion_profile_kernel(const T* __restrict__ src, const long long* __restrict__ shift,
+                                                                        int* __restrict__ prof, int H, int W, int nseg, int nband) {
+  if (shift != nullptr && motion_still(shift, blockIdx.x / (unsigned)nseg / (unsigned)nband)) return;
+  motion_profile<PlanarFrame<T>, VEC>(PlanarFrame<T>(src, H, W), prof, H, W, nseg, nband);
+}
 template <int SX, bool VEC>
 __global__ __launch_bounds__(MOTION_THREADS) void motion_profile_hwc_kernel(const unsigned char* __restrict__ src, long sb, long sy,
                                                                             int* __restrict__ prof, int H, int W, int nseg, int nband) {
-  __shared__ int red[MOTION_THREADS / 64][MOTION_SEG];
-  __shared__ int rsum[MOTION_THREADS / 64][MOTION_BAND];
-  const unsigned int blk = blockIdx.x;
-  const int seg = (int)(blk % (unsigned)nseg);
-  const int band = (int)((blk / (unsigned)nseg) % (unsigned)nband);
-  const size_t b = blk / (unsigned)nseg / (unsigned)nband;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int y0 = band * MOTION_BAND, rows = min(MOTION_BAND, H - y0);
-  int* prow = prof + b * ((size_t)H + W) + y0;
-  int* pcol = prof + b * ((size_t)H + W) + H;
-  if (VEC) {
-    const int x = seg * MOTION_SEG + lane * 4;
-    const unsigned char* base = src + b * (size_t)sb + (size_t)y0 * sy + (size_t)x * SX;
-    int acc[4] = {0, 0, 0, 0};
-    for (int r = wave; r < rows; r += MOTION_THREADS / 64) {
-      int l[4] = {0, 0, 0, 0};
-      if (x < W) {
-        const unsigned char* at = base + (size_t)r * sy;
-        if (SX == 3) {
-          const unsigned int w0 = *reinterpret_cast<const unsigned int*>(at), w1 = *reinterpret_cast<const unsigned int*>(at + 4),
-                             w2 = *reinterpret_cast<const unsigned int*>(at + 8);
-          l[0] = (int)__builtin_amdgcn_sad_u8(w0 & 0x00ffffffu, 0u, 0u);
-          l[1] = (int)__builtin_amdgcn_sad_u8(w0 >> 24, 0u, __builtin_amdgcn_sad_u8(w1 & 0x0000ffffu, 0u, 0u));
-          l[2] = (int)__builtin_amdgcn_sad_u8(w1 >> 16, 0u, __builtin_amdgcn_sad_u8(w2 & 0x000000ffu, 0u, 0u));
-          l[3] = (int)__builtin_amdgcn_sad_u8(w2 >> 8, 0u, 0u);
-        } else {
-          const hwc_u32x4 v = *reinterpret_cast<const hwc_u32x4*>(at);
-          l[0] = (int)__builtin_amdgcn_sad_u8(v.x & 0x00ffffffu, 0u, 0u);
-          l[1] = (int)__builtin_amdgcn_sad_u8(v.y & 0x00ffffffu, 0u, 0u);
-          l[2] = (int)__builtin_amdgcn_sad_u8(v.z & 0x00ffffffu, 0u, 0u);
-          l[3] = (int)__builtin_amdgcn_sad_u8(v.w & 0x00ffffffu, 0u, 0u);
-        }
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[j] += l[j];
-      const int rs = motion_wave_sum(l[0] + l[1] + l[2] + l[3]);
-      if (lane == 0) rsum[0][r] = rs;                   // a row is one wave's
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) red[wave][lane * 4 + j] = acc[j];
-    __syncthreads();
-    if ((int)threadIdx.x < rows) atomicAdd(prow + threadIdx.x, rsum[0][threadIdx.x]);
-    const int xc = seg * MOTION_SEG + (int)threadIdx.x;
-    if (xc < W) atomicAdd(pcol + xc, red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x]);
-  } else {
-    const int x = seg * MOTION_SEG + (int)threadIdx.x;
-    const unsigned char* base = src + b * (size_t)sb + (size_t)y0 * sy + (size_t)x * SX;
-    int acc = 0;
-    for (int r = 0; r < rows; ++r) {
-      int l = 0;
-      if (x < W) {
-        const unsigned char* at = base + (size_t)r * sy;
-        l = (int)at[0] + (int)at[1] + (int)at[2];
-      }
-      acc += l;
-      const int rs = motion_wave_sum(l);
-      if (lane == 0) rsum[wave][r] = rs;
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < rows)
-      atomicAdd(prow + threadIdx.x, rsum[0][threadIdx.x] + rsum[1][threadIdx.x] + rsum[2][threadIdx.x] + rsum[3][threadIdx.x]);
-    if (x < W) atomicAdd(pcol + x, acc);
-  }
+  motion_profile<HwcFrame<SX>, VEC>(HwcFrame<SX>(src, sb, sy, SX), prof, H, W, nseg, nband);
 }
 
 // One workgroup a viewer.  For each axis: P, K of length n in LDS; cost[j] for s = j - R = sum_{i=R}^{n-1-R} |P[i] - K[i - s]|, a wave
@@ -243,7 +151,7 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_estimate_kernel(const i
         const int v = P[i] - K[i - s];
         c += v < 0 ? -v : v;
       }
-      c = motion_wave_sum(c);
+      c = wave_sum_ll(c);
       if (lane == 0) cost[j] = c;
     }
     __syncthreads();
@@ -285,143 +193,71 @@ __device__ __forceinline__ unsigned int motion_get(const unsigned int* __restric
 
 // The workgroups of a viewer in the move and copy passes: nk over the key's bytes (V of them a lane, MOTION_ITER times), then nb over the
 // bit words (one a lane).
-// key2[c,y,x] = key[c,y-dy,x-dx] where that lies in the frame, else q(img[c,y,x]); bits2[y,x] = bits[y-dy,x-dx], else 0.
-template <int V>
-__global__ __launch_bounds__(MOTION_THREADS) void motion_move_kernel(const float* __restrict__ img, const long long* __restrict__ shift,
+// bits2[y,x] = bits[y-dy,x-dx] where that lies in the frame, else 0: word w of viewer b, by a funnel shift over the word border
+__device__ __forceinline__ void motion_move_bits(const unsigned int* __restrict__ bits, unsigned int* __restrict__ bits2, size_t b, unsigned int w,
+                                                 int dy, int dx, int H, int W, int P) {
+  if (w >= (unsigned int)(H * P)) return;
+  const int y = (int)(w / (unsigned)P), c = (int)(w - (unsigned)y * P);
+  const int sy = y - dy;
+  unsigned int out = 0;
+  if (sy >= 0 && sy < H) out = motion_get(bits + (b * H + sy) * P, P, W, 32 * c - dx) & motion_tail(c, P, W);
+  bits2[b * H * P + w] = out;
+}
+
+// key2[c,y,x] = key[c,y-dy,x-dx] where that lies in the frame, else the code of the frame's (c,y,x), read through its reader; the bit
+// words as above.
+template <class F, int V>
+__device__ __forceinline__ void motion_move(const F& f, const long long* __restrict__ shift, const unsigned char* __restrict__ key,
+                                            unsigned char* __restrict__ key2, const unsigned int* __restrict__ bits,
+                                            unsigned int* __restrict__ bits2, int H, int W, int P, unsigned int nk, unsigned int nb) {
+  const size_t b = blockIdx.x / (nk + nb);
+  const unsigned int r = blockIdx.x - (unsigned int)b * (nk + nb);
+  const int dy = (int)shift[4 * b], dx = (int)shift[4 * b + 1];
+  if (r < nk) {
+    const size_t plane = (size_t)H * W, per = 3 * plane;
+    const unsigned char* kb = key + b * per;
+    unsigned char* ob = key2 + b * per;
+    for (int it = 0; it < MOTION_ITER; ++it) {
+      const size_t e = (((size_t)r * MOTION_ITER + it) * MOTION_THREADS + threadIdx.x) * V;
+      if (e >= per) return;
+      const int c = (int)(e / plane);
+      const int rem = (int)(e - c * plane);
+      const int y = rem / W, x = rem - y * W;
+      const int sy = y - dy;
+      const bool row_in = sy >= 0 && sy < H;
+      const size_t srow = c * plane + (size_t)(row_in ? sy : 0) * W;
+      unsigned int out = 0;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {                    // V == 4: W % 4 == 0, the four pixels lie in one row
+        const int sx = x + j - dx;
+        const unsigned int k = (row_in && sx >= 0 && sx < W) ? (unsigned int)kb[srow + sx] : (unsigned int)f.code_of(b, e + j, c, y, x + j);
+        out |= k << (8 * j);
+      }
+      if (V == 4) *reinterpret_cast<unsigned int*>(ob + e) = out;
+      else ob[e] = (unsigned char)out;
+    }
+  } else {
+    motion_move_bits(bits, bits2, b, (r - nk) * MOTION_THREADS + threadIdx.x, dy, dx, H, W, P);
+  }
+}
+
+// its kernels: each layout keeps the parameters of its entry point and builds its reader from them; a still viewer's workgroups leave here
+template <typename T, int V>
+__global__ __launch_bounds__(MOTION_THREADS) void motion_move_kernel(const T* __restrict__ img, const long long* __restrict__ shift,
                                                                      const unsigned char* __restrict__ key, unsigned char* __restrict__ key2,
                                                                      const unsigned int* __restrict__ bits, unsigned int* __restrict__ bits2,
                                                                      int H, int W, int P, unsigned int nk, unsigned int nb) {
-  const size_t b = blockIdx.x / (nk + nb);
-  const unsigned int r = blockIdx.x - (unsigned int)b * (nk + nb);
-  if (motion_still(shift, b)) return;
-  const int dy = (int)shift[4 * b], dx = (int)shift[4 * b + 1];
-  if (r < nk) {
-    const size_t plane = (size_t)H * W, per = 3 * plane;
-    const float* ib = img + b * per;
-    const unsigned char* kb = key + b * per;
-    unsigned char* ob = key2 + b * per;
-    for (int it = 0; it < MOTION_ITER; ++it) {
-      const size_t e = (((size_t)r * MOTION_ITER + it) * MOTION_THREADS + threadIdx.x) * V;
-      if (e >= per) return;
-      const int c = (int)(e / plane);
-      const int rem = (int)(e - c * plane);
-      const int y = rem / W, x = rem - y * W;
-      const int sy = y - dy;
-      const bool row_in = sy >= 0 && sy < H;
-      const size_t srow = c * plane + (size_t)(row_in ? sy : 0) * W;
-      unsigned int out = 0;
-#pragma unroll
-      for (int j = 0; j < V; ++j) {                    // V == 4: W % 4 == 0, the four pixels lie in one row
-        const int sx = x + j - dx;
-        const unsigned int k = (row_in && sx >= 0 && sx < W) ? (unsigned int)kb[srow + sx] : (unsigned int)motion_q(ib[e + j]);
-        out |= k << (8 * j);
-      }
-      if (V == 4) *reinterpret_cast<unsigned int*>(ob + e) = out;
-      else ob[e] = (unsigned char)out;
-    }
-  } else {
-    const unsigned int w = (r - nk) * MOTION_THREADS + threadIdx.x;
-    if (w >= (unsigned int)(H * P)) return;
-    const int y = (int)(w / (unsigned)P), c = (int)(w - (unsigned)y * P);
-    const int sy = y - dy;
-    unsigned int out = 0;
-    if (sy >= 0 && sy < H) out = motion_get(bits + (b * H + sy) * P, P, W, 32 * c - dx) & motion_tail(c, P, W);
-    bits2[b * H * P + w] = out;
-  }
+  if (motion_still(shift, blockIdx.x / (nk + nb))) return;
+  motion_move<PlanarFrame<T>, V>(PlanarFrame<T>(img, H, W), shift, key, key2, bits, bits2, H, W, P, nk, nb);
 }
-
-// motion_move_kernel for a frame of bytes (fs_state_shift_u8): the uncovered border is filled with the frame's byte, the pixel code of
-// such a frame.  Everything else as above.
-template <int V>
-__global__ __launch_bounds__(MOTION_THREADS) void motion_move_u8_kernel(const unsigned char* __restrict__ img, const long long* __restrict__ shift,
-                                                                        const unsigned char* __restrict__ key, unsigned char* __restrict__ key2,
-                                                                        const unsigned int* __restrict__ bits, unsigned int* __restrict__ bits2,
-                                                                        int H, int W, int P, unsigned int nk, unsigned int nb) {
-  const size_t b = blockIdx.x / (nk + nb);
-  const unsigned int r = blockIdx.x - (unsigned int)b * (nk + nb);
-  if (motion_still(shift, b)) return;
-  const int dy = (int)shift[4 * b], dx = (int)shift[4 * b + 1];
-  if (r < nk) {
-    const size_t plane = (size_t)H * W, per = 3 * plane;
-    const unsigned char* ib = img + b * per;
-    const unsigned char* kb = key + b * per;
-    unsigned char* ob = key2 + b * per;
-    for (int it = 0; it < MOTION_ITER; ++it) {
-      const size_t e = (((size_t)r * MOTION_ITER + it) * MOTION_THREADS + threadIdx.x) * V;
-      if (e >= per) return;
-      const int c = (int)(e / plane);
-      const int rem = (int)(e - c * plane);
-      const int y = rem / W, x = rem - y * W;
-      const int sy = y - dy;
-      const bool row_in = sy >= 0 && sy < H;
-      const size_t srow = c * plane + (size_t)(row_in ? sy : 0) * W;
-      unsigned int out = 0;
-#pragma unroll
-      for (int j = 0; j < V; ++j) {                    // V == 4: W % 4 == 0, the four pixels lie in one row
-        const int sx = x + j - dx;
-        const unsigned int k = (row_in && sx >= 0 && sx < W) ? (unsigned int)kb[srow + sx] : (unsigned int)ib[e + j];
-        out |= k << (8 * j);
-      }
-      if (V == 4) *reinterpret_cast<unsigned int*>(ob + e) = out;
-      else ob[e] = (unsigned char)out;
-    }
-  } else {
-    const unsigned int w = (r - nk) * MOTION_THREADS + threadIdx.x;
-    if (w >= (unsigned int)(H * P)) return;
-    const int y = (int)(w / (unsigned)P), c = (int)(w - (unsigned)y * P);
-    const int sy = y - dy;
-    unsigned int out = 0;
-    if (sy >= 0 && sy < H) out = motion_get(bits + (b * H + sy) * P, P, W, 32 * c - dx) & motion_tail(c, P, W);
-    bits2[b * H * P + w] = out;
-  }
-}
-
-// motion_move_u8_kernel for an interleaved frame of bytes (fs_state_shift_hwc): the uncovered border is filled with the frame's byte of
-// that channel, read where it lies.  Everything else as above.
 template <int V>
 __global__ __launch_bounds__(MOTION_THREADS) void motion_move_hwc_kernel(const unsigned char* __restrict__ img, long sb, long sy, int sx,
                                                                          const long long* __restrict__ shift, const unsigned char* __restrict__ key,
                                                                          unsigned char* __restrict__ key2, const unsigned int* __restrict__ bits,
                                                                          unsigned int* __restrict__ bits2, int H, int W, int P, unsigned int nk,
                                                                          unsigned int nb) {
-  const size_t b = blockIdx.x / (nk + nb);
-  const unsigned int r = blockIdx.x - (unsigned int)b * (nk + nb);
-  if (motion_still(shift, b)) return;
-  const int dy = (int)shift[4 * b], dx = (int)shift[4 * b + 1];
-  if (r < nk) {
-    const size_t plane = (size_t)H * W, per = 3 * plane;
-    const unsigned char* ib = img + b * (size_t)sb;
-    const unsigned char* kb = key + b * per;
-    unsigned char* ob = key2 + b * per;
-    for (int it = 0; it < MOTION_ITER; ++it) {
-      const size_t e = (((size_t)r * MOTION_ITER + it) * MOTION_THREADS + threadIdx.x) * V;
-      if (e >= per) return;
-      const int c = (int)(e / plane);
-      const int rem = (int)(e - c * plane);
-      const int y = rem / W, x = rem - y * W;
-      const int sy0 = y - dy;
-      const bool row_in = sy0 >= 0 && sy0 < H;
-      const size_t srow = c * plane + (size_t)(row_in ? sy0 : 0) * W;
-      const unsigned char* frow = ib + (size_t)y * sy + c;
-      unsigned int out = 0;
-#pragma unroll
-      for (int j = 0; j < V; ++j) {                    // V == 4: W % 4 == 0, the four pixels lie in one row
-        const int sx0 = x + j - dx;
-        const unsigned int k = (row_in && sx0 >= 0 && sx0 < W) ? (unsigned int)kb[srow + sx0] : (unsigned int)frow[(size_t)(x + j) * sx];
-        out |= k << (8 * j);
-      }
-      if (V == 4) *reinterpret_cast<unsigned int*>(ob + e) = out;
-      else ob[e] = (unsigned char)out;
-    }
-  } else {
-    const unsigned int w = (r - nk) * MOTION_THREADS + threadIdx.x;
-    if (w >= (unsigned int)(H * P)) return;
-    const int y = (int)(w / (unsigned)P), c = (int)(w - (unsigned)y * P);
-    const int sy0 = y - dy;
-    unsigned int out = 0;
-    if (sy0 >= 0 && sy0 < H) out = motion_get(bits + (b * H + sy0) * P, P, W, 32 * c - dx) & motion_tail(c, P, W);
-    bits2[b * H * P + w] = out;
-  }
+  if (motion_still(shift, blockIdx.x / (nk + nb))) return;
+  motion_move<HwcFrame<0>, V>(HwcFrame<0>(img, sb, sy, sx), shift, key, key2, bits, bits2, H, W, P, nk, nb);
 }
 
 // key <- key2 and bits <- bits2 for the moving viewers; lane 0 of a viewer's first workgroup moves its gazes and totals and writes its
@@ -513,56 +349,62 @@ bool motion_sizes_ok(int B, int H, int W) {
 }
 bool motion_range_ok(int H, int W, int R) { return R >= 1 && R <= MOTION_MAX_R && 4L * R < (H < W ? H : W); }
 
+// the profile pass's launch by the frame's layout; vec = four pixels a lane
 template <typename T>
-int motion_profiles(const T* src, const long long* shift, int* prof, int B, int H, int W, bool vec, hipStream_t stream) {
+void motion_profile_launch(const PlanarFrame<T>& f, bool vec, dim3 grid, hipStream_t stream, const long long* shift, int* prof, int H, int W,
+                           int nseg, int nband) {
+  const dim3 block(MOTION_THREADS);
+  if (vec) hipLaunchKernelGGL((motion_profile_kernel<T, true>), grid, block, 0, stream, f.p, shift, prof, H, W, nseg, nband);
+  else hipLaunchKernelGGL((motion_profile_kernel<T, false>), grid, block, 0, stream, f.p, shift, prof, H, W, nseg, nband);
+}
+void motion_profile_launch(const HwcFrame<0>& f, bool vec, dim3 grid, hipStream_t stream, const long long*, int* prof, int H, int W, int nseg,
+                           int nband) {
+  const dim3 block(MOTION_THREADS);
+  if (f.sx == 3 && vec) hipLaunchKernelGGL((motion_profile_hwc_kernel<3, true>), grid, block, 0, stream, f.p, f.sb, f.sy, prof, H, W, nseg, nband);
+  else if (f.sx == 3) hipLaunchKernelGGL((motion_profile_hwc_kernel<3, false>), grid, block, 0, stream, f.p, f.sb, f.sy, prof, H, W, nseg, nband);
+  else if (vec) hipLaunchKernelGGL((motion_profile_hwc_kernel<4, true>), grid, block, 0, stream, f.p, f.sb, f.sy, prof, H, W, nseg, nband);
+  else hipLaunchKernelGGL((motion_profile_hwc_kernel<4, false>), grid, block, 0, stream, f.p, f.sb, f.sy, prof, H, W, nseg, nband);
+}
+
+// fs_frame_profiles / fs_key_profiles / fs_frame_profiles_hwc: the checks, prof zeroed, the profile pass on every viewer
+template <class F>
+int motion_profiles(const F& f, int* prof, int B, int H, int W, hipStream_t stream) {
+  FS_REQUIRE(f && prof && motion_sizes_ok(B, H, W) && f.ok(B, H, W));
   const int n = H + W;
   const int bpv = cdiv(n, MOTION_THREADS), nseg = cdiv(W, MOTION_SEG), nband = cdiv(H, MOTION_BAND);
   FS_REQUIRE((long)B * bpv <= MOTION_WGS_MAX && (long)B * nseg * nband <= MOTION_WGS_MAX);
-  hipLaunchKernelGGL(motion_zero_kernel, dim3((unsigned)(B * bpv)), dim3(MOTION_THREADS), 0, stream, prof, shift, n, (unsigned)bpv);
+  hipLaunchKernelGGL(motion_zero_kernel, dim3((unsigned)(B * bpv)), dim3(MOTION_THREADS), 0, stream, prof, (const long long*)nullptr, n,
+                     (unsigned)bpv);
   FS_LAUNCH_CHECK();
-  const dim3 grid((unsigned)(B * nseg * nband));
-  if (vec)
-    hipLaunchKernelGGL((motion_profile_kernel<T, true>), grid, dim3(MOTION_THREADS), 0, stream, src, shift, prof, H, W, nseg, nband);
-  else
-    hipLaunchKernelGGL((motion_profile_kernel<T, false>), grid, dim3(MOTION_THREADS), 0, stream, src, shift, prof, H, W, nseg, nband);
+  motion_profile_launch(f, f.quad(W), dim3((unsigned)(B * nseg * nband)), stream, nullptr, prof, H, W, nseg, nband);
   FS_LAUNCH_CHECK();
   return FS_OK;
 }
 
 long motion_pad2(long v) { return (v + 1) & ~1L; }
 
-// the move pass by the frame's type
-template <int V>
-void motion_move(const float* img, const long long* shift, const unsigned char* key, unsigned char* key2, const unsigned int* bits,
-                 unsigned int* bits2, int H, int W, int P, long nk, long nb, dim3 grid, hipStream_t stream) {
-  hipLaunchKernelGGL(motion_move_kernel<V>, grid, dim3(MOTION_THREADS), 0, stream, img, shift, key, key2, bits, bits2, H, W, P, (unsigned)nk,
+// the move pass's launch by the frame's layout
+template <int V, typename T>
+void motion_move_launch(const PlanarFrame<T>& f, const long long* shift, const unsigned char* key, unsigned char* key2, const unsigned int* bits,
+                        unsigned int* bits2, int H, int W, int P, long nk, long nb, dim3 grid, hipStream_t stream) {
+  hipLaunchKernelGGL((motion_move_kernel<T, V>), grid, dim3(MOTION_THREADS), 0, stream, f.p, shift, key, key2, bits, bits2, H, W, P, (unsigned)nk,
                      (unsigned)nb);
 }
 template <int V>
-void motion_move(const unsigned char* img, const long long* shift, const unsigned char* key, unsigned char* key2, const unsigned int* bits,
-                 unsigned int* bits2, int H, int W, int P, long nk, long nb, dim3 grid, hipStream_t stream) {
-  hipLaunchKernelGGL(motion_move_u8_kernel<V>, grid, dim3(MOTION_THREADS), 0, stream, img, shift, key, key2, bits, bits2, H, W, P, (unsigned)nk,
-                     (unsigned)nb);
+void motion_move_launch(const HwcFrame<0>& f, const long long* shift, const unsigned char* key, unsigned char* key2, const unsigned int* bits,
+                        unsigned int* bits2, int H, int W, int P, long nk, long nb, dim3 grid, hipStream_t stream) {
+  hipLaunchKernelGGL(motion_move_hwc_kernel<V>, grid, dim3(MOTION_THREADS), 0, stream, f.p, f.sb, f.sy, f.sx, shift, key, key2, bits, bits2, H, W, P,
+                     (unsigned)nk, (unsigned)nb);
 }
 
-template <int V>
-void motion_move(const HwcView& img, const long long* shift, const unsigned char* key, unsigned char* key2, const unsigned int* bits,
-                 unsigned int* bits2, int H, int W, int P, long nk, long nb, dim3 grid, hipStream_t stream) {
-  hipLaunchKernelGGL(motion_move_hwc_kernel<V>, grid, dim3(MOTION_THREADS), 0, stream, img.p, img.sb, img.sy, img.sx, shift, key, key2, bits, bits2,
-                     H, W, P, (unsigned)nk, (unsigned)nb);
-}
-inline bool motion_frame_ok(const float*, int, int, int) { return true; }
-inline bool motion_frame_ok(const unsigned char*, int, int, int) { return true; }
-inline bool motion_frame_ok(const HwcView& v, int B, int H, int W) { return hwc_view_ok(v, B, H, W); }
-
-// fs_state_shift / fs_state_shift_u8 / fs_state_shift_hwc: the checks and every pass, the move pass of the frame's type
-template <typename F>
-int motion_state_shift(F img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
+// fs_state_shift / fs_state_shift_u8 / fs_state_shift_hwc: the checks and every pass, the move pass of the frame's layout
+template <class F>
+int motion_state_shift(const F& img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
                        long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch, int B,
                        int H, int W, int cap, hipStream_t stream) {
   FS_REQUIRE(img && shift && key && key2 && bits && bits2 && gstate && stats && counts && prof_key && mstate && motion && scratch);
   FS_REQUIRE(motion_sizes_ok(B, H, W) && cap >= 1 && H <= MOTION_MAX_SIDE && W <= MOTION_MAX_SIDE && key != key2 && bits != bits2);
-  FS_REQUIRE(((uintptr_t)scratch & 7) == 0 && fs_mask_rle_scratch_ints(B, H, W) > 0 && motion_frame_ok(img, B, H, W));
+  FS_REQUIRE(((uintptr_t)scratch & 7) == 0 && fs_mask_rle_scratch_ints(B, H, W) > 0 && img.ok(B, H, W));
   const int P = (W + 31) / 32, n = H + W;
   const size_t per = (size_t)3 * H * W;
   const bool vec = W % 4 == 0 && ((uintptr_t)key & 3) == 0 && ((uintptr_t)key2 & 3) == 0;
@@ -576,12 +418,12 @@ int motion_state_shift(F img, const long long* shift, unsigned char* key, unsign
   int* rle = counts2 + motion_pad2((long)B * cap);
   const dim3 grid((unsigned)(B * (nk + nb))), block(MOTION_THREADS);
   if (vec) {
-    motion_move<4>(img, shift, key, key2, bits, bits2, H, W, P, nk, nb, grid, stream);
+    motion_move_launch<4>(img, shift, key, key2, bits, bits2, H, W, P, nk, nb, grid, stream);
     FS_LAUNCH_CHECK();
     hipLaunchKernelGGL(motion_back_kernel<4>, grid, block, 0, stream, shift, key2, key, bits2, bits, gstate, mstate, motion, H, W, P, (unsigned)nk,
                        (unsigned)nb);
   } else {
-    motion_move<1>(img, shift, key, key2, bits, bits2, H, W, P, nk, nb, grid, stream);
+    motion_move_launch<1>(img, shift, key, key2, bits, bits2, H, W, P, nk, nb, grid, stream);
     FS_LAUNCH_CHECK();
     hipLaunchKernelGGL(motion_back_kernel<1>, grid, block, 0, stream, shift, key2, key, bits2, bits, gstate, mstate, motion, H, W, P, (unsigned)nk,
                        (unsigned)nb);
@@ -592,29 +434,26 @@ int motion_state_shift(F img, const long long* shift, unsigned char* key, unsign
                      reinterpret_cast<const unsigned int*>(counts2), reinterpret_cast<unsigned int*>(stats), reinterpret_cast<unsigned int*>(counts),
                      prof_key, cap, n, (unsigned)bpv);
   FS_LAUNCH_CHECK();
-  const dim3 pgrid((unsigned)(B * cdiv(W, MOTION_SEG) * cdiv(H, MOTION_BAND)));
   const int nseg = cdiv(W, MOTION_SEG), nband = cdiv(H, MOTION_BAND);
-  if (vec)
-    hipLaunchKernelGGL((motion_profile_kernel<unsigned char, true>), pgrid, block, 0, stream, key, shift, prof_key, H, W, nseg, nband);
-  else
-    hipLaunchKernelGGL((motion_profile_kernel<unsigned char, false>), pgrid, block, 0, stream, key, shift, prof_key, H, W, nseg, nband);
+  motion_profile_launch(PlanarFrame<unsigned char>(key, H, W), vec, dim3((unsigned)(B * nseg * nband)), stream, shift, prof_key, H, W, nseg, nband);
   FS_LAUNCH_CHECK();
   return FS_OK;
 }
-
 
 }  // namespace
 
 extern "C" {
 
 int fs_frame_profiles(const float* img, int* prof, int B, int H, int W, hipStream_t stream) {
-  FS_REQUIRE(img && prof && motion_sizes_ok(B, H, W));
-  return motion_profiles(img, nullptr, prof, B, H, W, W % 4 == 0 && ((uintptr_t)img & 15) == 0, stream);
+  return motion_profiles(PlanarFrame<float>(img, H, W), prof, B, H, W, stream);
 }
 
 int fs_key_profiles(const unsigned char* key, int* prof, int B, int H, int W, hipStream_t stream) {
-  FS_REQUIRE(key && prof && motion_sizes_ok(B, H, W));
-  return motion_profiles(key, nullptr, prof, B, H, W, W % 4 == 0 && ((uintptr_t)key & 3) == 0, stream);
+  return motion_profiles(PlanarFrame<unsigned char>(key, H, W), prof, B, H, W, stream);
+}
+
+int fs_frame_profiles_hwc(const unsigned char* img, long sb, long sy, int sx, int* prof, int B, int H, int W, hipStream_t stream) {
+  return motion_profiles(HwcFrame<0>(img, sb, sy, sx), prof, B, H, W, stream);
 }
 
 int fs_profile_shift(const int* prof, const int* prof_key, const long long* gstate, long long* shift, int B, int H, int W, int R, int gain,
@@ -637,40 +476,22 @@ long fs_state_shift_scratch_ints(int B, int H, int W, int cap) {
 int fs_state_shift(const float* img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
                    long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch, int B,
                    int H, int W, int cap, hipStream_t stream) {
-  return motion_state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch, B, H, W, cap, stream);
+  return motion_state_shift(PlanarFrame<float>(img, H, W), shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch, B, H,
+                            W, cap, stream);
 }
 
 int fs_state_shift_u8(const unsigned char* img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
                       long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch, int B,
                       int H, int W, int cap, hipStream_t stream) {
-  return motion_state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch, B, H, W, cap, stream);
-}
-
-int fs_frame_profiles_hwc(const unsigned char* img, long sb, long sy, int sx, int* prof, int B, int H, int W, hipStream_t stream) {
-  FS_REQUIRE(img && prof && motion_sizes_ok(B, H, W));
-  const HwcView v{img, sb, sy, sx};
-  FS_REQUIRE(hwc_view_ok(v, B, H, W));
-  const int n = H + W;
-  const int bpv = cdiv(n, MOTION_THREADS), nseg = cdiv(W, MOTION_SEG), nband = cdiv(H, MOTION_BAND);
-  FS_REQUIRE((long)B * bpv <= MOTION_WGS_MAX && (long)B * nseg * nband <= MOTION_WGS_MAX);
-  hipLaunchKernelGGL(motion_zero_kernel, dim3((unsigned)(B * bpv)), dim3(MOTION_THREADS), 0, stream, prof, (const long long*)nullptr, n,
-                     (unsigned)bpv);
-  FS_LAUNCH_CHECK();
-  const dim3 grid((unsigned)(B * nseg * nband)), block(MOTION_THREADS);
-  const bool vec = hwc_vec_ok(v, W);
-  if (sx == 3 && vec) hipLaunchKernelGGL((motion_profile_hwc_kernel<3, true>), grid, block, 0, stream, img, sb, sy, prof, H, W, nseg, nband);
-  else if (sx == 3) hipLaunchKernelGGL((motion_profile_hwc_kernel<3, false>), grid, block, 0, stream, img, sb, sy, prof, H, W, nseg, nband);
-  else if (vec) hipLaunchKernelGGL((motion_profile_hwc_kernel<4, true>), grid, block, 0, stream, img, sb, sy, prof, H, W, nseg, nband);
-  else hipLaunchKernelGGL((motion_profile_hwc_kernel<4, false>), grid, block, 0, stream, img, sb, sy, prof, H, W, nseg, nband);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
+  return motion_state_shift(PlanarFrame<unsigned char>(img, H, W), shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch,
+                            B, H, W, cap, stream);
 }
 
 int fs_state_shift_hwc(const unsigned char* img, long sb, long sy, int sx, const long long* shift, unsigned char* key, unsigned char* key2,
                        unsigned int* bits, unsigned int* bits2, long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate,
                        long long* motion, int* scratch, int B, int H, int W, int cap, hipStream_t stream) {
-  return motion_state_shift(HwcView{img, sb, sy, sx}, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch, B, H, W,
-                            cap, stream);
+  return motion_state_shift(HwcFrame<0>(img, sb, sy, sx), shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch, B, H,
+                            W, cap, stream);
 }
 
 int fs_motion_commit(const int* idx, int n, const int* prof, int* prof_key, long long* mstate, int B, int H, int W, hipStream_t stream) {

@@ -31,28 +31,20 @@ __device__ __forceinline__ Taps make_taps(float gx, float gy, int H, int W) {
   t.oky0 = (t.y0 >= 0) & (t.y0 < H); t.oky1 = (t.y0 + 1 >= 0) & (t.y0 + 1 < H);
   return t;
 }
-__device__ __forceinline__ float sample_plane(const float* __restrict__ p, int W, const Taps& t) {
-  const float vnw = (t.oky0 & t.okx0) ? p[(long)t.y0 * W + t.x0] : 0.f;
-  const float vne = (t.oky0 & t.okx1) ? p[(long)t.y0 * W + t.x0 + 1] : 0.f;
-  const float vsw = (t.oky1 & t.okx0) ? p[(long)(t.y0 + 1) * W + t.x0] : 0.f;
-  const float vse = (t.oky1 & t.okx1) ? p[(long)(t.y0 + 1) * W + t.x0 + 1] : 0.f;
+// the chain over the four taps' values (0 for a tap outside the plane)
+__device__ __forceinline__ float sample_chain(float vnw, float vne, float vsw, float vse, const Taps& t) {
   float acc = __fmul_rn(vnw, t.nw);
   acc = __fmaf_rn(vne, t.ne, acc);
   acc = __fmaf_rn(vsw, t.sw, acc);
   acc = __fmaf_rn(vse, t.se, acc);
   return acc;
 }
-// a plane of bytes (frames_u8.hip): the pixel value is (float)byte / 255, correctly rounded; the same taps and the same chain
-__device__ __forceinline__ float sample_plane(const unsigned char* __restrict__ p, int W, const Taps& t) {
-  const float vnw = (t.oky0 & t.okx0) ? __fdiv_rn((float)p[(long)t.y0 * W + t.x0], 255.0f) : 0.f;
-  const float vne = (t.oky0 & t.okx1) ? __fdiv_rn((float)p[(long)t.y0 * W + t.x0 + 1], 255.0f) : 0.f;
-  const float vsw = (t.oky1 & t.okx0) ? __fdiv_rn((float)p[(long)(t.y0 + 1) * W + t.x0], 255.0f) : 0.f;
-  const float vse = (t.oky1 & t.okx1) ? __fdiv_rn((float)p[(long)(t.y0 + 1) * W + t.x0 + 1], 255.0f) : 0.f;
-  float acc = __fmul_rn(vnw, t.nw);
-  acc = __fmaf_rn(vne, t.ne, acc);
-  acc = __fmaf_rn(vsw, t.sw, acc);
-  acc = __fmaf_rn(vse, t.se, acc);
-  return acc;
+__device__ __forceinline__ float sample_plane(const float* __restrict__ p, int W, const Taps& t) {
+  const float vnw = (t.oky0 & t.okx0) ? p[(long)t.y0 * W + t.x0] : 0.f;
+  const float vne = (t.oky0 & t.okx1) ? p[(long)t.y0 * W + t.x0 + 1] : 0.f;
+  const float vsw = (t.oky1 & t.okx0) ? p[(long)(t.y0 + 1) * W + t.x0] : 0.f;
+  const float vse = (t.oky1 & t.okx1) ? p[(long)(t.y0 + 1) * W + t.x0 + 1] : 0.f;
+  return sample_chain(vnw, vne, vsw, vse, t);
 }
 
 }  // namespace

@@ -1381,14 +1381,6 @@ def byte_frame_layout(img):
     return layout
 
 
-def _hwc_args(img, layout):
-    """The (pointer, sb, sy, sx) of an hwc view (byte_frame_layout) for the fs_*_hwc entry points."""
-    _, sb, sy, sx = layout
-    if not img.is_cuda:
-        raise hip.HipLibraryError("fovealseg kernels need device tensors (got a CPU tensor); there is no CPU path")
-    return img.data_ptr(), sb, sy, sx
-
-
 def _byte_frame(img, what="img"):
     """("planar",) or ("hwc", ...) of a uint8 frame the *_u8 functions take; ValueError for any other layout, before any launch."""
     layout = byte_frame_layout(img)
@@ -1397,6 +1389,26 @@ def _byte_frame(img, what="img"):
                          f"(ops.byte_frame_layout), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))} with strides "
                          f"{tuple(img.stride()) if isinstance(img, torch.Tensor) else None}; call .contiguous() on it")
     return layout
+
+
+def _frame_route(img, what="img"):
+    """Which of a pass's three entry points reads the frame tensor img, and what follows the frame's pointer in its arguments: ("", ())
+    for fp32, ("_u8", ()) for contiguous bytes, ("_hwc", (sb, sy, sx)) for an hwc view; ValueError for bytes in any other layout
+    (_byte_frame).  A function of dtype, shape, strides and storage size alone: no device is asked."""
+    if img.dtype != torch.uint8:
+        return "", ()
+    layout = _byte_frame(img, what)
+    return ("_u8", ()) if layout[0] == "planar" else ("_hwc", layout[1:])
+
+
+def _frame_args(img, strides):
+    """The frame's leading arguments of the entry point _frame_route chose: the device pointer and the strides of an hwc view (which is
+    not contiguous, as hip.ptr asks of every other tensor)."""
+    if not strides:
+        return (hip.ptr(img),)
+    if not img.is_cuda:
+        raise hip.HipLibraryError("fovealseg kernels need device tensors (got a CPU tensor); there is no CPU path")
+    return (img.data_ptr(),) + strides
 
 
 def byte_frame_select(img, sel):
@@ -1418,14 +1430,11 @@ def gaze_lowres(x, focus, hs, ws):
     B, C, H, W = x.shape
     assert C == 3
     out = torch.empty(B, hs, ws, 5, device=x.device, dtype=torch.float32)
-    if x.dtype == torch.uint8 and not x.is_contiguous():    # an interleaved frame of bytes, read where it lies
-        _launch("fe_gaze_lowres_hwc", 1.0 * B * hs * ws * (12 + 20), "fs_gaze_lowres_hwc_fwd", *_hwc_args(x, _byte_frame(x, "x")),
-                hip.ptr(focus), hip.ptr(out), B, H, W, hs, ws)
-        return out
-    if x.dtype == torch.uint8:                          # a frame of bytes: four one-byte taps a channel, 12 bytes read and 20 written a point
-        _launch("fe_gaze_lowres_u8", 1.0 * B * hs * ws * (12 + 20), "fs_gaze_lowres_u8_fwd", hip.ptr(x), hip.ptr(focus), hip.ptr(out), B, H, W, hs, ws)
-        return out
-    _launch("fe_gaze_lowres", 4.0 * B * hs * ws * (4 * 3 + 5), "fs_gaze_lowres_fwd", hip.ptr(x), hip.ptr(focus), hip.ptr(out), B, H, W, hs, ws)
+    suffix, strides = _frame_route(x, "x")
+    # a frame of bytes, planar or read where it lies interleaved: four one-byte taps a channel, 12 bytes read and 20 written a point
+    traffic = (12 + 20) if suffix else 4 * (4 * 3 + 5)
+    _launch("fe_gaze_lowres" + suffix, 1.0 * B * hs * ws * traffic, f"fs_gaze_lowres{suffix}_fwd", *_frame_args(x, strides), hip.ptr(focus),
+            hip.ptr(out), B, H, W, hs, ws)
     return out
 
 
@@ -1597,14 +1606,13 @@ def grid_sample_u8(x, grid):
     if grid.dim() != 4 or grid.shape[0] != B or grid.shape[3] != 2 or grid.numel() == 0 or grid.dtype != torch.float32:
         raise ValueError(f"grid must be a non-empty fp32 ({B},h,w,2), got {grid.dtype} {tuple(grid.shape)}")
     h, w = int(grid.shape[1]), int(grid.shape[2])
-    if not x.is_contiguous():                           # an interleaved frame (three channels), read where it lies: one address a tap
-        layout = _byte_frame(x, "x")
-        out = torch.empty(B, h, w, C, device=x.device, dtype=torch.float32)
-        _launch("fe_grid_sample_hwc_fwd", 1.0 * B * h * w * (4 * C + 8 + 4 * C), "fs_grid_sample_hwc_fwd", *_hwc_args(x, layout), hip.ptr(grid),
-                hip.ptr(out), B, H, W, h, w, 1)
-        return out
     out = torch.empty(B, h, w, C, device=x.device, dtype=torch.float32)
-    _launch("fe_grid_sample_u8_fwd", 1.0 * B * h * w * (4 * C + 8 + 4 * C), "fs_grid_sample_u8_fwd", hip.ptr(x), hip.ptr(grid), hip.ptr(out), B, C, H, W, h, w, 1)
+    traffic = 1.0 * B * h * w * (4 * C + 8 + 4 * C)
+    if x.is_contiguous():                               # any C
+        _launch("fe_grid_sample_u8_fwd", traffic, "fs_grid_sample_u8_fwd", hip.ptr(x), hip.ptr(grid), hip.ptr(out), B, C, H, W, h, w, 1)
+    else:                                               # an interleaved frame (three channels), read where it lies: one address a tap
+        _, strides = _frame_route(x, "x")
+        _launch("fe_grid_sample_hwc_fwd", traffic, "fs_grid_sample_hwc_fwd", *_frame_args(x, strides), hip.ptr(grid), hip.ptr(out), B, H, W, h, w, 1)
     return out
 
 
@@ -2367,7 +2375,7 @@ def _gate_tile(T):
     return int(T)
 
 
-def _gate_tiles(name, dtype, img, key, tile, out):
+def _gate_tiles(dtype, img, key, tile, out):
     T = _gate_tile(tile)
     what = "fp32" if dtype == torch.float32 else "uint8"
     if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
@@ -2375,17 +2383,13 @@ def _gate_tiles(name, dtype, img, key, tile, out):
     if key.dtype != torch.uint8 or key.shape != img.shape:
         raise ValueError(f"key must be uint8 {tuple(img.shape)}, got {key.dtype} {tuple(key.shape)}")
     B, _, H, W = (int(v) for v in img.shape)
-    if dtype == torch.uint8 and not img.is_contiguous():
-        hwc = _hwc_args(img, _byte_frame(img))
+    suffix, strides = _frame_route(img)
     shape = (B, (H + T - 1) // T, (W + T - 1) // T)
     if out is None:
         out = torch.empty(shape, device=img.device, dtype=torch.int32)
     elif out.dtype != torch.int32 or tuple(out.shape) != shape:
         raise ValueError(f"out must be int32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    if dtype == torch.uint8 and not img.is_contiguous():
-        hip.call("fs_gate_tiles_hwc", *hwc, hip.ptr(key), hip.ptr(out), B, H, W, T)
-    else:
-        hip.call(name, hip.ptr(img), hip.ptr(key), hip.ptr(out), B, H, W, T)
+    hip.call("fs_gate_tiles" + suffix, *_frame_args(img, strides), hip.ptr(key), hip.ptr(out), B, H, W, T)
     return out
 
 
@@ -2394,14 +2398,14 @@ def gate_tiles(img, key, tile=32, out=None):
     no counterpart).  img (B,3,H,W) fp32, key (B,3,H,W) uint8 = q of the frames the records were made from, q(v) = rint(clamp(v, 0, 1) *
     255) in fp32, NaN -> 0.  Returns sad (B,th,tw) int32, th = ceil(H / tile), tw = ceil(W / tile): the sum of |q(img) - key| over the
     three channels and the tile's pixels (the last tiles are ragged).  out: a (B,th,tw) int32 tensor to write into."""
-    return _gate_tiles("fs_gate_tiles", torch.float32, img, key, tile, out)
+    return _gate_tiles(torch.float32, img, key, tile, out)
 
 
 def gate_tiles_u8(img, key, tile=32, out=None):
     """gate_tiles for frames of bytes (fs_gate_tiles_u8): img (B,3,H,W) uint8, the pixel value byte / 255, whose code q is the byte.  sad
     is the sum of |img - key|, equal to gate_tiles(img.float() / 255, key, tile); 6 bytes read a pixel instead of 15.  img is contiguous,
     or an hwc view of interleaved bytes (byte_frame_layout; fs_gate_tiles_hwc), read where it lies; ValueError for any other layout."""
-    return _gate_tiles("fs_gate_tiles_u8", torch.uint8, img, key, tile, out)
+    return _gate_tiles(torch.uint8, img, key, tile, out)
 
 
 def gate_decide(sad, gstate, focus, stats, bits, frame_size, tile=32, level=8, scene_tiles=0, roi_tiles=0, margin=16,
@@ -2439,14 +2443,14 @@ def gate_decide(sad, gstate, focus, stats, bits, frame_size, tile=32, level=8, s
     return out
 
 
-def _gate_commit(name, dtype, img, idx, key, gstate, focus, src, dst):
+def _gate_commit(dtype, img, idx, key, gstate, focus, src, dst):
     what = "fp32" if dtype == torch.float32 else "uint8"
     if (not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype
             or key.dtype != torch.uint8 or key.shape != img.shape):
         raise ValueError(f"img must be a non-empty {what} (B,3,H,W) and key uint8 of its shape, got {getattr(img, 'dtype', None)} "
                          f"{tuple(getattr(img, 'shape', ()))} and {tuple(key.shape)}")
     B, _, H, W = (int(v) for v in img.shape)
-    hwc = _hwc_args(img, _byte_frame(img)) if dtype == torch.uint8 and not img.is_contiguous() else None
+    suffix, strides = _frame_route(img)
     n = 0 if idx is None else int(idx.shape[0])
     if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 1 or n > B):
         raise ValueError(f"idx must be int32 (n,) with n <= {B}, got {idx.dtype} {tuple(idx.shape)}")
@@ -2464,10 +2468,8 @@ def _gate_commit(name, dtype, img, idx, key, gstate, focus, src, dst):
             raise ValueError(f"a src record tensor must be {dt} {(n,) + tail}, got {s.dtype} {tuple(s.shape)}")
     sp = [hip.ptr(s) for s in src] + [None] * (5 - len(src))
     dp = [hip.ptr(d) for d in dst] + [None] * (5 - len(dst))
-    if hwc is not None:
-        hip.call("fs_gate_commit_hwc", *hwc, hip.ptr(idx), n, hip.ptr(key), hip.ptr(gstate), hip.ptr(focus), *sp, *dp, B, H, W, cap)
-        return
-    hip.call(name, hip.ptr(img), hip.ptr(idx), n, hip.ptr(key), hip.ptr(gstate), hip.ptr(focus), *sp, *dp, B, H, W, cap)
+    hip.call("fs_gate_commit" + suffix, *_frame_args(img, strides), hip.ptr(idx), n, hip.ptr(key), hip.ptr(gstate), hip.ptr(focus), *sp, *dp,
+             B, H, W, cap)
 
 
 def gate_commit(img, idx, key, gstate, focus, src, dst):
@@ -2476,14 +2478,14 @@ def gate_commit(img, idx, key, gstate, focus, src, dst):
     with B rows: row j moves to row idx[j]; a pair that is one tensor is already in place.  For the viewers of idx key (B,3,H,W) uint8
     <- q(img), g_key <- g, age <- 0, valid <- 1 in gstate (B,6) int64; for every viewer g_prev <- g; any other viewer's age grows by
     one.  With n = 0 src is not read (pass dst)."""
-    _gate_commit("fs_gate_commit", torch.float32, img, idx, key, gstate, focus, src, dst)
+    _gate_commit(torch.float32, img, idx, key, gstate, focus, src, dst)
 
 
 def gate_commit_u8(img, idx, key, gstate, focus, src, dst):
     """gate_commit for frames of bytes (fs_gate_commit_u8): img (B,3,H,W) uint8; for the viewers of idx key <- img, a copy.  Everything
     else as gate_commit, and equal to it on img.float() / 255.  img is contiguous, or an hwc view of interleaved bytes (byte_frame_layout;
     fs_gate_commit_hwc: the key takes the de-interleaved frame and stays planar); ValueError for any other layout."""
-    _gate_commit("fs_gate_commit_u8", torch.uint8, img, idx, key, gstate, focus, src, dst)
+    _gate_commit(torch.uint8, img, idx, key, gstate, focus, src, dst)
 
 
 MOTION_MAX_PX = 255                                 # fs_profile_shift's largest search range
@@ -2522,20 +2524,20 @@ def _profile_sizes(B, H, W):
     return (B, H + W)
 
 
-def _profiles(name, src, dtype, out):
+_PROFILE_ENTRY = {"": "fs_frame_profiles", "_u8": "fs_key_profiles", "_hwc": "fs_frame_profiles_hwc"}    # a planar frame of bytes is a key
+
+
+def _profiles(src, dtype, out):
     if not isinstance(src, torch.Tensor) or src.dim() != 4 or src.shape[1] != 3 or src.numel() == 0 or src.dtype != dtype:
         raise ValueError(f"the frames must be a non-empty {dtype} (B,3,H,W), got {getattr(src, 'dtype', None)} {tuple(getattr(src, 'shape', ()))}")
     B, _, H, W = (int(v) for v in src.shape)
-    hwc = _hwc_args(src, _byte_frame(src, "the frames")) if dtype == torch.uint8 and not src.is_contiguous() else None
+    suffix, strides = _frame_route(src, "the frames")
     shape = _profile_sizes(B, H, W)
     if out is None:
         out = torch.empty(shape, device=src.device, dtype=torch.int32)
     elif out.dtype != torch.int32 or tuple(out.shape) != shape:
         raise ValueError(f"out must be int32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    if hwc is not None:
-        hip.call("fs_frame_profiles_hwc", *hwc, hip.ptr(out), B, H, W)
-    else:
-        hip.call(name, hip.ptr(src), hip.ptr(out), B, H, W)
+    hip.call(_PROFILE_ENTRY[suffix], *_frame_args(src, strides), hip.ptr(out), B, H, W)
     return out
 
 
@@ -2543,14 +2545,14 @@ def frame_profiles(img, out=None):
     """The integral projections of frames (fs_frame_profiles; no autograd; unpinned: the reference has no counterpart).  img (B,3,H,W)
     fp32.  Returns prof (B, H + W) int32: prof[b, :H] = the row sums and prof[b, H:] = the column sums of the luma code L = q_r + q_g +
     q_b, q the gate's pixel code (gate_tiles).  out: a (B, H + W) int32 tensor to write into."""
-    return _profiles("fs_frame_profiles", img, torch.float32, out)
+    return _profiles(img, torch.float32, out)
 
 
 def key_profiles(key, out=None):
     """frame_profiles of 8-bit key frames (fs_key_profiles): key (B,3,H,W) uint8.  The profiles of a frame and of the key gate_commit
     made from it are equal.  A frame of bytes may also be an hwc view of interleaved bytes (byte_frame_layout; fs_frame_profiles_hwc), read
     where it lies; ValueError for any other non-contiguous layout."""
-    return _profiles("fs_key_profiles", key, torch.uint8, out)
+    return _profiles(key, torch.uint8, out)
 
 
 def profile_shift(prof, prof_key, gstate, frame_size, motion_px, motion_gain=6, out=None):
@@ -2582,11 +2584,11 @@ def state_shift_scratch(B, H, W, cap, device):
     return torch.empty(hip.query("fs_state_shift_scratch_ints", int(B), int(H), int(W), int(cap)), device=device, dtype=torch.int32)
 
 
-def _state_shift(entry, dtype, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch):
+def _state_shift(dtype, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch):
     if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
         raise ValueError(f"img must be a non-empty {'fp32' if dtype == torch.float32 else 'uint8'} (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
     B, _, H, W = (int(v) for v in img.shape)
-    hwc = _hwc_args(img, _byte_frame(img)) if dtype == torch.uint8 and not img.is_contiguous() else None
+    suffix, strides = _frame_route(img)
     _profile_sizes(B, H, W)
     P = (W + 31) // 32
     for name, k in (("key", key), ("key2", key2)):
@@ -2614,11 +2616,7 @@ def _state_shift(entry, dtype, img, shift, key, key2, bits, bits2, gstate, stats
         scratch = torch.empty(need, device=img.device, dtype=torch.int32)
     elif scratch.dtype != torch.int32 or scratch.dim() != 1 or scratch.numel() < need:
         raise ValueError(f"scratch must be int32 with at least {need} entries, got {scratch.dtype} {tuple(scratch.shape)}")
-    if hwc is not None:
-        entry, frame = "fs_state_shift_hwc", hwc
-    else:
-        frame = (hip.ptr(img),)
-    hip.call(entry, *frame, hip.ptr(shift), hip.ptr(key), hip.ptr(key2), hip.ptr(bits), hip.ptr(bits2), hip.ptr(gstate),
+    hip.call("fs_state_shift" + suffix, *_frame_args(img, strides), hip.ptr(shift), hip.ptr(key), hip.ptr(key2), hip.ptr(bits), hip.ptr(bits2), hip.ptr(gstate),
              hip.ptr(stats), hip.ptr(counts), hip.ptr(prof_key), hip.ptr(mstate), hip.ptr(motion), hip.ptr(scratch), B, H, W, cap)
     return motion
 
@@ -2631,14 +2629,14 @@ def state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_
     (B,6) int64 and counts (B,cap) int32 become mask_rle's of the moved bits; prof_key (B, H + W) int32 becomes key_profiles of the
     moved key; mstate (B,4) int64 = (dy_total, dx_total, moves, path) grows.  A still viewer's rows are not written.  Returns motion
     (B,6) int64 = (dy, dx, cost_best, cost_zero, dy_total, dx_total), written for every viewer.  scratch: state_shift_scratch(...)."""
-    return _state_shift("fs_state_shift", torch.float32, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch)
+    return _state_shift(torch.float32, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch)
 
 
 def state_shift_u8(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion=None, scratch=None):
     """state_shift for frames of bytes (fs_state_shift_u8): img (B,3,H,W) uint8; the key's uncovered border is filled with the frame's
     byte.  Everything else as state_shift, and equal to it on img.float() / 255; the scratch is the same.  img is contiguous, or an hwc
     view of interleaved bytes (byte_frame_layout; fs_state_shift_hwc); ValueError for any other layout."""
-    return _state_shift("fs_state_shift_u8", torch.uint8, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch)
+    return _state_shift(torch.uint8, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch)
 
 
 def motion_commit(idx, prof, prof_key, mstate, frame_size):

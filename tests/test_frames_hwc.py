@@ -124,6 +124,53 @@ def test_byte_frame_layout_of_stride_patterns():
         assert ops.byte_frame_layout(other) is None
 
 
+def test_frame_route_of_dtypes_and_stride_patterns():
+    """ops._frame_route: the entry-point suffix and the arguments after the frame's pointer that gate_tiles*, gate_commit*, frame_profiles /
+    key_profiles, state_shift*, gaze_lowres and grid_sample_u8 all take from it -- byte_frame_layout's rule, on CPU tensors: no device is
+    asked before the call."""
+    B, H, W = 3, 6, 8
+    u8 = lambda *s: torch.zeros(*s, dtype=torch.uint8)
+    hwc = lambda t: t.permute(0, 3, 1, 2)[:, :3]
+    pitch = W * 3 + 5
+    table = [
+        ("planar fp32", torch.zeros(B, 3, H, W), ("", ())),
+        ("planar uint8", u8(B, 3, H, W), ("_u8", ())),
+        ("tight RGB", hwc(u8(B, H, W, 3)), ("_hwc", (H * W * 3, W * 3, 3))),
+        ("RGBA [:, :3]", hwc(u8(B, H, W, 4)), ("_hwc", (H * W * 4, W * 4, 4))),
+        ("channels_last", u8(B, 3, H, W).contiguous(memory_format=torch.channels_last), ("_hwc", (H * W * 3, W * 3, 3))),
+        ("padded pitch", u8(B * H * pitch).as_strided((B, 3, H, W), (H * pitch, 1, pitch, 3)), ("_hwc", (H * pitch, pitch, 3))),
+        ("padded pitch, base one byte off", u8(1 + B * H * pitch).as_strided((B, 3, H, W), (H * pitch, 1, pitch, 3), 1), ("_hwc", (H * pitch, pitch, 3))),
+        ("a crop", hwc(u8(B, H + 5, W + 7, 4)[:, 2:2 + H, 3:3 + W]), ("_hwc", ((H + 5) * (W + 7) * 4, (W + 7) * 4, 4))),
+        ("sb == 0, expanded", hwc(u8(1, H, W, 3)).expand(B, 3, H, W), ("_hwc", (0, W * 3, 3))),
+        ("B == 1", hwc(u8(1, H, W, 3)), ("_hwc", (0, W * 3, 3))),
+        ("H == 1", hwc(u8(B, 1, W, 4)), ("_hwc", (W * 4, W * 4, 4))),
+        ("W == 1", hwc(u8(B, H, 1, 3)), ("_hwc", (H * 3, 3, 3))),
+        ("B == H == W == 1: contiguous", hwc(u8(1, 1, 1, 4)), ("_u8", ())),
+        # fp32 has one entry point: a view of it is refused at the call, by hip.ptr, as every non-contiguous tensor is
+        ("non-contiguous fp32", torch.zeros(B, 3, H, 2 * W)[:, :, :, ::2], ("", ())),
+        ("uint8 with sc != 1", u8(B, 3, H, 2 * W)[:, :, :, ::2], ValueError),
+        ("uint8, H and W transposed", u8(B, 3, W, H).transpose(2, 3), ValueError),
+        ("sx == 5", hwc(u8(B, H, W, 5)), ValueError),
+        ("images that overlap", u8(B * H * W * 3).as_strided((B, 3, H, W), (W * 3, 1, W * 3, 3)), ValueError),
+        ("ends short of its storage", u8(B * H * W * 4 - 1).as_strided((B, 3, H, W), (H * W * 4, 1, W * 4, 4)), ValueError),
+    ]
+    for name, t, want in table:
+        if want is ValueError:
+            with pytest.raises(ValueError):
+                ops._frame_route(t)
+            continue
+        assert ops._frame_route(t) == want, name
+        if t.dtype == torch.uint8:                                                         # the rule is byte_frame_layout's
+            assert ops.byte_frame_layout(t) == (("planar",) if want[0] == "_u8" else ("hwc",) + want[1]), name
+        with pytest.raises(hip.HipLibraryError):                                           # the device check stays at the call
+            ops._frame_args(t, want[1])
+    assert ops._PROFILE_ENTRY == {"": "fs_frame_profiles", "_u8": "fs_key_profiles", "_hwc": "fs_frame_profiles_hwc"}
+    for stem in ("fs_gate_tiles", "fs_gate_commit", "fs_state_shift"):
+        assert all(stem + suffix in hip.SIGNATURES for suffix in ("", "_u8", "_hwc"))
+    for stem in ("fs_gaze_lowres", "fs_grid_sample"):
+        assert all(f"{stem}{suffix}_fwd" in hip.SIGNATURES for suffix in ("", "_u8", "_hwc"))
+
+
 def test_deinterleaving_commutes_with_the_reference_passes():
     """The premise on the reference code: tiles, profiles and the border fill of an interleaved frame, computed on the bytes where they
     lie, are those of its de-interleaved copy -- whatever the alpha bytes and the pitch padding hold."""
@@ -468,6 +515,74 @@ def test_grid_sample_hwc(nhwc):
         x, gd = torch.from_numpy(planar).cuda(), torch.from_numpy(grid).cuda()
         view = x.contiguous(memory_format=torch.channels_last)
         assert not view.is_contiguous() and torch.equal(ops.grid_sample_u8(view, gd).view(torch.int32), ops.grid_sample_u8(x, gd).view(torch.int32))
+
+
+# ------------------------------------------------------------------------------------------------------------------ GPU: one frame, five layouts
+@pytest.mark.gpu
+@pytest.mark.parametrize("T_", [8, 16])
+@pytest.mark.parametrize("H,W", [(24, 64), (9, 37)])      # vector routes, a 16-pixel piece over two tiles at T = 8 | one-pixel routes, ragged tiles, a partial bit word
+def test_every_pass_agrees_across_the_five_layouts(H, W, T_):
+    """One random byte frame as fp32 (byte / 255), planar bytes, tight RGB, RGBA and RGB with a pitch of W * 3 + 5 from a base one byte off
+    (the one-pixel route at any W), through every op that reads a frame: all results torch.equal, the interleaved buffers unchanged."""
+    B, cap, hs, ws = 2, 16, 5, 7
+    gen = torch.Generator().manual_seed(H * 1009 + W * 7 + T_)
+    rnd = lambda *s: torch.randint(0, 256, s, generator=gen, dtype=torch.uint8)
+    planar = rnd(B, 3, H, W).cuda()
+    hwc_of = planar.permute(0, 2, 3, 1)
+    rgb_buf = hwc_of.contiguous()
+    rgba_buf = rnd(B, H, W, 4).cuda()
+    rgba_buf[..., :3] = hwc_of
+    pitch = W * 3 + 5
+    off_buf = rnd(1 + B * H * pitch).cuda()
+    off_view = off_buf.as_strided((B, 3, H, W), (H * pitch, 1, pitch, 3), 1)
+    off_view.copy_(planar)
+    frames = {"fp32": floats(planar), "planar": planar, "rgb": rgb_buf.permute(0, 3, 1, 2), "rgba": rgba_buf.permute(0, 3, 1, 2)[:, :3],
+              "pitch5 off1": off_view}
+    bufs = {"rgb": rgb_buf, "rgba": rgba_buf, "pitch5 off1": off_buf}
+    before = {k: v.clone() for k, v in bufs.items()}
+    want_route = 1 if W % 16 == 0 else 0
+    for name, want in (("rgb", want_route), ("rgba", want_route), ("pitch5 off1", 0)):     # each view runs the route it is there for
+        suffix, (sb, sy, sx) = ops._frame_route(frames[name])
+        assert suffix == "_hwc" and hip.load().fs_byte_frame_route(frames[name].data_ptr(), sb, sy, sx, W) == want, name
+    by_dtype = lambda f32_op, u8_op, x: f32_op if x.dtype == torch.float32 else u8_op
+
+    key = rnd(B, 3, H, W).cuda()
+    focus = torch.tensor([[0.2, 0.9], [0.5, 0.5]], device="cuda")
+    mask = np.zeros((H, W), dtype=bool)
+    mask[2:H - 2, W - 9:W - 1] = True                                                      # reaches the partial bit word at W = 37
+    bits = torch.from_numpy(np.stack([RLE.bits(mask), RLE.bits(mask[::-1].copy())])).cuda()
+    i64 = lambda *s: torch.randint(0, 16 * (min(H, W) - 1), s, generator=gen, dtype=torch.int64).cuda()
+    gstate, mstate, stats = i64(B, 6), i64(B, 4), i64(B, 6)
+    counts = torch.zeros(B, cap, dtype=torch.int32, device="cuda")
+    shift = torch.tensor([[1, -2, 11, 22], [-2, 1, 33, 44]], dtype=torch.int64, device="cuda")          # within motion_px = 2: 4 R < min(H, W) at H = 9
+    grid = (torch.rand(B, 6, 5, 2, generator=gen) * 2.2 - 1.1).cuda()
+    idx = torch.tensor([1], dtype=torch.int32, device="cuda")
+
+    results = {}
+    for name, x in frames.items():
+        out = {"tiles": by_dtype(ops.gate_tiles, ops.gate_tiles_u8, x)(x, key, T_)}
+        k, g = key.clone(), gstate.clone()
+        rec = (torch.zeros(B, dtype=torch.int64, device="cuda"), stats.clone(), counts.clone(), bits.clone())
+        by_dtype(ops.gate_commit, ops.gate_commit_u8, x)(x, idx, k, g, focus, rec, rec)
+        out["commit key"], out["commit gstate"] = k, g
+        out["profiles"] = by_dtype(ops.frame_profiles, ops.key_profiles, x)(x)
+        st = dict(key=key.clone(), bits=bits.clone(), gstate=gstate.clone(), stats=stats.clone(), counts=counts.clone(),
+                  prof_key=ops.key_profiles(key), mstate=mstate.clone())
+        out["motion"] = by_dtype(ops.state_shift, ops.state_shift_u8, x)(x, shift, st["key"], torch.zeros_like(key), st["bits"], torch.zeros_like(bits),
+                                                                         st["gstate"], st["stats"], st["counts"], st["prof_key"], st["mstate"])
+        out.update({"shift " + k_: v for k_, v in st.items()})
+        out["lowres"] = ops.gaze_lowres(x, focus, hs, ws)
+        out["sample"] = ops.GridSample.apply(x, grid) if x.dtype == torch.float32 else ops.grid_sample_u8(x, grid)
+        results[name] = out
+    torch.cuda.synchronize()
+    want = results["planar"]
+    assert bool(want["tiles"].any()) and not torch.equal(want["shift key"], key) and torch.equal(want["commit key"][1], planar[1])
+    assert torch.equal(want["commit key"][0], key[0]) and want["motion"][:, :2].tolist() == [[1, -2], [-2, 1]]
+    for name, got in results.items():
+        for what in want:
+            assert got[what].dtype == want[what].dtype and torch.equal(got[what], want[what]), (name, what)
+    for name, buf in bufs.items():
+        assert torch.equal(buf, before[name]), name
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU: refusals ---

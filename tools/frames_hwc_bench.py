@@ -10,13 +10,21 @@ changing every iteration:
     instances_planar / _rgb   module.predict_instances(frame, Fp, return_bits=True)
 
     python tools/frames_hwc_bench.py [--sizes 1:1024,64:1024] [--warmup 3] [--iters 10] [--parent-lib FILE.so] [--out FILE.json]
+    python tools/frames_hwc_bench.py --pass-ab --parent-lib FILE.so [--out FILE.json]      # every frame pass against the parent's, below
 
 Route figures are host wall time in ms, median (min - max) per round; a step ends with its own read-back, the other routes with a device
 synchronise.  "tiles" are device-event times over 20 back-to-back calls of the tile pass, alternated over three rounds, in microseconds a
 call, with the bytes each must read (planar and RGB 6 B a pixel, RGBA 7 B; the copy route reads 3 and writes 3 more) and the rate in
 TB/s on those bytes: (a) fs_gate_tiles_u8 on a planar frame, (b) permute().contiguous() followed by fs_gate_tiles_u8, and
-fs_gate_tiles_hwc on the RGB and the RGBA view (the vector route)."""
+fs_gate_tiles_hwc on the RGB and the RGBA view (the vector route).
+
+--pass-ab (for a change that must leave every pass as fast as it was; no network is built): every pass that reads a frame -- tiles,
+commit, profiles, state shift with every viewer moving, gaze_lowres, grid_sample_u8 -- on an fp32, a planar uint8, an RGB and an RGBA
+frame, B = 64, H = 1024, at W = 1024 (every vector route) and W = 1021 (every one-pixel route), through this tree's library and through
+--parent-lib: device-event time over 100 back-to-back calls in microseconds a call, one round of both libraries that is not kept, then
+three rounds in which the two alternate and the one that goes first changes; a row's ranges overlap or they do not."""
 import argparse
+import ctypes
 import json
 import os
 import random
@@ -44,13 +52,14 @@ def stats(v):
 
 
 class ParentLibrary:
-    """A library built from the parent commit, bound like this one's without the interleaved entry points; inside a `with` every
-    hip.call goes to it."""
+    """A library built from the parent commit, bound like this one's without those of the interleaved entry points it does not have;
+    inside a `with` every hip.call goes to it."""
 
     def __init__(self, path):
         own_lib, own_path, own_env = hip._lib, hip.LIB_PATH, os.environ.get("FS_HIP_LIB")
-        new = {k: hip.SIGNATURES.pop(k) for k in NEW}
-        new_host = {k: hip.HOST_ONLY.pop(k) for k in NEW_HOST}
+        has = ctypes.CDLL(path)
+        new = {k: hip.SIGNATURES.pop(k) for k in NEW if not hasattr(has, k)}
+        new_host = {k: hip.HOST_ONLY.pop(k) for k in NEW_HOST if not hasattr(has, k)}
         os.environ["FS_HIP_LIB"], hip.LIB_PATH, hip._lib = path, path, None
         try:
             self.lib = hip.load()
@@ -112,6 +121,68 @@ def tile_pass(B, side, tile=32, rounds=3):
             "rgba_beats_copy_outside_the_spread": spread("rgba")[1] < spread("copy")[0]}
 
 
+def frame_passes(B, H, W):
+    """layout -> pass -> a call of the op on tensors of its own."""
+    g = torch.Generator(device="cuda").manual_seed(B * 7 + W)
+    rnd = lambda *s: torch.randint(0, 256, s, device="cuda", dtype=torch.uint8, generator=g)
+    U, key = rnd(B, 3, H, W), rnd(B, 3, H, W)
+    rgb, rgba = views(U)
+    P, cap = (W + 31) // 32, 64
+    focus = torch.rand(B, 2, device="cuda")
+    idx = torch.arange(B, dtype=torch.int32, device="cuda")
+    i64 = lambda *s: torch.zeros(*s, dtype=torch.int64, device="cuda")
+    i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device="cuda")
+    shift = i64(B, 4)
+    shift[:, 0], shift[:, 1] = 3, -5
+    grid = torch.rand(B, 256, 256, 2, device="cuda") * 2 - 1
+    calls = {}
+    for name, x in {"fp32": (U.cpu().float() / 255).cuda(), "planar": U, "rgb": rgb, "rgba": rgba}.items():
+        f32 = x.dtype == torch.float32
+        tiles, commit, profiles, move = ((ops.gate_tiles, ops.gate_commit, ops.frame_profiles, ops.state_shift) if f32 else
+                                         (ops.gate_tiles_u8, ops.gate_commit_u8, ops.key_profiles, ops.state_shift_u8))
+        sad, prof = i32(B, (H + 31) // 32, (W + 31) // 32), i32(B, H + W)
+        k, k2, bits, bits2 = key.clone(), key.clone(), i32(B, H, P), i32(B, H, P)
+        bits[:, H // 4:H // 2, 1:P - 1] = -1
+        rec = (i64(B), i64(B, 6), i32(B, cap), bits.clone())
+        st = (i64(B, 6), i64(B, 6), i32(B, cap), ops.key_profiles(key), i64(B, 4), i64(B, 6), ops.state_shift_scratch(B, H, W, cap, "cuda"))
+        gstate = i64(B, 6)
+        calls[name] = {"tiles": lambda x=x, sad=sad, tiles=tiles: tiles(x, key, 32, out=sad),
+                       "commit": lambda x=x, k=k, gstate=gstate, rec=rec, commit=commit: commit(x, idx, k, gstate, focus, rec, rec),
+                       "profiles": lambda x=x, prof=prof, profiles=profiles: profiles(x, out=prof),
+                       "shift": lambda x=x, k=k, k2=k2, bits=bits, bits2=bits2, st=st, move=move: move(x, shift, k, k2, bits, bits2, *st),
+                       "lowres": lambda x=x: ops.gaze_lowres(x, focus, 256, 256)}
+        if not f32:
+            calls[name]["sample"] = lambda x=x: ops.grid_sample_u8(x, grid)
+    return calls
+
+
+def pass_ab(parent, out):
+    def timed(who, fn):
+        if who == "new":
+            return round(event_us(fn, 100), 2)
+        with parent:
+            return round(event_us(fn, 100), 2)
+    res = []
+    for B, H, W in ((64, 1024, 1024), (64, 1024, 1021)):
+        calls, rows = frame_passes(B, H, W), {}
+        for rnd in range(-1, 3):                         # round -1 is not kept
+            for name, of_layout in calls.items():
+                for what, fn in of_layout.items():
+                    order = ("new", "parent") if rnd % 2 == 0 else ("parent", "new")
+                    timed(order[1], fn)                  # not kept: whoever goes first follows the other library's run of the same pass
+                    for who in order:
+                        t = timed(who, fn)
+                        if rnd >= 0:
+                            rows.setdefault((name, what), {"new": [], "parent": []})[who].append(t)
+        for (name, what), r in rows.items():
+            res.append({"B": B, "H": H, "W": W, "layout": name, "pass": what, "new_us": r["new"], "parent_us": r["parent"],
+                        "ranges_overlap": min(r["new"]) <= max(r["parent"]) and min(r["parent"]) <= max(r["new"])})
+            print(json.dumps(res[-1]), flush=True)
+    if out:
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="1:1024,64:1024", help="batch:side pairs")
@@ -121,9 +192,13 @@ def main():
     ap.add_argument("--motion-px", type=int, default=16)
     ap.add_argument("--parent-lib", default=None)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--pass-ab", action="store_true", help="every frame pass, this library against --parent-lib, and nothing else")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "frames_hwc_bench measures on the GPU"
     hip.load()
+    if args.pass_ab:
+        assert args.parent_lib, "--pass-ab compares with --parent-lib"
+        return pass_ab(ParentLibrary(args.parent_lib), args.out)
     module, _ = T.build_module(fovealseg.lvis50_cfg(), device="cuda")
     module.eval()
     ops.static_weight_packs(module)
