@@ -53,6 +53,25 @@ __device__ __forceinline__ void hwc_split4(unsigned int d0, unsigned int d1, uns
   b = hwc_perm(v1, v0, hwc_sel(0, 1, 4, 5));
 }
 
+// The inverses, for a pass that writes a frame (frame_overlay.hip): one dword a channel, pixel j in byte j -> four pixels of interleaved
+// bytes.  RGB: d0 = r0 g0 b0 r1, d1 = g1 b1 r2 g2, d2 = b2 r3 g3 b3; R and G meet first, B fills its bytes: two perms a dword.
+__device__ __forceinline__ void hwc_join3(unsigned int r, unsigned int g, unsigned int b, unsigned int& d0, unsigned int& d1,
+                                          unsigned int& d2) {
+  d0 = hwc_perm(b, hwc_perm(g, r, hwc_sel(0, 4, 0, 1)), hwc_sel(0, 1, 4, 3));
+  d1 = hwc_perm(b, hwc_perm(g, r, hwc_sel(5, 0, 2, 6)), hwc_sel(0, 5, 2, 3));
+  d2 = hwc_perm(b, hwc_perm(g, r, hwc_sel(0, 3, 7, 0)), hwc_sel(6, 1, 2, 7));
+}
+// RGBA: a dword a pixel, its fourth byte 255.  R G pairs and B 255 pairs, then a pixel from each: eight perms.
+__device__ __forceinline__ void hwc_join4(unsigned int r, unsigned int g, unsigned int b, unsigned int& d0, unsigned int& d1,
+                                          unsigned int& d2, unsigned int& d3) {
+  const unsigned int u0 = hwc_perm(g, r, hwc_sel(0, 4, 1, 5)), u1 = hwc_perm(g, r, hwc_sel(2, 6, 3, 7));          // R G R G
+  const unsigned int v0 = hwc_perm(0xffffffffu, b, hwc_sel(0, 4, 1, 4)), v1 = hwc_perm(0xffffffffu, b, hwc_sel(2, 4, 3, 4));      // B 255 B 255
+  d0 = hwc_perm(v0, u0, hwc_sel(0, 1, 4, 5));
+  d1 = hwc_perm(v0, u0, hwc_sel(2, 3, 6, 7));
+  d2 = hwc_perm(v1, u1, hwc_sel(0, 1, 4, 5));
+  d3 = hwc_perm(v1, u1, hwc_sel(2, 3, 6, 7));
+}
+
 // Four codes from one aligned load, added to l: 16 bytes of fp32, 4 of bytes.
 __device__ __forceinline__ void code4(const float* p, int* l) {
   const f32x4 v = *reinterpret_cast<const f32x4*>(p);
@@ -168,6 +187,75 @@ struct HwcFrame {
   bool wide(int W) const { return route(W) == 1; }
   bool wide_commit(int W, size_t) const { return wide(W); }
   bool quad(int W) const { return wide(W); }
+};
+
+// A frame a pass can write (frame_overlay.hip): always bytes, described by (p, ob, oy, ox).  ox = 1, planar: the byte of channel c at
+// (b, y, x) is p[b * ob + c * H * W + y * W + x], oy == W, images ob >= 3 * H * W apart.  ox = 3 or 4, interleaved: p[b * ob + y * oy + x *
+// ox + c], rows of any pitch oy >= W * ox, images ob >= H * oy apart; the fourth byte of an RGBA pixel is written as 255.  OX = 1, 3 or 4
+// where the pass knows the step at compile time (the vector forms), 0 for the ox given at run time (the one-pixel forms).  A pixel is
+// stored as three or four bytes, sixteen pixels of a row -- sixteen bytes a channel in planar order, what a reader's load16 gives -- as
+// three or four 16-byte pieces: stored by their lane (store16), or joined (join16) for a pass that lets other lanes store them (piece).
+template <int OX>
+struct FrameWriter {
+  unsigned char* p;
+  long ob, oy;
+  int ox;
+  size_t plane;
+  __host__ __device__ FrameWriter(unsigned char* p_, long ob_, long oy_, int ox_, int H, int W) : p(p_), ob(ob_), oy(oy_), ox(ox_), plane((size_t)H * W) {}
+
+  __device__ __forceinline__ int step() const { return OX > 0 ? OX : ox; }
+  __device__ __forceinline__ void store1(size_t b, int y, int x, int r, int g, int bl) const {
+    if (step() == 1) {
+      unsigned char* a = p + b * (size_t)ob + (size_t)y * oy + x;
+      a[0] = (unsigned char)r, a[plane] = (unsigned char)g, a[2 * plane] = (unsigned char)bl;
+    } else {
+      unsigned char* a = p + b * (size_t)ob + (size_t)y * oy + (size_t)x * step();
+      a[0] = (unsigned char)r, a[1] = (unsigned char)g, a[2] = (unsigned char)bl;
+      if (step() == 4) a[3] = 255;
+    }
+  }
+  // where pixel (b, y, x) of an interleaved destination begins (channel 0 of a planar one)
+  __device__ __forceinline__ unsigned char* piece(size_t b, int y, int x) const { return p + b * (size_t)ob + (size_t)y * oy + (size_t)x * step(); }
+  // Sixteen pixels, v[c][q] = pixels 4q .. 4q + 3 of channel c, pixel j in byte j, as the OX = 3 or 4 16-byte pieces they are in memory
+  __device__ __forceinline__ void join16(const unsigned int (*v)[4], u32x4* m) const {
+    if (OX == 3) {
+      unsigned int d[12];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) hwc_join3(v[0][q], v[1][q], v[2][q], d[3 * q], d[3 * q + 1], d[3 * q + 2]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) m[i] = u32x4{d[4 * i], d[4 * i + 1], d[4 * i + 2], d[4 * i + 3]};
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        unsigned int d0, d1, d2, d3;
+        hwc_join4(v[0][q], v[1][q], v[2][q], d0, d1, d2, d3);
+        m[q] = u32x4{d0, d1, d2, d3};
+      }
+    }
+  }
+  // the sixteen pixels stored by their own lane; x a multiple of 16 and the address 16-byte aligned (wide)
+  __device__ __forceinline__ void store16(size_t b, int y, int x, const unsigned int (*v)[4]) const {
+    if (OX == 1) {
+      unsigned char* a = piece(b, y, x);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) *reinterpret_cast<u32x4*>(a + c * plane) = u32x4{v[c][0], v[c][1], v[c][2], v[c][3]};
+    } else {
+      u32x4 m[OX > 1 ? OX : 1];
+      join16(v, m);
+      u32x4* a = reinterpret_cast<u32x4*>(piece(b, y, x));
+#pragma unroll
+      for (int i = 0; i < OX; ++i) a[i] = m[i];
+    }
+  }
+
+  // the description can be written: the pointer, the pixel step, the pitch and an image step that keeps B images apart
+  bool ok(int B, int H, int W) const {
+    if (p == nullptr || B < 1 || H < 1 || W < 1 || ob < 0) return false;
+    if (ox == 1) return oy == W && (B == 1 || ob >= 3 * (long)H * W);
+    return (ox == 3 || ox == 4) && oy >= (long)W * ox && (B == 1 || ob >= (long)H * oy);
+  }
+  // every 16-pixel piece of every row (and plane) starts at a multiple of 16 bytes: HwcFrame::route's conditions, or aligned planes
+  bool wide(int W) const { return W % 16 == 0 && ((uintptr_t)p & 15) == 0 && oy % 16 == 0 && ob % 16 == 0; }
 };
 
 }  // namespace

@@ -77,6 +77,10 @@ SIGNATURES = {
     "fs_gate_commit_hwc": "plli" + "p" + "i" + "p" * 13 + "iiii",
     "fs_frame_profiles_hwc": "plli" + "p" + "iii",
     "fs_state_shift_hwc": "plli" + "p" * 12 + "iiii",
+    "fs_frame_overlay": "p" + "ppppp" + "l" + "pi" + "plli" + "iii",
+    "fs_frame_overlay_u8": "p" + "ppppp" + "l" + "pi" + "plli" + "iii",
+    "fs_frame_overlay_hwc": "plli" + "ppppp" + "l" + "pi" + "plli" + "iii",
+    "fs_color_encode": "pp" + "plli" + "iiii",
     "fs_conv2d_fwd": "ppppiiiiiiiiiiiifuplp",
     "fs_conv2d_fwd_residual": "ppppp" + "iiiiiiiiiiii" + "fufu" + "l" + "plp",
     "fs_conv2d_fwd_stats": "pppppiiiiiiiiiiiifuplp",

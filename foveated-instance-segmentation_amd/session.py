@@ -145,6 +145,38 @@ class GazeSession:
         elif viewers:
             self._gstate[torch.tensor(viewers, device=self._dev), 0] = 0
 
+    @torch.no_grad()
+    def render(self, img, focus=None, style=None, outline_px=0, out=None):
+        """Every viewer's current record drawn onto img, in one launch (ops.draw_instances; unpinned).  img (B,3,H,W) as step() takes it --
+        fp32, uint8, or a uint8 view of interleaved bytes, read where it lies -- usually the frame just stepped.  The session's bits and
+        stats are drawn as they stand after the last step, any motion_px move included; a viewer without a record (before its first step,
+        after reset()) is drawn empty: column 0 of the gate's state is the kernel's live flag, read on the device.  focus (B,2) adds the
+        gaze marker of the style; style is ops.overlay_style's table (None: its defaults); outline_px = d > 0 outlines the mask with the
+        band bits & ~E_d(bits).  out: a uint8 (B,3,H,W) tensor, contiguous or an interleaved view (ops.byte_frame_dest), img itself for a
+        frame of bytes; None: a new contiguous one.  With out given and outline_px = 0 nothing is allocated (after the first call, which
+        makes the default style); with an outline the band and its scratch are made at the first call and kept.  No host read; step() is
+        untouched.  Returns out.  RuntimeError before the first step."""
+        B, H, W = self.batch, self.H, self.W
+        if self._dev is None:
+            raise RuntimeError("GazeSession.render() draws the records step() made: call step() first")
+        if not isinstance(img, torch.Tensor) or tuple(img.shape) != (B, 3, H, W) or img.dtype not in (torch.float32, torch.uint8):
+            raise ValueError(f"img must be fp32 or uint8 {(B, 3, H, W)}, got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
+        if img.device != self._dev:
+            raise ValueError(f"the session lives on {self._dev}, img is on {img.device}")
+        if style is None:
+            style = getattr(self, "_style", None)
+            if style is None:
+                style = self._style = ops.overlay_style(device=self._dev)
+        bits, band = self._rec[3], None
+        d = ops._int_ge_zero("outline_px", outline_px)
+        if d > 0:
+            kept = getattr(self, "_band", None)
+            if kept is None or kept[0] != d:
+                scratch = torch.empty(max(1, ops.hip.query("fs_mask_erode_scratch_ints", B, H, W, ops._morph_d(d))), device=self._dev, dtype=torch.int32)
+                kept = self._band = (d, torch.empty_like(bits), torch.empty_like(bits), scratch)
+            band = ops.overlay_band(bits, W, d, er=kept[2], scratch=kept[3], band=kept[1])[0]
+        return ops.draw_instances(img, bits, stats=self._rec[1], focus=focus, style=style, out=out, live=self._gstate[:, 0], band=band)
+
     def _force(self, force, dev):
         if force is None:
             return None

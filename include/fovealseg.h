@@ -525,6 +525,62 @@ int fs_frame_profiles_hwc(const unsigned char* img, long sb, long sy, int sx, in
 int fs_state_shift_hwc(const unsigned char* img, long sb, long sy, int sx, const long long* shift, unsigned char* key, unsigned char* key2,
                        unsigned int* bits, unsigned int* bits2, long long* gstate, long long* stats, int* counts, int* prof_key,
                        long long* mstate, long long* motion, int* scratch, int B, int H, int W, int cap, fs_stream_t stream);
+/* Showing the record: the gazed instance drawn onto the frame (UNPINNED, a definition of this library's).  The reference
+ * visualises on the host, with matplotlib, PIL and numpy (eval.py:70-83 visualize_result, utils.py:207-221 colorEncode, the TensorBoard
+ * panels of models/models.py); this replaces what a caller composed from torch shifts, torch.where, an fp32 blend and permute().contiguous().
+ * All integers.  For viewer b and pixel (y, x), s_c = the source pixel's code in channel c (fs_gate_tiles' q of an fp32 value, the byte
+ * itself of a byte source); out_c is the first of these that applies:
+ *   1 marker   r > 0, d2 = (y-py)^2 + (x-px)^2 <= r^2 and d2 >= max(r - w, 0)^2 -> the marker colour; (py, px) is fs_mask_component's gaze
+ *              pixel (1/16-pixel units, NaN -> 0, clamped); w >= r gives a disc, a smaller w a ring.
+ *   2 box      t > 0, the record's box (x0, y0, bw, bh) = stats[b, 1:5] has bw > 0, bh > 0 and contains (y, x), and x - x0 < t, x0 + bw - 1 -
+ *              x < t, y - y0 < t or y0 + bh - 1 - y < t (within t pixels of a side, measured inward) -> the box colour.  The stats values
+ *              are compared as integers only and never form an address: any int64 is defined, the sums taken without overflow.
+ *   3 outline  the outline flag is on and the pixel's bit in band is set -> the outline colour.
+ *   4 mask     the pixel's bit in bits is set -> (s_c * (256 - a) + tint_c * a + 128) >> 8.
+ *   5 else     (s_c * dim + 128) >> 8: dim = 256 leaves the pixel as it is, a smaller dim darkens what the viewer does not look at.
+ * bits, band (B,H,P), P = ceil(W/32), as fs_mask_bits lays them out (the bits at x >= W are never read as pixels); band is meant to be
+ * bits & ~E_d(bits), E_d fs_mask_erode's, and is only read.  band, stats and focus are nullable: a null one switches its element off.
+ * live is nullable, int64, read as live[b * live_stride]: where it is 0 the viewer's mask, band and box count as empty, the marker and
+ * dim still apply (GazeSession passes column 0 of its gstate (B,6) as it lies, live_stride = 6).  style (S,20) int32 on the device, S = 1
+ * (every viewer) or S = B (a row a viewer): columns 0-2 tint r g b, 3 a, 4-6 outline r g b, 7 dim, 8-10 box r g b, 11 t, 12-14 marker r g
+ * b, 15 r, 16 w, 17 the outline flag, 18-19 reserved; every entry is clamped by the kernel (colours to 0 .. 255, a and dim to 0 .. 256, t,
+ * r, w to 0 .. 16384) and none forms an address.
+ * The destination is always bytes, (out, ob, oy, ox): ox = 1 planar, the byte of channel c at (b, y, x) is out[b * ob + c * H * W + y * W + x],
+ * oy == W, ob >= 3 * H * W; ox = 3 or 4 interleaved, out[b * ob + y * oy + x * ox + c], oy >= W * ox, ob >= H * oy, and for ox = 4 the fourth
+ * byte is written as 255 (ob is not looked at for B = 1).  One launch; every output byte is written once by a plain store: no atomics, no
+ * host read, nothing to zero; the source is never written unless it is out.  out == img is allowed where source and destination have the
+ * same description (planar bytes both, or equal sb, sy, sx): each workgroup reads its pixels before it stores them, and owns them alone.
+ * fs_frame_overlay: img (B,3,H,W) fp32 NCHW, 12 bytes read and 3 or 4 written a pixel; sixteen pixels a lane (twelve 16-byte loads)
+ * where W % 16 == 0, img is 16-byte aligned and the destination's pieces are as fs_frame_overlay_u8 asks, one otherwise.  FS_ERR_ARG, with nothing
+ * launched, for a null img, bits, style or out, S outside {1, B}, non-positive sizes, a side above 16384, H * W >= 2^31, ox outside {1, 3,
+ * 4}, a pitch or image step too small (ob = 0 with B > 1 among them), out == img with differing descriptions, live_stride < 1 with live
+ * given. */
+int fs_frame_overlay(const float* img, const unsigned int* bits, const unsigned int* band, const long long* stats, const float* focus,
+                     const long long* live, long live_stride, const int* style, int S, unsigned char* out, long ob, long oy, int ox, int B,
+                     int H, int W, fs_stream_t stream);
+/* fs_frame_overlay on planar bytes (B,3,H,W).  Sixteen pixels a lane where W % 16 == 0, img is 16-byte aligned and the destination's
+ * sixteen-pixel pieces are (out, oy and ob multiples of 16): three 16-byte loads, a half word of bits and of band, and three 16-byte
+ * stores for a planar destination, or the sixteen pixels re-interleaved with v_perm_b32 (6 perms four RGB pixels, 8 four RGBA pixels) into
+ * three or four 16-byte pieces, which a workgroup lays down in LDS in memory order so that neighbouring lanes store neighbouring
+ * pieces.  One pixel a lane otherwise. */
+int fs_frame_overlay_u8(const unsigned char* img, const unsigned int* bits, const unsigned int* band, const long long* stats,
+                        const float* focus, const long long* live, long live_stride, const int* style, int S, unsigned char* out, long ob,
+                        long oy, int ox, int B, int H, int W, fs_stream_t stream);
+/* fs_frame_overlay_u8 on an interleaved frame (img, sb, sy, sx), read where it lies; also FS_ERR_ARG for a description fs_gate_tiles_hwc
+ * refuses.  Sixteen pixels a lane on route 1 of fs_byte_frame_route and a destination as above: the lane's 48 or 64 bytes are split into
+ * planar order in registers as fs_gate_tiles_hwc splits them, and joined again for an interleaved destination -- camera RGBA in, display
+ * RGBA out is 4 bytes read and 4 written a pixel.  One pixel a lane otherwise. */
+int fs_frame_overlay_hwc(const unsigned char* img, long sb, long sy, int sx, const unsigned int* bits, const unsigned int* band,
+                         const long long* stats, const float* focus, const long long* live, long live_stride, const int* style, int S,
+                         unsigned char* out, long ob, long oy, int ox, int B, int H, int W, fs_stream_t stream);
+/* A class map as colours: utils.py:207-221 colorEncode(labelmap, colors, mode='RGB') for fs_unwarp_labels' map.  labels (B,H,W) int64,
+ * palette (K,3) bytes; out, described as fs_frame_overlay's destination, = palette[label], (0, 0, 0) for a label < 0 or >= K.  The
+ * reference skips negative labels, which leaves its zeros, and would raise an IndexError on a label >= K: black there is this library's
+ * choice.  A label forms an address only inside the palette.  Sixteen labels a lane where the destination's sixteen-pixel pieces and
+ * labels are 16-byte aligned, one otherwise; plain stores, the same writer.  FS_ERR_ARG, with nothing launched, for a null pointer, K < 1,
+ * and as fs_frame_overlay for the sizes and the destination. */
+int fs_color_encode(const long long* labels, const unsigned char* palette, unsigned char* out, long ob, long oy, int ox, int B, int H, int W,
+                    int K, fs_stream_t stream);
 /* u=int((gx+1)/2*(W-1)), v=int((gy+1)/2*(H-1)) for n grid points.  models/models.py:644-645. */
 int fs_inverse_index_maps(const float* grid, long long* u, long long* v, long n, int H, int W, fs_stream_t stream);
 
