@@ -147,14 +147,3 @@ int fs_slab_reduce(const float* part, int nslab, long n, float* out, int accumul
 int fs_slab_reduce_inplace(float* part, int nslab, long n, float* out, int accumulate, hipStream_t stream);
 // two sums of equal shape in one launch (a wave per column: meant for n up to a few thousand)
 int fs_slab_reduce_pair(const float* part0, const float* part1, int nslab, long n, float* out0, float* out1, int accumulate, hipStream_t stream);
-
-// mask_component.hip: the sizes of fs_mask_component and its two passes, for the callers that compose it (unwarp.hip).  ok = launchable
-// (positive sizes, sides <= 16384, Hs * Ws < 2^31); scratch in ints; in_lds = the grow pass keeps the reached set in LDS.
-struct ComponentPlan {
-  int P, pitch, rpr, wpr;
-  bool in_lds, ok;
-  long scratch;
-};
-ComponentPlan component_plan(int B, int Hs, int Ws);
-int component_launch(const ComponentPlan& p, const unsigned int* bits, const float* focus, unsigned int* out, long long* comp, int* scratch,
-                     int B, int Hs, int Ws, int conn, long snap2, hipStream_t stream);

@@ -11,14 +11,12 @@
 // hwc_join4) into three or four 16-byte pieces that leave through LDS so that neighbouring lanes store neighbouring bytes.
 // Everything else -- odd widths, pitches and pointers -- takes the one-pixel form over the same reader and writer.  A workgroup reads
 // its pixels before it stores them and owns them alone, so out may be img where the two descriptions are the same.
-#include "common.h"
+#include "mask_words.h"
 #include "frame_view.h"
 
 namespace {
 
 constexpr int OVL_THREADS = 256;
-constexpr int OVL_MAX_SIDE = 16384;                    // squared distances stay below 2^30: ints
-constexpr long OVL_INT_LIMIT = 2147483647L;
 constexpr int OVL_STYLE = 20;                          // ints a style row
 constexpr int OVL_FAR = 65536;                         // box edges are clamped to +-OVL_FAR: beyond every x - t and x + t
 
@@ -43,16 +41,6 @@ struct OverlayRule {
   bool live, outline;
 };
 
-// the gaze coordinate in 1/16-pixel units as gaze_gate.hip's gate_gaze and mask_component.hip's comp_gaze form it (restated: those
-// files' objects stay what they are): clamp(rint((double)f * ((side - 1) * 16)), 0, (side - 1) * 16), NaN -> 0
-__device__ __forceinline__ long long ovl_gaze(float f, int side) {
-  const double top = (double)(((long long)side - 1) * 16);
-  double v = rint(__dmul_rn((double)f, top));
-  v = v > 0.0 ? v : 0.0;
-  v = v < top ? v : top;
-  return (long long)v;
-}
-
 __device__ __forceinline__ int ovl_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 __device__ __forceinline__ int ovl_far(long long v) { return v < -OVL_FAR ? -OVL_FAR : (v > OVL_FAR ? OVL_FAR : (int)v); }
 
@@ -75,10 +63,10 @@ __device__ __forceinline__ OverlayRule overlay_rule(const OverlayArgs& A, size_t
   R.outline = R.live && A.band != nullptr && st[17] != 0;
   R.r = 0, R.r2 = 0, R.in2 = 0, R.py = 0, R.px = 0;
   if (A.focus != nullptr) {
-    const int r = ovl_clamp(st[15], OVL_MAX_SIDE), w = ovl_clamp(st[16], OVL_MAX_SIDE);
+    const int r = ovl_clamp(st[15], MASK_MAX_SIDE), w = ovl_clamp(st[16], MASK_MAX_SIDE);     // squared distances stay below 2^30: ints
     const int in = r > w ? r - w : 0;
     R.r = r, R.r2 = r * r, R.in2 = in * in;
-    R.py = (int)((ovl_gaze(A.focus[2 * b], H) + 8) >> 4), R.px = (int)((ovl_gaze(A.focus[2 * b + 1], W) + 8) >> 4);
+    R.py = mask_gaze_px(mask_gaze16(A.focus[2 * b], H)), R.px = mask_gaze_px(mask_gaze16(A.focus[2 * b + 1], W));
   }
   R.t = 0, R.bx0 = 0, R.bx1 = 0, R.by0 = 0, R.by1 = 0;
   if (A.stats != nullptr && R.live) {
@@ -86,7 +74,7 @@ __device__ __forceinline__ OverlayRule overlay_rule(const OverlayArgs& A, size_t
     if (bw > 0 && bh > 0) {
       const long long top = 0x7fffffffffffffffLL;
       const long long x1 = (x0 > 0 && bw > top - x0) ? top : x0 + bw, y1 = (y0 > 0 && bh > top - y0) ? top : y0 + bh;
-      R.t = ovl_clamp(st[11], OVL_MAX_SIDE);
+      R.t = ovl_clamp(st[11], MASK_MAX_SIDE);
       R.bx0 = ovl_far(x0), R.bx1 = ovl_far(x1), R.by0 = ovl_far(y0), R.by1 = ovl_far(y1);
     }
   }
@@ -130,9 +118,9 @@ __device__ __forceinline__ void overlay_px(const F& f, const OverlayArgs& A, con
   const int y = (int)(i / (unsigned int)W), x = (int)(i - (unsigned int)y * W);
   const OverlayRule R = overlay_rule(A, b, H, W);
   const OverlayRow row = overlay_row(R, y);
-  const size_t word = (b * H + y) * (size_t)((W + 31) >> 5) + (x >> 5);
-  const bool bit = R.live && ((A.bits[word] >> (x & 31)) & 1u) != 0;
-  const bool bnd = R.outline && ((A.band[word] >> (x & 31)) & 1u) != 0;
+  const size_t word = (b * H + y) * (size_t)mask_row_words(W) + (x >> 5);
+  const bool bit = R.live && mask_bit(A.bits[word], x) != 0;
+  const bool bnd = R.outline && mask_bit(A.band[word], x) != 0;
   const auto a = f.px(b, y, x);
   const int s[3] = {f.code(a, 0), f.code(a, 1), f.code(a, 2)};
   int c[3];
@@ -193,7 +181,7 @@ __device__ __forceinline__ void overlay_wide(const F& f, const OverlayArgs& A, c
   if (mine) {
     const OverlayRule R = overlay_rule(A, b, H, W);
     const OverlayRow row = overlay_row(R, y);
-    const size_t word = (b * H + y) * (size_t)((W + 31) >> 5) + (x >> 5);
+    const size_t word = (b * H + y) * (size_t)mask_row_words(W) + (x >> 5);
     const unsigned int bits = R.live ? (A.bits[word] >> (x & 16)) & 0xffffu : 0u;
     const unsigned int band = R.outline ? (A.band[word] >> (x & 16)) & 0xffffu : 0u;
     u32x4 v[3];
@@ -290,7 +278,7 @@ void overlay_launch(const HwcFrame<0>& f, const FrameWriter<0>& o, bool wide, di
 }
 
 bool overlay_sizes_ok(int B, int H, int W) {
-  return B > 0 && H > 0 && W > 0 && H <= OVL_MAX_SIDE && W <= OVL_MAX_SIDE && (long)H * W < OVL_INT_LIMIT;
+  return B > 0 && H > 0 && W > 0 && H <= MASK_MAX_SIDE && W <= MASK_MAX_SIDE && (long)H * W < MASK_INT_LIMIT;
 }
 
 // fs_frame_overlay / _u8 / _hwc: the checks and the choice of the form, here alone
@@ -302,7 +290,7 @@ int overlay_run(const F& f, const OverlayArgs& A, unsigned char* out, long ob, l
   FS_REQUIRE((const void*)f.p != (const void*)out || overlay_same(f, o, B, H, W));
   const bool wide = f.wide(W) && o.wide(W);             // the writer's W % 16 == 0 goes for an fp32 frame too, whose own rule is W % 4
   const long bpi = ((long)H * (wide ? W / 16 : W) + OVL_THREADS - 1) / OVL_THREADS;
-  FS_REQUIRE((long)B * bpi < OVL_INT_LIMIT);
+  FS_REQUIRE((long)B * bpi < MASK_INT_LIMIT);
   overlay_launch(f, o, wide, dim3((unsigned)((long)B * bpi)), stream, A, H, W, (unsigned int)bpi);
   FS_LAUNCH_CHECK();
   return FS_OK;
@@ -385,7 +373,7 @@ int fs_color_encode(const long long* labels, const unsigned char* palette, unsig
   FS_REQUIRE(labels && palette && out && K >= 1 && overlay_sizes_ok(B, H, W) && o.ok(B, H, W));
   const bool wide = o.wide(W) && ((uintptr_t)labels & 15) == 0;
   const long bpi = ((long)H * (wide ? W / 16 : W) + OVL_THREADS - 1) / OVL_THREADS;
-  FS_REQUIRE((long)B * bpi < OVL_INT_LIMIT);
+  FS_REQUIRE((long)B * bpi < MASK_INT_LIMIT);
   const dim3 grid((unsigned)((long)B * bpi)), block(OVL_THREADS);
   if (!wide) hipLaunchKernelGGL(color_encode_kernel<0>, grid, block, 0, stream, labels, palette, K, out, ob, oy, ox, H, W, (unsigned int)bpi);
   else if (ox == 1) hipLaunchKernelGGL(color_encode_kernel<1>, grid, block, 0, stream, labels, palette, K, out, ob, oy, ox, H, W, (unsigned int)bpi);

@@ -6,15 +6,15 @@
 //            the decision table.  Pure: it writes the gate record only.
 //   commit   for the viewers that ran the network: the frame becomes the key frame, the gaze the key gaze, the new record's rows move to
 //            the viewer's slots; every viewer's previous gaze and age advance.
-// The pixel code q (frame_view.h) and the gaze in 1/16-pixel units are one function each, used by every pass that needs them: a frame
-// against the key that commit made from it differs nowhere, NaN pixels included.
+// The pixel code q (frame_view.h) and the gaze in 1/16-pixel units (mask_words.h) are one function each, used by every pass that needs
+// them: a frame against the key that commit made from it differs nowhere, NaN pixels included.
 // A frame comes in three layouts -- planar fp32, planar bytes (pixel value byte / 255, whose code q is the byte; 6 bytes a pixel read
 // instead of 15), interleaved bytes read where they lie -- and every pass that reads one is written once over the frame's reader
 // (frame_view.h): the one-pixel tile pass for all three, the 16-pixel band for the two byte layouts (an interleaved frame's sixteen pixels
 // are de-interleaved in registers, v_perm_b32, so that v_sad_u8 meets matching bytes and the key stays planar), commit's frame pass for
 // the planar two.  The fp32 four-pixel band has a cut of its own.  A kernel a layout remains where the layouts' arguments differ; it
 // builds its reader and calls the pass.  decide, and commit's state and row passes, read no frame.
-#include "common.h"
+#include "mask_words.h"
 #include "frame_view.h"
 
 namespace {
@@ -23,15 +23,6 @@ constexpr long GATE_INT_LIMIT = 2147483647L;           // pixel and tile indices
 constexpr long GATE_WGS_MAX = 16777215L;               // workgroups of 256 threads: fewer than 2^32 work-items a launch
 constexpr int GATE_MAX_SIDE = 1 << 26;                 // decide / commit: the gaze in 1/16 pixels stays below 2^30, its squared distances below 2^62
 constexpr int GATE_THREADS = 256;
-
-// the gaze coordinate in 1/16-pixel units: clamp(rint((double)f * ((side - 1) * 16)), 0, (side - 1) * 16), NaN -> 0
-__device__ __forceinline__ long long gate_gaze(float f, int side) {
-  const double top = (double)(((long long)side - 1) * 16);
-  double v = rint(__dmul_rn((double)f, top));
-  v = v > 0.0 ? v : 0.0;
-  v = v < top ? v : top;
-  return (long long)v;
-}
 
 __device__ __forceinline__ long long gate_d2(long long ay, long long ax, long long by, long long bx) {
   const long long dy = ay - by, dx = ax - bx;
@@ -230,8 +221,8 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_decide_kernel(const int* __
   __shared__ int red_c[GATE_THREADS / 64], red_r[GATE_THREADS / 64];
   __shared__ long long red_t[GATE_THREADS / 64];
   const size_t b = blockIdx.x;
-  const long long gy = gate_gaze(focus[2 * b], p.H), gx = gate_gaze(focus[2 * b + 1], p.W);
-  const int py = (int)((gy + 8) >> 4), px = (int)((gx + 8) >> 4);
+  const long long gy = mask_gaze16(focus[2 * b], p.H), gx = mask_gaze16(focus[2 * b + 1], p.W);
+  const int py = mask_gaze_px(gy), px = mask_gaze_px(gx);
   const int gty = py / p.T, gtx = px / p.T;
   // the record's box grown by the margin and clipped, as a range of tiles; empty for an empty mask
   const long long* st = stats + b * 6;
@@ -274,7 +265,7 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_decide_kernel(const int* __
   const long long* g = gstate + b * 6;
   const long long valid = g[0], age1 = g[5] + 1;
   const long long d2_key = gate_d2(gy, gx, g[1], g[2]), d2_prev = gate_d2(gy, gx, g[3], g[4]);
-  const int inside = (int)((bits[(b * p.H + py) * p.P + (px >> 5)] >> (px & 31)) & 1u);
+  const int inside = (int)mask_bit(bits[(b * p.H + py) * p.P + (px >> 5)], px);
   int code = 0;
   if (force != nullptr && force[b] != 0) code = 7;
   else if (valid == 0) code = 1;
@@ -310,7 +301,7 @@ __global__ void gate_commit_state_kernel(const int* __restrict__ idx, int n, lon
                                          int B, int H, int W) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
-  const long long gy = gate_gaze(focus[2 * (size_t)b], H), gx = gate_gaze(focus[2 * (size_t)b + 1], W);
+  const long long gy = mask_gaze16(focus[2 * (size_t)b], H), gx = mask_gaze16(focus[2 * (size_t)b + 1], W);
   long long* g = gstate + (size_t)b * 6;
   if (n > 0 && gate_ran(idx, n, b)) {
     g[0] = 1;
@@ -472,7 +463,7 @@ int gate_commit_run(const F& img, const int* idx, int n, unsigned char* key, lon
   const bool vec = img.wide_commit(W, per) && gate_key_ok<F>(key);
   const long bpi = (long)((per / (vec ? F::lane : 1) + GATE_THREADS - 1) / GATE_THREADS);
   GateRows r;
-  const long nbits = (long)H * ((W + 31) / 32);
+  const long nbits = (long)H * mask_row_words(W);
   const void* src[5] = {src_cat, src_stats, src_counts, src_bits, src_conf};
   void* dst[5] = {dst_cat, dst_stats, dst_counts, dst_bits, dst_conf};
   const long words[5] = {2, 12, cap, nbits, 3};
@@ -529,7 +520,7 @@ int fs_gate_decide(const int* sad, const long long* gstate, const float* focus, 
   FS_REQUIRE(sad && gstate && focus && stats && bits && gate && B > 0 && H > 0 && W > 0 && gate_tile_ok(T) && (long)H * W < GATE_INT_LIMIT);
   FS_REQUIRE(level >= 0 && level <= 254 && margin >= 0 && H <= GATE_MAX_SIDE && W <= GATE_MAX_SIDE && B <= GATE_WGS_MAX);
   GateRule p;
-  p.H = H, p.W = W, p.T = T, p.th = cdiv(H, T), p.tw = cdiv(W, T), p.P = (W + 31) / 32;
+  p.H = H, p.W = W, p.T = T, p.th = cdiv(H, T), p.tw = cdiv(W, T), p.P = mask_row_words(W);
   p.level = level, p.scene_tiles = scene_tiles, p.roi_tiles = roi_tiles, p.margin = margin, p.max_age = max_age, p.inside_on = inside_on;
   p.saccade2 = saccade2, p.fixation2 = fixation2;
   hipLaunchKernelGGL(gate_decide_kernel, dim3((unsigned)B), dim3(GATE_THREADS), 0, stream, sad, gstate, focus, stats, bits, force, gate, p);

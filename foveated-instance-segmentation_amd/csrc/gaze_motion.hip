@@ -10,19 +10,15 @@
 //   move     for the viewers whose shift is not (0, 0) only -- every workgroup reads shift[b] and leaves otherwise: the key frame and
 //            the mask's bit words are written, moved, into second buffers (the bits by funnel shifts over the word borders) and copied
 //            back; one lane a viewer moves the gazes and the totals and writes the motion row; fs_mask_rle's passes re-encode the moved
-//            words into scratch rows that reach stats / counts for the moving viewers alone; the key profiles are taken again.
+//            words (mask_words.h: the layout) into scratch rows that reach stats / counts for the moving viewers alone; the key
+//            profiles are taken again.
 //   commit   for the viewers whose record was made anew: the frame's profiles become the key's, the totals 0.
 // The pixel code q is the gate's, one function (frame_view.h).  A frame comes as planar fp32, planar bytes (pixel value byte / 255, q the
 // byte: its profiles are fs_key_profiles of it) or interleaved bytes read where they lie; the profile pass and the move pass, which fills
 // the key's uncovered border with the frame's codes, are written once over the frame's reader (frame_view.h), a kernel a layout where
 // the layouts' arguments differ.  Every other pass reads no frame.
-#include "common.h"
+#include "mask_words.h"
 #include "frame_view.h"
-
-extern "C" {
-long fs_mask_rle_scratch_ints(int B, int Hs, int Ws);
-int fs_mask_rle(const unsigned int* bits, long long* stats, int* counts, int* scratch, int B, int Hs, int Ws, int cap, hipStream_t stream);
-}
 
 namespace {
 
@@ -178,19 +174,6 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_estimate_kernel(const i
   }
 }
 
-__device__ __forceinline__ unsigned int motion_tail(int c, int P, int W) {          // the bits of word column c that are pixels
-  return (c == P - 1 && (W & 31)) ? (1u << (W & 31)) - 1u : 0xffffffffu;
-}
-
-// 32 bits of a row's stream of pixels from bit position `bit` (any int: what lies outside the W pixels is 0)
-__device__ __forceinline__ unsigned int motion_get(const unsigned int* __restrict__ row, int P, int W, int bit) {
-  const int w = bit >> 5, s = bit & 31;                // floor and remainder, also for a negative position
-  const unsigned int lo = (w >= 0 && w < P) ? row[w] & motion_tail(w, P, W) : 0u;
-  if (s == 0) return lo;
-  const unsigned int hi = (w + 1 >= 0 && w + 1 < P) ? row[w + 1] & motion_tail(w + 1, P, W) : 0u;
-  return (lo >> s) | (hi << (32 - s));
-}
-
 // The workgroups of a viewer in the move and copy passes: nk over the key's bytes (V of them a lane, MOTION_ITER times), then nb over the
 // bit words (one a lane).
 // bits2[y,x] = bits[y-dy,x-dx] where that lies in the frame, else 0: word w of viewer b, by a funnel shift over the word border
@@ -200,7 +183,7 @@ __device__ __forceinline__ void motion_move_bits(const unsigned int* __restrict_
   const int y = (int)(w / (unsigned)P), c = (int)(w - (unsigned)y * P);
   const int sy = y - dy;
   unsigned int out = 0;
-  if (sy >= 0 && sy < H) out = motion_get(bits + (b * H + sy) * P, P, W, 32 * c - dx) & motion_tail(c, P, W);
+  if (sy >= 0 && sy < H) out = mask_window<true>(bits + (b * H + sy) * P, P, W, 32 * c - dx) & mask_tail(c, P, W);
   bits2[b * H * P + w] = out;
 }
 
@@ -404,8 +387,9 @@ int motion_state_shift(const F& img, const long long* shift, unsigned char* key,
                        int H, int W, int cap, hipStream_t stream) {
   FS_REQUIRE(img && shift && key && key2 && bits && bits2 && gstate && stats && counts && prof_key && mstate && motion && scratch);
   FS_REQUIRE(motion_sizes_ok(B, H, W) && cap >= 1 && H <= MOTION_MAX_SIDE && W <= MOTION_MAX_SIDE && key != key2 && bits != bits2);
-  FS_REQUIRE(((uintptr_t)scratch & 7) == 0 && fs_mask_rle_scratch_ints(B, H, W) > 0 && img.ok(B, H, W));
-  const int P = (W + 31) / 32, n = H + W;
+  const RlePlan rp = rle_plan(B, H, W);
+  FS_REQUIRE(((uintptr_t)scratch & 7) == 0 && rp.total > 0 && img.ok(B, H, W));
+  const int P = mask_row_words(W), n = H + W;
   const size_t per = (size_t)3 * H * W;
   const bool vec = W % 4 == 0 && ((uintptr_t)key & 3) == 0 && ((uintptr_t)key2 & 3) == 0;
   const long chunk = (long)MOTION_THREADS * MOTION_ITER * (vec ? 4 : 1);
@@ -429,7 +413,8 @@ int motion_state_shift(const F& img, const long long* shift, unsigned char* key,
                        (unsigned)nb);
   }
   FS_LAUNCH_CHECK();
-  FS_TRY(fs_mask_rle(bits, stats2, counts2, rle, B, H, W, cap, stream));
+  FS_REQUIRE(rp.ok);
+  FS_TRY(rle_launch(rp, bits, stats2, counts2, rle, B, H, W, cap, stream));
   hipLaunchKernelGGL(motion_finish_kernel, dim3((unsigned)(B * bpv)), block, 0, stream, shift, reinterpret_cast<const unsigned int*>(stats2),
                      reinterpret_cast<const unsigned int*>(counts2), reinterpret_cast<unsigned int*>(stats), reinterpret_cast<unsigned int*>(counts),
                      prof_key, cap, n, (unsigned)bpv);
@@ -470,7 +455,7 @@ int fs_profile_shift(const int* prof, const int* prof_key, const long long* gsta
 
 long fs_state_shift_scratch_ints(int B, int H, int W, int cap) {
   if (!motion_sizes_ok(B, H, W) || cap < 1) return 0;
-  return 12L * B + motion_pad2((long)B * cap) + fs_mask_rle_scratch_ints(B, H, W);
+  return 12L * B + motion_pad2((long)B * cap) + rle_plan(B, H, W).total;
 }
 
 int fs_state_shift(const float* img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,

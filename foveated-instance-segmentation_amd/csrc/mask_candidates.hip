@@ -2,26 +2,23 @@
 // annotation and putting the gaze on a pixel inside it (DynamicFocus/e_preprocess_scripts/b2_preprocess_lvis.py:258-333: rasterise the
 // annotation, ridx_rrcc = np.random.randint(len(rrs))); this is the inverse of that step -- gaze and annotations given, which one is
 // looked at -- and has no counterpart there.  UNPINNED: the definition is this library's (include/fovealseg.h).  All
-// of it is integer work on the bit words of fs_mask_bits, by plain stores, without atomics and without a host read.  Passes:
+// of it is integer work on bit words (mask_words.h: the layout), by plain stores, without atomics and without a host read.  Passes:
 //   valid   one workgroup: cand_off[0] == 0, non-decreasing, cand_off[B] == N -> scratch[0].  Decided once; every later pass reads it.
 //   count   the hot pass, one workgroup per (candidate, band of rows): the candidate finds its image by bisecting cand_off (positions
 //           only: no offset value forms an address), then reads its words once -- four a 16-byte load where a row is whole groups of
 //           four and the planes are 16-byte aligned -- and the image's prediction words beside them (re-read by every candidate of the
-//           image: L2).  Per word the popcounts |c|, |c & p|, |p| and the nearest set pixel to the gaze as
-//           component_seed_kernel's key = d2 * 2^31 + (y * Ws + x).  Shuffles in the wave, LDS across the waves, one lane stores the
-//           band's record (area, inter, parea, key) into scratch.
+//           image: L2).  Per word the popcounts |c|, |c & p|, |p| and the nearest set pixel to the gaze as mask_near_key.  Shuffles
+//           in the wave, LDS across the waves, one lane stores the band's record (area, inter, parea, key) into scratch.
 //   select  a wave per image: each lane adds the band records of its candidates in index order, writes their cand rows and keeps the
 //           least (d2, area, n) and the greatest IoU with the prediction (cross-multiplied in int64); shuffles, then one lane writes sel.
 //   copy    one workgroup per (image, band of rows): the selected candidate's words with the tail masked, or zeros, into gbits.
 // Sums and minima of integers in a fixed order, and total orders with the row as the last key: the same bits in every run.
-#include "common.h"
+#include "mask_words.h"
 
 namespace {
 
 constexpr int CAND_THREADS = 256;
 constexpr int CAND_WAVES = CAND_THREADS / 64;
-constexpr int CAND_MAX_SIDE = 16384;                   // d2 < 2^29, key < 2^60; inter * union < 2^57
-constexpr long CAND_INT_LIMIT = 2147483647L;           // pixel indices are ints, and the key keeps them in 31 bits
 constexpr int CAND_BAND_ROWS = 256;                    // the count pass: rows a band at the most
 constexpr int CAND_BAND_WORDS = 8192;                  // ... and words a band at the most (one row where a row is longer): 32 a thread
 constexpr int CAND_COPY_ROWS = 64;                     // the copy pass: it has B images to fill the machine with, not N candidates
@@ -39,8 +36,9 @@ struct CandPlan {
 
 CandPlan cand_plan(int B, int N, int Hs, int Ws) {
   CandPlan p = {};
-  if (!(B > 0 && N >= 0 && Hs > 0 && Ws > 0 && Hs <= CAND_MAX_SIDE && Ws <= CAND_MAX_SIDE && (long)Hs * Ws < CAND_INT_LIMIT)) return p;
-  p.P = cdiv(Ws, 32);
+  // sides: d2 < 2^29, key < 2^60, inter * union < 2^57; pixel indices are ints, and the key keeps them in 31 bits
+  if (!(B > 0 && N >= 0 && Hs > 0 && Ws > 0 && Hs <= MASK_MAX_SIDE && Ws <= MASK_MAX_SIDE && (long)Hs * Ws < MASK_INT_LIMIT)) return p;
+  p.P = mask_row_words(Ws);
   // Measured on one MI355X at B = 64, 1024^2, 64 candidates an image (profiles/r31/README.md): bands of 64 rows / 2048 words 190 us a
   // call, 256 rows / 8192 words 147 us (the count pass 167 -> 121 us, the copy pass 7.6 -> 16.5 us: hence its own, smaller bands),
   // 16 rows / 512 words 442 us; one word a load instead of four 268 and 230 us.  FS_CAND_ROWS / FS_CAND_WORDS / FS_CAND_VEC exist in
@@ -54,22 +52,8 @@ CandPlan cand_plan(int B, int N, int Hs, int Ws) {
   p.crows = min(Hs, min(CAND_COPY_ROWS, max(1, CAND_COPY_WORDS / p.P)));
   p.cbands = cdiv(Hs, p.crows);
   p.scratch = CAND_HEAD + (long)N * p.bands * CAND_REC;
-  p.ok = (long)N * p.bands <= CAND_INT_LIMIT && (long)B * p.cbands <= CAND_INT_LIMIT;     // the grids of the count and copy passes
+  p.ok = (long)N * p.bands <= MASK_INT_LIMIT && (long)B * p.cbands <= MASK_INT_LIMIT;     // the grids of the count and copy passes
   return p;
-}
-
-// the gaze coordinate in 1/16-pixel units as mask_component.hip's comp_gaze and gaze_gate.hip's gate_gaze form it (restated: those
-// files' objects stay what they are): clamp(rint((double)f * ((side - 1) * 16)), 0, (side - 1) * 16), NaN -> 0
-__device__ __forceinline__ long long cand_gaze(float f, int side) {
-  const double top = (double)(((long long)side - 1) * 16);
-  double v = rint(__dmul_rn((double)f, top));
-  v = v > 0.0 ? v : 0.0;
-  v = v < top ? v : top;
-  return (long long)v;
-}
-
-__device__ __forceinline__ unsigned int cand_tail(int c, int P, int Ws) {          // the bits of word column c that are pixels
-  return (c == P - 1 && (Ws & 31)) ? (1u << (Ws & 31)) - 1u : 0xffffffffu;
 }
 
 // head[0] = 1 unless cand_off[0] == 0 <= cand_off[1] <= ... <= cand_off[B] == N; one workgroup
@@ -107,8 +91,7 @@ __global__ __launch_bounds__(CAND_THREADS) void cand_count_kernel(const unsigned
   const unsigned int* cw = cbits + ((size_t)n * Hs + r0) * P;
   const unsigned int* pw = (pbits && !bad) ? pbits + ((size_t)b * Hs + r0) * P : nullptr;
   int py = 0, px = 0;
-  if (!bad) py = (int)((cand_gaze(focus[2 * (size_t)b], Hs) + 8) >> 4), px = (int)((cand_gaze(focus[2 * (size_t)b + 1], Ws) + 8) >> 4);
-  const int pc = px >> 5, pb = px & 31;
+  if (!bad) py = mask_gaze_px(mask_gaze16(focus[2 * (size_t)b], Hs)), px = mask_gaze_px(mask_gaze16(focus[2 * (size_t)b + 1], Ws));
   // a thread's loads are CAND_THREADS apart: (row, column) move by a fixed step, one division a thread
   const int qs = CAND_THREADS / PV, rs = CAND_THREADS - qs * PV;
   int y = r0 + tid / PV, cv = tid - (tid / PV) * PV;
@@ -128,45 +111,20 @@ __global__ __launch_bounds__(CAND_THREADS) void cand_count_kernel(const unsigned
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
       const int c = cv * VEC + j;
-      const unsigned int tail = cand_tail(c, P, Ws);
+      const unsigned int tail = mask_tail(c, P, Ws);
       const unsigned int m = mw[j] & tail, p = pv[j] & tail;
       inter += __popc(m & p);
       parea += __popc(p);
       if (m == 0u) continue;
       area += __popc(m);
       if (bad) continue;
-      const long long dy = y - py;
-      const int x0 = c << 5;
-      int xa = -1, xb = -1;                            // the nearest set bit at or left of the gaze column, and at or right of it
-      if (c < pc) xa = x0 + 31 - __clz((int)m);
-      else if (c > pc) xb = x0 + __ffs((int)m) - 1;
-      else {
-        const unsigned int lo = m & (0xffffffffu >> (31 - pb)), hi = m & (0xffffffffu << pb);
-        if (lo) xa = x0 + 31 - __clz((int)lo);
-        if (hi) xb = x0 + __ffs((int)hi) - 1;
-      }
-      if (xa >= 0) {
-        const long long dx = xa - px;
-        const unsigned long long k = ((unsigned long long)(dy * dy + dx * dx) << 31) + (unsigned long long)((long long)y * Ws + xa);
-        key = k < key ? k : key;
-      }
-      if (xb >= 0) {
-        const long long dx = xb - px;
-        const unsigned long long k = ((unsigned long long)(dy * dy + dx * dx) << 31) + (unsigned long long)((long long)y * Ws + xb);
-        key = k < key ? k : key;
-      }
+      key = mask_near_key(key, m, y, c, py, px, Ws);
     }
     y += qs, cv += rs;
     if (cv >= PV) cv -= PV, ++y;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long k = __shfl_xor(key, o, 64);
-    key = k < key ? k : key;
-    area += __shfl_xor(area, o, 64);
-    inter += __shfl_xor(inter, o, 64);
-    parea += __shfl_xor(parea, o, 64);
-  }
+  key = mask_key_wave_min(key);
+  area = wave_sum_i(area), inter = wave_sum_i(inter), parea = wave_sum_i(parea);
   if ((tid & 63) == 0) red_k[tid >> 6] = key, red_c[tid >> 6][0] = area, red_c[tid >> 6][1] = inter, red_c[tid >> 6][2] = parea;
   __syncthreads();
   if (tid != 0) return;
@@ -286,7 +244,7 @@ __global__ __launch_bounds__(CAND_THREADS) void cand_copy_kernel(const unsigned 
   const int rs = CAND_THREADS % P;
   int c = tid % P;
   for (int i = tid; i < nw; i += CAND_THREADS) {
-    dst[i] = src[i] & cand_tail(c, P, Ws);
+    dst[i] = src[i] & mask_tail(c, P, Ws);
     c += rs;
     if (c >= P) c -= P;
   }

@@ -1,8 +1,7 @@
 // The connected component of a bit mask under the gaze (fs_mask_component; no counterpart in the reference: UNPINNED, a definition of
-// this library's).  All of it is integer work on the bit words of fs_mask_bits.  Passes, one workgroup per image each:
+// this library's).  All of it is integer work on bit words (mask_words.h: the layout).  Passes, one workgroup per image each:
 //   seed   one pass over the words: the popcount of the mask, and the set pixel nearest to the gaze pixel as the minimum of
-//          key = d2 * 2^31 + (y * Ws + x) -- per word the nearest set bit at or right of the gaze column and the nearest at or left
-//          of it.  Shuffles in the wave, LDS across the waves, one lane writes comp and the seed record.  No atomics.
+//          mask_near_key.  Shuffles in the wave, LDS across the waves, one lane writes comp and the seed record.  No atomics.
 //   grow   the hot pass: the reached set R starts as the seed bit and grows inside the mask M until a sweep changes no word.  A sweep
 //          is (a) every thread walking a vertical strip -- one word column over a run of rows, down then up, the reached word above
 //          carried in a register -- and (b) every thread walking a run of words along a row, right then left, carrying bit 31 / bit 0
@@ -12,30 +11,14 @@
 // component, so whichever value a read sees is a subset of it, and a sweep in which no thread changed a word has read final values
 // everywhere -- R is then closed under the step relation inside M, i.e. the component.  The result is a set function of the input:
 // the same bits whatever the order of the walks.
-#include "common.h"
+#include "mask_words.h"
 
 namespace {
 
 constexpr int COMP_THREADS = 1024;
-constexpr int COMP_MAX_SIDE = 16384;                   // d2 < 2^29, key < 2^60
-constexpr long COMP_INT_LIMIT = 2147483647L;           // pixel indices are ints, and the key keeps them in 31 bits
 constexpr long COMP_LDS_WORDS = 39936;                 // R in LDS: 156 KiB of the workgroup's 160, the rest is the static reductions'
 constexpr int COMP_MIN_ROWS = 32, COMP_MIN_WORDS = 8; // the shortest strip of pass (a) and run of pass (b), where the image has as many
 constexpr int COMP_REC = 4;                            // ints of scratch per image: seed_y, seed_x (-1, -1: none), the grow pass's sweeps (a diagnostic of tools/component_bench.py, no part of the ABI), 1 spare
-
-// the gaze coordinate in 1/16-pixel units as gaze_gate.hip's gate_gaze forms it (restated: that file's object stays what it is):
-// clamp(rint((double)f * ((side - 1) * 16)), 0, (side - 1) * 16), NaN -> 0
-__device__ __forceinline__ long long comp_gaze(float f, int side) {
-  const double top = (double)(((long long)side - 1) * 16);
-  double v = rint(__dmul_rn((double)f, top));
-  v = v > 0.0 ? v : 0.0;
-  v = v < top ? v : top;
-  return (long long)v;
-}
-
-__device__ __forceinline__ unsigned int comp_tail(int c, int P, int Ws) {          // the bits of word column c that are pixels
-  return (c == P - 1 && (Ws & 31)) ? (1u << (Ws & 31)) - 1u : 0xffffffffu;
-}
 
 // every bit of m joined to a bit of s by a run of set bits of m, in both directions (s within m)
 __device__ __forceinline__ unsigned int comp_fill(unsigned int s, unsigned int m) {
@@ -61,44 +44,20 @@ __global__ __launch_bounds__(COMP_THREADS) void component_seed_kernel(const unsi
   __shared__ unsigned long long red_k[COMP_THREADS / 64];
   __shared__ long long red_a[COMP_THREADS / 64];
   const size_t b = blockIdx.x;
-  const int py = (int)((comp_gaze(focus[2 * b], Hs) + 8) >> 4), px = (int)((comp_gaze(focus[2 * b + 1], Ws) + 8) >> 4);
+  const int py = mask_gaze_px(mask_gaze16(focus[2 * b], Hs)), px = mask_gaze_px(mask_gaze16(focus[2 * b + 1], Ws));
   const int words = Hs * P;
   const unsigned int* mb = bits + b * (size_t)words;
-  const int pc = px >> 5, pb = px & 31;
   unsigned long long key = ~0ull;
   long long area = 0;
   for (int i = threadIdx.x; i < words; i += COMP_THREADS) {
     const int y = i / P, c = i - y * P;
-    const unsigned int m = mb[i] & comp_tail(c, P, Ws);
+    const unsigned int m = mb[i] & mask_tail(c, P, Ws);
     if (m == 0u) continue;
     area += __popc(m);
-    const long long dy = y - py;
-    const int x0 = c << 5;
-    int xa = -1, xb = -1;                              // the candidates: at or left of the gaze column, at or right of it
-    if (c < pc) xa = x0 + 31 - __clz((int)m);
-    else if (c > pc) xb = x0 + __ffs((int)m) - 1;
-    else {
-      const unsigned int lo = m & (0xffffffffu >> (31 - pb)), hi = m & (0xffffffffu << pb);
-      if (lo) xa = x0 + 31 - __clz((int)lo);
-      if (hi) xb = x0 + __ffs((int)hi) - 1;
-    }
-    if (xa >= 0) {
-      const long long dx = xa - px;
-      const unsigned long long k = ((unsigned long long)(dy * dy + dx * dx) << 31) + (unsigned long long)((long long)y * Ws + xa);
-      key = k < key ? k : key;
-    }
-    if (xb >= 0) {
-      const long long dx = xb - px;
-      const unsigned long long k = ((unsigned long long)(dy * dy + dx * dx) << 31) + (unsigned long long)((long long)y * Ws + xb);
-      key = k < key ? k : key;
-    }
+    key = mask_near_key(key, m, y, c, py, px, Ws);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long k = __shfl_xor(key, o, 64);
-    key = k < key ? k : key;
-    area += __shfl_xor(area, o, 64);
-  }
+  key = mask_key_wave_min(key);
+  area = wave_sum_ll(area);
   if ((threadIdx.x & 63) == 0) { red_k[threadIdx.x >> 6] = key; red_a[threadIdx.x >> 6] = area; }
   __syncthreads();
   if (threadIdx.x != 0) return;
@@ -161,7 +120,7 @@ __global__ __launch_bounds__(COMP_THREADS) void component_grow_kernel(const unsi
       for (int item = threadIdx.x; item < items_a; item += COMP_THREADS) {
         const int strip = item / P, c = item - strip * P;
         const int y0 = strip * rpr, y1 = min(y0 + rpr, Hs);
-        const unsigned int tail = comp_tail(c, P, Ws);
+        const unsigned int tail = mask_tail(c, P, Ws);
         const int step = dir == 0 ? 1 : -1;
         int y = dir == 0 ? y0 : y1 - 1;
         int yp = y - step;                             // the row the walk comes from; outside the image it is background
@@ -207,7 +166,7 @@ __global__ __launch_bounds__(COMP_THREADS) void component_grow_kernel(const unsi
           const unsigned int r = comp_ld(R + y * pitch + c);
           unsigned int v = r;
           if ((dir == 0 && r != 0u) || carry != 0u) {               // the walk to the right fills every word once; the way back only what a carry adds to
-            const unsigned int m = mb[y * P + c] & comp_tail(c, P, Ws);
+            const unsigned int m = mb[y * P + c] & mask_tail(c, P, Ws);
             v = r | (m & carry);
             if (v != 0u && (dir == 0 || v != r)) v = comp_fill(v, m);
             if (v != r) {
@@ -235,8 +194,9 @@ __global__ __launch_bounds__(COMP_THREADS) void component_grow_kernel(const unsi
 
 ComponentPlan component_plan(int B, int Hs, int Ws) {
   ComponentPlan p = {};
-  if (!(B > 0 && Hs > 0 && Ws > 0 && Hs <= COMP_MAX_SIDE && Ws <= COMP_MAX_SIDE && (long)Hs * Ws < COMP_INT_LIMIT)) return p;
-  p.P = (Ws + 31) / 32;
+  // sides: d2 < 2^29, key < 2^60; pixel indices are ints, and the key keeps them in 31 bits
+  if (!(B > 0 && Hs > 0 && Ws > 0 && Hs <= MASK_MAX_SIDE && Ws <= MASK_MAX_SIDE && (long)Hs * Ws < MASK_INT_LIMIT)) return p;
+  p.P = mask_row_words(Ws);
   const long pitch = p.P | 1;
   p.in_lds = (long)Hs * pitch <= COMP_LDS_WORDS;
   p.pitch = (int)(p.in_lds ? pitch : p.P);

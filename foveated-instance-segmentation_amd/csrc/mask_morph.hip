@@ -1,6 +1,6 @@
 // Morphology on bit words: erosion by a (2d+1)^2 square and the six pair counters of mask IoU / Boundary IoU (fs_mask_erode,
 // fs_mask_pair_counts; no counterpart in the reference: UNPINNED, restated from the published definition of Boundary IoU, Cheng et al.,
-// CVPR 2021).  All of it is integer work on the bit words of fs_mask_bits.
+// CVPR 2021).  All of it is integer work on bit words (mask_words.h: the layout).
 //   E_d(m)[y,x] = 1 iff every pixel of the (2d+1) x (2d+1) square centred on (y,x) is set, pixels outside the image unset.
 // The square is separable, and an AND over a run of L = 2d+1 positions is built by doubling: A_1 = m, A_2k[x] = A_k[x] & A_k[x+k]
 // (the run x .. x+2k-1), and for the largest power of two k <= L, A_L[x] = A_k[x] & A_k[x+L-k]; the erosion is A_L[x-d].  Passes:
@@ -12,13 +12,11 @@
 //   count  (pair counts) popcounts of a&b, a, b and of the three bands m & ~E_d(m): shuffles in the wave, LDS across the waves, one
 //          record of six ints a workgroup, then one workgroup per image adds its records in index order.  No atomics.
 // With 2d+1 above a side the erosion is empty: out is cleared (the band is the mask) and neither pass runs.
-#include "common.h"
+#include "mask_words.h"
 
 namespace {
 
 constexpr int MORPH_THREADS = 256;
-constexpr int MORPH_MAX_SIDE = 16384;
-constexpr long MORPH_INT_LIMIT = 2147483647L;
 constexpr int MORPH_MAX_D = 2047;                      // 2d+1 rows of halo and one output row fit MORPH_LDS_WORDS at one word column
 constexpr int MORPH_LDS_WORDS = 4096;                  // words a stage; two stages (ping and pong) are 32 KiB of static LDS
 constexpr int MORPH_ROW_WORDS = 1024;                  // words a workgroup of the rows pass takes, where a row is shorter than that
@@ -35,10 +33,10 @@ struct MorphPlan {
 
 MorphPlan morph_plan(int B, int Hs, int Ws, int d) {
   MorphPlan p = {};
-  if (!(B > 0 && Hs > 0 && Ws > 0 && Hs <= MORPH_MAX_SIDE && Ws <= MORPH_MAX_SIDE && (long)Hs * Ws < MORPH_INT_LIMIT && d >= 1 &&
+  if (!(B > 0 && Hs > 0 && Ws > 0 && Hs <= MASK_MAX_SIDE && Ws <= MASK_MAX_SIDE && (long)Hs * Ws < MASK_INT_LIMIT && d >= 1 &&
         d <= MORPH_MAX_D))
     return p;
-  p.P = (Ws + 31) / 32;
+  p.P = mask_row_words(Ws);
   p.words = (long)Hs * p.P;
   p.empty = 2L * d + 1 > (Hs < Ws ? Hs : Ws);
   p.R = MORPH_ROW_WORDS / p.P > 0 ? MORPH_ROW_WORDS / p.P : 1;
@@ -55,21 +53,8 @@ MorphPlan morph_plan(int B, int Hs, int Ws, int d) {
   p.chunks = (int)((p.words + MORPH_COUNT_WORDS - 1) / MORPH_COUNT_WORDS);
   // every grid is images * tiles workgroups in x, for up to 2 B images
   const long most = (long)p.tiles_y * p.tiles_c > p.tiles_r ? (long)p.tiles_y * p.tiles_c : p.tiles_r;
-  p.ok = 2L * B * (most > p.chunks ? most : p.chunks) < MORPH_INT_LIMIT && 2L * B * p.words < (1L << 40);
+  p.ok = 2L * B * (most > p.chunks ? most : p.chunks) < MASK_INT_LIMIT && 2L * B * p.words < (1L << 40);
   return p;
-}
-
-__device__ __forceinline__ unsigned int morph_tail(int c, int P, int Ws) {         // the bits of word column c that are pixels
-  return (c == P - 1 && (Ws & 31)) ? (1u << (Ws & 31)) - 1u : 0xffffffffu;
-}
-
-// 32 bits of a row's stream from bit position `bit` (any int: what lies outside the P words is 0)
-__device__ __forceinline__ unsigned int morph_get(const unsigned int* row, int P, int bit) {
-  const int w = bit >> 5, s = bit & 31;                // floor and remainder, also for a negative position
-  const unsigned int lo = (w >= 0 && w < P) ? row[w] : 0u;
-  if (s == 0) return lo;
-  const unsigned int hi = (w + 1 >= 0 && w + 1 < P) ? row[w + 1] : 0u;
-  return (lo >> s) | (hi << (32 - s));
 }
 
 // image i of a launch over 2 B images: the first B are a's, the rest b's
@@ -89,7 +74,7 @@ __global__ __launch_bounds__(MORPH_THREADS) void morph_rows_kernel(const unsigne
   const int y0 = tile * R;
   const int n = min(R, Hs - y0) * P;
   const size_t base = (size_t)y0 * P;
-  for (int i = threadIdx.x; i < n; i += MORPH_THREADS) stage[0][i] = src[base + i] & morph_tail(i % P, P, Ws);
+  for (int i = threadIdx.x; i < n; i += MORPH_THREADS) stage[0][i] = src[base + i] & mask_tail(i % P, P, Ws);
   __syncthreads();
   const int L = 2 * d + 1;
   int cur = 0, k = 1;
@@ -97,14 +82,14 @@ __global__ __launch_bounds__(MORPH_THREADS) void morph_rows_kernel(const unsigne
     for (int i = threadIdx.x; i < n; i += MORPH_THREADS) {
       const int r = i / P, c = i - r * P;
       const unsigned int* row = stage[cur] + r * P;
-      stage[cur ^ 1][i] = row[c] & morph_get(row, P, 32 * c + k);
+      stage[cur ^ 1][i] = row[c] & mask_window<false>(row, P, Ws, 32 * c + k);
     }
     __syncthreads();
   }
   for (int i = threadIdx.x; i < n; i += MORPH_THREADS) {
     const int r = i / P, c = i - r * P;
     const unsigned int* row = stage[cur] + r * P;
-    dst[base + i] = morph_get(row, P, 32 * c - d) & morph_get(row, P, 32 * c - d + L - k);
+    dst[base + i] = mask_window<false>(row, P, Ws, 32 * c - d) & mask_window<false>(row, P, Ws, 32 * c - d + L - k);
   }
 }
 
@@ -166,7 +151,7 @@ __global__ __launch_bounds__(MORPH_THREADS) void morph_count_kernel(const unsign
   int v[MORPH_REC] = {0, 0, 0, 0, 0, 0};
   for (int i = threadIdx.x; i < n; i += MORPH_THREADS) {
     const size_t at = i0 + i;
-    const unsigned int tail = morph_tail((int)(at % P), P, Ws);
+    const unsigned int tail = mask_tail((int)(at % P), P, Ws);
     const unsigned int wa = pa[at] & tail, wb = pb[at] & tail;
     const unsigned int ba = ea ? wa & ~ea[at] : wa, bb = eb ? wb & ~eb[at] : wb;
     v[0] += __popc(wa & wb), v[1] += __popc(wa), v[2] += __popc(wb);

@@ -19,17 +19,14 @@
 //           ballot over the wave; the result is ORed into the mask and the toggle word cleared for the next ring.
 // After the last ring the band is stored, every word by a plain store, and its popcount goes to scratch; a second kernel adds an
 // image's bands into info.  XOR and OR in LDS do not depend on order: the same bits in every mode and in every run.
-#include "common.h"
+#include "mask_words.h"
 
 namespace {
 
 constexpr int POLY_THREADS = 256;
 constexpr int POLY_WAVES = POLY_THREADS / 64;
-constexpr int POLY_SIDE_MAX = 16384;                   // (y - y0) dx stays below 2^28
 constexpr int POLY_BAND_ROWS = 64;                     // rows a band at the most
 constexpr int POLY_BAND_WORDS = 4096;                  // words a row buffer at the most: two buffers are 32 KiB of LDS
-constexpr long POLY_INT_LIMIT = 2147483647L;
-constexpr long POLY_SLOTS_MAX = 4294967295L - 255;     // bit slots B * Hs * P * 32, as fs_mask_bits
 
 struct PolyPlan {
   int P, rows, bands;                                  // words a row; rows a band; bands an image
@@ -39,8 +36,8 @@ struct PolyPlan {
 
 PolyPlan poly_plan(int B, int Hs, int Ws) {
   PolyPlan p = {};
-  if (!(B > 0 && Hs > 0 && Ws > 0 && Hs <= POLY_SIDE_MAX && Ws <= POLY_SIDE_MAX)) return p;
-  p.P = cdiv(Ws, 32);
+  if (!(B > 0 && Hs > 0 && Ws > 0 && Hs <= MASK_MAX_SIDE && Ws <= MASK_MAX_SIDE)) return p;     // (y - y0) dx stays below 2^28
+  p.P = mask_row_words(Ws);
   // Bands of 64 rows (32 KiB of LDS at the most) were measured against bands that fill 64 KiB (250 rows at 1024 wide) on one MI355X at
   // B = 64: the tall bands were 1.35 - 1.94 x slower on every case of tools/poly_bench.py (a quarter of the workgroups, each clearing,
   // scanning and storing four times the rows), 128 rows 1.08 - 1.25 x slower on four of five, 16 rows 0 - 7 % slower
@@ -51,7 +48,7 @@ PolyPlan poly_plan(int B, int Hs, int Ws) {
   p.bands = cdiv(Hs, p.rows);
   p.parts = (long)B * p.bands;
   // a workgroup stores at least one row, so the grid stays below 2^31 with the slots below 2^32
-  p.ok = (long)Hs * Ws < POLY_INT_LIMIT && (long)B * Hs * p.P * 32 <= POLY_SLOTS_MAX;
+  p.ok = (long)Hs * Ws < MASK_INT_LIMIT && (long)B * Hs * p.P * 32 <= THREADS_MAX;     // bit slots, as fs_mask_bits
   return p;
 }
 

@@ -13,15 +13,13 @@
 //          reads of end[] are a contiguous stretch too, next to its neighbours'.  An image whose status is not 0 stores zeros.
 // Every index into counts, scratch, info and bits is bounded by B, Hs, Ws, cap and n_read alone: the ends are compared, never used
 // as addresses.
-#include "common.h"
+#include "mask_words.h"
 
 namespace {
 
 constexpr int DEC_THREADS = 256;
 constexpr int DEC_WAVES = DEC_THREADS / 64;
 constexpr int DEC_ROWS = 64;                           // rows a wave: one kept ballot a lane
-constexpr long DEC_INT_LIMIT = 2147483647L;
-constexpr long DEC_SLOTS_MAX = 4294967295L - 255;      // bit slots B * Hs * P * 32, as fs_mask_bits
 enum { DEC_OK = 0, DEC_CUT = 1, DEC_BAD = 2, DEC_SUM = 3 };
 
 struct DecodePlan {
@@ -34,11 +32,11 @@ DecodePlan decode_plan(int B, int Hs, int Ws, int cap) {
   DecodePlan p = {};
   if (!(B > 0 && cap > 0)) return p;
   p.ends = 0, p.meta = (long)B * cap, p.total = p.meta + 2L * B;
-  if (!(Hs > 0 && Ws > 0 && (long)Hs * Ws < DEC_INT_LIMIT)) return p;
-  p.P = cdiv(Ws, 32);
+  if (!(Hs > 0 && Ws > 0 && (long)Hs * Ws < MASK_INT_LIMIT)) return p;
+  p.P = mask_row_words(Ws);
   p.tiles_x = cdiv(Ws, 64), p.tiles_y = cdiv(Hs, DEC_ROWS * DEC_WAVES), p.per = p.tiles_x * p.tiles_y;
   // a workgroup covers at most 2^14 bit slots of its own, so the grid stays below 2^31 with the slots below 2^32
-  p.ok = (long)B * Hs * p.P * 32 <= DEC_SLOTS_MAX && (long)B * p.per < DEC_INT_LIMIT;
+  p.ok = (long)B * Hs * p.P * 32 <= THREADS_MAX && (long)B * p.per < MASK_INT_LIMIT;
   return p;
 }
 

@@ -5,22 +5,22 @@
 //   fill         exact nearest claimed pixel for the holes: nearest column per row, then the best row   (models.py:159-286, 'nearest')
 //   decide       the C1 head's argmax once per grid point, gathered through owner + fill -> class map    (models/models.py:930-940; eval.py:195)
 //   gather       which grid point feeds a full-resolution pixel: feeding_point / feeding_points4, the one rule under every stage below;
-//                its bit-word output: bit_slot, store_word_nibbles / store_word_ballot, gather_bits
+//                its bit-word output: gather_bits over mask_words.h's bit_slot, store_word_nibbles / store_word_ballot
 //   count        the same gather, counting against the label instead of storing: the six counters and four accuracies of
 //                MODEL.upsample (models/models.py:378-474,968), the trimap buckets (eval.py:41-67), the per-class areas of the three
 //                spaces (eval.py:197,218-257,313-322; models/models_instance.py:909-918; utils.py:289-317)
 //   trimap bands which band of width 1, 2, 4 .. 2^D around the label's boundary a pixel lies in     (eval.py:41-67)
 //   surface      the q-th percentile of the distances between two masks' borders (HD95), as two integer order statistics of d^2
 //                                                                                            (VAL.hd95; utils.py:25-101, in 2-D)
-//   instance     the mask "class is not K-1" gathered into bit words, its area, box and uncompressed COCO run-length code, and the head's
-//                class: the label-free output as a record (no counterpart in the reference; the code's format is the published one)
+//   instance     the mask "class is not K-1" gathered into bit words, its area, box and uncompressed COCO run-length code (mask_rle.hip's
+//                passes), and the head's class: the label-free output as a record (no counterpart in the reference)
 //   score        the record's confidence: the foreground softmax mass per grid point as a 24-bit integer table, summed over the set pixels
 //                in the instance gather, times the head's class probability (no counterpart in the reference; unpinned)
 // Host side: fs_unwarp_labels / _accuracy / _trimap / _class_areas / _hd / _instances / _instances_scored / _instances_component are one
 // launch sequence with optional parts.  unwarp_plan() derives
 // every size, scratch offset and limit from the shape and the feature set, UnwarpJob carries the caller's pointers, unwarp_run()
 // checks both and launches.  A refused call launches nothing: every check, fs_trimap_bands' included, comes before the first launch.
-#include "common.h"
+#include "mask_words.h"
 #include "grid_taps.h"
 
 namespace {
@@ -763,10 +763,9 @@ __global__ __launch_bounds__(256) void trimap_col_kernel(const unsigned char* __
 //   select   a two-level radix select over the pooled d^2 of an image: the row pass runs twice, first counting d^2 >> 15 into a
 //            histogram, whose prefix sums give the bucket of either rank, then counting the low 15 bits of the values in those buckets.
 //            No list of distances exists at any size; integer atomics only, the same bits in any order.
-// HD_SENT is g in a column without a border pixel.  With Hs, Ws <= 16384 a true d^2 is at most 2 * 16383^2 < 2^29, HD_SENT^2 = 2^30
-// lies above every one of them, and dx^2 + HD_SENT^2 <= 16383^2 + 2^30 < 2^31 stays an int.
+// HD_SENT is g in a column without a border pixel.  With Hs, Ws <= MASK_MAX_SIDE = 16384 a true d^2 is at most 2 * 16383^2 < 2^29,
+// HD_SENT^2 = 2^30 lies above every one of them, and dx^2 + HD_SENT^2 <= 16383^2 + 2^30 < 2^31 stays an int.
 constexpr int HD_SENT = 32768;
-constexpr int HD_MAX_SIDE = 16384;
 constexpr int HD_L1_SHIFT = 15;                        // level 1: d^2 >> 15, at most 2^14 buckets
 constexpr int HD_L2_BINS = 1 << HD_L1_SHIFT;           // level 2: the low 15 bits
 constexpr int HD_CACHE = 1024;                         // row pass: the first bins of a histogram are counted in LDS, then flushed
@@ -1012,46 +1011,9 @@ __global__ __launch_bounds__(256) void hd_select2_kernel(const int* __restrict__
 }
 
 // ---- the gazed instance as a record: bit mask, class, area, box and COCO run-length code (fs_unwarp_instances) ------------------------
-// The label-free output without a class map.  The mask "class is not K-1" is gathered straight into bit words, 32 columns a word, rows
-// pitched to P = ceil(Ws / 32) words with the bits past Ws clear; the statistics and the run-length code are made from the words, and
-// the class is the head's own decision.  The uncompressed COCO code reads the mask column-major (p = x * Hs + y) and lists the
-// distances between the boundaries T = {p : v[p] != v[p-1]}, v[-1] = 0 (format restated from its published definition; unpinned).
-//   bits     the predicate of every pixel's feeding point, packed as it is gathered (gather_bits: unwarp_bits_kernel), or the same words
-//            from a byte mask (mask_bits_kernel)
-//   count    one thread per (column, RLE_SEG-row segment): the boundaries in it, the position of its last one, its set pixels and
-//            their row range (rle_walk_kernel<false>)
-//   scan     one workgroup per image over its items in column-major order, which is the order of the runs: the exclusive sum of the
-//            boundary counts = where an item's first count goes, the running maximum of the last positions = the boundary before it;
-//            the same sweep sums the area, takes the box, and writes stats and the closing count (rle_scan_kernel)
-//   store    the walk again, storing counts[offset + i] = boundary - the one before, below cap (rle_walk_kernel<true>)
-// Plain stores only: the same bits in any order.  counts is zeroed by the launcher, so everything past the code reads 0.
-constexpr int RLE_SEG = 64;                            // rows per item: 16 items a column at 1024 rows
-
-// Word g of bits (words = B * Hs * P of them) is word i of row = b * Hs + y, the columns 32 i .. 32 i + 31.  LPW lanes make one word,
-// a workgroup 256 / LPW consecutive ones: LPW = 8, lane l of the eight holds the columns x .. x + 3 = 32 i + 4 l .. (Ws % 4 == 0: the
-// quad is inside the row or past its end as a whole); LPW = 32, one lane a column x.  live: the word exists and x < Ws.
-struct BitSlot { long g, row; int x; bool live; };
-template <int LPW>
-__device__ __forceinline__ BitSlot bit_slot(int Ws, int P, long words) {
-  BitSlot s;
-  s.g = (long)blockIdx.x * (256 / LPW) + threadIdx.x / LPW;
-  s.row = s.g / P;
-  s.x = 32 * (int)(s.g - s.row * P) + (32 / LPW) * (int)(threadIdx.x % LPW);
-  s.live = s.g < words && s.x < Ws;
-  return s;
-}
-// The two stores of word g; every thread of the wave calls them.  Eight lanes a word: nib = the flags of the lane's four columns, or-ed
-// over the eight by three shuffles.  One lane a bit: a ballot, two words a wave.  A lane that is not live passes no flag.
-__device__ __forceinline__ void store_word_nibbles(unsigned int* __restrict__ bits, long g, long words, unsigned int nib) {
-  const int l = threadIdx.x & 7;
-  unsigned int wd = nib << (4 * l);
-  wd |= __shfl_xor(wd, 1, 64); wd |= __shfl_xor(wd, 2, 64); wd |= __shfl_xor(wd, 4, 64);
-  if (l == 0 && g < words) bits[g] = wd;
-}
-__device__ __forceinline__ void store_word_ballot(unsigned int* __restrict__ bits, long g, long words, bool f) {
-  const unsigned long long bal = __ballot(f);
-  if ((threadIdx.x & 31) == 0 && g < words) bits[g] = (unsigned int)(bal >> (threadIdx.x & 32));
-}
+// The label-free output without a class map.  The mask "class is not K-1" is gathered straight into bit words (mask_words.h: the layout
+// and the word stores; the padding bits are stored clear), the statistics and the run-length code are made from the words by
+// mask_rle.hip's passes, and the class is the head's own decision.
 // head_fg_q_kernel's packed word of a grid point (the score section below): the foreground flag in the sign bit, q in the rest
 constexpr int SCORE_FG_BIT = 31;
 constexpr int SCORE_Q_MASK = 0x7fffffff;
@@ -1096,12 +1058,6 @@ __global__ __launch_bounds__(256) void unwarp_bits_kernel(const int* __restrict_
                                                           unsigned int* __restrict__ bits, int Hs, int Ws, int P, int hw, int K, long words) {
   gather_bits<VEC, false>(owner, rowx, dec, bits, Hs, Ws, P, hw, K - 1, words);
 }
-// the same words from a byte mask (non-zero = set), any alignment
-__global__ __launch_bounds__(256) void mask_bits_kernel(const unsigned char* __restrict__ mask, unsigned int* __restrict__ bits, int Ws, int P,
-                                                        long words) {
-  const BitSlot sl = bit_slot<32>(Ws, P, words);
-  store_word_ballot(bits, sl.g, words, sl.live && mask[sl.row * Ws + sl.x] != 0);
-}
 // cat[b] = the first maximal k < K-1 of cls[b,k], NaN maximal: unwarp_decide_kernel's comparison on the planes themselves
 __global__ __launch_bounds__(256) void instance_cat_kernel(const float* __restrict__ cls, long long* __restrict__ cat, int B, int K) {
   const int b = blockIdx.x * 256 + threadIdx.x;
@@ -1115,113 +1071,6 @@ __global__ __launch_bounds__(256) void instance_cat_kernel(const float* __restri
   }
   cat[b] = arg;
 }
-// Item (x, s) = rows s * RLE_SEG .. of column x, item index x * S + s: column-major.  Lanes take neighbouring columns of one segment, so a
-// wave reads two words a row.  The pixel above the top of column x > 0 is the bottom of column x - 1; above pixel (0,0) it is 0.
-// STORE = false: cnt[item] = boundaries in the item, last[item] = position of its last one (0 without: no boundary lies before
-// position 0, and positions only grow along the items), st[item] = set pixels | (first set row in the segment) << 8 | (last) << 16.
-// STORE = true: cnt / last hold the scan's results (see rle_scan_kernel), and the item's i-th boundary at position p stores
-// counts[cnt + i] = p - the boundary before it, where cnt + i < cap.
-template <bool STORE>
-__global__ __launch_bounds__(256) void rle_walk_kernel(const unsigned int* __restrict__ bits, int* __restrict__ cnt, int* __restrict__ last,
-                                                       int* __restrict__ st, int* __restrict__ counts, int Hs, int Ws, int P, int S,
-                                                       int blocks_per_image, int cap) {
-  const int b = blockIdx.x / blocks_per_image;
-  const int g = (blockIdx.x - b * blocks_per_image) * 256 + (int)threadIdx.x;
-  const int M = Ws * S;
-  if (g >= M) return;
-  const int s = g / Ws, x = g - s * Ws;
-  const long item = (long)b * M + (long)x * S + s;
-  const unsigned int* ib = bits + (long)b * Hs * P;
-  const unsigned int* col = ib + (x >> 5);
-  const int sh = x & 31;
-  const int y0 = s * RLE_SEG, y1 = min(y0 + RLE_SEG, Hs);
-  unsigned int prev = 0u;
-  if (s > 0) prev = (col[(long)(y0 - 1) * P] >> sh) & 1u;
-  else if (x > 0) prev = (ib[(long)(Hs - 1) * P + ((x - 1) >> 5)] >> ((x - 1) & 31)) & 1u;
-  int n = 0, pos = 0, area = 0, ylo = 0, yhi = 0;
-  int* out = nullptr;
-  if (STORE) { n = cnt[item]; pos = last[item]; out = counts + (long)b * cap; }
-  const int p0 = x * Hs;
-  for (int y = y0; y < y1; ++y) {
-    const unsigned int v = (col[(long)y * P] >> sh) & 1u;
-    if (v != prev) {
-      if (STORE) {
-        if (n < cap) out[n] = p0 + y - pos;
-      }
-      pos = p0 + y;
-      ++n;
-    }
-    if (!STORE && v) {
-      if (area == 0) ylo = y - y0;
-      yhi = y - y0;
-      ++area;
-    }
-    prev = v;
-  }
-  if (!STORE) { cnt[item] = n; last[item] = pos; st[item] = area | ylo << 8 | yhi << 16; }
-}
-// One workgroup per image; thread t owns the items [t * chunk, (t+1) * chunk) of its M = Ws * S.  cnt[item] <- the boundaries before the
-// item, last[item] <- the position of the last boundary before it (0 = none: the code's first count is T[0] - 0).  stats[b] = (area,
-// x0, y0, bw, bh, n_runs) and counts[b, n_runs - 1] = N - the last boundary, where it lies below cap.
-__global__ __launch_bounds__(256) void rle_scan_kernel(int* __restrict__ cnt, int* __restrict__ last, const int* __restrict__ st,
-                                                       long long* __restrict__ stats, int* __restrict__ counts, int Hs, int Ws, int S, int cap) {
-  __shared__ int psum[256], pmax[256];
-  __shared__ long long red[16];
-  __shared__ int box[4];                               // max of: Ws - x, x + 1, Hs - y, y + 1 over the set pixels; 0 = none
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int M = Ws * S;
-  int* c = cnt + (long)b * M;
-  int* l = last + (long)b * M;
-  const int* sp = st + (long)b * M;
-  const int chunk = (M + 255) / 256;
-  const int i0 = min(tid * chunk, M), i1 = min(i0 + chunk, M);
-  if (tid < 4) box[tid] = 0;
-  int sum = 0, mx = 0, bx[4] = {0, 0, 0, 0};
-  long long area = 0;
-  for (int i = i0; i < i1; ++i) {
-    sum += c[i];
-    mx = max(mx, l[i]);
-    const int w = sp[i], a = w & 255;
-    if (a) {
-      const int x = i / S, yb = (i - x * S) * RLE_SEG;
-      area += a;
-      bx[0] = max(bx[0], Ws - x); bx[1] = max(bx[1], x + 1);
-      bx[2] = max(bx[2], Hs - (yb + ((w >> 8) & 255))); bx[3] = max(bx[3], yb + ((w >> 16) & 255) + 1);
-    }
-  }
-  psum[tid] = sum; pmax[tid] = mx;
-  __syncthreads();
-  if (area) {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) atomicMax(&box[q], bx[q]);
-  }
-  if (tid == 0) {                                      // exclusive sum and exclusive running maximum over the 256 chunks
-    int cs = 0, cm = 0;
-    for (int t = 0; t < 256; ++t) {
-      const int vs = psum[t], vm = pmax[t];
-      psum[t] = cs; pmax[t] = cm;
-      cs += vs; cm = max(cm, vm);
-    }
-  }
-  __syncthreads();
-  int run = psum[tid], pm = pmax[tid];
-  for (int i = i0; i < i1; ++i) {
-    const int n = c[i], p = l[i];
-    c[i] = run; l[i] = pm;
-    run += n; pm = max(pm, p);
-  }
-  area = block_sum<long long>(area, red);
-  if (tid == 255) {                                    // its run / pm have passed every item: |T| and T[last]
-    long long* o = stats + (long)b * 6;
-    const bool any = area != 0;
-    o[0] = area;
-    o[1] = any ? Ws - box[0] : 0; o[2] = any ? Hs - box[2] : 0;
-    o[3] = any ? box[1] - (Ws - box[0]) : 0; o[4] = any ? box[3] - (Hs - box[2]) : 0;
-    o[5] = (long long)run + 1;
-    if (run < cap) counts[(long)b * cap + run] = Hs * Ws - pm;
-  }
-}
-
 // ---- the instance's confidence score (fs_head_fg_q, fs_unwarp_instances_scored; no counterpart in the reference: unpinned) -------------
 // A pixel's foreground probability is the softmax mass of the classes below K-1 among the K values v[k] that unwarp_nearest(pred)
 // holds there -- the values unwarp_decide_kernel takes the argmax of, so one number per feeding point: qt[b,p] = rint(2^24 * P),
@@ -1373,8 +1222,7 @@ __global__ __launch_bounds__(256) void component_qsum_kernel(const int* __restri
   if (g < words) {
     const long row = g / P;
     const int c = (int)(g - row * P);
-    unsigned int wd = cbits[g];
-    if (c == P - 1 && (Ws & 31)) wd &= (1u << (Ws & 31)) - 1u;
+    unsigned int wd = cbits[g] & mask_tail(c, P, Ws);
     tb = row / Hs;
     if (wd != 0u) {
       const int y = (int)(row - tb * Hs);
@@ -1397,8 +1245,7 @@ __global__ __launch_bounds__(256) void component_qsum_kernel(const int* __restri
 }
 
 // ---- host: one plan, one job, one launcher -------------------------------------------------------------------------------------------
-constexpr long INT_LIMIT = 2147483647L;                // pixel / point indices are ints
-constexpr long THREADS_MAX = 4294967295L - 255;        // every launch: fewer than 2^32 work-items
+constexpr long INT_LIMIT = 2147483647L;                // pixel / point indices are ints (grid points and byte pitches too: not MASK_INT_LIMIT)
 constexpr long TRI_WGS_MAX = 16777215L;                // the trimap passes' workgroups (256 threads each: fewer than 2^32 work-items)
 inline bool row_fits_lds(int Ws) { return Ws <= 16384; }       // fill_row_nearest_kernel keeps one row of column indices in LDS
 inline long align4(long v) { return (v + 3) & ~3L; }           // ints: the next 16-byte boundary
@@ -1435,27 +1282,8 @@ SurfacePlan surface_plan(int B, int Hs, int Ws) {
   s.nb1 = (maxd2 >> HD_L1_SHIFT) + 1, s.nb2 = maxd2 + 1 < HD_L2_BINS ? maxd2 + 1 : HD_L2_BINS;
   s.g = 0, s.cnt = align4(s.n), s.sel = s.cnt + 2L * B, s.h1 = s.sel + 4L * B, s.h2 = s.h1 + (long)B * s.nb1;
   s.total = s.h2 + 2L * B * s.nb2;
-  s.ok = Hs <= HD_MAX_SIDE && Ws <= HD_MAX_SIDE && (long)B * Hs * 256 <= THREADS_MAX && (long)B * cdiv(Ws, 256) * 256 <= THREADS_MAX;
+  s.ok = Hs <= MASK_MAX_SIDE && Ws <= MASK_MAX_SIDE && (long)B * Hs * 256 <= THREADS_MAX && (long)B * cdiv(Ws, 256) * 256 <= THREADS_MAX;
   return s;
-}
-
-// fs_mask_bits' / fs_mask_rle's sizes.  Scratch of the run-length passes, in ints: cnt, last, st, each [B][M], M = Ws * S items an image.
-struct RlePlan {
-  long P, words;                                       // words per row, of the batch
-  long S, M, bpi;                                      // segments per column, items and walk workgroups per image
-  long cnt, last, st, total;
-  bool bits_ok, ok;                                    // launchable: the bit packing, the run-length passes
-};
-RlePlan rle_plan(int B, int Hs, int Ws) {
-  RlePlan r = {};
-  if (!(B > 0 && Hs > 0 && Ws > 0)) return r;
-  r.P = cdiv(Ws, 32), r.words = (long)B * Hs * r.P;
-  r.S = cdiv(Hs, RLE_SEG), r.M = (long)Ws * r.S, r.bpi = cdiv(r.M, 256);
-  r.cnt = 0, r.last = (long)B * r.M, r.st = 2 * r.last, r.total = 3 * r.last;
-  r.bits_ok = r.words * 32 <= THREADS_MAX;             // one lane a bit slot in the ballot kernels
-  // positions and counts are ints: N < 2^31 (so M is one too)
-  r.ok = (long)Hs * Ws <= INT_LIMIT && (long)B * r.bpi * 256 <= THREADS_MAX;
-  return r;
 }
 
 // What a call computes on top of the class-map gather.  UW_COUNT: the gather counts (fs_unwarp_accuracy); UW_TRIM / UW_AREA: it also
@@ -1587,30 +1415,6 @@ int surface_launch(const SurfacePlan& sp, const unsigned char* fg, long long* hd
                      (int)sp.nb2);
   FS_LAUNCH_CHECK();
   hipLaunchKernelGGL(hd_select2_kernel, dim3((unsigned)B), dim3(256), 0, stream, s + sp.cnt, s + sp.h2, s + sp.sel, hd, (int)sp.nb2);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
-int mask_bits_launch(const RlePlan& r, const unsigned char* mask, unsigned int* bits, int Ws, hipStream_t stream) {
-  hipLaunchKernelGGL(mask_bits_kernel, dim3(cdiv(r.words, 8)), dim3(256), 0, stream, mask, bits, Ws, (int)r.P, r.words);
-  FS_LAUNCH_CHECK();
-  return FS_OK;
-}
-
-// zeroed counts, then count, scan, store
-int rle_launch(const RlePlan& r, const unsigned int* bits, long long* stats, int* counts, int* s, int B, int Hs, int Ws, int cap,
-               hipStream_t stream) {
-  const hipError_t e = hipMemsetAsync(counts, 0, sizeof(int) * (size_t)B * cap, stream);
-  if (e != hipSuccess) return (int)e;
-  const dim3 grid((unsigned)(B * r.bpi));
-  hipLaunchKernelGGL(rle_walk_kernel<false>, grid, dim3(256), 0, stream, bits, s + r.cnt, s + r.last, s + r.st, counts, Hs, Ws, (int)r.P,
-                     (int)r.S, (int)r.bpi, cap);
-  FS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rle_scan_kernel, dim3((unsigned)B), dim3(256), 0, stream, s + r.cnt, s + r.last, s + r.st, stats, counts, Hs, Ws, (int)r.S,
-                     cap);
-  FS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rle_walk_kernel<true>, grid, dim3(256), 0, stream, bits, s + r.cnt, s + r.last, s + r.st, counts, Hs, Ws, (int)r.P,
-                     (int)r.S, (int)r.bpi, cap);
   FS_LAUNCH_CHECK();
   return FS_OK;
 }
@@ -1842,19 +1646,6 @@ int fs_unwarp_hd(const float* cls, const float* m, const float* grid, const floa
                  int D, int frame, int q, hipStream_t stream) {
   return unwarp_run(unwarp_plan(B, K, h, w, Hs, Ws, UW_COUNT | UW_HD | (areas ? UW_AREA : 0) | (trim ? UW_TRIM : 0)),
                     {cls, m, grid, scratch, {labels}, {y, cls_label, counts, acc}, {trim, D, frame}, {areas}, {hd, q}}, stream);
-}
-
-int fs_mask_bits(const unsigned char* mask, unsigned int* bits, int B, int Hs, int Ws, hipStream_t stream) {
-  const RlePlan r = rle_plan(B, Hs, Ws);
-  FS_REQUIRE(mask && bits && r.bits_ok);
-  return mask_bits_launch(r, mask, bits, Ws, stream);
-}
-
-long fs_mask_rle_scratch_ints(int B, int Hs, int Ws) { return rle_plan(B, Hs, Ws).total; }
-int fs_mask_rle(const unsigned int* bits, long long* stats, int* counts, int* scratch, int B, int Hs, int Ws, int cap, hipStream_t stream) {
-  const RlePlan r = rle_plan(B, Hs, Ws);
-  FS_REQUIRE(bits && stats && counts && scratch && r.ok && cap >= 1);
-  return rle_launch(r, bits, stats, counts, scratch, B, Hs, Ws, cap, stream);
 }
 
 long fs_unwarp_instances_scratch_ints(int B, int h, int w, int Hs, int Ws) { return unwarp_plan(B, 2, h, w, Hs, Ws, UW_BITS).total; }

@@ -124,7 +124,7 @@ def test_max_runs_argument():
 GUARD = 64
 SENTINEL = -0x5A5A5A5B
 GARBAGE = 0x3C3C3C3D
-RLE_SEG = 64                                             # csrc/unwarp.hip: rows per (column, segment) item of the run-length passes
+RLE_SEG = 64                                             # csrc/mask_rle.hip: rows per (column, segment) item of the run-length passes
 
 
 class Guarded:

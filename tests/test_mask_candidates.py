@@ -17,6 +17,7 @@ from fovealseg import hip, ops
 from fovealseg import train as T
 
 import candidates_ref as CR
+import component_ref as CP
 import poly_ref as PR
 import rle_ref as R
 
@@ -725,3 +726,117 @@ def test_score_coco_records_with_a_gaze():
     assert torch.equal(torch.cat(new.rows), torch.cat(old.rows)) and torch.equal(torch.cat(whole.rows), torch.cat(old.rows))
     res = new.result()
     assert res["n_images"] == 12 and 8 <= res["n_records"] <= 11 and res["mIoU"] > 0.0
+
+
+# ------------------------------------------------------------- the component's seed and the candidate choice: one gaze pixel, one key ----
+AGREE_SIZES = [(1, 1), (1, 70), (8, 32), (8, 33), (9, 7), (37, 300)]   # one word; a tail word; a word boundary; a row beyond a wave's words
+
+
+def _exact_gazes(side):
+    """The fp32 focus values whose 1/16-pixel product is exact: (k + 0.5 for an even k, for an odd k, 16 j + 8), or None for side 1,
+    where every product is 0.  side - 1 = odd * 2^e: i / 2^(e+5) gives odd * i / 2, i / 2^(e+1) gives 8 * odd * i -- dyadic, so exact."""
+    if side == 1:
+        return None
+    odd, e = side - 1, 0
+    while odd % 2 == 0:
+        odd, e = odd // 2, e + 1
+    a, b, c = 1.0 / 2 ** (e + 5), 3.0 / 2 ** (e + 5), 1.0 / 2 ** (e + 1)
+    top = float((side - 1) * 16)
+    ka, kb = (odd - 1) // 2, (3 * odd - 1) // 2
+    assert all(float(np.float32(v)) == v and v <= 1.0 for v in (a, b, c)) and (ka + kb) % 2 == 1
+    assert a * top == ka + 0.5 and b * top == kb + 0.5 and c * top == 8 * odd and (8 * odd) % 16 == 8
+    even, other = (a, b) if ka % 2 == 0 else (b, a)
+    return even, other, c
+
+
+def _agree_gazes(Hs, Ws):
+    """(row, col) focus pairs: the corners, rint's ties to an even and to an odd k on either axis, the pixel-rounding tie, NaN and values
+    outside [0, 1]"""
+    ey, ex = _exact_gazes(Hs) or (0.5, 0.5, 0.5), _exact_gazes(Ws) or (0.5, 0.5, 0.5)
+    nan = float("nan")
+    return [(0.0, 0.0), (0.0, 1.0), (1.0, 0.0), (1.0, 1.0), (ey[0], ex[1]), (ey[1], ex[0]), (ey[2], ex[2]), (nan, nan), (nan, 0.5),
+            (-0.25, 1.5), (1.5, -0.25)]
+
+
+def test_the_tie_gazes_are_ties():
+    """rint goes to the even neighbour on both kinds of tie, and the pixel tie 16 j + 8 goes up to pixel j + 1: on the references, whose
+    two restatements of the gaze must be one function"""
+    for side in sorted({v for hw in AGREE_SIZES for v in hw} - {1}):
+        even, other, c = _exact_gazes(side)
+        top = (side - 1) * 16
+        for f in (even, other):
+            k = int(math.floor(f * top))
+            assert CP.gaze(f, side) == CR.gaze(f, side) == (k if k % 2 == 0 else k + 1)
+        assert int(math.floor(even * top)) % 2 == 0 and int(math.floor(other * top)) % 2 == 1
+        g = CP.gaze(c, side)
+        assert g == CR.gaze(c, side) and g % 16 == 8 and CP.gaze_pixel((c, c), side, side) == ((g >> 4) + 1,) * 2
+    for f in (float("nan"), -0.25, 1.5, 0.0, 1.0):
+        assert all(CP.gaze(f, side) == CR.gaze(f, side) for side in (1, 7, 300))
+
+
+_AGREE = {}
+
+
+def _agree_case(Hs, Ws):
+    """B = 3 seeded masks of a size (density 0.02, 0.5 and an empty one), and for every gaze the two references' answers, made once:
+    (focus (3,2), snap2, comp (3,4) of component_ref, (sel, cand) of candidates_ref with one candidate an image equal to the mask)"""
+    if (Hs, Ws) not in _AGREE:
+        rng = np.random.default_rng(4000 * Hs + Ws)
+        masks = np.stack([rng.random((Hs, Ws)) < 0.02, rng.random((Hs, Ws)) < 0.5, np.zeros((Hs, Ws), dtype=bool)])
+        rows = []
+        for k, fo in enumerate(_agree_gazes(Hs, Ws)):
+            focus = np.array([fo] * 3, dtype=np.float32)
+            snap2 = CR.OFF2 if k % 2 == 0 else 2                                 # every other gaze with a snap distance of sqrt(2)
+            _c, comp = CP.component_batch(masks, focus, 8, snap2)
+            _g, sel, cand = CR.candidates(masks, [0, 1, 2, 3], focus, snap2=snap2)
+            rows.append((focus, snap2, comp, sel, cand))
+        _AGREE[(Hs, Ws)] = (masks, rows)
+    return _AGREE[(Hs, Ws)]
+
+
+def _agree(comp, sel, cand, snap2):
+    """fs_mask_component's comp rows and fs_mask_candidates' rows of one candidate an image say the same: the nearest pixel and its
+    squared distance (none for an empty mask), the area, and the seed is taken where the selection is"""
+    for b in range(3):
+        sy, sx, d2, area = (int(v) for v in comp[b])
+        assert cand[b].tolist()[:2] == [b, area] and area == int(sel[b, 3] if sel[b, 0] >= 0 else cand[b, 1])
+        assert (sel[b, 0] >= 0) == (sy >= 0) == (area > 0 and int(cand[b, 3]) <= snap2)
+        if sy >= 0:
+            assert [d2, sy, sx] == cand[b].tolist()[3:] and int(sel[b, 0]) == b and int(sel[b, 2]) == d2
+        else:
+            assert [sy, sx, d2] == [-1, -1, -1] and sel[b].tolist()[:3] == [-1, -1, -1]
+            assert (area == 0) == (cand[b].tolist()[3:] == [-1, -1, -1])
+
+
+@pytest.mark.parametrize("Hs,Ws", AGREE_SIZES)
+def test_reference_seed_and_candidate_choice_agree(Hs, Ws):
+    """component_ref and candidates_ref, written apart, on the inputs of the device test below"""
+    masks, rows = _agree_case(Hs, Ws)
+    seen = set()
+    for focus, snap2, comp, sel, cand in rows:
+        _agree(comp, sel, cand, snap2)
+        assert CP.gaze_pixel(focus[0], Hs, Ws) == CR.gaze_pixel(focus[0], Hs, Ws)
+        seen |= {(int(comp[b, 0]) >= 0, int(comp[b, 3]) > 0) for b in range(3)}
+    assert (False, False) in seen and ((True, True) in seen or Hs * Ws == 1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("Hs,Ws", AGREE_SIZES)
+def test_component_seed_and_candidate_choice_agree(Hs, Ws):
+    """One candidate an image equal to the mask: fs_mask_component's seed and fs_mask_candidates' nearest pixel are the same pixel at
+    the same squared distance with the same area, for gazes on the corners, on both kinds of rounding tie, NaN and outside [0, 1] --
+    and each is its own reference's."""
+    masks, rows = _agree_case(Hs, Ws)
+    rng = np.random.default_rng(Hs + Ws)
+    words = _garbage(np.stack([R.bits(m) for m in masks]), Ws, rng)
+    bits = torch.from_numpy(words).cuda()
+    need = hip.query("fs_mask_component_scratch_ints", 3, Hs, Ws)
+    for focus, snap2, wcomp, wsel, wcand in rows:
+        out, comp, scr = Buf(words.size), Buf(12, torch.int64), Buf(need)
+        f = torch.from_numpy(focus).cuda()
+        hip.call("fs_mask_component", bits.data_ptr(), f.data_ptr(), out.ptr, comp.ptr, scr.ptr, 3, Hs, Ws, 8, snap2)
+        torch.cuda.synchronize()
+        comp = comp.get(True).numpy().reshape(3, 4)
+        _gb, sel, cand = _abi(words, [0, 1, 2, 3], focus, Ws, snap2=snap2)
+        assert np.array_equal(comp, wcomp) and np.array_equal(sel, wsel) and np.array_equal(cand, wcand), (focus[0].tolist(), snap2)
+        _agree(comp, sel, cand, snap2)
