@@ -132,6 +132,7 @@ __device__ __forceinline__ void overlay_px(const F& f, const OverlayArgs& A, con
 // 16-byte loads of an fp32 frame, each value's code taken as it arrives.
 template <class F>
 __device__ __forceinline__ void overlay_load16(const F& f, const unsigned char* a, u32x4* v) { f.load16(a, v); }
+__device__ __forceinline__ void overlay_load16(const Nv12Frame& f, const Nv12Px& a, u32x4* v) { f.load16(a, v); }
 __device__ __forceinline__ void overlay_load16(const PlanarFrame<float>& f, const float* a, u32x4* v) {
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
@@ -238,6 +239,25 @@ __global__ __launch_bounds__(OVL_THREADS) void overlay_hwc_wide_kernel(const uns
   overlay_wide(HwcFrame<SX>(img, sb, sy, SX), A, FrameWriter<OX>(out, ob, oy, OX, H, W), H, W, bpi);
 }
 
+__global__ __launch_bounds__(OVL_THREADS) void overlay_nv12_kernel(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy,
+                                                                   Nv12Csc k, OverlayArgs A, unsigned char* out, long ob, long oy, int ox, int H,
+                                                                   int W, unsigned int bpi) {
+  overlay_px(Nv12Frame(yp, uvp, sb, sy, ub, uy, k), A, FrameWriter<0>(out, ob, oy, ox, H, W), H, W, bpi);
+}
+template <int OX>
+__global__ __launch_bounds__(OVL_THREADS) void overlay_nv12_wide_kernel(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub,
+                                                                        long uy, Nv12Csc k, OverlayArgs A, unsigned char* out, long ob, long oy,
+                                                                        int H, int W, unsigned int bpi) {
+  overlay_wide(Nv12Frame(yp, uvp, sb, sy, ub, uy, k), A, FrameWriter<OX>(out, ob, oy, OX, H, W), H, W, bpi);
+}
+
+// is out the frame's own memory?  (an NV12 frame is never what the pass writes: out at either of its planes is refused, since no
+// destination has its description)
+template <class F>
+bool overlay_in_place(const F& f, const unsigned char* out) { return (const void*)f.p == (const void*)out; }
+bool overlay_in_place(const Nv12Frame& f, const unsigned char* out) { return out == f.yp || out == f.uvp; }
+bool overlay_same(const Nv12Frame&, const FrameWriter<0>&, int, int, int) { return false; }
+
 // out may be img only where the two descriptions are the same (an image step counts where there is more than one image)
 bool overlay_same(const PlanarFrame<float>&, const FrameWriter<0>&, int, int, int) { return false; }
 bool overlay_same(const PlanarFrame<unsigned char>&, const FrameWriter<0>& o, int B, int H, int W) {
@@ -277,6 +297,19 @@ void overlay_launch(const HwcFrame<0>& f, const FrameWriter<0>& o, bool wide, di
   else overlay_launch_hwc_wide<4>(f, o, grid, stream, A, H, W, bpi);
 }
 
+void overlay_launch(const Nv12Frame& f, const FrameWriter<0>& o, bool wide, dim3 grid, hipStream_t stream, const OverlayArgs& A, int H, int W,
+                    unsigned int bpi) {
+  const dim3 block(OVL_THREADS);
+  if (!wide)
+    hipLaunchKernelGGL(overlay_nv12_kernel, grid, block, 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, A, o.p, o.ob, o.oy, o.ox, H, W, bpi);
+  else if (o.ox == 1)
+    hipLaunchKernelGGL(overlay_nv12_wide_kernel<1>, grid, block, 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, A, o.p, o.ob, o.oy, H, W, bpi);
+  else if (o.ox == 3)
+    hipLaunchKernelGGL(overlay_nv12_wide_kernel<3>, grid, block, 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, A, o.p, o.ob, o.oy, H, W, bpi);
+  else
+    hipLaunchKernelGGL(overlay_nv12_wide_kernel<4>, grid, block, 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, A, o.p, o.ob, o.oy, H, W, bpi);
+}
+
 bool overlay_sizes_ok(int B, int H, int W) {
   return B > 0 && H > 0 && W > 0 && H <= MASK_MAX_SIDE && W <= MASK_MAX_SIDE && (long)H * W < MASK_INT_LIMIT;
 }
@@ -287,7 +320,7 @@ int overlay_run(const F& f, const OverlayArgs& A, unsigned char* out, long ob, l
   const FrameWriter<0> o(out, ob, oy, ox, H, W);
   FS_REQUIRE(f && A.bits && A.style && out && overlay_sizes_ok(B, H, W) && (A.S == 1 || A.S == B));
   FS_REQUIRE(f.ok(B, H, W) && o.ok(B, H, W) && (A.live == nullptr || A.live_stride >= 1));
-  FS_REQUIRE((const void*)f.p != (const void*)out || overlay_same(f, o, B, H, W));
+  FS_REQUIRE(!overlay_in_place(f, out) || overlay_same(f, o, B, H, W));
   const bool wide = f.wide(W) && o.wide(W);             // the writer's W % 16 == 0 goes for an fp32 frame too, whose own rule is W % 4
   const long bpi = ((long)H * (wide ? W / 16 : W) + OVL_THREADS - 1) / OVL_THREADS;
   FS_REQUIRE((long)B * bpi < MASK_INT_LIMIT);
@@ -365,6 +398,14 @@ int fs_frame_overlay_hwc(const unsigned char* img, long sb, long sy, int sx, con
                          unsigned char* out, long ob, long oy, int ox, int B, int H, int W, hipStream_t stream) {
   const OverlayArgs A = {bits, band, stats, focus, live, live_stride, style, S};
   return overlay_run(HwcFrame<0>(img, sb, sy, sx), A, out, ob, oy, ox, B, H, W, stream);
+}
+
+int fs_frame_overlay_nv12(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu,
+                          int gv, int bu, const unsigned int* bits, const unsigned int* band, const long long* stats, const float* focus,
+                          const long long* live, long live_stride, const int* style, int S, unsigned char* out, long ob, long oy, int ox, int B,
+                          int H, int W, hipStream_t stream) {
+  const OverlayArgs A = {bits, band, stats, focus, live, live_stride, style, S};
+  return overlay_run(Nv12Frame(yp, uvp, sb, sy, ub, uy, Nv12Csc{yo, yg, rv, gu, gv, bu}), A, out, ob, oy, ox, B, H, W, stream);
 }
 
 int fs_color_encode(const long long* labels, const unsigned char* palette, unsigned char* out, long ob, long oy, int ox, int B, int H, int W,

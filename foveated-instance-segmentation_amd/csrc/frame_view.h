@@ -1,5 +1,5 @@
-// A frame a pass can read.  A (B,3,H,W) frame comes in three layouts, and every pass that takes one (gaze_gate.hip: tiles, commit;
-// gaze_motion.hip: profiles, move; frames_u8.hip: the network's front) is written once, over a reader of the layout:
+// A frame a pass can read.  A (B,3,H,W) frame comes in four layouts, and every pass that takes one (gaze_gate.hip: tiles, commit;
+// gaze_motion.hip: profiles, move; frames_u8.hip: the network's front; frame_overlay.hip) is written once, over a reader of the layout:
 //   PlanarFrame<float>           fp32, the value of channel c at (b, y, x) is p[(b * 3 + c) * H * W + y * W + x]; its code is q(value)
 //   PlanarFrame<unsigned char>   bytes in the same order; the pixel value is byte / 255, whose code is the byte
 //   HwcFrame<SX>                 interleaved bytes read where they lie (fs_*_hwc; include/fovealseg.h "frames as interleaved bytes"): the
@@ -7,6 +7,9 @@
 //                                fourth byte never read into a result), rows of any pitch sy >= W * sx, images sb apart or all one image
 //                                (sb = 0).  SX = 3 or 4 where the pass knows the step at compile time (the vector forms), 0 for the sx
 //                                given at run time (the one-pixel forms).
+//   Nv12Frame                    a decoder's surface read where it lies (fs_*_nv12; include/fovealseg.h "frames as NV12"): a luma plane and a
+//                                plane of interleaved chroma at half the resolution; the pixel's RGB byte, a fixed integer function of
+//                                (Y, U, V), is its code.  A pixel's position is an Nv12Px, not one pointer: the passes hold it as `auto`.
 // A reader is built inside the kernel from the kernel's own pointer and scalars, and on the host from an entry point's arguments.  On the
 // device it offers the few reads the passes use, all from a pixel's address px(b, y, x): the code of a channel, the luma codes of four
 // pixels from aligned loads, sixteen bytes a channel in planar order (bytes only), and a tap's value (float)byte / 255, correctly rounded
@@ -183,6 +186,140 @@ struct HwcFrame {
   long route(int W) const {
     if (!row_ok(W)) return -1;
     return (W % 16 == 0 && ((uintptr_t)p & 15) == 0 && sy % 16 == 0 && sb % 16 == 0) ? 1 : 0;
+  }
+  bool wide(int W) const { return route(W) == 1; }
+  bool wide_commit(int W, size_t) const { return wide(W); }
+  bool quad(int W) const { return wide(W); }
+};
+
+// An NV12 frame, as a video decoder or a camera makes it (fs_*_nv12; include/fovealseg.h "frames as NV12"): a plane of luma bytes, Y of
+// (b, y, x) = yp[b * sb + y * sy + x], and a plane of interleaved chroma at half the resolution both ways, (U, V) of (b, y, x) = uvp[b * ub +
+// (y >> 1) * uy + 2 * (x >> 1) + (0, 1)]: the sample of the pixel's 2 x 2 block, replicated.  Rows of any pitch sy >= W, uy >= 2 * ceil(W /
+// 2); images apart or all one image (sb = ub = 0).  The RGB byte of a pixel is a fixed integer function of (Y, U, V) and the table csc
+// (nv12_rgb below), that byte is the pixel's code and byte / 255 its value: every pass gives on an NV12 frame what it gives on the planar
+// frame of those bytes, bit for bit.
+struct Nv12Csc {
+  int yo, yg, rv, gu, gv, bu;
+  // no sum of nv12_rgb leaves int32: |yg * C| + 2 * 32768 * 128 + 128 < 2^25
+  bool ok() const {
+    const int co[5] = {yg, rv, gu, gv, bu};
+    for (int c : co)
+      if (c < -32768 || c > 32768) return false;
+    return yo >= 0 && yo <= 255;
+  }
+};
+// A pixel's position: where its luma byte and its chroma pair lie, and the parities of its column (bit 0) and row (bit 1), which say
+// when a step right or down reaches the next chroma sample.
+struct Nv12Px {
+  const unsigned char* lu;
+  const unsigned char* ch;
+  int par;
+};
+
+// the chroma products of one sample, made once for the two or four pixels that share it
+struct Nv12Chroma {
+  int r, g, b;
+};
+__device__ __forceinline__ Nv12Chroma nv12_chroma(const Nv12Csc& k, int U, int V) {
+  const int D = U - 128, E = V - 128;
+  return Nv12Chroma{k.rv * E, k.gu * D + k.gv * E, k.bu * D};
+}
+// clamp(v >> 8, 0, 255), written as the clamp first and the shift after it: v < 0 -> 0, v >= 65536 -> 65535 >> 8 = 255, v >> 8 between.
+// Spelled the other way round, two neighbours OR-ed into one word are selected as v_ashr_pk_u8_i32 (gfx950), whose result the compiler
+// takes to have sixteen zero bits on top; on the hardware the pixels above a negative sum then read 255 (profiles/r35/README.md).
+// Do not simplify it back.  Nothing but the compiler's choice keeps that instruction away from this spelling: after a change of
+// toolchain, test_nv12_to_rgb_over_all_triplets (tests/test_frames_nv12.py, on the GPU) is what says whether it still does.
+__device__ __forceinline__ int nv12_clamp(int v) { return min(max(v, 0), 65535) >> 8; }
+// R, G, B = clamp((yg * (Y - yo) + the channel's chroma product + 128) >> 8, 0, 255), >> the arithmetic shift
+__device__ __forceinline__ void nv12_rgb(const Nv12Csc& k, int Y, const Nv12Chroma& m, int& r, int& g, int& b) {
+  const int l = k.yg * (Y - k.yo) + 128;
+  r = nv12_clamp(l + m.r), g = nv12_clamp(l + m.g), b = nv12_clamp(l + m.b);
+}
+
+struct Nv12Frame {
+  static constexpr int lane = 48;                                 // commit's vector form: sixteen pixels, sixteen key bytes a channel
+  const unsigned char* yp;
+  const unsigned char* uvp;
+  long sb, sy, ub, uy;
+  Nv12Csc k;
+  __host__ __device__ Nv12Frame(const unsigned char* yp_, const unsigned char* uvp_, long sb_, long sy_, long ub_, long uy_, const Nv12Csc& k_)
+      : yp(yp_), uvp(uvp_), sb(sb_), sy(sy_), ub(ub_), uy(uy_), k(k_) {}
+
+  // y >> 1 and x >> 1 are arithmetic: a position one step outside the frame (a tap never read) steps back into it by right / down
+  __device__ __forceinline__ Nv12Px px(size_t b, int y, int x) const {
+    return Nv12Px{yp + b * (size_t)sb + (long)y * sy + x, uvp + b * (size_t)ub + (long)(y >> 1) * uy + 2 * (long)(x >> 1), (x & 1) | ((y & 1) << 1)};
+  }
+  __device__ __forceinline__ Nv12Px down(const Nv12Px& a, int rows) const {                // rows >= 0
+    const int n = (a.par >> 1) + rows;
+    return Nv12Px{a.lu + (size_t)rows * sy, a.ch + (size_t)(n >> 1) * uy, (a.par & 1) | ((n & 1) << 1)};
+  }
+  __device__ __forceinline__ Nv12Px right(const Nv12Px& a, int cols) const {               // cols >= 0
+    const int n = (a.par & 1) + cols;
+    return Nv12Px{a.lu + cols, a.ch + 2 * (size_t)(n >> 1), (a.par & 2) | (n & 1)};
+  }
+  __device__ __forceinline__ int code(const Nv12Px& a, int c) const {
+    int r, g, bl;
+    nv12_rgb(k, (int)a.lu[0], nv12_chroma(k, (int)a.ch[0], (int)a.ch[1]), r, g, bl);
+    return c == 0 ? r : c == 1 ? g : bl;
+  }
+  __device__ __forceinline__ int code_of(size_t b, size_t, int c, int y, int x) const { return code(px(b, y, x), c); }       // (c, y, x) are used
+  // Four pixels of a row, x a multiple of 4 and the vector form's alignment: 4 luma bytes and their two chroma pairs, a 4-byte load each
+  __device__ __forceinline__ void luma4(const Nv12Px& a, int* l) const {
+    const unsigned int y4 = *reinterpret_cast<const unsigned int*>(a.lu), c4 = *reinterpret_cast<const unsigned int*>(a.ch);
+#pragma unroll
+    for (int p = 0; p < 2; ++p) {
+      const Nv12Chroma m = nv12_chroma(k, (int)((c4 >> (16 * p)) & 255u), (int)((c4 >> (16 * p + 8)) & 255u));
+#pragma unroll
+      for (int j = 2 * p; j < 2 * p + 2; ++j) {
+        int r, g, bl;
+        nv12_rgb(k, (int)((y4 >> (8 * j)) & 255u), m, r, g, bl);
+        l[j] += r + g + bl;
+      }
+    }
+  }
+  // Sixteen pixels of a row, x a multiple of 16 and the vector form's alignment: one 16-byte load of luma and one of chroma, its eight
+  // samples' products made once each; v[c] = the sixteen bytes of channel c in planar order
+  __device__ __forceinline__ void load16(const Nv12Px& a, u32x4* v) const {
+    const u32x4 y16 = *reinterpret_cast<const u32x4*>(a.lu), c16 = *reinterpret_cast<const u32x4*>(a.ch);
+    const unsigned int yw[4] = {y16.x, y16.y, y16.z, y16.w}, cw[4] = {c16.x, c16.y, c16.z, c16.w};
+    unsigned int o[3][4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {                       // luma word q: pixels 4q .. 4q + 3, the chroma pairs of word q
+      unsigned int w[3] = {0u, 0u, 0u};
+#pragma unroll
+      for (int p = 0; p < 2; ++p) {
+        const Nv12Chroma m = nv12_chroma(k, (int)((cw[q] >> (16 * p)) & 255u), (int)((cw[q] >> (16 * p + 8)) & 255u));
+#pragma unroll
+        for (int j = 2 * p; j < 2 * p + 2; ++j) {
+          int r, g, bl;
+          nv12_rgb(k, (int)((yw[q] >> (8 * j)) & 255u), m, r, g, bl);
+          w[0] |= (unsigned int)r << (8 * j), w[1] |= (unsigned int)g << (8 * j), w[2] |= (unsigned int)bl << (8 * j);
+        }
+      }
+      o[0][q] = w[0], o[1][q] = w[1], o[2][q] = w[2];
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = u32x4{o[c][0], o[c][1], o[c][2], o[c][3]};
+  }
+  __device__ __forceinline__ float tap(const Nv12Px& a, int c) const { return __fdiv_rn((float)code(a, c), 255.0f); }
+
+  explicit operator bool() const { return yp != nullptr && uvp != nullptr; }
+  // a row of W pixels and its chroma row can be read, and the table keeps every sum in int32
+  bool row_ok(int W) const {
+    return yp != nullptr && uvp != nullptr && W > 0 && sy >= (long)W && uy >= 2 * (((long)W + 1) / 2) && sb >= 0 && ub >= 0 && k.ok();
+  }
+  // what every fs_*_nv12 entry point asks of the description beyond its twin's conditions: rows, and images that do not overlap in either
+  // plane or are all one image
+  bool ok(int B, int H, int W) const {
+    if (!row_ok(W) || H <= 0) return false;
+    if (B <= 1 || (sb == 0 && ub == 0)) return true;
+    return sb >= (long)H * sy && ub >= (((long)H + 1) / 2) * uy;
+  }
+  // fs_nv12_frame_route: -1 no readable row, 1 the vector forms (every 16-pixel piece of every luma row and its 16 chroma bytes start at
+  // a multiple of 16 bytes), 0 the one-pixel forms
+  long route(int W) const {
+    if (!row_ok(W)) return -1;
+    return (W % 16 == 0 && (((uintptr_t)yp | (uintptr_t)uvp) & 15) == 0 && sy % 16 == 0 && sb % 16 == 0 && uy % 16 == 0 && ub % 16 == 0) ? 1 : 0;
   }
   bool wide(int W) const { return route(W) == 1; }
   bool wide_commit(int W, size_t) const { return wide(W); }

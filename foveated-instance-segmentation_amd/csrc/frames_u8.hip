@@ -74,6 +74,12 @@ __global__ __launch_bounds__(256) void gaze_lowres_hwc_kernel(const unsigned cha
   gaze_lowres_bytes(HwcFrame<0>(x, sb, sy, sx), focus, out, B, H, W, hs, ws);
 }
 
+__global__ __launch_bounds__(256) void gaze_lowres_nv12_kernel(const unsigned char* __restrict__ yp, const unsigned char* __restrict__ uvp, long sb,
+                                                               long sy, long ub, long uy, Nv12Csc k, const float* __restrict__ focus,
+                                                               float* __restrict__ out, int B, int H, int W, int hs, int ws) {
+  gaze_lowres_bytes(Nv12Frame(yp, uvp, sb, sy, ub, uy, k), focus, out, B, H, W, hs, ws);
+}
+
 // C channels of image b, f the reader of that image alone -> point i of out (B,h,w,C) NHWC [nhwc_out=1] or (B,C,h,w) NCHW [nhwc_out=0],
 // fp32: sample_plane's taps and chain (grid_taps.h), a tap's address formed always and read only where the tap is inside
 template <class F>
@@ -104,6 +110,15 @@ __global__ __launch_bounds__(256) void grid_sample_hwc_kernel(const unsigned cha
   if (i >= (long)B * h * w) return;
   const int b = (int)(i / ((long)h * w));
   grid_sample_bytes(HwcFrame<0>(x + (long)b * sb, sb, sy, sx), grid, out, i, b, 3, H, W, h, w, nhwc_out);
+}
+
+__global__ __launch_bounds__(256) void grid_sample_nv12_kernel(const unsigned char* __restrict__ yp, const unsigned char* __restrict__ uvp, long sb,
+                                                               long sy, long ub, long uy, Nv12Csc k, const float* __restrict__ grid,
+                                                               float* __restrict__ out, int B, int H, int W, int h, int w, int nhwc_out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)B * h * w) return;
+  const int b = (int)(i / ((long)h * w));
+  grid_sample_bytes(Nv12Frame(yp + (long)b * sb, uvp + (long)b * ub, sb, sy, ub, uy, k), grid, out, i, b, 3, H, W, h, w, nhwc_out);
 }
 
 }  // namespace
@@ -141,6 +156,26 @@ int fs_grid_sample_u8_fwd(const unsigned char* x, const float* grid, float* out,
                           hipStream_t stream) {
   FS_REQUIRE(x && grid && out && B > 0 && C > 0 && H > 0 && W > 0 && h > 0 && w > 0);
   hipLaunchKernelGGL(grid_sample_u8_kernel, dim3(cdiv((long)B * h * w, 256)), dim3(256), 0, stream, x, grid, out, B, C, H, W, h, w, nhwc_out);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+int fs_gaze_lowres_nv12_fwd(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu,
+                            int gv, int bu, const float* focus, float* out, int B, int H, int W, int hs, int ws, hipStream_t stream) {
+  const Nv12Frame f(yp, uvp, sb, sy, ub, uy, Nv12Csc{yo, yg, rv, gu, gv, bu});
+  FS_REQUIRE(f && focus && out && B > 0 && H > 0 && W > 0 && hs > 1 && ws > 1 && f.ok(B, H, W));
+  hipLaunchKernelGGL(gaze_lowres_nv12_kernel, dim3(cdiv((long)B * hs * ws, 256)), dim3(256), 0, stream, yp, uvp, sb, sy, ub, uy, f.k, focus, out, B,
+                     H, W, hs, ws);
+  FS_LAUNCH_CHECK();
+  return FS_OK;
+}
+
+int fs_grid_sample_nv12_fwd(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu,
+                            int gv, int bu, const float* grid, float* out, int B, int H, int W, int h, int w, int nhwc_out, hipStream_t stream) {
+  const Nv12Frame f(yp, uvp, sb, sy, ub, uy, Nv12Csc{yo, yg, rv, gu, gv, bu});
+  FS_REQUIRE(f && grid && out && B > 0 && H > 0 && W > 0 && h > 0 && w > 0 && f.ok(B, H, W));
+  hipLaunchKernelGGL(grid_sample_nv12_kernel, dim3(cdiv((long)B * h * w, 256)), dim3(256), 0, stream, yp, uvp, sb, sy, ub, uy, f.k, grid, out, B, H,
+                     W, h, w, nhwc_out);
   FS_LAUNCH_CHECK();
   return FS_OK;
 }

@@ -8,12 +8,14 @@
 //            the viewer's slots; every viewer's previous gaze and age advance.
 // The pixel code q (frame_view.h) and the gaze in 1/16-pixel units (mask_words.h) are one function each, used by every pass that needs
 // them: a frame against the key that commit made from it differs nowhere, NaN pixels included.
-// A frame comes in three layouts -- planar fp32, planar bytes (pixel value byte / 255, whose code q is the byte; 6 bytes a pixel read
-// instead of 15), interleaved bytes read where they lie -- and every pass that reads one is written once over the frame's reader
-// (frame_view.h): the one-pixel tile pass for all three, the 16-pixel band for the two byte layouts (an interleaved frame's sixteen pixels
-// are de-interleaved in registers, v_perm_b32, so that v_sad_u8 meets matching bytes and the key stays planar), commit's frame pass for
-// the planar two.  The fp32 four-pixel band has a cut of its own.  A kernel a layout remains where the layouts' arguments differ; it
-// builds its reader and calls the pass.  decide, and commit's state and row passes, read no frame.
+// A frame comes in four layouts -- planar fp32, planar bytes (pixel value byte / 255, whose code q is the byte; 6 bytes a pixel read
+// instead of 15), interleaved bytes read where they lie, an NV12 surface read where it lies (4.5 bytes a pixel) -- and every pass that
+// reads one is written once over the frame's reader (frame_view.h): the one-pixel tile pass for all four, the 16-pixel band for the three
+// byte layouts (an interleaved frame's sixteen pixels are de-interleaved in registers, v_perm_b32, an NV12 frame's converted, so that
+// v_sad_u8 meets matching bytes and the key stays planar).  The fp32 four-pixel band has a cut of its own.  Commit's frame pass is one
+// template for the planar two, whose frames lie in the key's order, and a kernel each for the interleaved and the NV12 frame, which take
+// pieces of rows through the reader.  A kernel a layout remains where the layouts' arguments differ; it builds its reader and calls the
+// pass.  decide, and commit's state and row passes, read no frame.
 #include "mask_words.h"
 #include "frame_view.h"
 
@@ -138,7 +140,7 @@ __device__ __forceinline__ void gate_tiles_band(const F& f, const unsigned char*
   unsigned int s0 = 0, s1 = 0;
   if (x < W) {
     const size_t base = b * 3 * plane + (size_t)y0 * W + x;
-    const unsigned char* fbase = f.px(b, y0, x);
+    const auto fbase = f.px(b, y0, x);
 #pragma unroll 2
     for (int r = wave * sub + rs; r < rows; r += (GATE_THREADS / 64) * sub) {
       const size_t at = base + (size_t)r * W;
@@ -204,6 +206,20 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_tiles_hwc_band_kernel(const
                                                                            const unsigned char* __restrict__ key, int* __restrict__ sad, int H,
                                                                            int W, int T, int th, int tw, int nseg, int lg) {
   gate_tiles_band(HwcFrame<SX>(img, sb, sy, SX), key, sad, H, W, T, th, tw, nseg, lg);
+}
+
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_nv12_kernel(const unsigned char* __restrict__ yp, const unsigned char* __restrict__ uvp,
+                                                                       long sb, long sy, long ub, long uy, Nv12Csc k,
+                                                                       const unsigned char* __restrict__ key, int* __restrict__ sad, int H, int W,
+                                                                       int T, int th, int tw) {
+  gate_tiles_px(Nv12Frame(yp, uvp, sb, sy, ub, uy, k), key, sad, H, W, T, th, tw);
+}
+// a lane's sixteen converted pixels, four dwords a channel, meet the key's 16-byte loads as the byte frames' do
+__global__ __launch_bounds__(GATE_THREADS) void gate_tiles_nv12_band_kernel(const unsigned char* __restrict__ yp, const unsigned char* __restrict__ uvp,
+                                                                            long sb, long sy, long ub, long uy, Nv12Csc k,
+                                                                            const unsigned char* __restrict__ key, int* __restrict__ sad, int H,
+                                                                            int W, int T, int th, int tw, int nseg, int lg) {
+  gate_tiles_band(Nv12Frame(yp, uvp, sb, sy, ub, uy, k), key, sad, H, W, T, th, tw, nseg, lg);
 }
 
 struct GateRule {
@@ -367,6 +383,36 @@ __global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_hwc_kernel(con
   }
 }
 
+// key[idx[j]] <- the converted frame of viewer idx[j] (fs_gate_commit_nv12); the key stays planar RGB bytes.  VEC, the vector form (the
+// tile pass's conditions): a lane takes sixteen pixels of a row and stores sixteen bytes a channel; per = H * W / 16 such pieces a viewer.
+// Otherwise per = 3 * H * W bytes a viewer, a lane one of them.
+template <bool VEC>
+__global__ __launch_bounds__(GATE_THREADS) void gate_commit_frame_nv12_kernel(const unsigned char* __restrict__ yp, const unsigned char* __restrict__ uvp,
+                                                                              long sb, long sy, long ub, long uy, Nv12Csc k,
+                                                                              const int* __restrict__ idx, unsigned char* __restrict__ key, int B,
+                                                                              int H, int W, size_t per, unsigned int bpi) {
+  const unsigned int j = blockIdx.x / bpi;
+  const int b = idx[j];
+  if (b < 0 || b >= B) return;                         // an index outside the batch writes nothing
+  const size_t e = (size_t)(blockIdx.x - j * bpi) * GATE_THREADS + threadIdx.x;
+  if (e >= per) return;
+  const Nv12Frame f(yp, uvp, sb, sy, ub, uy, k);
+  const size_t plane = (size_t)H * W;
+  if (VEC) {
+    const int w16 = W >> 4;
+    const int y = (int)(e / (unsigned)w16), x = (int)(e - (size_t)y * w16) * 16;
+    u32x4 v[3];
+    f.load16(f.px(b, y, x), v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) *reinterpret_cast<u32x4*>(key + ((size_t)b * 3 + c) * plane + (size_t)y * W + x) = v[c];
+  } else {
+    const int c = (int)(e / plane);
+    const size_t rem = e - c * plane;
+    const int y = (int)(rem / (unsigned)W), x = (int)(rem - (size_t)y * W);
+    key[(size_t)b * 3 * plane + e] = (unsigned char)f.code(f.px(b, y, x), c);
+  }
+}
+
 // The record tensors as rows of 32-bit words (an int64 is two): cat 2, stats 12, counts cap, bits H * P, conf 3.  src == dst (or a
 // null pair, conf) is a part of no words.
 struct GateRows {
@@ -412,7 +458,15 @@ void gate_tiles_launch(const HwcFrame<0>& f, bool band, dim3 grid, hipStream_t s
   else hipLaunchKernelGGL(gate_tiles_hwc_kernel, grid, block, 0, stream, f.p, f.sb, f.sy, f.sx, key, sad, H, W, T, th, tw);
 }
 
-// fs_gate_tiles_u8 / fs_gate_tiles_hwc: the checks, and the lanes a row and the segments of the 16-pixel form, chosen here alone
+void gate_tiles_launch(const Nv12Frame& f, bool band, dim3 grid, hipStream_t stream, const unsigned char* key, int* sad, int H, int W, int T, int th,
+                       int tw, int nseg, int lg) {
+  const dim3 block(GATE_THREADS);
+  if (band)
+    hipLaunchKernelGGL(gate_tiles_nv12_band_kernel, grid, block, 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, key, sad, H, W, T, th, tw, nseg, lg);
+  else hipLaunchKernelGGL(gate_tiles_nv12_kernel, grid, block, 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, key, sad, H, W, T, th, tw);
+}
+
+// fs_gate_tiles_u8 / fs_gate_tiles_hwc / fs_gate_tiles_nv12: the checks, and the lanes a row and the segments of the 16-pixel form, chosen here alone
 template <class F>
 int gate_tiles_bytes(const F& f, const unsigned char* key, int* sad, int B, int H, int W, int T, hipStream_t stream) {
   FS_REQUIRE(f && key && sad && B > 0 && H > 0 && W > 0 && gate_tile_ok(T) && (long)H * W < GATE_INT_LIMIT && f.ok(B, H, W));
@@ -449,7 +503,18 @@ void gate_commit_frame(const HwcFrame<0>& f, const int* idx, unsigned char* key,
     hipLaunchKernelGGL(gate_commit_frame_hwc_kernel<0>, grid, block, 0, stream, f.p, f.sb, f.sy, f.sx, idx, key, B, H, W, units, (unsigned)bpi);
 }
 
-// fs_gate_commit / fs_gate_commit_u8 / fs_gate_commit_hwc: the checks, the state pass, the frame pass of the frame's layout, the row pass
+void gate_commit_frame(const Nv12Frame& f, const int* idx, unsigned char* key, int B, int H, int W, size_t per, bool vec, long wgs, long bpi,
+                       hipStream_t stream) {
+  const dim3 grid((unsigned)wgs), block(GATE_THREADS);
+  if (vec)
+    hipLaunchKernelGGL(gate_commit_frame_nv12_kernel<true>, grid, block, 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, idx, key, B, H, W, per / 48,
+                       (unsigned)bpi);
+  else
+    hipLaunchKernelGGL(gate_commit_frame_nv12_kernel<false>, grid, block, 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, idx, key, B, H, W, per,
+                       (unsigned)bpi);
+}
+
+// fs_gate_commit / fs_gate_commit_u8 / fs_gate_commit_hwc / fs_gate_commit_nv12: the checks, the state pass, the frame pass of the frame's layout, the row pass
 template <class F>
 int gate_commit_run(const F& img, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus, const long long* src_cat,
                     const long long* src_stats, const int* src_counts, const unsigned int* src_bits, const float* src_conf, long long* dst_cat,
@@ -555,6 +620,20 @@ int fs_gate_commit_hwc(const unsigned char* img, long sb, long sy, int sx, const
                        unsigned int* dst_bits, float* dst_conf, int B, int H, int W, int cap, hipStream_t stream) {
   return gate_commit_run(HwcFrame<0>(img, sb, sy, sx), idx, n, key, gstate, focus, src_cat, src_stats, src_counts, src_bits, src_conf, dst_cat, dst_stats,
                          dst_counts, dst_bits, dst_conf, B, H, W, cap, stream);
+}
+
+int fs_gate_tiles_nv12(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu, int gv,
+                       int bu, const unsigned char* key, int* sad, int B, int H, int W, int T, hipStream_t stream) {
+  return gate_tiles_bytes(Nv12Frame(yp, uvp, sb, sy, ub, uy, Nv12Csc{yo, yg, rv, gu, gv, bu}), key, sad, B, H, W, T, stream);
+}
+
+int fs_gate_commit_nv12(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu, int gv,
+                        int bu, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus, const long long* src_cat,
+                        const long long* src_stats, const int* src_counts, const unsigned int* src_bits, const float* src_conf, long long* dst_cat,
+                        long long* dst_stats, int* dst_counts, unsigned int* dst_bits, float* dst_conf, int B, int H, int W, int cap,
+                        hipStream_t stream) {
+  return gate_commit_run(Nv12Frame(yp, uvp, sb, sy, ub, uy, Nv12Csc{yo, yg, rv, gu, gv, bu}), idx, n, key, gstate, focus, src_cat, src_stats, src_counts,
+                         src_bits, src_conf, dst_cat, dst_stats, dst_counts, dst_bits, dst_conf, B, H, W, cap, stream);
 }
 
 }  // extern "C"

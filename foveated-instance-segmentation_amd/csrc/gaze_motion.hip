@@ -113,6 +113,13 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_profile_hwc_kernel(cons
   motion_profile<HwcFrame<SX>, VEC>(HwcFrame<SX>(src, sb, sy, SX), prof, H, W, nseg, nband);
 }
 
+template <bool VEC>
+__global__ __launch_bounds__(MOTION_THREADS) void motion_profile_nv12_kernel(const unsigned char* __restrict__ yp, const unsigned char* __restrict__ uvp,
+                                                                             long sb, long sy, long ub, long uy, Nv12Csc k, int* __restrict__ prof,
+                                                                             int H, int W, int nseg, int nband) {
+  motion_profile<Nv12Frame, VEC>(Nv12Frame(yp, uvp, sb, sy, ub, uy, k), prof, H, W, nseg, nband);
+}
+
 // One workgroup a viewer.  For each axis: P, K of length n in LDS; cost[j] for s = j - R = sum_{i=R}^{n-1-R} |P[i] - K[i - s]|, a wave
 // a shift; lane 0 takes the least, ties to the smaller |s|, then to the negative s, and keeps it only if cost * 8 <= cost(0) * gain.
 __global__ __launch_bounds__(MOTION_THREADS) void motion_estimate_kernel(const int* __restrict__ pnew, const int* __restrict__ pkey,
@@ -243,6 +250,17 @@ __global__ __launch_bounds__(MOTION_THREADS) void motion_move_hwc_kernel(const u
   motion_move<HwcFrame<0>, V>(HwcFrame<0>(img, sb, sy, sx), shift, key, key2, bits, bits2, H, W, P, nk, nb);
 }
 
+template <int V>
+__global__ __launch_bounds__(MOTION_THREADS) void motion_move_nv12_kernel(const unsigned char* __restrict__ yp, const unsigned char* __restrict__ uvp,
+                                                                          long sb, long sy, long ub, long uy, Nv12Csc k,
+                                                                          const long long* __restrict__ shift, const unsigned char* __restrict__ key,
+                                                                          unsigned char* __restrict__ key2, const unsigned int* __restrict__ bits,
+                                                                          unsigned int* __restrict__ bits2, int H, int W, int P, unsigned int nk,
+                                                                          unsigned int nb) {
+  if (motion_still(shift, blockIdx.x / (nk + nb))) return;
+  motion_move<Nv12Frame, V>(Nv12Frame(yp, uvp, sb, sy, ub, uy, k), shift, key, key2, bits, bits2, H, W, P, nk, nb);
+}
+
 // key <- key2 and bits <- bits2 for the moving viewers; lane 0 of a viewer's first workgroup moves its gazes and totals and writes its
 // motion row (every viewer).  gstate (B,6) as the gate's; mstate (B,4) = (dy_total, dx_total, moves, path); motion (B,6) = (dy, dx,
 // cost_best, cost_zero, dy_total, dx_total).
@@ -349,7 +367,14 @@ void motion_profile_launch(const HwcFrame<0>& f, bool vec, dim3 grid, hipStream_
   else hipLaunchKernelGGL((motion_profile_hwc_kernel<4, false>), grid, block, 0, stream, f.p, f.sb, f.sy, prof, H, W, nseg, nband);
 }
 
-// fs_frame_profiles / fs_key_profiles / fs_frame_profiles_hwc: the checks, prof zeroed, the profile pass on every viewer
+void motion_profile_launch(const Nv12Frame& f, bool vec, dim3 grid, hipStream_t stream, const long long*, int* prof, int H, int W, int nseg,
+                           int nband) {
+  const dim3 block(MOTION_THREADS);
+  if (vec) hipLaunchKernelGGL(motion_profile_nv12_kernel<true>, grid, block, 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, prof, H, W, nseg, nband);
+  else hipLaunchKernelGGL(motion_profile_nv12_kernel<false>, grid, block, 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, prof, H, W, nseg, nband);
+}
+
+// fs_frame_profiles / fs_key_profiles / fs_frame_profiles_hwc / fs_frame_profiles_nv12: the checks, prof zeroed, the profile pass on every viewer
 template <class F>
 int motion_profiles(const F& f, int* prof, int B, int H, int W, hipStream_t stream) {
   FS_REQUIRE(f && prof && motion_sizes_ok(B, H, W) && f.ok(B, H, W));
@@ -380,7 +405,14 @@ void motion_move_launch(const HwcFrame<0>& f, const long long* shift, const unsi
                      (unsigned)nk, (unsigned)nb);
 }
 
-// fs_state_shift / fs_state_shift_u8 / fs_state_shift_hwc: the checks and every pass, the move pass of the frame's layout
+template <int V>
+void motion_move_launch(const Nv12Frame& f, const long long* shift, const unsigned char* key, unsigned char* key2, const unsigned int* bits,
+                        unsigned int* bits2, int H, int W, int P, long nk, long nb, dim3 grid, hipStream_t stream) {
+  hipLaunchKernelGGL(motion_move_nv12_kernel<V>, grid, dim3(MOTION_THREADS), 0, stream, f.yp, f.uvp, f.sb, f.sy, f.ub, f.uy, f.k, shift, key, key2, bits,
+                     bits2, H, W, P, (unsigned)nk, (unsigned)nb);
+}
+
+// fs_state_shift / fs_state_shift_u8 / fs_state_shift_hwc / fs_state_shift_nv12: the checks and every pass, the move pass of the frame's layout
 template <class F>
 int motion_state_shift(const F& img, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
                        long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch, int B,
@@ -441,6 +473,11 @@ int fs_frame_profiles_hwc(const unsigned char* img, long sb, long sy, int sx, in
   return motion_profiles(HwcFrame<0>(img, sb, sy, sx), prof, B, H, W, stream);
 }
 
+int fs_frame_profiles_nv12(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu,
+                           int gv, int bu, int* prof, int B, int H, int W, hipStream_t stream) {
+  return motion_profiles(Nv12Frame(yp, uvp, sb, sy, ub, uy, Nv12Csc{yo, yg, rv, gu, gv, bu}), prof, B, H, W, stream);
+}
+
 int fs_profile_shift(const int* prof, const int* prof_key, const long long* gstate, long long* shift, int B, int H, int W, int R, int gain,
                      hipStream_t stream) {
   FS_REQUIRE(prof && prof_key && gstate && shift && motion_sizes_ok(B, H, W) && B <= MOTION_WGS_MAX);
@@ -477,6 +514,14 @@ int fs_state_shift_hwc(const unsigned char* img, long sb, long sy, int sx, const
                        long long* motion, int* scratch, int B, int H, int W, int cap, hipStream_t stream) {
   return motion_state_shift(HwcFrame<0>(img, sb, sy, sx), shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch, B, H,
                             W, cap, stream);
+}
+
+int fs_state_shift_nv12(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu, int gv,
+                        int bu, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
+                        long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch, int B,
+                        int H, int W, int cap, hipStream_t stream) {
+  return motion_state_shift(Nv12Frame(yp, uvp, sb, sy, ub, uy, Nv12Csc{yo, yg, rv, gu, gv, bu}), shift, key, key2, bits, bits2, gstate, stats, counts,
+                            prof_key, mstate, motion, scratch, B, H, W, cap, stream);
 }
 
 int fs_motion_commit(const int* idx, int n, const int* prof, int* prof_key, long long* mstate, int B, int H, int W, hipStream_t stream) {

@@ -77,6 +77,15 @@ SIGNATURES = {
     "fs_gate_commit_hwc": "plli" + "p" + "i" + "p" * 13 + "iiii",
     "fs_frame_profiles_hwc": "plli" + "p" + "iii",
     "fs_state_shift_hwc": "plli" + "p" * 12 + "iiii",
+    # an NV12 frame: yp, uvp, sb, sy, ub, uy, then the colour table yo, yg, rv, gu, gv, bu
+    "fs_nv12_to_rgb": "ppllll" + "iiiiii" + "plli" + "iii",
+    "fs_gaze_lowres_nv12_fwd": "ppllll" + "iiiiii" + "pp" + "iiiii",
+    "fs_grid_sample_nv12_fwd": "ppllll" + "iiiiii" + "pp" + "iiiiii",
+    "fs_gate_tiles_nv12": "ppllll" + "iiiiii" + "pp" + "iiii",
+    "fs_gate_commit_nv12": "ppllll" + "iiiiii" + "p" + "i" + "p" * 13 + "iiii",
+    "fs_frame_profiles_nv12": "ppllll" + "iiiiii" + "p" + "iii",
+    "fs_state_shift_nv12": "ppllll" + "iiiiii" + "p" * 12 + "iiii",
+    "fs_frame_overlay_nv12": "ppllll" + "iiiiii" + "ppppp" + "l" + "pi" + "plli" + "iii",
     "fs_frame_overlay": "p" + "ppppp" + "l" + "pi" + "plli" + "iii",
     "fs_frame_overlay_u8": "p" + "ppppp" + "l" + "pi" + "plli" + "iii",
     "fs_frame_overlay_hwc": "plli" + "ppppp" + "l" + "pi" + "plli" + "iii",
@@ -198,6 +207,7 @@ HOST_ONLY = {
     "fs_mask_candidates_scratch_ints": ("l", "iiii"),
     "fs_state_shift_scratch_ints": ("l", "iiii"),
     "fs_byte_frame_route": ("l", "plli" + "i"),
+    "fs_nv12_frame_route": ("l", "ppllll" + "i"),
 }
 
 

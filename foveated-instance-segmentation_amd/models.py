@@ -202,7 +202,9 @@ class DeformSegmentationModule(nn.Module):
         value is byte / 255 correctly rounded: the results equal those of the fp32 frame of that quotient bit for bit, and the frame is
         read as bytes by the two gathers of the front (ops.gaze_lowres, ops.grid_sample_u8).  A uint8 frame may also be a view of
         interleaved bytes (hwc.permute(0, 3, 1, 2), rgba.permute(0, 3, 1, 2)[:, :3], padded rows, a crop: ops.byte_frame_layout): the
-        gathers read it where it lies, nothing is copied, and the results equal those of its planar copy bit for bit."""
+        gathers read it where it lies, nothing is copied, and the results equal those of its planar copy bit for bit.  An ops.Nv12Frame (a
+        decoder's luma and chroma planes) is taken in a uint8 frame's place and read where it lies too: the results equal those of
+        ops.nv12_to_rgb(img) bit for bit."""
         if self.training:
             raise RuntimeError(f"{who}() needs eval mode (module.eval()): in train mode the encoder would update its BatchNorm running statistics")
         if img.dim() != 4 or img.shape[1] != 3:
@@ -217,7 +219,8 @@ class DeformSegmentationModule(nn.Module):
         self.check_nan()
         ops.reset_step_state()
         # a uint8 view of interleaved bytes (ops.byte_frame_layout: a permuted HWC / RGBA buffer) is read where it lies
-        hwc = img.dtype == torch.uint8 and not img.is_contiguous() and ops.byte_frame_layout(img) is not None
+        # so is an NV12 frame (ops.Nv12Frame: a decoder's surface), each tap converted to its RGB byte as it is read
+        hwc = isinstance(img, ops.Nv12Frame) or (img.dtype == torch.uint8 and not img.is_contiguous() and ops.byte_frame_layout(img) is not None)
         x = img if hwc else img.contiguous()
         xs, _ = self.saliency(x, focus.float().contiguous())
         self._note_nan(xs)

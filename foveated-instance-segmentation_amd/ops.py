@@ -1391,10 +1391,174 @@ def _byte_frame(img, what="img"):
     return layout
 
 
+NV12_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}          # (Kr, Kb)
+NV12_COEF_MAX = 32768
+
+
+def nv12_csc(matrix, full_range=False):
+    """The integer colour table (yo, yg, rv, gu, gv, bu) of an NV12 frame (include/fovealseg.h "frames as NV12"): rint(256 * real
+    coefficient) from the matrix's (Kr, Kb); the luma gain is 255 / 219 and the chroma gain 255 / 224 for limited range (yo = 16), both 1
+    for full range (yo = 0).  matrix: "bt601" or "bt709"."""
+    if matrix not in NV12_MATRICES:
+        raise ValueError(f"matrix must be one of {sorted(NV12_MATRICES)}, got {matrix!r}")
+    kr, kb = NV12_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    ly, lc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
+    real = (ly, lc * 2 * (1 - kr), -lc * 2 * (1 - kb) * kb / kg, -lc * 2 * (1 - kr) * kr / kg, lc * 2 * (1 - kb))
+    return (0 if full_range else 16,) + tuple(int(round(256.0 * v)) for v in real)
+
+
+def _nv12_table(csc):
+    try:
+        t = tuple(operator.index(v) for v in csc)
+    except TypeError:
+        t = ()
+    if len(t) != 6 or any(isinstance(v, bool) for v in csc):
+        raise ValueError(f"csc must be six integers (yo, yg, rv, gu, gv, bu), got {csc!r}")
+    if not 0 <= t[0] <= 255 or any(abs(v) > NV12_COEF_MAX for v in t[1:]):
+        raise ValueError(f"csc wants 0 <= yo <= 255 and every coefficient in [-{NV12_COEF_MAX}, {NV12_COEF_MAX}], got {t}")
+    return t
+
+
+def nv12_frame_strides(y_shape, y_strides, uv_shape, uv_strides):
+    """(sb, sy, ub, uy) of an NV12 frame from the shapes and strides of its two views alone, or None: y (B,H,W) with unit column stride
+    and rows sy >= W apart, uv (B,ceil(H/2),ceil(W/2),2) with strides (ub, uy, 2, 1) and rows uy >= 2 * ceil(W/2) apart; images that do
+    not overlap (sb >= H * sy, ub >= ceil(H/2) * uy) or are all one image (sb = ub = 0).  The strides of a dimension of one element are
+    normalised: sb = ub = 0 for B == 1, sy = W for H == 1, uy = 2 * ceil(W/2) for one chroma row."""
+    if len(y_shape) != 3 or len(uv_shape) != 4:
+        return None
+    B, H, W = (int(v) for v in y_shape)
+    if min(B, H, W) < 1:
+        return None
+    Hc, Wc = (H + 1) // 2, (W + 1) // 2
+    if tuple(int(v) for v in uv_shape) != (B, Hc, Wc, 2):
+        return None
+    sb, sy, sx = (int(v) for v in y_strides)
+    ub, uy, ux, uc = (int(v) for v in uv_strides)
+    if (W > 1 and sx != 1) or uc != 1 or (Wc > 1 and ux != 2):
+        return None
+    if H == 1:
+        sy = W
+    if Hc == 1:
+        uy = 2 * Wc
+    if B == 1:
+        sb = ub = 0
+    if sy < W or uy < 2 * Wc or sb < 0 or ub < 0:
+        return None
+    if not (sb == 0 and ub == 0) and (sb < H * sy or ub < Hc * uy):
+        return None
+    return sb, sy, ub, uy
+
+
+class Nv12Frame:
+    """An NV12 frame of B images of H x W pixels where a decoder or a camera left it (include/fovealseg.h "frames as NV12"; unpinned):
+    y (B,H,W) uint8, the luma plane, a device tensor or view with unit column stride; uv (B,ceil(H/2),ceil(W/2),2) uint8, the interleaved
+    chroma plane, a view with strides (ub, uy, 2, 1).  Two allocations, or two views of one surface (nv12_from_surface).  matrix: "bt601"
+    or "bt709", with full_range -- it has no default: a silent wrong colour matrix is worse than a required keyword; csc: a table of the
+    caller's own (yo, yg, rv, gu, gv, bu) instead (nv12_csc's rule; matrix is then only a label and may be None).
+
+    predict*, evaluate*, GazeSession.step / render and the ops that take a uint8 frame take this object in its place, and give what they
+    give on the planar uint8 frame nv12_to_rgb(frame), bit for bit; the frame is read where it lies and never written.  It shows
+    shape == (B,3,H,W), dtype == torch.uint8, device and is_cuda as that frame would.  ValueError for any other dtypes, shapes or
+    strides, views on different devices, bytes the kernels may read outside the tensors' storage, or a table out of range."""
+
+    def __init__(self, y, uv, *, matrix, full_range=False, csc=None):
+        if not isinstance(y, torch.Tensor) or not isinstance(uv, torch.Tensor) or y.dtype != torch.uint8 or uv.dtype != torch.uint8:
+            raise ValueError(f"y and uv must be uint8 tensors, got {getattr(y, 'dtype', None)} and {getattr(uv, 'dtype', None)}")
+        strides = nv12_frame_strides(y.shape, y.stride(), uv.shape, uv.stride()) if y.dim() == 3 and uv.dim() == 4 else None
+        if strides is None:
+            raise ValueError(f"y must be a non-empty (B,H,W) with unit column stride and uv (B,ceil(H/2),ceil(W/2),2) with strides (ub, uy, 2, 1), "
+                             f"rows and images that do not overlap (or one image expanded over the batch in both), got {tuple(y.shape)} with "
+                             f"strides {tuple(y.stride())} and {tuple(uv.shape)} with strides {tuple(uv.stride())}")
+        if y.device != uv.device:
+            raise ValueError(f"y and uv must be on one device, got {y.device} and {uv.device}")
+        B, H, W = (int(v) for v in y.shape)
+        sb, sy, ub, uy = strides
+        if (y.storage_offset() + (B - 1) * sb + (H - 1) * sy + W > y.untyped_storage().nbytes()
+                or uv.storage_offset() + (B - 1) * ub + ((H + 1) // 2 - 1) * uy + 2 * ((W + 1) // 2) > uv.untyped_storage().nbytes()):
+            raise ValueError("y or uv ends short of the bytes its shape and strides describe")
+        if csc is None:
+            csc = nv12_csc(matrix, full_range)
+        elif matrix is not None and matrix not in NV12_MATRICES:
+            raise ValueError(f"matrix must be one of {sorted(NV12_MATRICES)} or None beside csc, got {matrix!r}")
+        self.y, self.uv = y, uv
+        self.matrix, self.full_range = matrix, bool(full_range)
+        self.csc = _nv12_table(csc)
+        self.strides = strides
+        # what _frame_route and _frame_args hand to every call, made once: the planes stay where they are while the frame holds them
+        self._tail = self.strides + self.csc
+        self._args = (y.data_ptr(), uv.data_ptr()) + self._tail
+        self.shape = torch.Size((B, 3, H, W))
+        self.dtype = torch.uint8
+        self.device = y.device
+        self.is_cuda = y.is_cuda
+
+    def dim(self):
+        return 4
+
+    def numel(self):
+        return self.shape.numel()
+
+    def like(self, y, uv):
+        """The frame of other planes under this frame's colour table."""
+        return Nv12Frame(y, uv, matrix=self.matrix, full_range=self.full_range, csc=self.csc)
+
+    def route(self):
+        """fs_nv12_frame_route of the frame: 1 the vector forms, 0 the one-pixel forms."""
+        return int(hip.load().fs_nv12_frame_route(self.y.data_ptr(), self.uv.data_ptr(), *self.strides, int(self.shape[3])))
+
+
+_FRAME_TYPES = (torch.Tensor, Nv12Frame)
+
+
+def nv12_from_surface(buf, H, W, pitch, uv_offset, batch_stride=None, *, matrix, full_range=False, csc=None):
+    """The Nv12Frame of one decoder surface: buf, a uint8 tensor of the surface's bytes (any shape; it is read flat and must be
+    contiguous); B = its images.  Luma rows lie pitch apart from byte 0 of an image, chroma rows pitch apart from byte uv_offset (H *
+    pitch for a tight surface; decoders that align the plane give their own); images batch_stride apart (None: one image, B = 1)."""
+    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or not buf.is_contiguous():
+        raise ValueError(f"buf must be a contiguous uint8 tensor, got {getattr(buf, 'dtype', None)}")
+    H, W, pitch, uv_offset = int(H), int(W), int(pitch), int(uv_offset)
+    Hc, Wc = (H + 1) // 2, (W + 1) // 2
+    if min(H, W) < 1 or pitch < max(W, 2 * Wc) or uv_offset < H * pitch:
+        raise ValueError(f"a surface of {H} x {W} pixels wants pitch >= {max(W, 2 * Wc)} and uv_offset >= H * pitch, got {pitch} and {uv_offset}")
+    flat = buf.view(-1)
+    per = uv_offset + (Hc - 1) * pitch + 2 * Wc
+    if batch_stride is None:
+        B, batch_stride = 1, per
+    else:
+        batch_stride = int(batch_stride)
+        if batch_stride < uv_offset + Hc * pitch:
+            raise ValueError(f"batch_stride must be at least uv_offset + ceil(H/2) * pitch = {uv_offset + Hc * pitch}, got {batch_stride}")
+        B = (flat.numel() - per) // batch_stride + 1 if flat.numel() >= per else 0
+    if flat.numel() < per or B < 1:
+        raise ValueError(f"buf has {flat.numel()} bytes, one image of this surface needs {per}")
+    y = flat.as_strided((B, H, W), (batch_stride, pitch, 1))
+    uv = flat.as_strided((B, Hc, Wc, 2), (batch_stride, pitch, 2, 1), flat.storage_offset() + uv_offset)      # as_strided counts from the storage
+    return Nv12Frame(y, uv, matrix=matrix, full_range=full_range, csc=csc)
+
+
+def nv12_to_rgb(frame, out=None):
+    """The RGB bytes of an NV12 frame (fs_nv12_to_rgb; no autograd; unpinned): out, a uint8 (B,3,H,W) tensor, contiguous or a view of
+    interleaved (B,H,W,3) / (B,H,W,4) bytes (byte_frame_dest; RGBA gets alpha 255); None: a new contiguous one.  The planar result is
+    the frame every other entry point is equal on.  Returns out."""
+    if not isinstance(frame, Nv12Frame):
+        raise ValueError(f"frame must be an ops.Nv12Frame, got {type(frame).__name__}")
+    B, _, H, W = (int(v) for v in frame.shape)
+    if out is None:
+        out = torch.empty(B, 3, H, W, device=frame.device, dtype=torch.uint8)
+    dest = byte_frame_dest(out, (B, 3, H, W))
+    suffix, strides = _frame_route(frame)
+    hip.call("fs_nv12_to_rgb", *_frame_args(frame, strides), *_dest_args(out, dest), B, H, W)
+    return out
+
+
 def _frame_route(img, what="img"):
-    """Which of a pass's three entry points reads the frame tensor img, and what follows the frame's pointer in its arguments: ("", ())
-    for fp32, ("_u8", ()) for contiguous bytes, ("_hwc", (sb, sy, sx)) for an hwc view; ValueError for bytes in any other layout
-    (_byte_frame).  A function of dtype, shape, strides and storage size alone: no device is asked."""
+    """Which of a pass's four entry points reads the frame img, and what follows the frame's pointer in its arguments: ("", ()) for fp32,
+    ("_u8", ()) for contiguous bytes, ("_hwc", (sb, sy, sx)) for an hwc view, ("_nv12", (sb, sy, ub, uy, yo, yg, rv, gu, gv, bu)) for an
+    Nv12Frame; ValueError for bytes in any other layout (_byte_frame).  A function of type, dtype, shape, strides and storage size
+    alone: no device is asked."""
+    if isinstance(img, Nv12Frame):
+        return "_nv12", img._tail
     if img.dtype != torch.uint8:
         return "", ()
     layout = _byte_frame(img, what)
@@ -1403,17 +1567,28 @@ def _frame_route(img, what="img"):
 
 def _frame_args(img, strides):
     """The frame's leading arguments of the entry point _frame_route chose: the device pointer and the strides of an hwc view (which is
-    not contiguous, as hip.ptr asks of every other tensor)."""
+    not contiguous, as hip.ptr asks of every other tensor), the two plane pointers, the strides and the table of an Nv12Frame."""
     if not strides:
         return (hip.ptr(img),)
     if not img.is_cuda:
         raise hip.HipLibraryError("fovealseg kernels need device tensors (got a CPU tensor); there is no CPU path")
+    if isinstance(img, Nv12Frame):
+        return img._args
     return (img.data_ptr(),) + strides
 
 
 def byte_frame_select(img, sel):
     """img.index_select(0, sel) for an hwc view that stays one: the rows of the chosen frames are gathered from the underlying bytes (3 * H *
-    W or 4 * H * W bytes a frame, never a planar copy) and viewed as (n,3,H,W) again.  With sb == 0 the n frames are the one frame."""
+    W or 4 * H * W bytes a frame, never a planar copy) and viewed as (n,3,H,W) again.  With sb == 0 the n frames are the one frame.  An
+    Nv12Frame stays one likewise: the chosen frames' luma and chroma rows are gathered as they lie, 1.5 bytes a pixel, no RGB copy."""
+    if isinstance(img, Nv12Frame):
+        B, _, H, W = (int(v) for v in img.shape)
+        n = int(sel.shape[0])
+        sb, sy, ub, uy = img.strides
+        Hc, Wc = (H + 1) // 2, (W + 1) // 2
+        if sb == 0 and ub == 0:
+            return img.like(img.y[:1].expand(n, H, W), img.uv[:1].expand(n, Hc, Wc, 2))
+        return img.like(img.y.index_select(0, sel), img.uv.index_select(0, sel))
     layout = byte_frame_layout(img)
     if layout is None or layout[0] != "hwc":
         return img.index_select(0, sel)
@@ -1600,7 +1775,7 @@ class GridSample(Function):
 def grid_sample_u8(x, grid):
     """GridSample's forward on a frame of bytes (fs_grid_sample_u8_fwd; no autograd): x (B,C,H,W) uint8 with the pixel value byte / 255,
     grid (B,h,w,2) fp32 -> (B,h,w,C) fp32 NHWC, equal to GridSample.apply(x.float() / 255, grid) bit for bit."""
-    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.numel() == 0 or x.dtype != torch.uint8:
+    if not isinstance(x, _FRAME_TYPES) or x.dim() != 4 or x.numel() == 0 or x.dtype != torch.uint8:
         raise ValueError(f"x must be a non-empty uint8 (B,C,H,W), got {getattr(x, 'dtype', None)} {tuple(getattr(x, 'shape', ()))}")
     B, C, H, W = (int(v) for v in x.shape)
     if grid.dim() != 4 or grid.shape[0] != B or grid.shape[3] != 2 or grid.numel() == 0 or grid.dtype != torch.float32:
@@ -1608,7 +1783,10 @@ def grid_sample_u8(x, grid):
     h, w = int(grid.shape[1]), int(grid.shape[2])
     out = torch.empty(B, h, w, C, device=x.device, dtype=torch.float32)
     traffic = 1.0 * B * h * w * (4 * C + 8 + 4 * C)
-    if x.is_contiguous():                               # any C
+    if isinstance(x, Nv12Frame):                        # three channels, each tap converted as it is read
+        _, strides = _frame_route(x, "x")
+        _launch("fe_grid_sample_nv12_fwd", traffic, "fs_grid_sample_nv12_fwd", *_frame_args(x, strides), hip.ptr(grid), hip.ptr(out), B, H, W, h, w, 1)
+    elif x.is_contiguous():                             # any C
         _launch("fe_grid_sample_u8_fwd", traffic, "fs_grid_sample_u8_fwd", hip.ptr(x), hip.ptr(grid), hip.ptr(out), B, C, H, W, h, w, 1)
     else:                                               # an interleaved frame (three channels), read where it lies: one address a tap
         _, strides = _frame_route(x, "x")
@@ -2378,7 +2556,7 @@ def _gate_tile(T):
 def _gate_tiles(dtype, img, key, tile, out):
     T = _gate_tile(tile)
     what = "fp32" if dtype == torch.float32 else "uint8"
-    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
+    if not isinstance(img, _FRAME_TYPES) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
         raise ValueError(f"img must be a non-empty {what} (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
     if key.dtype != torch.uint8 or key.shape != img.shape:
         raise ValueError(f"key must be uint8 {tuple(img.shape)}, got {key.dtype} {tuple(key.shape)}")
@@ -2445,7 +2623,7 @@ def gate_decide(sad, gstate, focus, stats, bits, frame_size, tile=32, level=8, s
 
 def _gate_commit(dtype, img, idx, key, gstate, focus, src, dst):
     what = "fp32" if dtype == torch.float32 else "uint8"
-    if (not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype
+    if (not isinstance(img, _FRAME_TYPES) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype
             or key.dtype != torch.uint8 or key.shape != img.shape):
         raise ValueError(f"img must be a non-empty {what} (B,3,H,W) and key uint8 of its shape, got {getattr(img, 'dtype', None)} "
                          f"{tuple(getattr(img, 'shape', ()))} and {tuple(key.shape)}")
@@ -2524,11 +2702,12 @@ def _profile_sizes(B, H, W):
     return (B, H + W)
 
 
-_PROFILE_ENTRY = {"": "fs_frame_profiles", "_u8": "fs_key_profiles", "_hwc": "fs_frame_profiles_hwc"}    # a planar frame of bytes is a key
+# the profile pass's entry point by _frame_route's suffix: fs_frame_profiles + suffix ("_nv12" among them), but a planar frame of bytes is a key
+_PROFILE_ENTRY = {"": "fs_frame_profiles", "_u8": "fs_key_profiles", "_hwc": "fs_frame_profiles_hwc"}
 
 
 def _profiles(src, dtype, out):
-    if not isinstance(src, torch.Tensor) or src.dim() != 4 or src.shape[1] != 3 or src.numel() == 0 or src.dtype != dtype:
+    if not isinstance(src, _FRAME_TYPES) or src.dim() != 4 or src.shape[1] != 3 or src.numel() == 0 or src.dtype != dtype:
         raise ValueError(f"the frames must be a non-empty {dtype} (B,3,H,W), got {getattr(src, 'dtype', None)} {tuple(getattr(src, 'shape', ()))}")
     B, _, H, W = (int(v) for v in src.shape)
     suffix, strides = _frame_route(src, "the frames")
@@ -2537,7 +2716,7 @@ def _profiles(src, dtype, out):
         out = torch.empty(shape, device=src.device, dtype=torch.int32)
     elif out.dtype != torch.int32 or tuple(out.shape) != shape:
         raise ValueError(f"out must be int32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    hip.call(_PROFILE_ENTRY[suffix], *_frame_args(src, strides), hip.ptr(out), B, H, W)
+    hip.call(_PROFILE_ENTRY.get(suffix, "fs_frame_profiles" + suffix), *_frame_args(src, strides), hip.ptr(out), B, H, W)
     return out
 
 
@@ -2585,7 +2764,7 @@ def state_shift_scratch(B, H, W, cap, device):
 
 
 def _state_shift(dtype, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch):
-    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
+    if not isinstance(img, _FRAME_TYPES) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
         raise ValueError(f"img must be a non-empty {'fp32' if dtype == torch.float32 else 'uint8'} (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
     B, _, H, W = (int(v) for v in img.shape)
     suffix, strides = _frame_route(img)
@@ -2795,7 +2974,7 @@ def draw_instances(img, bits, stats=None, focus=None, style=None, outline_px=0, 
     out: a uint8 (B,3,H,W) tensor to write, contiguous or an interleaved view (byte_frame_dest: an RGBA view gets alpha 255); None: a new
     contiguous one.  out may be img itself for a frame of bytes.  The rule per pixel, first that holds: marker, box, outline, tint, dim
     (include/fovealseg.h).  Returns out."""
-    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype not in (torch.float32, torch.uint8):
+    if not isinstance(img, _FRAME_TYPES) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype not in (torch.float32, torch.uint8):
         raise ValueError(f"img must be a non-empty fp32 or uint8 (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
     B, _, H, W = (int(v) for v in img.shape)
     if max(H, W) > OVERLAY_MAX_PX:
@@ -2814,7 +2993,9 @@ def draw_instances(img, bits, stats=None, focus=None, style=None, outline_px=0, 
     f = None if focus is None else _focus_arg(focus, B, dev)
     live_ptr, live_stride = _live_arg(live, B, dev)
     outline_px = _int_ge_zero("outline_px", outline_px)
-    if img.dtype == torch.uint8 and byte_frame_layout(img) is None or img.dtype == torch.float32 and not img.is_contiguous():
+    if isinstance(img, Nv12Frame):
+        pass                                            # read where it lies
+    elif img.dtype == torch.uint8 and byte_frame_layout(img) is None or img.dtype == torch.float32 and not img.is_contiguous():
         img = img.contiguous()
     if out is None:
         out = torch.empty(B, 3, H, W, device=dev, dtype=torch.uint8)

@@ -159,7 +159,7 @@ class GazeSession:
         B, H, W = self.batch, self.H, self.W
         if self._dev is None:
             raise RuntimeError("GazeSession.render() draws the records step() made: call step() first")
-        if not isinstance(img, torch.Tensor) or tuple(img.shape) != (B, 3, H, W) or img.dtype not in (torch.float32, torch.uint8):
+        if not isinstance(img, (torch.Tensor, ops.Nv12Frame)) or tuple(img.shape) != (B, 3, H, W) or img.dtype not in (torch.float32, torch.uint8):
             raise ValueError(f"img must be fp32 or uint8 {(B, 3, H, W)}, got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
         if img.device != self._dev:
             raise ValueError(f"the session lives on {self._dev}, img is on {img.device}")
@@ -194,7 +194,10 @@ class GazeSession:
         A uint8 frame may also be a view of interleaved bytes, as a camera or a decoder makes them -- hwc.permute(0, 3, 1, 2) of a (B,H,W,3)
         buffer, rgba.permute(0, 3, 1, 2)[:, :3] of a (B,H,W,4) one, with padded rows, as a crop, or one frame expanded over the viewers
         (ops.byte_frame_layout) --: it is read where it lies, gives what its planar copy gives bit for bit, and a step in which nobody
-        runs allocates nothing.  Any other non-contiguous frame is copied, as before.
+        runs allocates nothing.  Any other non-contiguous frame is copied, as before.  An ops.Nv12Frame -- a video decoder's luma and
+        chroma planes, 1.5 bytes a pixel -- is taken in a uint8 frame's place: every pass reads it where it lies and gives what it gives on
+        ops.nv12_to_rgb(img) bit for bit, a step in which nobody runs allocates nothing, and a partial run gathers the running viewers'
+        luma and chroma rows alone.
 
         Returns (cat, stats, counts, bits[, conf], gate[, motion]): the record of every viewer as predict_instances(img, focus, return_bits=True)
         makes it -- made now for the viewers that ran, the held one for the others -- and gate (B,8) int64 on the host = (code,
@@ -208,7 +211,7 @@ class GazeSession:
         if self.module.training:
             raise RuntimeError("GazeSession.step() needs eval mode (module.eval()): in train mode the encoder would update its BatchNorm running statistics")
         B, H, W = self.batch, self.H, self.W
-        if not isinstance(img, torch.Tensor) or tuple(img.shape) != (B, 3, H, W) or img.dtype not in (torch.float32, torch.uint8):
+        if not isinstance(img, (torch.Tensor, ops.Nv12Frame)) or tuple(img.shape) != (B, 3, H, W) or img.dtype not in (torch.float32, torch.uint8):
             raise ValueError(f"img must be fp32 or uint8 {(B, 3, H, W)}, got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
         if not isinstance(focus, torch.Tensor) or tuple(focus.shape) != (B, 2):
             raise ValueError(f"focus must be ({B}, 2), got {tuple(getattr(focus, 'shape', ()))}")
@@ -220,7 +223,8 @@ class GazeSession:
             raise ValueError(f"the session lives on {self._dev}, img is on {img.device}")
         fdev = self._force(force, img.device)
         # a view of interleaved bytes (ops.byte_frame_layout: a camera's HWC / RGBA buffer, permuted) is read where it lies
-        hwc = img.dtype == torch.uint8 and not img.is_contiguous() and ops.byte_frame_layout(img) is not None
+        # and so is an NV12 frame (ops.Nv12Frame: a decoder's surface): the state stays planar RGB bytes
+        hwc = isinstance(img, ops.Nv12Frame) or (img.dtype == torch.uint8 and not img.is_contiguous() and ops.byte_frame_layout(img) is not None)
         x = img if hwc else img.contiguous()
         f = focus.float().contiguous()
         moving = self.motion_px is not None

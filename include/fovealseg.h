@@ -525,6 +525,64 @@ int fs_frame_profiles_hwc(const unsigned char* img, long sb, long sy, int sx, in
 int fs_state_shift_hwc(const unsigned char* img, long sb, long sy, int sx, const long long* shift, unsigned char* key, unsigned char* key2,
                        unsigned int* bits, unsigned int* bits2, long long* gstate, long long* stats, int* counts, int* prof_key,
                        long long* mstate, long long* motion, int* scratch, int B, int H, int W, int cap, fs_stream_t stream);
+/* Frames as NV12, read where they lie (UNPINNED: the reference reads image files only): what a video decoder's surface
+ * ("Y plane followed by interleaved UV plane", a device pointer and a pitch per plane), a camera ISP and V4L2 make.  1.5 bytes a pixel.
+ * Layout.  A frame of B images of H x W pixels, any H, W >= 1, odd included, is (yp, uvp, sb, sy, ub, uy): the luma byte of (b, y, x) is
+ * yp[b * sb + y * sy + x], sy >= W; with j = y >> 1, i = x >> 1 its chroma is U = uvp[b * ub + j * uy + 2 * i], V = uvp[b * ub + j * uy + 2 * i
+ * + 1], uy >= 2 * ceil(W / 2): the sample of the pixel's 2 x 2 block, nearest, replicated -- no interpolation, no siting offset.  Images do
+ * not overlap (sb >= H * sy, ub >= ceil(H / 2) * uy) or are all one image (sb = ub = 0); neither is looked at for B = 1.
+ * Colour.  csc = (yo, yg, rv, gu, gv, bu), six int32 passed by value.  With C = Y - yo, D = U - 128, E = V - 128 in int32 and >> the
+ * arithmetic (floor) shift:
+ *   R = clamp((yg * C + rv * E          + 128) >> 8, 0, 255)
+ *   G = clamp((yg * C + gu * D + gv * E + 128) >> 8, 0, 255)
+ *   B = clamp((yg * C + bu * D          + 128) >> 8, 0, 255)
+ * 0 <= yo <= 255 and every coefficient in [-32768, 32768], so no sum leaves int32.  The standard tables are rint(256 * real coefficient)
+ * from (Kr, Kb), luma gain 255 / 219 and chroma gain 255 / 224 for limited range, 1 for full range (yo, yg, rv, gu, gv, bu):
+ *   bt601 limited 16 298 409 -100 -208 516    bt601 full 0 256 359 -88 -183 454
+ *   bt709 limited 16 298 459  -55 -136 541    bt709 full 0 256 403 -48 -120 475
+ * each within 1 grey level of clip(rint(real formula)) over all 2^24 (Y, U, V).
+ * The RGB byte is the pixel's code q and byte / 255 its value: each entry point below equals its planar uint8 twin fed fs_nv12_to_rgb's
+ * planar frame bit for bit.  All integer work but the taps' (float)byte / 255; plain vector loads and stores; the frame is never written; no
+ * address is formed from frame data.  FS_ERR_ARG, with nothing launched, under the twin's conditions and for a null plane, sy < W, uy < 2 *
+ * ceil(W / 2), sb < 0, ub < 0, overlapping images with B > 1 (sb = 0 with ub != 0 among them), yo outside 0 .. 255 or a coefficient
+ * outside [-32768, 32768].
+ * fs_nv12_frame_route (host only): 1 the vector forms (W % 16 == 0, yp and uvp 16-byte aligned, sy, sb, uy, ub multiples of 16: every
+ * sixteen pixels of a row and their sixteen chroma bytes are one aligned load each), 0 the one-pixel forms, -1 a description refused. */
+long fs_nv12_frame_route(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int W);
+/* The conversion alone: out, described as fs_frame_overlay's destination (planar, RGB, or RGBA with alpha 255), <- the RGB bytes.  Sixteen
+ * pixels a lane (a 16-byte load of luma and one of chroma, the chroma products made once a sample) on route 1 with the destination's
+ * sixteen-pixel pieces aligned, one pixel a lane otherwise.  What a caller displays, and the twin the other entry points are held to.
+ * Also FS_ERR_ARG for out == yp or out == uvp. */
+int fs_nv12_to_rgb(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu, int gv,
+                   int bu, unsigned char* out, long ob, long oy, int ox, int B, int H, int W, fs_stream_t stream);
+/* fs_gaze_lowres_u8_fwd on an NV12 frame: the same four taps, each converted as it is read, then the same operations. */
+int fs_gaze_lowres_nv12_fwd(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu,
+                            int gv, int bu, const float* focus, float* out, int B, int H, int W, int hs, int ws, fs_stream_t stream);
+/* fs_grid_sample_u8_fwd with C = 3 on an NV12 frame: out fp32 (B,h,w,3) [nhwc_out=1] or (B,3,h,w) [nhwc_out=0]. */
+int fs_grid_sample_nv12_fwd(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu,
+                            int gv, int bu, const float* grid, float* out, int B, int H, int W, int h, int w, int nhwc_out, fs_stream_t stream);
+/* fs_gate_tiles_u8 on an NV12 frame, the hot pass: 4.5 bytes read per pixel (1.5 of the frame, 3 of the key), plain stores, no atomics.
+ * Vector form (route 1 and key 16-byte aligned): fs_gate_tiles_u8's cut; a lane converts its sixteen pixels into a register quad a
+ * channel and meets the key's 16-byte load per channel with the same twelve v_sad_u8.  One pixel a lane otherwise. */
+int fs_gate_tiles_nv12(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu, int gv,
+                       int bu, const unsigned char* key, int* sad, int B, int H, int W, int T, fs_stream_t stream);
+/* fs_gate_commit_u8 on an NV12 frame: key[idx[j]] <- the converted frame of viewer idx[j]; the key stays planar RGB bytes.  Sixteen
+ * pixels a lane (three 16-byte stores) under the tile pass's conditions, one byte a lane otherwise. */
+int fs_gate_commit_nv12(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu, int gv,
+                        int bu, const int* idx, int n, unsigned char* key, long long* gstate, const float* focus, const long long* src_cat,
+                        const long long* src_stats, const int* src_counts, const unsigned int* src_bits, const float* src_conf,
+                        long long* dst_cat, long long* dst_stats, int* dst_counts, unsigned int* dst_bits, float* dst_conf, int B, int H, int W,
+                        int cap, fs_stream_t stream);
+/* fs_key_profiles of an NV12 frame: the row and column sums of the luma code r + g + b of the converted pixel, as everywhere -- not of
+ * the Y plane.  Four pixels a lane (a 4-byte load of luma and one of chroma) on route 1, one pixel a lane otherwise. */
+int fs_frame_profiles_nv12(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu,
+                           int gv, int bu, int* prof, int B, int H, int W, fs_stream_t stream);
+/* fs_state_shift_u8 on an NV12 frame: only the move pass reads the frame (the key's uncovered border takes the converted pixel's byte of
+ * that channel); every other pass and the scratch are fs_state_shift's. */
+int fs_state_shift_nv12(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu, int gv,
+                        int bu, const long long* shift, unsigned char* key, unsigned char* key2, unsigned int* bits, unsigned int* bits2,
+                        long long* gstate, long long* stats, int* counts, int* prof_key, long long* mstate, long long* motion, int* scratch,
+                        int B, int H, int W, int cap, fs_stream_t stream);
 /* Showing the record: the gazed instance drawn onto the frame (UNPINNED, a definition of this library's).  The reference
  * visualises on the host, with matplotlib, PIL and numpy (eval.py:70-83 visualize_result, utils.py:207-221 colorEncode, the TensorBoard
  * panels of models/models.py); this replaces what a caller composed from torch shifts, torch.where, an fp32 blend and permute().contiguous().
@@ -573,6 +631,14 @@ int fs_frame_overlay_u8(const unsigned char* img, const unsigned int* bits, cons
 int fs_frame_overlay_hwc(const unsigned char* img, long sb, long sy, int sx, const unsigned int* bits, const unsigned int* band,
                          const long long* stats, const float* focus, const long long* live, long live_stride, const int* style, int S,
                          unsigned char* out, long ob, long oy, int ox, int B, int H, int W, fs_stream_t stream);
+/* fs_frame_overlay_u8 on an NV12 frame ("frames as NV12" above), read where it lies: s_c is the converted pixel's byte; the destinations as
+ * above, never the frame itself: FS_ERR_ARG for out == yp or out == uvp (no destination has the frame's description); that out overlaps
+ * neither plane otherwise is the caller's duty, as for every entry point.  Sixteen pixels a lane on route 1 of fs_nv12_frame_route and a
+ * destination as above, one otherwise. */
+int fs_frame_overlay_nv12(const unsigned char* yp, const unsigned char* uvp, long sb, long sy, long ub, long uy, int yo, int yg, int rv, int gu,
+                          int gv, int bu, const unsigned int* bits, const unsigned int* band, const long long* stats, const float* focus,
+                          const long long* live, long live_stride, const int* style, int S, unsigned char* out, long ob, long oy, int ox,
+                          int B, int H, int W, fs_stream_t stream);
 /* A class map as colours: utils.py:207-221 colorEncode(labelmap, colors, mode='RGB') for fs_unwarp_labels' map.  labels (B,H,W) int64,
  * palette (K,3) bytes; out, described as fs_frame_overlay's destination, = palette[label], (0, 0, 0) for a label < 0 or >= K.  The
  * reference skips negative labels, which leaves its zeros, and would raise an IndexError on a label >= K: black there is this library's
