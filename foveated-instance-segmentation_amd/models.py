@@ -12,6 +12,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
+from . import frames, masks
 from . import modules as M
 from . import ops
 from .weights import apply_name_keyed_init  # noqa: F401  (re-export for callers)
@@ -220,8 +221,7 @@ class DeformSegmentationModule(nn.Module):
         ops.reset_step_state()
         # a uint8 view of interleaved bytes (ops.byte_frame_layout: a permuted HWC / RGBA buffer) is read where it lies
         # so is an NV12 frame (ops.Nv12Frame: a decoder's surface), each tap converted to its RGB byte as it is read
-        hwc = isinstance(img, ops.Nv12Frame) or (img.dtype == torch.uint8 and not img.is_contiguous() and ops.byte_frame_layout(img) is not None)
-        x = img if hwc else img.contiguous()
+        x, _in_place = frames.frame_in_place(img)
         xs, _ = self.saliency(x, focus.float().contiguous())
         self._note_nan(xs)
         if self.cfg.MODEL.uniform_sample != "":
@@ -286,7 +286,7 @@ class DeformSegmentationModule(nn.Module):
             if snap_px is not None:
                 raise ValueError("snap_px goes with component = 4 or 8")
         else:
-            ops._component_args(component, snap_px)
+            masks._component_args(component, snap_px)
         cls, m, grid, seg_size = self._head_parts(img, focus, seg_size, "predict_instances")
         if component is not None:
             out = ops.unwarp_instances(cls, m, grid, *seg_size, max_runs=max_runs, return_bits=return_bits, score=return_score,
@@ -338,7 +338,8 @@ class DeformSegmentationModule(nn.Module):
             if snap_px is not None:
                 raise ValueError("snap_px goes with component = 4 or 8")
         else:
-            ops._component_args(component, snap_px)
+            masks._component_args(component, snap_px)
+        # each kind of label checks its own arguments and says how its bit words are made once the record's are there; nothing runs before
         if candidates is not None:
             if seg_label is not None or cls_label is not None:
                 raise ValueError("with candidates the label is the selected candidate: seg_label and cls_label must be None")
@@ -348,19 +349,16 @@ class DeformSegmentationModule(nn.Module):
                 raise ValueError("candidates need seg_size = (H, W): bit words do not carry their width")
             cbits, cand_off, cand_cat = candidates
             label_size = (int(seg_size[0]), int(seg_size[1]))
-            ops._component_args(8, cand_snap_px)
-            _N, Hc, _P, Bc = ops._candidate_args(cbits, cand_off, label_size[1], cand_cat)          # before the network runs
+            masks._component_args(8, cand_snap_px)
+            _N, Hc, _P, Bc = masks._candidate_args(cbits, cand_off, label_size[1], cand_cat)        # before the network runs
             if Hc != label_size[0] or Bc != img.shape[0]:
                 raise ValueError(f"candidates of height {Hc} for {Bc} images do not go with seg_size {label_size} and img's batch size {img.shape[0]}")
-            d = ops.boundary_dilation(*label_size, boundary)
-            if d > ops.MORPH_MAX_D:
-                raise ValueError(f"boundary {boundary!r} gives a dilation of {d} pixels at {label_size}, above ops.MORPH_MAX_D = {ops.MORPH_MAX_D}")
-            out = self.predict_instances(img, focus, label_size, max_runs=max_runs, return_bits=True, return_score=True, component=component,
-                                         snap_px=snap_px)
-            gbits, sel, _cand = ops.mask_candidates(cbits, cand_off, focus, label_size[1], pred=out[3], cand_cat=cand_cat, snap_px=cand_snap_px)
-            pair = ops.mask_pair_counts(out[3], gbits, d, Ws=label_size[1])
-            return out[:3] + out[4:] + (pair, sel)
-        if isinstance(seg_label, (tuple, list)):
+            d = masks.boundary_dilation_capped(*label_size, boundary)
+
+            def label_words(bits):                      # the candidate the gaze selects, and sel behind the pair
+                gbits, sel, _cand = ops.mask_candidates(cbits, cand_off, focus, label_size[1], pred=bits, cand_cat=cand_cat, snap_px=cand_snap_px)
+                return gbits, (sel,)
+        elif isinstance(seg_label, (tuple, list)):
             if len(seg_label) != 2:
                 raise ValueError(f"a run-length label is a tuple (counts, n_runs), got {len(seg_label)} elements")
             if seg_size is None or len(seg_size) != 2:
@@ -370,33 +368,30 @@ class DeformSegmentationModule(nn.Module):
             if not isinstance(counts, torch.Tensor) or counts.dim() != 2 or counts.shape[0] != img.shape[0] or cls_label.shape[0] != img.shape[0]:
                 raise ValueError(f"counts {tuple(getattr(counts, 'shape', ()))} and cls_label {tuple(cls_label.shape)} must have img's batch size "
                                  f"{img.shape[0]}")
-            d = ops.boundary_dilation(*label_size, boundary)
-            if d > ops.MORPH_MAX_D:
-                raise ValueError(f"boundary {boundary!r} gives a dilation of {d} pixels at {label_size}, above ops.MORPH_MAX_D = {ops.MORPH_MAX_D}")
-            ops._rle_args(counts, n_runs, label_size)                               # other dtypes and shapes raise before the network runs
-            out = self.predict_instances(img, focus, label_size, max_runs=max_runs, return_bits=True, return_score=True, component=component,
-                                         snap_px=snap_px)
-            label, _info = ops.rle_bits(counts, n_runs, label_size)                 # behind the network's peak, where mask_bits stands
-            pair = ops.mask_pair_counts(out[3], label, d, Ws=label_size[1])
-            return out[:3] + out[4:] + (pair,)
-        if seg_label.dim() not in (3, 4) or (seg_label.dim() == 4 and seg_label.shape[1] != 1):
-            raise ValueError(f"seg_label must be (B,H,W) or (B,1,H,W), got {tuple(seg_label.shape)}")
-        label_size = (int(seg_label.shape[-2]), int(seg_label.shape[-1]))
-        if seg_size is not None and (len(seg_size) != 2 or (int(seg_size[0]), int(seg_size[1])) != label_size):
-            raise ValueError(f"seg_size {tuple(seg_size)} differs from the label's size {label_size}: the counters are taken pixel against pixel")
-        if seg_label.shape[0] != img.shape[0] or cls_label.shape[0] != img.shape[0]:
-            raise ValueError(f"seg_label {tuple(seg_label.shape)} and cls_label {tuple(cls_label.shape)} must have img's batch size {img.shape[0]}")
-        d = ops.boundary_dilation(*label_size, boundary)
-        if d > ops.MORPH_MAX_D:
-            raise ValueError(f"boundary {boundary!r} gives a dilation of {d} pixels at {label_size}, above ops.MORPH_MAX_D = {ops.MORPH_MAX_D}")
+            d = masks.boundary_dilation_capped(*label_size, boundary)
+            masks._rle_args(counts, n_runs, label_size)                             # other dtypes and shapes raise before the network runs
+
+            def label_words(bits):
+                return ops.rle_bits(counts, n_runs, label_size)[0], ()
+        else:
+            if seg_label.dim() not in (3, 4) or (seg_label.dim() == 4 and seg_label.shape[1] != 1):
+                raise ValueError(f"seg_label must be (B,H,W) or (B,1,H,W), got {tuple(seg_label.shape)}")
+            label_size = (int(seg_label.shape[-2]), int(seg_label.shape[-1]))
+            if seg_size is not None and (len(seg_size) != 2 or (int(seg_size[0]), int(seg_size[1])) != label_size):
+                raise ValueError(f"seg_size {tuple(seg_size)} differs from the label's size {label_size}: the counters are taken pixel against pixel")
+            if seg_label.shape[0] != img.shape[0] or cls_label.shape[0] != img.shape[0]:
+                raise ValueError(f"seg_label {tuple(seg_label.shape)} and cls_label {tuple(cls_label.shape)} must have img's batch size {img.shape[0]}")
+            d = masks.boundary_dilation_capped(*label_size, boundary)
+
+            def label_words(bits):
+                y = seg_label.reshape(seg_label.shape[0], *label_size)
+                # seg_label.long() != 0 without the int64 copy: truncation towards 0 keeps what is at least 1 in magnitude (NaN: unset)
+                return ops.mask_bits((y >= 1) | (y <= -1) if y.is_floating_point() else y != 0), ()
         out = self.predict_instances(img, focus, label_size, max_runs=max_runs, return_bits=True, return_score=True, component=component,
                                      snap_px=snap_px)
-        bits = out[3]
-        y = seg_label.reshape(seg_label.shape[0], *label_size)
-        # seg_label.long() != 0 without the int64 copy: truncation towards 0 keeps what is at least 1 in magnitude (NaN: unset)
-        label = ops.mask_bits((y >= 1) | (y <= -1) if y.is_floating_point() else y != 0)
-        pair = ops.mask_pair_counts(bits, label, d, Ws=label_size[1])
-        return out[:3] + out[4:] + (pair,)
+        label, extra = label_words(out[3])                                          # behind the network's peak
+        pair = ops.mask_pair_counts(out[3], label, d, Ws=label_size[1])
+        return out[:3] + out[4:] + (pair,) + extra
 
     @torch.no_grad()
     def evaluate(self, img, focus, seg_label, cls_label, seg_size=None, return_labels=False, class_areas=False, hausdorff=None, trimap=None, trimap_frame=True):

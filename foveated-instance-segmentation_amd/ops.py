@@ -16,6 +16,14 @@ import torch
 from torch.autograd import Function
 
 from . import hip
+# the stateless serving and scoring ops live in modules of their own (DESIGN.md "Where things live"); every public name of theirs stays
+# reachable as ops.<name>.  What is assigned through this module (TIMER, ACT_TRACE, FUSE_*, ...) is defined here, and they read none of it.
+from .frames import *  # noqa: F401,F403
+from .masks import *  # noqa: F401,F403
+from .gaze import *  # noqa: F401,F403
+from .overlay import *  # noqa: F401,F403
+from .unwarp import *  # noqa: F401,F403
+from .frames import _FRAME_TYPES, Nv12Frame, _frame_args, _frame_route      # the timed front-end ops below read frames through them
 
 ACT_NONE, ACT_RELU, ACT_RELU6 = 0, 1, 2
 BN_EPS = 1e-5
@@ -1333,274 +1341,6 @@ class SegLoss(Function):
 # ----------------------------------------------------------------------------------------------
 # foveation front-end
 # ----------------------------------------------------------------------------------------------
-def byte_frame_strides(shape, strides):
-    """byte_frame_layout's rule as a pure function of a (B,3,H,W) shape and its element strides (sb, sc, sy, sx); strides of dimensions
-    of size 1 are ignored.  ("planar",) for a contiguous tensor; ("hwc", sb, sy, sx) for interleaved bytes -- sc == 1, sx in {3, 4}, sy
-    >= W * sx, and sb == 0 (every viewer sees the one frame), sb >= H * sy or B == 1; None for anything else.  In the hwc tuple the
-    ignored strides are normalised: sb = 0 for B == 1, sy = W * sx for H == 1, sx = 3 for W == 1."""
-    B, C, H, W = (int(v) for v in shape)
-    sb, sc, sy, sx = (int(v) for v in strides)
-    if C != 3 or min(B, H, W) < 1:
-        return None
-    if (W == 1 or sx == 1) and (H == 1 or sy == W) and (sc == H * W) and (B == 1 or sb == 3 * H * W):
-        return ("planar",)
-    if sc != 1:
-        return None
-    if W == 1:
-        sx = 3
-    if sx not in (3, 4):
-        return None
-    if H == 1:
-        sy = W * sx
-    if sy < W * sx:
-        return None
-    if B == 1:
-        sb = 0
-    if sb != 0 and sb < H * sy:
-        return None
-    return ("hwc", sb, sy, sx)
-
-
-def byte_frame_layout(img):
-    """How a uint8 frame (B,3,H,W) lies in memory, from its strides alone: ("planar",) when it is contiguous (the fs_*_u8 route);
-    ("hwc", sb, sy, sx) when it is a view of interleaved bytes, the byte of channel c at (b, y, x) being byte b * sb + y * sy + x * sx + c
-    from img.data_ptr() (the fs_*_hwc route: nothing is copied); None for anything else.  An hwc view is what a camera's or a decoder's
-    (B,H,W,3) or (B,H,W,4) buffer is after permute(0, 3, 1, 2) (and [:, :3] for RGBA / RGBX, whose fourth byte is never used): tight or
-    with padded rows, a crop of a larger buffer, x.contiguous(memory_format=torch.channels_last), or one frame expanded over the batch
-    (sb == 0).  The channel order is the tensor's own.  The kernels read whole pixels, so the W * sx bytes of the last row must lie inside
-    the tensor's storage (an RGBA view's last alpha byte: true of every view of a real (B,H,W,4) buffer); a view that ends short is None."""
-    if not isinstance(img, torch.Tensor) or img.dim() != 4 or img.dtype != torch.uint8 or img.shape[1] != 3 or img.numel() == 0:
-        return None
-    if img.is_contiguous():
-        return ("planar",)
-    layout = byte_frame_strides(img.shape, img.stride())
-    if layout is not None and layout[0] == "hwc":
-        _, sb, sy, sx = layout
-        if img.storage_offset() + (img.shape[0] - 1) * sb + (img.shape[2] - 1) * sy + img.shape[3] * sx > img.untyped_storage().nbytes():
-            return None
-    return layout
-
-
-def _byte_frame(img, what="img"):
-    """("planar",) or ("hwc", ...) of a uint8 frame the *_u8 functions take; ValueError for any other layout, before any launch."""
-    layout = byte_frame_layout(img)
-    if layout is None:
-        raise ValueError(f"{what} must be a contiguous uint8 (B,3,H,W) or a view of interleaved (B,H,W,3) / (B,H,W,4) bytes "
-                         f"(ops.byte_frame_layout), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))} with strides "
-                         f"{tuple(img.stride()) if isinstance(img, torch.Tensor) else None}; call .contiguous() on it")
-    return layout
-
-
-NV12_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}          # (Kr, Kb)
-NV12_COEF_MAX = 32768
-
-
-def nv12_csc(matrix, full_range=False):
-    """The integer colour table (yo, yg, rv, gu, gv, bu) of an NV12 frame (include/fovealseg.h "frames as NV12"): rint(256 * real
-    coefficient) from the matrix's (Kr, Kb); the luma gain is 255 / 219 and the chroma gain 255 / 224 for limited range (yo = 16), both 1
-    for full range (yo = 0).  matrix: "bt601" or "bt709"."""
-    if matrix not in NV12_MATRICES:
-        raise ValueError(f"matrix must be one of {sorted(NV12_MATRICES)}, got {matrix!r}")
-    kr, kb = NV12_MATRICES[matrix]
-    kg = 1.0 - kr - kb
-    ly, lc = (1.0, 1.0) if full_range else (255.0 / 219.0, 255.0 / 224.0)
-    real = (ly, lc * 2 * (1 - kr), -lc * 2 * (1 - kb) * kb / kg, -lc * 2 * (1 - kr) * kr / kg, lc * 2 * (1 - kb))
-    return (0 if full_range else 16,) + tuple(int(round(256.0 * v)) for v in real)
-
-
-def _nv12_table(csc):
-    try:
-        t = tuple(operator.index(v) for v in csc)
-    except TypeError:
-        t = ()
-    if len(t) != 6 or any(isinstance(v, bool) for v in csc):
-        raise ValueError(f"csc must be six integers (yo, yg, rv, gu, gv, bu), got {csc!r}")
-    if not 0 <= t[0] <= 255 or any(abs(v) > NV12_COEF_MAX for v in t[1:]):
-        raise ValueError(f"csc wants 0 <= yo <= 255 and every coefficient in [-{NV12_COEF_MAX}, {NV12_COEF_MAX}], got {t}")
-    return t
-
-
-def nv12_frame_strides(y_shape, y_strides, uv_shape, uv_strides):
-    """(sb, sy, ub, uy) of an NV12 frame from the shapes and strides of its two views alone, or None: y (B,H,W) with unit column stride
-    and rows sy >= W apart, uv (B,ceil(H/2),ceil(W/2),2) with strides (ub, uy, 2, 1) and rows uy >= 2 * ceil(W/2) apart; images that do
-    not overlap (sb >= H * sy, ub >= ceil(H/2) * uy) or are all one image (sb = ub = 0).  The strides of a dimension of one element are
-    normalised: sb = ub = 0 for B == 1, sy = W for H == 1, uy = 2 * ceil(W/2) for one chroma row."""
-    if len(y_shape) != 3 or len(uv_shape) != 4:
-        return None
-    B, H, W = (int(v) for v in y_shape)
-    if min(B, H, W) < 1:
-        return None
-    Hc, Wc = (H + 1) // 2, (W + 1) // 2
-    if tuple(int(v) for v in uv_shape) != (B, Hc, Wc, 2):
-        return None
-    sb, sy, sx = (int(v) for v in y_strides)
-    ub, uy, ux, uc = (int(v) for v in uv_strides)
-    if (W > 1 and sx != 1) or uc != 1 or (Wc > 1 and ux != 2):
-        return None
-    if H == 1:
-        sy = W
-    if Hc == 1:
-        uy = 2 * Wc
-    if B == 1:
-        sb = ub = 0
-    if sy < W or uy < 2 * Wc or sb < 0 or ub < 0:
-        return None
-    if not (sb == 0 and ub == 0) and (sb < H * sy or ub < Hc * uy):
-        return None
-    return sb, sy, ub, uy
-
-
-class Nv12Frame:
-    """An NV12 frame of B images of H x W pixels where a decoder or a camera left it (include/fovealseg.h "frames as NV12"; unpinned):
-    y (B,H,W) uint8, the luma plane, a device tensor or view with unit column stride; uv (B,ceil(H/2),ceil(W/2),2) uint8, the interleaved
-    chroma plane, a view with strides (ub, uy, 2, 1).  Two allocations, or two views of one surface (nv12_from_surface).  matrix: "bt601"
-    or "bt709", with full_range -- it has no default: a silent wrong colour matrix is worse than a required keyword; csc: a table of the
-    caller's own (yo, yg, rv, gu, gv, bu) instead (nv12_csc's rule; matrix is then only a label and may be None).
-
-    predict*, evaluate*, GazeSession.step / render and the ops that take a uint8 frame take this object in its place, and give what they
-    give on the planar uint8 frame nv12_to_rgb(frame), bit for bit; the frame is read where it lies and never written.  It shows
-    shape == (B,3,H,W), dtype == torch.uint8, device and is_cuda as that frame would.  ValueError for any other dtypes, shapes or
-    strides, views on different devices, bytes the kernels may read outside the tensors' storage, or a table out of range."""
-
-    def __init__(self, y, uv, *, matrix, full_range=False, csc=None):
-        if not isinstance(y, torch.Tensor) or not isinstance(uv, torch.Tensor) or y.dtype != torch.uint8 or uv.dtype != torch.uint8:
-            raise ValueError(f"y and uv must be uint8 tensors, got {getattr(y, 'dtype', None)} and {getattr(uv, 'dtype', None)}")
-        strides = nv12_frame_strides(y.shape, y.stride(), uv.shape, uv.stride()) if y.dim() == 3 and uv.dim() == 4 else None
-        if strides is None:
-            raise ValueError(f"y must be a non-empty (B,H,W) with unit column stride and uv (B,ceil(H/2),ceil(W/2),2) with strides (ub, uy, 2, 1), "
-                             f"rows and images that do not overlap (or one image expanded over the batch in both), got {tuple(y.shape)} with "
-                             f"strides {tuple(y.stride())} and {tuple(uv.shape)} with strides {tuple(uv.stride())}")
-        if y.device != uv.device:
-            raise ValueError(f"y and uv must be on one device, got {y.device} and {uv.device}")
-        B, H, W = (int(v) for v in y.shape)
-        sb, sy, ub, uy = strides
-        if (y.storage_offset() + (B - 1) * sb + (H - 1) * sy + W > y.untyped_storage().nbytes()
-                or uv.storage_offset() + (B - 1) * ub + ((H + 1) // 2 - 1) * uy + 2 * ((W + 1) // 2) > uv.untyped_storage().nbytes()):
-            raise ValueError("y or uv ends short of the bytes its shape and strides describe")
-        if csc is None:
-            csc = nv12_csc(matrix, full_range)
-        elif matrix is not None and matrix not in NV12_MATRICES:
-            raise ValueError(f"matrix must be one of {sorted(NV12_MATRICES)} or None beside csc, got {matrix!r}")
-        self.y, self.uv = y, uv
-        self.matrix, self.full_range = matrix, bool(full_range)
-        self.csc = _nv12_table(csc)
-        self.strides = strides
-        # what _frame_route and _frame_args hand to every call, made once: the planes stay where they are while the frame holds them
-        self._tail = self.strides + self.csc
-        self._args = (y.data_ptr(), uv.data_ptr()) + self._tail
-        self.shape = torch.Size((B, 3, H, W))
-        self.dtype = torch.uint8
-        self.device = y.device
-        self.is_cuda = y.is_cuda
-
-    def dim(self):
-        return 4
-
-    def numel(self):
-        return self.shape.numel()
-
-    def like(self, y, uv):
-        """The frame of other planes under this frame's colour table."""
-        return Nv12Frame(y, uv, matrix=self.matrix, full_range=self.full_range, csc=self.csc)
-
-    def route(self):
-        """fs_nv12_frame_route of the frame: 1 the vector forms, 0 the one-pixel forms."""
-        return int(hip.load().fs_nv12_frame_route(self.y.data_ptr(), self.uv.data_ptr(), *self.strides, int(self.shape[3])))
-
-
-_FRAME_TYPES = (torch.Tensor, Nv12Frame)
-
-
-def nv12_from_surface(buf, H, W, pitch, uv_offset, batch_stride=None, *, matrix, full_range=False, csc=None):
-    """The Nv12Frame of one decoder surface: buf, a uint8 tensor of the surface's bytes (any shape; it is read flat and must be
-    contiguous); B = its images.  Luma rows lie pitch apart from byte 0 of an image, chroma rows pitch apart from byte uv_offset (H *
-    pitch for a tight surface; decoders that align the plane give their own); images batch_stride apart (None: one image, B = 1)."""
-    if not isinstance(buf, torch.Tensor) or buf.dtype != torch.uint8 or not buf.is_contiguous():
-        raise ValueError(f"buf must be a contiguous uint8 tensor, got {getattr(buf, 'dtype', None)}")
-    H, W, pitch, uv_offset = int(H), int(W), int(pitch), int(uv_offset)
-    Hc, Wc = (H + 1) // 2, (W + 1) // 2
-    if min(H, W) < 1 or pitch < max(W, 2 * Wc) or uv_offset < H * pitch:
-        raise ValueError(f"a surface of {H} x {W} pixels wants pitch >= {max(W, 2 * Wc)} and uv_offset >= H * pitch, got {pitch} and {uv_offset}")
-    flat = buf.view(-1)
-    per = uv_offset + (Hc - 1) * pitch + 2 * Wc
-    if batch_stride is None:
-        B, batch_stride = 1, per
-    else:
-        batch_stride = int(batch_stride)
-        if batch_stride < uv_offset + Hc * pitch:
-            raise ValueError(f"batch_stride must be at least uv_offset + ceil(H/2) * pitch = {uv_offset + Hc * pitch}, got {batch_stride}")
-        B = (flat.numel() - per) // batch_stride + 1 if flat.numel() >= per else 0
-    if flat.numel() < per or B < 1:
-        raise ValueError(f"buf has {flat.numel()} bytes, one image of this surface needs {per}")
-    y = flat.as_strided((B, H, W), (batch_stride, pitch, 1))
-    uv = flat.as_strided((B, Hc, Wc, 2), (batch_stride, pitch, 2, 1), flat.storage_offset() + uv_offset)      # as_strided counts from the storage
-    return Nv12Frame(y, uv, matrix=matrix, full_range=full_range, csc=csc)
-
-
-def nv12_to_rgb(frame, out=None):
-    """The RGB bytes of an NV12 frame (fs_nv12_to_rgb; no autograd; unpinned): out, a uint8 (B,3,H,W) tensor, contiguous or a view of
-    interleaved (B,H,W,3) / (B,H,W,4) bytes (byte_frame_dest; RGBA gets alpha 255); None: a new contiguous one.  The planar result is
-    the frame every other entry point is equal on.  Returns out."""
-    if not isinstance(frame, Nv12Frame):
-        raise ValueError(f"frame must be an ops.Nv12Frame, got {type(frame).__name__}")
-    B, _, H, W = (int(v) for v in frame.shape)
-    if out is None:
-        out = torch.empty(B, 3, H, W, device=frame.device, dtype=torch.uint8)
-    dest = byte_frame_dest(out, (B, 3, H, W))
-    suffix, strides = _frame_route(frame)
-    hip.call("fs_nv12_to_rgb", *_frame_args(frame, strides), *_dest_args(out, dest), B, H, W)
-    return out
-
-
-def _frame_route(img, what="img"):
-    """Which of a pass's four entry points reads the frame img, and what follows the frame's pointer in its arguments: ("", ()) for fp32,
-    ("_u8", ()) for contiguous bytes, ("_hwc", (sb, sy, sx)) for an hwc view, ("_nv12", (sb, sy, ub, uy, yo, yg, rv, gu, gv, bu)) for an
-    Nv12Frame; ValueError for bytes in any other layout (_byte_frame).  A function of type, dtype, shape, strides and storage size
-    alone: no device is asked."""
-    if isinstance(img, Nv12Frame):
-        return "_nv12", img._tail
-    if img.dtype != torch.uint8:
-        return "", ()
-    layout = _byte_frame(img, what)
-    return ("_u8", ()) if layout[0] == "planar" else ("_hwc", layout[1:])
-
-
-def _frame_args(img, strides):
-    """The frame's leading arguments of the entry point _frame_route chose: the device pointer and the strides of an hwc view (which is
-    not contiguous, as hip.ptr asks of every other tensor), the two plane pointers, the strides and the table of an Nv12Frame."""
-    if not strides:
-        return (hip.ptr(img),)
-    if not img.is_cuda:
-        raise hip.HipLibraryError("fovealseg kernels need device tensors (got a CPU tensor); there is no CPU path")
-    if isinstance(img, Nv12Frame):
-        return img._args
-    return (img.data_ptr(),) + strides
-
-
-def byte_frame_select(img, sel):
-    """img.index_select(0, sel) for an hwc view that stays one: the rows of the chosen frames are gathered from the underlying bytes (3 * H *
-    W or 4 * H * W bytes a frame, never a planar copy) and viewed as (n,3,H,W) again.  With sb == 0 the n frames are the one frame.  An
-    Nv12Frame stays one likewise: the chosen frames' luma and chroma rows are gathered as they lie, 1.5 bytes a pixel, no RGB copy."""
-    if isinstance(img, Nv12Frame):
-        B, _, H, W = (int(v) for v in img.shape)
-        n = int(sel.shape[0])
-        sb, sy, ub, uy = img.strides
-        Hc, Wc = (H + 1) // 2, (W + 1) // 2
-        if sb == 0 and ub == 0:
-            return img.like(img.y[:1].expand(n, H, W), img.uv[:1].expand(n, Hc, Wc, 2))
-        return img.like(img.y.index_select(0, sel), img.uv.index_select(0, sel))
-    layout = byte_frame_layout(img)
-    if layout is None or layout[0] != "hwc":
-        return img.index_select(0, sel)
-    _, sb, sy, sx = layout
-    B, _, H, W = (int(v) for v in img.shape)
-    n = int(sel.shape[0])
-    if sb == 0:
-        return img[:1].expand(n, 3, H, W)
-    rows = img.as_strided((B, H, W * sx), (sb, sy, 1)).index_select(0, sel)
-    return rows.view(n, H, W, sx).permute(0, 3, 1, 2)[:, :3]
-
-
 def gaze_lowres(x, focus, hs, ws):
     B, C, H, W = x.shape
     assert C == 3
@@ -1802,1426 +1542,6 @@ def grid_sample_label(y, grid, return_float=False):
     ys = torch.empty(B, h, w, device=y.device, dtype=torch.float32) if return_float else None
     _launch("fe_grid_sample_label", 4.0 * B * h * w * (4 + 2 + 2), "fs_grid_sample_label", hip.ptr(y), hip.ptr(grid), hip.ptr(label), hip.ptr(ys), B, H, W, h, w)
     return (label, ys) if return_float else label
-
-
-def inverse_index_maps(grid, H, W):
-    n = grid.numel() // 2
-    u = torch.empty(grid.shape[:-1], device=grid.device, dtype=torch.int64)
-    v = torch.empty_like(u)
-    hip.call("fs_inverse_index_maps", hip.ptr(grid), hip.ptr(u), hip.ptr(v), n, H, W)
-    return u, v
-
-
-def inverse_grid(grid, Hs, Ws):
-    """models/models.py:639-655: (owner (B,Hs,Ws) int32 with -1 in holes, grid_inv (B,Hs,Ws,2) with 0 in holes)."""
-    B, h, w, _ = grid.shape
-    owner = torch.empty(B, Hs, Ws, device=grid.device, dtype=torch.int32)
-    inv = torch.empty(B, Hs, Ws, 2, device=grid.device, dtype=torch.float32)
-    hip.call("fs_inverse_grid", hip.ptr(grid.contiguous()), hip.ptr(owner), hip.ptr(inv), B, h, w, Hs, Ws)
-    return owner, inv
-
-
-def unwarp_nearest(pred, grid, Hs, Ws):
-    """Full-resolution prediction from the foveated one (no autograd): pred (B,C,h,w) is sampled through the inverse grid
-    (F.grid_sample(pred, grid_inv), models/models.py:933) and the never-claimed pixels take their nearest claimed
-    neighbour (rev_deform_interp='nearest').  Returns (pred_full (B,C,Hs,Ws), hole mask (B,Hs,Ws) bool)."""
-    B, C, h, w = pred.shape
-    owner, inv = inverse_grid(grid, Hs, Ws)
-    out = torch.empty(B, C, Hs, Ws, device=pred.device, dtype=torch.float32)
-    hip.call("fs_grid_sample_fwd", hip.ptr(pred.contiguous()), hip.ptr(inv), hip.ptr(out), B, C, h, w, Hs, Ws, 0)
-    scratch = torch.empty(2 * B * Hs * Ws, device=pred.device, dtype=torch.int32)
-    hip.call("fs_fill_nearest", hip.ptr(out), hip.ptr(owner), hip.ptr(scratch), B, C, Hs, Ws)
-    return out, owner < 0
-
-
-def unwarp_labels(cls, m, grid, Hs, Ws):
-    """Full-resolution class map of the C1 head (no autograd): bit for bit
-    `unwarp_nearest(PredAssemble.apply(cls, m), grid, Hs, Ws)[0].argmax(1)`, without the (B,K,Hs,Ws) prediction -- the argmax is
-    taken once per grid point and gathered through the owner map (fs_unwarp_labels).  cls (B,K), m (B,h,w) at the grid's
-    resolution, grid (B,h,w,2).  Returns (labels (B,Hs,Ws) int64, hole mask (B,Hs,Ws) bool)."""
-    B, K = cls.shape
-    _, h, w, _ = grid.shape
-    if tuple(m.shape) != (B, h, w):
-        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
-    labels = torch.empty(B, Hs, Ws, device=cls.device, dtype=torch.int64)
-    hole = torch.empty(B, Hs, Ws, device=cls.device, dtype=torch.bool)
-    scratch = torch.empty(hip.query("fs_unwarp_labels_scratch_ints", B, h, w, Hs, Ws), device=cls.device, dtype=torch.int32)
-    hip.call("fs_unwarp_labels", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(labels),
-             hip.ptr(hole), hip.ptr(scratch), B, K, h, w, Hs, Ws)
-    return labels, hole
-
-
-def _max_runs(max_runs, Ws):
-    """The capacity of a run-length code: any int >= 1; None = 8 * Ws + 1, which holds every mask whose columns each cross its outline
-    at most eight times (a blob entered and left four times by a column) -- 32 KB of int32 per 1024-wide image."""
-    if max_runs is None:
-        return 8 * int(Ws) + 1
-    if isinstance(max_runs, bool) or int(max_runs) != max_runs or int(max_runs) < 1:
-        raise ValueError(f"max_runs must be an integer >= 1, got {max_runs!r}")
-    return int(max_runs)
-
-
-def mask_bits(mask):
-    """A mask as bit words (fs_mask_bits; no autograd): mask (B,Hs,Ws) or (Hs,Ws), bool or uint8 (non-zero = set), on the device.
-    Returns bits (B,Hs,P) int32, P = ceil(Ws / 32): bit j of word i of row y is pixel x = 32 i + j, the bits at x >= Ws are 0."""
-    if mask.dim() == 2:
-        mask = mask[None]
-    if mask.dim() != 3 or mask.numel() == 0:
-        raise ValueError(f"mask {tuple(mask.shape)} must be a non-empty (B, Hs, Ws)")
-    if mask.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"the mask must be bool or uint8, got {mask.dtype}")
-    B, Hs, Ws = (int(v) for v in mask.shape)
-    bits = torch.empty(B, Hs, (Ws + 31) // 32, device=mask.device, dtype=torch.int32)
-    hip.call("fs_mask_bits", hip.ptr(mask.contiguous()), hip.ptr(bits), B, Hs, Ws)
-    return bits
-
-
-def _bits_arg(mask_or_bits, Ws):
-    """(bits (B,Hs,P) int32, Ws) of a mask argument as mask_rle / mask_component take it; bits is None for a mask still to be packed."""
-    if not isinstance(mask_or_bits, torch.Tensor):
-        raise ValueError("the mask must be a tensor: bool / uint8 (B,Hs,Ws) or (Hs,Ws), or int32 bit words with Ws")
-    if mask_or_bits.dtype == torch.int32:
-        bits = mask_or_bits
-        if bits.dim() != 3 or bits.numel() == 0 or Ws is None or int(Ws) < 1 or bits.shape[2] != (int(Ws) + 31) // 32:
-            raise ValueError(f"bit words {tuple(bits.shape)} must be a non-empty (B, Hs, ceil(Ws / 32)) with Ws given, got Ws = {Ws!r}")
-        return bits, int(Ws)
-    if mask_or_bits.dtype not in (torch.bool, torch.uint8) or mask_or_bits.dim() not in (2, 3) or mask_or_bits.numel() == 0:
-        raise ValueError(f"the mask must be a non-empty bool / uint8 (B,Hs,Ws) or (Hs,Ws), got {mask_or_bits.dtype} {tuple(mask_or_bits.shape)}")
-    if Ws is not None and int(Ws) != mask_or_bits.shape[-1]:
-        raise ValueError(f"Ws = {Ws!r} differs from the mask's width {mask_or_bits.shape[-1]}")
-    return None, int(mask_or_bits.shape[-1])
-
-
-def _mask_words(mask_or_bits, Ws):
-    """_bits_arg with the mask packed: (bits (B,Hs,P) int32, Ws)."""
-    bits, Ws = _bits_arg(mask_or_bits, Ws)
-    return (mask_bits(mask_or_bits) if bits is None else bits), Ws
-
-
-def mask_rle(mask_or_bits, Ws=None, max_runs=None):
-    """Area, box and uncompressed COCO run-length code of any mask, exact and on the device (fs_mask_rle; no autograd).  The argument
-    is a bool / uint8 mask (B,Hs,Ws) or (Hs,Ws), or int32 bit words (B,Hs,ceil(Ws/32)) as mask_bits returns them together with Ws.
-    Returns (stats (B,6) int64 = area, x0, y0, bw, bh, n_runs; counts (B,max_runs) int32).  [x0, y0, bw, bh] is the COCO box of the set
-    pixels, all 0 for an empty mask.  counts is the code of the mask read column-major (p = x * Hs + y): the run of zeros before the
-    first set pixel (0 when pixel (0,0) is set), then alternating run lengths, runs continuing from the bottom of a column into the
-    top of the next; an empty mask is [Hs * Ws], a full one [0, Hs * Ws].  n_runs is always the true length of the code; the first
-    min(n_runs, max_runs) entries of counts are its, the rest is 0, and n_runs > max_runs tells that the code was cut.  max_runs
-    defaults to 8 * Ws + 1 (see _max_runs).  The format is restated from its published definition (pycocotools' uncompressed RLE)."""
-    bits, Ws = _mask_words(mask_or_bits, Ws)
-    B, Hs = int(bits.shape[0]), int(bits.shape[1])
-    cap = _max_runs(max_runs, Ws)
-    stats = torch.empty(B, 6, device=bits.device, dtype=torch.int64)
-    counts = torch.empty(B, cap, device=bits.device, dtype=torch.int32)
-    scratch = torch.empty(hip.query("fs_mask_rle_scratch_ints", B, Hs, Ws), device=bits.device, dtype=torch.int32)
-    hip.call("fs_mask_rle", hip.ptr(bits.contiguous()), hip.ptr(stats), hip.ptr(counts), hip.ptr(scratch), B, Hs, Ws, cap)
-    return stats, counts
-
-
-COMPONENT_OFF2 = 2 ** 62                            # a squared distance no pixel reaches: snap_px = None
-
-
-def _component_args(component, snap_px):
-    """(conn, snap2) of mask_component / unwarp_instances(component=...): connectivity 4 or 8; snap_px None (no limit) or a finite number
-    of pixels >= 0, snap2 = floor(snap_px ** 2)."""
-    if isinstance(component, bool) or component not in (4, 8):
-        raise ValueError(f"the connectivity must be 4 or 8, got {component!r}")
-    if snap_px is None:
-        return int(component), COMPONENT_OFF2
-    px = float(snap_px)
-    if not (px >= 0.0) or math.isinf(px):
-        raise ValueError(f"snap_px must be a finite number of pixels >= 0, got {snap_px!r}")
-    return int(component), COMPONENT_OFF2 if px >= 2.0 ** 31 else int(math.floor(px * px))     # 2^31 squared is 2^62: no overflow in px * px
-
-
-def _focus_arg(focus, B, dev):
-    if not isinstance(focus, torch.Tensor) or tuple(focus.shape) != (B, 2):
-        raise ValueError(f"focus must be (B, 2) = ({B}, 2), got {tuple(getattr(focus, 'shape', ()))}")
-    return focus.to(device=dev, dtype=torch.float32).contiguous()
-
-
-def mask_component(mask_or_bits, focus, Ws=None, connectivity=8, snap_px=None):
-    """The connected component of a mask under the gaze, on the device and on bit words (fs_mask_component; no autograd; unpinned:
-    the reference has no counterpart).  The mask as mask_rle takes it: bool / uint8 (B,Hs,Ws) or (Hs,Ws), or int32 bit words
-    (B,Hs,ceil(Ws/32)) together with Ws.  focus (B,2) normalised (row, col), turned into a gaze pixel as gate_decide does.  The seed is
-    the gaze pixel where it is set, else the nearest set pixel (ties: the smaller row-major index), unless it lies more than snap_px
-    pixels away (None: any distance; snap2 = floor(snap_px ** 2) against the squared distance).  connectivity 4 or 8.  Returns
-    (bits_c (B,Hs,ceil(Ws/32)) int32, the component's words, all 0 where there is none; comp (B,4) int64 = (seed_y, seed_x, d2, area_all),
-    (-1, -1, -1, area_all) where there is none; area_all counts the input's set pixels).  mask_rle(bits_c, Ws) gives its record."""
-    conn, snap2 = _component_args(connectivity, snap_px)
-    bits, Ws = _mask_words(mask_or_bits, Ws)
-    B, Hs = int(bits.shape[0]), int(bits.shape[1])
-    f = _focus_arg(focus, B, bits.device)
-    out = torch.empty_like(bits, memory_format=torch.contiguous_format)
-    comp = torch.empty(B, 4, device=bits.device, dtype=torch.int64)
-    scratch = torch.empty(hip.query("fs_mask_component_scratch_ints", B, Hs, Ws), device=bits.device, dtype=torch.int32)
-    hip.call("fs_mask_component", hip.ptr(bits.contiguous()), hip.ptr(f), hip.ptr(out), hip.ptr(comp), hip.ptr(scratch), B, Hs, Ws, conn, snap2)
-    return out, comp
-
-
-def boundary_dilation(Hs, Ws, ratio=0.02):
-    """The dilation of Boundary IoU in pixels (Cheng et al., CVPR 2021, restated: unpinned): d = max(1, int(round(ratio *
-    math.sqrt(Hs * Hs + Ws * Ws)))) in Python floats, ratio a finite float > 0 -- 0.02 of the image diagonal, 29 at 1024 x 1024."""
-    if isinstance(Hs, bool) or isinstance(Ws, bool) or int(Hs) != Hs or int(Ws) != Ws or int(Hs) < 1 or int(Ws) < 1:
-        raise ValueError(f"the size must be two integers >= 1, got {(Hs, Ws)!r}")
-    if isinstance(ratio, bool) or not isinstance(ratio, (int, float)) or not (float(ratio) > 0.0) or math.isinf(float(ratio)):
-        raise ValueError(f"the boundary ratio must be a finite number > 0, got {ratio!r}")
-    Hs, Ws = int(Hs), int(Ws)
-    return max(1, int(round(float(ratio) * math.sqrt(Hs * Hs + Ws * Ws))))
-
-
-MORPH_MAX_D = 2047                                  # fs_mask_erode's cap: a diagonal of 100 000 pixels at the default ratio
-
-
-def _morph_d(d):
-    if isinstance(d, bool) or not isinstance(d, int) or d < 1 or d > MORPH_MAX_D:
-        raise ValueError(f"d must be an int 1 .. {MORPH_MAX_D}, got {d!r}")
-    return d
-
-
-def mask_erode(mask_or_bits, d, Ws=None):
-    """Erosion of a mask by a (2d+1) x (2d+1) square, on the device and on bit words (fs_mask_erode; no autograd; unpinned: restated
-    from the published definition of Boundary IoU).  The mask as mask_rle takes it: bool / uint8 (B,Hs,Ws) or (Hs,Ws), or int32 bit
-    words (B,Hs,ceil(Ws/32)) together with Ws; d an int >= 1 (and <= 2047), not a bool.  Returns bits (B,Hs,ceil(Ws/32)) int32: pixel
-    (y,x) is set iff every pixel of the square centred on it is set, every pixel outside the image counting as unset -- scipy's
-    binary_erosion(m, ones((3,3)), iterations=d, border_value=0); all 0 where 2d+1 exceeds a side."""
-    d = _morph_d(d)
-    bits, Ws = _mask_words(mask_or_bits, Ws)
-    B, Hs = int(bits.shape[0]), int(bits.shape[1])
-    out = torch.empty_like(bits, memory_format=torch.contiguous_format)
-    scratch = torch.empty(max(1, hip.query("fs_mask_erode_scratch_ints", B, Hs, Ws, d)), device=bits.device, dtype=torch.int32)
-    hip.call("fs_mask_erode", hip.ptr(bits.contiguous()), hip.ptr(out), hip.ptr(scratch), B, Hs, Ws, d)
-    return out
-
-
-def mask_boundary(mask_or_bits, d, Ws=None):
-    """The boundary band of Boundary IoU as bit words: m & ~mask_erode(m, d), the set pixels within d of an unset pixel or of the
-    image's outside (chessboard distance); the mask itself where 2d+1 exceeds a side.  Arguments as mask_erode's; the bits at
-    x >= Ws of the result are 0."""
-    d = _morph_d(d)
-    bits, Ws = _mask_words(mask_or_bits, Ws)
-    er = mask_erode(bits, d, Ws)
-    band = bits & ~er
-    if Ws & 31:
-        band[:, :, -1] &= (1 << (Ws & 31)) - 1                      # the input's padding bits are no pixels
-    return band
-
-
-def mask_pair_counts(a, b, d, Ws=None):
-    """The counters of mask IoU and Boundary IoU of a prediction a and a label b (fs_mask_pair_counts; no autograd; unpinned).  a and
-    b as mask_erode takes a mask, of one shape and kind; d as there.  Returns pair (B,6) int64 = (|a & b|, |a|, |b|, |band(a) &
-    band(b)|, |band(a)|, |band(b)|), band = mask_boundary's; both erosions and the counts are taken on the device without a host
-    read, on nothing wider than a bit a pixel.  pair_scores makes the two measures."""
-    d = _morph_d(d)
-    abits, Wa = _bits_arg(a, Ws)
-    bbits, Wb = _bits_arg(b, Ws)
-    if (abits is None) != (bbits is None) or tuple(a.shape[-2:]) != tuple(b.shape[-2:]) or Wa != Wb or a.device != b.device:
-        raise ValueError(f"the two masks must be of one kind, size and device, got {a.dtype} {tuple(a.shape)} and {b.dtype} {tuple(b.shape)}")
-    if abits is None:
-        if (a.dim() == 3 and b.dim() == 3 and a.shape[0] != b.shape[0]) or a.dim() != b.dim():
-            raise ValueError(f"the two masks must have one batch size, got {tuple(a.shape)} and {tuple(b.shape)}")
-        abits, bbits = mask_bits(a), mask_bits(b)
-    elif a.shape[0] != b.shape[0]:
-        raise ValueError(f"the two masks must have one batch size, got {tuple(a.shape)} and {tuple(b.shape)}")
-    B, Hs = int(abits.shape[0]), int(abits.shape[1])
-    pair = torch.empty(B, 6, device=abits.device, dtype=torch.int64)
-    scratch = torch.empty(max(1, hip.query("fs_mask_pair_scratch_ints", B, Hs, Wa, d)), device=abits.device, dtype=torch.int32)
-    hip.call("fs_mask_pair_counts", hip.ptr(abits.contiguous()), hip.ptr(bbits.contiguous()), hip.ptr(pair), hip.ptr(scratch), B, Hs, Wa, d)
-    return pair
-
-
-def pair_scores(pair):
-    """(iou, biou), two fp64 tensors (B,), from mask_pair_counts' counters: n / (a + b - n) per triple, 0 where the union is 0."""
-    if pair.dim() != 2 or pair.shape[1] != 6:
-        raise ValueError(f"pair must be (B, 6), got {tuple(pair.shape)}")
-    p = pair.to(torch.int64)
-    out = []
-    for o in (0, 3):
-        n, u = p[:, o], p[:, o + 1] + p[:, o + 2] - p[:, o]
-        out.append(torch.where(u > 0, n.double() / u.clamp(min=1).double(), torch.zeros_like(n, dtype=torch.float64)))
-    return out[0], out[1]
-
-
-def head_fg_q(cls, m):
-    """The C1 head's foreground probability per grid point as an integer table (fs_head_fg_q; no autograd; unpinned: the reference
-    has no counterpart).  cls (B,K), m (B,h,w).  Returns q (B, h*w+1) int32 = rint(P * 2^24): P is the softmax mass of the classes
-    below K-1 among the K fp32 values `unwarp_nearest(PredAssemble(cls, m), ...)` carries from grid point p (entry h*w: from the sample at
-    (0,0), which feeds an image without a claimed pixel), evaluated in fp64 with the maximum subtracted; 0 where P is NaN."""
-    B, K = cls.shape
-    if m.dim() != 3 or m.shape[0] != B:
-        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) with B = {B}")
-    h, w = int(m.shape[1]), int(m.shape[2])
-    q = torch.empty(B, h * w + 1, device=cls.device, dtype=torch.int32)
-    hip.call("fs_head_fg_q", hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(q), B, K, h, w)
-    return q
-
-
-def unwarp_instances(cls, m, grid, Hs, Ws, max_runs=None, return_bits=False, score=False, component=None, focus=None, snap_px=None):
-    """The gazed instance of the C1 head as a record instead of a class map (fs_unwarp_instances; no autograd).  Arguments and checks
-    are unwarp_labels'.  The mask is `unwarp_labels(cls, m, grid, Hs, Ws)[0] != K - 1` bit for bit; no (B,Hs,Ws) tensor wider than its
-    bit words is allocated.  Returns (cat, stats, counts[, bits]): cat (B,) int64 = torch.argmax(cls[:, :K-1], 1), the head's
-    classification (first maximum, NaN maximal); stats (B,6) int64 and counts (B,max_runs) int32 are mask_rle's of the mask; bits
-    (B,Hs,ceil(Ws/32)) int32 are mask_bits' of it.  cat is the label of every set pixel except where the bilinear sample of the constant
-    class planes ties two classes by rounding or has no in-bounds weight (a grid point on the outer border).  max_runs: any int >= 1,
-    default 8 * Ws + 1 -- room for a mask every column of which crosses its outline at most eight times, 32 KB per 1024-wide image;
-    n_runs = stats[:, 5] > max_runs tells a cut code.  instances_to_coco makes the result records.
-
-    score=True (fs_unwarp_instances_scored; unpinned) appends conf (B,3) fp32 = (score, cls_prob, mask_prob) and qsum (B,) int64 behind
-    everything else: qsum is the sum of head_fg_q(cls, m)[b, feeding point] over the set pixels, added in the same gather; mask_prob =
-    qsum / (area * 2^24), 0 for an empty mask; cls_prob = softmax(cls[b, :K-1])[cat[b]] in fp64, NaN where that row holds a NaN; score
-    = their product, the mean probability of class cat over the mask.  The other results are the unscored call's bit for bit.
-
-    component = 4 or 8 (fs_unwarp_instances_component; unpinned) keeps only the connected component of that mask under the gaze: focus
-    (B,2) normalised (row, col) and snap_px as mask_component's.  stats, counts, bits, qsum, mask_prob and score then describe the
-    component (the empty mask's record where there is none); cat and cls_prob are unchanged.  comp (B,4) int64 = (seed_y, seed_x, d2,
-    area_all) is appended as the last element, behind conf / qsum where present.  Nothing is read on the host in between."""
-    B, K = cls.shape
-    _, h, w, _ = grid.shape
-    if tuple(m.shape) != (B, h, w):
-        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
-    if component is None and (focus is not None or snap_px is not None):
-        raise ValueError("focus and snap_px go with component = 4 or 8")
-    Hs, Ws = int(Hs), int(Ws)
-    cap = _max_runs(max_runs, Ws)
-    dev = cls.device
-    comp = component is not None
-    if comp:
-        conn, snap2 = _component_args(component, snap_px)
-        if focus is None:
-            raise ValueError("component needs focus (B, 2): the gaze that picks it")
-        f = _focus_arg(focus, B, dev)
-    cat = torch.empty(B, device=dev, dtype=torch.int64)
-    stats = torch.empty(B, 6, device=dev, dtype=torch.int64)
-    counts = torch.empty(B, cap, device=dev, dtype=torch.int32)
-    bits = torch.empty(B, Hs, (Ws + 31) // 32, device=dev, dtype=torch.int32) if return_bits else None
-    conf = torch.empty(B, 3, device=dev, dtype=torch.float32) if score else None
-    qsum = torch.empty(B, device=dev, dtype=torch.int64) if score else None
-    cout = torch.empty(B, 4, device=dev, dtype=torch.int64) if comp else None
-    # the smallest entry point for what is asked; the component's takes conf and qsum null for no score
-    name = "fs_unwarp_instances_component" if comp else "fs_unwarp_instances_scored" if score else "fs_unwarp_instances"
-    scratch = torch.empty(hip.query(name + "_scratch_ints", B, h, w, Hs, Ws), device=dev, dtype=torch.int32)
-    tensors = ([cls.contiguous(), m.contiguous(), grid.contiguous()] + ([f] if comp else []) + [cat, stats, counts, bits] +
-               ([cout] if comp else []) + ([conf, qsum] if comp or score else []) + [scratch])
-    hip.call(name, *[hip.ptr(t) for t in tensors], B, K, h, w, Hs, Ws, cap, *((conn, snap2) if comp else ()))
-    return (cat, stats, counts) + ((bits,) if return_bits else ()) + ((conf, qsum) if score else ()) + ((cout,) if comp else ())
-
-
-RLE_STATUS = {0: "valid", 1: "the code was cut: n_runs exceeds the capacity of counts", 2: "n_runs is below 1 or a count is negative",
-              3: "the counts do not sum to Hs * Ws"}
-
-
-def rle_bits(counts, n_runs, size, check=False):
-    """mask_rle's inverse: the uncompressed run-length code back into bit words, on the device (fs_rle_bits; no autograd; unpinned, as
-    the code itself).  counts (B,cap) int32 on the device, as mask_rle / unwarp_instances / coco_to_instances make them; n_runs the
-    codes' lengths, int64 (B,) -- or a stats (B,6) int64 tensor, whose column 5 is read where it lies, without a copy; size = (Hs, Ws).
-    Entries of counts at or past n_runs are never read.  Every well-formed code decodes, canonical or not (zero-length runs anywhere).
-    Returns (bits (B,Hs,ceil(Ws/32)) int32 in mask_bits' layout, the bits at x >= Ws 0; info (B,4) int64 = (status, area, n_read,
-    total)): status 0 valid, 1 cut (n_runs > cap), 2 bad (n_runs < 1 or a negative count), 3 the counts do not sum to Hs * Ws (the
-    first that applies); area the set pixels of a valid code, else 0; an image whose status is not 0 gets all-zero words.  No host
-    read -- unless check=True, which reads info once and raises ValueError naming the first such image and its status in words."""
-    B, cap, Hs, Ws = _rle_args(counts, n_runs, size)
-    n_runs = n_runs.contiguous()
-    n_ptr, n_stride = (hip.ptr(n_runs) + 5 * 8, 6) if n_runs.dim() == 2 else (hip.ptr(n_runs), 1)
-    dev = counts.device
-    bits = torch.empty(B, Hs, (Ws + 31) // 32, device=dev, dtype=torch.int32)
-    info = torch.empty(B, 4, device=dev, dtype=torch.int64)
-    scratch = torch.empty(hip.query("fs_rle_bits_scratch_ints", B, cap), device=dev, dtype=torch.int32)
-    hip.call("fs_rle_bits", hip.ptr(counts.contiguous()), n_ptr, n_stride, hip.ptr(bits), hip.ptr(info), hip.ptr(scratch), B, Hs, Ws, cap)
-    if check:
-        for b, st in enumerate(info[:, 0].cpu().tolist()):
-            if st != 0:
-                raise ValueError(f"image {b}: {RLE_STATUS[st]} (status {st}; size {(Hs, Ws)}, capacity {cap})")
-    return bits, info
-
-
-def _rle_args(counts, n_runs, size):
-    """(B, cap, Hs, Ws) of rle_bits' arguments, or ValueError: the checks of the host, nothing launched."""
-    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32 or counts.dim() != 2 or counts.numel() == 0:
-        raise ValueError(f"counts must be a non-empty int32 (B, cap) tensor, got {getattr(counts, 'dtype', None)} {tuple(getattr(counts, 'shape', ()))}")
-    B, cap = int(counts.shape[0]), int(counts.shape[1])
-    if not isinstance(n_runs, torch.Tensor) or n_runs.dtype != torch.int64 or tuple(n_runs.shape) not in ((B,), (B, 6)) \
-            or n_runs.device != counts.device:
-        raise ValueError(f"n_runs must be an int64 (B,) = ({B},) tensor or a stats ({B}, 6) tensor on counts' device, got "
-                         f"{getattr(n_runs, 'dtype', None)} {tuple(getattr(n_runs, 'shape', ()))}")
-    if len(size) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 1 for v in size):
-        raise ValueError(f"size must be two integers >= 1 (Hs, Ws), got {size!r}")
-    return B, cap, int(size[0]), int(size[1])
-
-
-def rle_to_string(counts):
-    """The compressed string form of a run-length code, the one COCO / LVIS files carry (host; unpinned: restated from the published
-    definition, pycocotools' rleToString).  counts: a list of Python ints.  Count i is written as x = counts[i], less counts[i - 2]
-    for i > 2, in 5-bit groups, low group first: c = x & 31, x >>= 5 (arithmetic); another group follows iff x != -1 where c & 16 is
-    set, iff x != 0 otherwise; a group that is followed has bit 32 set; the character is chr(c + 48).  [0, 5] -> "05",
-    [10, 20, 30, 5] -> ":d0n0A"."""
-    out = []
-    counts = list(counts)
-    for i, v in enumerate(counts):
-        if isinstance(v, bool) or not isinstance(v, int):
-            raise ValueError(f"count {i} must be a Python int, got {v!r}")
-        x = v - counts[i - 2] if i > 2 else v
-        while True:
-            c = x & 31
-            x >>= 5
-            more = x != -1 if c & 16 else x != 0
-            out.append(chr((c | 32 if more else c) + 48))
-            if not more:
-                break
-    return "".join(out)
-
-
-RLE_STRING_GROUPS = 13                              # 65 bits: more than any int64 count or difference needs
-
-
-def rle_from_string(s):
-    """rle_to_string's inverse (host; unpinned: pycocotools' rleFrString restated): s a str or ASCII bytes -> the list of counts.  Per
-    count, (c & 31) << 5 k is accumulated over the groups k = 0, 1, ... while bit 32 of c = ord(ch) - 48 is set, the value is
-    sign-extended from bit 16 of the last group, and counts[i - 2] is added for i > 2.  ValueError, naming the position, for a character
-    outside chr(48) .. chr(111), a string that ends inside a count, or a count of more than 13 groups; an empty string is []."""
-    if isinstance(s, (bytes, bytearray)):
-        try:
-            s = bytes(s).decode("ascii")
-        except UnicodeDecodeError:
-            raise ValueError("the compressed code holds a byte outside ASCII") from None
-    if not isinstance(s, str):
-        raise ValueError(f"the compressed code must be a str or bytes, got {type(s).__name__}")
-    counts, p, n = [], 0, len(s)
-    while p < n:
-        x, k = 0, 0
-        while True:
-            if p >= n:
-                raise ValueError(f"the compressed code ends inside count {len(counts)} (position {p})")
-            c = ord(s[p]) - 48
-            if c < 0 or c > 63:
-                raise ValueError(f"character {s[p]!r} at position {p} is outside chr(48) .. chr(111)")
-            if k >= RLE_STRING_GROUPS:
-                raise ValueError(f"count {len(counts)} has more than {RLE_STRING_GROUPS} groups (position {p})")
-            x |= (c & 31) << (5 * k)
-            p, k = p + 1, k + 1
-            if not c & 32:
-                if c & 16:
-                    x -= 1 << (5 * k)
-                break
-        if len(counts) > 2:
-            x += counts[-2]
-        counts.append(x)
-    return counts
-
-
-def instances_to_coco(cat, stats, counts, seg_size, image_ids=None, conf=None, compressed=False):
-    """unwarp_instances' / predict_instances' tensors (on any device) as a list of COCO / LVIS result records, one per image:
-    {"image_id", "category_id", "bbox": [x, y, w, h], "area", "segmentation": {"size": [H, W], "counts": [...]}} with the uncompressed
-    run-length code pycocotools.mask.frPyObjects takes -- or, with compressed=True, "counts" as the compressed string result files carry
-    (rle_to_string; about a fifth of the list's size in JSON).  One device-to-host copy.  category_id is the class index cat[b]; image_id is
-    image_ids[b], or b.  With conf (B,3) -- unwarp_instances(score=True)'s / predict_instances(return_score=True)'s -- every record
-    also has "score": conf[b, 0] as a Python float, the key COCOeval and the LVIS evaluator rank by; without it no score is made up.
-    OverflowError, naming the image and the max_runs it needs, where a code was cut (n_runs > counts.shape[1]); ValueError, naming the
-    image, where a score is NaN.  coco_to_instances is the inverse."""
-    B, cap = int(counts.shape[0]), int(counts.shape[1])
-    if tuple(cat.shape) != (B,) or tuple(stats.shape) != (B, 6) or counts.dim() != 2:
-        raise ValueError(f"cat {tuple(cat.shape)}, stats {tuple(stats.shape)}, counts {tuple(counts.shape)} must be (B,), (B, 6), (B, max_runs)")
-    H, W = int(seg_size[0]), int(seg_size[1])
-    ids = list(range(B)) if image_ids is None else list(image_ids)
-    if len(ids) != B:
-        raise ValueError(f"{len(ids)} image ids for {B} images")
-    if conf is not None and (conf.dim() != 2 or conf.shape[0] != B or conf.shape[1] < 1):
-        raise ValueError(f"conf {tuple(conf.shape)} must be (B, 3) = ({B}, 3): (score, cls_prob, mask_prob) per image")
-    head = torch.cat([cat.to(torch.int64).reshape(B, 1), stats.to(torch.int64)], 1).contiguous()
-    parts = [head.view(torch.int32)]                                                   # the int64 columns as pairs of words
-    if conf is not None:
-        parts.append(conf[:, :1].to(torch.float32).contiguous().view(torch.int32))     # the score's fp32 word
-    n0 = sum(int(t.shape[1]) for t in parts)
-    host = torch.cat(parts + [counts.to(torch.int32)], 1).cpu()
-    head, code = host[:, :14].contiguous().view(torch.int64).tolist(), host[:, n0:]
-    scores = host[:, 14:15].contiguous().view(torch.float32).reshape(B).tolist() if conf is not None else None
-    out = []
-    for b in range(B):
-        c, area, x0, y0, bw, bh, n = head[b]
-        if n > cap:
-            raise OverflowError(f"image {ids[b]}: the run-length code has {n} counts and was cut at max_runs = {cap}; it needs max_runs >= {n}")
-        runs = code[b, :n].tolist()
-        rec = {"image_id": ids[b], "category_id": c, "bbox": [x0, y0, bw, bh], "area": area,
-               "segmentation": {"size": [H, W], "counts": rle_to_string(runs) if compressed else runs}}
-        if scores is not None:
-            if scores[b] != scores[b]:
-                raise ValueError(f"image {ids[b]}: the score is NaN (a NaN among the head's class logits)")
-            rec["score"] = scores[b]
-        out.append(rec)
-    return out
-
-
-INT32_MAX = 2 ** 31 - 1
-
-
-def coco_to_instances(records, device, max_runs=None):
-    """instances_to_coco's inverse: a list of COCO / LVIS result records, or of annotation records, as the tensors the library's own
-    operations take.  Every record has "image_id", "category_id" and "segmentation" = {"size": [H, W], "counts": ...}, counts a list of
-    ints (the uncompressed code) or the compressed string (rle_from_string); "score" in every record or in none.  Returns (image_ids, a
-    list; cat (n,) int64; n_runs (n,) int64; counts (n,cap) int32, zero behind each code; sizes (n,2) int64 = (H, W); scores (n,)
-    fp32, or None where no record has one), the tensors on `device`, made by ONE host-to-device copy.  cap defaults to the longest code;
-    with max_runs (an int >= 1) a longer code is stored cut while n_runs stays its true length, which rle_bits reports as status 1.
-    rle_bits(counts[sel], n_runs[sel], (H, W)) decodes the records of one size.  ValueError, naming the record, for a polygon
-    segmentation (rasterising polygons is not built), a missing key, a count outside int32, a malformed string, or scores in only some."""
-    records = list(records)
-    if not records:
-        raise ValueError("no records")
-    rows, ids, longest = [], [], 1
-    with_score = [isinstance(r, dict) and "score" in r for r in records]
-    if any(with_score) and not all(with_score):
-        raise ValueError(f"record {with_score.index(False)} has no score while others have: scores go with every record or with none")
-    for i, r in enumerate(records):
-        if not isinstance(r, dict):
-            raise ValueError(f"record {i} is no dict")
-        for key in ("image_id", "category_id", "segmentation"):
-            if key not in r:
-                raise ValueError(f"record {i}: the key {key!r} is missing")
-        seg = r["segmentation"]
-        if not isinstance(seg, dict):
-            raise ValueError(f"record {i} (image {r['image_id']!r}): the segmentation is a polygon list, not an RLE dict; polygons are not rasterised here")
-        for key in ("size", "counts"):
-            if key not in seg:
-                raise ValueError(f"record {i} (image {r['image_id']!r}): the segmentation's key {key!r} is missing")
-        size, code = seg["size"], seg["counts"]
-        if len(size) != 2 or any(isinstance(v, bool) or not isinstance(v, int) or v < 1 or v > INT32_MAX for v in size):
-            raise ValueError(f"record {i} (image {r['image_id']!r}): the size must be two integers >= 1, got {size!r}")
-        if isinstance(code, (str, bytes, bytearray)):
-            try:
-                code = rle_from_string(code)
-            except ValueError as e:
-                raise ValueError(f"record {i} (image {r['image_id']!r}): {e}") from None
-        code = list(code)
-        for j, v in enumerate(code):
-            if isinstance(v, bool) or not isinstance(v, int) or v < -INT32_MAX - 1 or v > INT32_MAX:
-                raise ValueError(f"record {i} (image {r['image_id']!r}): count {j} = {v!r} is no integer within int32")
-        c = r["category_id"]
-        if isinstance(c, bool) or not isinstance(c, int):
-            raise ValueError(f"record {i} (image {r['image_id']!r}): category_id must be an integer, got {c!r}")
-        ids.append(r["image_id"])
-        rows.append((c, len(code), int(size[0]), int(size[1]), code))
-        longest = max(longest, len(code))
-    cap = longest if max_runs is None else _max_runs(max_runs, 1)
-    n = len(rows)
-    head = torch.tensor([row[:4] for row in rows], dtype=torch.int64).reshape(n, 4)
-    score = torch.tensor([float(r["score"]) for r in records] if all(with_score) else [0.0] * n, dtype=torch.float32).reshape(n, 1)
-    code = torch.zeros(n, cap, dtype=torch.int32)
-    for i, row in enumerate(rows):
-        m = min(row[1], cap)
-        if m:
-            code[i, :m] = torch.tensor(row[4][:m], dtype=torch.int32)
-    dev = torch.cat([head.view(torch.int32), score.view(torch.int32), code], 1).to(device)            # the one copy
-    head = dev[:, :8].reshape(-1).view(torch.int64).reshape(n, 4)                                     # flat first: a row's stride is odd
-    scores = dev[:, 8].contiguous().view(torch.float32) if all(with_score) else None
-    return ids, head[:, 0].contiguous(), head[:, 1].contiguous(), dev[:, 9:].contiguous(), head[:, 2:4].contiguous(), scores
-
-
-POLY_SIDE_MAX = 16384                               # fs_poly_bits' cap on a side: coordinate products stay inside int32
-POLY_STATUS = {0: "valid", 1: "the image's ring or vertex offsets are out of range or decreasing"}
-
-
-def polygon_rings(polys):
-    """COCO / LVIS polygon lists as the three tables fs_poly_bits takes (host).  polys: a list with one entry per image, each entry a
-    polygon list [[x0, y0, x1, y1, ...], ...] as an annotation's "segmentation" carries it; an empty polygon list is allowed and is
-    the empty mask.  Returns CPU tensors (verts (V,2) int32 = (y, x); ring_off (R+1,) int32: ring r owns verts[ring_off[r] :
-    ring_off[r+1]]; img_ring (B+1,) int32: image b owns the rings img_ring[b] : img_ring[b+1]).  The coordinates are rounded half to
-    even on float64 (np.round, as the reference's b2_preprocess_lvis.py:282-297 does) and NOT clipped: poly_bits clamps them onto
-    the frame.  ValueError, naming the image and the ring, for an entry that is not a list of lists, a ring of odd or zero length, a
-    coordinate that is no number or not finite, and a rounded value outside int32."""
-    import numpy as np
-    if not isinstance(polys, (list, tuple)):
-        raise ValueError(f"polys must be a list with one polygon list per image, got {type(polys).__name__}")
-    rows, ring_off, img_ring = [], [0], [0]
-    for b, entry in enumerate(polys):
-        if not isinstance(entry, (list, tuple)) or any(not isinstance(ring, (list, tuple)) for ring in entry):
-            raise ValueError(f"image {b}: the segmentation must be a polygon list, a list of lists [x0, y0, x1, y1, ...]")
-        for j, ring in enumerate(entry):
-            if len(ring) == 0 or len(ring) % 2:
-                raise ValueError(f"image {b}, ring {j}: a ring is x, y pairs; it has {len(ring)} numbers")
-            for k, v in enumerate(ring):
-                if isinstance(v, bool) or not isinstance(v, (int, float)):
-                    raise ValueError(f"image {b}, ring {j}: coordinate {k} = {v!r} is no number")
-            try:
-                xy = np.round(np.array([float(v) for v in ring], dtype=np.float64))
-            except OverflowError:
-                raise ValueError(f"image {b}, ring {j}: a coordinate is outside float64") from None
-            if not np.isfinite(xy).all():
-                raise ValueError(f"image {b}, ring {j}: coordinate {int(np.flatnonzero(~np.isfinite(xy))[0])} is not finite")
-            if (xy < -INT32_MAX - 1).any() or (xy > INT32_MAX).any():
-                raise ValueError(f"image {b}, ring {j}: a rounded coordinate is outside int32")
-            rows.append(xy.reshape(-1, 2)[:, ::-1].astype(np.int32))                  # (x, y) pairs -> (y, x)
-            ring_off.append(ring_off[-1] + len(ring) // 2)
-        img_ring.append(len(ring_off) - 1)
-    if ring_off[-1] > INT32_MAX:
-        raise ValueError(f"{ring_off[-1]} vertices are more than int32 offsets hold")
-    verts = np.concatenate(rows, 0) if rows else np.zeros((0, 2), dtype=np.int32)
-    return (torch.from_numpy(np.ascontiguousarray(verts)), torch.tensor(ring_off, dtype=torch.int32), torch.tensor(img_ring, dtype=torch.int32))
-
-
-def _poly_args(verts, ring_off, img_ring, size):
-    """(B, R, V, Hs, Ws) of poly_bits' arguments, or ValueError: the checks of the host, nothing launched."""
-    for name, t, ok in (("verts", verts, lambda t: t.dim() == 2 and t.shape[1] == 2), ("ring_off", ring_off, lambda t: t.dim() == 1 and t.numel() >= 1),
-                        ("img_ring", img_ring, lambda t: t.dim() == 1 and t.numel() >= 2)):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or not ok(t):
-            raise ValueError(f"{name} must be an int32 tensor -- verts (V, 2), ring_off (R + 1,), img_ring (B + 1,), B >= 1 -- got "
-                             f"{getattr(t, 'dtype', None)} {tuple(getattr(t, 'shape', ()))}")
-    if not (verts.device == ring_off.device == img_ring.device):
-        raise ValueError("verts, ring_off and img_ring must be on one device")
-    if len(size) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 1 or int(v) > POLY_SIDE_MAX for v in size):
-        raise ValueError(f"size must be two integers 1 .. {POLY_SIDE_MAX} (Hs, Ws), got {size!r}")
-    return int(img_ring.numel()) - 1, int(ring_off.numel()) - 1, int(verts.shape[0]), int(size[0]), int(size[1])
-
-
-def poly_bits(verts, ring_off, img_ring, size, device=None, check=False):
-    """Polygon lists as bit words, on the device (fs_poly_bits; no autograd).  verts, ring_off, img_ring as polygon_rings makes them
-    (int32; (y, x) vertices rounded but not clipped), size = (Hs, Ws), each side at most 16384.  Tables on the host go to `device`
-    (default "cuda") in ONE host-to-device copy; tables already on a device are used where they lie.  UNPINNED -- the reference makes
-    its labels with np.round, a clip onto the frame and skimage.draw.polygon (b2_preprocess_lvis.py:282-297), which is not at hand, so
-    the rule is this library's restatement of what that is understood to give for integer vertices, not verified against it: a vertex
-    is clamped to the frame; a ring is the closed chain of a polygon's vertices; it sets pixel (y, x) iff the pixel lies on one of its
-    edges (end points included) or the even-odd crossing number is odd (edges oriented so that y0 < y1, y0 <= y < y1, counted where
-    (x - x0)(y1 - y0) < (y - y0)(x1 - x0)); an image's mask is the OR of its rings, so overlapping polygons do not cancel while a
-    self-intersecting ring follows even-odd.  It is not pycocotools' frPoly, which traces a 5x upsampled outline and differs along the
-    rim.  Returns (bits (B,Hs,ceil(Ws/32)) int32 in mask_bits' layout, the bits at x >= Ws 0; info (B,4) int64 = (status, area,
-    n_rings, n_vertices)): status 0 valid, 1 the image's offsets are out of range or decreasing (all-zero words, area 0); an image
-    without rings is the empty mask.  No host read -- unless check=True, which reads info once and raises ValueError naming the first
-    image whose status is not 0.  mask_rle(bits, Ws) gives the label evaluate_instances(seg_label=(counts, stats)) takes."""
-    B, R, V, Hs, Ws = _poly_args(verts, ring_off, img_ring, size)
-    if verts.device.type == "cpu":
-        dev = torch.device("cuda" if device is None else device)
-        keep = torch.cat([img_ring, ring_off, verts.reshape(-1)]).to(dev)              # the one copy
-        p_img = hip.ptr(keep)
-        p_ring, p_verts = p_img + 4 * (B + 1), p_img + 4 * (B + 1 + R + 1)             # the buffer's end where V = 0: never read
-    else:
-        dev = verts.device
-        if device is not None and torch.device(device) != dev:
-            raise ValueError(f"the tables are on {dev}, not on {device}")
-        keep = (verts.contiguous(), ring_off.contiguous(), img_ring.contiguous())
-        p_ring, p_img = hip.ptr(keep[1]), hip.ptr(keep[2])
-        p_verts = hip.ptr(keep[0]) if V else p_ring
-    bits = torch.empty(B, Hs, (Ws + 31) // 32, device=dev, dtype=torch.int32)
-    info = torch.empty(B, 4, device=dev, dtype=torch.int64)
-    scratch = torch.empty(max(1, hip.query("fs_poly_bits_scratch_ints", B, Hs, Ws)), device=dev, dtype=torch.int32)
-    hip.call("fs_poly_bits", p_verts, p_ring, p_img, hip.ptr(bits), hip.ptr(info), hip.ptr(scratch), B, R, V, Hs, Ws)
-    del keep                                                                           # the tables, held until the launch is queued
-    if check:
-        for b, st in enumerate(info[:, 0].cpu().tolist()):
-            if st != 0:
-                raise ValueError(f"image {b}: {POLY_STATUS[st]} (status {st}; {R} rings, {V} vertices)")
-    return bits, info
-
-
-def coco_masks(records, size, device):
-    """COCO / LVIS records of ONE size as bit words, whichever way each carries its mask: "segmentation" an RLE dict (counts a list or
-    the compressed string) or a polygon list.  size = (H, W); records as coco_to_instances takes them ("image_id", "category_id",
-    "segmentation"; "score" in every record or in none).  Returns (image_ids, a list; cat (n,) int64; bits (n,H,ceil(W/32)) int32;
-    info (n,2) int64 = (status, area); scores (n,) fp32 or None), the rows in record order.  RLE rows go through coco_to_instances and
-    rle_bits, polygon rows through polygon_rings and poly_bits (unpinned rules both; see there): each kind is handed all n rows, the
-    other kind's rows as empty masks, and the two results are ORed, so the order needs no index on the device.  At most two
-    host-to-device copies (one a kind) and no host read: a code or offsets that are not valid give an empty mask and a status that is
-    not 0 (rle_bits' for an RLE row, poly_bits' for a polygon row).  ValueError as coco_to_instances and polygon_rings raise it (the
-    latter's "image i" is record i), and for an RLE record whose size is not `size`."""
-    records = list(records)
-    if len(size) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 1 for v in size):
-        raise ValueError(f"size must be two integers >= 1 (H, W), got {size!r}")
-    H, W = int(size[0]), int(size[1])
-    empty = {"size": [H, W], "counts": [H * W]}
-    as_rle, polys, n_poly = [], [], 0
-    for i, r in enumerate(records):
-        seg = r.get("segmentation") if isinstance(r, dict) else None
-        if isinstance(seg, (list, tuple)):
-            as_rle.append(dict(r, segmentation=empty))
-            polys.append(seg)
-            n_poly += 1
-        else:
-            if isinstance(seg, dict) and "size" in seg and list(seg["size"]) != [H, W]:
-                raise ValueError(f"record {i} (image {r.get('image_id')!r}): the code's size {seg['size']!r} is not {[H, W]}")
-            as_rle.append(r)
-            polys.append([])
-    ids, cat, n_runs, counts, _sizes, scores = coco_to_instances(as_rle, device)
-    bits = info = None
-    if n_poly < len(records):
-        bits, info4 = rle_bits(counts, n_runs, (H, W))
-        info = info4[:, :2]
-    if n_poly:
-        pbits, pinfo = poly_bits(*polygon_rings(polys), (H, W), device=device)
-        bits, info = (pbits, pinfo[:, :2]) if bits is None else (bits | pbits, info + pinfo[:, :2])
-    return ids, cat, bits, info.contiguous(), scores
-
-
-def _candidate_args(cbits, cand_off, Ws, cand_cat):
-    """(N, Hs, P, B) of mask_candidates' tables, or ValueError: the checks of the host, nothing launched."""
-    if not isinstance(cbits, torch.Tensor) or cbits.dtype != torch.int32 or cbits.dim() != 3 or Ws is None or isinstance(Ws, bool) \
-            or int(Ws) != Ws or int(Ws) < 1 or cbits.shape[2] != (int(Ws) + 31) // 32 or cbits.shape[1] < 1:
-        raise ValueError(f"cbits must be int32 bit words (N, Hs, ceil(Ws / 32)) with Hs >= 1 and Ws given, got "
-                         f"{getattr(cbits, 'dtype', None)} {tuple(getattr(cbits, 'shape', ()))} and Ws = {Ws!r}")
-    N, Hs, P = (int(v) for v in cbits.shape)
-    if not isinstance(cand_off, torch.Tensor) or cand_off.dtype != torch.int32 or cand_off.dim() != 1 or cand_off.numel() < 2:
-        raise ValueError(f"cand_off must be an int32 tensor (B + 1,), B >= 1, got {getattr(cand_off, 'dtype', None)} "
-                         f"{tuple(getattr(cand_off, 'shape', ()))}")
-    if cand_cat is not None and (not isinstance(cand_cat, torch.Tensor) or cand_cat.dtype != torch.int64 or tuple(cand_cat.shape) != (N,)):
-        raise ValueError(f"cand_cat must be int64 ({N},), got {getattr(cand_cat, 'dtype', None)} {tuple(getattr(cand_cat, 'shape', ()))}")
-    for name, t in (("cand_off", cand_off), ("cand_cat", cand_cat)):
-        if t is not None and t.device != cbits.device:
-            raise ValueError(f"{name} is on {t.device}, cbits on {cbits.device}")
-    if Hs > POLY_SIDE_MAX or int(Ws) > POLY_SIDE_MAX:
-        raise ValueError(f"a side of {(Hs, int(Ws))} is above {POLY_SIDE_MAX}")
-    return N, Hs, P, int(cand_off.numel()) - 1
-
-
-def mask_candidates(cbits, cand_off, focus, Ws, pred=None, cand_cat=None, snap_px=None):
-    """Of every image's annotated instances, the one under the gaze, on the device and on bit words (fs_mask_candidates; no autograd).
-    UNPINNED: the reference builds its labels by choosing an annotation and putting the gaze inside it
-    (b2_preprocess_lvis.py:258-333); this is the inverse of that step and a definition of this library's.  cbits (N,Hs,ceil(Ws/32))
-    int32, the candidates' masks in mask_bits' layout (N = 0 allowed; the bits at x >= Ws are not read); cand_off (B+1,) int32: image
-    b owns the rows cand_off[b] : cand_off[b+1]; focus (B,2) normalised (row, col), turned into a gaze pixel as mask_component does;
-    pred (B,Hs,ceil(Ws/32)) int32 or None, a prediction's bit words per image; cand_cat (N,) int64 or None; snap_px None (any
-    distance) or a finite number of pixels >= 0, snap2 = floor(snap_px ** 2) (as mask_component).  Returns (gbits, sel, cand):
-
-    cand (N,6) int64 = (b, area, inter, d2, near_y, near_x): the row's image, its set pixels, |c & pred[b]| (0 without pred), and its
-    set pixel nearest to the gaze pixel with the squared distance (ties to the smaller row-major index; -1, -1, -1 for an empty row).
-    sel (B,8) int64 = (index, cls, d2, area, inter, n_hit, best, status).  index: the SELECTED row -- among the image's rows with area >
-    0 and d2 <= snap2 the least (d2, area, row): of several instances that contain the gaze pixel the smallest (a cup on a table gives
-    the cup), of none the nearest within the snap distance, ties to the smaller area, then row -- or -1; cls = cand_cat[index] (-1
-    for none or without cand_cat); d2, area, inter the selected row's (-1, 0, 0); n_hit how many of the image's rows contain the gaze
-    pixel; best: among rows with inter > 0 the one of the greatest IoU with pred[b], compared exactly in integers, ties to the smaller
-    area, then row, or -1.  gbits (B,Hs,ceil(Ws/32)) int32 = the selected row's words with the bits at x >= Ws cleared, all 0 where
-    none is selected.  status 1 in every image where cand_off is not 0 = cand_off[0] <= ... <= cand_off[B] = N: then nothing is
-    selected anywhere and every cand row is (-1, area, 0, -1, -1, -1).  No host read; the same bits in every run."""
-    _conn, snap2 = _component_args(8, snap_px)
-    N, Hs, P, B = _candidate_args(cbits, cand_off, Ws, cand_cat)
-    Ws, dev = int(Ws), cbits.device
-    f = _focus_arg(focus, B, dev)
-    if pred is not None and (not isinstance(pred, torch.Tensor) or pred.dtype != torch.int32 or tuple(pred.shape) != (B, Hs, P) or pred.device != dev):
-        raise ValueError(f"pred must be int32 bit words {(B, Hs, P)} on {dev}, got {getattr(pred, 'dtype', None)} {tuple(getattr(pred, 'shape', ()))}")
-    gbits = torch.empty(B, Hs, P, device=dev, dtype=torch.int32)
-    sel = torch.empty(B, 8, device=dev, dtype=torch.int64)
-    cand = torch.empty(N, 6, device=dev, dtype=torch.int64)
-    scratch = torch.empty(max(1, hip.query("fs_mask_candidates_scratch_ints", B, N, Hs, Ws)), device=dev, dtype=torch.int32)
-    hip.call("fs_mask_candidates", hip.ptr(cbits.contiguous()) if N else None, hip.ptr(cand_off.contiguous()),
-             None if cand_cat is None or N == 0 else hip.ptr(cand_cat.contiguous()), hip.ptr(f),
-             None if pred is None else hip.ptr(pred.contiguous()), hip.ptr(cand) if N else None, hip.ptr(sel), hip.ptr(gbits),
-             hip.ptr(scratch), B, N, Hs, Ws, snap2)
-    return gbits, sel, cand
-
-
-def coco_candidates(records, size, device, image_ids):
-    """COCO / LVIS annotation records of ONE size, several an image, as mask_candidates' arguments.  records as coco_masks takes them
-    (RLE dicts or polygon lists, mixed); size = (H, W); image_ids the images in the order the batch has them.  The records are grouped
-    stably by "image_id" in the order of image_ids -- an id without records gets an empty range -- and rasterised through coco_masks
-    with its copies (at most two) plus one for the offsets.  Returns (cbits (N,H,ceil(W/32)) int32; cand_off (B+1,) int32; cand_cat
-    (N,) int64; info (N,2) int64 = coco_masks' (status, area); rows, a list: rows[i] is the index into `records` of candidate row i,
-    which maps mask_candidates' sel[:, 0] back to an annotation: records[rows[index]]["id"]).  "iscrowd" is not interpreted: a
-    crowd record is a candidate like any other.  ValueError for a record whose image is not in image_ids, an id named twice, and as
-    coco_masks."""
-    records, image_ids = list(records), list(image_ids)
-    if not image_ids:
-        raise ValueError("no image_ids")
-    place = {}
-    for b, image_id in enumerate(image_ids):
-        if image_id in place:
-            raise ValueError(f"image_ids names {image_id!r} twice")
-        place[image_id] = b
-    per = [[] for _ in image_ids]
-    for i, r in enumerate(records):
-        if not isinstance(r, dict) or "image_id" not in r:
-            raise ValueError(f"record {i}: the key 'image_id' is missing")
-        if r["image_id"] not in place:
-            raise ValueError(f"record {i}: image {r['image_id']!r} is not among image_ids")
-        per[place[r["image_id"]]].append(i)
-    rows = [i for group in per for i in group]
-    off = [0]
-    for group in per:
-        off.append(off[-1] + len(group))
-    if len(size) != 2 or any(isinstance(v, bool) or int(v) != v or int(v) < 1 for v in size):
-        raise ValueError(f"size must be two integers >= 1 (H, W), got {size!r}")
-    dev = torch.device(device)
-    H, W = int(size[0]), int(size[1])
-    cand_off = torch.tensor(off, dtype=torch.int32).to(dev)
-    if not rows:
-        return (torch.empty(0, H, (W + 31) // 32, device=dev, dtype=torch.int32), cand_off, torch.empty(0, device=dev, dtype=torch.int64),
-                torch.empty(0, 2, device=dev, dtype=torch.int64), rows)
-    _ids, cat, cbits, info, _scores = coco_masks([{k: v for k, v in records[i].items() if k != "score"} for i in rows], size, dev)
-    return cbits, cand_off, cat, info, rows
-
-
-GATE_TILES = (8, 16, 32, 64)
-GATE_CODES = {0: "REUSE", 1: "RUN_INIT", 2: "HOLD_SACCADE", 3: "RUN_SCENE", 4: "RUN_ROI", 5: "RUN_GAZE", 6: "RUN_AGE", 7: "RUN_FORCED"}
-GATE_RUNS = (1, 3, 4, 5, 6, 7)                      # the codes after which the network runs
-
-
-def _gate_tile(T):
-    if isinstance(T, bool) or int(T) != T or int(T) not in GATE_TILES:
-        raise ValueError(f"the tile side must be one of {GATE_TILES}, got {T!r}")
-    return int(T)
-
-
-def _gate_tiles(dtype, img, key, tile, out):
-    T = _gate_tile(tile)
-    what = "fp32" if dtype == torch.float32 else "uint8"
-    if not isinstance(img, _FRAME_TYPES) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
-        raise ValueError(f"img must be a non-empty {what} (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
-    if key.dtype != torch.uint8 or key.shape != img.shape:
-        raise ValueError(f"key must be uint8 {tuple(img.shape)}, got {key.dtype} {tuple(key.shape)}")
-    B, _, H, W = (int(v) for v in img.shape)
-    suffix, strides = _frame_route(img)
-    shape = (B, (H + T - 1) // T, (W + T - 1) // T)
-    if out is None:
-        out = torch.empty(shape, device=img.device, dtype=torch.int32)
-    elif out.dtype != torch.int32 or tuple(out.shape) != shape:
-        raise ValueError(f"out must be int32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    hip.call("fs_gate_tiles" + suffix, *_frame_args(img, strides), hip.ptr(key), hip.ptr(out), B, H, W, T)
-    return out
-
-
-def gate_tiles(img, key, tile=32, out=None):
-    """How much every tile of new frames differs from the 8-bit key frames (fs_gate_tiles; no autograd; unpinned: the reference has
-    no counterpart).  img (B,3,H,W) fp32, key (B,3,H,W) uint8 = q of the frames the records were made from, q(v) = rint(clamp(v, 0, 1) *
-    255) in fp32, NaN -> 0.  Returns sad (B,th,tw) int32, th = ceil(H / tile), tw = ceil(W / tile): the sum of |q(img) - key| over the
-    three channels and the tile's pixels (the last tiles are ragged).  out: a (B,th,tw) int32 tensor to write into."""
-    return _gate_tiles(torch.float32, img, key, tile, out)
-
-
-def gate_tiles_u8(img, key, tile=32, out=None):
-    """gate_tiles for frames of bytes (fs_gate_tiles_u8): img (B,3,H,W) uint8, the pixel value byte / 255, whose code q is the byte.  sad
-    is the sum of |img - key|, equal to gate_tiles(img.float() / 255, key, tile); 6 bytes read a pixel instead of 15.  img is contiguous,
-    or an hwc view of interleaved bytes (byte_frame_layout; fs_gate_tiles_hwc), read where it lies; ValueError for any other layout."""
-    return _gate_tiles(torch.uint8, img, key, tile, out)
-
-
-def gate_decide(sad, gstate, focus, stats, bits, frame_size, tile=32, level=8, scene_tiles=0, roi_tiles=0, margin=16,
-                saccade2=2 ** 62, fixation2=0, max_age=0, inside_on=True, force=None, out=None):
-    """The gate's decision per viewer (fs_gate_decide; no autograd; unpinned).  sad (B,th,tw) int32 as gate_tiles returns it; gstate
-    (B,6) int64 = (valid, gy_key, gx_key, gy_prev, gx_prev, age), gazes in 1/16-pixel units; focus (B,2) fp32 normalised (row, col);
-    stats (B,6) int64 and bits (B,H,ceil(W/32)) int32 the records' (mask_rle, mask_bits); force (B,) int32 or None; frame_size = (H, W).
-    saccade2 and fixation2 are squared distances in 1/16-pixel units, floor((px * 16) ** 2).  Returns gate (B,8) int64 = (code,
-    n_changed, n_roi_changed, sad_total, d2_key, d2_prev, inside_bit, age + 1); the codes are GATE_CODES, the first rule that holds in
-    the order 7, 1, 2, 3, 4, 5, 6, 0 (include/fovealseg.h).  Nothing but gate is written."""
-    T = _gate_tile(tile)
-    H, W = int(frame_size[0]), int(frame_size[1])
-    B = int(sad.shape[0])
-    if sad.dtype != torch.int32 or tuple(sad.shape) != (B, (H + T - 1) // T, (W + T - 1) // T):
-        raise ValueError(f"sad must be int32 (B, ceil(H/T), ceil(W/T)) for H, W, T = {H}, {W}, {T}, got {sad.dtype} {tuple(sad.shape)}")
-    if gstate.dtype != torch.int64 or tuple(gstate.shape) != (B, 6) or stats.dtype != torch.int64 or tuple(stats.shape) != (B, 6):
-        raise ValueError(f"gstate and stats must be int64 ({B}, 6), got {tuple(gstate.shape)} and {tuple(stats.shape)}")
-    if focus.dtype != torch.float32 or tuple(focus.shape) != (B, 2):
-        raise ValueError(f"focus must be fp32 ({B}, 2), got {focus.dtype} {tuple(focus.shape)}")
-    if bits.dtype != torch.int32 or tuple(bits.shape) != (B, H, (W + 31) // 32):
-        raise ValueError(f"bits must be int32 {(B, H, (W + 31) // 32)}, got {bits.dtype} {tuple(bits.shape)}")
-    if force is not None and (force.dtype != torch.int32 or tuple(force.shape) != (B,)):
-        raise ValueError(f"force must be int32 ({B},), got {force.dtype} {tuple(force.shape)}")
-    if isinstance(level, bool) or int(level) != level or not 0 <= int(level) <= 254:
-        raise ValueError(f"level must be an integer 0 .. 254, got {level!r}")
-    if int(margin) < 0:
-        raise ValueError(f"margin must be >= 0, got {margin!r}")
-    if out is None:
-        out = torch.empty(B, 8, device=sad.device, dtype=torch.int64)
-    elif out.dtype != torch.int64 or tuple(out.shape) != (B, 8):
-        raise ValueError(f"out must be int64 ({B}, 8), got {out.dtype} {tuple(out.shape)}")
-    hip.call("fs_gate_decide", hip.ptr(sad), hip.ptr(gstate), hip.ptr(focus), hip.ptr(stats), hip.ptr(bits), hip.ptr(force), hip.ptr(out),
-             B, H, W, T, int(level), int(scene_tiles), int(roi_tiles), int(margin), int(saccade2), int(fixation2), int(max_age),
-             1 if inside_on else 0)
-    return out
-
-
-def _gate_commit(dtype, img, idx, key, gstate, focus, src, dst):
-    what = "fp32" if dtype == torch.float32 else "uint8"
-    if (not isinstance(img, _FRAME_TYPES) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype
-            or key.dtype != torch.uint8 or key.shape != img.shape):
-        raise ValueError(f"img must be a non-empty {what} (B,3,H,W) and key uint8 of its shape, got {getattr(img, 'dtype', None)} "
-                         f"{tuple(getattr(img, 'shape', ()))} and {tuple(key.shape)}")
-    B, _, H, W = (int(v) for v in img.shape)
-    suffix, strides = _frame_route(img)
-    n = 0 if idx is None else int(idx.shape[0])
-    if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 1 or n > B):
-        raise ValueError(f"idx must be int32 (n,) with n <= {B}, got {idx.dtype} {tuple(idx.shape)}")
-    if gstate.dtype != torch.int64 or tuple(gstate.shape) != (B, 6) or focus.dtype != torch.float32 or tuple(focus.shape) != (B, 2):
-        raise ValueError(f"gstate must be int64 ({B}, 6) and focus fp32 ({B}, 2), got {tuple(gstate.shape)} and {tuple(focus.shape)}")
-    if len(src) != len(dst) or len(dst) not in (4, 5):
-        raise ValueError("src and dst must both be (cat, stats, counts, bits) or (cat, stats, counts, bits, conf)")
-    cap = int(dst[2].shape[1])
-    tails = ((), (6,), (cap,), (H, (W + 31) // 32), (3,))
-    dtypes = (torch.int64, torch.int64, torch.int32, torch.int32, torch.float32)
-    for s, d, tail, dt in zip(src, dst, tails, dtypes):
-        if d.dtype != dt or tuple(d.shape) != (B,) + tail:
-            raise ValueError(f"a dst record tensor must be {dt} {(B,) + tail}, got {d.dtype} {tuple(d.shape)}")
-        if s is not d and n > 0 and (s.dtype != dt or tuple(s.shape) != (n,) + tail):
-            raise ValueError(f"a src record tensor must be {dt} {(n,) + tail}, got {s.dtype} {tuple(s.shape)}")
-    sp = [hip.ptr(s) for s in src] + [None] * (5 - len(src))
-    dp = [hip.ptr(d) for d in dst] + [None] * (5 - len(dst))
-    hip.call("fs_gate_commit" + suffix, *_frame_args(img, strides), hip.ptr(idx), n, hip.ptr(key), hip.ptr(gstate), hip.ptr(focus), *sp, *dp,
-             B, H, W, cap)
-
-
-def gate_commit(img, idx, key, gstate, focus, src, dst):
-    """What a step leaves behind (fs_gate_commit; no autograd; unpinned), in place.  idx (n,) int32 ascending, or None for n = 0: the
-    viewers whose record was made anew from img (B,3,H,W) fp32.  src = (cat, stats, counts, bits[, conf]) with n rows, dst the same
-    with B rows: row j moves to row idx[j]; a pair that is one tensor is already in place.  For the viewers of idx key (B,3,H,W) uint8
-    <- q(img), g_key <- g, age <- 0, valid <- 1 in gstate (B,6) int64; for every viewer g_prev <- g; any other viewer's age grows by
-    one.  With n = 0 src is not read (pass dst)."""
-    _gate_commit(torch.float32, img, idx, key, gstate, focus, src, dst)
-
-
-def gate_commit_u8(img, idx, key, gstate, focus, src, dst):
-    """gate_commit for frames of bytes (fs_gate_commit_u8): img (B,3,H,W) uint8; for the viewers of idx key <- img, a copy.  Everything
-    else as gate_commit, and equal to it on img.float() / 255.  img is contiguous, or an hwc view of interleaved bytes (byte_frame_layout;
-    fs_gate_commit_hwc: the key takes the de-interleaved frame and stays planar); ValueError for any other layout."""
-    _gate_commit(torch.uint8, img, idx, key, gstate, focus, src, dst)
-
-
-MOTION_MAX_PX = 255                                 # fs_profile_shift's largest search range
-
-
-def _index_or_none(v):
-    """v as an int where it is an integer of any integer type (no bool, no float), else None."""
-    if isinstance(v, bool):
-        return None
-    try:
-        return operator.index(v)
-    except TypeError:
-        return None
-
-
-def _motion_px(motion_px, H, W):
-    """The search range R of the motion estimate: an integer 1 .. 255 with 4 R < min(H, W)."""
-    R = _index_or_none(motion_px)
-    if R is None or not 1 <= R <= MOTION_MAX_PX or 4 * R >= min(int(H), int(W)):
-        raise ValueError(f"motion_px must be an integer 1 .. {MOTION_MAX_PX} with 4 * motion_px < min(H, W) = {min(int(H), int(W))}, got {motion_px!r}")
-    if 8 * max(int(H), int(W)) + 8 * (2 * R + 1) > 65536:
-        raise ValueError(f"a side of {max(int(H), int(W))} pixels with motion_px = {R} is beyond the estimate's 64 KiB of LDS")
-    return R
-
-
-def _motion_gain(gain):
-    g = _index_or_none(gain)
-    if g is None or not 0 <= g <= 8:
-        raise ValueError(f"motion_gain must be an integer 0 .. 8, got {gain!r}")
-    return g
-
-
-def _profile_sizes(B, H, W):
-    if 765 * max(H, W) >= 2 ** 31 or H * W >= 2 ** 31:
-        raise ValueError(f"a frame of {H} x {W} pixels is beyond int32 profiles")
-    return (B, H + W)
-
-
-# the profile pass's entry point by _frame_route's suffix: fs_frame_profiles + suffix ("_nv12" among them), but a planar frame of bytes is a key
-_PROFILE_ENTRY = {"": "fs_frame_profiles", "_u8": "fs_key_profiles", "_hwc": "fs_frame_profiles_hwc"}
-
-
-def _profiles(src, dtype, out):
-    if not isinstance(src, _FRAME_TYPES) or src.dim() != 4 or src.shape[1] != 3 or src.numel() == 0 or src.dtype != dtype:
-        raise ValueError(f"the frames must be a non-empty {dtype} (B,3,H,W), got {getattr(src, 'dtype', None)} {tuple(getattr(src, 'shape', ()))}")
-    B, _, H, W = (int(v) for v in src.shape)
-    suffix, strides = _frame_route(src, "the frames")
-    shape = _profile_sizes(B, H, W)
-    if out is None:
-        out = torch.empty(shape, device=src.device, dtype=torch.int32)
-    elif out.dtype != torch.int32 or tuple(out.shape) != shape:
-        raise ValueError(f"out must be int32 {shape}, got {out.dtype} {tuple(out.shape)}")
-    hip.call(_PROFILE_ENTRY.get(suffix, "fs_frame_profiles" + suffix), *_frame_args(src, strides), hip.ptr(out), B, H, W)
-    return out
-
-
-def frame_profiles(img, out=None):
-    """The integral projections of frames (fs_frame_profiles; no autograd; unpinned: the reference has no counterpart).  img (B,3,H,W)
-    fp32.  Returns prof (B, H + W) int32: prof[b, :H] = the row sums and prof[b, H:] = the column sums of the luma code L = q_r + q_g +
-    q_b, q the gate's pixel code (gate_tiles).  out: a (B, H + W) int32 tensor to write into."""
-    return _profiles(img, torch.float32, out)
-
-
-def key_profiles(key, out=None):
-    """frame_profiles of 8-bit key frames (fs_key_profiles): key (B,3,H,W) uint8.  The profiles of a frame and of the key gate_commit
-    made from it are equal.  A frame of bytes may also be an hwc view of interleaved bytes (byte_frame_layout; fs_frame_profiles_hwc), read
-    where it lies; ValueError for any other non-contiguous layout."""
-    return _profiles(key, torch.uint8, out)
-
-
-def profile_shift(prof, prof_key, gstate, frame_size, motion_px, motion_gain=6, out=None):
-    """The integer translation of every viewer against its key frame (fs_profile_shift; no autograd; unpinned).  prof, prof_key (B, H +
-    W) int32 as frame_profiles / key_profiles make them; gstate (B,6) int64 the gate's; frame_size = (H, W); motion_px = R, the search
-    range.  Per axis cost(s) = sum_{i=R}^{n-1-R} |P[i] - K[i - s]|; the least cost wins, ties to the smaller |s|, then to the negative s,
-    and the shift is taken only if cost(s) * 8 <= cost(0) * motion_gain.  Returns shift (B,4) int64 = (dy, dx, cost_best, cost_zero),
-    all 0 for a viewer without a record."""
-    H, W = int(frame_size[0]), int(frame_size[1])
-    R, gain = _motion_px(motion_px, H, W), _motion_gain(motion_gain)
-    if not isinstance(prof, torch.Tensor) or prof.dim() != 2 or prof.dtype != torch.int32 or prof.shape[1] != H + W or prof.shape[0] < 1:
-        raise ValueError(f"prof must be int32 (B, H + W) = (B, {H + W}), got {getattr(prof, 'dtype', None)} {tuple(getattr(prof, 'shape', ()))}")
-    B = int(prof.shape[0])
-    _profile_sizes(B, H, W)
-    if prof_key.dtype != torch.int32 or prof_key.shape != prof.shape:
-        raise ValueError(f"prof_key must be int32 {tuple(prof.shape)}, got {prof_key.dtype} {tuple(prof_key.shape)}")
-    if gstate.dtype != torch.int64 or tuple(gstate.shape) != (B, 6):
-        raise ValueError(f"gstate must be int64 ({B}, 6), got {gstate.dtype} {tuple(gstate.shape)}")
-    if out is None:
-        out = torch.empty(B, 4, device=prof.device, dtype=torch.int64)
-    elif out.dtype != torch.int64 or tuple(out.shape) != (B, 4):
-        raise ValueError(f"out must be int64 ({B}, 4), got {out.dtype} {tuple(out.shape)}")
-    hip.call("fs_profile_shift", hip.ptr(prof), hip.ptr(prof_key), hip.ptr(gstate), hip.ptr(out), B, H, W, R, gain)
-    return out
-
-
-def state_shift_scratch(B, H, W, cap, device):
-    """The scratch tensor state_shift wants for these sizes (fs_state_shift_scratch_ints ints)."""
-    return torch.empty(hip.query("fs_state_shift_scratch_ints", int(B), int(H), int(W), int(cap)), device=device, dtype=torch.int32)
-
-
-def _state_shift(dtype, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch):
-    if not isinstance(img, _FRAME_TYPES) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype != dtype:
-        raise ValueError(f"img must be a non-empty {'fp32' if dtype == torch.float32 else 'uint8'} (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
-    B, _, H, W = (int(v) for v in img.shape)
-    suffix, strides = _frame_route(img)
-    _profile_sizes(B, H, W)
-    P = (W + 31) // 32
-    for name, k in (("key", key), ("key2", key2)):
-        if k.dtype != torch.uint8 or k.shape != img.shape:
-            raise ValueError(f"{name} must be uint8 {tuple(img.shape)}, got {k.dtype} {tuple(k.shape)}")
-    for name, w in (("bits", bits), ("bits2", bits2)):
-        if w.dtype != torch.int32 or tuple(w.shape) != (B, H, P):
-            raise ValueError(f"{name} must be int32 {(B, H, P)}, got {w.dtype} {tuple(w.shape)}")
-    if key2.data_ptr() == key.data_ptr() or bits2.data_ptr() == bits.data_ptr():
-        raise ValueError("key2 and bits2 must be buffers of their own: the move does not read what it writes")
-    if counts.dtype != torch.int32 or counts.dim() != 2 or counts.shape[0] != B or counts.shape[1] < 1:
-        raise ValueError(f"counts must be int32 ({B}, cap), got {counts.dtype} {tuple(counts.shape)}")
-    cap = int(counts.shape[1])
-    for name, t, tail in (("shift", shift, (4,)), ("gstate", gstate, (6,)), ("stats", stats, (6,)), ("mstate", mstate, (4,))):
-        if t.dtype != torch.int64 or tuple(t.shape) != (B,) + tail:
-            raise ValueError(f"{name} must be int64 {(B,) + tail}, got {t.dtype} {tuple(t.shape)}")
-    if prof_key.dtype != torch.int32 or tuple(prof_key.shape) != (B, H + W):
-        raise ValueError(f"prof_key must be int32 {(B, H + W)}, got {prof_key.dtype} {tuple(prof_key.shape)}")
-    if motion is None:
-        motion = torch.empty(B, 6, device=img.device, dtype=torch.int64)
-    elif motion.dtype != torch.int64 or tuple(motion.shape) != (B, 6):
-        raise ValueError(f"motion must be int64 ({B}, 6), got {motion.dtype} {tuple(motion.shape)}")
-    need = hip.query("fs_state_shift_scratch_ints", B, H, W, cap)
-    if scratch is None:
-        scratch = torch.empty(need, device=img.device, dtype=torch.int32)
-    elif scratch.dtype != torch.int32 or scratch.dim() != 1 or scratch.numel() < need:
-        raise ValueError(f"scratch must be int32 with at least {need} entries, got {scratch.dtype} {tuple(scratch.shape)}")
-    hip.call("fs_state_shift" + suffix, *_frame_args(img, strides), hip.ptr(shift), hip.ptr(key), hip.ptr(key2), hip.ptr(bits), hip.ptr(bits2), hip.ptr(gstate),
-             hip.ptr(stats), hip.ptr(counts), hip.ptr(prof_key), hip.ptr(mstate), hip.ptr(motion), hip.ptr(scratch), B, H, W, cap)
-    return motion
-
-
-def state_shift(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion=None, scratch=None):
-    """Move the state of every viewer whose shift is not (0, 0), in place (fs_state_shift; no autograd; unpinned).  img (B,3,H,W) fp32
-    the new frames; shift (B,4) int64 as profile_shift returns it; key (B,3,H,W) uint8 and bits (B,H,ceil(W/32)) int32 are moved by (dy,
-    dx) -- the key's uncovered border is filled with q(img), the mask's with 0 -- through the spare buffers key2 and bits2 of the same
-    shapes, whose contents afterwards are unspecified; the four gaze coordinates of gstate (B,6) int64 move by 16 * d, clamped; stats
-    (B,6) int64 and counts (B,cap) int32 become mask_rle's of the moved bits; prof_key (B, H + W) int32 becomes key_profiles of the
-    moved key; mstate (B,4) int64 = (dy_total, dx_total, moves, path) grows.  A still viewer's rows are not written.  Returns motion
-    (B,6) int64 = (dy, dx, cost_best, cost_zero, dy_total, dx_total), written for every viewer.  scratch: state_shift_scratch(...)."""
-    return _state_shift(torch.float32, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch)
-
-
-def state_shift_u8(img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion=None, scratch=None):
-    """state_shift for frames of bytes (fs_state_shift_u8): img (B,3,H,W) uint8; the key's uncovered border is filled with the frame's
-    byte.  Everything else as state_shift, and equal to it on img.float() / 255; the scratch is the same.  img is contiguous, or an hwc
-    view of interleaved bytes (byte_frame_layout; fs_state_shift_hwc); ValueError for any other layout."""
-    return _state_shift(torch.uint8, img, shift, key, key2, bits, bits2, gstate, stats, counts, prof_key, mstate, motion, scratch)
-
-
-def motion_commit(idx, prof, prof_key, mstate, frame_size):
-    """What a step leaves behind for the motion estimate (fs_motion_commit; no autograd; unpinned), in place, after gate_commit: for the
-    viewers of idx (int32 (n,) ascending, or None) prof_key (B, H + W) int32 <- prof, this step's frame_profiles, and mstate (B,4) int64
-    <- 0.  frame_size = (H, W)."""
-    H, W = int(frame_size[0]), int(frame_size[1])
-    if not isinstance(prof, torch.Tensor) or prof.dim() != 2 or prof.dtype != torch.int32 or prof.shape[1] != H + W or prof.shape[0] < 1:
-        raise ValueError(f"prof must be int32 (B, H + W) = (B, {H + W}), got {getattr(prof, 'dtype', None)} {tuple(getattr(prof, 'shape', ()))}")
-    B = int(prof.shape[0])
-    _profile_sizes(B, H, W)
-    n = 0 if idx is None else int(idx.shape[0])
-    if idx is not None and (idx.dtype != torch.int32 or idx.dim() != 1 or n > B):
-        raise ValueError(f"idx must be int32 (n,) with n <= {B}, got {idx.dtype} {tuple(idx.shape)}")
-    if prof_key.dtype != torch.int32 or prof_key.shape != prof.shape:
-        raise ValueError(f"prof_key must be int32 {tuple(prof.shape)}, got {prof_key.dtype} {tuple(prof_key.shape)}")
-    if mstate.dtype != torch.int64 or tuple(mstate.shape) != (B, 4):
-        raise ValueError(f"mstate must be int64 ({B}, 4), got {mstate.dtype} {tuple(mstate.shape)}")
-    if n:
-        hip.call("fs_motion_commit", hip.ptr(idx), n, hip.ptr(prof), hip.ptr(prof_key), hip.ptr(mstate), B, H, W)
-
-
-# ---- showing the record: the overlay pass (csrc/frame_overlay.hip) ----------------------------------------------------------------
-OVERLAY_STYLE_COLS = 20                             # ints a style row (include/fovealseg.h "showing the record")
-OVERLAY_MAX_PX = 16384                              # the kernel's cap on t, r, w and on a side
-
-
-def _overlay_colour(name, v):
-    if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) != 3:
-        raise ValueError(f"{name} must be three integers (r, g, b) in 0 .. 255, got {v!r}")
-    out = []
-    for c in v:
-        if isinstance(c, bool) or int(c) != c or not 0 <= int(c) <= 255:
-            raise ValueError(f"{name} must be three integers (r, g, b) in 0 .. 255, got {v!r}")
-        out.append(int(c))
-    return out
-
-
-def _overlay_int(name, v, hi):
-    if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= hi:
-        raise ValueError(f"{name} must be an integer 0 .. {hi}, got {v!r}")
-    return int(v)
-
-
-def _int_ge_zero(name, v):
-    if isinstance(v, bool) or int(v) != v or int(v) < 0:
-        raise ValueError(f"{name} must be an integer >= 0, got {v!r}")
-    return int(v)
-
-
-def overlay_style(tint=(0, 255, 0), alpha=128, outline=None, box=None, box_px=2, marker=None, marker_px=6, marker_width=None, dim=256,
-                  cat=None, palette=None, device=None):
-    """The style table of draw_instances / fs_frame_overlay: (S, 20) int32 on `device`, columns tint r g b, a, outline r g b, dim, box r g b,
-    t, marker r g b, r, w, the outline flag, two reserved.  tint, and outline / box / marker where given, are (r, g, b) integers 0 .. 255;
-    None switches the element off (its colour columns stay 0, and t, r or the flag 0).  alpha and dim are integers 0 .. 256: a mask pixel
-    becomes (s * (256 - alpha) + tint * alpha + 128) >> 8, any other (s * dim + 128) >> 8.  box_px = t, the box's line width inward;
-    marker_px = r, the gaze marker's radius, marker_width = w its ring width (None: a disc); all 0 .. 16384.  One row, for every viewer,
-    unless cat (B,) int64 and palette (K,3) uint8 are given: then S = B and viewer b's tint is palette[cat[b]] (the given tint for a class
-    outside the palette), looked up on cat's device without a host read.  ValueError for anything else."""
-    row = [0] * OVERLAY_STYLE_COLS
-    row[0:3] = _overlay_colour("tint", tint)
-    row[3] = _overlay_int("alpha", alpha, 256)
-    row[7] = _overlay_int("dim", dim, 256)
-    if outline is not None:
-        row[4:7] = _overlay_colour("outline", outline)
-        row[17] = 1
-    if box is not None:
-        row[8:11] = _overlay_colour("box", box)
-        row[11] = _overlay_int("box_px", box_px, OVERLAY_MAX_PX)
-    if marker is not None:
-        row[12:15] = _overlay_colour("marker", marker)
-        row[15] = _overlay_int("marker_px", marker_px, OVERLAY_MAX_PX)
-        row[16] = row[15] if marker_width is None else _overlay_int("marker_width", marker_width, OVERLAY_MAX_PX)
-    if (cat is None) != (palette is None):
-        raise ValueError("cat and palette go together: a tint a viewer by class needs both")
-    if cat is None:
-        return torch.tensor([row], dtype=torch.int32, device=device)
-    if not isinstance(cat, torch.Tensor) or cat.dim() != 1 or cat.dtype != torch.int64 or cat.numel() == 0:
-        raise ValueError(f"cat must be a non-empty int64 (B,), got {getattr(cat, 'dtype', None)} {tuple(getattr(cat, 'shape', ()))}")
-    pal = torch.as_tensor(palette)
-    if pal.dim() != 2 or pal.shape[1] != 3 or pal.shape[0] < 1 or pal.dtype != torch.uint8:
-        raise ValueError(f"palette must be uint8 (K, 3), got {pal.dtype} {tuple(pal.shape)}")
-    dev = cat.device if device is None else torch.device(device)
-    cat, pal = cat.to(dev), pal.to(dev)
-    K = int(pal.shape[0])
-    style = torch.tensor([row], dtype=torch.int32, device=dev).repeat(int(cat.shape[0]), 1)
-    inside = (cat >= 0) & (cat < K)
-    looked = pal[cat.clamp(0, K - 1)].to(torch.int32)
-    style[:, 0:3] = torch.where(inside[:, None], looked, style[:, 0:3])
-    return style
-
-
-def byte_frame_dest(out, shape=None):
-    """(ob, oy, ox) of a uint8 (B,3,H,W) tensor the overlay pass can write, from byte_frame_layout's rule: (3 * H * W, W, 1) for a
-    contiguous one; (sb, sy, sx) for a view of interleaved bytes (hwc.permute(0, 3, 1, 2) of a (B,H,W,3) buffer, rgba.permute(0, 3, 1,
-    2)[:, :3] of a (B,H,W,4) one whose fourth byte is then written as 255, padded rows, a crop).  ValueError for any other tensor, another
-    shape than `shape`, and one image expanded over several viewers (sb == 0 with B > 1: the viewers' pictures would overwrite each other)."""
-    layout = byte_frame_layout(out)
-    if layout is None or (shape is not None and tuple(out.shape) != tuple(shape)):
-        raise ValueError(f"out must be a uint8 {tuple(shape) if shape is not None else '(B,3,H,W)'}, contiguous or a view of interleaved (B,H,W,3) / "
-                         f"(B,H,W,4) bytes (ops.byte_frame_layout), got {getattr(out, 'dtype', None)} {tuple(getattr(out, 'shape', ()))} with "
-                         f"strides {tuple(out.stride()) if isinstance(out, torch.Tensor) else None}")
-    B, _, H, W = (int(v) for v in out.shape)
-    if layout[0] == "planar":
-        return 3 * H * W, W, 1
-    _, sb, sy, sx = layout
-    if B > 1 and sb == 0:
-        raise ValueError("out is one image expanded over several viewers: every viewer needs bytes of its own")
-    return sb, sy, sx
-
-
-def _dest_args(out, dest):
-    if not out.is_cuda:
-        raise hip.HipLibraryError("fovealseg kernels need device tensors (got a CPU tensor); there is no CPU path")
-    return (out.data_ptr(),) + tuple(dest)
-
-
-def overlay_band(bits, Ws, d, er=None, scratch=None, band=None):
-    """The outline band of draw_instances: bits & ~E_d(bits), E_d fs_mask_erode's, with no host read.  er, band (like bits) and scratch
-    (fs_mask_erode_scratch_ints int32) are made where not given; the bits at x >= Ws of the band are unspecified (the overlay pass reads
-    none of them).  Returns (band, er, scratch)."""
-    d = _morph_d(d)
-    B, Hs = int(bits.shape[0]), int(bits.shape[1])
-    if er is None:
-        er = torch.empty_like(bits, memory_format=torch.contiguous_format)
-    if band is None:
-        band = torch.empty_like(bits, memory_format=torch.contiguous_format)
-    if scratch is None:
-        scratch = torch.empty(max(1, hip.query("fs_mask_erode_scratch_ints", B, Hs, Ws, d)), device=bits.device, dtype=torch.int32)
-    hip.call("fs_mask_erode", hip.ptr(bits), hip.ptr(er), hip.ptr(scratch), B, Hs, Ws, d)
-    torch.bitwise_not(er, out=er)
-    torch.bitwise_and(bits, er, out=band)
-    return band, er, scratch
-
-
-def _live_arg(live, B, dev):
-    """(pointer, stride in elements) of the nullable live flags: an int64 (B,) tensor on the device, contiguous or a column of a matrix."""
-    if live is None:
-        return None, 1
-    if not isinstance(live, torch.Tensor) or live.dtype != torch.int64 or tuple(live.shape) != (B,) or live.device != dev:
-        raise ValueError(f"live must be int64 ({B},) on {dev}, got {getattr(live, 'dtype', None)} {tuple(getattr(live, 'shape', ()))}")
-    stride = int(live.stride(0)) if B > 1 else 1
-    if stride < 1:
-        raise ValueError(f"live must have a positive stride, got {stride}")
-    return live.data_ptr(), stride
-
-
-def draw_instances(img, bits, stats=None, focus=None, style=None, outline_px=0, out=None, live=None, band=None):
-    """The record drawn onto the frame, in one launch (fs_frame_overlay / _u8 / _hwc; no autograd; unpinned: the reference draws on the
-    host).  img (B,3,H,W) as the serving entry points take it, on the device: fp32 (its pixel code q(v) = rint(clamp(v, 0, 1) * 255) is what
-    is drawn on), contiguous uint8, or a uint8 view of interleaved bytes (byte_frame_layout), read where it lies; any other layout is
-    copied.  bits (B,H,ceil(W/32)) int32, the record's mask; stats (B,6) int64, the record's, for the box; focus (B,2), for the gaze
-    marker; a None switches its element off.  style: overlay_style's table, (1,20) or (B,20) int32 (None: its defaults).  outline_px = d >
-    0 makes the outline band bits & ~E_d(bits) first (fs_mask_erode; no host read) unless `band` brings it; the style's outline colour
-    shows it.  live: None, or int64 (B,) flags (a column of a matrix will do): where 0, the viewer's mask, outline and box count as empty.
-    out: a uint8 (B,3,H,W) tensor to write, contiguous or an interleaved view (byte_frame_dest: an RGBA view gets alpha 255); None: a new
-    contiguous one.  out may be img itself for a frame of bytes.  The rule per pixel, first that holds: marker, box, outline, tint, dim
-    (include/fovealseg.h).  Returns out."""
-    if not isinstance(img, _FRAME_TYPES) or img.dim() != 4 or img.shape[1] != 3 or img.numel() == 0 or img.dtype not in (torch.float32, torch.uint8):
-        raise ValueError(f"img must be a non-empty fp32 or uint8 (B,3,H,W), got {getattr(img, 'dtype', None)} {tuple(getattr(img, 'shape', ()))}")
-    B, _, H, W = (int(v) for v in img.shape)
-    if max(H, W) > OVERLAY_MAX_PX:
-        raise ValueError(f"a frame of {H} x {W} pixels has a side above {OVERLAY_MAX_PX}")
-    dev = img.device
-    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.int32 or tuple(bits.shape) != (B, H, (W + 31) // 32):
-        raise ValueError(f"bits must be int32 {(B, H, (W + 31) // 32)}, got {getattr(bits, 'dtype', None)} {tuple(getattr(bits, 'shape', ()))}")
-    if stats is not None and (stats.dtype != torch.int64 or tuple(stats.shape) != (B, 6)):
-        raise ValueError(f"stats must be int64 ({B}, 6), got {stats.dtype} {tuple(stats.shape)}")
-    if style is None:
-        style = overlay_style(device=dev)
-    if not isinstance(style, torch.Tensor) or style.dtype != torch.int32 or style.dim() != 2 or style.shape[1] != OVERLAY_STYLE_COLS or \
-            int(style.shape[0]) not in (1, B):
-        raise ValueError(f"style must be int32 (1, {OVERLAY_STYLE_COLS}) or ({B}, {OVERLAY_STYLE_COLS}) (ops.overlay_style), got "
-                         f"{getattr(style, 'dtype', None)} {tuple(getattr(style, 'shape', ()))}")
-    f = None if focus is None else _focus_arg(focus, B, dev)
-    live_ptr, live_stride = _live_arg(live, B, dev)
-    outline_px = _int_ge_zero("outline_px", outline_px)
-    if isinstance(img, Nv12Frame):
-        pass                                            # read where it lies
-    elif img.dtype == torch.uint8 and byte_frame_layout(img) is None or img.dtype == torch.float32 and not img.is_contiguous():
-        img = img.contiguous()
-    if out is None:
-        out = torch.empty(B, 3, H, W, device=dev, dtype=torch.uint8)
-    dest = byte_frame_dest(out, (B, 3, H, W))
-    bits = bits.contiguous()
-    if band is None and int(outline_px) > 0:
-        band = overlay_band(bits, W, int(outline_px))[0]
-    elif band is not None and (band.dtype != torch.int32 or band.shape != bits.shape):
-        raise ValueError(f"band must be int32 {tuple(bits.shape)}, got {band.dtype} {tuple(band.shape)}")
-    suffix, strides = _frame_route(img)
-    hip.call("fs_frame_overlay" + suffix, *_frame_args(img, strides), hip.ptr(bits), hip.ptr(band), hip.ptr(stats if stats is None else stats.contiguous()),
-             hip.ptr(f), live_ptr, live_stride, hip.ptr(style.contiguous()), int(style.shape[0]), *_dest_args(out, dest), B, H, W)
-    return out
-
-
-def color_encode(labels, palette, out=None):
-    """A class map as colours (fs_color_encode; utils.py:207-221 colorEncode, mode RGB, on the device): labels (B,H,W) or (H,W) int64,
-    predict()'s map; palette (K,3) uint8.  out (B,3,H,W) uint8 as draw_instances takes it (None: a new contiguous one) = palette[label],
-    (0, 0, 0) for a label < 0 or >= K -- the reference skips negative labels and would raise on one >= K.  Returns out."""
-    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64 or labels.dim() not in (2, 3) or labels.numel() == 0:
-        raise ValueError(f"labels must be a non-empty int64 (B,H,W) or (H,W), got {getattr(labels, 'dtype', None)} {tuple(getattr(labels, 'shape', ()))}")
-    if labels.dim() == 2:
-        labels = labels[None]
-    B, H, W = (int(v) for v in labels.shape)
-    if max(H, W) > OVERLAY_MAX_PX:
-        raise ValueError(f"a map of {H} x {W} pixels has a side above {OVERLAY_MAX_PX}")
-    pal = torch.as_tensor(palette)
-    if pal.dim() != 2 or pal.shape[1] != 3 or pal.shape[0] < 1 or pal.dtype != torch.uint8:
-        raise ValueError(f"palette must be uint8 (K, 3), got {pal.dtype} {tuple(pal.shape)}")
-    pal = pal.to(labels.device).contiguous()
-    if out is None:
-        out = torch.empty(B, 3, H, W, device=labels.device, dtype=torch.uint8)
-    dest = byte_frame_dest(out, (B, 3, H, W))
-    hip.call("fs_color_encode", hip.ptr(labels.contiguous()), hip.ptr(pal), *_dest_args(out, dest), B, H, W, int(pal.shape[0]))
-    return out
-
-
-def _hd_q(q):
-    if isinstance(q, bool) or int(q) != q or not 1 <= int(q) <= 100:
-        raise ValueError(f"the Hausdorff percentile must be an integer 1 .. 100, got {q!r}")
-    return int(q)
-
-
-def unwarp_count(cls, m, grid, y, cls_label, dia_factor=None, frame=True, areas=False, return_labels=False, hd_q=None):
-    """The checks, allocations and call that unwarp_accuracy, unwarp_trimap and unwarp_class_areas share; models.py's evaluate() calls
-    it directly.  Internal to the package: the documented ops are those three.  dia_factor=None: no trimap.  hd_q (None, or 1 .. 100):
-    the surface-distance statistics of surface_hd, prediction foreground (class != K-1) against label foreground.  The entry point is
-    the smallest that counts what is asked for: fs_unwarp_hd with hd_q, else fs_unwarp_class_areas with areas, else fs_unwarp_trimap
-    with a trimap, else fs_unwarp_accuracy.  Returns the six-tuple (counts, acc, areas, trim, labels, hd) in this order, None where not
-    asked for."""
-    with_trim = dia_factor is not None
-    D, fr = _trimap_args(dia_factor, frame) if with_trim else (0, 0)
-    q = _hd_q(hd_q) if hd_q is not None else None
-    B, K = cls.shape
-    _, h, w, _ = grid.shape
-    if tuple(m.shape) != (B, h, w):
-        raise ValueError(f"m {tuple(m.shape)} must be (B, h, w) = {(B, h, w)}: the mask at the grid's resolution")
-    if y.dim() == 4 and y.shape[1] == 1:
-        y = y[:, 0]
-    if y.dim() != 3 or y.shape[0] != B:
-        raise ValueError(f"y {tuple(y.shape)} must be (B, Hs, Ws) or (B, 1, Hs, Ws) with B = {B}")
-    Hs, Ws = int(y.shape[1]), int(y.shape[2])
-    if cls_label.dim() == 2 and cls_label.shape[1] == 1:
-        cls_label = cls_label[:, 0]
-    if tuple(cls_label.shape) != (B,):
-        raise ValueError(f"cls_label {tuple(cls_label.shape)} must be (B,) or (B, 1) with B = {B}")
-    dev = cls.device
-    counts = torch.empty(B, 6, device=dev, dtype=torch.int64)
-    acc = torch.empty(4, device=dev, dtype=torch.float32)
-    area = torch.empty(B, 3, K, 3, device=dev, dtype=torch.int64) if areas else None
-    trim = torch.empty(B, D + 1, 3, device=dev, dtype=torch.int64) if with_trim else None
-    labels = torch.empty(B, Hs, Ws, device=dev, dtype=torch.int64) if return_labels else None
-    hd = torch.empty(B, 4, device=dev, dtype=torch.int64) if q is not None else None
-    # (entry point, the dimensions its scratch query takes, its outputs after acc, its arguments after the dimensions)
-    if q is not None:
-        name, qdims, outs, tail = "fs_unwarp_hd", (B, K, h, w, Hs, Ws), (area, trim, labels, hd), (D, fr, q)
-    elif areas:
-        name, qdims, outs, tail = "fs_unwarp_class_areas", (B, K, h, w, Hs, Ws), (area, trim, labels), (D, fr)
-    elif with_trim:
-        name, qdims, outs, tail = "fs_unwarp_trimap", (B, h, w, Hs, Ws), (trim, labels), (D, fr)
-    else:
-        name, qdims, outs, tail = "fs_unwarp_accuracy", (B, h, w, Hs, Ws), (labels,), ()
-    scratch = torch.empty(hip.query(name + "_scratch_ints", *qdims), device=dev, dtype=torch.int32)
-    hip.call(name, hip.ptr(cls.contiguous()), hip.ptr(m.contiguous()), hip.ptr(grid.contiguous()), hip.ptr(y.float().contiguous()),
-             hip.ptr(cls_label.long().contiguous()), hip.ptr(counts), hip.ptr(acc), *(hip.ptr(t) for t in outs), hip.ptr(scratch),
-             B, K, h, w, Hs, Ws, *tail)
-    return counts, acc, area, trim, labels, hd
-
-
-def unwarp_accuracy(cls, m, grid, y, cls_label, return_labels=False):
-    """The four full-resolution accuracies of MODEL.upsample for the C1 head (no autograd), without the (B,K,Hs,Ws) prediction, a class
-    map or a ground-truth tensor: the predicted class of a pixel is `unwarp_labels`'s, its ground truth `t = y.long()`,
-    `t * cls_label + (1 - t) * (K - 1)`, and the gather pass counts instead of storing (fs_unwarp_accuracy).  cls (B,K), m (B,h,w),
-    grid (B,h,w,2) as for unwarp_labels; y (B,Hs,Ws) or (B,1,Hs,Ws) the label mask at the output size; cls_label (B,) or (B,1).
-    Returns (counts (B,6) int64 = cls_fg, bin_fg, union_fg, cls_bg, bin_bg, union_bg per image, acc (4,) fp32 = acc, acc_bin_fg,
-    acc_cls_fbg, acc_bin_fbg as SegLoss's out[3:7]) and, with return_labels, the (B,Hs,Ws) int64 class map of unwarp_labels."""
-    counts, acc, _, _, labels, _ = unwarp_count(cls, m, grid, y, cls_label, return_labels=return_labels)
-    return (counts, acc, labels) if return_labels else (counts, acc)
-
-
-def _trimap_args(dia_factor, frame):
-    D = int(dia_factor)
-    if not 0 <= D <= 7:
-        raise ValueError(f"dia_factor must be 0 .. 7 (band widths 1 .. 2**dia_factor), got {dia_factor}")
-    return D, 1 if frame else 0
-
-
-def trimap_bands(y, dia_factor=5, frame=True):
-    """Which trimap band every pixel of the label mask lies in (eval.py:41-67; VAL.trimap_dia_factor): uint8 (B,Hs,Ws), the smallest
-    i <= dia_factor such that the pixel is within 2**i city-block steps of the label's boundary, 255 if none, so that band i of the
-    reference (FIND_EDGES, then binary_dilation(iterations=2**i)) is `bands <= i` (fs_trimap_bands).  y (B,Hs,Ws) or (B,1,Hs,Ws), read
-    as t = y.long().  A boundary seed is a background pixel (t == 0) with a foreground 8-neighbour; frame=True also seeds every
-    background pixel of the outer one-pixel ring, as PIL's filter does -- the reference bit for bit -- and frame=False is the
-    neighbour rule alone, pixels outside the image being background.  No autograd."""
-    D, fr = _trimap_args(dia_factor, frame)
-    if y.dim() == 4 and y.shape[1] == 1:
-        y = y[:, 0]
-    if y.dim() != 3 or y.numel() == 0:
-        raise ValueError(f"y {tuple(y.shape)} must be a non-empty (B, Hs, Ws) or (B, 1, Hs, Ws)")
-    B, Hs, Ws = (int(v) for v in y.shape)
-    band = torch.empty(B, Hs, Ws, device=y.device, dtype=torch.uint8)
-    scratch = torch.empty(hip.query("fs_trimap_bands_scratch_ints", B, Hs, Ws), device=y.device, dtype=torch.int32)
-    hip.call("fs_trimap_bands", hip.ptr(y.float().contiguous()), hip.ptr(band), hip.ptr(scratch), B, Hs, Ws, D, fr)
-    return band
-
-
-def unwarp_trimap(cls, m, grid, y, cls_label, dia_factor=5, frame=True, return_labels=False):
-    """unwarp_accuracy with the trimap boundary accuracies of eval.py:41-67 counted in the same gather pass (fs_unwarp_trimap).
-    Arguments and checks are unwarp_accuracy's; dia_factor / frame are trimap_bands'.  Returns (counts, acc, trim[, labels]): counts,
-    acc and labels are unwarp_accuracy's bit for bit, trim (B, dia_factor + 1, 3) int64 holds per image and band width 2**i the number of
-    pixels in the band, of those whose predicted class equals the ground truth (the reference's acc_sum) and of those that agree with
-    it on foreground versus background.  An image without a boundary seed (a constant label with frame=False, an all-foreground one
-    with frame=True) has all-zero rows: the reference divides 0 by 0 there, trimap_from_counts and train.TrimapMeter leave it out."""
-    if dia_factor is None:
-        raise TypeError("unwarp_trimap needs dia_factor (0 .. 7); unwarp_accuracy is the op without a trimap")
-    counts, acc, _, trim, labels, _ = unwarp_count(cls, m, grid, y, cls_label, dia_factor, frame, return_labels=return_labels)
-    return (counts, acc, trim, labels) if return_labels else (counts, acc, trim)
-
-
-def trimap_from_counts(trim):
-    """(B, D+1, 3) trim counters (unwarp_trimap's, on any device) -> (B, D+1, 2) fp64: per image and band width the class accuracy
-    cls_ok / (total + 1e-10) -- the reference's Python-float quotient, eval.py:64 -- and the foreground / background accuracy
-    bin_ok / (total + 1e-10).  An empty band gives 0; `trim[..., 0] > 0` tells which images count (see unwarp_trimap)."""
-    if trim.dim() != 3 or trim.shape[2] != 3:
-        raise ValueError(f"trim must be (B, D+1, 3), got {tuple(trim.shape)}")
-    t = trim.to(torch.float64)
-    return t[..., 1:] / (t[..., :1] + 1e-10)
-
-
-def unwarp_class_areas(cls, m, grid, y, cls_label, dia_factor=None, frame=True, return_labels=False):
-    """unwarp_accuracy with the per-class areas of the reference's evaluation summary (eval.py:218-257,313-322; utils.intersectionAndUnion,
-    utils.py:289-317) counted in the same gather pass (fs_unwarp_class_areas).  Arguments and checks are unwarp_trimap's; dia_factor=None
-    leaves the trimap out.  Returns (counts, acc, areas[, trim][, labels]): counts, acc, trim and labels are unwarp_accuracy's /
-    unwarp_trimap's bit for bit; areas (B, 3, K, 3) int64 holds per image, space and class (inter, pred, lab), the union being
-    pred + lab - inter.  Space 0 is the prediction at full resolution (unwarp_labels against the ground truth), space 1 the sampling
-    ceiling -- the label after the sampler and the nearest un-warp against itself (VAL.y_sampled_reverse, models/models_instance.py:909-918):
-    every pixel takes grid_sample_label's value of the grid point that feeds it -- and space 2 the prediction in the sampled space
-    (PredAssemble(cls, m).argmax(1) against the sampled ground truth).  A cls_label outside 0 .. K-1 has no lab / inter row."""
-    counts, acc, areas, trim, labels, _ = unwarp_count(cls, m, grid, y, cls_label, dia_factor, frame, areas=True, return_labels=return_labels)
-    return (counts, acc, areas) + ((trim,) if trim is not None else ()) + ((labels,) if return_labels else ())
-
-
-def class_scores_from_areas(areas):
-    """(..., K, 3) class areas (unwarp_class_areas', on any device; summed over a dataset or not) -> (iou, dice), each (..., K) fp64:
-    iou = inter / (union + 1e-10) and dice = 2 * inter / (union + inter + 1e-10) with union = pred + lab - inter -- the reference's
-    expressions (eval.py:252, 313-315).  A class with an empty union scores 0."""
-    if areas.dim() < 2 or areas.shape[-1] != 3:
-        raise ValueError(f"areas must be (..., K, 3), got {tuple(areas.shape)}")
-    a = areas.to(torch.float64)
-    inter, union = a[..., 0], a[..., 1] + a[..., 2] - a[..., 0]
-    return inter / (union + 1e-10), 2 * inter / (union + inter + 1e-10)
-
-
-def surface_hd(a, b, q=95):
-    """The q-th percentile of the Hausdorff distances between the borders of two masks (HD95 at q = 95; VAL.hd95), as the integers it is
-    made of (fs_surface_hd; no autograd).  a, b (B,H,W) or (H,W), bool or uint8 (non-zero = foreground), on the device; H, W <= 16384.
-    The border of a mask is its foreground with a background 4-neighbour, outside the image counting as background; every border pixel
-    of either mask takes the squared distance to the nearest border pixel of the other, and the two sets are pooled.  Returns hd (B,4)
-    int64 = (n_a, n_b, d2_lo, d2_hi): the border sizes and the pooled squared distances at the two ranks np.percentile interpolates
-    between; d2 = -1 where a border is empty.  hd_from_stats makes the distance.  This is the published 2-D definition; the
-    reference's utils.hd95 flattens both masks before it erodes them and returns something else."""
-    q = _hd_q(q)
-    if a.dim() == 2 and b.dim() == 2:
-        a, b = a[None], b[None]
-    if a.dim() != 3 or a.shape != b.shape or a.numel() == 0:
-        raise ValueError(f"a {tuple(a.shape)} and b {tuple(b.shape)} must be two non-empty (B, H, W) masks of one shape")
-    if a.dtype not in (torch.bool, torch.uint8) or b.dtype not in (torch.bool, torch.uint8):
-        raise ValueError(f"masks must be bool or uint8, got {a.dtype} and {b.dtype}")
-    B, Hs, Ws = (int(v) for v in a.shape)
-    fg = ((a != 0).to(torch.uint8) | ((b != 0).to(torch.uint8) << 1)).contiguous()
-    hd = torch.empty(B, 4, device=a.device, dtype=torch.int64)
-    scratch = torch.empty(hip.query("fs_surface_hd_scratch_ints", B, Hs, Ws), device=a.device, dtype=torch.int32)
-    hip.call("fs_surface_hd", hip.ptr(fg), hip.ptr(hd), hip.ptr(scratch), B, Hs, Ws, q)
-    return hd
-
-
-def hd_from_stats(hd, q=95):
-    """(B,4) surface statistics (surface_hd's / evaluate(hausdorff=q)'s, on any device) -> (B,) fp64: np.percentile(distances, q) =
-    sqrt(d2_lo) + (sqrt(d2_hi) - sqrt(d2_lo)) * frac with frac = (q (n-1) mod 100) / 100, n = n_a + n_b; NaN where a border is empty
-    (the reference raises there).  q must be the q the statistics were made with.  Plain torch."""
-    q = _hd_q(q)
-    if hd.dim() != 2 or hd.shape[1] != 4:
-        raise ValueError(f"hd must be (B, 4), got {tuple(hd.shape)}")
-    hd = hd.to(torch.int64)
-    n = hd[:, 0] + hd[:, 1]
-    frac = ((q * (n - 1)) % 100).to(torch.float64) / 100.0
-    empty = (hd[:, 0] <= 0) | (hd[:, 1] <= 0) | (hd[:, 2] < 0)
-    lo, hi = hd[:, 2].clamp(min=0).to(torch.float64).sqrt(), hd[:, 3].clamp(min=0).to(torch.float64).sqrt()
-    out = lo + (hi - lo) * frac
-    return torch.where(empty, torch.full_like(out, float("nan")), out)
-
-
-def image_accuracies_from_counts(counts):
-    """(B,6) counts -> (B,4) fp32 per-image acc, acc_bin_fg, acc_cls_fbg, acc_bin_fbg (models/models.py:378-474): plain torch, any device."""
-    c = counts.to(torch.float32)
-    ufg, ubg = c[:, 2] + 1e-10, c[:, 5] + 1e-10
-    cls_fg, bin_fg, cls_bg, bin_bg = c[:, 0] / ufg, c[:, 1] / ufg, c[:, 3] / ubg, c[:, 4] / ubg
-    return torch.stack([cls_fg, bin_fg, cls_fg * 0.5 + cls_bg * 0.5, bin_fg * 0.5 + bin_bg * 0.5], 1)
-
-
-def accuracies_from_counts(counts):
-    """(B,6) counts (unwarp_accuracy's, on any device) -> (4,) fp32: the batch's four accuracies, the mean over its images of the fp32
-    per-image quotients -- fs_unwarp_accuracy's and SegLoss's arithmetic in plain torch."""
-    if counts.dim() != 2 or counts.shape[1] != 6:
-        raise ValueError(f"counts must be (B, 6), got {tuple(counts.shape)}")
-    return (image_accuracies_from_counts(counts).double().sum(0) / counts.shape[0]).float()
 
 
 # ----------------------------------------------------------------------------------------------

@@ -11,7 +11,7 @@ import math
 
 import torch
 
-from . import ops
+from . import frames, gaze, masks, ops, overlay
 
 OFF2 = 2 ** 62                                      # a squared distance no gaze reaches: the saccade rule switched off
 _DEFAULT = object()                                 # saccade_px not given (None means "off")
@@ -74,7 +74,7 @@ class GazeSession:
         self.H, self.W = _int_ge("frame height", frame_size[0], 1), _int_ge("frame width", frame_size[1], 1)
         if self.H * self.W >= 2 ** 31 or max(self.H, self.W) > 2 ** 26:
             raise ValueError(f"a frame of {self.H} x {self.W} pixels is beyond 32-bit pixel indices")
-        self.tile = ops._gate_tile(tile)
+        self.tile = gaze._gate_tile(tile)
         self.level = _int_ge("level", level, 0)
         if self.level > 254:
             raise ValueError(f"level must be an integer 0 .. 254, got {level!r}")
@@ -93,17 +93,17 @@ class GazeSession:
             self.saccade2 = px_to_thr2(0.10 * side if saccade_px is _DEFAULT else saccade_px)
         self.max_age = _int_ge("max_age", max_age, 0)
         self.inside_on = bool(reuse_inside_mask)
-        self.cap = ops._max_runs(max_runs, self.W)
+        self.cap = masks._max_runs(max_runs, self.W)
         self.max_runs = max_runs
         self.score = bool(score)
         if component is None:
             if snap_px is not None:
                 raise ValueError("snap_px goes with component = 4 or 8")
         else:
-            ops._component_args(component, snap_px)
+            masks._component_args(component, snap_px)
         self.component, self.snap_px = component, snap_px
-        self.motion_gain = ops._motion_gain(motion_gain)
-        self.motion_px = None if motion_px is None else ops._motion_px(motion_px, self.H, self.W)
+        self.motion_gain = gaze._motion_gain(motion_gain)
+        self.motion_px = None if motion_px is None else gaze._motion_px(motion_px, self.H, self.W)
         self.counts = {code: 0 for code in sorted(ops.GATE_CODES)}
         self._dev = None
 
@@ -168,11 +168,11 @@ class GazeSession:
             if style is None:
                 style = self._style = ops.overlay_style(device=self._dev)
         bits, band = self._rec[3], None
-        d = ops._int_ge_zero("outline_px", outline_px)
+        d = overlay._int_ge_zero("outline_px", outline_px)
         if d > 0:
             kept = getattr(self, "_band", None)
             if kept is None or kept[0] != d:
-                scratch = torch.empty(max(1, ops.hip.query("fs_mask_erode_scratch_ints", B, H, W, ops._morph_d(d))), device=self._dev, dtype=torch.int32)
+                scratch = torch.empty(max(1, ops.hip.query("fs_mask_erode_scratch_ints", B, H, W, masks._morph_d(d))), device=self._dev, dtype=torch.int32)
                 kept = self._band = (d, torch.empty_like(bits), torch.empty_like(bits), scratch)
             band = ops.overlay_band(bits, W, d, er=kept[2], scratch=kept[3], band=kept[1])[0]
         return ops.draw_instances(img, bits, stats=self._rec[1], focus=focus, style=style, out=out, live=self._gstate[:, 0], band=band)
@@ -224,8 +224,7 @@ class GazeSession:
         fdev = self._force(force, img.device)
         # a view of interleaved bytes (ops.byte_frame_layout: a camera's HWC / RGBA buffer, permuted) is read where it lies
         # and so is an NV12 frame (ops.Nv12Frame: a decoder's surface): the state stays planar RGB bytes
-        hwc = isinstance(img, ops.Nv12Frame) or (img.dtype == torch.uint8 and not img.is_contiguous() and ops.byte_frame_layout(img) is not None)
-        x = img if hwc else img.contiguous()
+        x, hwc = frames.frame_in_place(img)
         f = focus.float().contiguous()
         moving = self.motion_px is not None
         # a frame of bytes stays bytes: its pixel code is the byte, so its profiles are key_profiles of it and the gate compares bytes

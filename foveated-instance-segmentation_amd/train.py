@@ -608,8 +608,8 @@ class HausdorffMeter:
     empty-band images are."""
 
     def __init__(self, device, q=95):
-        from . import ops
-        self.q = ops._hd_q(q)
+        from . import unwarp
+        self.q = unwarp._hd_q(q)
         self.sums = torch.zeros(4, device=device, dtype=torch.float64)           # distance sum, images, empty pred, empty label
 
     def update(self, hd):
@@ -786,7 +786,7 @@ def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64, imag
     "iscrowd" is not interpreted: a crowd record is a candidate like any other.  No host read beyond the parse.  ValueError for
     gaze without images, an image of gt without a gaze, a gaze that is not two numbers, and records of one image that differ in size.
     With gaze=None every call, result and error is what it is without the argument, the "more than one record" error included."""
-    from . import ops
+    from . import masks, ops
     if isinstance(boundary, bool) or not isinstance(boundary, float) or not (boundary > 0.0) or math.isinf(boundary):
         raise ValueError(f"boundary must be a finite float > 0, got {boundary!r}")
     if isinstance(chunk, bool) or int(chunk) != chunk or int(chunk) < 1:
@@ -854,9 +854,7 @@ def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64, imag
                 raise ValueError(f"image {image_id!r}: the result's size {size_of(r, 'the result')} differs from the ground truth's "
                                  f"{size_of(many[image_id][0], 'the ground truth')}")
         for (H, W), ids in groups.items():
-            d = ops.boundary_dilation(H, W, boundary)
-            if d > ops.MORPH_MAX_D:
-                raise ValueError(f"boundary {boundary!r} gives a dilation of {d} pixels at {(H, W)}, above ops.MORPH_MAX_D = {ops.MORPH_MAX_D}")
+            masks.boundary_dilation_capped(H, W, boundary)
         for (H, W), ids in groups.items():
             d = ops.boundary_dilation(H, W, boundary)
             for at in range(0, len(ids), int(chunk)):
@@ -887,9 +885,7 @@ def score_coco_records(dt, gt, meter, boundary=0.02, device=None, chunk=64, imag
             raise ValueError(f"image {image_id!r}: the result's size {size_of(r, 'the result')} differs from the ground truth's "
                              f"{size_of(gts[image_id], 'the ground truth')}")
     for (H, W), ids in groups.items():
-        d = ops.boundary_dilation(H, W, boundary)
-        if d > ops.MORPH_MAX_D:
-            raise ValueError(f"boundary {boundary!r} gives a dilation of {d} pixels at {(H, W)}, above ops.MORPH_MAX_D = {ops.MORPH_MAX_D}")
+        d = masks.boundary_dilation_capped(H, W, boundary)
         for at in range(0, len(ids), int(chunk)):
             part = ids[at:at + int(chunk)]
             n = len(part)

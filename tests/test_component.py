@@ -147,8 +147,8 @@ def test_argument_checks_on_the_host():
                dict(snap_px=float("inf"))):
         with pytest.raises(ValueError):
             ops.mask_component(mask, focus, **kw)
-    assert ops._component_args(8, 1e200) == (8, 2 ** 62) and ops._component_args(8, 2.0 ** 31) == (8, 2 ** 62)      # finite, however large: no limit
-    assert ops._component_args(8, None) == (8, 2 ** 62) and ops._component_args(4, 2.999) == (4, 8) and ops._component_args(4, 0) == (4, 0)
+    assert fovealseg.masks._component_args(8, 1e200) == (8, 2 ** 62) and fovealseg.masks._component_args(8, 2.0 ** 31) == (8, 2 ** 62)      # finite, however large: no limit
+    assert fovealseg.masks._component_args(8, None) == (8, 2 ** 62) and fovealseg.masks._component_args(4, 2.999) == (4, 8) and fovealseg.masks._component_args(4, 0) == (4, 0)
     cls, m, grid = torch.zeros(1, 3), torch.zeros(1, 2, 2), torch.zeros(1, 2, 2, 2)
     for kw in (dict(component=3, focus=focus), dict(component=8, focus=focus, snap_px=-1), dict(snap_px=2.0), dict(focus=focus),
                dict(component=8), dict(component=8, focus=torch.zeros(2, 2))):

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import fovealseg
 from fovealseg import hip, ops
 from fovealseg import train as T
 from fovealseg.session import GazeSession
@@ -157,14 +158,14 @@ def test_frame_route_of_dtypes_and_stride_patterns():
     for name, t, want in table:
         if want is ValueError:
             with pytest.raises(ValueError):
-                ops._frame_route(t)
+                fovealseg.frames._frame_route(t)
             continue
-        assert ops._frame_route(t) == want, name
+        assert fovealseg.frames._frame_route(t) == want, name
         if t.dtype == torch.uint8:                                                         # the rule is byte_frame_layout's
             assert ops.byte_frame_layout(t) == (("planar",) if want[0] == "_u8" else ("hwc",) + want[1]), name
         with pytest.raises(hip.HipLibraryError):                                           # the device check stays at the call
-            ops._frame_args(t, want[1])
-    assert ops._PROFILE_ENTRY == {"": "fs_frame_profiles", "_u8": "fs_key_profiles", "_hwc": "fs_frame_profiles_hwc"}
+            fovealseg.frames._frame_args(t, want[1])
+    assert fovealseg.gaze._PROFILE_ENTRY == {"": "fs_frame_profiles", "_u8": "fs_key_profiles", "_hwc": "fs_frame_profiles_hwc"}
     for stem in ("fs_gate_tiles", "fs_gate_commit", "fs_state_shift"):
         assert all(stem + suffix in hip.SIGNATURES for suffix in ("", "_u8", "_hwc"))
     for stem in ("fs_gaze_lowres", "fs_grid_sample"):
@@ -542,7 +543,7 @@ def test_every_pass_agrees_across_the_five_layouts(H, W, T_):
     before = {k: v.clone() for k, v in bufs.items()}
     want_route = 1 if W % 16 == 0 else 0
     for name, want in (("rgb", want_route), ("rgba", want_route), ("pitch5 off1", 0)):     # each view runs the route it is there for
-        suffix, (sb, sy, sx) = ops._frame_route(frames[name])
+        suffix, (sb, sy, sx) = fovealseg.frames._frame_route(frames[name])
         assert suffix == "_hwc" and hip.load().fs_byte_frame_route(frames[name].data_ptr(), sb, sy, sx, W) == want, name
     by_dtype = lambda f32_op, u8_op, x: f32_op if x.dtype == torch.float32 else u8_op
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import fovealseg
 from fovealseg import hip, ops
 from fovealseg import train as T
 from fovealseg.session import GazeSession
@@ -319,16 +320,16 @@ def test_nv12_frame_refuses_before_any_launch():
 def test_frame_route_of_an_nv12_frame():
     B, H, W = 2, 6, 32
     f = ops.Nv12Frame(*_planes(B, H, W, 48, 64), matrix="bt709")
-    suffix, tail = ops._frame_route(f)
+    suffix, tail = fovealseg.frames._frame_route(f)
     assert suffix == "_nv12" and tail == (H * 48, 48, 3 * 64, 64) + N.TABLES[("bt709", False)]
     with pytest.raises(hip.HipLibraryError):                                               # the device check stays at the call
-        ops._frame_args(f, tail)
+        fovealseg.frames._frame_args(f, tail)
     for stem in ("fs_gate_tiles", "fs_gate_commit", "fs_state_shift", "fs_frame_overlay", "fs_frame_profiles"):
         assert stem + suffix in hip.SIGNATURES
     for stem in ("fs_gaze_lowres", "fs_grid_sample"):
         assert f"{stem}{suffix}_fwd" in hip.SIGNATURES
     # tensors go where they went
-    assert ops._frame_route(torch.zeros(B, 3, H, W)) == ("", ()) and ops._frame_route(torch.zeros(B, 3, H, W, dtype=torch.uint8)) == ("_u8", ())
+    assert fovealseg.frames._frame_route(torch.zeros(B, 3, H, W)) == ("", ()) and fovealseg.frames._frame_route(torch.zeros(B, 3, H, W, dtype=torch.uint8)) == ("_u8", ())
 
 
 def test_byte_frame_select_of_an_nv12_frame_gathers_the_planes():

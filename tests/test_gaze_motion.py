@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import fovealseg
 from fovealseg import hip, ops
 from fovealseg.session import GazeSession
 
@@ -176,9 +177,9 @@ def test_session_takes_the_motion_parameters():
     s = GazeSession(_Stub(), 2, (64, 80), motion_px=np.int64(3), motion_gain=0)
     assert (s.motion_px, s.motion_gain) == (3, 0)
     assert GazeSession(_Stub(), 2, (64, 80)).motion_px is None
-    assert ops._motion_px(255, 1024, 1100) == 255
+    assert fovealseg.gaze._motion_px(255, 1024, 1100) == 255
     with pytest.raises(ValueError):
-        ops._motion_px(255, 1024, 8000)                  # 8 * 8000 + 8 * 511 bytes of LDS
+        fovealseg.gaze._motion_px(255, 1024, 8000)                  # 8 * 8000 + 8 * 511 bytes of LDS
 
 
 def test_the_ctypes_table_binds_the_motion_entry_points():

@@ -246,7 +246,7 @@ def test_the_ctypes_table_binds_the_gate():
     assert sorted(ops.GATE_CODES) == list(range(8)) and ops.GATE_RUNS == R.RUNS and ops.GATE_CODES[2] == "HOLD_SACCADE"
     for bad in (12, 0, True, 7.5):
         with pytest.raises(ValueError):
-            ops._gate_tile(bad)
+            fovealseg.gaze._gate_tile(bad)
 
 
 # ---- the seeded viewers of the decide test -----------------------------------------------------------------------------------------

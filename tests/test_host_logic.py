@@ -652,3 +652,43 @@ def test_stash_grad_hands_the_second_reader_gradient_to_the_conv_consumer():
     assert torch.equal(run_without_conv_consumer(None), want)
     padded = ops.ConvProblem.of((2, 2, 2, 16), (1, 16, 1, 1), 1, 0)
     assert torch.equal(run_without_conv_consumer(padded), want)      # a consumer of a padded copy: other shape
+
+
+# ---- where the stateless ops live: frames / masks / gaze / overlay / unwarp beside ops (DESIGN.md "Where things live") ----------------
+_OP_MODULES = ("frames", "masks", "gaze", "overlay", "unwarp")
+
+
+@pytest.mark.parametrize("name", _OP_MODULES)
+def test_op_module_names_resolve_through_ops(name):
+    mod = getattr(fovealseg, name)
+    assert mod.__all__ and len(set(mod.__all__)) == len(mod.__all__)
+    for n in mod.__all__:
+        assert not n.startswith("_")
+        assert getattr(ops, n) is getattr(mod, n), n
+    # every public thing the module defines is in its __all__: nothing is reachable there and missing from ops
+    own = [n for n, v in vars(mod).items() if not n.startswith("_") and getattr(v, "__module__", mod.__name__) == mod.__name__
+           and not isinstance(v, type(os))]
+    assert sorted(n for n in own if n not in mod.__all__) == []
+
+
+@pytest.mark.parametrize("name", _OP_MODULES)
+def test_op_modules_do_not_import_ops(name):
+    mod = getattr(fovealseg, name)
+    assert "ops" not in vars(mod)
+    assert not any(v is ops for v in vars(mod).values())
+
+
+def test_frame_in_place():
+    B, H, W = 2, 4, 6
+    f32 = torch.rand(B, 3, H, W)
+    planar = torch.randint(0, 256, (B, 3, H, W), dtype=torch.uint8)
+    hwc = torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8).permute(0, 3, 1, 2)
+    sliced = torch.randint(0, 256, (B, 3, H, 2 * W), dtype=torch.uint8)[..., ::2]
+    nv12 = ops.Nv12Frame(torch.randint(0, 256, (B, H, W), dtype=torch.uint8), torch.randint(0, 256, (B, H // 2, W // 2, 2), dtype=torch.uint8),
+                         matrix="bt601")
+    assert ops.byte_frame_layout(hwc)[0] == "hwc" and ops.byte_frame_layout(sliced) is None and tuple(sliced.shape) == (B, 3, H, W)
+    for img, stays in ((f32, False), (planar, False), (hwc, True), (nv12, True)):
+        x, in_place = fovealseg.frames.frame_in_place(img)
+        assert x is img and in_place is stays
+    x, in_place = fovealseg.frames.frame_in_place(sliced)
+    assert x is not sliced and x.is_contiguous() and torch.equal(x, sliced) and in_place is False

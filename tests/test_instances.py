@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import fovealseg
 from fovealseg import hip, ops
 
 import rle_ref as R
@@ -114,10 +115,10 @@ def test_the_ctypes_table_binds_the_new_symbols():
 
 
 def test_max_runs_argument():
-    assert ops._max_runs(None, 1024) == 8 * 1024 + 1 and ops._max_runs(1, 1024) == 1 and ops._max_runs(77, 5) == 77
+    assert fovealseg.masks._max_runs(None, 1024) == 8 * 1024 + 1 and fovealseg.masks._max_runs(1, 1024) == 1 and fovealseg.masks._max_runs(77, 5) == 77
     for bad in (0, -3, 2.5, True):
         with pytest.raises(ValueError):
-            ops._max_runs(bad, 8)
+            fovealseg.masks._max_runs(bad, 8)
 
 
 # ------------------------------------------------------------------------------------------------------------------ GPU: C ABI ----
